@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- sequence-pairs/s of the all-pairs similarity hot path on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one full pass of similarityMH(k=4, n_hash=500) over the workload with the packed residues already
@@ -13,9 +13,14 @@ rank's compact block is exchanged with ONE RCCL all-gather and mirrored / widene
 rank (T_g); total work is fixed, so `scaling` is "strong".
 
 Headline workload (BASELINE.json configs[3], the one the metric is quoted on): 100 000 h3n2-like 20-mers, MinHash
-k=4 n_hash=500, hash seed 12345.  The same JSON line also carries
+k=4 n_hash=500, hash seed 12345.  A plain run sets up, warms up, times the --steps steps and prints the JSON line; besides the
+headline figures it carries what the timed steps themselves yield:
+    phases_ms     the library's HIP-event phase times of the timed steps, and the route they took
     roofline      the dominant kernel of the timed step: algorithmic bytes / HIP-event duration vs the 8 TB/s HBM peak
                   (k_expand_rows when the duplicate-collapsing route runs, with K2 on the unique rows beside it; K2 + its VALU bound otherwise)
+--dump-outputs DIR writes a fixed, seeded sample of the matrix the last timed step left in HBM (see dump_outputs).
+Everything else runs with --full only, after the headline steps (the --no-* options drop single legs of it):
+    one_stream    the pipelined duplicate route with its compare and expansion one after the other (roofline.frac_one_stream)
     direct        the same input with the route off (K2 on all N rows) and K2's roofline object
     nw            similarityNW BLOSUM62/10/4 on the same set (second half of the metric) with its own roofline object
     uniform       the other SURVEY 8(d) workload, S100k uniform (16 code planes instead of 12: k_mh_compare_a16)
@@ -23,6 +28,7 @@ k=4 n_hash=500, hash seed 12345.  The same JSON line also carries
     edges         similarityMH + clusterbreak's quantile threshold as an edge list
     clusterbreak  BASELINE configs[4]: clusterbreak(size_max=800, thresh_p=.8) end to end on the device edge path
     cpu_baseline  the CPU oracle timed on this box's host cores (rank 0, N=1 only) and speedups on the T_h boundary
+    N > 1 only: verified_against_single_gpu (the sharded matrix against a single-GPU call) and replicas_no_collective
 """
 import argparse
 import json
@@ -48,6 +54,10 @@ def parse():
     ap.add_argument("--n", type=int, default=int(os.environ.get("DYNAALIGN_BENCH_N", "100000")),
                     help="number of peptides (default: the 100k headline set; DYNAALIGN_BENCH_N sets it where a launcher eats --n)")
     ap.add_argument("--workload", default="h3n2like", choices=["h3n2like", "uniform"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of the last timed step's matrix to DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps, also run every secondary measurement (other routes and workloads, similarityNW, "
+                         "edges, clusterbreak, host boundary, CPU baseline, the N > 1 self-check); the --no-* options drop single legs")
     ap.add_argument("--no-nw", action="store_true", help="skip the similarityNW measurement")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle baseline")
     ap.add_argument("--no-edges", action="store_true", help="skip the threshold + edge-list measurement")
@@ -169,6 +179,32 @@ def pmc_traffic(kernel, n):
             return {"bytes": None, "source": src + " -- STALE: the running sources are %s, traffic not reported" % cur}
         return {"bytes": (k["WRITE_SIZE"] + 2.0 * k["FETCH_SIZE"]) * 1024.0, "source": src}
     return None
+
+
+DUMP_SEED = 20240517
+DUMP_ROW_BYTES = 24 << 20
+DUMP_ELEMENTS = 4 << 20
+
+
+def dump_positions(n):
+    """the sampled positions of an N x N matrix: row indices (ascending) and flat element indices (row * N + column, in draw order)"""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(n, size=max(1, min(n, DUMP_ROW_BYTES // (8 * n))), replace=False))
+    return rows, rng.integers(0, n * n, size=DUMP_ELEMENTS, dtype=np.int64)
+
+
+def dump_outputs(out, path):
+    """What a caller of the timed path receives, the dense float64 N x N matrix, sampled to at most 56 MiB:
+        mh_rows.npy      whole rows (as many as fit in 24 MiB, at least one) at seeded row indices
+        mh_elements.npy  4 Mi single elements at seeded positions
+    The positions (dump_positions) depend on N only, so runs with the same arguments can be compared value for value."""
+    import numpy as np
+    import torch
+    rows, flat = dump_positions(out.shape[0])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "mh_rows.npy"), out[torch.from_numpy(rows).to(out.device)].cpu().numpy())
+    np.save(os.path.join(path, "mh_elements.npy"), out.view(-1)[torch.from_numpy(flat).to(out.device)].cpu().numpy())
 
 
 def free_port():
@@ -440,6 +476,8 @@ def main():
         return max_over_ranks(time.perf_counter() - t0), evs
 
     dt, evs = timed_steps(step, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out, a.dump_outputs)
     def phase_means(evs):
         if world == 1:
             return {nm: float(np.mean([e[nm] for e in evs])) for nm in phase_names}
@@ -570,7 +608,7 @@ def main():
             main_roof["note"] += ("; PIPELINED: %d chunk launches per step (mean size reported per launch; frac = bytes of all launches / the time some launch was "
                                   "running), co-running with the compare of the unique table (phases_ms.k2_ms = its span on the side stream: the first bands at "
                                   "full occupancy, then one persistent workgroup per CU)%s: they overlap; "
-                                  "`one_stream` below is the same input with DYNAALIGN_MH_NO_PIPE=1 (each kernel alone)"
+                                  "`one_stream` (--full) is the same input with DYNAALIGN_MH_NO_PIPE=1 (each kernel alone)"
                                   % (el, "" if rows_form else " and the column gathers (phases_ms.gather_ms = sum of the launches incl. their wait for LDS)"))
         else:
             main_roof["k2_on_unique"] = k2_roofline(phases["k2_ms"], state["bits"], route["unique"], 2)
@@ -601,7 +639,7 @@ def main():
                          "expansion": route.get("expansion", ""), "chunks": route.get("chunks", 0), "sparse": route.get("sparse", False), "plane_bits": route["plane_bits"],
                          "note": "dedup: byte-identical sequences collapsed (exact) -- K1 / K1b / K2 on the unique strings, then the index expansion to "
                                  "the dense N x N (rows: k_expand_stream, one pass; tiles: column gather + k_expand_rows); direct: the three kernels on all N rows"}
-        if route.get("pipelined"):
+        if a.full and route.get("pipelined"):
             os.environ["DYNAALIGN_MH_NO_PIPE"] = "1"             # the same route with the table finished before the expansion starts: every kernel alone
             try:
                 odt, oevs = timed_steps(step, max(2, min(a.steps, 3)), 1)
@@ -617,7 +655,7 @@ def main():
             line["one_stream"] = {"ms_per_step": odt / osteps * 1e3, "value": pairs_mh / (odt / osteps), "unit": "pairs/s", "steps": osteps,
                                   "phases_ms": oph, "roofline": oroof,
                                   "note": "DYNAALIGN_MH_NO_PIPE=1: K2 on the unique strings, then the expansion, one after the other on one stream"}
-        if route["dedup"]:
+        if a.full and route["dedup"]:
             os.environ["DYNAALIGN_MH_NO_DEDUP"] = "1"            # the same input with the routes off: K2 on all N rows
             os.environ["DYNAALIGN_MH_NO_SPARSE"] = "1"
             try:
@@ -660,7 +698,8 @@ def main():
         return None if int(hi.item()) == 2 else bool(lo.item())
 
     if world > 1:
-        line["verified_against_single_gpu"] = same_as_single_gpu(lambda ref: device.similarity_mh(ds, k, n_hash, d_seeds, out=ref))
+        if a.full:
+            line["verified_against_single_gpu"] = same_as_single_gpu(lambda ref: device.similarity_mh(ds, k, n_hash, d_seeds, out=ref))
         line["rccl"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                         "all_gather_bytes_per_rank": int(state["block_bytes"]), "all_gather_ms": phases["all_gather"],
                         "finalize_ms": phases["shards_to_table"] + phases["expand"] if state["dedup"] else phases["finalize"]}
@@ -677,18 +716,19 @@ def main():
         line["route"] = {"n": n, "unique": state["unique"], "dedup": state["dedup"],
                          "note": "dedup: every rank builds the same duplicate plan, the ranks shard the count table of the unique strings "
                                  "(one all-gather of (U/n)^2 of the bytes) and expand it locally; direct: the n x n pair space is sharded"}
-        # beside the sharded step: every rank computing the whole matrix by itself (the single-GPU call, no collective).  The dense result is
-        # replicated on every rank either way, so when the compare is cheap next to the N x N stores (duplicates collapsed: 5 of 17 ms) sharding
-        # it cannot pay for its all-gather -- this leg says by how much.  Not `value`: the north-star's N > 1 configuration is the sharded one.
-        rsteps = max(2, min(a.steps, 3))
-        rdt, revs = timed_steps(lambda: (device.similarity_mh(ds, k, n_hash, d_seeds, out=out), device.mh_last_route())[1], rsteps, 1)
-        line["replicas_no_collective"] = {"ms_per_step": rdt / rsteps * 1e3, "value": pairs_mh / (rdt / rsteps), "unit": "pairs/s", "steps": rsteps,
-                                          "route": {k_: revs[-1][k_] for k_ in ("dedup", "pipelined", "expansion", "unique", "plane_bits")},
-                                          "note": "each rank runs da_dev_similarity_mh on the whole set (same result on every rank, no exchange); "
-                                                  "barrier-bracketed, max over ranks"}
+        if a.full:
+            # beside the sharded step: every rank computing the whole matrix by itself (the single-GPU call, no collective).  The dense result is
+            # replicated on every rank either way, so when the compare is cheap next to the N x N stores (duplicates collapsed: 5 of 17 ms) sharding
+            # it cannot pay for its all-gather -- this leg says by how much.  Not `value`: the north-star's N > 1 configuration is the sharded one.
+            rsteps = max(2, min(a.steps, 3))
+            rdt, revs = timed_steps(lambda: (device.similarity_mh(ds, k, n_hash, d_seeds, out=out), device.mh_last_route())[1], rsteps, 1)
+            line["replicas_no_collective"] = {"ms_per_step": rdt / rsteps * 1e3, "value": pairs_mh / (rdt / rsteps), "unit": "pairs/s", "steps": rsteps,
+                                              "route": {k_: revs[-1][k_] for k_ in ("dedup", "pipelined", "expansion", "unique", "plane_bits")},
+                                              "note": "each rank runs da_dev_similarity_mh on the whole set (same result on every rank, no exchange); "
+                                                      "barrier-bracketed, max over ranks"}
 
     # ---- similarityNW on the same set (second half of the metric), >= 3 timed launches
-    if not a.no_nw:
+    if a.full and not a.no_nw:
         bad = device.nw_encode(ds)
         assert int(bad.item()) == 0
         if world == 1:
@@ -752,7 +792,7 @@ def main():
     # ---- similarityMH + clusterbreak's quantile threshold as an edge list:
     # shard compare -> histogram -> ONE all-reduce of n_hash+1 words -> exact type-7 quantile -> local edges.
     # No N x N exchange, so this is the variant of the path whose whole-job time scales with the rank count.
-    if not a.no_edges:
+    if a.full and not a.no_edges:
         if world == 1:
             # one GPU: nothing to shard -- symmetric uint16 compare, histogram of the upper triangle, exact quantile, edges
             cnt16 = out.view(-1).view(torch.int16)[:n * n].view(n, n)          # the f64 result buffer is free here: reuse its first 20 GB
@@ -812,7 +852,7 @@ def main():
         del ei, ej, evv
 
     # ---- the other SURVEY 8(d) workload: S100k uniform.  Its column dictionaries are larger (D ~ 15 000 -> 16 code planes)
-    if world == 1 and not a.no_uniform and a.workload == "h3n2like":
+    if a.full and world == 1 and not a.no_uniform and a.workload == "h3n2like":
         ures, uoff = synth.uniform_peptides(n, L)
         uds = device.DeviceSequences(ures, uoff, "cuda")
         usteps = max(2, min(a.steps, 3))
@@ -841,7 +881,7 @@ def main():
 
     # ---- BASELINE configs[4]: clusterbreak(size_max=800, thresh_p=.8) end to end, GPU similarityMH backend on the
     # device edge path (signatures resident; per recursion level codes + compare + histogram + quantile + edges), host Louvain
-    if world == 1 and not a.no_clusterbreak:
+    if a.full and world == 1 and not a.no_clusterbreak:
         from dynaalign_amd.session import MinHashSession
         out = cnt16 = None                  # the 80 GB result buffer is not needed any more (closures above are done)
         torch.cuda.empty_cache()
@@ -880,7 +920,7 @@ def main():
 
     # ---- T_h: the host-pointer boundary (what R sees): da_similarity_mh / da_similarity_nw into a pageable host matrix,
     # upload + kernels + pipelined D2H.  PCIe-bound; never `value`.
-    if world == 1 and not a.no_host:
+    if a.full and world == 1 and not a.no_host:
         import psutil
         out = cnt16 = None
         torch.cuda.empty_cache()
@@ -928,7 +968,7 @@ def main():
         del hout
 
     # ---- CPU oracle on this box's host cores (baseline only; rank 0, N = 1)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         cb = cpu_baseline(gen_name, a.cpu_seconds)
         line["cpu_baseline"] = cb
         sp = {"boundary": "T_h (whole call, result in host memory) on both sides where t_h was measured, else T_k / whole-call CPU",

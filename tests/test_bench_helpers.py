@@ -60,3 +60,22 @@ def test_committed_pmc_profile_matches_the_committed_sources():
         import pytest
         pytest.skip("%s was measured on other kernel sources (%s, tree %s): bench.py will print traffic null until tools/prof_pmc.sh is re-run"
                     % (newest, d.get("source_hash"), source_hash.source_hash()))
+
+
+def test_dump_outputs_writes_a_fixed_float64_sample_of_the_matrix(tmp_path):
+    """--dump-outputs: whole rows and single elements of the N x N matrix at positions that depend on N only, float64, within
+    64 MB at the headline N"""
+    import numpy as np
+    import torch
+    import bench
+    rows, flat = bench.dump_positions(100000)
+    assert (len(rows) * 100000 + len(flat)) * 8 <= 64e6 and len(rows) >= 1 and len(set(rows.tolist())) == len(rows)
+    n = 700
+    M = torch.arange(n * n, dtype=torch.float64).reshape(n, n)
+    bench.dump_outputs(M, str(tmp_path / "a"))
+    bench.dump_outputs(M.clone(), str(tmp_path / "b"))
+    rows, flat = bench.dump_positions(n)
+    want = {"mh_rows": M.numpy()[rows], "mh_elements": M.numpy().reshape(-1)[flat]}
+    for name, w in want.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, w) and np.array_equal(b, w)
