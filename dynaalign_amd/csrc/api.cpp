@@ -126,10 +126,12 @@ struct DevBuf {
   void *p = nullptr;
   size_t cap = 0;
   int dev = 0;
-  ~DevBuf() {
+  ~DevBuf() { release(); }
+  void release() {   // back to the cache (or freed) now
     if (!p) return;
     if (cap >= BigCache::MIN_BYTES && !da::config().no_buffer_cache) big_cache().park(dev, p, cap);
     else (void)hipFree(p);
+    p = nullptr;
   }
   int alloc(size_t bytes) {
     if (bytes == 0) bytes = 16;
@@ -391,6 +393,7 @@ namespace {
 bool env_flag(const char *name) { return getenv(name) != nullptr; }
 int64_t env_i64(const char *name, int64_t dflt) { const char *e = getenv(name); return e ? atoll(e) : dflt; }
 uint64_t env_u64(const char *name, uint64_t dflt) { const char *e = getenv(name); return e ? strtoull(e, nullptr, 10) : dflt; }
+enum MhExpand { MH_EXPAND_DEFAULT, MH_EXPAND_ROWS, MH_EXPAND_ROWSPIPE, MH_EXPAND_PIPE, MH_EXPAND_TILES };   // Config::mh_expand
 Config parse_config() {
   Config c;
   c.mh_no_dedup = env_flag("DYNAALIGN_MH_NO_DEDUP");
@@ -404,7 +407,8 @@ Config parse_config() {
   c.mh_hybrid_min_n = env_i64("DYNAALIGN_MH_HYBRID_MIN_N", -1);
   c.mh_hybrid_dedup = env_flag("DYNAALIGN_MH_HYBRID_DEDUP");
   if (const char *e = getenv("DYNAALIGN_MH_EXPAND"))
-    c.mh_expand = !strcmp(e, "rows") ? 1 : !strcmp(e, "rowspipe") ? 2 : !strcmp(e, "pipe") ? 3 : !strcmp(e, "tiles") ? 4 : 0;
+    c.mh_expand = !strcmp(e, "rows") ? MH_EXPAND_ROWS : !strcmp(e, "rowspipe") ? MH_EXPAND_ROWSPIPE : !strcmp(e, "pipe") ? MH_EXPAND_PIPE
+                : !strcmp(e, "tiles") ? MH_EXPAND_TILES : MH_EXPAND_DEFAULT;
   c.mh_pipe_step = (int)std::max<int64_t>(0, env_i64("DYNAALIGN_MH_PIPE_STEP", 0));
   c.mh_pipe_wg = (int)std::max<int64_t>(0, std::min<int64_t>(4, env_i64("DYNAALIGN_MH_PIPE_WG", 0)));
   c.mh_pipe_head = (int)std::max<int64_t>(0, env_i64("DYNAALIGN_MH_PIPE_HEAD", 0));
@@ -533,85 +537,37 @@ int da_dev_minhash_signatures(const uint8_t *d_residues, const int64_t *d_offset
 }
 
 // signatures -> compare operand: dictionary codes (16 planes / group) when n allows, raw values otherwise
-static int env_plane_bits() {   // DYNAALIGN_PLANE_BITS: 32 = raw planes, 12 / 16 = at least that many code planes
-  return da::config().plane_bits;
+static int env_plane_bits() { return da::config().plane_bits; }   // DYNAALIGN_PLANE_BITS: 32 = raw planes, 12 / 16 = at least that many code planes
+// Step 1: the column dictionaries (launch_mh_dictionary), read back -- run when n allows and codes are wanted (min_bits != 32).  ok: every column's
+// values got codes; max_ids: the largest column's repeated values; bits_data: the code planes they need.  Synchronises `stream`.
+struct Dictionary { bool ok = false; int max_ids = 0, bits_data = 32; int *d_status = nullptr; };
+static int run_dictionary(const uint32_t *d_sig, int64_t ld_sig, int64_t n, int n_hash, int min_bits, void *d_work, size_t work_bytes,
+                          Dictionary *dict, hipStream_t stream) {
+  if (n > DA_DICT_MAX_N || min_bits == 32) return DA_OK;
+  if (!d_work || work_bytes < mh_planes_workspace_bytes(n, n_hash))
+    return fail(DA_ERR_BAD_ARG, "workspace smaller than da_mh_planes_workspace_bytes(n, n_hash)");
+  int rc;
+  if ((rc = launch_mh_dictionary(d_sig, ld_sig, n, n_hash, d_work, &dict->d_status, stream)) != DA_OK) return rc;
+  int status[2] = {0, 0};
+  DA_HIP_TRY(hipMemcpyAsync(status, dict->d_status, sizeof(status), hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  dict->ok = status[0] == 0; dict->max_ids = status[1];
+  dict->bits_data = dict->ok ? mh_plane_bits_for(status[1]) : 32;
+  return DA_OK;
 }
-// The sparse route (minhash_kernels.hip "SPARSE route"): the caller of build_planes asks for it by passing a SparseHint; when the
-// dictionary says the signatures rarely agree (few matching incidences, no large class) build_planes returns with take = true and
-// WITHOUT building the bit planes -- the caller then runs launch_mh_sparse on the dictionary codes in the workspace.
-struct SparseHint { bool take = false; int max_ids = 0; uint64_t pairs = 0, max_mult = 0; };
-// The heavy / rare split (dict_kernels.hip k_hy_split): asked for the same way; when the dictionaries need 12 - 16 code planes but all except a few
-// matching incidences sit on each column's 254 most frequent values, build_planes returns EIGHT planes of dense codes for those (take = true,
-// *bits_out = 8) and leaves the codes of the rare repeated values in the workspace (sparse_codes): the caller runs launch_mh_sparse_lists on them
-// and, after the dense compare, launch_mh_sparse_fixup.
-constexpr int HY_KEEP = 254;
-struct HybridHint { int only_from_bits = 12; bool take = false; int max_ids = 0, bits_before = 0; uint64_t pairs = 0, max_mult = 0; const uint16_t *sparse_codes = nullptr; int64_t ld_ids = 0; };
+// Step 2: codes -> planes (at least min_bits of them) when the dictionary gave codes, raw signature bits otherwise
+static int planes_from(const Dictionary &dict, const uint32_t *d_sig, int64_t ld_sig, int64_t n, int n_hash, int min_bits, const void *d_work,
+                       uint32_t *d_planes, int *bits_out, hipStream_t stream) {
+  *bits_out = dict.ok ? std::max(dict.bits_data, min_bits) : 32;
+  return dict.ok ? launch_ids_to_planes(d_work, n, n_hash, *bits_out, d_planes, stream) : launch_sig_to_planes(d_sig, ld_sig, n, n_hash, d_planes, stream);
+}
 // min_bits: 0 = as few code planes as the data needs, 12 / 16 = at least that many, 32 = raw planes
 static int build_planes(const uint32_t *d_sig, int64_t ld_sig, int64_t n, int n_hash, int min_bits, void *d_work,
-                        size_t work_bytes, uint32_t *d_planes, int *bits_out, hipStream_t stream, SparseHint *sparse = nullptr,
-                        HybridHint *hybrid = nullptr) {
-  int rc;
-  const int env = env_plane_bits();
-  if (env > min_bits) min_bits = env;
-  if (n <= DA_DICT_MAX_N && min_bits != 32) {
-    if (!d_work || work_bytes < mh_planes_workspace_bytes(n, n_hash))
-      return fail(DA_ERR_BAD_ARG, "workspace smaller than da_mh_planes_workspace_bytes(n, n_hash)");
-    int *d_status = nullptr;
-    if ((rc = launch_mh_dictionary(d_sig, ld_sig, n, n_hash, d_work, &d_status, stream)) != DA_OK) return rc;
-    int status[2] = {0, 0};
-    DA_HIP_TRY(hipMemcpyAsync(status, d_status, sizeof(status), hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    int bits_data = status[0] == 0 ? mh_plane_bits_for(status[1]) : 32;
-    int64_t hy_min_n = 16384;                                       // below that the compare is too short to pay for the list kernels
-    if (da::config().mh_hybrid_min_n >= 0) hy_min_n = da::config().mh_hybrid_min_n;   // DYNAALIGN_MH_HYBRID_MIN_N (tests lower it)
-    const bool sparse_ok = sparse && status[0] == 0 && status[1] >= 1 && status[1] <= 32768 && min_bits == 0 && n >= 2048 && n_hash + 1 <= 2048 &&
-                           !da::config().mh_no_sparse;
-    const bool hybrid_ok = hybrid && status[0] == 0 && bits_data >= hybrid->only_from_bits && bits_data <= 16 && min_bits == 0 && status[1] <= 32768 && n >= hy_min_n && n <= 131072 &&
-                           n_hash > 32 && n_hash + 1 <= 2048 && !da::config().mh_no_hybrid && !da::config().k2_no_asm;
-    if (sparse_ok || hybrid_ok) {
-      // how many (pair, hash function) incidences match, and how large is the largest class -- over all repeated values (sparse route) and over the values
-      // outside each column's HY_KEEP most frequent ones (heavy / rare split)?  One kernel, one more read-back (~0.15 ms)
-      int64_t ld_ids = 0;
-      const uint16_t *ids = mh_dictionary_codes(d_work, n, n_hash, &ld_ids);
-      unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(d_status + 4);     // behind the two status words (the workspace ends 256 bytes later)
-      const uint16_t *dense = nullptr, *rare = nullptr;
-      unsigned long long st[4] = {0, 0, 0, 0};                        // rare incidences, largest rare class, all incidences, largest class
-      if (hybrid_ok) {
-        if ((rc = launch_mh_heavy_split(d_work, n, n_hash, status[1], HY_KEEP, &dense, &rare, d_stats, stream)) != DA_OK) return rc;
-        DA_HIP_TRY(hipMemcpyAsync(st, d_stats, sizeof(st), hipMemcpyDeviceToHost, stream));
-      } else {
-        if ((rc = launch_mh_sparse_count(ids, ld_ids, n, n_hash, status[1], d_stats, stream)) != DA_OK) return rc;
-        DA_HIP_TRY(hipMemcpyAsync(st + 2, d_stats, 16, hipMemcpyDeviceToHost, stream));
-      }
-      DA_HIP_TRY(hipStreamSynchronize(stream));
-      const double pairs_all = 0.5 * (double)n * (double)(n - 1);
-      if (sparse_ok) {
-        sparse->pairs = st[2]; sparse->max_mult = st[3]; sparse->max_ids = status[1];
-        // admission: the bucket phase costs ~37 ps per incidence (5.1 ms for 1.37e8) and the tile pass ~2.5 ps per pair, the dense compare ~6.3 ps
-        // per pair at n_hash = 500 -- so the route pays while the average number of matches per pair stays below ~0.1 (x n_hash / 500);
-        // plus a memory cap on the bucket and a cap on the class size (a thread walks its class)
-        if (st[2] <= mh_sparse_pairs_limit() && st[3] <= 4096 && (double)st[2] <= pairs_all * (double)n_hash / 5000.0) {
-          sparse->take = true; *bits_out = 0; return DA_OK;
-        }
-      }
-      // heavy / rare split: four to eight planes less = 30 - 47 % of the compare's plane work (~2 ps per pair and 4 planes at n_hash = 500), against
-      // ~37 ps per rare incidence in the list kernels + ~1 ms of fixed cost: taken while the rare values match in < 0.02 of the pairs (x n_hash / 500)
-      if (hybrid_ok && st[0] <= mh_sparse_pairs_limit() && st[1] <= 4096 && (double)st[0] <= pairs_all * (double)n_hash / 25000.0) {
-        hybrid->take = true; hybrid->max_ids = status[1]; hybrid->bits_before = bits_data; hybrid->pairs = st[0]; hybrid->max_mult = st[1];
-        hybrid->sparse_codes = rare; hybrid->ld_ids = ld_ids;
-        *bits_out = 8;
-        return launch_ids_to_planes(d_work, n, n_hash, 8, d_planes, stream, dense);
-      }
-    }
-    if (status[0] == 0) {
-      int bits = bits_data;
-      if (bits < min_bits) bits = min_bits;
-      *bits_out = bits;
-      return launch_ids_to_planes(d_work, n, n_hash, bits, d_planes, stream);
-    }
-  }
-  *bits_out = 32;
-  return launch_sig_to_planes(d_sig, ld_sig, n, n_hash, d_planes, stream);
+                        size_t work_bytes, uint32_t *d_planes, int *bits_out, hipStream_t stream) {
+  min_bits = std::max(min_bits, env_plane_bits());
+  Dictionary dict;
+  const int rc = run_dictionary(d_sig, ld_sig, n, n_hash, min_bits, d_work, work_bytes, &dict, stream);
+  return rc != DA_OK ? rc : planes_from(dict, d_sig, ld_sig, n, n_hash, min_bits, d_work, d_planes, bits_out, stream);
 }
 
 size_t da_mh_planes_workspace_bytes(int64_t n, int n_hash) { return mh_planes_workspace_bytes(n, n_hash); }
@@ -662,6 +618,7 @@ int da_dev_mh_compare(const uint32_t *d_planes, int plane_bits, int64_t n, int n
 // otherwise (uniform peptides: nothing to collapse), or when the expansion's fast passes do not cover the shape
 // (U > 65536, n_hash > 2047, n < 2048), the direct kernels run.  Synchronises `stream` (K1b reads the dictionary sizes back).
 // DYNAALIGN_MH_NO_DEDUP=1 switches the route off.
+namespace {
 // side stream + events of the pipelined form, pooled per device (creating them costs more than the route's small kernels)
 struct PipeRes { hipStream_t side = nullptr, alt[2] = {nullptr, nullptr}; std::vector<hipEvent_t> ev; int dev = 0; };
 struct PipePool { std::mutex m; std::vector<PipeRes *> idle[64]; };
@@ -689,338 +646,388 @@ static PipeRes *pipe_acquire(size_t events) {
   if (r->ev.size() < events) { std::lock_guard<std::mutex> g(pipe_pool().m); pipe_pool().idle[dev & 63].push_back(r); return nullptr; }
   return r;
 }
-static void pipe_release(PipeRes *r) {
-  if (!r) return;
-  std::lock_guard<std::mutex> g(pipe_pool().m);
-  pipe_pool().idle[r->dev & 63].push_back(r);
+// a PipeRes held by one form (r: nullptr if none wanted / to be had); drains its streams, so declare it after the buffers they use
+struct PipeLease {
+  PipeRes *const r;
+  explicit PipeLease(size_t events, bool want = true) : r(want ? pipe_acquire(events) : nullptr) {}
+  ~PipeLease() {
+    if (!r) return;
+    (void)hipStreamSynchronize(r->side); (void)hipStreamSynchronize(r->alt[0]); (void)hipStreamSynchronize(r->alt[1]);
+    std::lock_guard<std::mutex> g(pipe_pool().m);
+    pipe_pool().idle[r->dev & 63].push_back(r);
+  }
+};
+// the unique strings of a plan laid out by nw_dedup_layout: launch_nw_dedup_count, *U = M + S read back (synchronises `stream`)
+static int count_unique(const uint8_t *d_bytes, const int64_t *d_offsets, int64_t n, const NwDedupPlan &p, hipStream_t stream, int64_t *U) {
+  int rc;
+  if ((rc = launch_nw_dedup_count(d_bytes, d_offsets, n, p, stream)) != DA_OK) return rc;
+  int32_t M = 0, S = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&M, p.pm + n, 4, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(&S, p.ps + n, 4, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  *U = (int64_t)M + S; return DA_OK;
 }
-struct MhRoute { int64_t n = 0, unique = 0, hybrid_pairs = -1; int taken = 0, plane_bits = 0, chunks = 0, expand_launches = 0, hybrid_bits_before = 0; float ms[6] = {0, 0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, column gather, k_expand_rows, diagonal / border tiles
+enum MhForm { MH_DIRECT = 0, MH_TILES = 1, MH_SPARSE = 2, MH_TILES_PIPE = 3, MH_ROWS = 4, MH_ROWS_PIPE = 5 };   // da_mh_last_route's `taken`
+struct MhRoute { int64_t n = 0, unique = 0, hybrid_pairs = -1; int taken = MH_DIRECT, plane_bits = 0, chunks = 0, expand_launches = 0, hybrid_bits_before = 0; float ms[6] = {0, 0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, column gather, k_expand_rows, diagonal / border tiles
 static MhRoute &mh_route() { static thread_local MhRoute r; return r; }
+// the seven events of one call: [0] call, [1] plan done, [2] compare operand done, [3 ..] the form's own
+struct MhEvents {
+  hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~MhEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  hipEvent_t operator[](int i) const { return e[i]; }
+  static void ms(MhRoute &r, int i, hipEvent_t from, hipEvent_t to) { (void)hipEventElapsedTime(&r.ms[i], from, to); }
+  void steps(MhRoute &r, int count) const { for (int i = 0; i < count; ++i) ms(r, i, e[i], e[i + 1]); }   // ms[i] = e[i] -> e[i + 1]
+};
+// ms[4] of the pipelined forms: the time some expansion launch was running -- the launches (in order) overlap on the alternating streams, so
+// the union of their [begin, end) intervals, not the sum
+struct LaunchUnion {
+  hipEvent_t origin; float total = 0, covered_to = 0;
+  void add(hipEvent_t begin, hipEvent_t end) {
+    float b = 0, e = 0;
+    (void)hipEventElapsedTime(&b, origin, begin); (void)hipEventElapsedTime(&e, origin, end);
+    if (e > covered_to) { total += e - std::max(b, covered_to); covered_to = e; }
+  }
+};
+// The duplicate plan: U unique strings; when collapsed (`take`), ids by first occurrence, the expansion family (`rows`: k_expand_stream, else tiles)
+// and for the tiles ub[b] = unique ids the input rows [0, 1024 b) use (the plan's prefix counts at band boundaries): the tile pipeline's schedule
+struct MhDedup { int64_t U = 0; bool take = false, rows = false; DevBuf work; NwDedupPlan p{}; std::vector<int32_t> ub; };
+static int mh_dedup_plan(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t total, int n_hash, const double *d_out, int64_t ld,
+                         MhDedup *d, hipStream_t stream) {
+  const Config &cfg = da::config();
+  int rc;
+  d->U = n;
+  const int64_t min_n = cfg.mh_dedup_min_n >= 0 ? cfg.mh_dedup_min_n : 2048;   // DYNAALIGN_MH_DEDUP_MIN_N: tests lower it to reach the route with small inputs
+  if (n < min_n || n > 0x7ffffff0LL || total <= 0 || n_hash > 2047 || cfg.mh_no_dedup) return DA_OK;
+  if ((rc = d->work.alloc(nw_dedup_workspace_bytes(n, total))) != DA_OK) return rc;
+  d->p = nw_dedup_layout(d->work.p, n, total);
+  if ((rc = count_unique(d_res, d_off, n, d->p, stream, &d->U)) != DA_OK) return rc;
+  const int64_t U = d->U;
+  // K2 on U rows + column gather + expansion (0.5 + 1.6 f + 22 f^2 + 4.1 f + 14.4 ms at N = 100k, f = U / n) against K1 + K1b + K2 with its
+  // own float64 stores (27.2 ms): the route pays below f = 0.63
+  // ... with the tile expansion.  With the row expansion (no gather, no copy of the table) the route costs ~1.5 + 26 f^2 + 14 ms one kernel after the
+  // other: 24.4 ms at f = 0.60, 26.6 at f = 0.65 against 27 (12 code planes) - 30 ms (14) for the direct kernels (profiles/r03_q_dedup_threshold.txt): 0.68
+  const int64_t max_pct = cfg.mh_dedup_max_pct >= 0 ? cfg.mh_dedup_max_pct                             // DYNAALIGN_MH_DEDUP_MAX_PCT
+                        : expand_stream_ok(n, std::min<int64_t>(U, 65536), n_hash, d_out, ld) ? 68 : 60;
+  d->take = U > 0 && U * 100 <= n * max_pct && expand_rows_workspace_bytes(n, U, DA_OUT_F64, false, n_hash, 0) != 0;
+  if (!d->take) return DA_OK;
+  if ((rc = launch_nw_dedup_build(d_res, d_off, n, U, d->p, stream, true)) != DA_OK) return rc;   // ids by first occurrence
+  d->rows = cfg.mh_expand <= MH_EXPAND_ROWSPIPE && expand_stream_ok(n, U, n_hash, d_out, ld);
+  if (d->rows) return DA_OK;
+  const int64_t NB = mh_sym_bands(n);
+  std::vector<int32_t> b((size_t)NB);
+  d->ub.resize((size_t)NB + 1);
+  DA_HIP_TRY(hipMemcpy2DAsync(d->ub.data(), 4, d->p.pm, 4096, 4, (size_t)NB, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpy2DAsync(b.data(), 4, d->p.ps, 4096, 4, (size_t)NB, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  for (int64_t q = 0; q < NB; ++q) d->ub[(size_t)q] += b[(size_t)q];
+  d->ub[(size_t)NB] = (int32_t)U;
+  return DA_OK;
+}
+// Admission of the two ways around comparing every code plane.  Sparse (minhash_kernels.hip "SPARSE route"): the signatures rarely agree --
+// no planes, the matching incidences are enumerated from the dictionary codes.  Split (dict_kernels.hip k_hy_split): 12 - 16 code planes, but all
+// except a few matching incidences sit on each column's HY_KEEP most frequent values -- EIGHT planes of dense codes for those, and the rare
+// values' codes go to launch_mh_sparse_lists and, after the dense compare, launch_mh_sparse_fixup.
+constexpr int HY_KEEP = 254;
+enum class MhOperand { dense, sparse, split };
+// pairs: matching (sparse) / rare (split) incidences; codes: what the list kernels read (all / the rare codes); dense: the split's dense codes
+struct MhAdmission { MhOperand form = MhOperand::dense; uint64_t pairs = 0; const uint16_t *codes = nullptr, *dense = nullptr; int64_t ld_ids = 0; };
+static int mh_admit(const Dictionary &dict, void *d_work, int64_t n, int n_hash, bool ask_sparse, int split_from_bits, MhAdmission *a,
+                    hipStream_t stream) {
+  const Config &cfg = da::config();
+  if (!dict.ok || env_plane_bits() != 0) return DA_OK;              // both need codes, and no more planes than the data needs
+  // below n = 16384 the compare is too short to pay for the list kernels (DYNAALIGN_MH_HYBRID_MIN_N: tests lower it)
+  const int64_t hy_min_n = cfg.mh_hybrid_min_n >= 0 ? cfg.mh_hybrid_min_n : 16384;
+  const bool sparse_ok = ask_sparse && dict.max_ids >= 1 && dict.max_ids <= 32768 && n >= 2048 && n_hash + 1 <= 2048 && !cfg.mh_no_sparse;
+  const bool split_ok = dict.bits_data >= split_from_bits && dict.bits_data <= 16 && dict.max_ids <= 32768 && n >= hy_min_n && n <= 131072 &&
+                        n_hash > 32 && n_hash + 1 <= 2048 && !cfg.mh_no_hybrid && !cfg.k2_no_asm;
+  if (!sparse_ok && !split_ok) return DA_OK;
+  // how many (pair, hash function) incidences match, and how large is the largest class -- over all repeated values (sparse route) and over the values
+  // outside each column's HY_KEEP most frequent ones (heavy / rare split)?
+  int rc;
+  int64_t ld_ids = 0;
+  const uint16_t *ids = mh_dictionary_codes(d_work, n, n_hash, &ld_ids);
+  unsigned long long *d_stats = reinterpret_cast<unsigned long long *>(dict.d_status + 4);     // behind the two status words (the workspace ends 256 bytes later)
+  const uint16_t *dense = nullptr, *rare = nullptr;
+  unsigned long long st[4] = {0, 0, 0, 0};                          // rare incidences, largest rare class, all incidences, largest class
+  if ((rc = split_ok ? launch_mh_heavy_split(d_work, n, n_hash, dict.max_ids, HY_KEEP, &dense, &rare, d_stats, stream)
+                     : launch_mh_sparse_count(ids, ld_ids, n, n_hash, dict.max_ids, d_stats, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpyAsync(split_ok ? st : st + 2, d_stats, split_ok ? sizeof(st) : 16, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  const double pairs_all = 0.5 * (double)n * (double)(n - 1);
+  // sparse: the bucket phase costs ~37 ps per incidence (5.1 ms for 1.37e8) and the tile pass ~2.5 ps per pair, the dense compare ~6.3 ps
+  // per pair at n_hash = 500 -- so the route pays while the average number of matches per pair stays below ~0.1 (x n_hash / 500);
+  // plus a memory cap on the bucket and a cap on the class size (a thread walks its class)
+  if (sparse_ok && st[2] <= mh_sparse_pairs_limit() && st[3] <= 4096 && (double)st[2] <= pairs_all * (double)n_hash / 5000.0)
+    *a = MhAdmission{MhOperand::sparse, st[2], ids, nullptr, ld_ids};
+  // split: four to eight planes less = 30 - 47 % of the compare's plane work (~2 ps per pair and 4 planes at n_hash = 500), against
+  // ~37 ps per rare incidence in the list kernels + ~1 ms of fixed cost: taken while the rare values match in < 0.02 of the pairs (x n_hash / 500)
+  else if (split_ok && st[0] <= mh_sparse_pairs_limit() && st[1] <= 4096 && (double)st[0] <= pairs_all * (double)n_hash / 25000.0)
+    *a = MhAdmission{MhOperand::split, st[0], rare, dense, ld_ids};
+  return DA_OK;
+}
+// The compare operand for `m` rows (K1 + K1b and the admission above) and the list kernels' scratch of the sparse route and the split
+struct MhCodes {
+  DevBuf sig, planes, pwork, scratch, entries32, entries;
+  int64_t m = 0;
+  int n_hash = 0, bits = 32;   // the planes built (0: none, the sparse route)
+  Dictionary dict;
+  MhAdmission adm;
+  bool split() const { return adm.form == MhOperand::split; }
+  // lists of the rare values' incidences (tile by tile) and, after a compare, their addition to its result (tile rows [tr0, tr1), all by default)
+  int lists(hipStream_t st) const {
+    return launch_mh_sparse_lists(adm.codes, adm.ld_ids, m, n_hash, dict.max_ids, adm.pairs, scratch.as<uint32_t>(), entries32.as<uint32_t>(), entries.as<uint16_t>(), st);
+  }
+  int fixup(int kind, void *out, int64_t ld_out, hipStream_t st, int64_t tr0 = 0, int64_t tr1 = -1) const {
+    return launch_mh_sparse_fixup(scratch.as<uint32_t>(), entries.as<uint16_t>(), m, n_hash, dict.max_ids, adm.ld_ids, kind, out, ld_out, tr0,
+                                  tr1 < 0 ? (m + 127) / 128 : tr1, st);
+  }
+};
+static int mh_codes(const uint8_t *d_res, const int64_t *d_off, int64_t m, int k, int n_hash, const uint32_t *d_seeds, bool ask_sparse,
+                    int split_from_bits, MhCodes *c, hipStream_t stream) {
+  int rc;
+  const int64_t lds = sig_ld_for(n_hash);
+  const size_t wb = mh_planes_workspace_bytes(m, n_hash);
+  c->m = m; c->n_hash = n_hash;
+  if ((rc = c->sig.alloc((size_t)m * lds * sizeof(uint32_t))) != DA_OK || (rc = c->planes.alloc((size_t)mh_planes_words(m, n_hash) * sizeof(uint32_t))) != DA_OK ||
+      (rc = c->pwork.alloc(wb)) != DA_OK) return rc;
+  uint32_t *sig = c->sig.as<uint32_t>(), *planes = c->planes.as<uint32_t>();
+  if ((rc = launch_minhash_signatures(d_res, d_off, m, k, n_hash, d_seeds, sig, lds, stream)) != DA_OK) return rc;
+  const int min_bits = env_plane_bits();
+  const Dictionary &dict = c->dict;
+  if ((rc = run_dictionary(sig, lds, m, n_hash, min_bits, c->pwork.p, wb, &c->dict, stream)) != DA_OK) return rc;
+  if ((rc = mh_admit(dict, c->pwork.p, m, n_hash, ask_sparse, split_from_bits, &c->adm, stream)) != DA_OK) return rc;
+  // Both forms are optimisations: when the lists' scratch does not fit, what did allocate goes back and the dense planes are built instead.
+  // Those are the planes of a full build_planes -- the dictionary's codes at bits_data: both forms are admitted only when DYNAALIGN_PLANE_BITS
+  // leaves min_bits == 0, and k_hy_split writes its codes to the sort scratch (w.sz / w.si), so the dictionary's codes (idsT) in pwork are intact.
+  if (c->adm.form != MhOperand::dense &&
+      (c->scratch.alloc(mh_sparse_scratch_words(m, n_hash, dict.max_ids, c->adm.ld_ids) * 4) != DA_OK ||
+       c->entries32.alloc((size_t)c->adm.pairs * 4 + 16) != DA_OK || c->entries.alloc((size_t)c->adm.pairs * 2 + 16) != DA_OK)) {
+    (void)hipGetLastError();
+    c->scratch.release(); c->entries32.release(); c->entries.release();
+    c->adm = MhAdmission();
+  }
+  if (c->adm.form == MhOperand::sparse) { c->bits = 0; return DA_OK; }
+  if (c->split()) { c->bits = 8; return launch_ids_to_planes(c->pwork.p, m, n_hash, 8, planes, stream, c->adm.dense); }
+  return planes_from(dict, sig, lds, m, n_hash, min_bits, c->pwork.p, planes, &c->bits, stream);
+}
+// what the forms share; duplicate route: the U x U count table (ld_d) and the expansion's scratch (copy lists / column-gathered table)
+struct MhCall {
+  int64_t n; int n_hash; double *out; int64_t ld; hipStream_t stream; MhRoute &route; const MhEvents &ev; const MhCodes &c; const MhDedup &d;
+  uint16_t *dtab = nullptr; int64_t ld_d = 0; void *ex = nullptr;
+};
+constexpr int MH_NO_PIPE = -1;   // a pipelined form's return when no side stream / events are to be had: the one-stream form needs none
+// the end of every form: its last event on the caller's stream, the sync after which the buffers may go back to the cache, the route report
+static int mh_finish(const MhCall &k, int last_event, MhForm taken, int steps) {
+  DA_HIP_TRY(hipEventRecord(k.ev[last_event], k.stream));
+  DA_HIP_TRY(hipStreamSynchronize(k.stream));
+  k.route.taken = taken; k.ev.steps(k.route, steps);
+  return DA_OK;
+}
+// SPARSE route: the matching incidences are enumerated from the dictionary codes, bucketed per output tile and every tile written once (exact;
+// minhash_kernels.hip).  ms[2] = link + walk + scan (buckets), ms[4] = the tile pass.
+static int mh_sparse(const MhCall &k) {
+  const MhCodes &c = k.c;
+  int rc;
+  if ((rc = launch_mh_sparse(c.adm.codes, c.adm.ld_ids, k.n, k.n_hash, c.dict.max_ids, c.adm.pairs, c.scratch.as<uint32_t>(), c.entries32.as<uint32_t>(),
+                             c.entries.as<uint16_t>(), k.out, k.ld, k.stream, k.ev[3])) != DA_OK || (rc = mh_finish(k, 4, MH_SPARSE, 3)) != DA_OK) return rc;
+  k.route.unique = (int64_t)c.adm.pairs;                            // (reported as `sparse_pairs` by the Python wrapper)
+  MhEvents::ms(k.route, 4, k.ev[3], k.ev[4]);
+  return DA_OK;
+}
+// the direct kernels on all n rows; the split's list kernels (latency-bound, ~0.9 ms at 100k) run on a side stream beside the dense compare,
+// without a side stream before it
+static int mh_direct(const MhCall &k) {
+  const MhCodes &c = k.c;
+  int rc;
+  const PipeLease lease(1, c.split());
+  PipeRes *const pr = lease.r;
+  if (pr) {
+    DA_HIP_TRY(hipStreamWaitEvent(pr->side, k.ev[2], 0));
+    if ((rc = c.lists(pr->side)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(pr->ev[0], pr->side));
+  } else if (c.split() && (rc = c.lists(k.stream)) != DA_OK) return rc;
+  if ((rc = launch_mh_compare(c.planes.as<uint32_t>(), k.n, k.n_hash, 0, k.n, true, DA_OUT_F64, k.out, k.ld, k.stream, c.bits)) != DA_OK) return rc;
+  if (pr) DA_HIP_TRY(hipStreamWaitEvent(k.stream, pr->ev[0], 0));
+  if (c.split() && (rc = c.fixup(DA_OUT_F64, k.out, k.ld, k.stream)) != DA_OK) return rc;
+  return mh_finish(k, 3, MH_DIRECT, 3);
+}
+// The one-stream duplicate forms: K2 on the U unique rows into the count table (+ the split's lists and fix-up), then the expansion --
+//   rows    k_expand_stream: every output row written once from its table row in LDS (no gathered copy); ms[3] = the copy lists (positions
+//           of every id, work items), ms[4] = k_expand_stream
+//   tiles   column gather (k_gather_columns), tile expansion (k_expand_rows) + diagonal / border tiles, one after the other
+static int mh_one_stream(const MhCall &k) {
+  const MhCodes &c = k.c;
+  int rc;
+  if (c.split() && (rc = c.lists(k.stream)) != DA_OK) return rc;
+  if ((rc = launch_mh_compare(c.planes.as<uint32_t>(), k.d.U, k.n_hash, 0, k.d.U, true, DA_OUT_COMPACT, k.dtab, k.ld_d, k.stream, c.bits)) != DA_OK) return rc;
+  if (c.split() && (rc = c.fixup(DA_OUT_COMPACT, k.dtab, k.ld_d, k.stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipEventRecord(k.ev[3], k.stream));
+  if ((rc = k.d.rows ? launch_expand_stream(k.dtab, k.ld_d, k.d.p.uidx, k.n, k.d.U, k.n_hash, k.out, k.ld, k.ex, k.stream, k.ev[4])
+                     : launch_expand_unique(k.dtab, k.ld_d, k.d.p.uidx, k.n, DA_OUT_F64, false, k.n_hash, k.out, k.ld, k.stream, 0,
+                                            static_cast<uint16_t *>(k.ex), k.d.p.ufirst, k.d.U, k.ev[4], k.ev[5])) != DA_OK) return rc;
+  k.route.chunks = k.route.expand_launches = 1;
+  return k.d.rows ? mh_finish(k, 5, MH_ROWS, 5) : mh_finish(k, 6, MH_TILES, 6);
+}
+// rowspipe: the row expansion PIPELINED with K2 -- the first `head` bands of the table at full occupancy, the rest by the persistent kernel with
+// `wg` workgroup(s) per CU on a side stream (one 36 KB ring fits beside the expansion's 94 KB row) while the finished table rows are expanded
+static int mh_rows_pipe(const MhCall &k) {
+  const Config &cfg = da::config();
+  const MhCodes &c = k.c;
+  const int64_t U = k.d.U, KB = mh_sym_bands(U);
+  const hipStream_t stream = k.stream;
+  int rc;
+  // K2 rings (36 KB, 128 VGPRs x 4 waves) that fit beside one expansion workgroup: two when its LDS row is packed (n_hash <= 511), else one --
+  // and a slower K2 wants a head start and smaller chunks (profiles/r03_m_pipeline_rows_*.txt: head x step sweeps for both)
+  const bool two = expand_stream_packed(k.n_hash);
+  const int wg = cfg.mh_pipe_wg > 0 ? cfg.mh_pipe_wg : two ? 2 : 1, head = cfg.mh_pipe_head > 0 ? cfg.mh_pipe_head : two ? 1 : 4,
+            step = cfg.mh_pipe_step > 0 ? cfg.mh_pipe_step : two ? 8 : 4;
+  const bool alt = !cfg.mh_pipe_one_stream;   // DYNAALIGN_MH_PIPE_STEP / _WG / _HEAD / _ONE_STREAM: schedule experiments
+  std::vector<int64_t> cuts{0};
+  while (cuts.back() < KB) cuts.push_back(std::min(KB, cuts.back() + (cuts.size() == 1 ? head : step)));
+  const size_t C = cuts.size() - 1;
+  const PipeLease lease(3 * C + 2);
+  PipeRes *const pr = lease.r;
+  if (!pr) return MH_NO_PIPE;
+  hipEvent_t *pe = pr->ev.data();                                  // per chunk: table rows done, rows begin / end; [3 C]: lists done
+  // beside the first band on the side stream: the table's diagonal / border tiles and the copy lists, both on the caller's stream
+  DA_HIP_TRY(hipStreamWaitEvent(pr->side, k.ev[2], 0));
+  if ((rc = launch_mh_compare_edges_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, stream, c.bits)) != DA_OK) return rc;
+  if ((rc = launch_expand_stream_lists(k.d.p.uidx, k.n, U, k.ex, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipEventRecord(pe[3 * C], stream));
+  if (c.split()) {     // the rare values' lists behind them on the caller's stream (on the idle expansion stream instead: 17.3 vs 16.6 ms, round 4)
+    if ((rc = c.lists(stream)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(pe[3 * C + 1], stream));
+  }
+  if (alt) { DA_HIP_TRY(hipStreamWaitEvent(pr->alt[0], pe[3 * C], 0)); DA_HIP_TRY(hipStreamWaitEvent(pr->alt[1], pe[3 * C], 0)); }
+  for (size_t ci = 0; ci < C; ++ci) {
+    if ((rc = launch_mh_compare_bands_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, cuts[ci], cuts[ci + 1], ci == 0 ? 4 : wg, pr->side, c.bits)) != DA_OK) return rc;
+    if (c.split()) {     // the rare values' incidences of these tile rows (direct + mirrored elements), once the edge tiles and the lists are there
+      if (ci == 0) { DA_HIP_TRY(hipStreamWaitEvent(pr->side, pe[3 * C], 0)); DA_HIP_TRY(hipStreamWaitEvent(pr->side, pe[3 * C + 1], 0)); }
+      if ((rc = c.fixup(DA_OUT_COMPACT, k.dtab, k.ld_d, pr->side, cuts[ci] * 8, cuts[ci + 1] * 8)) != DA_OK) return rc;
+    }
+    DA_HIP_TRY(hipEventRecord(pe[3 * ci], pr->side));
+    const hipStream_t es = alt ? pr->alt[ci & 1] : stream;
+    DA_HIP_TRY(hipStreamWaitEvent(es, pe[3 * ci], 0));
+    DA_HIP_TRY(hipEventRecord(pe[3 * ci + 1], es));
+    if ((rc = launch_expand_stream_rows(k.dtab, k.ld_d, k.d.p.uidx, k.n, U, k.n_hash, k.out, k.ld, k.ex, cuts[ci] * 1024, cuts[ci + 1] * 1024, es,
+                                        (int)ci)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(pe[3 * ci + 2], es));
+  }
+  if (alt) for (size_t ci = (C >= 2 ? C - 2 : 0); ci < C; ++ci) DA_HIP_TRY(hipStreamWaitEvent(stream, pe[3 * ci + 2], 0));
+  if ((rc = mh_finish(k, 5, MH_ROWS_PIPE, 2)) != DA_OK) return rc;
+  k.route.chunks = k.route.expand_launches = (int)C;
+  MhEvents::ms(k.route, 2, k.ev[2], pe[3 * (C - 1)]);             // the compare's span on the side stream
+  MhEvents::ms(k.route, 3, k.ev[2], pe[3 * C]);                   // the copy lists (beside the compare)
+  LaunchUnion expand{k.ev[2]};
+  for (size_t ci = 0; ci < C; ++ci) expand.add(pe[3 * ci + 1], pe[3 * ci + 2]);
+  k.route.ms[4] = expand.total;
+  return DA_OK;
+}
+// pipe: the PIPELINED tile form.  The table is compared band by band (1024 unique rows each, in order) by the persistent kernel
+// on a side stream with only `wg` workgroups per CU, so the rest of every CU stays free; the output row bands whose strings are all numbered below
+// the finished table rows are gathered (on `stream`) and expanded (on two alternating streams: chunk c + 1 fills the CUs as chunk c drains)
+// meanwhile.  The compare is VALU work, the expansion store work; unique ids are numbered by first occurrence, so both sweep their triangles in
+// the same direction and the compare stays ahead.  Same kernels, same bits.  Only diagonal / border tiles are left to launch_expand_unique.
+static int mh_tiles_pipe(const MhCall &k) {
+  const Config &cfg = da::config();
+  const MhCodes &c = k.c;
+  uint16_t *ftab = static_cast<uint16_t *>(k.ex);
+  const hipStream_t stream = k.stream;
+  const std::vector<int32_t> &ub = k.d.ub;
+  const int64_t U = k.d.U, KB = mh_sym_bands(U), NB = (int64_t)ub.size() - 1, ld_f = ceil_div(k.n, 8) * 8;
+  int rc;
+  const int step = cfg.mh_pipe_step > 0 ? cfg.mh_pipe_step : 4, wg = cfg.mh_pipe_wg > 0 ? cfg.mh_pipe_wg : 2;
+  const bool alt = !cfg.mh_pipe_one_stream;
+  struct Chunk { int64_t kb0, kb1, ob0, ob1; };
+  std::vector<Chunk> chunks;
+  for (int64_t kb = 0, ob = 0; kb < KB;) {
+    const int64_t kb1 = std::min(KB, kb + (chunks.empty() ? 1 : step));   // a first chunk of one band: the expansion starts early
+    int64_t ob1 = ob;
+    if (kb1 == KB) ob1 = NB;
+    else while (ob1 < NB && (int64_t)ub[(size_t)ob1 + 1] <= kb1 * 1024) ++ob1;   // rows below 1024 (ob1 + 1) only use ids < ub[ob1 + 1]
+    chunks.push_back({kb, kb1, ob, ob1});
+    kb = kb1; ob = ob1;
+  }
+  const size_t C = chunks.size();
+  const PipeLease lease(5 * C);
+  PipeRes *const pr = lease.r;
+  if (!pr) return MH_NO_PIPE;
+  hipEvent_t *pe = pr->ev.data();                                  // per chunk: table rows done, gather begin / end, rows begin / end
+  DA_HIP_TRY(hipStreamWaitEvent(pr->side, k.ev[2], 0));
+  if ((rc = launch_mh_compare_edges_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, pr->side, c.bits)) != DA_OK) return rc;
+  if (c.split() && (rc = c.lists(pr->side)) != DA_OK) return rc;
+  for (size_t ci = 0; ci < C; ++ci) {
+    const Chunk &ch = chunks[ci];
+    if ((rc = launch_mh_compare_bands_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, ch.kb0, ch.kb1, wg, pr->side, c.bits)) != DA_OK) return rc;
+    if (c.split() && (rc = c.fixup(DA_OUT_COMPACT, k.dtab, k.ld_d, pr->side, ch.kb0 * 8, ch.kb1 * 8)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(pe[5 * ci], pr->side));
+    DA_HIP_TRY(hipStreamWaitEvent(stream, pe[5 * ci], 0));
+    DA_HIP_TRY(hipEventRecord(pe[5 * ci + 1], stream));
+    if ((rc = launch_gather_columns(k.dtab, k.ld_d, k.d.p.uidx, k.d.p.ufirst, k.n, U, ftab, ld_f, false, stream, 1, 0, ch.kb0 * 1024,
+                                    std::min(U, ch.kb1 * 1024))) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(pe[5 * ci + 2], stream));
+    const hipStream_t es = alt ? pr->alt[ci & 1] : stream;
+    if (alt) DA_HIP_TRY(hipStreamWaitEvent(es, pe[5 * ci + 2], 0));
+    DA_HIP_TRY(hipEventRecord(pe[5 * ci + 3], es));
+    if ((rc = launch_expand_rows(ftab, ld_f, k.d.p.uidx, k.n, false, k.n_hash, 0, k.out, k.ld, ch.ob0, ch.ob1, es)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(pe[5 * ci + 4], es));
+  }
+  if (alt) for (size_t ci = (C >= 2 ? C - 2 : 0); ci < C; ++ci) DA_HIP_TRY(hipStreamWaitEvent(stream, pe[5 * ci + 4], 0));
+  DA_HIP_TRY(hipEventRecord(k.ev[5], stream));
+  if ((rc = launch_expand_unique(k.dtab, k.ld_d, k.d.p.uidx, k.n, DA_OUT_F64, false, k.n_hash, k.out, k.ld, stream, 0, ftab, k.d.p.ufirst, U,
+                                 nullptr, nullptr, 1, 0, true)) != DA_OK) return rc;
+  if ((rc = mh_finish(k, 6, MH_TILES_PIPE, 2)) != DA_OK) return rc;
+  k.route.chunks = (int)C;
+  MhEvents::ms(k.route, 2, k.ev[2], pe[5 * (C - 1)]);             // the compare's span on the side stream (it overlaps what follows)
+  LaunchUnion expand{k.ev[2]};
+  for (size_t ci = 0; ci < C; ++ci) {
+    float g = 0;
+    (void)hipEventElapsedTime(&g, pe[5 * ci + 1], pe[5 * ci + 2]);
+    k.route.ms[3] += g;                                              // gathers: summed (each includes its wait for free LDS beside the expansion)
+    if (chunks[ci].ob1 > chunks[ci].ob0) { ++k.route.expand_launches; expand.add(pe[5 * ci + 3], pe[5 * ci + 4]); }
+  }
+  k.route.ms[4] = expand.total;
+  MhEvents::ms(k.route, 5, k.ev[5], k.ev[6]);
+  return DA_OK;
+}
+}  // namespace
 
 static int mh_full_symmetric(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t total, int k, int n_hash,
                              const uint32_t *d_seeds, double *d_out, int64_t ld, hipStream_t stream) {
+  const Config &cfg = da::config();
   int rc;
-  MhRoute &route = mh_route();
-  route = MhRoute();
-  route.n = route.unique = n;
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 7; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
-  for (auto &e : ev) DA_HIP_TRY(hipEventCreate(&e));
+  MhRoute &route = mh_route() = MhRoute();
+  route.n = n;
+  MhEvents ev;
+  for (auto &e : ev.e) DA_HIP_TRY(hipEventCreate(&e));
   DA_HIP_TRY(hipEventRecord(ev[0], stream));
-  const int64_t lds = sig_ld_for(n_hash);
-  int64_t min_n = 2048;
-  if (da::config().mh_dedup_min_n >= 0) min_n = da::config().mh_dedup_min_n;   // DYNAALIGN_MH_DEDUP_MIN_N: tests lower it to reach the route with small inputs
-  const bool eligible = n >= min_n && n <= 0x7ffffff0LL && total > 0 && n_hash <= 2047 && !da::config().mh_no_dedup;
-  DevBuf plan_work;
-  NwDedupPlan p{};
-  int64_t U = n;
-  bool take = false;
-  std::vector<int32_t> ub;
-  if (eligible) {
-    if ((rc = plan_work.alloc(nw_dedup_workspace_bytes(n, total))) != DA_OK) return rc;
-    p = nw_dedup_layout(plan_work.p, n, total);
-    if ((rc = launch_nw_dedup_count(d_res, d_off, n, p, stream)) != DA_OK) return rc;
-    int32_t M = 0, S = 0;
-    DA_HIP_TRY(hipMemcpyAsync(&M, p.pm + n, 4, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipMemcpyAsync(&S, p.ps + n, 4, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    U = (int64_t)M + S;
-    route.unique = U;
-    // K2 on U rows + column gather + expansion (0.5 + 1.6 f + 22 f^2 + 4.1 f + 14.4 ms at N = 100k, f = U / n) against K1 + K1b + K2 with its
-    // own float64 stores (27.2 ms): the route pays below f = 0.63
-    // ... with the tile expansion.  With the row expansion (no gather, no copy of the table) the route costs ~1.5 + 26 f^2 + 14 ms one kernel after the
-    // other: 24.4 ms at f = 0.60, 26.6 at f = 0.65 against 27 (12 code planes) - 30 ms (14) for the direct kernels (profiles/r03_q_dedup_threshold.txt): 0.68
-    int64_t max_pct = expand_stream_ok(n, std::min<int64_t>(U, 65536), n_hash, d_out, ld) ? 68 : 60;
-    if (da::config().mh_dedup_max_pct >= 0) max_pct = da::config().mh_dedup_max_pct;   // DYNAALIGN_MH_DEDUP_MAX_PCT
-    take = U > 0 && U * 100 <= n * max_pct && expand_rows_workspace_bytes(n, U, DA_OUT_F64, false, n_hash, 0) != 0;
-    if (take && (rc = launch_nw_dedup_build(d_res, d_off, n, U, p, stream, true)) != DA_OK) return rc;   // ids by first occurrence
-    const int form0 = da::config().mh_expand;                      // DYNAALIGN_MH_EXPAND: 0 default, 1 rows, 2 rowspipe, 3 pipe, 4 tiles
-    const bool rows_form = form0 <= 2 && expand_stream_ok(n, U, n_hash, d_out, ld);
-    if (take && !rows_form) {                                      // (the row expansion needs no schedule of output bands: one read-back less)
-      // ub[b] = unique ids the input rows [0, 1024 b) use (prefix counts of the plan, read at the band boundaries): the TILE pipeline's schedule
-      const int64_t NB = mh_sym_bands(n);
-      std::vector<int32_t> a((size_t)NB), b((size_t)NB);
-      DA_HIP_TRY(hipMemcpy2DAsync(a.data(), 4, p.pm, 4096, 4, (size_t)NB, hipMemcpyDeviceToHost, stream));
-      DA_HIP_TRY(hipMemcpy2DAsync(b.data(), 4, p.ps, 4096, 4, (size_t)NB, hipMemcpyDeviceToHost, stream));
-      DA_HIP_TRY(hipStreamSynchronize(stream));
-      ub.resize((size_t)NB + 1);
-      for (int64_t q = 0; q < NB; ++q) ub[(size_t)q] = a[(size_t)q] + b[(size_t)q];
-      ub[(size_t)NB] = (int32_t)U;
-    }
-  }
+  MhDedup d;
+  if ((rc = mh_dedup_plan(d_res, d_off, n, total, n_hash, d_out, ld, &d, stream)) != DA_OK) return rc;
+  route.unique = d.U;
   DA_HIP_TRY(hipEventRecord(ev[1], stream));
-  const int64_t m = take ? U : n;                                   // rows the kernels see
-  const uint8_t *res_m = take ? p.ucodes : d_res;
-  const int64_t *off_m = take ? p.uoff : d_off;
-  DevBuf sig, planes, pwork;
-  const size_t wb = mh_planes_workspace_bytes(m, n_hash);
-  if ((rc = sig.alloc((size_t)m * lds * sizeof(uint32_t))) != DA_OK) return rc;
-  if ((rc = planes.alloc((size_t)mh_planes_words(m, n_hash) * sizeof(uint32_t))) != DA_OK) return rc;
-  if ((rc = pwork.alloc(wb)) != DA_OK) return rc;
-  if ((rc = launch_minhash_signatures(res_m, off_m, m, k, n_hash, d_seeds, sig.as<uint32_t>(), lds, stream)) != DA_OK) return rc;
-  int bits = 32;
-  SparseHint sp;
-  // the sparse route is only worth asking about when the input has few duplicates (clustered inputs have large classes: the dense kernels win)
-  const bool ask_sparse = !take && U * 10 >= n * 9;
-  // the heavy / rare split (8 dense planes + incidence lists for the rare values): the direct route; the duplicate route's table compare on request
-  // (duplicate route: when the table's dictionaries need more than 12 planes -- there is no banded kernel for those, so the split is what lets the
-  // route pipeline at all; with 12 planes the pipelined route gains 0.2 ms of 16.8 from it at 100k, profiles/r04_l_*: on request only)
-  HybridHint hy;
-  if (take && !da::config().mh_hybrid_dedup) hy.only_from_bits = 13;
-  if ((rc = build_planes(sig.as<uint32_t>(), lds, m, n_hash, 0, pwork.p, wb, planes.as<uint32_t>(), &bits, stream, ask_sparse ? &sp : nullptr, &hy)) != DA_OK) return rc;
-  DevBuf hy_scratch, hy_entries32, hy_entries;
-  if (hy.take) {
-    // the split is an optimisation: when the lists' scratch does not fit, the planes are rebuilt with all the code bits
-    const bool fits = hy_scratch.alloc(mh_sparse_scratch_words(m, n_hash, hy.max_ids, hy.ld_ids) * 4) == DA_OK &&
-                      hy_entries32.alloc((size_t)hy.pairs * 4 + 16) == DA_OK && hy_entries.alloc((size_t)hy.pairs * 2 + 16) == DA_OK;
-    if (!fits) {
-      (void)hipGetLastError();
-      hy = HybridHint();
-      if ((rc = build_planes(sig.as<uint32_t>(), lds, m, n_hash, 0, pwork.p, wb, planes.as<uint32_t>(), &bits, stream, nullptr, nullptr)) != DA_OK) return rc;
-    }
-  }
-  route.plane_bits = bits;
-  route.hybrid_pairs = hy.take ? (int64_t)hy.pairs : -1;
-  route.hybrid_bits_before = hy.bits_before;
+  // sparse route: only with few duplicates (clustered inputs have large classes: the dense kernels win).  Split: the direct route; the duplicate
+  // route's table when it needs more than 12 planes (no banded kernel for those: the split lets the route pipeline at all); with 12 planes the
+  // pipelined route gains 0.2 ms of 16.8 from it at 100k (profiles/r04_l_*): on request only (DYNAALIGN_MH_HYBRID_DEDUP)
+  MhCodes c;
+  if ((rc = mh_codes(d.take ? d.p.ucodes : d_res, d.take ? d.p.uoff : d_off, d.take ? d.U : n, k, n_hash, d_seeds, !d.take && d.U * 10 >= n * 9,
+                     d.take && !cfg.mh_hybrid_dedup ? 13 : 12, &c, stream)) != DA_OK) return rc;
+  route.plane_bits = c.bits;
+  if (c.split()) { route.hybrid_pairs = (int64_t)c.adm.pairs; route.hybrid_bits_before = c.dict.bits_data; }
   DA_HIP_TRY(hipEventRecord(ev[2], stream));
-  // lists of the rare values' incidences (tile by tile) and, after a compare, their addition to its result
-  auto hy_lists = [&](hipStream_t st) -> int {
-    return launch_mh_sparse_lists(hy.sparse_codes, hy.ld_ids, m, n_hash, hy.max_ids, hy.pairs, hy_scratch.as<uint32_t>(), hy_entries32.as<uint32_t>(),
-                                  hy_entries.as<uint16_t>(), st);
-  };
-  auto hy_fixup = [&](int kind, void *out, int64_t ld_out, int64_t tr0, int64_t tr1, hipStream_t st) -> int {
-    return launch_mh_sparse_fixup(hy_scratch.as<uint32_t>(), hy_entries.as<uint16_t>(), m, n_hash, hy.max_ids, hy.ld_ids, kind, out, ld_out, tr0, tr1, st);
-  };
-  const int64_t TR_ALL = (m + 127) / 128;
-  if (!take && sp.take) {
-    // SPARSE route: the signatures rarely agree -- the matching incidences are enumerated from the dictionary codes, bucketed per output
-    // tile and every tile written once (exact; minhash_kernels.hip).  ms[2] = link + walk + scan (buckets), ms[4] = the tile pass.
-    int64_t ld_ids = 0;
-    const uint16_t *ids = mh_dictionary_codes(pwork.p, n, n_hash, &ld_ids);
-    DevBuf scratch, entries32, entries;
-    // the route is an optimisation: when its scratch does not fit (or the incidence count exceeds what its 32-bit offsets cover) the
-    // call does not fail -- the dense compare below needs none of it
-    const bool fits = sp.pairs <= 0xfffffff0ull && scratch.alloc(mh_sparse_scratch_words(n, n_hash, sp.max_ids, ld_ids) * 4) == DA_OK &&
-                      entries32.alloc((size_t)sp.pairs * 4 + 16) == DA_OK && entries.alloc((size_t)sp.pairs * 2 + 16) == DA_OK;
-    if (!fits) {
-      (void)hipGetLastError();
-      sp.take = false;
-      if ((rc = build_planes(sig.as<uint32_t>(), lds, m, n_hash, 0, pwork.p, wb, planes.as<uint32_t>(), &bits, stream, nullptr)) != DA_OK) return rc;
-      route.plane_bits = bits;
-      DA_HIP_TRY(hipEventRecord(ev[2], stream));
-    }
-    else if ((rc = launch_mh_sparse(ids, ld_ids, n, n_hash, sp.max_ids, sp.pairs, scratch.as<uint32_t>(), entries32.as<uint32_t>(), entries.as<uint16_t>(), d_out, ld,
-                               stream, ev[3])) != DA_OK) return rc;
-    if (sp.take) {
-    DA_HIP_TRY(hipEventRecord(ev[4], stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    route.taken = 2;
-    route.unique = (int64_t)sp.pairs;                               // (reported as `sparse_pairs` by the Python wrapper)
-    (void)hipEventElapsedTime(&route.ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&route.ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&route.ms[2], ev[2], ev[3]);
-    (void)hipEventElapsedTime(&route.ms[4], ev[3], ev[4]);
-    return DA_OK;
-    }
-  }
-  if (!take) {
-    // heavy / rare split: the list kernels (latency-bound, ~0.9 ms at 100k) run on a side stream beside the dense compare; without a side stream, before it
-    PipeRes *pr = hy.take ? pipe_acquire(1) : nullptr;
-    struct PipeGuard { PipeRes *r; ~PipeGuard() { if (r) { (void)hipStreamSynchronize(r->side); pipe_release(r); } } } pguard{pr};
-    if (pr) {
-      DA_HIP_TRY(hipStreamWaitEvent(pr->side, ev[2], 0));
-      if ((rc = hy_lists(pr->side)) != DA_OK) return rc;
-      DA_HIP_TRY(hipEventRecord(pr->ev[0], pr->side));
-    } else if (hy.take && (rc = hy_lists(stream)) != DA_OK) return rc;
-    if ((rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, 0, n, true, DA_OUT_F64, d_out, ld, stream, bits)) != DA_OK) return rc;
-    if (pr) DA_HIP_TRY(hipStreamWaitEvent(stream, pr->ev[0], 0));
-    if (hy.take && (rc = hy_fixup(DA_OUT_F64, d_out, ld, 0, TR_ALL, stream)) != DA_OK) return rc;
-    DA_HIP_TRY(hipEventRecord(ev[3], stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    (void)hipEventElapsedTime(&route.ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&route.ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&route.ms[2], ev[2], ev[3]);
-    return DA_OK;
-  }
-  const int64_t ld_d = (U + 7) / 8 * 8;
-  DevBuf dtab, ftab;
-  if ((rc = dtab.alloc((size_t)U * (size_t)ld_d * 2)) != DA_OK) return rc;
-  // The expansion has two kernels families and each a pipelined form (DYNAALIGN_MH_EXPAND = rowspipe | rows | pipe | tiles; default: the first
-  // whose shape test passes; DYNAALIGN_MH_NO_PIPE=1 takes the pipelined forms out):
-  //   rows    K2 on the table, then k_expand_stream: every output row written once from its table row in LDS (no gathered copy)
-  //   tiles   K2, column gather (k_gather_columns), tile expansion (k_expand_rows) + diagonal / border tiles, one after the other
-  //   rowspipe / pipe   the same kernels with K2 run band by band on a side stream while finished table rows are expanded
-  static const char *const form_names[5] = {"", "rows", "rowspipe", "pipe", "tiles"};
-  const std::string form = form_names[da::config().mh_expand];
-  const bool may_pipe = !da::config().mh_no_pipe && mh_compare_bands_ok(U, n_hash, bits, dtab.p, ld_d);
-  if ((form.empty() || form == "rows" || form == "rowspipe") && expand_stream_ok(n, U, n_hash, d_out, ld)) {
-    DevBuf lists;
-    if ((rc = lists.alloc(expand_stream_scratch_bytes(n, U))) != DA_OK) return rc;
-    if (form != "rows" && may_pipe) do {
-      // the row expansion PIPELINED with K2: the first `head` bands of the table at full occupancy, the rest by the persistent kernel with `wg`
-      // workgroup(s) per CU on a side stream (one 36 KB ring fits beside the expansion's 94 KB row) while the finished table rows are expanded
-      const int64_t KB = mh_sym_bands(U);
-      // K2 rings (36 KB, 128 VGPRs x 4 waves) that fit beside one expansion workgroup: two when its LDS row is packed (n_hash <= 511), else one --
-      // and a slower K2 wants a head start and smaller chunks (profiles/r03_m_pipeline_rows_*.txt: head x step sweeps for both)
-      const bool two = expand_stream_packed(n_hash);
-      int wg = two ? 2 : 1, head = two ? 1 : 4, step = two ? 8 : 4;
-      if (da::config().mh_pipe_step > 0) step = da::config().mh_pipe_step;       // DYNAALIGN_MH_PIPE_STEP / _WG / _HEAD / _ONE_STREAM: schedule experiments
-      if (da::config().mh_pipe_wg > 0) wg = da::config().mh_pipe_wg;
-      if (da::config().mh_pipe_head > 0) head = da::config().mh_pipe_head;
-      const bool alt = !da::config().mh_pipe_one_stream;
-      std::vector<int64_t> cuts{0};
-      while (cuts.back() < KB) cuts.push_back(std::min(KB, cuts.back() + (cuts.size() == 1 ? head : step)));
-      const size_t C = cuts.size() - 1;
-      PipeRes *pr = pipe_acquire(3 * C + 2);
-      if (!pr) break;   // no side stream / events to be had: the one-stream form below needs none
-      struct PipeGuard { PipeRes *r; ~PipeGuard() { (void)hipStreamSynchronize(r->side); (void)hipStreamSynchronize(r->alt[0]); (void)hipStreamSynchronize(r->alt[1]); pipe_release(r); } } pguard{pr};
-      hipEvent_t *pe = pr->ev.data();                                // per chunk: table rows done, rows begin / end; [3 C]: lists done
-      // beside the first band on the side stream: the table's diagonal / border tiles and the copy lists, both on the caller's stream
-      DA_HIP_TRY(hipStreamWaitEvent(pr->side, ev[2], 0));
-      if ((rc = launch_mh_compare_edges_u16(planes.as<uint32_t>(), U, n_hash, dtab.as<uint16_t>(), ld_d, stream, bits)) != DA_OK) return rc;
-      if ((rc = launch_expand_stream_lists(p.uidx, n, U, lists.p, stream)) != DA_OK) return rc;
-      DA_HIP_TRY(hipEventRecord(pe[3 * C], stream));
-      if (hy.take) {     // the rare values' lists behind them on the caller's stream (on the idle expansion stream instead: 17.3 vs 16.6 ms, round 4)
-        if ((rc = hy_lists(stream)) != DA_OK) return rc;
-        DA_HIP_TRY(hipEventRecord(pe[3 * C + 1], stream));
-      }
-      if (alt) { DA_HIP_TRY(hipStreamWaitEvent(pr->alt[0], pe[3 * C], 0)); DA_HIP_TRY(hipStreamWaitEvent(pr->alt[1], pe[3 * C], 0)); }
-      for (size_t c = 0; c < C; ++c) {
-        if ((rc = launch_mh_compare_bands_u16(planes.as<uint32_t>(), U, n_hash, dtab.as<uint16_t>(), ld_d, cuts[c], cuts[c + 1], c == 0 ? 4 : wg, pr->side, bits)) != DA_OK) return rc;
-        if (hy.take) {     // the rare values' incidences of these tile rows (direct + mirrored elements), once the edge tiles and the lists are there
-          if (c == 0) { DA_HIP_TRY(hipStreamWaitEvent(pr->side, pe[3 * C], 0)); DA_HIP_TRY(hipStreamWaitEvent(pr->side, pe[3 * C + 1], 0)); }
-          if ((rc = hy_fixup(DA_OUT_COMPACT, dtab.p, ld_d, cuts[c] * 8, cuts[c + 1] * 8, pr->side)) != DA_OK) return rc;
-        }
-        DA_HIP_TRY(hipEventRecord(pe[3 * c], pr->side));
-        const hipStream_t es = alt ? pr->alt[c & 1] : stream;
-        DA_HIP_TRY(hipStreamWaitEvent(es, pe[3 * c], 0));
-        DA_HIP_TRY(hipEventRecord(pe[3 * c + 1], es));
-        if ((rc = launch_expand_stream_rows(dtab.as<uint16_t>(), ld_d, p.uidx, n, U, n_hash, d_out, ld, lists.p, cuts[c] * 1024, cuts[c + 1] * 1024, es, (int)c)) != DA_OK) return rc;
-        DA_HIP_TRY(hipEventRecord(pe[3 * c + 2], es));
-      }
-      if (alt) for (size_t c = (C >= 2 ? C - 2 : 0); c < C; ++c) DA_HIP_TRY(hipStreamWaitEvent(stream, pe[3 * c + 2], 0));
-      DA_HIP_TRY(hipEventRecord(ev[5], stream));
-      DA_HIP_TRY(hipStreamSynchronize(stream));
-      route.taken = 5;
-      route.chunks = route.expand_launches = (int)C;
-      (void)hipEventElapsedTime(&route.ms[0], ev[0], ev[1]);
-      (void)hipEventElapsedTime(&route.ms[1], ev[1], ev[2]);
-      (void)hipEventElapsedTime(&route.ms[2], ev[2], pe[3 * (C - 1)]);   // the compare's span on the side stream
-      (void)hipEventElapsedTime(&route.ms[3], ev[2], pe[3 * C]);          // the copy lists (beside the compare)
-      float covered_to = 0;
-      for (size_t c = 0; c < C; ++c) {                                    // ms[4]: the time some k_expand_stream launch was running (union)
-        float b = 0, e = 0;
-        (void)hipEventElapsedTime(&b, ev[2], pe[3 * c + 1]);
-        (void)hipEventElapsedTime(&e, ev[2], pe[3 * c + 2]);
-        if (e > covered_to) { route.ms[4] += e - std::max(b, covered_to); covered_to = e; }
-      }
-      return DA_OK;
-    } while (0);
-    if (hy.take && (rc = hy_lists(stream)) != DA_OK) return rc;
-    if ((rc = launch_mh_compare(planes.as<uint32_t>(), U, n_hash, 0, U, true, DA_OUT_COMPACT, dtab.p, ld_d, stream, bits)) != DA_OK) return rc;
-    if (hy.take && (rc = hy_fixup(DA_OUT_COMPACT, dtab.p, ld_d, 0, TR_ALL, stream)) != DA_OK) return rc;
-    DA_HIP_TRY(hipEventRecord(ev[3], stream));
-    if ((rc = launch_expand_stream(dtab.as<uint16_t>(), ld_d, p.uidx, n, U, n_hash, d_out, ld, lists.p, stream, ev[4])) != DA_OK) return rc;
-    DA_HIP_TRY(hipEventRecord(ev[5], stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    route.taken = 4;
-    route.chunks = route.expand_launches = 1;
-    (void)hipEventElapsedTime(&route.ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&route.ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&route.ms[2], ev[2], ev[3]);
-    (void)hipEventElapsedTime(&route.ms[3], ev[3], ev[4]);             // the copy lists (positions of every id, work items)
-    (void)hipEventElapsedTime(&route.ms[4], ev[4], ev[5]);             // k_expand_stream
-    return DA_OK;
-  }
-  if ((rc = ftab.alloc(expand_rows_workspace_bytes(n, U, DA_OUT_F64, false, n_hash, 0))) != DA_OK) return rc;
+  MhCall call{n, n_hash, d_out, ld, stream, route, ev, c, d};
+  if (!d.take) return c.adm.form == MhOperand::sparse ? mh_sparse(call) : mh_direct(call);
+  // The expansion has two kernel families and each a pipelined form (DYNAALIGN_MH_EXPAND = rowspipe | rows | pipe | tiles; default: the first
+  // whose shape test passes; DYNAALIGN_MH_NO_PIPE=1 takes the pipelined forms out)
+  DevBuf dtab, ex;
+  call.ld_d = (d.U + 7) / 8 * 8;
+  if ((rc = dtab.alloc((size_t)d.U * (size_t)call.ld_d * 2)) != DA_OK) return rc;
+  if ((rc = ex.alloc(d.rows ? expand_stream_scratch_bytes(n, d.U) : expand_rows_workspace_bytes(n, d.U, DA_OUT_F64, false, n_hash, 0))) != DA_OK) return rc;
+  call.dtab = dtab.as<uint16_t>(); call.ex = ex.p;
   // (the pipelined tile form leaves only diagonal / border tiles to launch_expand_unique: the output must qualify for the streaming passes)
-  if (form != "tiles" && !ub.empty() && may_pipe && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) do {
-    // PIPELINED form.  The table is compared band by band (1024 unique rows each, in order) by the persistent kernel on
-    // a side stream with only `wg` workgroups per CU, so the rest of every CU stays free; the output row bands whose strings are all
-    // numbered below the finished table rows are gathered (on `stream`) and expanded (on two alternating streams: chunk c + 1 fills
-    // the CUs as chunk c drains) meanwhile.  The compare is VALU work, the expansion store work; unique ids are numbered by first
-    // occurrence, so both sweep their triangles in the same direction and the compare stays ahead.  Same kernels, same bits.
-    const int64_t KB = mh_sym_bands(U), NB = (int64_t)ub.size() - 1, ld_f = ceil_div(n, 8) * 8;
-    int step = 4, wg = 2;
-    if (da::config().mh_pipe_step > 0) step = da::config().mh_pipe_step;
-    if (da::config().mh_pipe_wg > 0) wg = da::config().mh_pipe_wg;
-    const bool alt = !da::config().mh_pipe_one_stream;
-    struct Chunk { int64_t kb0, kb1, ob0, ob1; };
-    std::vector<Chunk> chunks;
-    for (int64_t kb = 0, ob = 0; kb < KB;) {
-      const int64_t kb1 = std::min(KB, kb + (chunks.empty() ? 1 : step));   // a first chunk of one band: the expansion starts early
-      int64_t ob1 = ob;
-      if (kb1 == KB) ob1 = NB;
-      else while (ob1 < NB && (int64_t)ub[(size_t)ob1 + 1] <= kb1 * 1024) ++ob1;   // rows below 1024 (ob1 + 1) only use ids < ub[ob1 + 1]
-      chunks.push_back({kb, kb1, ob, ob1});
-      kb = kb1; ob = ob1;
-    }
-    const size_t C = chunks.size();
-    PipeRes *pr = pipe_acquire(5 * C);
-    if (!pr) break;   // no side stream / events to be had: the one-stream form below needs none
-    // leaves the side streams idle before the buffers declared above go back to the cache (error returns included)
-    struct PipeGuard { PipeRes *r; ~PipeGuard() { (void)hipStreamSynchronize(r->side); (void)hipStreamSynchronize(r->alt[0]); (void)hipStreamSynchronize(r->alt[1]); pipe_release(r); } } pguard{pr};
-    hipEvent_t *pe = pr->ev.data();                                  // per chunk: table rows done, gather begin / end, rows begin / end
-    DA_HIP_TRY(hipStreamWaitEvent(pr->side, ev[2], 0));
-    if ((rc = launch_mh_compare_edges_u16(planes.as<uint32_t>(), U, n_hash, dtab.as<uint16_t>(), ld_d, pr->side, bits)) != DA_OK) return rc;
-    if (hy.take && (rc = hy_lists(pr->side)) != DA_OK) return rc;
-    for (size_t c = 0; c < C; ++c) {
-      const Chunk &ch = chunks[c];
-      if ((rc = launch_mh_compare_bands_u16(planes.as<uint32_t>(), U, n_hash, dtab.as<uint16_t>(), ld_d, ch.kb0, ch.kb1, wg, pr->side, bits)) != DA_OK) return rc;
-      if (hy.take && (rc = hy_fixup(DA_OUT_COMPACT, dtab.p, ld_d, ch.kb0 * 8, ch.kb1 * 8, pr->side)) != DA_OK) return rc;
-      DA_HIP_TRY(hipEventRecord(pe[5 * c], pr->side));
-      DA_HIP_TRY(hipStreamWaitEvent(stream, pe[5 * c], 0));
-      DA_HIP_TRY(hipEventRecord(pe[5 * c + 1], stream));
-      if ((rc = launch_gather_columns(dtab.as<uint16_t>(), ld_d, p.uidx, p.ufirst, n, U, ftab.as<uint16_t>(), ld_f, false, stream, 1, 0,
-                                      ch.kb0 * 1024, std::min(U, ch.kb1 * 1024))) != DA_OK) return rc;
-      DA_HIP_TRY(hipEventRecord(pe[5 * c + 2], stream));
-      const hipStream_t es = alt ? pr->alt[c & 1] : stream;
-      if (alt) DA_HIP_TRY(hipStreamWaitEvent(es, pe[5 * c + 2], 0));
-      DA_HIP_TRY(hipEventRecord(pe[5 * c + 3], es));
-      if ((rc = launch_expand_rows(ftab.as<uint16_t>(), ld_f, p.uidx, n, false, n_hash, 0, d_out, ld, ch.ob0, ch.ob1, es)) != DA_OK) return rc;
-      DA_HIP_TRY(hipEventRecord(pe[5 * c + 4], es));
-    }
-    if (alt) for (size_t c = (C >= 2 ? C - 2 : 0); c < C; ++c) DA_HIP_TRY(hipStreamWaitEvent(stream, pe[5 * c + 4], 0));
-    DA_HIP_TRY(hipEventRecord(ev[5], stream));
-    if ((rc = launch_expand_unique(dtab.as<uint16_t>(), ld_d, p.uidx, n, DA_OUT_F64, false, n_hash, d_out, ld, stream, 0, ftab.as<uint16_t>(),
-                                   p.ufirst, U, nullptr, nullptr, 1, 0, true)) != DA_OK) return rc;
-    DA_HIP_TRY(hipEventRecord(ev[6], stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    route.taken = 3;
-    route.chunks = (int)C;
-    for (const Chunk &ch : chunks) route.expand_launches += ch.ob1 > ch.ob0 ? 1 : 0;
-    (void)hipEventElapsedTime(&route.ms[0], ev[0], ev[1]);
-    (void)hipEventElapsedTime(&route.ms[1], ev[1], ev[2]);
-    (void)hipEventElapsedTime(&route.ms[2], ev[2], pe[5 * (C - 1)]);       // the compare's span on the side stream (it overlaps what follows)
-    float covered_to = 0;                                                  // ms[4]: the time some k_expand_rows launch was running (their
-    for (size_t c = 0; c < C; ++c) {                                       // intervals overlap on the alternating streams: union, not sum)
-      float g = 0, b = 0, e = 0;
-      (void)hipEventElapsedTime(&g, pe[5 * c + 1], pe[5 * c + 2]);
-      (void)hipEventElapsedTime(&b, ev[2], pe[5 * c + 3]);
-      (void)hipEventElapsedTime(&e, ev[2], pe[5 * c + 4]);
-      route.ms[3] += g;                                                    // gathers: summed (each includes its wait for free LDS beside the expansion)
-      if (chunks[c].ob1 > chunks[c].ob0 && e > covered_to) { route.ms[4] += e - std::max(b, covered_to); covered_to = e; }
-    }
-    (void)hipEventElapsedTime(&route.ms[5], ev[5], ev[6]);
-    return DA_OK;
-  } while (0);
-  if (hy.take && (rc = hy_lists(stream)) != DA_OK) return rc;
-  if ((rc = launch_mh_compare(planes.as<uint32_t>(), U, n_hash, 0, U, true, DA_OUT_COMPACT, dtab.p, ld_d, stream, bits)) != DA_OK) return rc;
-  if (hy.take && (rc = hy_fixup(DA_OUT_COMPACT, dtab.p, ld_d, 0, TR_ALL, stream)) != DA_OK) return rc;
-  DA_HIP_TRY(hipEventRecord(ev[3], stream));
-  if ((rc = launch_expand_unique(dtab.as<uint16_t>(), ld_d, p.uidx, n, DA_OUT_F64, false, n_hash, d_out, ld, stream, 0, ftab.as<uint16_t>(),
-                                 p.ufirst, U, ev[4], ev[5])) != DA_OK) return rc;
-  DA_HIP_TRY(hipEventRecord(ev[6], stream));
-  DA_HIP_TRY(hipStreamSynchronize(stream));                         // the buffers go back to the parked-buffer cache here
-  route.taken = 1;
-  route.chunks = route.expand_launches = 1;
-  (void)hipEventElapsedTime(&route.ms[0], ev[0], ev[1]);
-  (void)hipEventElapsedTime(&route.ms[1], ev[1], ev[2]);
-  (void)hipEventElapsedTime(&route.ms[2], ev[2], ev[3]);
-  (void)hipEventElapsedTime(&route.ms[3], ev[3], ev[4]);
-  (void)hipEventElapsedTime(&route.ms[4], ev[4], ev[5]);
-  (void)hipEventElapsedTime(&route.ms[5], ev[5], ev[6]);
-  return DA_OK;
+  const bool pipe = !cfg.mh_no_pipe && mh_compare_bands_ok(d.U, n_hash, c.bits, dtab.p, call.ld_d) &&
+                    (d.rows ? cfg.mh_expand != MH_EXPAND_ROWS : cfg.mh_expand != MH_EXPAND_TILES && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0);
+  if (pipe && (rc = d.rows ? mh_rows_pipe(call) : mh_tiles_pipe(call)) != MH_NO_PIPE) return rc;
+  return mh_one_stream(call);
 }
 
 int da_dev_similarity_mh(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t total_residues, int k, int n_hash,
@@ -1076,12 +1083,8 @@ int da_dev_unique_plan(const uint8_t *d_bytes, const int64_t *d_offsets, int64_t
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   int rc;
   const NwDedupPlan p = nw_dedup_layout(d_work, n, total_bytes > 0 ? total_bytes : 1);
-  if ((rc = launch_nw_dedup_count(d_bytes, d_offsets, n, p, stream)) != DA_OK) return rc;
-  int32_t M = 0, S = 0;
-  DA_HIP_TRY(hipMemcpyAsync(&M, p.pm + n, 4, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipMemcpyAsync(&S, p.ps + n, 4, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipStreamSynchronize(stream));
-  const int64_t U = (int64_t)M + S;
+  int64_t U = 0;
+  if ((rc = count_unique(d_bytes, d_offsets, n, p, stream, &U)) != DA_OK) return rc;
   if (U <= 0 || U > n) return fail(DA_ERR_HIP, "unique plan: inconsistent counts (%lld unique of %lld)", (long long)U, (long long)n);
   if ((rc = launch_nw_dedup_build(d_bytes, d_offsets, n, U, p, stream)) != DA_OK) return rc;
   plan->n = n; plan->unique = U;
@@ -1202,12 +1205,8 @@ static int nw_full_symmetric(const uint8_t *d_codes, const int64_t *d_offsets, i
     DevBuf work;
     if ((rc = work.alloc(nw_dedup_workspace_bytes(n, total))) != DA_OK) return rc;
     const NwDedupPlan p = nw_dedup_layout(work.p, n, total);
-    if ((rc = launch_nw_dedup_count(d_codes, d_offsets, n, p, stream)) != DA_OK) return rc;
-    int32_t M = 0, S = 0;
-    DA_HIP_TRY(hipMemcpyAsync(&M, p.pm + n, 4, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipMemcpyAsync(&S, p.ps + n, 4, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    const int64_t U = (int64_t)M + S;
+    int64_t U = 0;
+    if ((rc = count_unique(d_codes, d_offsets, n, p, stream, &U)) != DA_OK) return rc;
     if (unique_out) *unique_out = U;
     route.unique = U;
     if (U > 0 && U * 100 <= n * 85) {

@@ -254,8 +254,9 @@ int da_dev_mh_compare(const uint32_t *d_planes, int plane_bits, int64_t n, int n
  * dictionaries need 12 - 16 code planes but nearly all matching incidences sit on each column's 254 most frequent values (clustered data: 7e6 of
  * 2.2e10 on the h3n2-like 100k set), the bit-sliced compare runs on EIGHT planes of dense codes for those values -- every other value reads as
  * "never equal" -- and the incidences of the remaining repeated values are enumerated by the sparse route's list kernels and added to the result
- * (count' = count + m, the float64 element recomputed as (count + m) / n_hash: same division, same bits).  Exact.  Taken when n >= 16384
- * (DYNAALIGN_MH_HYBRID_MIN_N), 32 < n_hash <= 2047, <= 32768 repeated values per column, the rare incidences number <= n_hash / 25000 per pair on average;
+ * (count' = count + m, the float64 element recomputed as (count + m) / n_hash: same division, same bits).  Exact.  Taken when 16384
+ * (DYNAALIGN_MH_HYBRID_MIN_N) <= n <= 131072, 32 < n_hash <= 2047, <= 32768 repeated values per column, the largest rare class <= 4096, the rare
+ * incidences number <= DYNAALIGN_MH_SPARSE_MAX_PAIRS in all and <= n_hash / 25000 per pair on average;
  * DYNAALIGN_MH_NO_HYBRID=1 disables it.  Then *plane_bits_out = 8 and da_mh_last_route_split gives the number of rare incidences (-1: not taken)
  * and the plane count the dictionaries would have needed.
  * Any pointer may be NULL. */

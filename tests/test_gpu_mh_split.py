@@ -1,4 +1,4 @@
-"""GPU tests of the heavy / rare split of similarityMH's compare (api.cpp build_planes / mh_full_symmetric, dict_kernels.hip k_hy_split,
+"""GPU tests of the heavy / rare split of similarityMH's compare (api.cpp mh_admit / mh_full_symmetric, dict_kernels.hip k_hy_split,
 minhash_kernels.hip k_mh_compare_p12<.., 8, ..> + k_sp_* lists + k_hy_fixup*): per hash function the 254 most frequent signature values get dense
 codes on EIGHT bit planes -- every other value reads as "never equal" there -- and the matching incidences of the remaining repeated values are
 enumerated from lists and added to the dense result.  matches(i, j) = sum over h of [sig equal] (reference src/minHash.cpp:168-173) is a sum over
