@@ -364,6 +364,8 @@ struct Trace {
   }
 };
 
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 // How many result rows to keep on the device at once (host-pointer paths).
 int64_t rows_per_block(int64_t n, size_t bytes_per_elem) {
   size_t free_b = 0, total_b = 0;
@@ -1596,6 +1598,147 @@ static int edges_deliver(const EdgeSet &es, int64_t n_edges, double *threshold_o
   }
   return DA_OK;
 }
+}  // extern "C"  (reopened below)
+
+struct da_edges { EdgeSet es; int64_t n_edges = 0; };
+
+// ---- what the host-pointer, edge-list and multi-device entry points share
+namespace da {
+namespace {
+
+int sync_or_fail(const char *what) {
+  return hipStreamSynchronize(nullptr) == hipSuccess ? DA_OK : fail(DA_ERR_HIP, "%s", what);
+}
+
+// The MinHash preparation on the current device: the uploaded input (in), the signatures (K1) and bit planes (K1b) of up to `cap`
+// hash functions at a time, and the planes workspace, held from the first build() (or alloc_work()) to finish().
+struct MhPlanes {
+  DeviceInput in;
+  DevBuf sig, planes, work;
+  int64_t n = 0, lds = 0;
+  int cap = 0, bits = 32;
+  size_t wb = 0;
+  int alloc(int64_t n_, int cap_, bool with_planes = true) {
+    n = n_; cap = cap_; lds = sig_ld_for(cap);
+    int rc = sig.alloc((size_t)n * lds * sizeof(uint32_t));
+    if (rc == DA_OK && with_planes) rc = planes.alloc((size_t)mh_planes_words(n, cap) * sizeof(uint32_t));
+    return rc;
+  }
+  int alloc_work() { wb = mh_planes_workspace_bytes(n, cap); return work.alloc(wb); }
+  // K1 of hash functions [h0, h0 + nh)
+  int signatures(int k, int h0, int nh) {
+    return launch_minhash_signatures(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, nh, in.seeds.as<uint32_t>() + h0,
+                                     sig.as<uint32_t>(), lds, nullptr);
+  }
+  // K1 + K1b of hash functions [h0, h0 + nh): the planes and their `bits`
+  int build(int k, int h0, int nh) {
+    int rc;
+    if ((rc = signatures(k, h0, nh)) != DA_OK) return rc;
+    if (!work.p && (rc = alloc_work()) != DA_OK) return rc;
+    return build_planes(sig.as<uint32_t>(), lds, n, nh, 0, work.p, wb, planes.as<uint32_t>(), &bits, nullptr);
+  }
+  int finish() {
+    DA_HIP_TRY(hipStreamSynchronize(nullptr));   // the workspace is released here, before anything measures free memory
+    work.release();
+    return DA_OK;
+  }
+};
+
+// The NW preparation on the current device: the uploaded input (in) and its residues encoded for the DP (codes)
+struct NwCodes {
+  DeviceInput in;
+  DevBuf codes, bad;
+  int upload(const uint8_t *residues, const int64_t *offsets, int64_t n, int64_t total) {
+    int rc;
+    if ((rc = in.upload(residues, offsets, n, total, nullptr, 0)) != DA_OK) return rc;
+    if ((rc = codes.alloc((size_t)total)) != DA_OK) return rc;
+    if ((rc = bad.alloc(sizeof(int32_t))) != DA_OK) return rc;
+    DA_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int32_t), nullptr));
+    return launch_nw_encode(in.res.as<uint8_t>(), total, codes.as<uint8_t>(), bad.as<int32_t>(), nullptr);
+  }
+};
+
+// The similarity a uint16 result code stands for.  MinHash: match count c -> c / n_hash (src/minHash.cpp:174).
+// NW: (matches << 8 | length) -> matches / length (src/pairwiseSeqAlign.cpp:311), `len0` at length 0.
+std::vector<double> mh_code_values(int n_hash) {
+  std::vector<double> v((size_t)n_hash + 1);
+  for (int c = 0; c <= n_hash; ++c) v[(size_t)c] = (double)c / (double)n_hash;
+  return v;
+}
+std::vector<double> nw_code_values(int count, double len0) {
+  std::vector<double> v((size_t)count);
+  for (int c = 0; c < count; ++c) {
+    const int ln = c & 255;
+    v[(size_t)c] = ln ? (double)(c >> 8) / (double)ln : len0;
+  }
+  return v;
+}
+
+// The n x n float64 matrix for a HOST caller as uint16 codes: compute(d) writes them to the device buffer d, a quarter of the bytes
+// cross PCIe, and the host widens them while copying, out[i] = table[code[i]] -- the divide behind every table entry is the same IEEE
+// operation here as on the device.
+template <typename F> int codes_to_host(int64_t n, double *out, const std::vector<double> &table, Trace &tr, F compute) {
+  const size_t bytes = (size_t)n * (size_t)n * sizeof(uint16_t);
+  DevBuf d;
+  int rc;
+  if ((rc = d.alloc(bytes)) != DA_OK) return rc;
+  if ((rc = compute(d.p)) != DA_OK) return rc;
+  if ((rc = d2h_pipelined(out, d.p, bytes, table.data())) != DA_OK) return rc;
+  tr.mark("device -> host + widen");
+  return DA_OK;
+}
+
+// Rows [r0, r1) of an n-column result (esz bytes per element) to the host at out, in blocks of as many rows as the device holds:
+// compute(b0, b1, d) writes rows [b0, b1) to the device buffer d, then they are copied out.  The block size is measured here, after
+// the caller's allocations.  compute_ms / d2h_ms, if given, add up the time of each step.
+template <typename F> int rows_to_host(int64_t n, int64_t r0, int64_t r1, size_t esz, void *out, F compute,
+                                       double *compute_ms = nullptr, double *d2h_ms = nullptr) {
+  const int64_t blk = rows_per_block(n, esz);
+  DevBuf d;
+  int rc;
+  if ((rc = d.alloc((size_t)std::min(blk, r1 - r0) * (size_t)n * esz)) != DA_OK) return rc;
+  for (int64_t b0 = r0; b0 < r1; b0 += blk) {
+    const int64_t b1 = std::min(r1, b0 + blk);
+    double t = now_ms();
+    if ((rc = compute(b0, b1, d.p)) != DA_OK) return rc;
+    if (compute_ms) *compute_ms += now_ms() - t;
+    t = now_ms();
+    rc = d2h_pipelined(static_cast<char *>(out) + (size_t)(b0 - r0) * (size_t)n * esz, d.p, (size_t)(b1 - b0) * (size_t)n * esz);
+    if (d2h_ms) *d2h_ms += now_ms() - t;
+    if (rc != DA_OK) return rc;
+  }
+  return DA_OK;
+}
+
+// The public edge-list forms around core(want_edges, es, &n_edges).  da_similarity_*_edges: size query (buffers NULL) or fill -- each
+// call runs the whole pipeline.  da_similarity_*_edges_begin / da_edges_fetch / da_edges_free: ONE pass; the result waits in a handle.
+template <typename Core> int edges_run_deliver(double *threshold_out, int64_t *n_edges_out, int64_t capacity, int32_t *ei, int32_t *ej,
+                                              double *ew, Core core) {
+  if (!threshold_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if ((ei || ej || ew) && (!ei || !ej || !ew)) return fail(DA_ERR_BAD_ARG, "NULL edge buffer");
+  EdgeSet es;
+  int64_t m = 0;
+  const int rc = core(ei != nullptr, es, &m);
+  if (rc != DA_OK) return rc;
+  return edges_deliver(es, m, threshold_out, n_edges_out, capacity, ei, ej, ew);
+}
+
+template <typename Core> int edges_run_handle(da_edges **handle_out, double *threshold_out, int64_t *n_edges_out, Core core) {
+  if (!handle_out || !threshold_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *handle_out = nullptr;
+  std::unique_ptr<da_edges> h(new da_edges);
+  const int rc = core(true, h->es, &h->n_edges);
+  if (rc != DA_OK) return rc;
+  *threshold_out = h->es.threshold;
+  *n_edges_out = h->n_edges;
+  *handle_out = h.release();
+  return DA_OK;
+}
+
+}  // namespace
+}  // namespace da
+
+extern "C" {
 
 // similarityNW + clusterbreak's threshold step as an edge list.  The uint16 code (matches << 8 | length)
 // takes few distinct values, so the same histogram / quantile / extraction path as for MinHash applies;
@@ -1617,27 +1760,19 @@ static int nw_edges_core(const uint8_t *residues, const int64_t *offsets, int64_
                   (long long)(i + 1));
   if (max_len > 127) return fail(DA_ERR_UNSUPPORTED, "the NW edge list works on uint16 codes: sequences up to 127 residues");
   if ((rc = require_device()) != DA_OK) return rc;
-  DeviceInput in;
-  if ((rc = in.upload(residues, offsets, n, total, nullptr, 0)) != DA_OK) return rc;
-  DevBuf codes, bad, cnt, hist;
-  if ((rc = codes.alloc((size_t)total)) != DA_OK) return rc;
-  if ((rc = bad.alloc(sizeof(int32_t))) != DA_OK) return rc;
-  DA_HIP_TRY(hipMemset(bad.p, 0, sizeof(int32_t)));
-  if ((rc = launch_nw_encode(in.res.as<uint8_t>(), total, codes.as<uint8_t>(), bad.as<int32_t>(), nullptr)) != DA_OK)
-    return rc;
+  NwCodes nw;
+  DevBuf cnt, hist;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
   if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK) return rc;      // uint16 codes stay on the device
   const int nbins = (int)((max_len << 8) | (2 * max_len)) + 1;              // matches <= max_len, length <= 2 * max_len
   if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;
   DA_HIP_TRY(hipMemset(hist.p, 0, (size_t)nbins * 8));
-  if ((rc = nw_full_symmetric(codes.as<uint8_t>(), in.off.as<int64_t>(), n, total, max_len, mid, gap_open, gap_ext, DA_OUT_COMPACT,
+  if ((rc = nw_full_symmetric(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, total, max_len, mid, gap_open, gap_ext, DA_OUT_COMPACT,
                               cnt.p, n, nullptr)) != DA_OK) return rc;
   if ((rc = launch_upper_histogram(cnt.as<uint16_t>(), n, n, nbins, hist.as<unsigned long long>(), nullptr)) != DA_OK) return rc;
-  std::vector<double> values(nbins);
-  for (int b = 0; b < nbins; ++b) {
-    const int ln = b & 255;
-    values[b] = ln ? (double)(b >> 8) / (double)ln : 0.0;                   // length 0 cannot occur (no empty sequences)
-  }
-  return edges_from_counts(cnt.as<uint16_t>(), n, nbins, hist.as<unsigned long long>(), values, thresh_p, want_edges, es, n_edges_out);
+  // length 0 cannot occur (no empty sequences)
+  return edges_from_counts(cnt.as<uint16_t>(), n, nbins, hist.as<unsigned long long>(), nw_code_values(nbins, 0.0), thresh_p, want_edges,
+                           es, n_edges_out);
 }
 
 static int mh_edges_core(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash,
@@ -1651,89 +1786,52 @@ static int mh_edges_core(const uint8_t *residues, const int64_t *offsets, int64_
   int64_t total, max_len;
   if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
-  DeviceInput in;
-  if ((rc = in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
-  const int64_t lds = sig_ld_for(n_hash);
-  DevBuf sig, planes, cnt, hist;
-  if ((rc = sig.alloc((size_t)n * lds * 4)) != DA_OK) return rc;
-  if ((rc = planes.alloc((size_t)mh_planes_words(n, n_hash) * 4)) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf cnt, hist;
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash)) != DA_OK) return rc;
   if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK) return rc;   // uint16 counts stay on the device
   const int nbins = n_hash + 1;
   if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;
   DA_HIP_TRY(hipMemset(hist.p, 0, (size_t)nbins * 8));
-  if ((rc = launch_minhash_signatures(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, n_hash, in.seeds.as<uint32_t>(),
-                                      sig.as<uint32_t>(), lds, nullptr)) != DA_OK) return rc;
-  int bits = 32;
-  {
-    DevBuf work;
-    const size_t wb = mh_planes_workspace_bytes(n, n_hash);
-    if ((rc = work.alloc(wb)) != DA_OK) return rc;
-    if ((rc = build_planes(sig.as<uint32_t>(), lds, n, n_hash, 0, work.p, wb, planes.as<uint32_t>(), &bits, nullptr)) != DA_OK)
-      return rc;
-    DA_HIP_TRY(hipStreamSynchronize(nullptr));   // the workspace is released here
-  }
-  if ((rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, 0, n, true, DA_OUT_COMPACT, cnt.p, n, nullptr, bits)) != DA_OK)
+  if ((rc = mh.build(k, 0, n_hash)) != DA_OK || (rc = mh.finish()) != DA_OK) return rc;
+  if ((rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, n_hash, 0, n, true, DA_OUT_COMPACT, cnt.p, n, nullptr, mh.bits)) != DA_OK)
     return rc;
   if ((rc = launch_upper_histogram(cnt.as<uint16_t>(), n, n, nbins, hist.as<unsigned long long>(), nullptr)) != DA_OK) return rc;
-  std::vector<double> values(nbins);
-  for (int b = 0; b < nbins; ++b) values[b] = (double)b / n_hash;          // src/minHash.cpp:174
-  return edges_from_counts(cnt.as<uint16_t>(), n, nbins, hist.as<unsigned long long>(), values, thresh_p, want_edges, es, n_edges_out);
+  return edges_from_counts(cnt.as<uint16_t>(), n, nbins, hist.as<unsigned long long>(), mh_code_values(n_hash), thresh_p, want_edges, es,
+                           n_edges_out);
 }
-
-// ---- public forms.  da_similarity_*_edges: size query (buffers NULL) or fill -- each call runs the whole pipeline.
-// da_similarity_*_edges_begin / da_edges_fetch / da_edges_free: ONE pass; the result waits in a handle until fetched.
-struct da_edges { EdgeSet es; int64_t n_edges = 0; };
 
 int da_similarity_nw_edges(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name,
                            int gap_open, int gap_ext, double thresh_p, double *threshold_out, int64_t *n_edges_out,
                            int64_t capacity, int32_t *ei, int32_t *ej, double *ew) {
-  if (!threshold_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  if ((ei || ej || ew) && (!ei || !ej || !ew)) return fail(DA_ERR_BAD_ARG, "NULL edge buffer");
-  EdgeSet es;
-  int64_t m = 0;
-  int rc = nw_edges_core(residues, offsets, n, matrix_name, gap_open, gap_ext, thresh_p, ei != nullptr, es, &m);
-  if (rc != DA_OK) return rc;
-  return edges_deliver(es, m, threshold_out, n_edges_out, capacity, ei, ej, ew);
+  return edges_run_deliver(threshold_out, n_edges_out, capacity, ei, ej, ew, [&](bool want_edges, EdgeSet &es, int64_t *m) {
+    return nw_edges_core(residues, offsets, n, matrix_name, gap_open, gap_ext, thresh_p, want_edges, es, m);
+  });
 }
 
 int da_similarity_mh_edges(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash,
                            const uint32_t *seeds, double thresh_p, double *threshold_out, int64_t *n_edges_out,
                            int64_t capacity, int32_t *ei, int32_t *ej, double *ew) {
-  if (!threshold_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  if ((ei || ej || ew) && (!ei || !ej || !ew)) return fail(DA_ERR_BAD_ARG, "NULL edge buffer");
-  EdgeSet es;
-  int64_t m = 0;
-  int rc = mh_edges_core(residues, offsets, n, k, n_hash, seeds, thresh_p, ei != nullptr, es, &m);
-  if (rc != DA_OK) return rc;
-  return edges_deliver(es, m, threshold_out, n_edges_out, capacity, ei, ej, ew);
+  return edges_run_deliver(threshold_out, n_edges_out, capacity, ei, ej, ew, [&](bool want_edges, EdgeSet &es, int64_t *m) {
+    return mh_edges_core(residues, offsets, n, k, n_hash, seeds, thresh_p, want_edges, es, m);
+  });
 }
 
 int da_similarity_mh_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash,
                                  const uint32_t *seeds, double thresh_p, da_edges **handle_out, double *threshold_out,
                                  int64_t *n_edges_out) {
-  if (!handle_out || !threshold_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  *handle_out = nullptr;
-  std::unique_ptr<da_edges> h(new da_edges);
-  int rc = mh_edges_core(residues, offsets, n, k, n_hash, seeds, thresh_p, true, h->es, &h->n_edges);
-  if (rc != DA_OK) return rc;
-  *threshold_out = h->es.threshold;
-  *n_edges_out = h->n_edges;
-  *handle_out = h.release();
-  return DA_OK;
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool want_edges, EdgeSet &es, int64_t *m) {
+    return mh_edges_core(residues, offsets, n, k, n_hash, seeds, thresh_p, want_edges, es, m);
+  });
 }
 
 int da_similarity_nw_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name,
                                  int gap_open, int gap_ext, double thresh_p, da_edges **handle_out, double *threshold_out,
                                  int64_t *n_edges_out) {
-  if (!handle_out || !threshold_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  *handle_out = nullptr;
-  std::unique_ptr<da_edges> h(new da_edges);
-  int rc = nw_edges_core(residues, offsets, n, matrix_name, gap_open, gap_ext, thresh_p, true, h->es, &h->n_edges);
-  if (rc != DA_OK) return rc;
-  *threshold_out = h->es.threshold;
-  *n_edges_out = h->n_edges;
-  *handle_out = h.release();
-  return DA_OK;
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool want_edges, EdgeSet &es, int64_t *m) {
+    return nw_edges_core(residues, offsets, n, matrix_name, gap_open, gap_ext, thresh_p, want_edges, es, m);
+  });
 }
 
 int da_edges_fetch(const da_edges *h, int64_t capacity, int32_t *ei, int32_t *ej, double *ew) {
@@ -1758,15 +1856,10 @@ int da_minhash_signatures(const uint8_t *residues, const int64_t *offsets, int64
   int64_t total, max_len;
   if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
-  DeviceInput in;
-  if ((rc = in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
-  const int64_t ld = sig_ld_for(n_hash);
-  DevBuf sig;
-  if ((rc = sig.alloc((size_t)n * ld * sizeof(uint32_t))) != DA_OK) return rc;
-  rc = launch_minhash_signatures(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, n_hash,
-                                 in.seeds.as<uint32_t>(), sig.as<uint32_t>(), ld, nullptr);
-  if (rc != DA_OK) return rc;
-  DA_HIP_TRY(hipMemcpy2D(sig_out, (size_t)n_hash * 4, sig.p, (size_t)ld * 4, (size_t)n_hash * 4, (size_t)n,
+  MhPlanes mh;
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash, false)) != DA_OK || (rc = mh.signatures(k, 0, n_hash)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy2D(sig_out, (size_t)n_hash * 4, mh.sig.p, (size_t)mh.lds * 4, (size_t)n_hash * 4, (size_t)n,
                          hipMemcpyDeviceToHost));
   return DA_OK;
 }
@@ -1785,23 +1878,16 @@ static int mh_host_chunked(const uint8_t *residues, const int64_t *offsets, int6
   if (rows_per_block(n, 4 + 2 + 8) < n)
     return fail(DA_ERR_UNSUPPORTED, "n_hash = %d (> 65535) needs the %lld x %lld count matrix resident in HBM (14 bytes per pair)", n_hash,
                 (long long)n, (long long)n);
-  DeviceInput in;
-  if ((rc = in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
-  const int64_t lds = sig_ld_for(CHUNK);
-  DevBuf sig, planes, work, acc, cnt, dout;
-  const size_t wb = mh_planes_workspace_bytes(n, CHUNK);
-  if ((rc = sig.alloc((size_t)n * lds * 4)) != DA_OK) return rc;
-  if ((rc = planes.alloc((size_t)mh_planes_words(n, CHUNK) * 4)) != DA_OK) return rc;
-  if ((rc = work.alloc(wb)) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf acc, cnt, dout;
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, CHUNK)) != DA_OK || (rc = mh.alloc_work()) != DA_OK) return rc;
   if ((rc = acc.alloc((size_t)n * (size_t)n * 4)) != DA_OK) return rc;
   if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK) return rc;
   for (int h0 = 0; h0 < n_hash; h0 += CHUNK) {
     const int nh = std::min(CHUNK, n_hash - h0);
-    if ((rc = launch_minhash_signatures(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, nh, in.seeds.as<uint32_t>() + h0,
-                                        sig.as<uint32_t>(), lds, nullptr)) != DA_OK) return rc;
-    int bits = 32;
-    if ((rc = build_planes(sig.as<uint32_t>(), lds, n, nh, 0, work.p, wb, planes.as<uint32_t>(), &bits, nullptr)) != DA_OK) return rc;
-    if ((rc = launch_mh_compare(planes.as<uint32_t>(), n, nh, 0, n, true, DA_OUT_COMPACT, cnt.p, n, nullptr, bits)) != DA_OK) return rc;
+    if ((rc = mh.build(k, h0, nh)) != DA_OK) return rc;
+    if ((rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, nh, 0, n, true, DA_OUT_COMPACT, cnt.p, n, nullptr, mh.bits)) != DA_OK) return rc;
     if ((rc = launch_acc_counts(acc.as<uint32_t>(), cnt.as<uint16_t>(), n * n, h0 == 0, nullptr)) != DA_OK) return rc;
   }
   if ((rc = dout.alloc((size_t)n * (size_t)n * 8)) != DA_OK) return rc;
@@ -1825,62 +1911,29 @@ static int mh_host_common(const uint8_t *residues, const int64_t *offsets, int64
   if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
   Trace tr("similarityMH host path");
-  DeviceInput in;
-  if ((rc = in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
-  const int64_t lds = sig_ld_for(n_hash);
-  DevBuf sig, planes;
-  if ((rc = sig.alloc((size_t)n * lds * sizeof(uint32_t))) != DA_OK) return rc;
-  if ((rc = planes.alloc((size_t)mh_planes_words(n, n_hash) * sizeof(uint32_t))) != DA_OK) return rc;
+  MhPlanes mh;
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash)) != DA_OK) return rc;
   tr.mark("upload + small allocations");
-  rc = launch_minhash_signatures(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, n_hash,
-                                 in.seeds.as<uint32_t>(), sig.as<uint32_t>(), lds, nullptr);
-  if (rc != DA_OK) return rc;
-  int bits = 32;
-  {
-    DevBuf work;
-    const size_t wb = mh_planes_workspace_bytes(n, n_hash);
-    if ((rc = work.alloc(wb)) != DA_OK) return rc;
-    if ((rc = build_planes(sig.as<uint32_t>(), lds, n, n_hash, 0, work.p, wb, planes.as<uint32_t>(), &bits, nullptr)) != DA_OK)
-      return rc;
-    DA_HIP_TRY(hipStreamSynchronize(nullptr));   // the workspace is released here
-  }
+  if ((rc = mh.build(k, 0, n_hash)) != DA_OK || (rc = mh.finish()) != DA_OK) return rc;
   tr.mark("signatures + codes");
-  if (kind == DA_OUT_F64 && row_begin == 0 && row_end == n && rows_per_block(n, sizeof(uint16_t)) >= n && !da::config().no_host_widen) {
-    // the float64 matrix for a HOST caller: counts (uint16) leave the device, a quarter of the bytes over PCIe, and the host
-    // widens them while copying -- count / n_hash is the same IEEE divide here as on the device (src/minHash.cpp:174)
-    DevBuf dcnt;
-    if ((rc = dcnt.alloc((size_t)n * (size_t)n * sizeof(uint16_t))) != DA_OK) return rc;
-    if ((rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, 0, n, true, DA_OUT_COMPACT, dcnt.p, n, nullptr, bits)) != DA_OK) return rc;
-    tr.mark("compare (uint16 counts)");
-    std::vector<double> table((size_t)n_hash + 1);
-    for (int c = 0; c <= n_hash; ++c) table[(size_t)c] = (double)c / (double)n_hash;
-    if ((rc = d2h_pipelined(out, dcnt.p, (size_t)n * (size_t)n * sizeof(uint16_t), table.data())) != DA_OK) return rc;
-    tr.mark("device -> host + widen");
-    return DA_OK;
-  }
+  if (kind == DA_OUT_F64 && row_begin == 0 && row_end == n && rows_per_block(n, sizeof(uint16_t)) >= n && !da::config().no_host_widen)
+    return codes_to_host(n, static_cast<double *>(out), mh_code_values(n_hash), tr, [&](void *d) {
+      const int rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, n_hash, 0, n, true, DA_OUT_COMPACT, d, n, nullptr, mh.bits);
+      if (rc == DA_OK) tr.mark("compare (uint16 counts)");
+      return rc;
+    });
   const size_t esz = kind == DA_OUT_F64 ? sizeof(double) : sizeof(uint16_t);
-  const int64_t rows_total = row_end - row_begin;
-  const int64_t blk = rows_per_block(n, esz);
-  const bool whole = (row_begin == 0 && row_end == n && blk >= n);
-  DevBuf dout;
-  if ((rc = dout.alloc((size_t)std::min(blk, rows_total) * (size_t)n * esz)) != DA_OK) return rc;
-  tr.mark(whole ? "result allocation (whole)" : "result allocation (row blocks)");
-  if (whole) {  // everything fits: compare only the upper triangle, store both halves
-    rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, 0, n, true, kind, dout.p, n, nullptr, bits);
-    if (rc != DA_OK) return rc;
-    tr.mark("compare");
-    if ((rc = d2h_pipelined(out, dout.p, (size_t)n * (size_t)n * esz)) != DA_OK) return rc;
-    tr.mark("device -> host");
-    return DA_OK;
-  }
-  for (int64_t r0 = row_begin; r0 < row_end; r0 += blk) {
-    const int64_t r1 = std::min(row_end, r0 + blk);
-    rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, r0, r1, false, kind, dout.p, n, nullptr, bits);
-    if (rc != DA_OK) return rc;
-    if ((rc = d2h_pipelined(static_cast<char *>(out) + (size_t)(r0 - row_begin) * (size_t)n * esz, dout.p,
-                            (size_t)(r1 - r0) * (size_t)n * esz)) != DA_OK) return rc;
-  }
-  return DA_OK;
+  bool whole = false;   // everything fits: compare only the upper triangle, store both halves
+  rc = rows_to_host(n, row_begin, row_end, esz, out, [&](int64_t b0, int64_t b1, void *d) {
+    whole = b0 == 0 && b1 == n;
+    if (b0 == row_begin) tr.mark(whole ? "result allocation (whole)" : "result allocation (row blocks)");
+    const int rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, n_hash, b0, b1, whole, kind, d, n, nullptr, mh.bits);
+    if (rc == DA_OK && whole) tr.mark("compare");
+    return rc;
+  });
+  if (rc == DA_OK && whole) tr.mark("device -> host");
+  return rc;
 }
 
 int da_similarity_mh(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash,
@@ -1935,61 +1988,37 @@ static int nw_host_common(const uint8_t *residues, const int64_t *offsets, int64
   if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
   Trace tr("similarityNW host path");
-  DeviceInput in;
-  if ((rc = in.upload(residues, offsets, n, total, nullptr, 0)) != DA_OK) return rc;
-  DevBuf codes, bad;
-  if ((rc = codes.alloc((size_t)total)) != DA_OK) return rc;
-  if ((rc = bad.alloc(sizeof(int32_t))) != DA_OK) return rc;
-  DA_HIP_TRY(hipMemset(bad.p, 0, sizeof(int32_t)));
-  if ((rc = launch_nw_encode(in.res.as<uint8_t>(), total, codes.as<uint8_t>(), bad.as<int32_t>(), nullptr)) != DA_OK)
-    return rc;
+  NwCodes nw;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+  const uint8_t *codes = nw.codes.as<uint8_t>();
+  const int64_t *d_off = nw.in.off.as<int64_t>();
 
-  const int64_t rows_total = row_end - row_begin;
   if (out_f64 && row_begin == 0 && row_end == n && max_len <= 127 && rows_per_block(n, sizeof(uint16_t)) >= n &&
       !da::config().no_host_widen) {
-    // as for similarityMH: the (matches << 8 | length) codes cross PCIe and the host divides (src/pairwiseSeqAlign.cpp:311)
-    DevBuf dcode;
-    if ((rc = dcode.alloc((size_t)n * (size_t)n * sizeof(uint16_t))) != DA_OK) return rc;
-    tr.mark("validation + upload + allocations");
-    if ((rc = nw_full_symmetric(codes.as<uint8_t>(), in.off.as<int64_t>(), n, total, max_len, mid, gap_open, gap_ext, DA_OUT_COMPACT,
-                                dcode.p, n, nullptr)) != DA_OK) return rc;
-    if (tr.on) {
-      const NwRoute &r = nw_route();
-      fprintf(stderr, "[dynaalign]   (plan %.2f ms, DP %.2f ms, expansion %.2f ms; %lld unique of %lld)\n", r.plan_ms, r.dp_ms, r.expand_ms,
-                (long long)r.unique, (long long)r.n);
-    }
-    tr.mark("codes on the device (uint16)");
-    std::vector<double> table(65536);
     const uint64_t nan_bits = 0xFFF8000000000000ULL;        // 0/0 as the reference's x86 host produces it
-    for (uint32_t v = 0; v < 65536; ++v) {
-      const uint32_t ln = v & 255u;
-      if (ln == 0) memcpy(&table[v], &nan_bits, 8);
-      else table[v] = (double)(v >> 8) / (double)ln;
-    }
-    rc = d2h_pipelined(out_f64, dcode.p, (size_t)n * (size_t)n * sizeof(uint16_t), table.data());
-    tr.mark("device -> host + widen");
-    return rc;
-  }
-  if (out_f64) {
-    const int64_t blk = rows_per_block(n, sizeof(double));
-    const bool whole = (row_begin == 0 && row_end == n && blk >= n);
-    DevBuf dout;
-    if ((rc = dout.alloc((size_t)std::min(blk, rows_total) * (size_t)n * sizeof(double))) != DA_OK) return rc;
-    for (int64_t r0 = row_begin; r0 < row_end; r0 += blk) {
-      const int64_t r1 = std::min(row_end, r0 + blk);
-      if (whole)
-        rc = nw_full_symmetric(codes.as<uint8_t>(), in.off.as<int64_t>(), n, total, max_len, mid, gap_open, gap_ext, DA_OUT_F64,
-                               dout.p, n, nullptr);
-      else
-        rc = launch_nw(codes.as<uint8_t>(), in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, r0, r1,
-                       false, DA_OUT_F64, dout.p, n, nullptr, 0, nullptr);
+    double nan;
+    memcpy(&nan, &nan_bits, 8);
+    return codes_to_host(n, out_f64, nw_code_values(65536, nan), tr, [&](void *d) -> int {
+      tr.mark("validation + upload + allocations");
+      const int rc = nw_full_symmetric(codes, d_off, n, total, max_len, mid, gap_open, gap_ext, DA_OUT_COMPACT, d, n, nullptr);
       if (rc != DA_OK) return rc;
-      if ((rc = d2h_pipelined(out_f64 + (size_t)(r0 - row_begin) * (size_t)n, dout.p,
-                              (size_t)(r1 - r0) * (size_t)n * sizeof(double))) != DA_OK) return rc;
-    }
-    return DA_OK;
+      if (tr.on) {
+        const NwRoute &r = nw_route();
+        fprintf(stderr, "[dynaalign]   (plan %.2f ms, DP %.2f ms, expansion %.2f ms; %lld unique of %lld)\n", r.plan_ms, r.dp_ms, r.expand_ms,
+                (long long)r.unique, (long long)r.n);
+      }
+      tr.mark("codes on the device (uint16)");
+      return DA_OK;
+    });
   }
+  if (out_f64)
+    return rows_to_host(n, row_begin, row_end, sizeof(double), out_f64, [&](int64_t b0, int64_t b1, void *d) {
+      if (b0 == 0 && b1 == n)   // everything fits
+        return nw_full_symmetric(codes, d_off, n, total, max_len, mid, gap_open, gap_ext, DA_OUT_F64, d, n, nullptr);
+      return launch_nw(codes, d_off, n, max_len, mid, gap_open, gap_ext, b0, b1, false, DA_OUT_F64, d, n, nullptr, 0, nullptr);
+    });
   // integer outputs: 32-bit packed (matches<<16|len) + score, unpacked on the host
+  const int64_t rows_total = row_end - row_begin;
   const int64_t blk = rows_per_block(n, sizeof(uint32_t) + sizeof(int32_t));
   DevBuf dpk, dsc;
   const int64_t brow = std::min(blk, rows_total);
@@ -1999,7 +2028,7 @@ static int nw_host_common(const uint8_t *residues, const int64_t *offsets, int64
   for (int64_t r0 = row_begin; r0 < row_end; r0 += blk) {
     const int64_t r1 = std::min(row_end, r0 + blk);
     const bool whole = (r0 == 0 && r1 == n);
-    rc = launch_nw(codes.as<uint8_t>(), in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, r0, r1, whole,
+    rc = launch_nw(codes, d_off, n, max_len, mid, gap_open, gap_ext, r0, r1, whole,
                    DA_OUT_PACK32, dpk.p, n, score_out ? dsc.as<int32_t>() : nullptr, n, nullptr);
     if (rc != DA_OK) return rc;
     const size_t cnt = (size_t)(r1 - r0) * (size_t)n, base = (size_t)(r0 - row_begin) * (size_t)n;
@@ -2114,8 +2143,6 @@ struct Multi {
   double t_entry = 0.0, comm_setup_ms = 0.0;       // entry of the C call; ncclCommInitAll (first call with this device list)
   std::unique_lock<std::mutex> comm_use;           // held while this call uses the cached communicators
 };
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // RCCL communicators are kept per device list: ncclCommInitAll costs far more than the exchange it serves, and the glue calls
 // once per recursion level.  One call at a time uses them (comm_use_mutex); da_release_device_memory() destroys them.
@@ -2259,6 +2286,49 @@ int exchange_blocks(Multi &m, int p, const void *mine, size_t bytes, void *gathe
   return DA_OK;
 }
 
+// da_debug_comm_cache_state(force_fail != 0): rank 0 of the next DA_EXCHANGE_ALLGATHER call fails right after its compute phase
+std::atomic<int> g_force_exchange_error{0};
+
+// Rank p of a sharded mode (ALLGATHER, PEERCOPY) after its setup, which returned rc: compute(local, block) fills this rank's cyclic
+// upper-triangle tiles into local (sg.rows x sg.W uint16, zeroed) and leaves the block to exchange in `block` -- a buffer of
+// pack_bytes, or local itself when pack_bytes is 0; after the exchange, finalize(gathered, dout) builds the full n x n float64 matrix
+// from every rank's block, and this rank copies its rows of it to out.  A rank whose setup or compute failed still arrives at the
+// first barrier: every rank then learns of the failure there and returns.
+template <typename Compute, typename Finalize>
+int sharded_rank(Multi &m, int p, int rc, int64_t n, const ShardGeom &sg, size_t pack_bytes, double *out, Compute compute,
+                 Finalize finalize) {
+  const size_t local_bytes = (size_t)sg.rows * (size_t)sg.W * 2, bytes = pack_bytes ? pack_bytes : local_bytes;
+  DevBuf local, pk, gathered, dout;
+  int64_t r0, r1;
+  row_split(n, m.P, p, &r0, &r1);
+  double t = now_ms();
+  if (rc == DA_OK) do {
+    if ((rc = local.alloc(local_bytes)) != DA_OK) break;
+    if (pack_bytes && (rc = pk.alloc(pack_bytes)) != DA_OK) break;
+    if ((rc = gathered.alloc(bytes * (size_t)m.P)) != DA_OK) break;
+    if ((rc = dout.alloc((size_t)n * (size_t)n * sizeof(double))) != DA_OK) break;
+    if (hipMemsetAsync(local.p, 0, local_bytes, nullptr) != hipSuccess) { rc = fail(DA_ERR_HIP, "hipMemsetAsync failed"); break; }
+    rc = compute(local.p, pack_bytes ? pk.p : local.p);
+  } while (0);
+  m.ms[p][PH_COMPUTE] = now_ms() - t;
+  m.block[p] = pack_bytes ? pk.p : local.p;
+  if (p == 0 && rc == DA_OK && m.exchange == DA_EXCHANGE_ALLGATHER && g_force_exchange_error.exchange(0))   // (test hook)
+    rc = fail(DA_ERR_HIP, "forced exchange failure (test hook)");
+  if (!m.bar->arrive(rc == DA_OK)) return rc;     // every block is complete (and nobody failed) before anyone exchanges
+  t = now_ms();
+  rc = exchange_blocks(m, p, m.block[p], bytes, gathered.p);
+  m.ms[p][PH_EXCHANGE] = now_ms() - t;
+  if (!m.bar->arrive(rc == DA_OK)) return rc;     // peers have finished reading my block before it is freed
+  t = now_ms();
+  if ((rc = finalize(gathered.p, dout.as<double>())) != DA_OK) return rc;
+  if ((rc = sync_or_fail("finalize kernel failed")) != DA_OK) return rc;
+  m.ms[p][PH_FINALIZE] = now_ms() - t;
+  t = now_ms();
+  if (r1 > r0) rc = d2h_pipelined(out + (size_t)r0 * (size_t)n, dout.as<double>() + (size_t)r0 * (size_t)n, (size_t)(r1 - r0) * (size_t)n * sizeof(double));
+  m.ms[p][PH_D2H] = now_ms() - t;
+  return rc;
+}
+
 }  // namespace
 
 size_t destroy_cached_comms() {
@@ -2275,8 +2345,8 @@ size_t destroy_cached_comms() {
 extern "C" {
 
 /* tests: {cached device lists, evictions after a failed ALLGATHER call}; with force_fail != 0 the NEXT DA_EXCHANGE_ALLGATHER call's rank 0
- * fails right after its compute phase (before the collective) -- every rank then skips the exchange and the cache entry must go */
-static std::atomic<int> g_force_exchange_error{0};
+ * (similarityMH or similarityNW) fails right after its compute phase (before the collective) -- every rank then skips the exchange and
+ * the cache entry must go */
 int da_debug_comm_cache_state(int force_fail, size_t *out2) {
   std::lock_guard<std::mutex> u(da::comm_use_mutex());
   if (out2) { out2[0] = da::comm_cache().size(); out2[1] = da::g_comm_evictions; }
@@ -2310,77 +2380,34 @@ int da_similarity_mh_opts(const uint8_t *residues, const int64_t *offsets, int64
   const ShardGeom sg = shard_geom(n, m.P, 128);
   const size_t packed = (size_t)shard_packed_bytes(sg, vbits);
   return run_ranks(m, opts, [&](int p) -> int {
-    int rc = DA_OK;
-    bool ok;
-    double t = now_ms();
-    DeviceInput in;
-    DevBuf sig, planes, local, pk, gathered, dout;
-    int bits = 32;
-    const int64_t lds = sig_ld_for(n_hash);
-    int64_t r0, r1;
-    row_split(n, m.P, p, &r0, &r1);
+    const double t = now_ms();
+    MhPlanes mh;
+    int rc;
     do {   // setup: upload + K1 + K1b on this device
-      if ((rc = in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) break;
-      if ((rc = sig.alloc((size_t)n * lds * 4)) != DA_OK) break;
-      if ((rc = planes.alloc((size_t)mh_planes_words(n, n_hash) * 4)) != DA_OK) break;
-      if ((rc = launch_minhash_signatures(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, n_hash, in.seeds.as<uint32_t>(),
-                                          sig.as<uint32_t>(), lds, nullptr)) != DA_OK) break;
-      DevBuf work;
-      const size_t wb = mh_planes_workspace_bytes(n, n_hash);
-      if ((rc = work.alloc(wb)) != DA_OK) break;
-      if ((rc = build_planes(sig.as<uint32_t>(), lds, n, n_hash, 0, work.p, wb, planes.as<uint32_t>(), &bits, nullptr)) != DA_OK) break;
-      if (hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(DA_ERR_HIP, "stream synchronisation failed");
+      if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) break;
+      if ((rc = mh.alloc(n, n_hash)) != DA_OK || (rc = mh.build(k, 0, n_hash)) != DA_OK) break;
+      if (mh.finish() != DA_OK) rc = fail(DA_ERR_HIP, "stream synchronisation failed");
     } while (0);
     m.ms[p][PH_SETUP] = now_ms() - t;
-    if (m.exchange == DA_EXCHANGE_ROWS) {
-      if (rc != DA_OK || r1 <= r0) return rc;
-      const int64_t blk = rows_per_block(n, sizeof(double));
-      if ((rc = dout.alloc((size_t)std::min(blk, r1 - r0) * (size_t)n * sizeof(double))) != DA_OK) return rc;
-      for (int64_t b0 = r0; b0 < r1 && rc == DA_OK; b0 += blk) {
-        const int64_t b1 = std::min(r1, b0 + blk);
-        t = now_ms();
-        if ((rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, b0, b1, false, DA_OUT_F64, dout.p, n, nullptr, bits)) != DA_OK) break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = fail(DA_ERR_HIP, "compare kernel failed"); break; }
-        m.ms[p][PH_COMPUTE] += now_ms() - t;
-        t = now_ms();
-        rc = d2h_pipelined(out + (size_t)b0 * (size_t)n, dout.p, (size_t)(b1 - b0) * (size_t)n * sizeof(double));
-        m.ms[p][PH_D2H] += now_ms() - t;
-      }
-      return rc;
-    }
-    // sharded modes: cyclic upper-triangle tiles -> packed block -> exchange -> full matrix on this device
-    t = now_ms();
-    if (rc == DA_OK) do {
-      if ((rc = local.alloc((size_t)sg.rows * (size_t)sg.W * 2)) != DA_OK) break;
-      if ((rc = pk.alloc(packed)) != DA_OK) break;
-      if ((rc = gathered.alloc(packed * (size_t)m.P)) != DA_OK) break;
-      if ((rc = dout.alloc((size_t)n * (size_t)n * sizeof(double))) != DA_OK) break;
-      if (hipMemsetAsync(local.p, 0, (size_t)sg.rows * (size_t)sg.W * 2, nullptr) != hipSuccess) { rc = fail(DA_ERR_HIP, "hipMemsetAsync failed"); break; }
-      if ((int64_t)p * 128 < n)
-        if ((rc = launch_mh_compare(planes.as<uint32_t>(), n, n_hash, (int64_t)p * 128, n, false, DA_OUT_COMPACT, local.p, sg.W, nullptr,
-                                    bits, m.P, true, sg.Q, sg.W)) != DA_OK) break;
-      if ((rc = launch_pack_shard(local.as<uint16_t>(), sg.W, sg, vbits, pk.as<uint8_t>(), nullptr)) != DA_OK) break;
-      if (hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(DA_ERR_HIP, "shard compare failed");
-    } while (0);
-    m.ms[p][PH_COMPUTE] = now_ms() - t;
-    m.block[p] = pk.p;
-    if (p == 0 && rc == DA_OK && m.exchange == DA_EXCHANGE_ALLGATHER && g_force_exchange_error.exchange(0))   // (test hook, da_debug_comm_cache_state)
-      rc = fail(DA_ERR_HIP, "forced exchange failure (test hook)");
-    ok = m.bar->arrive(rc == DA_OK);                 // every block is complete (and nobody failed) before anyone exchanges
-    if (!ok) return rc;
-    t = now_ms();
-    rc = exchange_blocks(m, p, pk.p, packed, gathered.p);
-    m.ms[p][PH_EXCHANGE] = now_ms() - t;
-    ok = m.bar->arrive(rc == DA_OK);                 // peers have finished reading my block before it is freed
-    if (!ok) return rc;
-    t = now_ms();
-    if ((rc = launch_finalize_packed(gathered.as<uint8_t>(), sg, vbits, n_hash, dout.as<double>(), n, nullptr)) != DA_OK) return rc;
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(DA_ERR_HIP, "finalize kernel failed");
-    m.ms[p][PH_FINALIZE] = now_ms() - t;
-    t = now_ms();
-    if (r1 > r0) rc = d2h_pipelined(out + (size_t)r0 * (size_t)n, dout.as<double>() + (size_t)r0 * (size_t)n, (size_t)(r1 - r0) * (size_t)n * sizeof(double));
-    m.ms[p][PH_D2H] = now_ms() - t;
-    return rc;
+    if (m.exchange != DA_EXCHANGE_ROWS)   // cyclic upper-triangle tiles -> packed block -> exchange -> full matrix on this device
+      return sharded_rank(m, p, rc, n, sg, packed, out, [&](void *local, void *pk) {
+        int rc;
+        if ((int64_t)p * 128 < n &&
+            (rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, n_hash, (int64_t)p * 128, n, false, DA_OUT_COMPACT, local, sg.W, nullptr,
+                                    mh.bits, m.P, true, sg.Q, sg.W)) != DA_OK) return rc;
+        if ((rc = launch_pack_shard(static_cast<const uint16_t *>(local), sg.W, sg, vbits, static_cast<uint8_t *>(pk), nullptr)) != DA_OK)
+          return rc;
+        return sync_or_fail("shard compare failed");
+      }, [&](const void *gathered, double *dout) {
+        return launch_finalize_packed(static_cast<const uint8_t *>(gathered), sg, vbits, n_hash, dout, n, nullptr);
+      });
+    int64_t r0, r1;
+    row_split(n, m.P, p, &r0, &r1);
+    if (rc != DA_OK || r1 <= r0) return rc;
+    return rows_to_host(n, r0, r1, sizeof(double), out + (size_t)r0 * (size_t)n, [&](int64_t b0, int64_t b1, void *d) {
+      const int rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, n_hash, b0, b1, false, DA_OUT_F64, d, n, nullptr, mh.bits);
+      return rc != DA_OK ? rc : sync_or_fail("compare kernel failed");
+    }, &m.ms[p][PH_COMPUTE], &m.ms[p][PH_D2H]);
   });
 }
 
@@ -2406,67 +2433,28 @@ int da_similarity_nw_opts(const uint8_t *residues, const int64_t *offsets, int64
       return nw_host_common(residues, offsets, n, matrix_name, gap_open, gap_ext, 0, n, out, nullptr, nullptr, nullptr);
     });
   const ShardGeom sg = shard_geom(n, m.P, 128);
-  const size_t blk_bytes = (size_t)sg.rows * (size_t)sg.W * 2;
   return run_ranks(m, opts, [&](int p) -> int {
-    int rc = DA_OK;
-    bool ok;
-    double t = now_ms();
-    DeviceInput in;
-    DevBuf codes, bad, local, gathered, dout;
+    const double t = now_ms();
+    NwCodes nw;
+    int rc = nw.upload(residues, offsets, n, total);
+    m.ms[p][PH_SETUP] = now_ms() - t;
+    const uint8_t *codes = nw.codes.as<uint8_t>();
+    const int64_t *d_off = nw.in.off.as<int64_t>();
+    if (m.exchange != DA_EXCHANGE_ROWS)
+      return sharded_rank(m, p, rc, n, sg, 0, out, [&](void *local, void *) {
+        const int rc = launch_nw(codes, d_off, n, max_len, mid, gap_open, gap_ext, 0, n, false, DA_OUT_COMPACT, local, sg.W, nullptr, 0,
+                                 nullptr, p, m.P);
+        return rc != DA_OK ? rc : sync_or_fail("NW shard kernel failed");
+      }, [&](const void *gathered, double *dout) {
+        return launch_finalize_sharded(static_cast<const uint16_t *>(gathered), sg.W, sg, true, 0, dout, n, nullptr);
+      });
     int64_t r0, r1;
     row_split(n, m.P, p, &r0, &r1);
-    do {
-      if ((rc = in.upload(residues, offsets, n, total, nullptr, 0)) != DA_OK) break;
-      if ((rc = codes.alloc((size_t)total)) != DA_OK) break;
-      if ((rc = bad.alloc(sizeof(int32_t))) != DA_OK) break;
-      if (hipMemsetAsync(bad.p, 0, sizeof(int32_t), nullptr) != hipSuccess) { rc = fail(DA_ERR_HIP, "hipMemsetAsync failed"); break; }
-      rc = launch_nw_encode(in.res.as<uint8_t>(), total, codes.as<uint8_t>(), bad.as<int32_t>(), nullptr);
-    } while (0);
-    m.ms[p][PH_SETUP] = now_ms() - t;
-    if (m.exchange == DA_EXCHANGE_ROWS) {
-      if (rc != DA_OK || r1 <= r0) return rc;
-      const int64_t blk = rows_per_block(n, sizeof(double));
-      if ((rc = dout.alloc((size_t)std::min(blk, r1 - r0) * (size_t)n * sizeof(double))) != DA_OK) return rc;
-      for (int64_t b0 = r0; b0 < r1 && rc == DA_OK; b0 += blk) {
-        const int64_t b1 = std::min(r1, b0 + blk);
-        t = now_ms();
-        if ((rc = launch_nw(codes.as<uint8_t>(), in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, false, DA_OUT_F64,
-                            dout.p, n, nullptr, 0, nullptr)) != DA_OK) break;
-        if (hipStreamSynchronize(nullptr) != hipSuccess) { rc = fail(DA_ERR_HIP, "NW kernel failed"); break; }
-        m.ms[p][PH_COMPUTE] += now_ms() - t;
-        t = now_ms();
-        rc = d2h_pipelined(out + (size_t)b0 * (size_t)n, dout.p, (size_t)(b1 - b0) * (size_t)n * sizeof(double));
-        m.ms[p][PH_D2H] += now_ms() - t;
-      }
-      return rc;
-    }
-    t = now_ms();
-    if (rc == DA_OK) do {
-      if ((rc = local.alloc(blk_bytes)) != DA_OK) break;
-      if ((rc = gathered.alloc(blk_bytes * (size_t)m.P)) != DA_OK) break;
-      if ((rc = dout.alloc((size_t)n * (size_t)n * sizeof(double))) != DA_OK) break;
-      if (hipMemsetAsync(local.p, 0, blk_bytes, nullptr) != hipSuccess) { rc = fail(DA_ERR_HIP, "hipMemsetAsync failed"); break; }
-      if ((rc = launch_nw(codes.as<uint8_t>(), in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, false, DA_OUT_COMPACT,
-                          local.p, sg.W, nullptr, 0, nullptr, p, m.P)) != DA_OK) break;
-      if (hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(DA_ERR_HIP, "NW shard kernel failed");
-    } while (0);
-    m.ms[p][PH_COMPUTE] = now_ms() - t;
-    m.block[p] = local.p;
-    ok = m.bar->arrive(rc == DA_OK);
-    if (!ok) return rc;
-    t = now_ms();
-    rc = exchange_blocks(m, p, local.p, blk_bytes, gathered.p);
-    m.ms[p][PH_EXCHANGE] = now_ms() - t;
-    ok = m.bar->arrive(rc == DA_OK);
-    if (!ok) return rc;
-    t = now_ms();
-    if ((rc = launch_finalize_sharded(gathered.as<uint16_t>(), sg.W, sg, true, 0, dout.as<double>(), n, nullptr)) != DA_OK) return rc;
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(DA_ERR_HIP, "finalize kernel failed");
-    m.ms[p][PH_FINALIZE] = now_ms() - t;
-    t = now_ms();
-    if (r1 > r0) rc = d2h_pipelined(out + (size_t)r0 * (size_t)n, dout.as<double>() + (size_t)r0 * (size_t)n, (size_t)(r1 - r0) * (size_t)n * sizeof(double));
-    m.ms[p][PH_D2H] = now_ms() - t;
-    return rc;
+    if (rc != DA_OK || r1 <= r0) return rc;
+    return rows_to_host(n, r0, r1, sizeof(double), out + (size_t)r0 * (size_t)n, [&](int64_t b0, int64_t b1, void *d) {
+      const int rc = launch_nw(codes, d_off, n, max_len, mid, gap_open, gap_ext, b0, b1, false, DA_OUT_F64, d, n, nullptr, 0, nullptr);
+      return rc != DA_OK ? rc : sync_or_fail("NW kernel failed");
+    }, &m.ms[p][PH_COMPUTE], &m.ms[p][PH_D2H]);
   });
 }
 
