@@ -670,7 +670,7 @@ static int count_unique(const uint8_t *d_bytes, const int64_t *d_offsets, int64_
   *U = (int64_t)M + S; return DA_OK;
 }
 enum MhForm { MH_DIRECT = 0, MH_TILES = 1, MH_SPARSE = 2, MH_TILES_PIPE = 3, MH_ROWS = 4, MH_ROWS_PIPE = 5 };   // da_mh_last_route's `taken`
-struct MhRoute { int64_t n = 0, unique = 0, hybrid_pairs = -1; int taken = MH_DIRECT, plane_bits = 0, chunks = 0, expand_launches = 0, hybrid_bits_before = 0; float ms[6] = {0, 0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, column gather, k_expand_rows, diagonal / border tiles
+struct MhRoute { int64_t n = 0, unique = 0, hybrid_pairs = -1; int taken = MH_DIRECT, plane_bits = 0, chunks = 0, expand_launches = 0, hybrid_bits_before = 0; bool packed_table = false; float ms[6] = {0, 0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, column gather, k_expand_rows, diagonal / border tiles
 static MhRoute &mh_route() { static thread_local MhRoute r; return r; }
 // the seven events of one call: [0] call, [1] plan done, [2] compare operand done, [3 ..] the form's own
 struct MhEvents {
@@ -812,10 +812,12 @@ static int mh_codes(const uint8_t *d_res, const int64_t *d_off, int64_t m, int k
   if (c->split()) { c->bits = 8; return launch_ids_to_planes(c->pwork.p, m, n_hash, 8, planes, stream, c->adm.dense); }
   return planes_from(dict, sig, lds, m, n_hash, min_bits, c->pwork.p, planes, &c->bits, stream);
 }
-// what the forms share; duplicate route: the U x U count table (ld_d) and the expansion's scratch (copy lists / column-gathered table)
+// what the forms share; duplicate route: the U x U count table (ld_d) and the expansion's scratch (copy lists / column-gathered table).
+// pk: the table is packed to 9 bits per count (da_common.hpp pk_*, ld_d = its low plane's bytes): the row forms with n_hash <= 511, 12 planes
+// and no heavy / rare split (k_hy_fixup adds into uint16 entries)
 struct MhCall {
   int64_t n; int n_hash; double *out; int64_t ld; hipStream_t stream; MhRoute &route; const MhEvents &ev; const MhCodes &c; const MhDedup &d;
-  uint16_t *dtab = nullptr; int64_t ld_d = 0; void *ex = nullptr;
+  uint16_t *dtab = nullptr; int64_t ld_d = 0; void *ex = nullptr; bool pk = false;
 };
 constexpr int MH_NO_PIPE = -1;   // a pipelined form's return when no side stream / events are to be had: the one-stream form needs none
 // the end of every form: its last event on the caller's stream, the sync after which the buffers may go back to the cache, the route report
@@ -861,10 +863,12 @@ static int mh_one_stream(const MhCall &k) {
   const MhCodes &c = k.c;
   int rc;
   if (c.split() && (rc = c.lists(k.stream)) != DA_OK) return rc;
-  if ((rc = launch_mh_compare(c.planes.as<uint32_t>(), k.d.U, k.n_hash, 0, k.d.U, true, DA_OUT_COMPACT, k.dtab, k.ld_d, k.stream, c.bits)) != DA_OK) return rc;
+  if ((rc = k.pk ? launch_mh_compare_pk(c.planes.as<uint32_t>(), k.d.U, k.n_hash, reinterpret_cast<uint8_t *>(k.dtab), k.stream)
+                 : launch_mh_compare(c.planes.as<uint32_t>(), k.d.U, k.n_hash, 0, k.d.U, true, DA_OUT_COMPACT, k.dtab, k.ld_d, k.stream, c.bits)) != DA_OK)
+    return rc;
   if (c.split() && (rc = c.fixup(DA_OUT_COMPACT, k.dtab, k.ld_d, k.stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipEventRecord(k.ev[3], k.stream));
-  if ((rc = k.d.rows ? launch_expand_stream(k.dtab, k.ld_d, k.d.p.uidx, k.n, k.d.U, k.n_hash, k.out, k.ld, k.ex, k.stream, k.ev[4])
+  if ((rc = k.d.rows ? launch_expand_stream(k.dtab, k.ld_d, k.d.p.uidx, k.n, k.d.U, k.n_hash, k.out, k.ld, k.ex, k.stream, k.ev[4], k.pk)
                      : launch_expand_unique(k.dtab, k.ld_d, k.d.p.uidx, k.n, DA_OUT_F64, false, k.n_hash, k.out, k.ld, k.stream, 0,
                                             static_cast<uint16_t *>(k.ex), k.d.p.ufirst, k.d.U, k.ev[4], k.ev[5])) != DA_OK) return rc;
   k.route.chunks = k.route.expand_launches = 1;
@@ -893,7 +897,7 @@ static int mh_rows_pipe(const MhCall &k) {
   hipEvent_t *pe = pr->ev.data();                                  // per chunk: table rows done, rows begin / end; [3 C]: lists done
   // beside the first band on the side stream: the table's diagonal / border tiles and the copy lists, both on the caller's stream
   DA_HIP_TRY(hipStreamWaitEvent(pr->side, k.ev[2], 0));
-  if ((rc = launch_mh_compare_edges_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, stream, c.bits)) != DA_OK) return rc;
+  if ((rc = launch_mh_compare_edges_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, stream, c.bits, k.pk)) != DA_OK) return rc;
   if ((rc = launch_expand_stream_lists(k.d.p.uidx, k.n, U, k.ex, stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipEventRecord(pe[3 * C], stream));
   if (c.split()) {     // the rare values' lists behind them on the caller's stream (on the idle expansion stream instead: 17.3 vs 16.6 ms, round 4)
@@ -902,7 +906,8 @@ static int mh_rows_pipe(const MhCall &k) {
   }
   if (alt) { DA_HIP_TRY(hipStreamWaitEvent(pr->alt[0], pe[3 * C], 0)); DA_HIP_TRY(hipStreamWaitEvent(pr->alt[1], pe[3 * C], 0)); }
   for (size_t ci = 0; ci < C; ++ci) {
-    if ((rc = launch_mh_compare_bands_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, cuts[ci], cuts[ci + 1], ci == 0 ? 4 : wg, pr->side, c.bits)) != DA_OK) return rc;
+    if ((rc = launch_mh_compare_bands_u16(c.planes.as<uint32_t>(), U, k.n_hash, k.dtab, k.ld_d, cuts[ci], cuts[ci + 1], ci == 0 ? 4 : wg, pr->side, c.bits,
+                                          k.pk)) != DA_OK) return rc;
     if (c.split()) {     // the rare values' incidences of these tile rows (direct + mirrored elements), once the edge tiles and the lists are there
       if (ci == 0) { DA_HIP_TRY(hipStreamWaitEvent(pr->side, pe[3 * C], 0)); DA_HIP_TRY(hipStreamWaitEvent(pr->side, pe[3 * C + 1], 0)); }
       if ((rc = c.fixup(DA_OUT_COMPACT, k.dtab, k.ld_d, pr->side, cuts[ci] * 8, cuts[ci + 1] * 8)) != DA_OK) return rc;
@@ -912,7 +917,7 @@ static int mh_rows_pipe(const MhCall &k) {
     DA_HIP_TRY(hipStreamWaitEvent(es, pe[3 * ci], 0));
     DA_HIP_TRY(hipEventRecord(pe[3 * ci + 1], es));
     if ((rc = launch_expand_stream_rows(k.dtab, k.ld_d, k.d.p.uidx, k.n, U, k.n_hash, k.out, k.ld, k.ex, cuts[ci] * 1024, cuts[ci + 1] * 1024, es,
-                                        (int)ci)) != DA_OK) return rc;
+                                        (int)ci, k.pk)) != DA_OK) return rc;
     DA_HIP_TRY(hipEventRecord(pe[3 * ci + 2], es));
   }
   if (alt) for (size_t ci = (C >= 2 ? C - 2 : 0); ci < C; ++ci) DA_HIP_TRY(hipStreamWaitEvent(stream, pe[3 * ci + 2], 0));
@@ -1021,8 +1026,10 @@ static int mh_full_symmetric(const uint8_t *d_res, const int64_t *d_off, int64_t
   // The expansion has two kernel families and each a pipelined form (DYNAALIGN_MH_EXPAND = rowspipe | rows | pipe | tiles; default: the first
   // whose shape test passes; DYNAALIGN_MH_NO_PIPE=1 takes the pipelined forms out)
   DevBuf dtab, ex;
-  call.ld_d = (d.U + 7) / 8 * 8;
-  if ((rc = dtab.alloc((size_t)d.U * (size_t)call.ld_d * 2)) != DA_OK) return rc;
+  call.pk = d.rows && !c.split() && mh_compare_pk_ok(d.U, n_hash, c.bits);
+  route.packed_table = call.pk;
+  call.ld_d = call.pk ? pk_lo_bytes(d.U) : (d.U + 7) / 8 * 8;
+  if ((rc = dtab.alloc(call.pk ? pk_table_bytes(d.U) : (size_t)d.U * (size_t)call.ld_d * 2)) != DA_OK) return rc;
   if ((rc = ex.alloc(d.rows ? expand_stream_scratch_bytes(n, d.U) : expand_rows_workspace_bytes(n, d.U, DA_OUT_F64, false, n_hash, 0))) != DA_OK) return rc;
   call.dtab = dtab.as<uint16_t>(); call.ex = ex.p;
   // (the pipelined tile form leaves only diagonal / border tiles to launch_expand_unique: the output must qualify for the streaming passes)
@@ -1053,6 +1060,13 @@ int da_mh_last_route_split(int64_t *rare_incidences_out, int *plane_bits_without
   const MhRoute &r = mh_route();
   if (rare_incidences_out) *rare_incidences_out = r.hybrid_pairs;
   if (plane_bits_without_out) *plane_bits_without_out = r.hybrid_bits_before;
+  return DA_OK;
+}
+
+// tests: whether the calling thread's last similarityMH call kept its count table packed (9 bits per count; the row forms with n_hash <= 511)
+extern "C" int da_debug_mh_last_table_packed(int *packed_out) {
+  if (!packed_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *packed_out = mh_route().packed_table ? 1 : 0;
   return DA_OK;
 }
 

@@ -136,6 +136,14 @@ inline int64_t mh_planes_words(int64_t n, int n_hash) {
   return raw > p16 ? raw : p16;
 }
 
+// ---- the packed U x U count table of the row expansion (n_hash <= 511: every count fits 9 bits) -------------------------------
+// Row r holds pk_lo_bytes(U) low bytes (column c at byte c), then one byte of bit 8 per 8 columns (column c at bit c & 7 of byte c >> 3):
+// exactly k_expand_stream's LDS image of the row.  The low plane is a whole number of 128-column tiles, so a compare tile owns one 128-byte
+// piece of the low plane and one 16-byte piece of the bit plane of each of its rows; the row stride stays a multiple of 16 bytes.
+__host__ __device__ inline int64_t pk_lo_bytes(int64_t U) { return (U + 127) / 128 * 128; }
+__host__ __device__ inline int64_t pk_row_bytes(int64_t lo_bytes) { return lo_bytes + lo_bytes / 8; }
+inline size_t pk_table_bytes(int64_t U) { return (size_t)U * (size_t)pk_row_bytes(pk_lo_bytes(U)); }
+
 // Kernel launchers implemented in the .hip translation units.  All are
 // asynchronous on `stream`; argument checking is done by the C-ABI layer.
 int launch_minhash_signatures(const uint8_t *d_res, const int64_t *d_off, int64_t n,
@@ -149,9 +157,14 @@ int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
 int64_t mh_sym_bands(int64_t n);
 int64_t mh_sym_band_prefix(int64_t n, int64_t band);
 bool mh_compare_bands_ok(int64_t n, int n_hash, int plane_bits, const void *d_out, int64_t ld);
+// (pk: d_out is the packed table (pk_*), ld its pk_lo_bytes; 12 planes only)
 int launch_mh_compare_bands_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, int64_t band_begin,
-                                int64_t band_end, int wg_per_cu, hipStream_t stream, int plane_bits = 12);
-int launch_mh_compare_edges_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, hipStream_t stream, int plane_bits = 12);
+                                int64_t band_end, int wg_per_cu, hipStream_t stream, int plane_bits = 12, bool pk = false);
+int launch_mh_compare_edges_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, hipStream_t stream, int plane_bits = 12,
+                                bool pk = false);
+// the whole symmetric 12-plane compare into the packed table, one tile per workgroup (the one-stream row form)
+bool mh_compare_pk_ok(int64_t n, int n_hash, int plane_bits);
+int launch_mh_compare_pk(const uint32_t *d_planes, int64_t n, int n_hash, uint8_t *d_tab, hipStream_t stream);
 // minhash_kernels.hip, SPARSE route of the symmetric float64 compare (inputs whose signatures rarely agree): see the kernels' header comment
 size_t mh_sparse_pairs_limit();
 int launch_mh_sparse_count(const uint16_t *d_idsT, int64_t ld_ids, int64_t n, int n_hash, int max_ids, unsigned long long *d_stats, hipStream_t stream);
@@ -228,11 +241,13 @@ int launch_expand_unique(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uid
 bool expand_stream_ok(int64_t n, int64_t U, int n_hash, const void *d_out, int64_t ld);
 size_t expand_stream_scratch_bytes(int64_t n, int64_t U);
 bool expand_stream_packed(int n_hash);   // the LDS row is packed to 9 bits per count: two K2 rings fit beside it
+// (pk: d_D is the packed table (pk_*) and ld_d its pk_lo_bytes; needs expand_stream_packed)
 int launch_expand_stream(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
-                         void *d_scratch, hipStream_t stream, hipEvent_t after_lists = nullptr);
+                         void *d_scratch, hipStream_t stream, hipEvent_t after_lists = nullptr, bool pk = false);
 int launch_expand_stream_lists(const int32_t *d_uidx, int64_t n, int64_t U, void *d_scratch, hipStream_t stream);
 int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
-                              void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no);   // launch_no: 0 .. 127, distinct per launch of a call
+                              void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no,   // launch_no: 0 .. 127, distinct per launch of a call
+                              bool pk = false);
 int launch_expand_rows(const uint16_t *d_F, int64_t ld_f, const int32_t *d_uidx, int64_t n, bool is_nw, int n_hash, int nw_max_len,
                        double *d_out, int64_t ld, int64_t band_begin, int64_t band_end, hipStream_t stream);
 // bytes of the column-gathered table (d_F) that switches launch_expand_unique to its two streaming passes; 0 = shape not covered

@@ -275,6 +275,74 @@ __device__ __forceinline__ bool a12_takes(int ti, int tj, int64_t n, int64_t ld,
          (reinterpret_cast<uintptr_t>(out) & (f64 ? 15 : 3)) == 0;
 }
 
+// ---- epilogue into the PACKED count table (da_common.hpp pk_*; the row expansion reads it as its LDS image) ----------------------
+// A lane holds the match counts of rows 32 (r >> 1) + 2 ty + (r & 1) and columns 32 g + 2 tx + {0, 1} (two per register, as mis[r][g]).
+// Eight passes over 9 KiB of LDS the caller no longer needs: pass p stages the lane's row r = p (16 direct table rows) and its column pair
+// c = p transposed (16 mirrored table rows) as uint16; then thread (s, ch) turns 16 counts of staged row s into 16 low bytes and the 16 bits
+// of bit 8.  Eight consecutive lanes store one 128-byte piece of a row's low plane, the first of them also the row's 16-byte piece of the
+// bit plane (gathered by shuffles) -- the tile owns both pieces, so nothing is read back or merged.  Rows >= n are not stored; columns >= n
+// of a border tile carry the padded rows' counts and are never read.
+constexpr int PK_STAGE_LD = 144;                                     // uint16 per staged row: 288 bytes, conflict-free lane writes
+constexpr int PK_STAGE_BYTES = 32 * PK_STAGE_LD * 2;
+__device__ __forceinline__ uint32_t pk_bit8(uint4 v) {               // bit 8 of the 8 counts in v (two per word, low half first)
+  return ((v.x >> 8) & 1u) | ((v.x >> 23) & 2u) | ((v.y >> 6) & 4u) | ((v.y >> 21) & 8u) | ((v.z >> 4) & 16u) | ((v.z >> 19) & 32u) |
+         ((v.w >> 2) & 64u) | ((v.w >> 17) & 128u);
+}
+__device__ __forceinline__ void store_tile_pk(uint16_t *stage, const uint32_t (&mis)[8][4], uint32_t nn, int tid, int64_t I0, int64_t J0,
+                                              bool mirror, int64_t n, uint8_t *tab, int64_t ld_lo) {
+  const int wave = tid >> 6, lane = tid & 63;
+  const int tx = ((wave & 1) << 3) + (lane & 7), ty = ((wave >> 1) << 3) + (lane >> 3);
+  const int s = tid >> 3, ch = tid & 7;                              // staged row (0..15 direct, 16..31 mirrored) and 16-column chunk
+  // waves 0, 1 store direct rows, waves 2, 3 mirrored ones: the row / column origin and the table address of the tile's first row are
+  // wave-uniform (scalar registers); a lane adds a 32-bit offset
+  const bool dir = __builtin_amdgcn_readfirstlane(wave) < 2;
+  const int64_t r0 = dir ? I0 : J0, c0 = dir ? J0 : I0, stride = pk_row_bytes(ld_lo);
+  const uint64_t o = (uint64_t)(r0 * stride + c0);                  // (readfirstlane returns a signed int: widen through uint32_t)
+  uint8_t *const base = tab + (((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(o >> 32)) << 32) |
+                               (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)o));
+  const uint32_t hi_off = (uint32_t)(ld_lo - c0 + (c0 >> 3));        // low-plane piece -> bit-plane piece of the same row
+  const uint32_t lane_off = (uint32_t)(2 * (s & 15)) * (uint32_t)stride;
+  const int rows_left = (int)min<int64_t>(n - r0, K2_TILE);
+  const bool live = dir || mirror;
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    __syncthreads();                                                 // the area is free (p = 0: the caller is done with it)
+    uint32_t *d = reinterpret_cast<uint32_t *>(stage + ty * PK_STAGE_LD + 2 * tx);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) d[16 * g] = nn - mis[p][g];
+    if (mirror) {
+      uint32_t *m = reinterpret_cast<uint32_t *>(stage + (16 + tx) * PK_STAGE_LD + 2 * ty);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const uint32_t lo = mis[2 * g][p >> 1], hi = mis[2 * g + 1][p >> 1];
+        const uint32_t pk = (p & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
+        m[16 * g] = nn - pk;
+      }
+    }
+    __syncthreads();
+    const uint4 *src = reinterpret_cast<const uint4 *>(stage + s * PK_STAGE_LD + 16 * ch);
+    const uint4 a = src[0], bb = src[1];
+    uint4 lo;
+    lo.x = __builtin_amdgcn_perm(a.y, a.x, 0x06040200u);             // bytes 0 and 2 of x, then of y
+    lo.y = __builtin_amdgcn_perm(a.w, a.z, 0x06040200u);
+    lo.z = __builtin_amdgcn_perm(bb.y, bb.x, 0x06040200u);
+    lo.w = __builtin_amdgcn_perm(bb.w, bb.z, 0x06040200u);
+    const uint32_t h = pk_bit8(a) | (pk_bit8(bb) << 8);             // bit-plane bytes 2 ch, 2 ch + 1
+    // lane + d's value (the lanes that use one read inside their group of 8); the permute addresses come from `tid`, not from the hardware
+    // lane id: in the persistent kernel they would otherwise be hoisted out of its tile loop and have to live across the asm block
+    auto pull = [&](uint32_t v, int d) { return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + d) & 63) << 2, (int)v); };
+    const uint32_t x = h | (pull(h, 1) << 16);
+    const uint4 hv = make_uint4(x, pull(x, 2), pull(x, 4), pull(x, 6));
+    const int pr = 32 * (p >> 1) + (p & 1);                          // the pass's first tile row
+    if (live && pr + 2 * (s & 15) < rows_left) {
+      uint8_t *rp = base + ((uint32_t)pr * (uint32_t)stride + lane_off);
+      *reinterpret_cast<uint4 *>(rp + 16 * ch) = lo;
+      if (ch == 0) *reinterpret_cast<uint4 *>(rp + hi_off) = hv;
+    }
+  }
+  __syncthreads();                                                   // the last pass's reads are done: the caller may reuse the area
+}
+
 // ---- 12-plane compare with a hand-allocated stage loop ------------------------------------------
 // hipcc needs ~30 VGPRs more than the loop strictly does, which pins k_mh_compare at 168 VGPRs = 3 waves per SIMD
 // -- an odd wave count, which costs the gfx950 VALU a quarter of its issue slots (tools/ubench/k2_inner2).  Here the
@@ -290,7 +358,7 @@ __device__ __forceinline__ bool a12_takes(int ti, int tj, int64_t n, int64_t ld,
 #define K2_PRO_PRIO 0     // wave priority of the tile prologue (decode + address arithmetic before the stage loop)
 #endif
 constexpr int K2_A12_TABLE_MAX = 3 * 2 * K2_TILE * 3 * 16 / 8;   // doubles that fit the 12-plane kernel's ring (3 stages x 256 rows x 48 B)
-template <bool F64>
+template <bool F64, bool PK = false>   // PK: uint16 counts into the packed table (out_v; ld = its pk_lo_bytes)
 __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a12(const uint32_t *__restrict__ planes, int64_t n, int n_hash,
                                                                   void *__restrict__ out_v, int64_t ld, int64_t ntiles,
                                                                   int64_t per_xcd) {
@@ -305,7 +373,7 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a12(const uint32_t
   const int64_t L = (bid & 7) * per_xcd + (bid >> 3);
   if (L >= ntiles) return;
   const TileId tl = decode_tile(L, T, T, true);
-  if (!tl.valid || !a12_takes(tl.ti, tl.tj, n, ld, out_v, F64)) return;
+  if (!tl.valid || !a12_takes(tl.ti, tl.tj, n, ld, out_v, F64 || PK)) return;
   if (!F64) K2_STAMP(6);                                      // (timing build, uint16 kind: prologue split)
   const int64_t I0 = (int64_t)tl.ti * K2_TILE, J0 = (int64_t)tl.tj * K2_TILE;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -382,7 +450,9 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a12(const uint32_t
   const int tx_e = ((wave_e & 1) << 3) + (lane_e & 7), ty_e = ((wave_e >> 1) << 3) + (lane_e >> 3);
 #define tx tx_e
 #define ty ty_e
-  if (F64) {
+  if (PK) {
+    store_tile_pk(reinterpret_cast<uint16_t *>(lds_ab), mis, nn, tid_e, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
+  } else if (F64) {
     double *ratio = reinterpret_cast<double *>(lds_ab);
     __syncthreads();                                           // everyone has left the ring: the area becomes the table
     for (int c = tid_e; c <= n_hash; c += K2_THREADS) ratio[c] = (double)c / (double)n_hash;   // src/minHash.cpp:174
@@ -791,12 +861,13 @@ constexpr int K2_P12_TABLE = 512, K2_P8_TABLE = 2048;
 // PL = 12, or 8: the dense half of the heavy / rare split (round 4; dict_kernels.hip k_hy_split): 32-byte slots, a 24 KiB ring, four two-plane
 // steps per stage -- k2_loop_p8p.inc (band kernel: no wave priority) / k2_loop_p8.inc (ONE = one tile per workgroup, the grid of k_mh_compare_a12:
 // the launcher passes wg_per_xcd = per_xcd; priority 2 inside the stage loop like k_mh_compare_a12's block).
-template <bool F64, int PL = 12, bool ONE = false>
+template <bool F64, int PL = 12, bool ONE = false, bool PK = false>   // PK: into the packed table (PL = 12; ld = its pk_lo_bytes)
 __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t *__restrict__ planes, int64_t n, int n_hash,
                                                                   void *__restrict__ out_v, int64_t ld, int64_t ntiles,
                                                                   int64_t per_xcd, int wg_per_xcd, int64_t tile_begin) {
   // the tile ids [tile_begin, ntiles) are dealt in 8 runs of per_xcd (the pipelined duplicate route launches one band range at a time)
   static_assert(PL == 12 || PL == 8, "generated blocks exist for 12 and 8 planes");
+  static_assert(!PK || (!F64 && PL == 12 && !ONE), "the packed table is written by the 12-plane band kernel");
   constexpr int SEGS = PL / 4, STAGE_UNITS = 2 * K2_TILE * SEGS;
   __shared__ __attribute__((aligned(16))) uint4 lds_ab[3 * STAGE_UNITS];   // 36 KiB ring (24 KiB at PL = 8)
   __shared__ double ratio_tab[F64 ? (PL == 8 ? K2_P8_TABLE : K2_P12_TABLE) : 1];   // (PL = 8: the ring is 12 KiB smaller, the table may be 12 KiB larger)
@@ -825,7 +896,7 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
       t = decode_tile(L, To, To, true);
       t.ti = __builtin_amdgcn_readfirstlane(t.ti);             // wave-uniform by construction: keep them in SGPRs, nothing
       t.tj = __builtin_amdgcn_readfirstlane(t.tj);             // per-lane may live across the block (it clobbers the VGPR file)
-      if (t.valid && a12_takes(t.ti, t.tj, n, ld, out_v, F64)) return L;
+      if (t.valid && a12_takes(t.ti, t.tj, n, ld, out_v, F64 || PK)) return L;
     }
     return lim;
   };
@@ -853,7 +924,7 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
       t = decode_tile(Lq, To, To, true);
       t.ti = __builtin_amdgcn_readfirstlane(t.ti);
       t.tj = __builtin_amdgcn_readfirstlane(t.tj);
-      if (t.valid && a12_takes(t.ti, t.tj, n, ld, out_v, F64)) return Lq;
+      if (t.valid && a12_takes(t.ti, t.tj, n, ld, out_v, F64 || PK)) return Lq;
     }
   };
   int L = next_dyn(cur);
@@ -933,7 +1004,14 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
     if (mis[0][0] == 0xdeadbeefu) reinterpret_cast<uint32_t *>(out_v)[0] = tid_after;
     if (n_hash > 0) { cur = nxt; L = Ln; flags = 0u; phase = (phase + nstage) % 3u; continue; }
 #endif
-    if (F64) {
+    if constexpr (PK) {
+      // the next tile's first two stages are landing in the ring slots (phase + nstage) % 3 and the one after it; the third slot held this
+      // tile's last stage (12 KiB: room for the 9 KiB staging area once every wave has left it -- store_tile_pk's first barrier).  The next
+      // block's stage 2 goes there only after the barrier of its stage 0.
+      static_assert(STAGE_UNITS * 16 >= PK_STAGE_BYTES, "the packed epilogue stages in one ring slot");
+      uint16_t *stage = reinterpret_cast<uint16_t *>(lds_ab + ((phase + nstage + 2u) % 3u) * STAGE_UNITS);
+      store_tile_pk(stage, mis, nn, (int)tid_after, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
+    } else if constexpr (F64) {
       const char *tb = reinterpret_cast<const char *>(ratio_tab);
       double *out = reinterpret_cast<double *>(out_v);
 #pragma unroll
@@ -995,7 +1073,7 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
 // PL = bit planes per group of 32 hash functions: 32 (raw uint32 values) or 16 / 12 / 8 (dictionary
 // codes of dict_kernels.hip, as many planes as the largest column dictionary needs: same equalities
 // off the diagonal, a fraction of the planes; the diagonal is forced).
-template <bool SYM, bool F64, int PL>
+template <bool SYM, bool F64, int PL, bool PK = false>   // PK: uint16 counts into the packed table (out_v; ld = its pk_lo_bytes)
 __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
     const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
     int64_t row_end, int tile_stride, int upper_only, int TR, void *__restrict__ out_v, int64_t ld,
@@ -1057,7 +1135,7 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
   if (I0 >= row_end || I0 >= n) return;
   if (!SYM && upper_only && J0 + K2_TILE <= I0) return;                     // tile entirely left of the diagonal
   // the interior tiles were taken by k_mh_compare_a12 (hand-scheduled 12-plane loop): only border / diagonal tiles here
-  if (SYM && only_edge && a12_takes(tid2.ti, tid2.tj, n, ld, out_v, F64)) return;
+  if (SYM && only_edge && a12_takes(tid2.ti, tid2.tj, n, ld, out_v, F64 || PK)) return;
   if (!SYM && !F64 && only_edge && s12_takes(I0, J0, n, row_end, ld, Jloc, out_v)) return;   // ... or by k_mh_compare_s12 (shard / row-block modes)
 
   const int tid = threadIdx.x;
@@ -1240,6 +1318,13 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
     }
   }
   K2_STAMP(2);
+  if constexpr (PK) {
+    static_assert(SYM && !F64 && sizeof(lds_ab) >= PK_STAGE_BYTES, "the packed table: symmetric counts, staged in the ring");
+    store_tile_pk(reinterpret_cast<uint16_t *>(lds_ab), mis, (uint32_t)n_hash * 0x10001u, tid, I0, J0, tid2.ti != tid2.tj, n,
+                  reinterpret_cast<uint8_t *>(out_v), ld);
+    K2_STAMP(3);
+    return;
+  }
   auto matches = [&](int r, int c) -> uint32_t {  // reference src/minHash.cpp:168-173
     return (uint32_t)n_hash - ((mis[r][c >> 1] >> ((c & 1) * 16)) & 0xffffu);
   };
@@ -1658,8 +1743,10 @@ bool mh_compare_bands_ok(int64_t n, int n_hash, int plane_bits, const void *d_ou
 // interior tiles of the bands [band_begin, band_end) by the persistent kernel with at most wg_per_cu resident workgroups per CU:
 // a grid that small leaves the rest of every CU to kernels of other streams (the expansion's stores)
 int launch_mh_compare_bands_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, int64_t band_begin,
-                                int64_t band_end, int wg_per_cu, hipStream_t stream, int plane_bits) {
-  if (!mh_compare_bands_ok(n, n_hash, plane_bits, d_out, ld)) return fail(DA_ERR_UNSUPPORTED, "banded compare: shape not covered");
+                                int64_t band_end, int wg_per_cu, hipStream_t stream, int plane_bits, bool pk) {
+  if (!mh_compare_bands_ok(n, n_hash, plane_bits, d_out, ld) ||
+      (pk && (!mh_compare_pk_ok(n, n_hash, plane_bits) || (reinterpret_cast<uintptr_t>(d_out) & 15))))   // = a12_takes' test for the packed table
+    return fail(DA_ERR_UNSUPPORTED, "banded compare: shape not covered");
   const int64_t t0 = mh_sym_band_prefix(n, band_begin), t1 = mh_sym_band_prefix(n, band_end);
   if (t1 <= t0) return DA_OK;
   static std::atomic<int> cus_cache;
@@ -1676,6 +1763,9 @@ int launch_mh_compare_bands_u16(const uint32_t *d_planes, int64_t n, int n_hash,
   if (plane_bits == 8)
     hipLaunchKernelGGL((k_mh_compare_p12<false, 8, false>), dim3((unsigned)(8 * wg_per_xcd)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
                        static_cast<void *>(d_out), ld, t1, per_xcd, wg_per_xcd, t0);
+  else if (pk)
+    hipLaunchKernelGGL((k_mh_compare_p12<false, 12, false, true>), dim3((unsigned)(8 * wg_per_xcd)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
+                       static_cast<void *>(d_out), ld, t1, per_xcd, wg_per_xcd, t0);
   else
     hipLaunchKernelGGL(k_mh_compare_p12<false>, dim3((unsigned)(8 * wg_per_xcd)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
                        static_cast<void *>(d_out), ld, t1, per_xcd, wg_per_xcd, t0);
@@ -1683,10 +1773,16 @@ int launch_mh_compare_bands_u16(const uint32_t *d_planes, int64_t n, int n_hash,
   return DA_OK;
 }
 // the tiles the kernel above leaves everywhere: diagonal tiles and the last tile column (with their mirrors)
-int launch_mh_compare_edges_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, hipStream_t stream, int plane_bits) {
+int launch_mh_compare_edges_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, hipStream_t stream, int plane_bits,
+                                bool pk) {
   const int T = (int)ceil_div(n, K2_TILE);
   const int64_t ntiles = count_tiles(T, T, true);
-  if (plane_bits == 8)
+  if (pk && (!mh_compare_pk_ok(n, n_hash, plane_bits) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
+    return fail(DA_ERR_UNSUPPORTED, "packed count table: shape not covered");
+  if (pk)
+    hipLaunchKernelGGL((k_mh_compare<true, false, 12, true>), dim3((unsigned)(2 * (int64_t)T - 1)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
+                       (int64_t)0, n, 1, 0, T, static_cast<void *>(d_out), ld, ntiles, ceil_div(ntiles, 8), 0, (int64_t)0, K2_BAND, 1);
+  else if (plane_bits == 8)
     hipLaunchKernelGGL((k_mh_compare<true, false, 8>), dim3((unsigned)(2 * (int64_t)T - 1)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
                        (int64_t)0, n, 1, 0, T, static_cast<void *>(d_out), ld, ntiles, ceil_div(ntiles, 8), 0, (int64_t)0, K2_BAND, 1);
   else
@@ -1694,6 +1790,20 @@ int launch_mh_compare_edges_u16(const uint32_t *d_planes, int64_t n, int n_hash,
                      (int64_t)0, n, 1, 0, T, static_cast<void *>(d_out), ld, ntiles, ceil_div(ntiles, 8), 0, (int64_t)0, K2_BAND, 1);
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
+}
+
+// the packed count table (pk_*) of n <= 65536 rows, n_hash <= 511 (9-bit counts), from the 12-plane operand; ld = pk_lo_bytes(n) everywhere
+bool mh_compare_pk_ok(int64_t n, int n_hash, int plane_bits) {
+  return plane_bits == 12 && n >= 1 && n <= 65536 && n_hash >= 1 && expand_stream_packed(n_hash) && !config().k2_no_asm;
+}
+int launch_mh_compare_pk(const uint32_t *d_planes, int64_t n, int n_hash, uint8_t *d_tab, hipStream_t stream) {
+  if (!mh_compare_pk_ok(n, n_hash, 12) || (reinterpret_cast<uintptr_t>(d_tab) & 15)) return fail(DA_ERR_UNSUPPORTED, "packed count table: shape not covered");
+  const int T = (int)ceil_div(n, K2_TILE);
+  const int64_t ntiles = count_tiles(T, T, true), per_xcd = ceil_div(ntiles, 8);
+  hipLaunchKernelGGL((k_mh_compare_a12<false, true>), dim3((unsigned)(per_xcd * 8)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
+                     static_cast<void *>(d_tab), pk_lo_bytes(n), ntiles, per_xcd);
+  DA_HIP_TRY(hipGetLastError());
+  return launch_mh_compare_edges_u16(d_planes, n, n_hash, reinterpret_cast<uint16_t *>(d_tab), pk_lo_bytes(n), stream, 12, true);
 }
 
 // Store phase shared by the three "64 x 64 uint16 tile in LDS -> float64 output, direct + mirrored" kernels below.  Interior
@@ -2146,9 +2256,12 @@ __global__ __launch_bounds__(256) void k_es_ratio_check(int n_hash, double *__re
   const double dn = (double)n_hash, rcp = 1.0 / dn;
   if (c <= n_hash) out[c] = es_ratio((uint32_t)c, dn, rcp);
 }
-// PACKED (counts <= 511, i.e. n_hash <= 511): the LDS row holds the low byte of every count + one bit plane for bit 8 -- 9/16 of the bytes (54.6 KB
-// instead of 93.9 KB at U = 44 931), which lets TWO rings of the persistent compare kernel stay resident beside it in the pipelined form
-template <bool PACKED, int NQ>                // NQ: 16-byte units of a table row per thread, ceil(U / 8192) rounded up to 2, 4, 6 or 8
+// Packed LDS row (counts <= 511, i.e. n_hash <= 511): the low byte of every count + one bit plane for bit 8 -- 9/16 of the bytes (54.6 KB
+// instead of 93.9 KB at U = 44 931), which lets TWO rings of the persistent compare kernel stay resident beside it in the pipelined form.
+// FMT: ES_U16 (uint16 table, uint16 LDS row), ES_U16_PK (uint16 table, repacked on its way into LDS), ES_PK (the packed table of da_common.hpp,
+// already the LDS image: a plain copy, and 9/16 of the table bytes read)
+enum { ES_U16 = 0, ES_U16_PK = 1, ES_PK = 2 };
+template <int FMT, int NQ>                    // NQ: 16-byte units of a table row per thread, rounded up to 2, 4, 6 or 8
 __global__ __launch_bounds__(ES_THREADS, 8)   // <= 64 VGPRs: the 4 waves per SIMD of one workgroup leave 256 VGPRs = two K2 waves
 void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t *__restrict__ uidx,
                                                               const uint32_t *__restrict__ cstart, const int32_t *__restrict__ cpos,
@@ -2159,6 +2272,7 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
 #ifdef ES_PRIO
   __builtin_amdgcn_s_setprio(ES_PRIO);   // (experiment: issue priority of the storing waves beside the compare's, which run their loop at priority 2)
 #endif
+  constexpr bool PACKED = FMT != ES_U16;
   uint16_t *row = reinterpret_cast<uint16_t *>(es_lds);
   unsigned char *row_lo = es_lds, *row_hi = row_lo + ld_d;           // (PACKED) ld_d low bytes, then ld_d / 8 bytes of bit 8
   const int tid = threadIdx.x;
@@ -2168,11 +2282,12 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
     return (uint32_t)row_lo[c] | ((((uint32_t)row_hi[c >> 3] >> (c & 7)) & 1u) << 8);
   };
   const int n_items = (int)istart[row_end];                          // the items of the table rows [row_begin, row_end)
-  const int units = (int)(ld_d >> 3);
+  const int64_t row_bytes = FMT == ES_PK ? pk_row_bytes(ld_d) : 2 * ld_d;
+  const int units = (int)(row_bytes >> 4);
   uint4 pre[NQ];
 #define ES_FETCH(r_)                                                                                    \
   {                                                                                                     \
-    const uint4 *src_ = reinterpret_cast<const uint4 *>(D + (int64_t)(r_) * ld_d);                      \
+    const uint4 *src_ = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned char *>(D) + (int64_t)(r_) * row_bytes); \
     _Pragma("unroll") for (int q = 0; q < NQ; ++q) {                                                    \
       const int u = tid + q * ES_THREADS;                                                               \
       pre[q] = u < units ? src_[u] : make_uint4(0, 0, 0, 0);                                            \
@@ -2195,7 +2310,7 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
     for (int q = 0; q < NQ; ++q) {
       const int u = tid + q * ES_THREADS;
       if (u >= units) continue;
-      if (!PACKED) { dst[u] = pre[q]; continue; }
+      if (FMT != ES_U16_PK) { dst[u] = pre[q]; continue; }
       const uint4 v = pre[q];                                        // counts 8 u ... 8 u + 7, two per word
       uint2 lo;
       lo.x = __builtin_amdgcn_perm(v.y, v.x, 0x06040200u);           // bytes 0 and 2 of x, then of y
@@ -2270,9 +2385,9 @@ int launch_expand_stream_lists(const int32_t *d_uidx, int64_t n, int64_t U, void
 }
 // k_expand_stream on the table rows [row_begin, row_end) (lists from launch_expand_stream_lists on the same scratch)
 int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
-                              void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no) {
-  if (!expand_stream_ok(n, U, n_hash, d_out, ld) || (ld_d & 7) || ld_d > 65536 || (reinterpret_cast<uintptr_t>(d_D) & 15) || launch_no < 0 ||
-      launch_no >= ES_TICKETS)
+                              void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no, bool pk) {
+  if (!expand_stream_ok(n, U, n_hash, d_out, ld) || (ld_d & (pk ? 127 : 7)) || ld_d > 65536 || (reinterpret_cast<uintptr_t>(d_D) & 15) || launch_no < 0 ||
+      launch_no >= ES_TICKETS || (pk && !expand_stream_packed(n_hash)))
     return fail(DA_ERR_UNSUPPORTED, "row expansion: shape not covered");
   if (row_end > U) row_end = U;
   if (row_begin >= row_end) return DA_OK;
@@ -2285,14 +2400,15 @@ int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *
     hipDeviceProp_t prop;
     DA_HIP_TRY(hipGetDeviceProperties(&prop, dev));
 #define DA_ES_ATTR(P, Q) DA_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_expand_stream<P, Q>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2))
-    DA_ES_ATTR(false, 2); DA_ES_ATTR(false, 4); DA_ES_ATTR(false, 6); DA_ES_ATTR(false, 8);
-    DA_ES_ATTR(true, 2); DA_ES_ATTR(true, 4); DA_ES_ATTR(true, 6); DA_ES_ATTR(true, 8);
+    DA_ES_ATTR(ES_U16, 2); DA_ES_ATTR(ES_U16, 4); DA_ES_ATTR(ES_U16, 6); DA_ES_ATTR(ES_U16, 8);
+    DA_ES_ATTR(ES_U16_PK, 2); DA_ES_ATTR(ES_U16_PK, 4); DA_ES_ATTR(ES_U16_PK, 6); DA_ES_ATTR(ES_U16_PK, 8);
+    DA_ES_ATTR(ES_PK, 2); DA_ES_ATTR(ES_PK, 4); DA_ES_ATTR(ES_PK, 6); DA_ES_ATTR(ES_PK, 8);
 #undef DA_ES_ATTR
     es_cus.store(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256);
     es_attr_done.fetch_or(1ull << (dev & 63));
   }
-  const bool packed = expand_stream_packed(n_hash);
-  size_t lds = packed ? (size_t)ld_d + (size_t)ld_d / 8 : (size_t)ld_d * 2;
+  const bool packed = pk || expand_stream_packed(n_hash);
+  size_t lds = packed ? (size_t)pk_row_bytes(ld_d) : (size_t)ld_d * 2;
   // never two of these workgroups on one CU (the pipelined form's consecutive launches would otherwise fill the VGPR file with 8 waves per SIMD
   // and lock the compare kernel out until the older launch has drained): ask for more than half of the CU's 160 KB
   lds = std::max<size_t>(lds, 82 * 1024);
@@ -2301,20 +2417,23 @@ int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *
   grid = std::min<int64_t>(grid, (row_end - row_begin) + n / ES_COPIES + 1);
 #define DA_ES(P, Q) hipLaunchKernelGGL((k_expand_stream<P, Q>), dim3((unsigned)grid), dim3(ES_THREADS), lds, stream, d_D, ld_d, d_uidx, L.cstart, L.cpos, L.items, \
                                        L.istart, (int)row_begin, (int)row_end, (int)n, n_hash, d_out, ld, L.ticket + launch_no)
-  const int64_t nq = ceil_div(ld_d >> 3, ES_THREADS);                 // 16-byte units of a row per thread
-  if (packed) { if (nq <= 2) DA_ES(true, 2); else if (nq <= 4) DA_ES(true, 4); else if (nq <= 6) DA_ES(true, 6); else DA_ES(true, 8); }
-  else { if (nq <= 2) DA_ES(false, 2); else if (nq <= 4) DA_ES(false, 4); else if (nq <= 6) DA_ES(false, 6); else DA_ES(false, 8); }
+  const int64_t nq = ceil_div((pk ? pk_row_bytes(ld_d) : 2 * ld_d) >> 4, ES_THREADS);   // 16-byte units of a table row per thread
+#define DA_ES_NQ(F) do { if (nq <= 2) DA_ES(F, 2); else if (nq <= 4) DA_ES(F, 4); else if (nq <= 6) DA_ES(F, 6); else DA_ES(F, 8); } while (0)
+  if (pk) DA_ES_NQ(ES_PK);
+  else if (packed) DA_ES_NQ(ES_U16_PK);
+  else DA_ES_NQ(ES_U16);
+#undef DA_ES_NQ
 #undef DA_ES
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
 int launch_expand_stream(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
-                         void *d_scratch, hipStream_t stream, hipEvent_t after_lists) {
+                         void *d_scratch, hipStream_t stream, hipEvent_t after_lists, bool pk) {
   if (!expand_stream_ok(n, U, n_hash, d_out, ld)) return fail(DA_ERR_UNSUPPORTED, "row expansion: shape not covered");
   int rc = launch_expand_stream_lists(d_uidx, n, U, d_scratch, stream);
   if (rc != DA_OK) return rc;
   if (after_lists) DA_HIP_TRY(hipEventRecord(after_lists, stream));
-  return launch_expand_stream_rows(d_D, ld_d, d_uidx, n, U, n_hash, d_out, ld, d_scratch, 0, U, stream, 0);
+  return launch_expand_stream_rows(d_D, ld_d, d_uidx, n, U, n_hash, d_out, ld, d_scratch, 0, U, stream, 0, pk);
 }
 
 // device bytes of the column-gathered table the two-pass expansion wants (0: the shape is not covered, pass NULL)
