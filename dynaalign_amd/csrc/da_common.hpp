@@ -179,9 +179,6 @@ int launch_mh_sparse_fixup(const uint32_t *d_scratch, const uint16_t *d_entries,
                            int64_t ld, int64_t tile_row_begin, int64_t tile_row_end, hipStream_t stream);
 // dict_kernels.hip: where the codes of launch_mh_dictionary sit in its workspace ([n_hash][*ld_ids] uint16, 0xFFFF = value seen once)
 const uint16_t *mh_dictionary_codes(const void *d_work, int64_t n, int n_hash, int64_t *ld_ids);
-#ifdef DA_K2_EXPERIMENTS
-size_t release_compare_scratch();   // (experiment library only: idle scratch of the role-split compare kernel)
-#endif
 // dict_kernels.hip: signatures -> compare operand.  Dictionary codes (8 / 12 / 16 planes per group,
 // whatever the largest column dictionary needs) are exact for n <= DA_DICT_MAX_N; *d_status_out
 // points at two ints in the workspace ({error, largest id count}), valid once the stream has drained.

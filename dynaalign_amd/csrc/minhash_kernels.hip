@@ -265,18 +265,77 @@ __device__ unsigned long long *g_k2_timing = nullptr;   // [blocks][8]: t_entry,
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
-#ifdef DA_K2_DEBUG
-__device__ uint32_t *g_k2_debug = nullptr;
-#endif
-// Which tiles the hand-scheduled kernel below computes: strictly above the diagonal, wholly inside the matrix,
+// The asm kernels' wide stores (two counts per 4-byte store, two doubles or a packed-table piece per 16-byte store) need an even ld and an
+// output aligned for them.  The launchers and the *_takes tests below apply this one rule.
+__host__ __device__ __forceinline__ bool k2_out_ok(const void *out, int64_t ld, bool wide) {
+  return (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & (wide ? 15 : 3)) == 0;
+}
+// Which tiles the hand-scheduled kernels below compute: strictly above the diagonal, wholly inside the matrix,
 // output aligned for its wide stores.  Everything else stays with k_mh_compare (only_edge = 1).
 __device__ __forceinline__ bool a12_takes(int ti, int tj, int64_t n, int64_t ld, const void *out, bool f64) {
-  return ti != tj && (int64_t)(ti + 1) * K2_TILE <= n && (int64_t)(tj + 1) * K2_TILE <= n && (ld & 1) == 0 &&
-         (reinterpret_cast<uintptr_t>(out) & (f64 ? 15 : 3)) == 0;
+  return ti != tj && (int64_t)(ti + 1) * K2_TILE <= n && (int64_t)(tj + 1) * K2_TILE <= n && k2_out_ok(out, ld, f64);
+}
+// ... and in the SHARD / row-block modes (rect_tile below): tiles completely inside the matrix and the row range whose 4-byte stores are
+// aligned -- the compiled kernel runs with only_edge = 1 on the same grid and returns at once for those.
+__device__ __forceinline__ bool s12_takes(int64_t I0, int64_t J0, int64_t n, int64_t row_end, int64_t ld, int64_t Jloc, const void *out) {
+  return I0 != J0 &&                                             // a diagonal tile: the general kernel forces count(i, i) = n_hash (singleton codes never match)
+         I0 + K2_TILE <= (row_end < n ? row_end : n) && J0 + K2_TILE <= n && (Jloc & 1) == 0 && k2_out_ok(out, ld, false);
 }
 
-// ---- epilogue into the PACKED count table (da_common.hpp pk_*; the row expansion reads it as its LDS image) ----------------------
-// A lane holds the match counts of rows 32 (r >> 1) + 2 ty + (r & 1) and columns 32 g + 2 tx + {0, 1} (two per register, as mis[r][g]).
+// The tile of a one-tile-per-workgroup asm kernel; valid = it exists and the kernel takes it.  Stored at local row = global row + Iloc,
+// local col = global col + Jloc.
+struct RectTile { int ti, tj; bool valid; int64_t I0, J0, Iloc, Jloc; };
+// symmetric: XCD x walks the id range [x * per_xcd, (x + 1) * per_xcd) of decode_tile's banded order (blocks b and b + 8 share an XCD)
+__device__ __forceinline__ RectTile sym_tile(int64_t n, int64_t ld, const void *out, int64_t ntiles, int64_t per_xcd, bool wide) {
+  RectTile t{0, 0, false, 0, 0, 0, 0};
+  const int64_t bid = blockIdx.x;
+  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
+  const int64_t L = (bid & 7) * per_xcd + (bid >> 3);
+  if (L >= ntiles) return t;
+  const TileId tl = decode_tile(L, T, T, true);
+  t.ti = tl.ti;
+  t.tj = tl.tj;
+  t.valid = tl.valid && a12_takes(tl.ti, tl.tj, n, ld, out, wide);
+  t.I0 = (int64_t)tl.ti * K2_TILE;
+  t.J0 = (int64_t)tl.tj * K2_TILE;
+  return t;
+}
+// rect: k_mh_compare's non-symmetric geometry (cyclic tile rows of a rank, folded shard rows, upper_only), the tiles s12_takes takes
+__device__ __forceinline__ RectTile rect_tile(int64_t bid, int64_t n, int64_t row_begin, int64_t row_end, int tile_stride, int upper_only, int TR,
+                                              int fold_q, int64_t fold_w, int band, int64_t ld, const void *out) {
+  RectTile t{0, 0, false, 0, 0, 0, 0};
+  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
+  const uint32_t per_band = (uint32_t)band * (uint32_t)T;
+  const uint32_t k = (uint32_t)(bid >> 3);
+  const uint32_t kb = k / per_band;
+  const int r0 = ((int)(bid & 7) + 8 * (int)kb) * band;
+  const int l = (int)(k - kb * per_band);
+  const int h = (TR - r0 < band) ? (TR - r0) : band;
+  if (h <= 0) return t;
+  t.tj = __builtin_amdgcn_readfirstlane(div_small(l, h));               // wave-uniform by construction: scalars, so that nothing of the tile's
+  t.ti = __builtin_amdgcn_readfirstlane(r0 + (l - t.tj * h));           // geometry sits in a VGPR across the loop block (it clobbers the file)
+  if (t.tj >= T) return t;
+  t.I0 = row_begin + (int64_t)t.ti * tile_stride * K2_TILE;
+  t.J0 = (int64_t)t.tj * K2_TILE;
+  t.Iloc = (int64_t)t.ti * K2_TILE - t.I0;
+  t.Jloc = 0;
+  if (fold_q > 0) {
+    const int q = t.ti;
+    const bool front = q <= fold_q - 1 - q;
+    t.Iloc = (int64_t)(front ? q : fold_q - 1 - q) * K2_TILE - t.I0;
+    t.Jloc = front ? -t.I0 : shard_back(fold_w, n);
+  }
+  if (t.I0 >= row_end || t.I0 >= n) return t;
+  if (upper_only && t.J0 + K2_TILE <= t.I0) return t;
+  t.valid = s12_takes(t.I0, t.J0, n, row_end, ld, t.Jloc, out);
+  return t;
+}
+
+// ---- tile epilogues of the asm kernels --------------------------------------------------------------------------------------------
+// A lane holds the match counts of rows 32 (r >> 1) + 2 ty + (r & 1) and columns 32 g + 2 tx + {0, 1} as nn - mis[r][g] (two per
+// register, low half first; nn = n_hash * 0x10001: no borrow, each count <= n_hash).
+//
+// Into the PACKED count table (da_common.hpp pk_*; the row expansion reads it as its LDS image).
 // Eight passes over 9 KiB of LDS the caller no longer needs: pass p stages the lane's row r = p (16 direct table rows) and its column pair
 // c = p transposed (16 mirrored table rows) as uint16; then thread (s, ch) turns 16 counts of staged row s into 16 low bytes and the 16 bits
 // of bit 8.  Eight consecutive lanes store one 128-byte piece of a row's low plane, the first of them also the row's 16-byte piece of the
@@ -342,292 +401,76 @@ __device__ __forceinline__ void store_tile_pk(uint16_t *stage, const uint32_t (&
   }
   __syncthreads();                                                   // the last pass's reads are done: the caller may reuse the area
 }
-
-// ---- 12-plane compare with a hand-allocated stage loop ------------------------------------------
-// hipcc needs ~30 VGPRs more than the loop strictly does, which pins k_mh_compare at 168 VGPRs = 3 waves per SIMD
-// -- an odd wave count, which costs the gfx950 VALU a quarter of its issue slots (tools/ubench/k2_inner2).  Here the
-// stage loop (DMA issue, counted waits, barriers, plane loop with 8-byte operands, popcounts) is ONE asm statement
-// with a fixed register map (tools/gen_k2_asm.py -> k2_loop_p12.inc): 116 + 10 VGPRs, so 4 workgroups per CU =
-// 4 waves per SIMD.  The C++ around it decodes the tile, hands five per-lane values over in v120..v124, reads the
-// 32 packed mismatch counters back from LDS and stores the tile like k_mh_compare's straight-line epilogue.
-// Symmetric mode, interior off-diagonal tiles only (a12_takes).
-#ifndef K2_LOOP_INC
-#define K2_LOOP_INC "k2_loop_p12.inc"
-#endif
-#ifndef K2_PRO_PRIO
-#define K2_PRO_PRIO 0     // wave priority of the tile prologue (decode + address arithmetic before the stage loop)
-#endif
-constexpr int K2_A12_TABLE_MAX = 3 * 2 * K2_TILE * 3 * 16 / 8;   // doubles that fit the 12-plane kernel's ring (3 stages x 256 rows x 48 B)
-template <bool F64, bool PK = false>   // PK: uint16 counts into the packed table (out_v; ld = its pk_lo_bytes)
-__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a12(const uint32_t *__restrict__ planes, int64_t n, int n_hash,
-                                                                  void *__restrict__ out_v, int64_t ld, int64_t ntiles,
-                                                                  int64_t per_xcd) {
-  constexpr int PL = 12, SEGS = 3, STAGE_UNITS = 2 * K2_TILE * SEGS;
-  __shared__ __attribute__((aligned(16))) uint4 lds_ab[3 * STAGE_UNITS];   // 36 KiB ring; afterwards counters, then the ratio table
-  static_assert(sizeof(lds_ab) / (sizeof(double)) == K2_A12_TABLE_MAX, "launch_mh_compare's table guard must match the ring size");
-  if (K2_PRO_PRIO) __builtin_amdgcn_s_setprio(K2_PRO_PRIO);
-  K2_STAMP(0);
-  K2_STAMP_HW();
-  const int64_t bid = blockIdx.x;
-  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
-  const int64_t L = (bid & 7) * per_xcd + (bid >> 3);
-  if (L >= ntiles) return;
-  const TileId tl = decode_tile(L, T, T, true);
-  if (!tl.valid || !a12_takes(tl.ti, tl.tj, n, ld, out_v, F64 || PK)) return;
-  if (!F64) K2_STAMP(6);                                      // (timing build, uint16 kind: prologue split)
-  const int64_t I0 = (int64_t)tl.ti * K2_TILE, J0 = (int64_t)tl.tj * K2_TILE;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tx = ((wave & 1) << 3) + (lane & 7), ty = ((wave >> 1) << 3) + (lane >> 3);
-  const PlaneGeom pg = plane_geom(n, n_hash, PL);
-  // DMA source of this lane in the wave's first instruction of stage 0; instructions q = 1, 2 read 1 KiB and 2 KiB
-  // further (the operand is stored in staging order), stage s reads 128 * 12 words further
-  const int u = wave * SEGS * 64 + lane, sl0 = u / SEGS, sl = sl0 & 127;
-  const uint32_t *src = planes + (sl0 < 128 ? 0 : pg.copy_words) +
-                        plane_unit_word(pg, (sl0 < 128 ? I0 : J0) + k2_row_of_slot(sl), 0, u - sl0 * SEGS);
-  if (!F64) K2_STAMP(7);
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)lds_ab);
-  const uint32_t a_off = lds_base + (uint32_t)(ty * SEGS * 16);
-  const uint32_t b_off = lds_base + (uint32_t)((K2_TILE * SEGS + tx * SEGS) * 16);
-  const uint32_t src_lo = (uint32_t)reinterpret_cast<uintptr_t>(src), src_hi = (uint32_t)(reinterpret_cast<uintptr_t>(src) >> 32);
-  const uint32_t wb = (uint32_t)tid * 4u;
-  const uint32_t nstage = (uint32_t)((n_hash + K2_GROUP - 1) / K2_GROUP), stage_bytes = 128u * PL * 4u;
-  const uint32_t wave_id = __builtin_amdgcn_readfirstlane((uint32_t)wave);
-  const uint32_t src_lo_u = __builtin_amdgcn_readfirstlane(src_lo), src_hi_u = __builtin_amdgcn_readfirstlane(src_hi);   // lane 0's source
-  K2_STAMP(1);
-  // the lane's 32 packed mismatch counters (columns 2j, 2j+1 per register) leave the block in v64..v95
-  uint32_t mis[8][4];
-  uint32_t tid_after;
-  {
-    register uint32_t r120 asm("v120") = a_off;
-    register uint32_t r121 asm("v121") = b_off;
-    register uint32_t r122 asm("v122") = src_lo;
-    register uint32_t r123 asm("v123") = src_hi;
-    register uint32_t r124 asm("v124") = wb;
-#define K2_CNT(i) register uint32_t c##i asm("v" #i);
-    K2_CNT(64) K2_CNT(65) K2_CNT(66) K2_CNT(67) K2_CNT(68) K2_CNT(69) K2_CNT(70) K2_CNT(71) K2_CNT(72) K2_CNT(73) K2_CNT(74)
-    K2_CNT(75) K2_CNT(76) K2_CNT(77) K2_CNT(78) K2_CNT(79) K2_CNT(80) K2_CNT(81) K2_CNT(82) K2_CNT(83) K2_CNT(84) K2_CNT(85)
-    K2_CNT(86) K2_CNT(87) K2_CNT(88) K2_CNT(89) K2_CNT(90) K2_CNT(91) K2_CNT(92) K2_CNT(93) K2_CNT(94) K2_CNT(95)
-#undef K2_CNT
-    asm volatile(
-#include K2_LOOP_INC
-        : "+v"(r122), "+v"(r123),                                // the block reuses them as an operand buffer
-          "=v"(c64), "=v"(c65), "=v"(c66), "=v"(c67), "=v"(c68), "=v"(c69), "=v"(c70), "=v"(c71), "=v"(c72), "=v"(c73), "=v"(c74),
-          "=v"(c75), "=v"(c76), "=v"(c77), "=v"(c78), "=v"(c79), "=v"(c80), "=v"(c81), "=v"(c82), "=v"(c83), "=v"(c84), "=v"(c85),
-          "=v"(c86), "=v"(c87), "=v"(c88), "=v"(c89), "=v"(c90), "=v"(c91), "=v"(c92), "=v"(c93), "=v"(c94), "=v"(c95)
-        : [lb] "s"(lds_base), [ns] "s"(nstage), [st] "s"(stage_bytes), [wv] "s"(wave_id), [sl] "s"(src_lo_u), [sh] "s"(src_hi_u),
-          "v"(r120), "v"(r121), "v"(r124)
-        : "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "v125",   // m0 is saved in s47 and restored by the block
-          "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",
-          "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39",
-          "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59",
-          "v60", "v61", "v62", "v63", "v96", "v97", "v98", "v99",
-          "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116",
-          "v117", "v118", "v119");
-    // everything lane-dependent the epilogue needs is re-derived from v124 (4 * thread id), which survives the block:
-    // nothing per-lane has to live across it (the block clobbers all but four VGPRs; hipcc spilled to scratch otherwise)
-    asm volatile("" : "+v"(r124));
-    tid_after = r124 >> 2;
-    const uint32_t cnt[32] = {c64, c65, c66, c67, c68, c69, c70, c71, c72, c73, c74, c75, c76, c77, c78, c79,
-                              c80, c81, c82, c83, c84, c85, c86, c87, c88, c89, c90, c91, c92, c93, c94, c95};
+// float64, symmetric: each count through the count -> double table tb ((double)c / n_hash, src/minHash.cpp:174), stored direct and
+// mirrored (src/minHash.cpp:176) with 16-byte streaming stores; two of the lane's rows at a time keeps the epilogue in 128 VGPRs
+__device__ __forceinline__ void store_counts_f64(double *out, int64_t ld, const char *tb, const uint32_t (&mis)[8][4], uint32_t nn,
+                                                   int64_t I0, int64_t J0, int tx, int ty) {
 #pragma unroll
-    for (int r = 0; r < 8; ++r)
+  for (int g = 0; g < 4; ++g) {
+    double v0[8], v1[8];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) mis[r][c] = cnt[4 * r + c];
-  }
-  K2_STAMP(2);
-#ifdef DA_K2_DEBUG
-  if (g_k2_debug && tl.ti == 0 && tl.tj == 1) {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(lds_ab);
-    for (int i = tid; i < 3 * STAGE_UNITS * 4; i += K2_THREADS) g_k2_debug[i] = w[i];
-  }
-#endif
-#ifdef K2_NO_STORES   // experiment: how long does the kernel take without its epilogue (tools/k2_variants.sh)?
-  if (n_hash > 0) { if (mis[0][0] == 0xdeadbeefu) reinterpret_cast<uint32_t *>(out_v)[0] = tid_after; return; }
-#endif
-  const uint32_t nn = (uint32_t)n_hash * 0x10001u;             // two match counts per register (no borrow: each <= n_hash)
-  // lane coordinates again, from the value that crossed the block (same formulas as above)
-  const int tid_e = (int)tid_after, wave_e = tid_e >> 6, lane_e = tid_e & 63;
-  const int tx_e = ((wave_e & 1) << 3) + (lane_e & 7), ty_e = ((wave_e >> 1) << 3) + (lane_e >> 3);
-#define tx tx_e
-#define ty ty_e
-  if (PK) {
-    store_tile_pk(reinterpret_cast<uint16_t *>(lds_ab), mis, nn, tid_e, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
-  } else if (F64) {
-    double *ratio = reinterpret_cast<double *>(lds_ab);
-    __syncthreads();                                           // everyone has left the ring: the area becomes the table
-    for (int c = tid_e; c <= n_hash; c += K2_THREADS) ratio[c] = (double)c / (double)n_hash;   // src/minHash.cpp:174
-    __syncthreads();
-    K2_STAMP(6);
-    K2_STAMP(7);
-    const char *tb = reinterpret_cast<const char *>(ratio);
-    double *out = reinterpret_cast<double *>(out_v);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {                              // two of the lane's rows at a time keeps the epilogue in 128 VGPRs
-      double v0[8], v1[8];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint32_t m0 = nn - mis[2 * g][c], m1 = nn - mis[2 * g + 1][c];
-        v0[2 * c] = *reinterpret_cast<const double *>(tb + ((m0 << 3) & 0x7fff8u));
-        v0[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m0 >> 13) & 0x7fff8u));
-        v1[2 * c] = *reinterpret_cast<const double *>(tb + ((m1 << 3) & 0x7fff8u));
-        v1[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m1 >> 13) & 0x7fff8u));
-      }
-      double *orow = out + (I0 + 32 * g + 2 * ty) * ld + (J0 + 2 * tx);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        nt_store2(orow + 32 * q, v0[2 * q], v0[2 * q + 1]);
-        nt_store2(orow + ld + 32 * q, v1[2 * q], v1[2 * q + 1]);
-      }
-#pragma unroll
-      for (int c = 0; c < 8; ++c)                              // mirrored store (src/minHash.cpp:176)
-        nt_store2(out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 32 * g + 2 * ty), v0[c], v1[c]);
+    for (int c = 0; c < 4; ++c) {
+      const uint32_t m0 = nn - mis[2 * g][c], m1 = nn - mis[2 * g + 1][c];
+      v0[2 * c] = *reinterpret_cast<const double *>(tb + ((m0 << 3) & 0x7fff8u));
+      v0[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m0 >> 13) & 0x7fff8u));
+      v1[2 * c] = *reinterpret_cast<const double *>(tb + ((m1 << 3) & 0x7fff8u));
+      v1[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m1 >> 13) & 0x7fff8u));
     }
-  } else {
-    uint16_t *out = reinterpret_cast<uint16_t *>(out_v);
+    double *orow = out + (I0 + 32 * g + 2 * ty) * ld + (J0 + 2 * tx);
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      uint16_t *orow = out + (I0 + 32 * (r >> 1) + 2 * ty + (r & 1)) * ld + (J0 + 2 * tx);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis[r][g];
+    for (int q = 0; q < 4; ++q) {
+      nt_store2(orow + 32 * q, v0[2 * q], v0[2 * q + 1]);
+      nt_store2(orow + ld + 32 * q, v1[2 * q], v1[2 * q + 1]);
     }
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      uint16_t *orow = out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 2 * ty);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const uint32_t lo = mis[2 * g][c >> 1], hi = mis[2 * g + 1][c >> 1];
-        const uint32_t pk = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-        *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - pk;
-      }
-    }
+    for (int c = 0; c < 8; ++c)
+      nt_store2(out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 32 * g + 2 * ty), v0[c], v1[c]);
   }
-  K2_STAMP(3);
-#undef tx
-#undef ty
 }
-
-// ---- the same hand-scheduled 12-plane loop for the SHARD / row-block modes (uint16 output, no mirror): VERDICT r2 item 2's last part ----
-// Tile geometry of k_mh_compare's non-symmetric mode (cyclic tile rows of a rank, folded shard rows, upper_only); takes the tiles that lie
-// completely inside the matrix and the row range and whose 4-byte stores are aligned (s12_takes) -- the compiled kernel runs with only_edge = 1
-// on the same grid and returns at once for those.
-__device__ __forceinline__ bool s12_takes(int64_t I0, int64_t J0, int64_t n, int64_t row_end, int64_t ld, int64_t Jloc, const void *out) {
-  return I0 != J0 &&                                             // a diagonal tile: the general kernel forces count(i, i) = n_hash (singleton codes never match)
-         I0 + K2_TILE <= (row_end < n ? row_end : n) && J0 + K2_TILE <= n && (ld & 1) == 0 && (Jloc & 1) == 0 &&
-         (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+// the lane's counters of tile column 32 (c >> 1) + 2 tx + (c & 1) in rows 32 g + 2 ty + {0, 1}, packed like a row's: the transposed tile
+__device__ __forceinline__ uint32_t mis_col(const uint32_t (&mis)[8][4], int g, int c) {
+  const uint32_t lo = mis[2 * g][c >> 1], hi = mis[2 * g + 1][c >> 1];
+  const uint32_t pk = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
+  return pk;
 }
-struct RectTile { int ti, tj; bool valid; int64_t I0, J0, Iloc, Jloc; };
-__device__ __forceinline__ RectTile decode_rect_tile(int64_t bid, int64_t n, int64_t row_begin, int64_t row_end, int tile_stride, int upper_only, int TR,
-                                                     int fold_q, int64_t fold_w, int band) {
-  RectTile t{0, 0, false, 0, 0, 0, 0};
-  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
-  const uint32_t per_band = (uint32_t)band * (uint32_t)T;
-  const uint32_t k = (uint32_t)(bid >> 3);
-  const uint32_t kb = k / per_band;
-  const int r0 = ((int)(bid & 7) + 8 * (int)kb) * band;
-  const int l = (int)(k - kb * per_band);
-  const int h = (TR - r0 < band) ? (TR - r0) : band;
-  if (h <= 0) return t;
-  t.tj = __builtin_amdgcn_readfirstlane(div_small(l, h));               // wave-uniform by construction: scalars, so that nothing of the tile's
-  t.ti = __builtin_amdgcn_readfirstlane(r0 + (l - t.tj * h));           // geometry sits in a VGPR across the loop block (it clobbers the file)
-  if (t.tj >= T) return t;
-  t.I0 = row_begin + (int64_t)t.ti * tile_stride * K2_TILE;
-  t.J0 = (int64_t)t.tj * K2_TILE;
-  t.Iloc = (int64_t)t.ti * K2_TILE - t.I0;
-  t.Jloc = 0;
-  if (fold_q > 0) {
-    const int q = t.ti;
-    const bool front = q <= fold_q - 1 - q;
-    t.Iloc = (int64_t)(front ? q : fold_q - 1 - q) * K2_TILE - t.I0;
-    t.Jloc = front ? -t.I0 : shard_back(fold_w, n);
-  }
-  if (t.I0 >= row_end || t.I0 >= n) return t;
-  if (upper_only && t.J0 + K2_TILE <= t.I0) return t;
-  t.valid = true;
-  return t;
-}
-__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s12(const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
-                                                                  int64_t row_end, int tile_stride, int upper_only, int TR, uint16_t *__restrict__ out,
-                                                                  int64_t ld, int fold_q, int64_t fold_w, int band) {
-  constexpr int PL = 12, SEGS = 3, STAGE_UNITS = 2 * K2_TILE * SEGS;
-  __shared__ __attribute__((aligned(16))) uint4 lds_ab[3 * STAGE_UNITS];   // 36 KiB ring
-  const RectTile rt = decode_rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band);
-  if (!rt.valid || !s12_takes(rt.I0, rt.J0, n, row_end, ld, rt.Jloc, out)) return;
-  const int64_t I0 = rt.I0, J0 = rt.J0;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tx = ((wave & 1) << 3) + (lane & 7), ty = ((wave >> 1) << 3) + (lane >> 3);
-  const PlaneGeom pg = plane_geom(n, n_hash, PL);
-  // DMA source of this lane in the wave's first instruction of stage 0; instructions q = 1, 2 read 1 KiB and 2 KiB
-  // further (the operand is stored in staging order), stage s reads 128 * 12 words further
-  const int u = wave * SEGS * 64 + lane, sl0 = u / SEGS, sl = sl0 & 127;
-  const uint32_t *src = planes + (sl0 < 128 ? 0 : pg.copy_words) +
-                        plane_unit_word(pg, (sl0 < 128 ? I0 : J0) + k2_row_of_slot(sl), 0, u - sl0 * SEGS);
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)lds_ab);
-  const uint32_t a_off = lds_base + (uint32_t)(ty * SEGS * 16);
-  const uint32_t b_off = lds_base + (uint32_t)((K2_TILE * SEGS + tx * SEGS) * 16);
-  const uint32_t src_lo = (uint32_t)reinterpret_cast<uintptr_t>(src), src_hi = (uint32_t)(reinterpret_cast<uintptr_t>(src) >> 32);
-  const uint32_t wb = (uint32_t)tid * 4u;
-  const uint32_t nstage = (uint32_t)((n_hash + K2_GROUP - 1) / K2_GROUP), stage_bytes = 128u * PL * 4u;
-  const uint32_t wave_id = __builtin_amdgcn_readfirstlane((uint32_t)wave);
-  const uint32_t src_lo_u = __builtin_amdgcn_readfirstlane(src_lo), src_hi_u = __builtin_amdgcn_readfirstlane(src_hi);   // lane 0's source
-  // the lane's 32 packed mismatch counters (columns 2j, 2j+1 per register) leave the block in v64..v95
-  uint32_t mis[8][4];
-  uint32_t tid_after;
-  {
-    register uint32_t r120 asm("v120") = a_off;
-    register uint32_t r121 asm("v121") = b_off;
-    register uint32_t r122 asm("v122") = src_lo;
-    register uint32_t r123 asm("v123") = src_hi;
-    register uint32_t r124 asm("v124") = wb;
-#define K2_CNT(i) register uint32_t c##i asm("v" #i);
-    K2_CNT(64) K2_CNT(65) K2_CNT(66) K2_CNT(67) K2_CNT(68) K2_CNT(69) K2_CNT(70) K2_CNT(71) K2_CNT(72) K2_CNT(73) K2_CNT(74)
-    K2_CNT(75) K2_CNT(76) K2_CNT(77) K2_CNT(78) K2_CNT(79) K2_CNT(80) K2_CNT(81) K2_CNT(82) K2_CNT(83) K2_CNT(84) K2_CNT(85)
-    K2_CNT(86) K2_CNT(87) K2_CNT(88) K2_CNT(89) K2_CNT(90) K2_CNT(91) K2_CNT(92) K2_CNT(93) K2_CNT(94) K2_CNT(95)
-#undef K2_CNT
-    asm volatile(
-#include K2_LOOP_INC
-        : "+v"(r122), "+v"(r123),                                // the block reuses them as an operand buffer
-          "=v"(c64), "=v"(c65), "=v"(c66), "=v"(c67), "=v"(c68), "=v"(c69), "=v"(c70), "=v"(c71), "=v"(c72), "=v"(c73), "=v"(c74),
-          "=v"(c75), "=v"(c76), "=v"(c77), "=v"(c78), "=v"(c79), "=v"(c80), "=v"(c81), "=v"(c82), "=v"(c83), "=v"(c84), "=v"(c85),
-          "=v"(c86), "=v"(c87), "=v"(c88), "=v"(c89), "=v"(c90), "=v"(c91), "=v"(c92), "=v"(c93), "=v"(c94), "=v"(c95)
-        : [lb] "s"(lds_base), [ns] "s"(nstage), [st] "s"(stage_bytes), [wv] "s"(wave_id), [sl] "s"(src_lo_u), [sh] "s"(src_hi_u),
-          "v"(r120), "v"(r121), "v"(r124)
-        : "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "v125",   // m0 is saved in s47 and restored by the block
-          "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",
-          "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39",
-          "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59",
-          "v60", "v61", "v62", "v63", "v96", "v97", "v98", "v99",
-          "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116",
-          "v117", "v118", "v119");
-    // everything lane-dependent the epilogue needs is re-derived from v124 (4 * thread id), which survives the block:
-    // nothing per-lane has to live across it (the block clobbers all but four VGPRs; hipcc spilled to scratch otherwise)
-    asm volatile("" : "+v"(r124));
-    tid_after = r124 >> 2;
-    const uint32_t cnt[32] = {c64, c65, c66, c67, c68, c69, c70, c71, c72, c73, c74, c75, c76, c77, c78, c79,
-                              c80, c81, c82, c83, c84, c85, c86, c87, c88, c89, c90, c91, c92, c93, c94, c95};
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) mis[r][c] = cnt[4 * r + c];
-  }
-  const uint32_t nn = (uint32_t)n_hash * 0x10001u;             // two match counts per register (no borrow: each <= n_hash)
-  const int tid_e = (int)tid_after, wave_e = tid_e >> 6, lane_e = tid_e & 63;
-  const int tx_e = ((wave_e & 1) << 3) + (lane_e & 7), ty_e = ((wave_e >> 1) << 3) + (lane_e >> 3);
+// uint16: two adjacent counts per 4-byte store, direct (at Iloc / Jloc) and, with mirror, the transposed tile
+__device__ __forceinline__ void store_counts_u16(uint16_t *out, int64_t ld, const uint32_t (&mis)[8][4], uint32_t nn, int64_t I0, int64_t J0,
+                                               int64_t Iloc, int64_t Jloc, int tx, int ty, bool mirror) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    uint16_t *orow = out + (I0 + 32 * (r >> 1) + 2 * ty_e + (r & 1) + rt.Iloc) * ld + (rt.Jloc + J0 + 2 * tx_e);
+    uint16_t *orow = out + (I0 + 32 * (r >> 1) + 2 * ty + (r & 1) + Iloc) * ld + (Jloc + J0 + 2 * tx);
 #pragma unroll
     for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis[r][g];
   }
+  if (!mirror) return;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    uint16_t *orow = out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 2 * ty);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis_col(mis, g, c);
+  }
 }
 
-// ---- 16 code planes (uniform-like data) with the same hand-allocated loop ---------------------------------------
-// k_mh_compare<.., 16> needs 168 VGPRs = 3 waves per SIMD (34.6 ms at N = 100k).  The generated block (K2ASM_PLANES=16,
-// k2_loop_p16.inc: 8 two-plane steps per stage) reads the PADDED twin of the operand (da_common.hpp: 80-byte slots), stages
-// it through a ring of TWO 20 KiB stages (40 KiB: four workgroups per CU) with five 1 KiB DMA pieces per wave and stage from a
-// wave-uniform SGPR base, and hands the counters over in v64..v95 like k_mh_compare_a12.  Symmetric mode, interior
-// off-diagonal tiles (a12_takes); diagonal / border tiles stay with k_mh_compare<.., 16> on the regular copies.
+// ---- the hand-allocated stage loops (tools/gen_k2_asm.py) ----------------------------------------------------------------------
+// hipcc needs ~30 VGPRs more than the loop strictly does, which pins k_mh_compare at 168 VGPRs = 3 waves per SIMD
+// -- an odd wave count, which costs the gfx950 VALU a quarter of its issue slots (tools/ubench/k2_inner2).  A generated block is the
+// whole stage loop (DMA issue, counted waits, barriers, plane loop with 8-byte operands, popcounts) as ONE asm statement with a fixed
+// register map: 116 + 10 VGPRs, so 4 workgroups per CU = 4 waves per SIMD.  It takes the lane's first row / column operand inside a
+// stage in v120 / v121, 4 * thread id in v124 and the stage geometry in scalars, and leaves the lane's 32 packed mismatch counters
+// (columns 2j, 2j+1 per register) in v64..v95.  The blocks:
+//   K2_P12         k2_loop_p12.inc: 12 planes, a ring of three 12 KiB stages; per-lane DMA source in v122 / v123 (then an operand buffer)
+//   K2_P14 .. P16  the PADDED 16-plane twin of the operand (da_common.hpp: 80-byte slots): a ring of TWO 20 KiB stages, five 1 KiB DMA
+//                  pieces per wave and stage from a wave-uniform SGPR base; 14 / 15 code bits leave out the zero top planes
+//   K2_P12P        persistent (k2_loop_p12p.inc): issues the NEXT tile's first two stages (source nl / nh) during the current tile's
+//                  last two and waits for them before it ends; fl = flags (bit 0: first tile, bit 1: a next tile), sp = ring phase
+//   K2_P8P, K2_P8  the same on 8 planes (the dense half of the heavy / rare split; 32-byte slots, a 24 KiB ring): the band kernel's
+//                  block, and the one-tile form with the stage loop at wave priority 2
+// (the one-tile blocks' values are their code bits)
+#ifndef K2_LOOP_INC
+#define K2_LOOP_INC "k2_loop_p12.inc"
+#endif
 #ifndef K2_LOOP_INC_14
-#define K2_LOOP_INC_14 "k2_loop_p14.inc"   // the same block with seven two-plane steps: 14-bit codes, planes 14 / 15 of the operand are zero
+#define K2_LOOP_INC_14 "k2_loop_p14.inc"   // seven two-plane steps: 14-bit codes, planes 14 / 15 of the operand are zero
 #endif
 #ifndef K2_LOOP_INC_15
 #define K2_LOOP_INC_15 "k2_loop_p15.inc"   // eight steps, the last one on plane 14 only: 15-bit codes
@@ -635,208 +478,200 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s12(const uint32_t
 #ifndef K2_LOOP_INC_16
 #define K2_LOOP_INC_16 "k2_loop_p16.inc"
 #endif
-constexpr int K2_A16_TABLE_MAX = 2 * 2 * K2_TILE * 80 / 8;   // doubles that fit the 40 KiB ring
-template <bool F64, int CODE_BITS = 16>
-__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a16(const uint32_t *__restrict__ planes, int64_t n, int n_hash,
-                                                                  void *__restrict__ out_v, int64_t ld, int64_t ntiles,
-                                                                  int64_t per_xcd) {
-  constexpr int SLOT = 80, STAGE_BYTES = 2 * K2_TILE * SLOT;
-  __shared__ __attribute__((aligned(16))) uint4 lds_ab[2 * STAGE_BYTES / 16];   // 40 KiB ring; afterwards the ratio table
-  static_assert(sizeof(lds_ab) / (sizeof(double)) == K2_A16_TABLE_MAX, "launch_mh_compare's table guard must match the ring size");
-  const int64_t bid = blockIdx.x;
-  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
-  const int64_t L = (bid & 7) * per_xcd + (bid >> 3);
-  if (L >= ntiles) return;
-  const TileId tl = decode_tile(L, T, T, true);
-  if (!tl.valid || !a12_takes(tl.ti, tl.tj, n, ld, out_v, F64)) return;
-  const int64_t I0 = (int64_t)tl.ti * K2_TILE, J0 = (int64_t)tl.tj * K2_TILE;
+#ifndef K2_LOOP_INC_P
+#define K2_LOOP_INC_P "k2_loop_p12p.inc"
+#endif
+enum K2Block { K2_P12 = 12, K2_P14 = 14, K2_P15 = 15, K2_P16 = 16, K2_P12P, K2_P8P, K2_P8 };
+struct K2Scalars { uint32_t lb, ns, st, wv, sl, sh; };   // LDS ring base, stages, source bytes per stage, wave id, DMA source (lane 0's / the wave's)
+struct K2Next { uint32_t nl, nh, fl, sp; };               // persistent blocks only
+// Runs block B and returns v124 as the block left it: everything lane-dependent after the block is re-derived from that value, so
+// nothing per-lane has to live across it (the block clobbers all but five VGPRs; hipcc spilled to scratch otherwise).
+template <K2Block B>
+__device__ __forceinline__ uint32_t k2_block(uint32_t (&mis)[8][4], const K2Scalars &s, uint32_t a_off, uint32_t b_off, uint32_t v124,
+                                             uint32_t src_lo = 0, uint32_t src_hi = 0, const K2Next &x = {}) {
+  register uint32_t r120 asm("v120") = a_off;
+  register uint32_t r121 asm("v121") = b_off;
+  register uint32_t r124 asm("v124") = v124;
+#define K2_CNT(i) register uint32_t c##i asm("v" #i);
+  K2_CNT(64) K2_CNT(65) K2_CNT(66) K2_CNT(67) K2_CNT(68) K2_CNT(69) K2_CNT(70) K2_CNT(71) K2_CNT(72) K2_CNT(73) K2_CNT(74)
+  K2_CNT(75) K2_CNT(76) K2_CNT(77) K2_CNT(78) K2_CNT(79) K2_CNT(80) K2_CNT(81) K2_CNT(82) K2_CNT(83) K2_CNT(84) K2_CNT(85)
+  K2_CNT(86) K2_CNT(87) K2_CNT(88) K2_CNT(89) K2_CNT(90) K2_CNT(91) K2_CNT(92) K2_CNT(93) K2_CNT(94) K2_CNT(95)
+#undef K2_CNT
+#define K2_OUT                                                                                                                  \
+  "=v"(c64), "=v"(c65), "=v"(c66), "=v"(c67), "=v"(c68), "=v"(c69), "=v"(c70), "=v"(c71), "=v"(c72), "=v"(c73), "=v"(c74),     \
+      "=v"(c75), "=v"(c76), "=v"(c77), "=v"(c78), "=v"(c79), "=v"(c80), "=v"(c81), "=v"(c82), "=v"(c83), "=v"(c84), "=v"(c85), \
+      "=v"(c86), "=v"(c87), "=v"(c88), "=v"(c89), "=v"(c90), "=v"(c91), "=v"(c92), "=v"(c93), "=v"(c94), "=v"(c95)
+#define K2_IN [lb] "s"(s.lb), [ns] "s"(s.ns), [st] "s"(s.st), [wv] "s"(s.wv), [sl] "s"(s.sl), [sh] "s"(s.sh)
+#define K2_VIN "v"(r120), "v"(r121), "v"(r124)
+#define K2_CLOBBER   /* m0 is saved in s47 and restored by the block */                                                                          \
+  "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "v125",                            \
+      "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",           \
+      "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", \
+      "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", \
+      "v60", "v61", "v62", "v63", "v96", "v97", "v98", "v99",                                                                                     \
+      "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116",     \
+      "v117", "v118", "v119"
+#define K2_UNIFORM : K2_OUT : K2_IN, K2_VIN : K2_CLOBBER, "v122", "v123"
+#define K2_PERSIST : K2_OUT : K2_IN, [nl] "s"(x.nl), [nh] "s"(x.nh), [fl] "s"(x.fl), [sp] "s"(x.sp), K2_VIN : K2_CLOBBER, "v122", "v123"
+  if constexpr (B == K2_P12) {
+    register uint32_t r122 asm("v122") = src_lo;
+    register uint32_t r123 asm("v123") = src_hi;
+    asm volatile(
+#include K2_LOOP_INC
+        : "+v"(r122), "+v"(r123), K2_OUT : K2_IN, K2_VIN : K2_CLOBBER);
+  } else if constexpr (B == K2_P14) {
+    asm volatile(
+#include K2_LOOP_INC_14
+        K2_UNIFORM);
+  } else if constexpr (B == K2_P15) {
+    asm volatile(
+#include K2_LOOP_INC_15
+        K2_UNIFORM);
+  } else if constexpr (B == K2_P16) {
+    asm volatile(
+#include K2_LOOP_INC_16
+        K2_UNIFORM);
+  } else if constexpr (B == K2_P12P) {
+    asm volatile(
+#include K2_LOOP_INC_P
+        K2_PERSIST);
+  } else if constexpr (B == K2_P8P) {
+    asm volatile(
+#include "k2_loop_p8p.inc"
+        K2_PERSIST);
+  } else {
+    static_assert(B == K2_P8, "a generated block");
+    asm volatile(
+#include "k2_loop_p8.inc"
+        K2_PERSIST);
+  }
+#undef K2_PERSIST
+#undef K2_UNIFORM
+#undef K2_CLOBBER
+#undef K2_VIN
+#undef K2_IN
+#undef K2_OUT
+  asm volatile("" : "+v"(r124));
+  const uint32_t cnt[32] = {c64, c65, c66, c67, c68, c69, c70, c71, c72, c73, c74, c75, c76, c77, c78, c79,
+                            c80, c81, c82, c83, c84, c85, c86, c87, c88, c89, c90, c91, c92, c93, c94, c95};
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) mis[r][c] = cnt[4 * r + c];
+  return r124;
+}
+
+// ---- one tile per workgroup behind a generated block: k_mh_compare_a12 / _s12 (K2_P12) and k_mh_compare_a16 / _s16 (K2_P14 .. P16) ----
+// SYM: the symmetric matrix (sym_tile), stored direct + mirrored as float64 (the count -> double table is built in the ring once every
+// wave has left it: n_hash + 1 <= K2_A12_TABLE_MAX / K2_A16_TABLE_MAX), uint16, or into the packed table (PK; ld = its pk_lo_bytes).
+// Otherwise the rect geometry of the shard / row-block modes (rect_tile): uint16, direct only.  Diagonal and border tiles stay with
+// k_mh_compare (only_edge = 1).
+#ifndef K2_PRO_PRIO
+#define K2_PRO_PRIO 0     // wave priority of the tile prologue (decode + address arithmetic before the stage loop)
+#endif
+__device__ __forceinline__ void k2_entry() {                 // a one-tile kernel's first instructions, ahead of the tile decode
+  if (K2_PRO_PRIO) __builtin_amdgcn_s_setprio(K2_PRO_PRIO);
+  K2_STAMP(0);
+  K2_STAMP_HW();
+}
+constexpr int K2_A12_TABLE_MAX = 3 * 2 * K2_TILE * 3 * 16 / 8;   // doubles that fit the 12-plane ring (3 stages x 256 rows x 48 B)
+constexpr int K2_A16_TABLE_MAX = 2 * 2 * K2_TILE * 80 / 8;       // ... the 16-plane ring (2 stages x 256 rows x 80 B)
+template <K2Block B, bool SYM, bool F64, bool PK>
+__device__ __forceinline__ void k2_one_tile(const uint32_t *planes, int64_t n, int n_hash, void *out_v, int64_t ld, const RectTile &t) {
+  static_assert(B == K2_P12 || B == K2_P14 || B == K2_P15 || B == K2_P16, "a one-tile block");
+  static_assert(SYM || (!F64 && !PK), "the rect geometry stores uint16 counts");
+  constexpr int PL = 12, SEGS = 3, SLOT = B == K2_P12 ? 4 * PL : 80;   // LDS bytes of a row or column per stage
+  __shared__ __attribute__((aligned(16))) uint4 lds_ab[(B == K2_P12 ? 3 : 2) * 2 * K2_TILE * SLOT / 16];   // the ring; afterwards the table
+  static_assert(sizeof(lds_ab) / (sizeof(double)) == (B == K2_P12 ? K2_A12_TABLE_MAX : K2_A16_TABLE_MAX),
+                "launch_mh_compare's table guard must match the ring size");
+  if (!t.valid) return;
+  if (!F64) K2_STAMP(6);                                      // (timing build, uint16 kind: prologue split)
+  const int64_t I0 = t.I0, J0 = t.J0;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tx0 = ((wave & 1) << 3) + (lane & 7), ty0 = ((wave >> 1) << 3) + (lane >> 3);
-  // wave-uniform DMA source: wave w stages LDS slots [64w, 64w + 64) = rows (w < 2, row copy) or columns (w >= 2, column copy)
+  const int tx = ((wave & 1) << 3) + (lane & 7), ty = ((wave >> 1) << 3) + (lane >> 3);
   const uint32_t wave_u = __builtin_amdgcn_readfirstlane((uint32_t)wave);
   const uint32_t nstage = (uint32_t)((n_hash + K2_GROUP - 1) / K2_GROUP), stage_bytes = (uint32_t)(K2_TILE * SLOT);
-  const uint64_t src = reinterpret_cast<uint64_t>(planes) +
-                       4u * (uint64_t)(pad16_base_words(n, n_hash) + (wave_u >= 2 ? pad16_copy_words(n, n_hash) : 0)) +
-                       (uint64_t)(wave_u >= 2 ? tl.tj : tl.ti) * nstage * stage_bytes + (wave_u & 1u) * (64u * SLOT);
-  const uint32_t sl = __builtin_amdgcn_readfirstlane((uint32_t)src), sh = __builtin_amdgcn_readfirstlane((uint32_t)(src >> 32));
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)lds_ab);
-  uint32_t mis[8][4];
-  uint32_t tid_after;
-  {
-    register uint32_t r120 asm("v120") = lds_base + (uint32_t)(ty0 * SLOT);
-    register uint32_t r121 asm("v121") = lds_base + (uint32_t)((K2_TILE + tx0) * SLOT);
-    register uint32_t r124 asm("v124") = (uint32_t)tid * 4u;
-#define K2_CNT(i) register uint32_t c##i asm("v" #i);
-    K2_CNT(64) K2_CNT(65) K2_CNT(66) K2_CNT(67) K2_CNT(68) K2_CNT(69) K2_CNT(70) K2_CNT(71) K2_CNT(72) K2_CNT(73) K2_CNT(74)
-    K2_CNT(75) K2_CNT(76) K2_CNT(77) K2_CNT(78) K2_CNT(79) K2_CNT(80) K2_CNT(81) K2_CNT(82) K2_CNT(83) K2_CNT(84) K2_CNT(85)
-    K2_CNT(86) K2_CNT(87) K2_CNT(88) K2_CNT(89) K2_CNT(90) K2_CNT(91) K2_CNT(92) K2_CNT(93) K2_CNT(94) K2_CNT(95)
-#undef K2_CNT
-#define K2_A16_OPERANDS                                                                                                                      \
-        : "=v"(c64), "=v"(c65), "=v"(c66), "=v"(c67), "=v"(c68), "=v"(c69), "=v"(c70), "=v"(c71), "=v"(c72), "=v"(c73), "=v"(c74),  \
-          "=v"(c75), "=v"(c76), "=v"(c77), "=v"(c78), "=v"(c79), "=v"(c80), "=v"(c81), "=v"(c82), "=v"(c83), "=v"(c84), "=v"(c85),  \
-          "=v"(c86), "=v"(c87), "=v"(c88), "=v"(c89), "=v"(c90), "=v"(c91), "=v"(c92), "=v"(c93), "=v"(c94), "=v"(c95)  \
-        : [lb] "s"(lds_base), [ns] "s"(nstage), [st] "s"(stage_bytes), [wv] "s"(wave_u), [sl] "s"(sl), [sh] "s"(sh),  \
-          "v"(r120), "v"(r121), "v"(r124)  \
-        : "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "v125",  \
-          "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",  \
-          "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39",  \
-          "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59",  \
-          "v60", "v61", "v62", "v63", "v96", "v97", "v98", "v99",  \
-          "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116",  \
-          "v117", "v118", "v119", "v122", "v123"
-    if (CODE_BITS == 14) {
-      asm volatile(
-#include K2_LOOP_INC_14
-          K2_A16_OPERANDS);
-    } else if (CODE_BITS == 15) {
-      asm volatile(
-#include K2_LOOP_INC_15
-          K2_A16_OPERANDS);
-    } else {
-      asm volatile(
-#include K2_LOOP_INC_16
-          K2_A16_OPERANDS);
-    }
-#undef K2_A16_OPERANDS
-    asm volatile("" : "+v"(r124));                               // lane ids are re-derived from the value that crossed the block
-    tid_after = r124 >> 2;
-    const uint32_t cnt[32] = {c64, c65, c66, c67, c68, c69, c70, c71, c72, c73, c74, c75, c76, c77, c78, c79,
-                              c80, c81, c82, c83, c84, c85, c86, c87, c88, c89, c90, c91, c92, c93, c94, c95};
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) mis[r][c] = cnt[4 * r + c];
+  uint32_t src_lo = 0, src_hi = 0, sl, sh;
+  if constexpr (B == K2_P12) {
+    // DMA source of this lane in the wave's first instruction of stage 0; instructions q = 1, 2 read 1 KiB and 2 KiB
+    // further (the operand is stored in staging order), stage s reads 128 * 12 words further
+    const PlaneGeom pg = plane_geom(n, n_hash, PL);
+    const int u = wave * SEGS * 64 + lane, sl0 = u / SEGS, slot = sl0 & 127;
+    const uint32_t *src = planes + (sl0 < 128 ? 0 : pg.copy_words) +
+                          plane_unit_word(pg, (sl0 < 128 ? I0 : J0) + k2_row_of_slot(slot), 0, u - sl0 * SEGS);
+    src_lo = (uint32_t)reinterpret_cast<uintptr_t>(src);
+    src_hi = (uint32_t)(reinterpret_cast<uintptr_t>(src) >> 32);
+    sl = __builtin_amdgcn_readfirstlane(src_lo);             // lane 0's source
+    sh = __builtin_amdgcn_readfirstlane(src_hi);
+  } else {
+    // wave-uniform: wave w stages LDS slots [64w, 64w + 64) = rows (w < 2, row copy) or columns (w >= 2, column copy) of the padded twin
+    const uint64_t blk = SYM ? (uint64_t)(wave_u >= 2 ? t.tj : t.ti) : (uint64_t)((wave_u >= 2 ? J0 : I0) / K2_TILE);
+    const uint64_t src = reinterpret_cast<uint64_t>(planes) +
+                         4u * (uint64_t)(pad16_base_words(n, n_hash) + (wave_u >= 2 ? pad16_copy_words(n, n_hash) : 0)) +
+                         blk * nstage * stage_bytes + (wave_u & 1u) * (64u * SLOT);
+    sl = __builtin_amdgcn_readfirstlane((uint32_t)src);
+    sh = __builtin_amdgcn_readfirstlane((uint32_t)(src >> 32));
   }
-  const uint32_t nn = (uint32_t)n_hash * 0x10001u;             // two match counts per register (no borrow: each <= n_hash)
-  const int tid_e = (int)tid_after, wave_e = tid_e >> 6, lane_e = tid_e & 63;
-  const int tx = ((wave_e & 1) << 3) + (lane_e & 7), ty = ((wave_e >> 1) << 3) + (lane_e >> 3);
-  if (F64) {
+  if (!F64) K2_STAMP(7);
+  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)lds_ab);
+  K2_STAMP(1);
+  uint32_t mis[8][4];
+  const uint32_t v124 = k2_block<B>(mis, {lds_base, nstage, stage_bytes, wave_u, sl, sh}, lds_base + (uint32_t)(ty * SLOT),
+                                    lds_base + (uint32_t)((K2_TILE + tx) * SLOT), (uint32_t)tid * 4u, src_lo, src_hi);
+  K2_STAMP(2);
+  const uint32_t nn = (uint32_t)n_hash * 0x10001u;
+  // lane coordinates again, from the value that crossed the block (same formulas as above)
+  const int tid_e = (int)(v124 >> 2), wave_e = tid_e >> 6, lane_e = tid_e & 63;
+  const int tx_e = ((wave_e & 1) << 3) + (lane_e & 7), ty_e = ((wave_e >> 1) << 3) + (lane_e >> 3);
+  if constexpr (!SYM) {
+    store_counts_u16(static_cast<uint16_t *>(out_v), ld, mis, nn, I0, J0, t.Iloc, t.Jloc, tx_e, ty_e, false);
+  } else if constexpr (PK) {
+    store_tile_pk(reinterpret_cast<uint16_t *>(lds_ab), mis, nn, tid_e, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
+  } else if constexpr (F64) {
     double *ratio = reinterpret_cast<double *>(lds_ab);
     __syncthreads();                                           // everyone has left the ring: the area becomes the table
     for (int c = tid_e; c <= n_hash; c += K2_THREADS) ratio[c] = (double)c / (double)n_hash;   // src/minHash.cpp:174
     __syncthreads();
-    const char *tb = reinterpret_cast<const char *>(ratio);
-    double *out = reinterpret_cast<double *>(out_v);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {                              // two of the lane's rows at a time keeps the epilogue in 128 VGPRs
-      double v0[8], v1[8];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint32_t m0 = nn - mis[2 * g][c], m1 = nn - mis[2 * g + 1][c];
-        v0[2 * c] = *reinterpret_cast<const double *>(tb + ((m0 << 3) & 0x7fff8u));
-        v0[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m0 >> 13) & 0x7fff8u));
-        v1[2 * c] = *reinterpret_cast<const double *>(tb + ((m1 << 3) & 0x7fff8u));
-        v1[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m1 >> 13) & 0x7fff8u));
-      }
-      double *orow = out + (I0 + 32 * g + 2 * ty) * ld + (J0 + 2 * tx);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        nt_store2(orow + 32 * q, v0[2 * q], v0[2 * q + 1]);
-        nt_store2(orow + ld + 32 * q, v1[2 * q], v1[2 * q + 1]);
-      }
-#pragma unroll
-      for (int c = 0; c < 8; ++c)                              // mirrored store (src/minHash.cpp:176)
-        nt_store2(out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 32 * g + 2 * ty), v0[c], v1[c]);
-    }
+    K2_STAMP(6);
+    K2_STAMP(7);
+    store_counts_f64(static_cast<double *>(out_v), ld, reinterpret_cast<const char *>(ratio), mis, nn, I0, J0, tx_e, ty_e);
   } else {
-    uint16_t *out = reinterpret_cast<uint16_t *>(out_v);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      uint16_t *orow = out + (I0 + 32 * (r >> 1) + 2 * ty + (r & 1)) * ld + (J0 + 2 * tx);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis[r][g];
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      uint16_t *orow = out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 2 * ty);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const uint32_t lo = mis[2 * g][c >> 1], hi = mis[2 * g + 1][c >> 1];
-        const uint32_t pk = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-        *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - pk;
-      }
-    }
+    store_counts_u16(static_cast<uint16_t *>(out_v), ld, mis, nn, I0, J0, 0, 0, tx_e, ty_e, true);
   }
+  K2_STAMP(3);
 }
-
-// ---- the 16-plane loop for the SHARD / row-block modes (uint16 output, no mirror): k_mh_compare_s12's tile geometry in front of
-// k_mh_compare_a16's block (round 4: the per-rank compare of inputs whose column dictionaries need 14 - 16 code bits -- uniform
-// peptides -- ran the compiled kernel).  Takes what s12_takes takes; the compiled kernel keeps diagonal / border tiles (only_edge).
+// symmetric, 12 planes
+template <bool F64, bool PK = false>   // PK: uint16 counts into the packed table (out_v; ld = its pk_lo_bytes)
+__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a12(const uint32_t *__restrict__ planes, int64_t n, int n_hash,
+                                                                  void *__restrict__ out_v, int64_t ld, int64_t ntiles,
+                                                                  int64_t per_xcd) {
+  k2_entry();
+  k2_one_tile<K2_P12, true, F64, PK>(planes, n, n_hash, out_v, ld, sym_tile(n, ld, out_v, ntiles, per_xcd, F64 || PK));
+}
+// shard / row-block modes, 12 planes (what the sharded routes compute per rank)
+__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s12(const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
+                                                                  int64_t row_end, int tile_stride, int upper_only, int TR, uint16_t *__restrict__ out,
+                                                                  int64_t ld, int fold_q, int64_t fold_w, int band) {
+  k2_entry();
+  k2_one_tile<K2_P12, false, false, false>(planes, n, n_hash, out, ld,
+                                           rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band, ld, out));
+}
+// symmetric, 14 - 16 code bits (uniform-like data; k_mh_compare<.., 16> needs 168 VGPRs = 3 waves per SIMD)
+template <bool F64, int CODE_BITS = 16>
+__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_a16(const uint32_t *__restrict__ planes, int64_t n, int n_hash,
+                                                                  void *__restrict__ out_v, int64_t ld, int64_t ntiles,
+                                                                  int64_t per_xcd) {
+  k2_entry();
+  k2_one_tile<K2Block(CODE_BITS), true, F64, false>(planes, n, n_hash, out_v, ld, sym_tile(n, ld, out_v, ntiles, per_xcd, F64));
+}
+// shard / row-block modes, 14 - 16 code bits (the per-rank compare of inputs whose column dictionaries need them: uniform peptides)
 template <int CODE_BITS>
 __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s16(const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
                                                                   int64_t row_end, int tile_stride, int upper_only, int TR, uint16_t *__restrict__ out,
                                                                   int64_t ld, int fold_q, int64_t fold_w, int band) {
-  constexpr int SLOT = 80, STAGE_BYTES = 2 * K2_TILE * SLOT;
-  __shared__ __attribute__((aligned(16))) uint4 lds_ab[2 * STAGE_BYTES / 16];   // 40 KiB ring
-  const RectTile rt = decode_rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band);
-  if (!rt.valid || !s12_takes(rt.I0, rt.J0, n, row_end, ld, rt.Jloc, out)) return;
-  const int64_t I0 = rt.I0, J0 = rt.J0;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int tx0 = ((wave & 1) << 3) + (lane & 7), ty0 = ((wave >> 1) << 3) + (lane >> 3);
-  // wave-uniform DMA source: wave w stages LDS slots [64w, 64w + 64) = rows (w < 2, row copy) or columns (w >= 2, column copy) of the padded twin
-  const uint32_t wave_u = __builtin_amdgcn_readfirstlane((uint32_t)wave);
-  const uint32_t nstage = (uint32_t)((n_hash + K2_GROUP - 1) / K2_GROUP), stage_bytes = (uint32_t)(K2_TILE * SLOT);
-  const uint64_t src = reinterpret_cast<uint64_t>(planes) +
-                       4u * (uint64_t)(pad16_base_words(n, n_hash) + (wave_u >= 2 ? pad16_copy_words(n, n_hash) : 0)) +
-                       (uint64_t)((wave_u >= 2 ? J0 : I0) / K2_TILE) * nstage * stage_bytes + (wave_u & 1u) * (64u * SLOT);
-  const uint32_t sl = __builtin_amdgcn_readfirstlane((uint32_t)src), sh = __builtin_amdgcn_readfirstlane((uint32_t)(src >> 32));
-  const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)lds_ab);
-  uint32_t mis[8][4];
-  uint32_t tid_after;
-  {
-    register uint32_t r120 asm("v120") = lds_base + (uint32_t)(ty0 * SLOT);
-    register uint32_t r121 asm("v121") = lds_base + (uint32_t)((K2_TILE + tx0) * SLOT);
-    register uint32_t r124 asm("v124") = (uint32_t)tid * 4u;
-#define K2_CNT(i) register uint32_t c##i asm("v" #i);
-    K2_CNT(64) K2_CNT(65) K2_CNT(66) K2_CNT(67) K2_CNT(68) K2_CNT(69) K2_CNT(70) K2_CNT(71) K2_CNT(72) K2_CNT(73) K2_CNT(74)
-    K2_CNT(75) K2_CNT(76) K2_CNT(77) K2_CNT(78) K2_CNT(79) K2_CNT(80) K2_CNT(81) K2_CNT(82) K2_CNT(83) K2_CNT(84) K2_CNT(85)
-    K2_CNT(86) K2_CNT(87) K2_CNT(88) K2_CNT(89) K2_CNT(90) K2_CNT(91) K2_CNT(92) K2_CNT(93) K2_CNT(94) K2_CNT(95)
-#undef K2_CNT
-#define K2_S16_OPERANDS                                                                                                                      \
-        : "=v"(c64), "=v"(c65), "=v"(c66), "=v"(c67), "=v"(c68), "=v"(c69), "=v"(c70), "=v"(c71), "=v"(c72), "=v"(c73), "=v"(c74),  \
-          "=v"(c75), "=v"(c76), "=v"(c77), "=v"(c78), "=v"(c79), "=v"(c80), "=v"(c81), "=v"(c82), "=v"(c83), "=v"(c84), "=v"(c85),  \
-          "=v"(c86), "=v"(c87), "=v"(c88), "=v"(c89), "=v"(c90), "=v"(c91), "=v"(c92), "=v"(c93), "=v"(c94), "=v"(c95)  \
-        : [lb] "s"(lds_base), [ns] "s"(nstage), [st] "s"(stage_bytes), [wv] "s"(wave_u), [sl] "s"(sl), [sh] "s"(sh),  \
-          "v"(r120), "v"(r121), "v"(r124)  \
-        : "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "v125",  \
-          "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19",  \
-          "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39",  \
-          "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59",  \
-          "v60", "v61", "v62", "v63", "v96", "v97", "v98", "v99",  \
-          "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116",  \
-          "v117", "v118", "v119", "v122", "v123"
-    if (CODE_BITS == 14) {
-      asm volatile(
-#include K2_LOOP_INC_14
-          K2_S16_OPERANDS);
-    } else if (CODE_BITS == 15) {
-      asm volatile(
-#include K2_LOOP_INC_15
-          K2_S16_OPERANDS);
-    } else {
-      asm volatile(
-#include K2_LOOP_INC_16
-          K2_S16_OPERANDS);
-    }
-#undef K2_S16_OPERANDS
-    asm volatile("" : "+v"(r124));                               // lane ids are re-derived from the value that crossed the block
-    tid_after = r124 >> 2;
-    const uint32_t cnt[32] = {c64, c65, c66, c67, c68, c69, c70, c71, c72, c73, c74, c75, c76, c77, c78, c79,
-                              c80, c81, c82, c83, c84, c85, c86, c87, c88, c89, c90, c91, c92, c93, c94, c95};
-#pragma unroll
-    for (int r = 0; r < 8; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) mis[r][c] = cnt[4 * r + c];
-  }
-  const uint32_t nn = (uint32_t)n_hash * 0x10001u;             // two match counts per register (no borrow: each <= n_hash)
-  const int tid_e = (int)tid_after, wave_e = tid_e >> 6, lane_e = tid_e & 63;
-  const int tx_e = ((wave_e & 1) << 3) + (lane_e & 7), ty_e = ((wave_e >> 1) << 3) + (lane_e >> 3);
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    uint16_t *orow = out + (I0 + 32 * (r >> 1) + 2 * ty_e + (r & 1) + rt.Iloc) * ld + (rt.Jloc + J0 + 2 * tx_e);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis[r][g];
-  }
+  k2_entry();
+  k2_one_tile<K2Block(CODE_BITS), false, false, false>(planes, n, n_hash, out, ld,
+                                                       rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band, ld, out));
 }
 
 // ---- the same 12-plane loop, PERSISTENT: a workgroup walks a sequence of tiles and its DMA ring never drains ----
@@ -851,12 +686,6 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s16(const uint32_t
 // stage 2).  The count -> double table lives in its own 4 KiB of LDS (built once per workgroup; 36 + 4 KiB x 4 workgroups =
 // the CU's 160 KiB), so the epilogue needs no barrier.  float64 output therefore needs n_hash <= 511; larger n_hash and
 // single-stage inputs (n_hash <= 32) stay with k_mh_compare_a12.
-#ifndef K2_LOOP_INC_P
-#define K2_LOOP_INC_P "k2_loop_p12p.inc"
-#endif
-#ifdef K2_DYNAMIC   // experiment: tile ids handed out by a per-XCD atomic counter (a sliding window like the hardware dispatcher's)
-__device__ unsigned int g_k2_next[8];
-#endif
 constexpr int K2_P12_TABLE = 512, K2_P8_TABLE = 2048;
 // PL = 12, or 8: the dense half of the heavy / rare split (round 4; dict_kernels.hip k_hy_split): 32-byte slots, a 24 KiB ring, four two-plane
 // steps per stage -- k2_loop_p8p.inc (band kernel: no wave priority) / k2_loop_p8.inc (ONE = one tile per workgroup, the grid of k_mh_compare_a12:
@@ -904,33 +733,12 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)lds_ab);
   const uint32_t nstage = (uint32_t)((n_hash + K2_GROUP - 1) / K2_GROUP), stage_bytes = 128u * PL * 4u;
   const uint32_t nn = (uint32_t)n_hash * 0x10001u;             // two match counts per register (no borrow: each <= n_hash)
-  register uint32_t r120 asm("v120") = lds_base + (uint32_t)(ty0 * SEGS * 16);                       // the lane's first row operand inside a stage
-  register uint32_t r121 asm("v121") = lds_base + (uint32_t)((K2_TILE * SEGS + tx0 * SEGS) * 16);   // ... first column operand
-  register uint32_t r124 asm("v124") = (uint32_t)tid * 4u;
+  const uint32_t a_off = lds_base + (uint32_t)(ty0 * SEGS * 16);                       // the lane's first row operand inside a stage
+  const uint32_t b_off = lds_base + (uint32_t)((K2_TILE * SEGS + tx0 * SEGS) * 16);   // ... first column operand
+  uint32_t v124 = (uint32_t)tid * 4u;                           // crosses every block: the lane ids are re-derived from it
 
   TileId cur, nxt;
-#ifdef K2_DYNAMIC
-  __shared__ unsigned int s_next[2];
-  int fetch_no = 0;
-  auto next_dyn = [&](TileId &t) -> int {
-    for (;;) {
-      if (tid == 0) s_next[fetch_no & 1] = atomicAdd(&g_k2_next[xcd], 1u);
-      __syncthreads();
-      const int Lq = (int)(tile_begin + (int64_t)xcd * per_xcd) + (int)__builtin_amdgcn_readfirstlane(s_next[fetch_no & 1]);
-      ++fetch_no;
-      if (Lq >= lim) return lim;
-      int To = T;
-      asm volatile("" : "+s"(To));
-      t = decode_tile(Lq, To, To, true);
-      t.ti = __builtin_amdgcn_readfirstlane(t.ti);
-      t.tj = __builtin_amdgcn_readfirstlane(t.tj);
-      if (t.valid && a12_takes(t.ti, t.tj, n, ld, out_v, F64 || PK)) return Lq;
-    }
-  };
-  int L = next_dyn(cur);
-#else
   int L = next_taken((int)(tile_begin + (int64_t)xcd * per_xcd) + slot, cur);
-#endif
   uint32_t flags = 1u, phase = 0u;                             // bit 0: first tile of this workgroup; ring slot of the tile's stage 0
 #ifdef DA_K2_TIMING
   int it_stamp = 0;
@@ -941,118 +749,31 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
 #endif
   while (L < lim) {
     K2P_STAMP(0);
-#ifdef K2_DYNAMIC
-    const int Ln = next_dyn(nxt);
-#else
     const int Ln = next_taken(L + wg_per_xcd, nxt);
-#endif
     if (Ln < lim) flags |= 2u;
     const uint64_t src = source_of(cur), src_n = source_of(nxt);
     const uint32_t sl = __builtin_amdgcn_readfirstlane((uint32_t)src), sh = __builtin_amdgcn_readfirstlane((uint32_t)(src >> 32));
     const uint32_t nl = __builtin_amdgcn_readfirstlane((uint32_t)src_n), nh = __builtin_amdgcn_readfirstlane((uint32_t)(src_n >> 32));
     const uint32_t fl = __builtin_amdgcn_readfirstlane(flags), sp = __builtin_amdgcn_readfirstlane(phase * (uint32_t)(STAGE_UNITS * 16));
     uint32_t mis[8][4];
-    uint32_t tid_after;
     K2P_STAMP(1);
-    {
-#define K2_CNT(i) register uint32_t c##i asm("v" #i);
-      K2_CNT(64) K2_CNT(65) K2_CNT(66) K2_CNT(67) K2_CNT(68) K2_CNT(69) K2_CNT(70) K2_CNT(71) K2_CNT(72) K2_CNT(73) K2_CNT(74)
-      K2_CNT(75) K2_CNT(76) K2_CNT(77) K2_CNT(78) K2_CNT(79) K2_CNT(80) K2_CNT(81) K2_CNT(82) K2_CNT(83) K2_CNT(84) K2_CNT(85)
-      K2_CNT(86) K2_CNT(87) K2_CNT(88) K2_CNT(89) K2_CNT(90) K2_CNT(91) K2_CNT(92) K2_CNT(93) K2_CNT(94) K2_CNT(95)
-#undef K2_CNT
-#define K2P_OPERANDS \
-          : "=v"(c64), "=v"(c65), "=v"(c66), "=v"(c67), "=v"(c68), "=v"(c69), "=v"(c70), "=v"(c71), "=v"(c72), "=v"(c73), "=v"(c74), \
-            "=v"(c75), "=v"(c76), "=v"(c77), "=v"(c78), "=v"(c79), "=v"(c80), "=v"(c81), "=v"(c82), "=v"(c83), "=v"(c84), "=v"(c85), \
-            "=v"(c86), "=v"(c87), "=v"(c88), "=v"(c89), "=v"(c90), "=v"(c91), "=v"(c92), "=v"(c93), "=v"(c94), "=v"(c95) \
-          : [lb] "s"(lds_base), [ns] "s"(nstage), [st] "s"(stage_bytes), [wv] "s"(wave_u), [sl] "s"(sl), [sh] "s"(sh), [nl] "s"(nl), \
-            [nh] "s"(nh), [fl] "s"(fl), [sp] "s"(sp), "v"(r120), "v"(r121), "v"(r124) \
-          : "memory", "vcc", "scc", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "v125",   /* m0 is saved in s47 and restored by the block */ \
-            "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", \
-            "v20", "v21", "v22", "v23", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", "v39", \
-            "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", \
-            "v60", "v61", "v62", "v63", "v96", "v97", "v98", "v99", \
-            "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", \
-            "v117", "v118", "v119", "v122", "v123"
-      if constexpr (PL == 12) {
-        asm volatile(
-#include K2_LOOP_INC_P
-            K2P_OPERANDS);
-      } else if constexpr (ONE) {
-        asm volatile(
-#include "k2_loop_p8.inc"
-            K2P_OPERANDS);
-      } else {
-        asm volatile(
-#include "k2_loop_p8p.inc"
-            K2P_OPERANDS);
-      }
-#undef K2P_OPERANDS
-      asm volatile("" : "+v"(r124));                             // lane ids are re-derived from the value that crossed the block
-      tid_after = r124 >> 2;
-      const uint32_t cnt[32] = {c64, c65, c66, c67, c68, c69, c70, c71, c72, c73, c74, c75, c76, c77, c78, c79,
-                                c80, c81, c82, c83, c84, c85, c86, c87, c88, c89, c90, c91, c92, c93, c94, c95};
-#pragma unroll
-      for (int r = 0; r < 8; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) mis[r][c] = cnt[4 * r + c];
-    }
+    v124 = k2_block<PL == 12 ? K2_P12P : ONE ? K2_P8 : K2_P8P>(mis, {lds_base, nstage, stage_bytes, wave_u, sl, sh}, a_off, b_off, v124, 0, 0,
+                                                              {nl, nh, fl, sp});
     K2P_STAMP(2);
-    const int wave_e = (int)tid_after >> 6, lane_e = (int)tid_after & 63;
+    const int tid_e = (int)(v124 >> 2), wave_e = tid_e >> 6, lane_e = tid_e & 63;
     const int tx = ((wave_e & 1) << 3) + (lane_e & 7), ty = ((wave_e >> 1) << 3) + (lane_e >> 3);
     const int64_t I0 = (int64_t)cur.ti * K2_TILE, J0 = (int64_t)cur.tj * K2_TILE;
-#ifdef K2_NO_STORES
-    if (mis[0][0] == 0xdeadbeefu) reinterpret_cast<uint32_t *>(out_v)[0] = tid_after;
-    if (n_hash > 0) { cur = nxt; L = Ln; flags = 0u; phase = (phase + nstage) % 3u; continue; }
-#endif
     if constexpr (PK) {
       // the next tile's first two stages are landing in the ring slots (phase + nstage) % 3 and the one after it; the third slot held this
       // tile's last stage (12 KiB: room for the 9 KiB staging area once every wave has left it -- store_tile_pk's first barrier).  The next
       // block's stage 2 goes there only after the barrier of its stage 0.
       static_assert(STAGE_UNITS * 16 >= PK_STAGE_BYTES, "the packed epilogue stages in one ring slot");
       uint16_t *stage = reinterpret_cast<uint16_t *>(lds_ab + ((phase + nstage + 2u) % 3u) * STAGE_UNITS);
-      store_tile_pk(stage, mis, nn, (int)tid_after, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
+      store_tile_pk(stage, mis, nn, tid_e, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
     } else if constexpr (F64) {
-      const char *tb = reinterpret_cast<const char *>(ratio_tab);
-      double *out = reinterpret_cast<double *>(out_v);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {                              // two of the lane's rows at a time keeps the epilogue in 128 VGPRs
-        double v0[8], v1[8];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const uint32_t m0 = nn - mis[2 * g][c], m1 = nn - mis[2 * g + 1][c];
-          v0[2 * c] = *reinterpret_cast<const double *>(tb + ((m0 << 3) & 0x7fff8u));
-          v0[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m0 >> 13) & 0x7fff8u));
-          v1[2 * c] = *reinterpret_cast<const double *>(tb + ((m1 << 3) & 0x7fff8u));
-          v1[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m1 >> 13) & 0x7fff8u));
-        }
-        double *orow = out + (I0 + 32 * g + 2 * ty) * ld + (J0 + 2 * tx);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          nt_store2(orow + 32 * q, v0[2 * q], v0[2 * q + 1]);
-          nt_store2(orow + ld + 32 * q, v1[2 * q], v1[2 * q + 1]);
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c)                              // mirrored store (src/minHash.cpp:176)
-          nt_store2(out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 32 * g + 2 * ty), v0[c], v1[c]);
-      }
+      store_counts_f64(reinterpret_cast<double *>(out_v), ld, reinterpret_cast<const char *>(ratio_tab), mis, nn, I0, J0, tx, ty);
     } else {
-      uint16_t *out = reinterpret_cast<uint16_t *>(out_v);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        uint16_t *orow = out + (I0 + 32 * (r >> 1) + 2 * ty + (r & 1)) * ld + (J0 + 2 * tx);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis[r][g];
-      }
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        uint16_t *orow = out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 2 * ty);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const uint32_t lo = mis[2 * g][c >> 1], hi = mis[2 * g + 1][c >> 1];
-          const uint32_t pk = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-          *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - pk;
-        }
-      }
+      store_counts_u16(reinterpret_cast<uint16_t *>(out_v), ld, mis, nn, I0, J0, 0, 0, tx, ty, true);
     }
     K2P_STAMP(3);
 #ifdef DA_K2_TIMING
@@ -1065,10 +786,6 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
   }
 #undef K2P_STAMP
 }
-
-#ifdef DA_K2_EXPERIMENTS   // round 3's two float64-store experiments (k_mh_compare_r12 / _q12): built only by tools/experiments/build.sh, never into the product library
-#include "../../tools/experiments/k2_store_kernels.inc"
-#endif
 
 // PL = bit planes per group of 32 hash functions: 32 (raw uint32 values) or 16 / 12 / 8 (dictionary
 // codes of dict_kernels.hip, as many planes as the largest column dictionary needs: same equalities
@@ -1424,6 +1141,7 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
     uint16_t *out = reinterpret_cast<uint16_t *>(out_v);
     const bool vec_ok = ((ld & 1) == 0) && ((Jloc & 1) == 0) && ((reinterpret_cast<uintptr_t>(out) & 3) == 0);
     if (interior && vec_ok) {   // two adjacent counts per 4-byte store
+      // (store_counts_u16's loops, but kept here: shared, they raise this kernel's scratch -- it runs at 168 VGPRs and spills already)
       const uint32_t nn = (uint32_t)n_hash * 0x10001u;
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
@@ -1436,11 +1154,7 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
         for (int c = 0; c < 8; ++c) {
           uint16_t *orow = out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 2 * ty);
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const uint32_t lo = mis[2 * g][c >> 1], hi = mis[2 * g + 1][c >> 1];
-            const uint32_t pk = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-            *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - pk;
-          }
+          for (int g = 0; g < 4; ++g) *reinterpret_cast<uint32_t *>(orow + 32 * g) = nn - mis_col(mis, g, c);
         }
       }
       K2_STAMP(3);
@@ -1537,12 +1251,6 @@ extern "C" int da_debug_set_k2_timing(unsigned long long *d_buf) {
 }
 #endif
 
-#ifdef DA_K2_DEBUG
-extern "C" int da_debug_set_k2_dump(uint32_t *d_buf) {
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_k2_debug), &d_buf, sizeof(d_buf));
-}
-#endif
-
 int launch_minhash_signatures(const uint8_t *d_res, const int64_t *d_off, int64_t n, int k,
                               int n_hash, const uint32_t *d_seeds, uint32_t *d_sig,
                               int64_t ld_sig, hipStream_t stream) {
@@ -1559,9 +1267,13 @@ int launch_minhash_signatures(const uint8_t *d_res, const int64_t *d_off, int64_
   return DA_OK;
 }
 
-#ifdef DA_K2_EXPERIMENTS
-#include "../../tools/experiments/k2_store_host.inc"
-#endif
+// f(std::integral_constant<decltype(V), V>{}) for the first V equal to x, the last V when none is: one launch site per instantiation
+template <auto V, auto... MORE, typename X, typename F>
+static void dispatch(X x, F &&f) {
+  if constexpr (sizeof...(MORE) == 0) f(std::integral_constant<decltype(V), V>{});
+  else if (x == V) f(std::integral_constant<decltype(V), V>{});
+  else dispatch<MORE...>(x, f);
+}
 
 int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
                       int64_t row_begin, int64_t row_end, bool symmetric, int kind,
@@ -1583,42 +1295,40 @@ int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
   const int64_t nblocks = symmetric ? per_xcd * 8 : 8 * ceil_div(ceil_div(TR, band), 8) * (int64_t)band * T;
   if (nblocks > 0x7fffffffLL) return fail(DA_ERR_UNSUPPORTED, "pair space too large for one launch");
   dim3 grid((unsigned)nblocks), block(K2_THREADS);
-  // symmetric 12-plane compares: interior tiles by the hand-scheduled kernel, the rest by the general one
-  // (float64 output: its count -> double table of n_hash + 1 entries lives in the kernel's 36 KiB ring, K2_A12_TABLE_MAX
-  // doubles; a larger n_hash stays with k_mh_compare, which divides directly when its table does not fit)
-  const bool a12 = symmetric && plane_bits == 12 && !config().k2_no_asm && (ld & 1) == 0 &&
-                   (kind != DA_OUT_F64 || (int64_t)n_hash + 1 <= K2_A12_TABLE_MAX) &&
-                   (reinterpret_cast<uintptr_t>(d_out) & (kind == DA_OUT_F64 ? 15 : 3)) == 0;   // = a12_takes' alignment test
+  // the hand-scheduled kernels take the interior tiles, the general one the rest (k2_out_ok: the output suits their stores)
+  const bool f64 = kind == DA_OUT_F64, asm_ok = !config().k2_no_asm && k2_out_ok(d_out, ld, f64);
+  // symmetric 12-plane compares (float64 output: the count -> double table of n_hash + 1 entries lives in the kernel's 36 KiB ring,
+  // K2_A12_TABLE_MAX doubles; a larger n_hash stays with k_mh_compare, which divides directly when its table does not fit)
+  const bool a12 = symmetric && plane_bits == 12 && asm_ok && (!f64 || (int64_t)n_hash + 1 <= K2_A12_TABLE_MAX);
   // symmetric 16-plane compares likewise (k_mh_compare_a16 on the padded twin of the operand)
-  const bool a16 = symmetric && plane_bits == 16 && !config().k2_no_asm && (ld & 1) == 0 &&
-                   (kind != DA_OUT_F64 || (int64_t)n_hash + 1 <= K2_A16_TABLE_MAX) &&
-                   (reinterpret_cast<uintptr_t>(d_out) & (kind == DA_OUT_F64 ? 15 : 3)) == 0;
+  const bool a16 = symmetric && plane_bits == 16 && asm_ok && (!f64 || (int64_t)n_hash + 1 <= K2_A16_TABLE_MAX);
   // symmetric 8-plane compares (the dense half of the heavy / rare split): the persistent kernel's 8-plane block, one tile per workgroup
   // (wg_per_xcd = per_xcd: the grid and tile order of k_mh_compare_a12); float64 needs its table (16 KiB beside the 24 KiB ring: n_hash <= 2047), two stages at least
-  const bool a8 = symmetric && plane_bits == 8 && !config().k2_no_asm && (ld & 1) == 0 && n_hash > K2_GROUP &&
-                  (kind != DA_OUT_F64 || n_hash < K2_P8_TABLE) && per_xcd < 0x7fffffffLL &&
-                  (reinterpret_cast<uintptr_t>(d_out) & (kind == DA_OUT_F64 ? 15 : 3)) == 0;
-  if (a8 && config().k2_persist) {            // DYNAALIGN_K2_PERSIST=1 (experiment): four resident workgroups per CU walk the tiles
-    int wg_per_xcd = 4 * 32;
-    if (config().k2_wg_per_cu > 0) wg_per_xcd = config().k2_wg_per_cu * 32;
-    if ((int64_t)wg_per_xcd > per_xcd) wg_per_xcd = (int)(per_xcd > 0 ? per_xcd : 1);
-    const dim3 pgrid((unsigned)(8 * wg_per_xcd));
-    if (kind == DA_OUT_F64)
-      hipLaunchKernelGGL((k_mh_compare_p12<true, 8, false>), pgrid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd, wg_per_xcd, (int64_t)0);
-    else
-      hipLaunchKernelGGL((k_mh_compare_p12<false, 8, false>), pgrid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd, wg_per_xcd, (int64_t)0);
-  } else if (a8) {
-    if (kind == DA_OUT_F64)
-      hipLaunchKernelGGL((k_mh_compare_p12<true, 8, true>), grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd, (int)per_xcd, (int64_t)0);
-    else
-      hipLaunchKernelGGL((k_mh_compare_p12<false, 8, true>), grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd, (int)per_xcd, (int64_t)0);
-  }
-  if (a16) {
-#define DA_A16(F, B) hipLaunchKernelGGL((k_mh_compare_a16<F, B>), grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd)
-    if (kind == DA_OUT_F64) { if (code_bits == 14) DA_A16(true, 14); else if (code_bits == 15) DA_A16(true, 15); else DA_A16(true, 16); }
-    else { if (code_bits == 14) DA_A16(false, 14); else if (code_bits == 15) DA_A16(false, 15); else DA_A16(false, 16); }
-#undef DA_A16
-  }
+  const bool a8 = symmetric && plane_bits == 8 && asm_ok && n_hash > K2_GROUP && (!f64 || n_hash < K2_P8_TABLE) && per_xcd < 0x7fffffffLL;
+  // shard / row-block modes with uint16 output (what the sharded routes compute per rank): the 12- and 16-plane loops behind the rectangular
+  // tile geometry
+  const bool s12 = !symmetric && plane_bits == 12 && kind == DA_OUT_COMPACT && asm_ok && (row_begin % K2_TILE) == 0;
+  const bool s16 = !symmetric && plane_bits == 16 && kind == DA_OUT_COMPACT && asm_ok && (row_begin % K2_TILE) == 0;
+  if (a8)
+    dispatch<false, true>(f64, [&](auto F64) {
+      if (config().k2_persist) {              // DYNAALIGN_K2_PERSIST=1 (experiment): four resident workgroups per CU walk the tiles
+        int wg_per_xcd = 4 * 32;
+        if (config().k2_wg_per_cu > 0) wg_per_xcd = config().k2_wg_per_cu * 32;
+        if ((int64_t)wg_per_xcd > per_xcd) wg_per_xcd = (int)(per_xcd > 0 ? per_xcd : 1);
+        hipLaunchKernelGGL((k_mh_compare_p12<decltype(F64)::value, 8, false>), dim3((unsigned)(8 * wg_per_xcd)), block, 0, stream, d_planes, n, n_hash,
+                           d_out, ld, ntiles, per_xcd, wg_per_xcd, (int64_t)0);
+      } else {
+        hipLaunchKernelGGL((k_mh_compare_p12<decltype(F64)::value, 8, true>), grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd,
+                           (int)per_xcd, (int64_t)0);
+      }
+    });
+  if (a16)
+    dispatch<false, true>(f64, [&](auto F64) {
+      dispatch<14, 15, 16>(code_bits, [&](auto B) {
+        hipLaunchKernelGGL((k_mh_compare_a16<decltype(F64)::value, decltype(B)::value>), grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles,
+                           per_xcd);
+      });
+    });
   // the persistent form of that kernel: >= 2 stages per tile, float64 needs its 4 KiB table (n_hash <= 511)
   // OPT-IN (DYNAALIGN_K2_PERSIST=1): measured slower than one tile per workgroup on MI355X -- 28.8 vs 24.9 ms (float64),
   // 26.3 vs 22.2 ms (uint16) at N = 100k (profiles/r02_c_k2_persistent_*.json): a wave that does not exit has to
@@ -1626,7 +1336,7 @@ int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
   // ~13 us either way; with one tile per workgroup that time is spent by an exiting workgroup while the slot's successor
   // already loads.  Kept because it is bit-exact, tested, and the structure the next step needs (stores interleaved into
   // the following tile's stage loop).
-  const bool p12 = a12 && n_hash > K2_GROUP && (kind != DA_OUT_F64 || n_hash < K2_P12_TABLE) && config().k2_persist;
+  const bool p12 = a12 && n_hash > K2_GROUP && (!f64 || n_hash < K2_P12_TABLE) && config().k2_persist;
   if (p12) {
     static std::atomic<int> occ_cache[2], cus_cache;              // resident workgroups per CU (4 expected), CUs of the device;
     const int ki = kind == DA_OUT_F64 ? 0 : 1;                    // (atomics: the multi-device entry points launch from several host threads)
@@ -1647,70 +1357,35 @@ int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
     int wg_per_xcd = occ_cache[ki].load() * ((cus_cache.load() + 7) / 8);
     if ((int64_t)wg_per_xcd > per_xcd) wg_per_xcd = (int)(per_xcd > 0 ? per_xcd : 1);
     const dim3 pgrid((unsigned)(8 * wg_per_xcd));
-#ifdef K2_DYNAMIC
-    {
-      static const unsigned int zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      DA_HIP_TRY(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_k2_next), zeros, sizeof(zeros), 0, hipMemcpyHostToDevice, stream));
-    }
-#endif
     if (kind == DA_OUT_F64)
       hipLaunchKernelGGL(k_mh_compare_p12<true>, pgrid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd, wg_per_xcd, (int64_t)0);
     else
       hipLaunchKernelGGL(k_mh_compare_p12<false>, pgrid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd, wg_per_xcd, (int64_t)0);
   } else if (a12) {
-    bool roles = false;
-#ifdef DA_K2_EXPERIMENTS
-    // (experiment library only, tools/experiments/: DYNAALIGN_K2_INLOOP=1 -> k_mh_compare_q12, DYNAALIGN_K2_ROLES=1 -> k_mh_compare_r12)
-    const int nst12 = (n_hash + K2_GROUP - 1) / K2_GROUP;
-    if (kind == DA_OUT_F64 && ntiles < 0x7fffffffLL && T < 65536) {
-      int rc_r = DA_OK;
-      if (getenv("DYNAALIGN_K2_ROLES") && n_hash > 2 * K2_GROUP && n_hash < R12_TABLE)
-        rc_r = launch_persistent_f64(true, d_planes, n, n_hash, static_cast<double *>(d_out), ld, ntiles, per_xcd, T, stream, &roles);
-      else if (getenv("DYNAALIGN_K2_INLOOP") && (nst12 == 16 || nst12 == 8 || nst12 == 4) && ld < ((int64_t)1 << 24))
-        rc_r = launch_persistent_f64(false, d_planes, n, n_hash, static_cast<double *>(d_out), ld, ntiles, per_xcd, T, stream, &roles);
-      if (rc_r != DA_OK) return rc_r;
-    }
-#endif
-    if (roles) {
-    } else if (kind == DA_OUT_F64)
+    if (f64)
       hipLaunchKernelGGL(k_mh_compare_a12<true>, grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd);
     else
       hipLaunchKernelGGL(k_mh_compare_a12<false>, grid, block, 0, stream, d_planes, n, n_hash, d_out, ld, ntiles, per_xcd);
   }
-  // shard / row-block modes with uint16 output (what the sharded routes compute per rank): the same loop behind the rectangular tile geometry
-  const bool s12 = !symmetric && plane_bits == 12 && kind == DA_OUT_COMPACT && !config().k2_no_asm && (ld & 1) == 0 &&
-                   (row_begin % K2_TILE) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 3) == 0;
   if (s12)
     hipLaunchKernelGGL(k_mh_compare_s12, grid, block, 0, stream, d_planes, n, n_hash, row_begin, row_end, tile_stride, upper_only ? 1 : 0, TR,
                        static_cast<uint16_t *>(d_out), ld, fold_q, fold_w, band);
-  // ... and with 14 - 16 code bits (k_mh_compare_a16's block behind the same geometry)
-  const bool s16 = !symmetric && plane_bits == 16 && kind == DA_OUT_COMPACT && !config().k2_no_asm && (ld & 1) == 0 &&
-                   (row_begin % K2_TILE) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 3) == 0;
-  if (s16) {
-#define DA_S16(B) hipLaunchKernelGGL((k_mh_compare_s16<B>), grid, block, 0, stream, d_planes, n, n_hash, row_begin, row_end, tile_stride, upper_only ? 1 : 0, TR, \
-                                     static_cast<uint16_t *>(d_out), ld, fold_q, fold_w, band)
-    if (code_bits == 14) DA_S16(14); else if (code_bits == 15) DA_S16(15); else DA_S16(16);
-#undef DA_S16
-  }
+  if (s16)
+    dispatch<14, 15, 16>(code_bits, [&](auto B) {
+      hipLaunchKernelGGL((k_mh_compare_s16<decltype(B)::value>), grid, block, 0, stream, d_planes, n, n_hash, row_begin, row_end, tile_stride,
+                         upper_only ? 1 : 0, TR, static_cast<uint16_t *>(d_out), ld, fold_q, fold_w, band);
+    });
   const int only_edge = (a12 || a16 || a8 || s12 || s16) ? 1 : 0;
   // what is left for the general kernel then: the diagonal tiles + the last tile column, enumerated directly
   if (a12 || a16 || a8) grid = dim3((unsigned)(2 * (int64_t)T - 1));
-#define DA_K2(SYM, F64, PL)                                                                              \
-  hipLaunchKernelGGL((k_mh_compare<SYM, F64, PL>), grid, block, 0, stream, d_planes, n, n_hash, \
-                     row_begin, row_end, tile_stride, upper_only ? 1 : 0, TR, d_out, ld, ntiles, per_xcd, fold_q, fold_w, band, only_edge)
-#define DA_K2_PL(PL)                                                                     \
-  do {                                                                                   \
-    if (symmetric) { if (kind == DA_OUT_F64) DA_K2(true, true, PL); else DA_K2(true, false, PL); } \
-    else           { if (kind == DA_OUT_F64) DA_K2(false, true, PL); else DA_K2(false, false, PL); } \
-  } while (0)
-  switch (plane_bits) {
-    case 8: DA_K2_PL(8); break;
-    case 12: DA_K2_PL(12); break;
-    case 16: DA_K2_PL(16); break;
-    default: DA_K2_PL(32); break;
-  }
-#undef DA_K2_PL
-#undef DA_K2
+  dispatch<false, true>(symmetric, [&](auto SYM) {
+    dispatch<false, true>(f64, [&](auto F64) {
+      dispatch<8, 12, 16, 32>(plane_bits, [&](auto PL) {
+        hipLaunchKernelGGL((k_mh_compare<decltype(SYM)::value, decltype(F64)::value, decltype(PL)::value>), grid, block, 0, stream, d_planes, n,
+                           n_hash, row_begin, row_end, tile_stride, upper_only ? 1 : 0, TR, d_out, ld, ntiles, per_xcd, fold_q, fold_w, band, only_edge);
+      });
+    });
+  });
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
@@ -1737,15 +1412,15 @@ extern "C" int da_debug_decode_sym_tile(int64_t L, int T, int *ti, int *tj) {
 }
 bool mh_compare_bands_ok(int64_t n, int n_hash, int plane_bits, const void *d_out, int64_t ld) {
   const int64_t T = ceil_div(n, K2_TILE);
-  return (plane_bits == 12 || plane_bits == 8) && n_hash > K2_GROUP && n_hash <= 65535 && !config().k2_no_asm && (ld & 1) == 0 &&
-         (reinterpret_cast<uintptr_t>(d_out) & 3) == 0 && T * (T + 1) / 2 < 0x7fffffffLL;
+  return (plane_bits == 12 || plane_bits == 8) && n_hash > K2_GROUP && n_hash <= 65535 && !config().k2_no_asm &&
+         k2_out_ok(d_out, ld, false) && T * (T + 1) / 2 < 0x7fffffffLL;
 }
 // interior tiles of the bands [band_begin, band_end) by the persistent kernel with at most wg_per_cu resident workgroups per CU:
 // a grid that small leaves the rest of every CU to kernels of other streams (the expansion's stores)
 int launch_mh_compare_bands_u16(const uint32_t *d_planes, int64_t n, int n_hash, uint16_t *d_out, int64_t ld, int64_t band_begin,
                                 int64_t band_end, int wg_per_cu, hipStream_t stream, int plane_bits, bool pk) {
   if (!mh_compare_bands_ok(n, n_hash, plane_bits, d_out, ld) ||
-      (pk && (!mh_compare_pk_ok(n, n_hash, plane_bits) || (reinterpret_cast<uintptr_t>(d_out) & 15))))   // = a12_takes' test for the packed table
+      (pk && (!mh_compare_pk_ok(n, n_hash, plane_bits) || !k2_out_ok(d_out, ld, true))))
     return fail(DA_ERR_UNSUPPORTED, "banded compare: shape not covered");
   const int64_t t0 = mh_sym_band_prefix(n, band_begin), t1 = mh_sym_band_prefix(n, band_end);
   if (t1 <= t0) return DA_OK;
@@ -1777,7 +1452,7 @@ int launch_mh_compare_edges_u16(const uint32_t *d_planes, int64_t n, int n_hash,
                                 bool pk) {
   const int T = (int)ceil_div(n, K2_TILE);
   const int64_t ntiles = count_tiles(T, T, true);
-  if (pk && (!mh_compare_pk_ok(n, n_hash, plane_bits) || (reinterpret_cast<uintptr_t>(d_out) & 15)))
+  if (pk && (!mh_compare_pk_ok(n, n_hash, plane_bits) || !k2_out_ok(d_out, ld, true)))
     return fail(DA_ERR_UNSUPPORTED, "packed count table: shape not covered");
   if (pk)
     hipLaunchKernelGGL((k_mh_compare<true, false, 12, true>), dim3((unsigned)(2 * (int64_t)T - 1)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
@@ -1797,7 +1472,7 @@ bool mh_compare_pk_ok(int64_t n, int n_hash, int plane_bits) {
   return plane_bits == 12 && n >= 1 && n <= 65536 && n_hash >= 1 && expand_stream_packed(n_hash) && !config().k2_no_asm;
 }
 int launch_mh_compare_pk(const uint32_t *d_planes, int64_t n, int n_hash, uint8_t *d_tab, hipStream_t stream) {
-  if (!mh_compare_pk_ok(n, n_hash, 12) || (reinterpret_cast<uintptr_t>(d_tab) & 15)) return fail(DA_ERR_UNSUPPORTED, "packed count table: shape not covered");
+  if (!mh_compare_pk_ok(n, n_hash, 12) || !k2_out_ok(d_tab, pk_lo_bytes(n), true)) return fail(DA_ERR_UNSUPPORTED, "packed count table: shape not covered");
   const int T = (int)ceil_div(n, K2_TILE);
   const int64_t ntiles = count_tiles(T, T, true), per_xcd = ceil_div(ntiles, 8);
   hipLaunchKernelGGL((k_mh_compare_a12<false, true>), dim3((unsigned)(per_xcd * 8)), dim3(K2_THREADS), 0, stream, d_planes, n, n_hash,
