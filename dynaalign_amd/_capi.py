@@ -33,6 +33,8 @@ SIGNATURES = {
     "da_hash_family_seeds": (_i32, [_u32, _i32, _vp]),
     "da_random_seed": (_u32, []),
     "da_similarity_mh": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "da_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32]),
+    "da_similarity_nw_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i32]),
     "da_similarity_mh_opts": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "da_similarity_nw_opts": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _vp]),
     "da_rccl_available": (_i32, []),
@@ -46,6 +48,10 @@ SIGNATURES = {
     "da_mh_planes_workspace_bytes": (_sz, [_i64, _i32]),
     "da_dev_mh_planes": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _i64, _vp, _vp]),
     "da_dev_mh_compare": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
+    "da_dev_mh_compare_rect": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "da_dev_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "da_mh_cross_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "da_dev_nw_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_last_route": (_i32, [_vp, _vp, _vp, _vp]),
     "da_dev_similarity_mh": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "da_mh_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp]),

@@ -366,8 +366,9 @@ struct Trace {
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// How many result rows to keep on the device at once (host-pointer paths).
-int64_t rows_per_block(int64_t n, size_t bytes_per_elem) {
+// How many result rows of n columns the device may hold at once (host-pointer paths): a multiple of 128, at least 128, whatever the
+// number of rows there are.
+int64_t block_rows(int64_t n, size_t bytes_per_elem) {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)8 << 30;
   {
@@ -381,8 +382,10 @@ int64_t rows_per_block(int64_t n, size_t bytes_per_elem) {
   int64_t rows = (int64_t)(budget / ((size_t)n * bytes_per_elem));
   rows = rows / 128 * 128;
   if (rows < 128) rows = 128;
-  return std::min(rows, n);
+  return rows;
 }
+// ... of a square n x n result: never more than its n rows
+int64_t rows_per_block(int64_t n, size_t bytes_per_elem) { return std::min(block_rows(n, bytes_per_elem), n); }
 
 }  // namespace
 }  // namespace da
@@ -689,6 +692,14 @@ struct LaunchUnion {
 // The duplicate plan: U unique strings; when collapsed (`take`), ids by first occurrence, the expansion family (`rows`: k_expand_stream, else tiles)
 // and for the tiles ub[b] = unique ids the input rows [0, 1024 b) use (the plan's prefix counts at band boundaries): the tile pipeline's schedule
 struct MhDedup { int64_t U = 0; bool take = false, rows = false; DevBuf work; NwDedupPlan p{}; std::vector<int32_t> ub; };
+// the first half of every MinHash duplicate plan: the plan's workspace and the number of unique strings (synchronises `stream`)
+static int mh_count_unique(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t total, DevBuf *work, NwDedupPlan *p, int64_t *U,
+                           hipStream_t stream) {
+  int rc;
+  if ((rc = work->alloc(nw_dedup_workspace_bytes(n, total))) != DA_OK) return rc;
+  *p = nw_dedup_layout(work->p, n, total);
+  return count_unique(d_res, d_off, n, *p, stream, U);
+}
 static int mh_dedup_plan(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t total, int n_hash, const double *d_out, int64_t ld,
                          MhDedup *d, hipStream_t stream) {
   const Config &cfg = da::config();
@@ -696,9 +707,7 @@ static int mh_dedup_plan(const uint8_t *d_res, const int64_t *d_off, int64_t n, 
   d->U = n;
   const int64_t min_n = cfg.mh_dedup_min_n >= 0 ? cfg.mh_dedup_min_n : 2048;   // DYNAALIGN_MH_DEDUP_MIN_N: tests lower it to reach the route with small inputs
   if (n < min_n || n > 0x7ffffff0LL || total <= 0 || n_hash > 2047 || cfg.mh_no_dedup) return DA_OK;
-  if ((rc = d->work.alloc(nw_dedup_workspace_bytes(n, total))) != DA_OK) return rc;
-  d->p = nw_dedup_layout(d->work.p, n, total);
-  if ((rc = count_unique(d_res, d_off, n, d->p, stream, &d->U)) != DA_OK) return rc;
+  if ((rc = mh_count_unique(d_res, d_off, n, total, &d->work, &d->p, &d->U, stream)) != DA_OK) return rc;
   const int64_t U = d->U;
   // K2 on U rows + column gather + expansion (0.5 + 1.6 f + 22 f^2 + 4.1 f + 14.4 ms at N = 100k, f = U / n) against K1 + K1b + K2 with its
   // own float64 stores (27.2 ms): the route pays below f = 0.63
@@ -1076,6 +1085,139 @@ int da_mh_last_route(int64_t *n_out, int64_t *unique_out, int *dedup_taken_out, 
   return DA_OK;
 }
 
+// ---- two sets: x (m sequences) against y (n sequences), the m x n rectangle ------------------------------------------------------------------
+int da_dev_mh_compare_rect(const uint32_t *d_planes, int plane_bits, int64_t n, int n_hash, int64_t row_begin, int64_t row_end, int64_t col_begin,
+                           int64_t col_end, int kind, void *d_out, int64_t ld, void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (n_hash <= 0) return fail(DA_ERR_BAD_NHASH, "%s", da_status_message(DA_ERR_BAD_NHASH));
+  if (!d_planes || !d_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (row_begin < 0 || row_end > n || row_begin > row_end) return fail(DA_ERR_BAD_ARG, "bad row range");
+  if (col_begin < 0 || col_end > n || col_begin > col_end) return fail(DA_ERR_BAD_ARG, "bad column range");
+  if (ld < col_end - col_begin) return fail(DA_ERR_BAD_ARG, "ld (%lld) < columns (%lld)", (long long)ld, (long long)(col_end - col_begin));
+  if (kind != DA_OUT_F64 && kind != DA_OUT_COMPACT) return fail(DA_ERR_BAD_ARG, "bad output kind");
+  if (n_hash > 65535)
+    return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: n_hash <= 65535 (got %d)", n_hash);
+  if (reinterpret_cast<uintptr_t>(d_planes) & 15) return fail(DA_ERR_BAD_ARG, "bit-plane buffer must be 16-byte aligned");
+  if (plane_bits != 8 && plane_bits != 12 && plane_bits != 14 && plane_bits != 15 && plane_bits != 16 && plane_bits != 32)
+    return fail(DA_ERR_BAD_ARG, "plane_bits must be 8, 12, 14, 15, 16 or 32 (got %d)", plane_bits);
+  return launch_mh_compare_rect(d_planes, n, n_hash, row_begin, row_end, col_begin, col_end, kind, d_out, ld, static_cast<hipStream_t>(stream),
+                                plane_bits);
+}
+
+namespace {
+// The compare operand of two sets: ONE signature matrix [x ; filler ; y] -- x padded to a multiple of 128 rows, so that both origins of the
+// rectangle are tile-aligned in the operand and the hand-scheduled loops take its interior -- and K1b ONCE on all of it: a cross pair is never on
+// the diagonal, so two strings agree only through codes of the same column dictionaries.  The filler rows repeat real rows (every equality is
+// kept) and their results are never stored.  The rectangle is rows [0, m) x columns [m_pad, m_pad + n) of the `rows`-row problem.
+struct MhCrossOperand {
+  DevBuf sig, planes, work;
+  int64_t m = 0, m_pad = 0, n = 0, rows = 0;
+  int bits = 32;
+};
+int mh_cross_operand(const uint8_t *d_xres, const int64_t *d_xoff, int64_t m, const uint8_t *d_yres, const int64_t *d_yoff, int64_t n, int k,
+                     int n_hash, const uint32_t *d_seeds, MhCrossOperand *c, hipStream_t stream) {
+  int rc;
+  const int64_t lds = sig_ld_for(n_hash);
+  c->m = m; c->n = n;
+  c->m_pad = (m + 127) / 128 * 128;
+  if (c->m_pad + n > DA_DICT_MAX_N && m + n <= DA_DICT_MAX_N) c->m_pad = m;   // keep the dictionary rather than the alignment
+  const int64_t rows = c->rows = c->m_pad + n;
+  const size_t wb = mh_planes_workspace_bytes(rows, n_hash);
+  if ((rc = c->sig.alloc((size_t)rows * lds * sizeof(uint32_t))) != DA_OK ||
+      (rc = c->planes.alloc((size_t)mh_planes_words(rows, n_hash) * sizeof(uint32_t))) != DA_OK || (rc = c->work.alloc(wb)) != DA_OK) return rc;
+  uint32_t *sig = c->sig.as<uint32_t>();
+  if ((rc = launch_minhash_signatures(d_xres, d_xoff, m, k, n_hash, d_seeds, sig, lds, stream)) != DA_OK ||
+      (rc = launch_minhash_signatures(d_yres, d_yoff, n, k, n_hash, d_seeds, sig + c->m_pad * lds, lds, stream)) != DA_OK ||
+      (rc = launch_fill_sig_rows(sig, lds, m, c->m_pad, n_hash, stream)) != DA_OK) return rc;
+  return build_planes(sig, lds, rows, n_hash, 0, c->work.p, wb, c->planes.as<uint32_t>(), &c->bits, stream);
+}
+int mh_cross_compare(const MhCrossOperand &c, int n_hash, int64_t r0, int64_t r1, int kind, void *d_out, int64_t ld, hipStream_t stream) {
+  return launch_mh_compare_rect(c.planes.as<uint32_t>(), c.rows, n_hash, r0, r1, c.m_pad, c.m_pad + c.n, kind, d_out, ld, stream, c.bits);
+}
+struct MhCrossRoute { int64_t m = 0, n = 0, ux = 0, uy = 0; int taken = 0, plane_bits = 0; float ms[5] = {0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, copy lists, expansion
+static MhCrossRoute &mh_cross_route() { static thread_local MhCrossRoute r; return r; }
+struct CrossEvents {
+  hipEvent_t e[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~CrossEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+// one side's duplicate plan (byte-identical strings collapsed): the unique count, and -- built on demand -- ids, unique strings, offsets
+struct CrossSide { DevBuf work; NwDedupPlan p{}; int64_t U = 0; };
+}  // namespace
+
+// similarityMH_cross on two resident sets as ONE call: direct (K1 per side, K1b on the union, the rectangle compare into d_out) or, when
+// collapsing byte-identical strings PER SIDE shrinks the compare enough, the rectangular duplicate route: the U_x x U_y count table of the unique
+// strings, then the rectangular row expansion (launch_expand_stream_rect).  One stream, no pipelining, no packed table, no heavy / rare split,
+// no sparse route.
+int da_dev_similarity_mh_cross(const uint8_t *d_x_residues, const int64_t *d_x_offsets, int64_t m, int64_t x_total, const uint8_t *d_y_residues,
+                               const int64_t *d_y_offsets, int64_t n, int64_t y_total, int k, int n_hash, const uint32_t *d_seeds, double *d_out,
+                               int64_t ld, void *stream_v) {
+  int rc;
+  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
+  if (!d_x_residues || !d_x_offsets || !d_y_residues || !d_y_offsets || !d_seeds || !d_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld < n) return fail(DA_ERR_BAD_ARG, "ld (%lld) < n (%lld)", (long long)ld, (long long)n);
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: the two-set calls take n_hash <= 65535 (got %d)", n_hash);
+  if (m > 0x7ffffff0LL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "two-set MinHash: too many sequences");
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const Config &cfg = da::config();
+  MhCrossRoute &route = mh_cross_route() = MhCrossRoute();
+  route.m = m; route.n = n; route.ux = m; route.uy = n;
+  CrossEvents ev;
+  for (auto &e : ev.e) DA_HIP_TRY(hipEventCreate(&e));
+  DA_HIP_TRY(hipEventRecord(ev.e[0], stream));
+  // admission of the duplicate route: the compare shrinks by U_x U_y / (m n) and the expansion costs what the direct kernel's stores cost, so --
+  // like the square route's U / n <= 0.68 -- it pays while sqrt(U_x U_y / (m n)) stays below that share (DYNAALIGN_MH_DEDUP_MAX_PCT changes
+  // it, DYNAALIGN_MH_DEDUP_MIN_N is compared with m + n)
+  CrossSide sx, sy;
+  bool take = false;
+  const int64_t min_n = cfg.mh_dedup_min_n >= 0 ? cfg.mh_dedup_min_n : 2048;
+  if (!cfg.mh_no_dedup && m + n >= min_n && x_total > 0 && y_total > 0 && n_hash <= 2047) {
+    if ((rc = mh_count_unique(d_x_residues, d_x_offsets, m, x_total, &sx.work, &sx.p, &sx.U, stream)) != DA_OK ||
+        (rc = mh_count_unique(d_y_residues, d_y_offsets, n, y_total, &sy.work, &sy.p, &sy.U, stream)) != DA_OK) return rc;
+    route.ux = sx.U; route.uy = sy.U;
+    const double pct = (double)(cfg.mh_dedup_max_pct >= 0 ? cfg.mh_dedup_max_pct : 68);
+    take = sx.U > 0 && sy.U > 0 && (double)sx.U * (double)sy.U * 10000.0 <= (double)m * (double)n * pct * pct &&
+           expand_stream_rect_ok(m, n, sx.U, sy.U, n_hash, d_out, ld);
+    if (take && ((rc = launch_nw_dedup_build(d_x_residues, d_x_offsets, m, sx.U, sx.p, stream, true)) != DA_OK ||
+                 (rc = launch_nw_dedup_build(d_y_residues, d_y_offsets, n, sy.U, sy.p, stream, true)) != DA_OK)) return rc;
+  }
+  DA_HIP_TRY(hipEventRecord(ev.e[1], stream));
+  MhCrossOperand c;
+  if ((rc = take ? mh_cross_operand(sx.p.ucodes, sx.p.uoff, sx.U, sy.p.ucodes, sy.p.uoff, sy.U, k, n_hash, d_seeds, &c, stream)
+                 : mh_cross_operand(d_x_residues, d_x_offsets, m, d_y_residues, d_y_offsets, n, k, n_hash, d_seeds, &c, stream)) != DA_OK) return rc;
+  route.plane_bits = c.bits;
+  DA_HIP_TRY(hipEventRecord(ev.e[2], stream));
+  DevBuf dtab, ex;
+  if (!take) {
+    if ((rc = mh_cross_compare(c, n_hash, 0, m, DA_OUT_F64, d_out, ld, stream)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(ev.e[3], stream));
+  } else {
+    const int64_t ld_d = (sy.U + 7) / 8 * 8;
+    if ((rc = dtab.alloc((size_t)sx.U * (size_t)ld_d * 2)) != DA_OK || (rc = ex.alloc(expand_stream_scratch_bytes(m, sx.U))) != DA_OK) return rc;
+    if ((rc = mh_cross_compare(c, n_hash, 0, sx.U, DA_OUT_COMPACT, dtab.p, ld_d, stream)) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(ev.e[3], stream));
+    if ((rc = launch_expand_stream_rect(dtab.as<uint16_t>(), ld_d, sx.p.uidx, m, sx.U, sy.p.uidx, n, sy.U, n_hash, d_out, ld, ex.p, stream,
+                                        ev.e[4])) != DA_OK) return rc;
+    DA_HIP_TRY(hipEventRecord(ev.e[5], stream));
+  }
+  DA_HIP_TRY(hipStreamSynchronize(stream));            // the intermediates go back to the cache after this
+  route.taken = take ? 1 : 0;
+  for (int i = 0; i < (take ? 5 : 3); ++i) (void)hipEventElapsedTime(&route.ms[i], ev.e[i], ev.e[i + 1]);
+  return DA_OK;
+}
+
+int da_mh_cross_last_route(int64_t *m_out, int64_t *n_out, int64_t *unique_x_out, int64_t *unique_y_out, int *route_out, int *plane_bits_out,
+                           double *ms5_out) {
+  const MhCrossRoute &r = mh_cross_route();
+  if (m_out) *m_out = r.m;
+  if (n_out) *n_out = r.n;
+  if (unique_x_out) *unique_x_out = r.ux;
+  if (unique_y_out) *unique_y_out = r.uy;
+  if (route_out) *route_out = r.taken;
+  if (plane_bits_out) *plane_bits_out = r.plane_bits;
+  if (ms5_out) for (int i = 0; i < 5; ++i) ms5_out[i] = r.ms[i];
+  return DA_OK;
+}
+
 // ---- pieces of the duplicate-collapsing routes for callers that orchestrate the steps themselves (the one-process-per-GPU
 // sharded drivers in dynaalign_amd/sharding.py: every rank builds the same plan, computes ITS shard of the unique table,
 // all-gathers the shards -- 0.2x the bytes of the N x N shards at N = 100k -- and expands locally)
@@ -1294,6 +1436,19 @@ int da_dev_nw(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, int64
   }
   return launch_nw(d_codes, d_offsets, n, max_len, matrix_id, gap_open, gap_ext, row_begin, row_end,
                    symmetric != 0, kind, d_out, ld, d_score, ld_score, static_cast<hipStream_t>(stream));
+}
+
+// rows [row_begin, row_end) x columns [col_begin, col_end) of the row-block mode above: pair (i, j) is calc(seq[min(i, j)], seq[max(i, j)])
+int da_dev_nw_rect(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, int64_t max_len, int matrix_id, int gap_open, int gap_ext,
+                   int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, void *stream) {
+  if (n <= 0) return DA_OK;
+  if (!d_codes || !d_offsets || !d_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (row_begin < 0 || row_end > n || row_begin > row_end) return fail(DA_ERR_BAD_ARG, "bad row range");
+  if (col_begin < 0 || col_end > n || col_begin > col_end) return fail(DA_ERR_BAD_ARG, "bad column range");
+  if (ld < col_end - col_begin) return fail(DA_ERR_BAD_ARG, "leading dimension < columns");
+  if (kind != DA_OUT_F64 && kind != DA_OUT_COMPACT && kind != DA_OUT_PACK32) return fail(DA_ERR_BAD_ARG, "bad output kind");
+  return launch_nw(d_codes, d_offsets, n, max_len, matrix_id, gap_open, gap_ext, row_begin, row_end, false, kind, d_out, ld, nullptr, 0,
+                   static_cast<hipStream_t>(stream), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, col_begin, col_end);
 }
 
 int da_dev_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, void *stream) {
@@ -1698,22 +1853,34 @@ template <typename F> int codes_to_host(int64_t n, double *out, const std::vecto
   return DA_OK;
 }
 
-// Rows [r0, r1) of an n-column result (esz bytes per element) to the host at out, in blocks of as many rows as the device holds:
-// compute(b0, b1, d) writes rows [b0, b1) to the device buffer d, then they are copied out.  The block size is measured here, after
-// the caller's allocations.  compute_ms / d2h_ms, if given, add up the time of each step.
-template <typename F> int rows_to_host(int64_t n, int64_t r0, int64_t r1, size_t esz, void *out, F compute,
-                                       double *compute_ms = nullptr, double *d2h_ms = nullptr) {
-  const int64_t blk = rows_per_block(n, esz);
-  DevBuf d;
+// Rows [r0, r1) of a result with `cols` columns (esz bytes per device element) to the host at out, in blocks of as many rows as the device
+// holds: compute(b0, b1, d) writes rows [b0, b1) to the device buffer d with leading dimension ld, then they are copied out.  The block
+// size is measured here, after the caller's allocations, and depends on the columns only -- a tall result (rows >> cols: the two-set calls)
+// is not cut by its column count, and every block starts on a multiple of 128 rows after r0.  compute_ms / d2h_ms, if given, add up the
+// time of each step.  table: the device elements are uint16 codes and the host widens them while copying, out (double) = table[code].
+// even_ld: ld = cols rounded up to even (what the hand-scheduled compare's stores need), compacted on the device before the copy;
+// otherwise ld = cols.
+template <typename F> int rows_to_host(int64_t cols, int64_t r0, int64_t r1, size_t esz, void *out, F compute,
+                                       double *compute_ms = nullptr, double *d2h_ms = nullptr, const double *table = nullptr,
+                                       bool even_ld = false) {
+  const int64_t ld = even_ld ? cols + (cols & 1) : cols;
+  const bool compact = ld != cols;
+  const int64_t blk = std::min(block_rows(compact ? ld + cols : cols, esz), r1 - r0);
+  const size_t out_esz = table ? sizeof(double) : esz;
+  DevBuf d, dc;
   int rc;
-  if ((rc = d.alloc((size_t)std::min(blk, r1 - r0) * (size_t)n * esz)) != DA_OK) return rc;
+  if ((rc = d.alloc((size_t)blk * (size_t)ld * esz)) != DA_OK) return rc;
+  if (compact && (rc = dc.alloc((size_t)blk * (size_t)cols * esz)) != DA_OK) return rc;
   for (int64_t b0 = r0; b0 < r1; b0 += blk) {
     const int64_t b1 = std::min(r1, b0 + blk);
     double t = now_ms();
     if ((rc = compute(b0, b1, d.p)) != DA_OK) return rc;
+    if (compact)
+      DA_HIP_TRY(hipMemcpy2DAsync(dc.p, (size_t)cols * esz, d.p, (size_t)ld * esz, (size_t)cols * esz, (size_t)(b1 - b0), hipMemcpyDeviceToDevice, nullptr));
     if (compute_ms) *compute_ms += now_ms() - t;
     t = now_ms();
-    rc = d2h_pipelined(static_cast<char *>(out) + (size_t)(b0 - r0) * (size_t)n * esz, d.p, (size_t)(b1 - b0) * (size_t)n * esz);
+    rc = d2h_pipelined(static_cast<char *>(out) + (size_t)(b0 - r0) * (size_t)cols * out_esz, compact ? dc.p : d.p,
+                       (size_t)(b1 - b0) * (size_t)cols * esz, table);
     if (d2h_ms) *d2h_ms += now_ms() - t;
     if (rc != DA_OK) return rc;
   }
@@ -2064,6 +2231,94 @@ int da_nw_pairs(const uint8_t *residues, const int64_t *offsets, int64_t n, cons
                 int32_t *len_out, int32_t *score_out) {
   return nw_host_common(residues, offsets, n, matrix_name, gap_open, gap_ext, row_begin, row_end, nullptr,
                         matches_out, len_out, score_out);
+}
+
+// ---- two sets on the host boundary: x (m sequences) against y (n sequences) ------------------------------------------------------------------
+// similarityMH for two sets: out[i][j] = #{h : sig_x[i][h] == sig_y[j][h]} / n_hash, no forced diagonal.  column_major: out[i + j * m]
+// (R's NumericMatrix(m, n)) -- the similarity is symmetric, so that is the row-major result of y against x.
+int da_similarity_mh_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                           int64_t n, int k, int n_hash, const uint32_t *seeds, double *out, int column_major) {
+  int rc;
+  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
+  if (!x_residues || !y_residues || !seeds || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the two-set calls take n_hash <= 65535 (got %d)", n_hash);
+  int64_t x_total, y_total, max_len;
+  if ((rc = check_offsets(x_offsets, m, &x_total, &max_len)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &max_len)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  DeviceInput dx, dy;
+  if ((rc = dx.upload(x_residues, x_offsets, m, x_total, seeds, n_hash)) != DA_OK || (rc = dy.upload(y_residues, y_offsets, n, y_total, nullptr, 0)) != DA_OK)
+    return rc;
+  const DeviceInput &rowset = column_major ? dy : dx, &colset = column_major ? dx : dy;
+  const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
+  MhCrossOperand c;
+  if ((rc = mh_cross_operand(rowset.res.as<uint8_t>(), rowset.off.as<int64_t>(), rows, colset.res.as<uint8_t>(), colset.off.as<int64_t>(), cols, k,
+                             n_hash, dx.seeds.as<uint32_t>(), &c, nullptr)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(nullptr));
+  c.work.release(); c.sig.release();                     // before the result blocks are sized
+  const std::vector<double> table = mh_code_values(n_hash);
+  const bool widen = !da::config().no_host_widen;
+  return rows_to_host(cols, 0, rows, widen ? sizeof(uint16_t) : sizeof(double), out, [&](int64_t b0, int64_t b1, void *d) {
+    return mh_cross_compare(c, n_hash, b0, b1, widen ? DA_OUT_COMPACT : DA_OUT_F64, d, cols + (cols & 1), nullptr);
+  }, nullptr, nullptr, widen ? table.data() : nullptr, true);
+}
+
+// What the reference's lazy fill would raise first with the pairs visited i ascending over x, j ascending over y (src/pairwiseSeqAlign.cpp:
+// 238-250 per pair: sequence1[0], every character of sequence2, then sequence1[1], ...; an empty sequence1 runs no row and checks nothing, an
+// empty sequence2 still has all of sequence1 checked).  Everything hinges on the first non-empty x[i0]: its pairs scan every y[j], and after its
+// row only characters of later x[i] can be wrong.
+static int nw_cross_validate(const uint8_t *xr, const int64_t *xo, int64_t m, const uint8_t *yr, const int64_t *yo, int64_t n) {
+  static const char order[] = "ARNDCQEGHILKMFPSTWYVBZX*";
+  auto valid = [&](uint8_t ch) { return ch != 0 && strchr(order, ch) != nullptr; };
+  auto seq1 = [&](uint8_t ch) { return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)ch); };
+  auto seq2 = [&](uint8_t ch) { return fail(DA_ERR_BAD_RESIDUE_SEQ2, "Invalid amino acid in sequence2: %c", (char)ch); };
+  int64_t i0 = 0;
+  while (i0 < m && xo[i0 + 1] == xo[i0]) ++i0;
+  if (i0 == m || n <= 0) return DA_OK;
+  const uint8_t *s1 = xr + xo[i0];
+  const int64_t l1 = xo[i0 + 1] - xo[i0];
+  if (!valid(s1[0])) return seq1(s1[0]);                                                   // pair (i0, 0), row 1
+  for (int64_t p = yo[0]; p < yo[1]; ++p) if (!valid(yr[p])) return seq2(yr[p]);           // ... its scan of y[0]
+  for (int64_t r = 1; r < l1; ++r) if (!valid(s1[r])) return seq1(s1[r]);                  // ... its later rows
+  for (int64_t p = yo[1]; p < yo[n]; ++p) if (!valid(yr[p])) return seq2(yr[p]);           // pairs (i0, 1 ..)
+  for (int64_t p = xo[i0 + 1]; p < xo[m]; ++p) if (!valid(xr[p])) return seq1(xr[p]);      // rows after i0: y is clean
+  return DA_OK;
+}
+
+// similarityNW for two sets: out[i][j] = calc(x[i], y[j]) with x[i] as sequence1.  Both sets are encoded into ONE code buffer [x ; y]; the
+// device evaluates pair (p, q) of it as calc(seq[min(p, q)], seq[max(p, q)]), so rows of x against columns of y give the row-major result and
+// rows of y against columns of x the column-major one (R's NumericMatrix(m, n)) -- sequence1 is the x string either way.
+int da_similarity_nw_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                           int64_t n, const char *matrix_name, int gap_open, int gap_ext, double *out, int column_major) {
+  const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (m <= 0 || n <= 0) return DA_OK;                    // an m x 0 or 0 x n matrix: nothing to write
+  if (!x_residues || !y_residues || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t x_total, y_total, x_max, y_max;
+  int rc;
+  if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
+  if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  const int64_t max_len = std::max(x_max, y_max), nt = m + n;
+  std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
+  std::vector<int64_t> off((size_t)nt + 1);
+  if (x_total) memcpy(res.data(), x_residues, (size_t)x_total);
+  if (y_total) memcpy(res.data() + x_total, y_residues, (size_t)y_total);
+  for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = x_offsets[i];
+  for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + y_offsets[j];
+  NwCodes nw;
+  if ((rc = nw.upload(res.data(), off.data(), nt, x_total + y_total)) != DA_OK) return rc;
+  const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
+  const int64_t r_base = column_major ? m : 0, c_base = column_major ? 0 : m;
+  const bool compact = max_len <= 127 && !da::config().no_host_widen;
+  const uint64_t nan_bits = 0xFFF8000000000000ULL;        // 0/0 as the reference's x86 host produces it
+  double nan;
+  memcpy(&nan, &nan_bits, 8);
+  const std::vector<double> table = compact ? nw_code_values(65536, nan) : std::vector<double>();
+  return rows_to_host(cols, 0, rows, compact ? sizeof(uint16_t) : sizeof(double), out, [&](int64_t b0, int64_t b1, void *d) {
+    return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), nt, max_len, mid, gap_open, gap_ext, r_base + b0, r_base + b1, false,
+                     compact ? DA_OUT_COMPACT : DA_OUT_F64, d, cols, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c_base,
+                     c_base + cols);
+  }, nullptr, nullptr, compact ? table.data() : nullptr);
 }
 
 

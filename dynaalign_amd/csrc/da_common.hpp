@@ -153,6 +153,11 @@ int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
                       int64_t row_begin, int64_t row_end, bool symmetric, int kind,
                       void *d_out, int64_t ld, hipStream_t stream, int plane_bits = 32, int tile_stride = 1,
                       bool upper_only = false, int fold_q = 0, int64_t fold_w = 0);
+// rows [row_begin, row_end) x columns [col_begin, col_end) of the pair space, each element stored once (da_dev_mh_compare_rect)
+int launch_mh_compare_rect(const uint32_t *d_planes, int64_t n, int n_hash, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                           int kind, void *d_out, int64_t ld, hipStream_t stream, int plane_bits);
+// rows [m, m_pad) of a signature matrix <- copies of its first rows (the two-set operand [x ; pad ; y])
+int launch_fill_sig_rows(uint32_t *d_sig, int64_t ld_sig, int64_t m, int64_t m_pad, int n_hash, hipStream_t stream);
 // the symmetric uint16 12-plane compare in pieces (pipelined duplicate route): tile-row bands of 8 x 128 rows, taken in order
 int64_t mh_sym_bands(int64_t n);
 int64_t mh_sym_band_prefix(int64_t n, int64_t band);
@@ -210,7 +215,8 @@ int launch_nw(const uint8_t *d_codes, const int64_t *d_off, int64_t n, int64_t m
               bool symmetric, int kind, void *d_out, int64_t ld, int32_t *d_score,
               int64_t ld_score, hipStream_t stream, int shard_rank = 0, int shard_world = 0,
               const int32_t *ord_first = nullptr, const int32_t *ord_minfirst = nullptr, const int32_t *ord_maxlast = nullptr,
-              const int32_t *ord_perm = nullptr, const uint8_t *ord_lcp = nullptr);   // ord_perm / ord_lcp: launch_nw_sort_unique (prefix sharing)
+              const int32_t *ord_perm = nullptr, const uint8_t *ord_lcp = nullptr,   // ord_perm / ord_lcp: launch_nw_sort_unique (prefix sharing)
+              int64_t col_begin = 0, int64_t col_end = -1);                          // row-block mode: only the columns [col_begin, col_end) (-1: n)
 // nw_kernels.hip: lexicographic order of (unique) sequences of <= 24 residues + the common prefix of sorted neighbours, for the ordered DP
 size_t nw_sort_unique_workspace_bytes(int64_t n);
 int launch_nw_sort_unique(const uint8_t *d_codes, const int64_t *d_off, int64_t n, void *d_work, size_t work_bytes, const int32_t **perm_out,
@@ -242,6 +248,12 @@ bool expand_stream_packed(int n_hash);   // the LDS row is packed to 9 bits per 
 int launch_expand_stream(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
                          void *d_scratch, hipStream_t stream, hipEvent_t after_lists = nullptr, bool pk = false);
 int launch_expand_stream_lists(const int32_t *d_uidx, int64_t n, int64_t U, void *d_scratch, hipStream_t stream);
+// the rectangular form (two sets collapsed per side): out[i][j] = D[ux(i)][uy(j)] / n_hash, D the U_x x U_y uint16 table (ld_d >= U_y, a multiple of
+// 8); d_scratch: expand_stream_scratch_bytes(m, U_x)
+bool expand_stream_rect_ok(int64_t m, int64_t n, int64_t U_x, int64_t U_y, int n_hash, const void *d_out, int64_t ld);
+int launch_expand_stream_rect(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx_x, int64_t m, int64_t U_x, const int32_t *d_uidx_y, int64_t n,
+                              int64_t U_y, int n_hash, double *d_out, int64_t ld, void *d_scratch, hipStream_t stream,
+                              hipEvent_t after_lists = nullptr);
 int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
                               void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no,   // launch_no: 0 .. 127, distinct per launch of a call
                               bool pk = false);

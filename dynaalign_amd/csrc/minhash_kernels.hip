@@ -277,9 +277,11 @@ __device__ __forceinline__ bool a12_takes(int ti, int tj, int64_t n, int64_t ld,
 }
 // ... and in the SHARD / row-block modes (rect_tile below): tiles completely inside the matrix and the row range whose 4-byte stores are
 // aligned -- the compiled kernel runs with only_edge = 1 on the same grid and returns at once for those.
-__device__ __forceinline__ bool s12_takes(int64_t I0, int64_t J0, int64_t n, int64_t row_end, int64_t ld, int64_t Jloc, const void *out) {
+// (col_end: the end of the column range, n in the shard / row-block modes; wide: float64 output, the rectangle calls only)
+__device__ __forceinline__ bool s12_takes(int64_t I0, int64_t J0, int64_t n, int64_t row_end, int64_t ld, int64_t Jloc, const void *out,
+                                          int64_t col_end, bool wide = false) {
   return I0 != J0 &&                                             // a diagonal tile: the general kernel forces count(i, i) = n_hash (singleton codes never match)
-         I0 + K2_TILE <= (row_end < n ? row_end : n) && J0 + K2_TILE <= n && (Jloc & 1) == 0 && k2_out_ok(out, ld, false);
+         I0 + K2_TILE <= (row_end < n ? row_end : n) && J0 + K2_TILE <= col_end && (Jloc & 1) == 0 && k2_out_ok(out, ld, wide);
 }
 
 // The tile of a one-tile-per-workgroup asm kernel; valid = it exists and the kernel takes it.  Stored at local row = global row + Iloc,
@@ -300,11 +302,14 @@ __device__ __forceinline__ RectTile sym_tile(int64_t n, int64_t ld, const void *
   t.J0 = (int64_t)tl.tj * K2_TILE;
   return t;
 }
-// rect: k_mh_compare's non-symmetric geometry (cyclic tile rows of a rank, folded shard rows, upper_only), the tiles s12_takes takes
+// rect: k_mh_compare's non-symmetric geometry (cyclic tile rows of a rank, folded shard rows, upper_only), the tiles s12_takes takes.
+// The rectangle calls (da_dev_mh_compare_rect) give a column range [col_begin, col_end), col_begin a multiple of K2_TILE: tile column tj starts
+// at global column col_begin + tj * K2_TILE and is stored from local column tj * K2_TILE; wide = float64 output.
 __device__ __forceinline__ RectTile rect_tile(int64_t bid, int64_t n, int64_t row_begin, int64_t row_end, int tile_stride, int upper_only, int TR,
-                                              int fold_q, int64_t fold_w, int band, int64_t ld, const void *out) {
+                                              int fold_q, int64_t fold_w, int band, int64_t ld, const void *out, int64_t col_begin, int64_t col_end,
+                                              bool wide = false) {
   RectTile t{0, 0, false, 0, 0, 0, 0};
-  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
+  const int T = (int)((col_end - col_begin + K2_TILE - 1) / K2_TILE);
   const uint32_t per_band = (uint32_t)band * (uint32_t)T;
   const uint32_t k = (uint32_t)(bid >> 3);
   const uint32_t kb = k / per_band;
@@ -316,9 +321,9 @@ __device__ __forceinline__ RectTile rect_tile(int64_t bid, int64_t n, int64_t ro
   t.ti = __builtin_amdgcn_readfirstlane(r0 + (l - t.tj * h));           // geometry sits in a VGPR across the loop block (it clobbers the file)
   if (t.tj >= T) return t;
   t.I0 = row_begin + (int64_t)t.ti * tile_stride * K2_TILE;
-  t.J0 = (int64_t)t.tj * K2_TILE;
+  t.J0 = col_begin + (int64_t)t.tj * K2_TILE;
   t.Iloc = (int64_t)t.ti * K2_TILE - t.I0;
-  t.Jloc = 0;
+  t.Jloc = -col_begin;
   if (fold_q > 0) {
     const int q = t.ti;
     const bool front = q <= fold_q - 1 - q;
@@ -327,7 +332,7 @@ __device__ __forceinline__ RectTile rect_tile(int64_t bid, int64_t n, int64_t ro
   }
   if (t.I0 >= row_end || t.I0 >= n) return t;
   if (upper_only && t.J0 + K2_TILE <= t.I0) return t;
-  t.valid = s12_takes(t.I0, t.J0, n, row_end, ld, t.Jloc, out);
+  t.valid = s12_takes(t.I0, t.J0, n, row_end, ld, t.Jloc, out, col_end, wide);
   return t;
 }
 
@@ -425,6 +430,29 @@ __device__ __forceinline__ void store_counts_f64(double *out, int64_t ld, const 
 #pragma unroll
     for (int c = 0; c < 8; ++c)
       nt_store2(out + (J0 + 32 * (c >> 1) + 2 * tx + (c & 1)) * ld + (I0 + 32 * g + 2 * ty), v0[c], v1[c]);
+  }
+}
+// float64, a rectangle (da_dev_mh_compare_rect): the direct half of store_counts_f64 at local row = global row + Iloc, local column =
+// global column + Jloc -- the same table lookup, every element stored once, nothing mirrored
+__device__ __forceinline__ void store_counts_f64_rect(double *out, int64_t ld, const char *tb, const uint32_t (&mis)[8][4], uint32_t nn,
+                                                        int64_t I0, int64_t J0, int64_t Iloc, int64_t Jloc, int tx, int ty) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    double v0[8], v1[8];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const uint32_t m0 = nn - mis[2 * g][c], m1 = nn - mis[2 * g + 1][c];
+      v0[2 * c] = *reinterpret_cast<const double *>(tb + ((m0 << 3) & 0x7fff8u));
+      v0[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m0 >> 13) & 0x7fff8u));
+      v1[2 * c] = *reinterpret_cast<const double *>(tb + ((m1 << 3) & 0x7fff8u));
+      v1[2 * c + 1] = *reinterpret_cast<const double *>(tb + ((m1 >> 13) & 0x7fff8u));
+    }
+    double *orow = out + (I0 + Iloc + 32 * g + 2 * ty) * ld + (J0 + Jloc + 2 * tx);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      nt_store2(orow + 32 * q, v0[2 * q], v0[2 * q + 1]);
+      nt_store2(orow + ld + 32 * q, v1[2 * q], v1[2 * q + 1]);
+    }
   }
 }
 // the lane's counters of tile column 32 (c >> 1) + 2 tx + (c & 1) in rows 32 g + 2 ty + {0, 1}, packed like a row's: the transposed tile
@@ -564,8 +592,8 @@ __device__ __forceinline__ uint32_t k2_block(uint32_t (&mis)[8][4], const K2Scal
 // ---- one tile per workgroup behind a generated block: k_mh_compare_a12 / _s12 (K2_P12) and k_mh_compare_a16 / _s16 (K2_P14 .. P16) ----
 // SYM: the symmetric matrix (sym_tile), stored direct + mirrored as float64 (the count -> double table is built in the ring once every
 // wave has left it: n_hash + 1 <= K2_A12_TABLE_MAX / K2_A16_TABLE_MAX), uint16, or into the packed table (PK; ld = its pk_lo_bytes).
-// Otherwise the rect geometry of the shard / row-block modes (rect_tile): uint16, direct only.  Diagonal and border tiles stay with
-// k_mh_compare (only_edge = 1).
+// Otherwise the rect geometry of the shard / row-block modes and of the rectangle calls (rect_tile): direct only, uint16 or -- the rectangle
+// calls -- float64 through the same table, each element stored once.  Diagonal and border tiles stay with k_mh_compare (only_edge = 1).
 #ifndef K2_PRO_PRIO
 #define K2_PRO_PRIO 0     // wave priority of the tile prologue (decode + address arithmetic before the stage loop)
 #endif
@@ -579,7 +607,7 @@ constexpr int K2_A16_TABLE_MAX = 2 * 2 * K2_TILE * 80 / 8;       // ... the 16-p
 template <K2Block B, bool SYM, bool F64, bool PK>
 __device__ __forceinline__ void k2_one_tile(const uint32_t *planes, int64_t n, int n_hash, void *out_v, int64_t ld, const RectTile &t) {
   static_assert(B == K2_P12 || B == K2_P14 || B == K2_P15 || B == K2_P16, "a one-tile block");
-  static_assert(SYM || (!F64 && !PK), "the rect geometry stores uint16 counts");
+  static_assert(SYM || !PK, "the rect geometry stores uint16 counts or float64, never the packed table");
   constexpr int PL = 12, SEGS = 3, SLOT = B == K2_P12 ? 4 * PL : 80;   // LDS bytes of a row or column per stage
   __shared__ __attribute__((aligned(16))) uint4 lds_ab[(B == K2_P12 ? 3 : 2) * 2 * K2_TILE * SLOT / 16];   // the ring; afterwards the table
   static_assert(sizeof(lds_ab) / (sizeof(double)) == (B == K2_P12 ? K2_A12_TABLE_MAX : K2_A16_TABLE_MAX),
@@ -623,17 +651,21 @@ __device__ __forceinline__ void k2_one_tile(const uint32_t *planes, int64_t n, i
   // lane coordinates again, from the value that crossed the block (same formulas as above)
   const int tid_e = (int)(v124 >> 2), wave_e = tid_e >> 6, lane_e = tid_e & 63;
   const int tx_e = ((wave_e & 1) << 3) + (lane_e & 7), ty_e = ((wave_e >> 1) << 3) + (lane_e >> 3);
-  if constexpr (!SYM) {
-    store_counts_u16(static_cast<uint16_t *>(out_v), ld, mis, nn, I0, J0, t.Iloc, t.Jloc, tx_e, ty_e, false);
-  } else if constexpr (PK) {
-    store_tile_pk(reinterpret_cast<uint16_t *>(lds_ab), mis, nn, tid_e, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
-  } else if constexpr (F64) {
-    double *ratio = reinterpret_cast<double *>(lds_ab);
+  double *ratio = reinterpret_cast<double *>(lds_ab);
+  if constexpr (F64) {
     __syncthreads();                                           // everyone has left the ring: the area becomes the table
     for (int c = tid_e; c <= n_hash; c += K2_THREADS) ratio[c] = (double)c / (double)n_hash;   // src/minHash.cpp:174
     __syncthreads();
     K2_STAMP(6);
     K2_STAMP(7);
+  }
+  if constexpr (!SYM && F64) {
+    store_counts_f64_rect(static_cast<double *>(out_v), ld, reinterpret_cast<const char *>(ratio), mis, nn, I0, J0, t.Iloc, t.Jloc, tx_e, ty_e);
+  } else if constexpr (!SYM) {
+    store_counts_u16(static_cast<uint16_t *>(out_v), ld, mis, nn, I0, J0, t.Iloc, t.Jloc, tx_e, ty_e, false);
+  } else if constexpr (PK) {
+    store_tile_pk(reinterpret_cast<uint16_t *>(lds_ab), mis, nn, tid_e, I0, J0, true, n, reinterpret_cast<uint8_t *>(out_v), ld);
+  } else if constexpr (F64) {
     store_counts_f64(static_cast<double *>(out_v), ld, reinterpret_cast<const char *>(ratio), mis, nn, I0, J0, tx_e, ty_e);
   } else {
     store_counts_u16(static_cast<uint16_t *>(out_v), ld, mis, nn, I0, J0, 0, 0, tx_e, ty_e, true);
@@ -654,7 +686,7 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s12(const uint32_t
                                                                   int64_t ld, int fold_q, int64_t fold_w, int band) {
   k2_entry();
   k2_one_tile<K2_P12, false, false, false>(planes, n, n_hash, out, ld,
-                                           rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band, ld, out));
+                                           rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band, ld, out, 0, n));
 }
 // symmetric, 14 - 16 code bits (uniform-like data; k_mh_compare<.., 16> needs 168 VGPRs = 3 waves per SIMD)
 template <bool F64, int CODE_BITS = 16>
@@ -671,7 +703,25 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_s16(const uint32_t
                                                                   int64_t ld, int fold_q, int64_t fold_w, int band) {
   k2_entry();
   k2_one_tile<K2Block(CODE_BITS), false, false, false>(planes, n, n_hash, out, ld,
-                                                       rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band, ld, out));
+                                                       rect_tile(blockIdx.x, n, row_begin, row_end, tile_stride, upper_only, TR, fold_q, fold_w, band, ld, out, 0, n));
+}
+// a rectangle rows [row_begin, row_end) x columns [col_begin, col_end) of the pair space (da_dev_mh_compare_rect; both origins multiples of
+// K2_TILE): every tile wholly inside it and off the global diagonal, stored once -- uint16 counts or float64
+template <bool F64>
+__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_r12(const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
+                                                                  int64_t row_end, int64_t col_begin, int64_t col_end, int TR,
+                                                                  void *__restrict__ out, int64_t ld, int band) {
+  k2_entry();
+  k2_one_tile<K2_P12, false, F64, false>(planes, n, n_hash, out, ld,
+                                         rect_tile(blockIdx.x, n, row_begin, row_end, 1, 0, TR, 0, 0, band, ld, out, col_begin, col_end, F64));
+}
+template <bool F64, int CODE_BITS>
+__global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_r16(const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
+                                                                  int64_t row_end, int64_t col_begin, int64_t col_end, int TR,
+                                                                  void *__restrict__ out, int64_t ld, int band) {
+  k2_entry();
+  k2_one_tile<K2Block(CODE_BITS), false, F64, false>(planes, n, n_hash, out, ld,
+                                                     rect_tile(blockIdx.x, n, row_begin, row_end, 1, 0, TR, 0, 0, band, ld, out, col_begin, col_end, F64));
 }
 
 // ---- the same 12-plane loop, PERSISTENT: a workgroup walks a sequence of tiles and its DMA ring never drains ----
@@ -790,11 +840,13 @@ __global__ __launch_bounds__(K2_THREADS, 4) void k_mh_compare_p12(const uint32_t
 // PL = bit planes per group of 32 hash functions: 32 (raw uint32 values) or 16 / 12 / 8 (dictionary
 // codes of dict_kernels.hip, as many planes as the largest column dictionary needs: same equalities
 // off the diagonal, a fraction of the planes; the diagonal is forced).
-template <bool SYM, bool F64, int PL, bool PK = false>   // PK: uint16 counts into the packed table (out_v; ld = its pk_lo_bytes)
-__global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
+// RECT: the rectangle calls' column range [col_begin, col_end) (any col_begin: an unaligned column block gathers its operand like an unaligned
+// row block); everywhere else the columns are [0, n).
+template <bool SYM, bool F64, int PL, bool PK, bool RECT>
+__device__ __forceinline__ void mh_compare_body(
     const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
     int64_t row_end, int tile_stride, int upper_only, int TR, void *__restrict__ out_v, int64_t ld,
-    int64_t ntiles, int64_t per_xcd, int fold_q, int64_t fold_w, int band, int only_edge) {
+    int64_t ntiles, int64_t per_xcd, int fold_q, int64_t fold_w, int band, int only_edge, int64_t col_begin, int64_t col_end) {
   // Row-block geometry: local tile row q covers global rows row_begin + q*tile_stride*128 + [0,128)
   // (tile_stride = 1: a contiguous block; = world: the cyclic shard of one rank) and is stored at
   // local rows q*128 + [0,128) of `out`.  upper_only skips tiles left of the diagonal.
@@ -815,7 +867,7 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
   K2_STAMP(0);
   K2_STAMP_HW();
   const int64_t bid = blockIdx.x;
-  const int T = (int)((n + K2_TILE - 1) / K2_TILE);
+  const int T = (int)((col_end - col_begin + K2_TILE - 1) / K2_TILE);
   TileId tid2;
   if (SYM && only_edge) {
     // the tiles k_mh_compare_a12 leaves: the T diagonal tiles, then the last tile column (when n is not a multiple of 128)
@@ -826,6 +878,18 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
     const int64_t L = (bid & 7) * per_xcd + (bid >> 3);
     if (L >= ntiles) return;
     tid2 = decode_tile(L, TR, T, true);
+  } else if (RECT && only_edge) {
+    // the tiles k_mh_compare_r12 / _r16 leave (both origins are multiples of K2_TILE then): the last tile row, the last tile column and the
+    // tiles on the global diagonal, ti + (row_begin - col_begin) / K2_TILE == tj -- enumerated directly, each once
+    const int delta = (int)((row_begin - col_begin) / K2_TILE), d0 = delta < 0 ? -delta : 0;
+    tid2.valid = true;
+    if (bid < T) { tid2.ti = TR - 1; tid2.tj = (int)bid; }
+    else if (bid < (int64_t)T + TR - 1) { tid2.ti = (int)(bid - T); tid2.tj = T - 1; }
+    else {
+      tid2.ti = d0 + (int)(bid - ((int64_t)T + TR - 1));
+      tid2.tj = tid2.ti + delta;
+      tid2.valid = tid2.ti < TR - 1 && tid2.tj < T - 1;
+    }
   } else {
     const uint32_t per_band = (uint32_t)band * (uint32_t)T;               // band = tile rows per band (launcher's choice)
     const uint32_t k = (uint32_t)(bid >> 3);
@@ -840,9 +904,9 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
   }
   if (!tid2.valid) return;
   const int64_t I0 = row_begin + (int64_t)tid2.ti * tile_stride * K2_TILE;  // global row of tile row 0
-  const int64_t J0 = (int64_t)tid2.tj * K2_TILE;
+  const int64_t J0 = col_begin + (int64_t)tid2.tj * K2_TILE;
   int64_t Iloc = (int64_t)tid2.ti * K2_TILE - I0;                           // local row = global row + Iloc
-  int64_t Jloc = 0;                                                         // local col = global col + Jloc
+  int64_t Jloc = -col_begin;                                                // local col = global col + Jloc
   if (!SYM && fold_q > 0) {  // folded shard layout (ShardGeom): tile rows q and Q-1-q share a stored row
     const int q = tid2.ti;
     const bool front = q <= fold_q - 1 - q;
@@ -853,7 +917,7 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
   if (!SYM && upper_only && J0 + K2_TILE <= I0) return;                     // tile entirely left of the diagonal
   // the interior tiles were taken by k_mh_compare_a12 (hand-scheduled 12-plane loop): only border / diagonal tiles here
   if (SYM && only_edge && a12_takes(tid2.ti, tid2.tj, n, ld, out_v, F64 || PK)) return;
-  if (!SYM && !F64 && only_edge && s12_takes(I0, J0, n, row_end, ld, Jloc, out_v)) return;   // ... or by k_mh_compare_s12 (shard / row-block modes)
+  if (!SYM && (!F64 || RECT) && only_edge && s12_takes(I0, J0, n, row_end, ld, Jloc, out_v, col_end, F64)) return;   // ... or by k_mh_compare_s12 / _r12 (shard / row-block modes, rectangles)
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
@@ -1067,7 +1131,7 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
   // epilogue: no per-element bounds tests, one table read per element, 16-byte stores at immediate
   // offsets.  The workgroup shares its SIMDs with two others that are in their plane loops, so every
   // instruction here costs ~3 issue slots: the general path below ran 10 us per tile, this one ~3.
-  const bool interior = I0 + K2_TILE <= (row_end < n ? row_end : n) && J0 + K2_TILE <= n;
+  const bool interior = I0 + K2_TILE <= (row_end < n ? row_end : n) && J0 + K2_TILE <= col_end;
   if (F64) {
     double *out = reinterpret_cast<double *>(out_v);
     const bool vec_ok = ((ld & 1) == 0) && ((Jloc & 1) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
@@ -1109,11 +1173,11 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
       for (int g = 0; g < 4; ++g) {
         const int64_t gj = J0 + 32 * g + 2 * tx;
         const double v0 = widen(matches(r, 2 * g)), v1 = widen(matches(r, 2 * g + 1));
-        if (vec_ok && gj + 1 < n) {
+        if (vec_ok && gj + 1 < col_end) {
           *reinterpret_cast<double2 *>(orow + gj) = make_double2(v0, v1);
         } else {
-          if (gj < n) orow[gj] = v0;
-          if (gj + 1 < n) orow[gj + 1] = v1;
+          if (gj < col_end) orow[gj] = v0;
+          if (gj + 1 < col_end) orow[gj + 1] = v1;
         }
       }
     }
@@ -1168,8 +1232,8 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int64_t gj = J0 + 32 * g + 2 * tx;
-        if (gj < n) orow[gj] = (uint16_t)matches(r, 2 * g);
-        if (gj + 1 < n) orow[gj + 1] = (uint16_t)matches(r, 2 * g + 1);
+        if (gj < col_end) orow[gj] = (uint16_t)matches(r, 2 * g);
+        if (gj + 1 < col_end) orow[gj + 1] = (uint16_t)matches(r, 2 * g + 1);
       }
     }
     if (SYM && tid2.ti != tid2.tj) {
@@ -1188,6 +1252,23 @@ __global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
     }
   }
   K2_STAMP(3);
+}
+template <bool SYM, bool F64, int PL, bool PK = false>   // PK: uint16 counts into the packed table (out_v; ld = its pk_lo_bytes)
+__global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare(
+    const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin,
+    int64_t row_end, int tile_stride, int upper_only, int TR, void *__restrict__ out_v, int64_t ld,
+    int64_t ntiles, int64_t per_xcd, int fold_q, int64_t fold_w, int band, int only_edge) {
+  mh_compare_body<SYM, F64, PL, PK, false>(planes, n, n_hash, row_begin, row_end, tile_stride, upper_only, TR, out_v, ld, ntiles, per_xcd, fold_q,
+                                           fold_w, band, only_edge, 0, n);
+}
+// the rectangle calls: what k_mh_compare_r12 / _r16 leave (only_edge = 1: border tiles, tiles on the global diagonal) or, for operands and outputs
+// they do not take, the whole rectangle
+template <bool F64, int PL>
+__global__ __launch_bounds__(K2_THREADS, 3) void k_mh_compare_rect(
+    const uint32_t *__restrict__ planes, int64_t n, int n_hash, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end, int TR,
+    void *__restrict__ out_v, int64_t ld, int band, int only_edge) {
+  mh_compare_body<false, F64, PL, false, true>(planes, n, n_hash, row_begin, row_end, 1, 0, TR, out_v, ld, 0, 0, 0, 0, band, only_edge, col_begin,
+                                               col_end);
 }
 
 // Lower triangle <- upper triangle (after a gather of upper-triangular rows).
@@ -1384,6 +1465,48 @@ int launch_mh_compare(const uint32_t *d_planes, int64_t n, int n_hash,
         hipLaunchKernelGGL((k_mh_compare<decltype(SYM)::value, decltype(F64)::value, decltype(PL)::value>), grid, block, 0, stream, d_planes, n,
                            n_hash, row_begin, row_end, tile_stride, upper_only ? 1 : 0, TR, d_out, ld, ntiles, per_xcd, fold_q, fold_w, band, only_edge);
       });
+    });
+  });
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+// The rectangle rows [row_begin, row_end) x columns [col_begin, col_end) of the n x n pair space, stored once at d_out[(i - row_begin) * ld +
+// (j - col_begin)] (da_dev_mh_compare_rect; the row-block mode is col_begin = 0, col_end = n).  The hand-scheduled loops take the tiles wholly
+// inside the rectangle when both origins are multiples of 128 rows of the operand and the output suits their wide stores; k_mh_compare_rect
+// takes the rest (border tiles, tiles on the global diagonal) or, otherwise, everything.
+int launch_mh_compare_rect(const uint32_t *d_planes, int64_t n, int n_hash, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                           int kind, void *d_out, int64_t ld, hipStream_t stream, int plane_bits) {
+  if (row_end <= row_begin || col_end <= col_begin) return DA_OK;
+  if (plane_bits != 8 && plane_bits != 12 && plane_bits != 14 && plane_bits != 15 && plane_bits != 16 && plane_bits != 32)
+    return fail(DA_ERR_BAD_ARG, "plane_bits must be 8, 12, 14, 15, 16 or 32 (got %d)", plane_bits);
+  const int code_bits = plane_bits;
+  if (plane_bits == 14 || plane_bits == 15) plane_bits = 16;
+  const int TR = (int)ceil_div(row_end - row_begin, K2_TILE), TC = (int)ceil_div(col_end - col_begin, K2_TILE);
+  int band = K2_BAND;                                    // bands of tile rows dealt round-robin to the XCDs, as in the row-block modes
+  while (band > 1 && ceil_div(TR, band) < 48) band >>= 1;
+  const int64_t nblocks = 8 * ceil_div(ceil_div(TR, band), 8) * (int64_t)band * TC;
+  if (nblocks > 0x7fffffffLL) return fail(DA_ERR_UNSUPPORTED, "pair space too large for one launch");
+  const dim3 grid((unsigned)nblocks), block(K2_THREADS);
+  const bool f64 = kind == DA_OUT_F64;
+  const bool asm_ok = !config().k2_no_asm && k2_out_ok(d_out, ld, f64) && (row_begin % K2_TILE) == 0 && (col_begin % K2_TILE) == 0;
+  const bool r12 = plane_bits == 12 && asm_ok && (!f64 || (int64_t)n_hash + 1 <= K2_A12_TABLE_MAX);
+  const bool r16 = plane_bits == 16 && asm_ok && (!f64 || (int64_t)n_hash + 1 <= K2_A16_TABLE_MAX);
+  dispatch<false, true>(f64, [&](auto F64) {
+    if (r12)
+      hipLaunchKernelGGL((k_mh_compare_r12<decltype(F64)::value>), grid, block, 0, stream, d_planes, n, n_hash, row_begin, row_end, col_begin, col_end,
+                         TR, d_out, ld, band);
+    if (r16)
+      dispatch<14, 15, 16>(code_bits, [&](auto B) {
+        hipLaunchKernelGGL((k_mh_compare_r16<decltype(F64)::value, decltype(B)::value>), grid, block, 0, stream, d_planes, n, n_hash, row_begin,
+                           row_end, col_begin, col_end, TR, d_out, ld, band);
+      });
+    dispatch<8, 12, 16, 32>(plane_bits, [&](auto PL) {
+      // what is left for the general kernel after the hand-scheduled one: last tile row + last tile column + at most min(TR, TC) diagonal tiles
+      const bool edge = r12 || r16;
+      hipLaunchKernelGGL((k_mh_compare_rect<decltype(F64)::value, decltype(PL)::value>),
+                         edge ? dim3((unsigned)((int64_t)TC + TR - 1 + std::min(TR, TC))) : grid, block, 0, stream, d_planes, n, n_hash, row_begin,
+                         row_end, col_begin, col_end, TR, d_out, ld, band, edge ? 1 : 0);
     });
   });
   DA_HIP_TRY(hipGetLastError());
@@ -2058,6 +2181,10 @@ int launch_expand_stream_lists(const int32_t *d_uidx, int64_t n, int64_t U, void
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
+// the launch both expansions share: table rows [row_begin, row_end) through the row lists L (copies among n_rows output rows), columns through
+// the id map d_colids[n_cols]
+static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_colids, int64_t n_cols, const EsLists &L, int64_t n_rows, int64_t row_begin,
+                     int64_t row_end, int n_hash, double *d_out, int64_t ld, hipStream_t stream, int launch_no, bool pk);
 // k_expand_stream on the table rows [row_begin, row_end) (lists from launch_expand_stream_lists on the same scratch)
 int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
                               void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no, bool pk) {
@@ -2066,7 +2193,10 @@ int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *
     return fail(DA_ERR_UNSUPPORTED, "row expansion: shape not covered");
   if (row_end > U) row_end = U;
   if (row_begin >= row_end) return DA_OK;
-  const EsLists L = es_layout(d_scratch, n, U);
+  return es_launch(d_D, ld_d, d_uidx, n, es_layout(d_scratch, n, U), n, row_begin, row_end, n_hash, d_out, ld, stream, launch_no, pk);
+}
+static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, const EsLists &L, int64_t n_rows, int64_t row_begin,
+                     int64_t row_end, int n_hash, double *d_out, int64_t ld, hipStream_t stream, int launch_no, bool pk) {
   static std::atomic<int> es_cus;
   static std::atomic<uint64_t> es_attr_done;
   int dev = 0;
@@ -2089,7 +2219,7 @@ int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *
   lds = std::max<size_t>(lds, 82 * 1024);
   // one resident workgroup (16 waves) per CU: every workgroup of the grid must be resident from the start (first items are dealt by block index)
   int64_t grid = (int64_t)es_cus.load();
-  grid = std::min<int64_t>(grid, (row_end - row_begin) + n / ES_COPIES + 1);
+  grid = std::min<int64_t>(grid, (row_end - row_begin) + n_rows / ES_COPIES + 1);
 #define DA_ES(P, Q) hipLaunchKernelGGL((k_expand_stream<P, Q>), dim3((unsigned)grid), dim3(ES_THREADS), lds, stream, d_D, ld_d, d_uidx, L.cstart, L.cpos, L.items, \
                                        L.istart, (int)row_begin, (int)row_end, (int)n, n_hash, d_out, ld, L.ticket + launch_no)
   const int64_t nq = ceil_div((pk ? pk_row_bytes(ld_d) : 2 * ld_d) >> 4, ES_THREADS);   // 16-byte units of a table row per thread
@@ -2109,6 +2239,41 @@ int launch_expand_stream(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uid
   if (rc != DA_OK) return rc;
   if (after_lists) DA_HIP_TRY(hipEventRecord(after_lists, stream));
   return launch_expand_stream_rows(d_D, ld_d, d_uidx, n, U, n_hash, d_out, ld, d_scratch, 0, U, stream, 0, pk);
+}
+
+// ---- the RECTANGULAR row expansion (two-set calls: da_dev_similarity_mh_cross) ----------------------------------------------------------------
+// out[i][j] = D[ux(i)][uy(j)] / n_hash for the m x n result of two sets collapsed per side: D is the U_x x U_y count table (not symmetric, not
+// square), d_uidx_x / d_uidx_y the unique ids of the m rows / n columns.  k_expand_stream takes its row lists and its column id map as separate
+// arguments, so the kernel is the square form's (uint16 table; the LDS row repacked to 9 bits when n_hash <= 511): a workgroup holds table
+// row r -- U_y counts -- in LDS and writes the output rows of r's copies in x, columns through y's id map, es_ratio's divide, 16-byte streaming
+// stores, every element once; an odd n has its last column peeled by the kernel.  One launch on one stream.
+bool expand_stream_rect_ok(int64_t m, int64_t n, int64_t U_x, int64_t U_y, int n_hash, const void *d_out, int64_t ld) {
+  return m >= 1 && m <= 0x7ffffff0LL && n >= 1 && n <= 0x7ffffff0LL && U_x >= 1 && U_x <= m && U_y >= 1 && U_y <= 65536 && n_hash >= 1 &&
+         n_hash <= 2047 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0;
+}
+int launch_expand_stream_rect(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx_x, int64_t m, int64_t U_x, const int32_t *d_uidx_y, int64_t n,
+                              int64_t U_y, int n_hash, double *d_out, int64_t ld, void *d_scratch, hipStream_t stream, hipEvent_t after_lists) {
+  if (!expand_stream_rect_ok(m, n, U_x, U_y, n_hash, d_out, ld) || ld_d < U_y || (ld_d & 7) || ld_d > 65536 || (reinterpret_cast<uintptr_t>(d_D) & 15))
+    return fail(DA_ERR_UNSUPPORTED, "rectangular row expansion: shape not covered");
+  int rc = launch_expand_stream_lists(d_uidx_x, m, U_x, d_scratch, stream);   // the copies of every unique row of x: expand_stream_scratch_bytes(m, U_x)
+  if (rc != DA_OK) return rc;
+  if (after_lists) DA_HIP_TRY(hipEventRecord(after_lists, stream));
+  return es_launch(d_D, ld_d, d_uidx_y, n, es_layout(d_scratch, m, U_x), m, 0, U_x, n_hash, d_out, ld, stream, 0, false);
+}
+
+// filler rows of a signature matrix: rows [m, m_pad) repeat rows 0, 1, ... of the real ones (the two-set operand [x ; pad ; y]: a filler row
+// only adds occurrences of values that are there already, so the column dictionaries keep every equality; its results are never stored)
+__global__ __launch_bounds__(256) void k_fill_sig_rows(uint32_t *__restrict__ sig, int64_t ld_sig, int64_t m, int64_t m_pad, int n_hash) {
+  const int64_t r = m + blockIdx.x;
+  if (r >= m_pad) return;
+  const uint32_t *src = sig + ((r - m) % m) * ld_sig;
+  for (int h = threadIdx.x; h < n_hash; h += 256) sig[r * ld_sig + h] = src[h];
+}
+int launch_fill_sig_rows(uint32_t *d_sig, int64_t ld_sig, int64_t m, int64_t m_pad, int n_hash, hipStream_t stream) {
+  if (m_pad <= m || m <= 0) return DA_OK;
+  hipLaunchKernelGGL(k_fill_sig_rows, dim3((unsigned)(m_pad - m)), dim3(256), 0, stream, d_sig, ld_sig, m, m_pad, n_hash);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
 }
 
 // device bytes of the column-gathered table the two-pass expansion wants (0: the shape is not covered, pass NULL)

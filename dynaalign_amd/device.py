@@ -149,6 +149,18 @@ def mh_compare(planes, n, n_hash, row_begin=0, row_end=None, symmetric=None, kin
     return out
 
 
+def mh_compare_rect(planes, n, n_hash, row_begin, row_end, col_begin, col_end, kind=DA_OUT_F64, out=None):
+    """K2 on a rectangle: rows [row_begin, row_end) x columns [col_begin, col_end) of the n-row problem `planes` was built
+    for, every element once (da_dev_mh_compare_rect).  Two sets are compared through ONE operand built on their
+    concatenation; origins that are multiples of 128 get the hand-scheduled kernels."""
+    lib = _capi.load()
+    _require_cuda(planes, "bit planes")
+    out = _alloc_out(row_end - row_begin, col_end - col_begin, kind, planes.device, out)
+    _call(lib.da_dev_mh_compare_rect, planes.data_ptr(), planes.bits, int(n), int(n_hash), int(row_begin), int(row_end),
+                                           int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
 def nw_encode(ds):
     """K0.  Fills ds.codes; returns the int32 flag tensor (0 = all residues valid)."""
     lib = _capi.load()
@@ -182,6 +194,28 @@ def nw(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row_end=
                               int(gap_ext), row_begin, row_end, 1 if symmetric else 0, kind, out.data_ptr(),
                               out.stride(0), None if score is None else score.data_ptr(),
                               0 if score is None else score.stride(0), _stream())
+    return out
+
+
+def nw_rect(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row_end=None, col_begin=0, col_end=None,
+            kind=DA_OUT_F64, out=None):
+    """K3 on a rectangle (da_dev_nw_rect): element (i, j) = calc(seq[min(i, j)], seq[max(i, j)]).  On the codes of x + y,
+    rows of x against columns of y give calc(x[i], y[j]); rows of y against columns of x its transpose."""
+    lib = _capi.load()
+    if ds.codes is None:
+        raise ValueError("call nw_encode(ds) first")
+    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
+    if mid < 0:
+        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    n = ds.n
+    row_end = n if row_end is None else row_end
+    col_end = n if col_end is None else col_end
+    if out is None:
+        dt = {DA_OUT_F64: torch.float64, DA_OUT_COMPACT: torch.int16}.get(kind, torch.int32)
+        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=dt, device=ds.residues.device)
+    _call(lib.da_dev_nw_rect, ds.codes.data_ptr(), ds.offsets.data_ptr(), n, ds.max_len, mid, int(gap_open), int(gap_ext),
+                                   int(row_begin), int(row_end), int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0),
+                                   _stream())
     return out
 
 
@@ -295,6 +329,35 @@ def similarity_mh(ds, k, n_hash, seeds, out=None):
     _call(lib.da_dev_similarity_mh, ds.residues.data_ptr(), ds.offsets.data_ptr(), n, ds.total, int(k), int(n_hash),
                                          seeds.data_ptr(), out.data_ptr(), out.stride(0), _stream())
     return out
+
+
+def similarity_mh_cross(dx, dy, k, n_hash, seeds, out=None):
+    """similarityMH_cross on two device-resident sets, one C call (da_dev_similarity_mh_cross): K1 per side, K1b on the union,
+    the rectangle compare -- or, when collapsing byte-identical strings per side pays, the table of the unique strings and
+    its rectangular row expansion.  Returns the (m, n) float64 tensor."""
+    lib = _capi.load()
+    if not torch.is_tensor(seeds):
+        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(dx.residues.device)
+    _require_cuda(dx.residues, "residues of x")
+    _require_cuda(dy.residues, "residues of y")
+    if out is None:
+        out = _alloc_out(dx.n, dy.n, DA_OUT_F64, dx.residues.device, None)
+    _call(lib.da_dev_similarity_mh_cross, dx.residues.data_ptr(), dx.offsets.data_ptr(), dx.n, dx.total, dy.residues.data_ptr(),
+                                               dy.offsets.data_ptr(), dy.n, dy.total, int(k), int(n_hash), seeds.data_ptr(),
+                                               out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
+def mh_cross_last_route():
+    """what this thread's last similarity_mh_cross call did: dict(m, n, unique_x, unique_y, dedup, plane_bits, plan_ms, codes_ms,
+    k2_ms, lists_ms, expand_ms)"""
+    m, n, ux, uy = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    t, b = ctypes.c_int(0), ctypes.c_int(0)
+    ms = (ctypes.c_double * 5)()
+    _capi.check(_capi.load().da_mh_cross_last_route(ctypes.addressof(m), ctypes.addressof(n), ctypes.addressof(ux), ctypes.addressof(uy),
+                                                    ctypes.addressof(t), ctypes.addressof(b), ctypes.addressof(ms)))
+    return {"m": m.value, "n": n.value, "unique_x": ux.value, "unique_y": uy.value, "dedup": t.value == 1, "plane_bits": b.value,
+            "plan_ms": ms[0], "codes_ms": ms[1], "k2_ms": ms[2], "lists_ms": ms[3], "expand_ms": ms[4]}
 
 
 def mh_last_route():

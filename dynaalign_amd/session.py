@@ -8,6 +8,7 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     s = MinHashSession(sequences, k=4, n_hash=500, seed=12345)      # upload + K1 once
     S = s.similarity(idx)                                           # == similarityMH(sequences[idx], 4, 500, seed=12345)
     thr, i, j, w = s.edges(idx, thresh_p=0.8)                       # == similarityMH_edges(sequences[idx], ...)
+    R = s.cross(new, idx)                                           # == similarityMH_cross(new, sequences[idx], 4, 500, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
 seeds per call, src/minHash.cpp:73,137); the contract -- MinHash estimates under one hash family -- holds.
@@ -56,6 +57,30 @@ class MinHashSession:
         planes, m = self.planes(idx)
         out = device.mh_compare(planes, m, self.n_hash)
         return SimilarityMatrix(out.cpu().numpy())
+
+    def cross(self, sequences, idx=None):
+        """New sequences against the resident set (or its subset idx): the (m, len(idx)) float64 matrix
+        similarityMH_cross(sequences, resident[idx], k, n_hash, seed=self.seed).  K1 on the new strings under the session's
+        seeds, ONE dictionary over [new ; filler ; resident[idx]] -- the new rows padded to a multiple of 128 with rows that
+        repeat real ones, so the rectangle's origins are tile-aligned -- then the rectangle compare."""
+        res, off = pack_sequences(sequences)
+        m = len(off) - 1
+        if m == 0:
+            _capi.check(_capi.DA_ERR_EMPTY_INPUT)
+        new = device.DeviceSequences(res, off, self.sig.device)
+        sig_new, _ = device.minhash_signatures(new, self.k, self.n_hash, self.seeds, want_planes=False)
+        sig_res, n = self._subset(idx)
+        m_pad = -(-m // 128) * 128
+        if m_pad + n > 131068 >= m + n:       # keep the dictionary rather than the alignment, as da_dev_similarity_mh_cross does
+            m_pad = m
+        joint = torch.empty((m_pad + n, self.sig.shape[1]), dtype=torch.int32, device=self.sig.device)
+        joint[:m] = sig_new[:m]
+        if m_pad > m:
+            joint[m:m_pad] = sig_new[torch.arange(m_pad - m, device=self.sig.device) % m]
+        joint[m_pad:] = sig_res[:n]
+        planes = device.mh_planes(joint, m_pad + n, self.n_hash)
+        out = device.mh_compare_rect(planes, m_pad + n, self.n_hash, 0, m, m_pad, m_pad + n)
+        return SimilarityMatrix(out.cpu().numpy()[:m, :n])
 
     def edges_csr(self, idx=None, thresh_p=0.8):
         """The thresholded graph of the subset as the canonical symmetric CSR clusterbreak.louvain_csr takes -- sorted ON THE DEVICE

@@ -3,6 +3,11 @@
     similarityMH(sequences, k=4, n_hash=50)                      reference R/RcppExports.R:15-17
     similarityNW(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4)   reference R/RcppExports.R:34-36
 
+and their two-set forms (no counterpart in the reference: a second set against the first, an m x n matrix)
+
+    similarityMH_cross(x, y, k=4, n_hash=50)
+    similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4)
+
 Same names, argument order, defaults and error texts as the reference; the
 bodies marshal to the C ABI (include/dynaalign.h) exactly as the Rcpp glue in
 r_glue/ does.  Results are dense symmetric n x n float64 matrices with
@@ -37,13 +42,13 @@ def get_option(name):
 
 
 class SimilarityMatrix(np.ndarray):
-    """float64 (n, n) ndarray carrying R-style ``dimnames``."""
+    """float64 (n, n) ndarray -- (m, n) for the two-set calls -- carrying R-style ``dimnames``."""
 
     def __new__(cls, arr):
         obj = np.asarray(arr).view(cls)
         n = obj.shape[0]
         labels = [str(i + 1) for i in range(n)]
-        obj.dimnames = [labels, list(labels)]
+        obj.dimnames = [labels, [str(j + 1) for j in range(obj.shape[1])] if obj.ndim == 2 else list(labels)]
         return obj
 
     def __array_finalize__(self, obj):
@@ -149,6 +154,20 @@ def similarityMH(sequences, k=4, n_hash=50, *, seed=None, devices=None, exchange
     return SimilarityMatrix(out[:n, :n])
 
 
+def similarityMH_cross(x, y, k=4, n_hash=50, *, seed=None):
+    """MinHash similarity of every sequence of ``x`` against every sequence of ``y``: the (m, n) matrix
+    R[i, j] = #{h : sig_x[i, h] == sig_y[j, h]} / n_hash -- bit for bit the block [0:m, m:m+n] of
+    ``similarityMH(x + y, k, n_hash)`` under the same seeds.  No forced diagonal: an element is 1.0 only because the
+    signatures agree.  Errors as similarityMH, with "Input sequences vector cannot be empty" for ``x``, then for ``y``."""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    n = len(yo) - 1
+    out = np.empty((max(m, 1), max(n, 1)), np.float64)
+    _capi.check(lib.da_similarity_mh_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash,
+                                           seeds.ctypes.data, out.ctypes.data, 0))
+    return SimilarityMatrix(out[:m, :n])
+
+
 def minhash_signatures(sequences, k=4, n_hash=50, *, seed=None):
     """The (n, n_hash) uint32 signature matrix (reference src/minHash.cpp:140-157)."""
     lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
@@ -191,6 +210,22 @@ def similarityNW(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, devi
                                               _as_int(gapExt, "gapExt"), out.ctypes.data, ctypes.addressof(opts)))
     _record_phases(keep)
     return SimilarityMatrix(out[:n, :n])
+
+
+def similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
+    """Fraction identity of every sequence of ``x`` against every sequence of ``y``: the (m, n) matrix
+    R[i, j] = calc(x[i], y[j]) with x[i] as sequence1 (the alignment is not symmetric) -- bit for bit the block
+    [0:m, m:m+n] of ``similarityNW(x + y, ...)``.  An empty ``x`` or ``y`` gives a (0, n) / (m, 0) matrix; residue errors are
+    what the reference's lazy fill would raise first with the pairs visited i over ``x``, then j over ``y``."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    out = np.empty((max(m, 1), max(n, 1)), np.float64)
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    _capi.check(lib.da_similarity_nw_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
+                                           _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), out.ctypes.data, 0))
+    return SimilarityMatrix(out[:m, :n])
 
 
 def nw_pairs(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, row_begin=0, row_end=None):

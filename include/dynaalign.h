@@ -45,6 +45,7 @@ extern "C" {
 #endif
 
 /* (round 4 added entry points only -- da_config_reload, da_debug_comm_cache_state, da_mh_last_route_split: the version stays)
+ * (the two-set entry points -- da_similarity_*_cross, da_dev_*_rect, da_dev_similarity_mh_cross, da_mh_cross_last_route -- were added likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -169,6 +170,33 @@ int da_nw_pairs(const uint8_t *residues, const int64_t *offsets, int64_t n,
                 int64_t row_begin, int64_t row_end,
                 int32_t *matches_out, int32_t *len_out, int32_t *score_out);
 
+/* ---- two sets: x (m sequences) against y (n sequences), an m x n float64 matrix R ---------
+ * What a caller does after clustering one set: compare a second set against it (new peptides against a library, one probe array
+ * against another, consensus sequences against members).
+ *   MinHash: R[i][j] = (double)#{h : sig_x[i][h] == sig_y[j][h]} / (double)n_hash, signatures, seeds and k-mers exactly those of
+ *            similarityMH (src/minHash.cpp:140-157, :174): bit for bit the block [0:m, m:m+n] of similarityMH(c(x, y), k, n_hash) under
+ *            the same seeds.  NO forced diagonal: R[i][j] is 1.0 only because the signatures agree.
+ *   NW:      R[i][j] = calc(x[i], y[j]) with x[i] as sequence1 (src/pairwiseSeqAlign.cpp:209-313): bit for bit the block [0:m, m:m+n] of
+ *            similarityNW(c(x, y), ...).  NaN where both strings are empty, 0.0 where exactly one is.
+ * column_major = 0 writes out[i * n + j]; 1 writes out[i + j * m] (R's NumericMatrix(m, n)); neither involves a host-side transpose.
+ * Validation, before any device is needed -- MinHash: x empty, then y empty (DA_ERR_EMPTY_INPUT), then k, then n_hash.  NW: the matrix
+ * name first; m == 0 or n == 0 returns DA_OK and writes nothing; residue errors are what the reference's lazy fill would raise first
+ * with the pairs visited i ascending over x and j ascending over y, each pair in calc's own order (:238-250: seq1[0], every character of
+ * seq2, seq1[1], ...; an empty x[i] checks nothing, an empty y[j] still has every character of x[i] checked).
+ * Limits: n_hash <= 65535 (DA_ERR_UNSUPPORTED beyond: the host-side chunking of da_similarity_mh is not carried over); NW sequence lengths
+ * as da_similarity_nw; more than 131 068 rows in the joint operand (m rounded up to a multiple of 128, + n) take the raw 32-plane
+ * operand, like n > 131 068 in da_dev_mh_planes -- still exact.  When only the padding of x pushes the joint operand over that bound
+ * (m + n <= 131 068 < m rounded up + n), x is left unpadded: the dictionary codes are kept and the compiled compare kernel serves the call
+ * (the column origin is then not a multiple of 128).  Single device; without one, DA_ERR_NO_DEVICE after validation.
+ * The host calls work in row blocks of DYNAALIGN_BLOCK_BYTES sized by the column count alone (a tall result is not cut by its width); for
+ * MinHash the device block has an even leading dimension, so odd column counts keep the hand-scheduled kernels. */
+int da_similarity_mh_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                           const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                           int k, int n_hash, const uint32_t *seeds, double *out, int column_major);
+int da_similarity_nw_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                           const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                           const char *matrix_name, int gap_open, int gap_ext, double *out, int column_major);
+
 /* ---- device-pointer entry points (bench / multi-GPU sharding) ------------ */
 
 /* Leading dimension (in uint32 elements) the library uses for signature
@@ -221,6 +249,35 @@ int da_dev_mh_planes(const uint32_t *d_sig, int64_t ld_sig, int64_t n, int n_has
 int da_dev_mh_compare(const uint32_t *d_planes, int plane_bits, int64_t n, int n_hash,
                       int64_t row_begin, int64_t row_end, int symmetric,
                       int kind, void *d_out, int64_t ld, void *stream);
+
+/* K2 on a RECTANGLE: rows [row_begin, row_end) x columns [col_begin, col_end) of the n-row problem the planes were built for, every element
+ * stored once: d_out holds (row_end - row_begin) rows of ld >= col_end - col_begin elements, element (i, j) at
+ * d_out[(i - row_begin) * ld + (j - col_begin)].  The row-block mode of da_dev_mh_compare is col_begin = 0, col_end = n.  An element whose
+ * global row equals its global column is n_hash (1.0), as there; everything else is a plain pair, so two sets compared through one
+ * operand must have been coded by ONE da_dev_mh_planes call on their concatenation.  kind = DA_OUT_F64 or DA_OUT_COMPACT.
+ * The hand-scheduled 12- and 14 / 15 / 16-bit loops take every tile that lies wholly inside the rectangle and off the global diagonal when
+ * row_begin and col_begin are multiples of 128, ld is even and d_out is 16-byte (float64; n_hash <= 4607 / 5119) or 4-byte (uint16) aligned;
+ * the compiled kernel takes the rest, or everything (8 / 32 planes, odd ld, unaligned output or origins, DYNAALIGN_K2_NO_ASM=1). */
+int da_dev_mh_compare_rect(const uint32_t *d_planes, int plane_bits, int64_t n, int n_hash,
+                           int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                           int kind, void *d_out, int64_t ld, void *stream);
+
+/* similarityMH_cross (see da_similarity_mh_cross) on two resident sets as ONE call, like da_dev_similarity_mh: d_out = m rows of ld >= n
+ * doubles.  Direct route: K1 per side into one signature matrix [x ; filler ; y] (x padded to a multiple of 128 rows with rows that repeat
+ * real ones: every equality is kept, their results are never stored), K1b ONCE on the union, da_dev_mh_compare_rect's kernels.  Duplicate
+ * route: byte-identical strings are collapsed PER SIDE (U_x, U_y unique strings), the unique strings are compared into a U_x x U_y uint16
+ * table and a rectangular row expansion (a workgroup holds a table row in LDS and writes the output rows of its copies in x, columns through
+ * y's id map) writes every element once.  Taken when sqrt(U_x U_y / (m n)) <= 0.68 (DYNAALIGN_MH_DEDUP_MAX_PCT, in percent), m + n >= 2048
+ * (DYNAALIGN_MH_DEDUP_MIN_N), U_y <= 65536, n_hash <= 2047, ld even and d_out 16-byte aligned; DYNAALIGN_MH_NO_DEDUP=1 disables it.
+ * One stream; no pipelining, packed table, heavy / rare split or sparse route here.  n_hash <= 65535.  Synchronises the stream.
+ * da_mh_cross_last_route: what the calling thread's last such call did -- m, n, unique strings per side (m, n when no plan was made),
+ * route (0 direct, 1 duplicate), the plane count K1b chose and the times in ms of {plans, K1 + K1b, K2, copy lists, expansion}
+ * (direct: {plans, K1 + K1b, K2, 0, 0}).  Any pointer may be NULL. */
+int da_dev_similarity_mh_cross(const uint8_t *d_x_residues, const int64_t *d_x_offsets, int64_t m, int64_t x_total,
+                               const uint8_t *d_y_residues, const int64_t *d_y_offsets, int64_t n, int64_t y_total,
+                               int k, int n_hash, const uint32_t *d_seeds, double *d_out, int64_t ld, void *stream);
+int da_mh_cross_last_route(int64_t *m_out, int64_t *n_out, int64_t *unique_x_out, int64_t *unique_y_out, int *route_out,
+                           int *plane_bits_out, double *ms5_out);
 
 /* K1 + K1b + K2 as ONE call: similarityMH (src/minHash.cpp:119-188) from packed residues in HBM to the dense float64
  * n x n matrix in HBM (d_out, leading dimension ld >= n doubles; 16-byte aligned and even ld for the wide-store kernels).
@@ -342,6 +399,15 @@ int da_dev_nw(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, int64
               int64_t row_begin, int64_t row_end, int symmetric,
               int kind, void *d_out, int64_t ld, int32_t *d_score, int64_t ld_score,
               void *stream);
+
+/* K3 on a RECTANGLE: the row-block mode of da_dev_nw restricted to the columns [col_begin, col_end); d_out holds (row_end - row_begin) rows of
+ * ld >= col_end - col_begin elements.  Pair (i, j) is calc(seq[min(i, j)], seq[max(i, j)]) as everywhere: on the codes of c(x, y), rows of x
+ * against columns of y give calc(x[i], y[j]) row-major, rows of y against columns of x the same values column-major.  Direct sweep only (no
+ * duplicate route, no prefix sharing); no score output; any kind. */
+int da_dev_nw_rect(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, int64_t max_len,
+                   int matrix_id, int gap_open, int gap_ext,
+                   int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                   int kind, void *d_out, int64_t ld, void *stream);
 
 /* With symmetric != 0, kind F64 / COMPACT and no score output, da_dev_nw (and da_similarity_nw[_edges]) first collapse
  * byte-identical sequences: the DP runs on the table of unique strings -- as an ORDERED square, calculate_similarity is

@@ -8,8 +8,8 @@
 // generated shims come out byte-identical; the two ADDED exports (similarityMH_edges,
 // similarityNW_edges) get new shims in src/RcppExports.cpp + R/RcppExports.R and need
 // `export(similarityMH_edges)` / `export(similarityNW_edges)` in NAMESPACE (roxygen writes them
-// from the @export tags below).  Without compileAttributes() only the two original functions
-// are callable.
+// from the @export tags below); likewise the two-set exports similarityMH_cross / similarityNW_cross.
+// Without compileAttributes() only the two original functions are callable.
 //
 // NOT compiled in the build container (R and Rcpp are absent there); it is the binding a
 // maintainer adds.  Everything it calls is exercised through the same C ABI by
@@ -57,6 +57,13 @@ void set_dimnames(NumericMatrix &m) {  // src/minHash.cpp:181-185, src/pairwiseS
   CharacterVector labels(n);
   for (R_xlen_t i = 0; i < n; ++i) labels[i] = std::to_string(i + 1);
   m.attr("dimnames") = List::create(labels, labels);
+}
+
+void set_dimnames_rect(NumericMatrix &m) {  // the two-set calls: rows "1".."m", columns "1".."n"
+  CharacterVector rows(m.nrow()), cols(m.ncol());
+  for (R_xlen_t i = 0; i < m.nrow(); ++i) rows[i] = std::to_string(i + 1);
+  for (R_xlen_t j = 0; j < m.ncol(); ++j) cols[j] = std::to_string(j + 1);
+  m.attr("dimnames") = List::create(rows, cols);
 }
 
 // Seed for HashFamily: the reference draws std::random_device{}() (src/minHash.cpp:73) and
@@ -224,4 +231,43 @@ List similarityNW_edges(CharacterVector sequences, std::string matrixName = "BLO
   for (int64_t e = 0; e < m; ++e) { from[e] += 1; to[e] += 1; }   // R is 1-based
   return List::create(_["threshold"] = thr,
                       _["edges"] = DataFrame::create(_["from"] = from, _["to"] = to, _["weight"] = weight));
+}
+
+//' @name similarityMH_cross
+//' @title MinHash similarity of every sequence of x against every sequence of y
+//' @description Non-breaking addition: the length(x) by length(y) matrix whose element (i, j) is the share of hash functions on which the
+//' signatures of x[i] and y[j] agree -- the block [seq_along(x), length(x) + seq_along(y)] of similarityMH(c(x, y), k, n_hash) under the
+//' same seeds.  No forced diagonal.
+//' @export
+// [[Rcpp::export]]
+NumericMatrix similarityMH_cross(CharacterVector x, CharacterVector y, int k = 4, int n_hash = 50) {
+  const Packed px(x), py(y);
+  const int64_t m = x.length(), n = y.length();
+  std::vector<uint32_t> seeds(n_hash > 0 ? n_hash : 1);
+  if (n_hash > 0) check(da_hash_family_seeds(hash_seed(), n_hash, seeds.data()));
+  if (m <= 0 || n <= 0 || k <= 0 || n_hash <= 0)   // always an error here: raised before the m * n allocation
+    check(da_similarity_mh_cross(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, k, n_hash, seeds.data(),
+                                 nullptr, 1));
+  NumericMatrix out(m, n);   // column-major: column_major = 1 fills it in place
+  check(da_similarity_mh_cross(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, k, n_hash, seeds.data(),
+                               REAL(out), 1));
+  set_dimnames_rect(out);
+  return out;
+}
+
+//' @name similarityNW_cross
+//' @title Needleman-Wunsch identity of every sequence of x against every sequence of y
+//' @description Non-breaking addition: element (i, j) is the identity of the alignment of x[i] (sequence1) with y[j] -- the block
+//' [seq_along(x), length(x) + seq_along(y)] of similarityNW(c(x, y), ...).
+//' @export
+// [[Rcpp::export]]
+NumericMatrix similarityNW_cross(CharacterVector x, CharacterVector y, std::string matrixName = "BLOSUM62", int gapOpen = 10,
+                                 int gapExt = 4) {
+  const Packed px(x), py(y);
+  const int64_t m = x.length(), n = y.length();
+  NumericMatrix out(m, n);
+  check(da_similarity_nw_cross(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, matrixName.c_str(), gapOpen,
+                               gapExt, (m > 0 && n > 0) ? REAL(out) : nullptr, 1));
+  set_dimnames_rect(out);
+  return out;
 }
