@@ -17,6 +17,7 @@ DA_ERR_EMPTY_INPUT, DA_ERR_BAD_K, DA_ERR_BAD_NHASH, DA_ERR_BAD_MATRIX = 1, 2, 3,
 DA_ERR_BAD_RESIDUE_SEQ1, DA_ERR_BAD_RESIDUE_SEQ2, DA_ERR_NOMEM, DA_ERR_NO_DEVICE = 5, 6, 7, 8
 DA_ERR_HIP, DA_ERR_UNSUPPORTED, DA_ERR_BAD_ARG = 9, 10, 11
 DA_OUT_F64, DA_OUT_COMPACT, DA_OUT_PACK32 = 0, 1, 2
+DA_TOPK_MAX = 1024   # da_dev_topk_rows: the candidates of a row are sorted in a fixed LDS buffer
 
 _vp, _i64, _i32, _u32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_uint32, C.c_size_t
 
@@ -35,6 +36,9 @@ SIGNATURES = {
     "da_similarity_mh": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "da_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32]),
     "da_similarity_nw_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i32]),
+    "da_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "da_similarity_nw_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp]),
+    "da_nw_code_ranks": (_i32, [_i32, _vp, _vp]),
     "da_similarity_mh_opts": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "da_similarity_nw_opts": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _vp]),
     "da_rccl_available": (_i32, []),
@@ -51,6 +55,8 @@ SIGNATURES = {
     "da_dev_mh_compare_rect": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_dev_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "da_mh_cross_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "da_dev_topk_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "da_dev_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "da_dev_nw_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_last_route": (_i32, [_vp, _vp, _vp, _vp]),
     "da_dev_similarity_mh": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),

@@ -1218,6 +1218,81 @@ int da_mh_cross_last_route(int64_t *m_out, int64_t *n_out, int64_t *unique_x_out
   return DA_OK;
 }
 
+// ---- two sets, top-k per row: the rectangle as uint16 codes in row blocks, the selection kernel on each block ------------------------------
+int da_dev_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
+                     uint16_t *d_key_out, int64_t ld_out, void *stream) {
+  if (rows < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (rows == 0) return DA_OK;
+  if (!d_keys || !d_idx || !d_key_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld < n) return fail(DA_ERR_BAD_ARG, "ld (%lld) < n (%lld)", (long long)ld, (long long)n);
+  if (rank_bits < 0 || rank_bits > 16) return fail(DA_ERR_BAD_ARG, "rank_bits must be 0 .. 16 (got %d)", rank_bits);
+  if (top >= 1 && top <= n && top <= DA_TOPK_MAX && ld_out < top) return fail(DA_ERR_BAD_ARG, "ld_out (%lld) < top (%d)", (long long)ld_out, top);
+  return launch_topk_rows(d_keys, rows, n, ld, d_rank, rank_bits, top, d_idx, ld_out, d_key_out, ld_out, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+// 1 <= top <= n (DA_ERR_BAD_ARG), top <= DA_TOPK_MAX (DA_ERR_UNSUPPORTED): what every top-k entry point says after its own validation
+int topk_check(int top, int64_t n) {
+  if (top < 1 || top > n) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = %lld)", top, (long long)n);
+  if (top > DA_TOPK_MAX)
+    return fail(DA_ERR_UNSUPPORTED, "top-k per row keeps its candidates in a fixed LDS buffer: top <= %d (got %d)", DA_TOPK_MAX, top);
+  return DA_OK;
+}
+int bits_of(int64_t max_value) {
+  int b = 1;
+  while (b < 16 && (max_value >> b) != 0) ++b;
+  return b;
+}
+// Rows [0, m) of a two-set rectangle with n columns, selected block by block: compute(b0, b1, d, ld) writes the uint16 codes of rows [b0, b1)
+// to the scratch block d (leading dimension ld: n rounded up to a multiple of 8, so that rows are read in 16-byte units), then
+// da_dev_topk_rows' kernel takes `top` of every row into d_idx / d_key.  The block is sized like rows_to_host's: by the column count alone.
+// Synchronises the stream (the scratch block goes back to the cache).
+int topk_blocks(int64_t m, int64_t n, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx, int64_t ld_idx, uint16_t *d_key,
+                int64_t ld_key, hipStream_t stream, const std::function<int(int64_t, int64_t, void *, int64_t)> &compute) {
+  const int64_t ld = (n + 7) / 8 * 8;
+  const int64_t blk = std::min(block_rows(ld, sizeof(uint16_t)), m);
+  DevBuf d;
+  int rc;
+  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint16_t))) != DA_OK) return rc;
+  for (int64_t b0 = 0; b0 < m; b0 += blk) {
+    const int64_t b1 = std::min(m, b0 + blk);
+    if ((rc = compute(b0, b1, d.p, ld)) != DA_OK) return rc;
+    if ((rc = launch_topk_rows(d.as<uint16_t>(), b1 - b0, n, ld, d_rank, rank_bits, top, d_idx + b0 * ld_idx, ld_idx, d_key + b0 * ld_key, ld_key,
+                               stream)) != DA_OK) return rc;
+  }
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  return DA_OK;
+}
+int mh_cross_topk(MhCrossOperand &c, int n_hash, int top, int32_t *d_idx, int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream) {
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  c.work.release(); c.sig.release();                     // before the scratch block is sized
+  return topk_blocks(c.m, c.n, nullptr, bits_of(n_hash), top, d_idx, ld_idx, d_key, ld_key, stream, [&](int64_t b0, int64_t b1, void *d, int64_t ld) {
+    return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, stream);
+  });
+}
+}  // namespace
+
+int da_dev_similarity_mh_cross_topk(const uint8_t *d_x_residues, const int64_t *d_x_offsets, int64_t m, const uint8_t *d_y_residues,
+                                    const int64_t *d_y_offsets, int64_t n, int k, int n_hash, const uint32_t *d_seeds, int top, int32_t *d_idx,
+                                    double *d_val, int64_t ld_out, void *stream_v) {
+  int rc;
+  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
+  if (!d_x_residues || !d_x_offsets || !d_y_residues || !d_y_offsets || !d_seeds || !d_idx || !d_val) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: the two-set calls take n_hash <= 65535 (got %d)", n_hash);
+  if (m > 0x7ffffff0LL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "two-set MinHash: too many sequences");
+  if ((rc = topk_check(top, n)) != DA_OK) return rc;
+  if (ld_out < top) return fail(DA_ERR_BAD_ARG, "ld_out (%lld) < top (%d)", (long long)ld_out, top);
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  MhCrossOperand c;
+  DevBuf key;
+  if ((rc = mh_cross_operand(d_x_residues, d_x_offsets, m, d_y_residues, d_y_offsets, n, k, n_hash, d_seeds, &c, stream)) != DA_OK) return rc;
+  if ((rc = key.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  if ((rc = mh_cross_topk(c, n_hash, top, d_idx, ld_out, key.as<uint16_t>(), top, stream)) != DA_OK) return rc;
+  if ((rc = launch_topk_values(key.as<uint16_t>(), top, m, top, n_hash, d_val, ld_out, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));              // the key block goes back to the cache after this
+  return DA_OK;
+}
+
 // ---- pieces of the duplicate-collapsing routes for callers that orchestrate the steps themselves (the one-process-per-GPU
 // sharded drivers in dynaalign_amd/sharding.py: every rank builds the same plan, computes ITS shard of the unique table,
 // all-gathers the shards -- 0.2x the bytes of the N x N shards at N = 100k -- and expands locally)
@@ -2234,16 +2309,24 @@ int da_nw_pairs(const uint8_t *residues, const int64_t *offsets, int64_t n, cons
 }
 
 // ---- two sets on the host boundary: x (m sequences) against y (n sequences) ------------------------------------------------------------------
+// what both two-set MinHash host calls check before a device is needed: x empty, y empty, k, n_hash, pointers, the 16-bit limit, the offsets
+static int mh_cross_host_validate(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                  int64_t n, int k, int n_hash, const uint32_t *seeds, const void *out, int64_t *x_total, int64_t *y_total) {
+  int rc;
+  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
+  if (!x_residues || !y_residues || !seeds || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the two-set calls take n_hash <= 65535 (got %d)", n_hash);
+  int64_t max_len;
+  if ((rc = check_offsets(x_offsets, m, x_total, &max_len)) != DA_OK || (rc = check_offsets(y_offsets, n, y_total, &max_len)) != DA_OK) return rc;
+  return DA_OK;
+}
 // similarityMH for two sets: out[i][j] = #{h : sig_x[i][h] == sig_y[j][h]} / n_hash, no forced diagonal.  column_major: out[i + j * m]
 // (R's NumericMatrix(m, n)) -- the similarity is symmetric, so that is the row-major result of y against x.
 int da_similarity_mh_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
                            int64_t n, int k, int n_hash, const uint32_t *seeds, double *out, int column_major) {
   int rc;
-  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
-  if (!x_residues || !y_residues || !seeds || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the two-set calls take n_hash <= 65535 (got %d)", n_hash);
-  int64_t x_total, y_total, max_len;
-  if ((rc = check_offsets(x_offsets, m, &x_total, &max_len)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &max_len)) != DA_OK) return rc;
+  int64_t x_total, y_total;
+  if ((rc = mh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, out, &x_total, &y_total)) != DA_OK) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
   DeviceInput dx, dy;
   if ((rc = dx.upload(x_residues, x_offsets, m, x_total, seeds, n_hash)) != DA_OK || (rc = dy.upload(y_residues, y_offsets, n, y_total, nullptr, 0)) != DA_OK)
@@ -2284,6 +2367,18 @@ static int nw_cross_validate(const uint8_t *xr, const int64_t *xo, int64_t m, co
   return DA_OK;
 }
 
+// the two sets as ONE encoded code buffer [x ; y] on the device (m + n sequences)
+static int nw_upload_joint(const uint8_t *xr, const int64_t *xo, int64_t m, int64_t x_total, const uint8_t *yr, const int64_t *yo, int64_t n,
+                           int64_t y_total, NwCodes *nw) {
+  std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
+  std::vector<int64_t> off((size_t)(m + n) + 1);
+  if (x_total) memcpy(res.data(), xr, (size_t)x_total);
+  if (y_total) memcpy(res.data() + x_total, yr, (size_t)y_total);
+  for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = xo[i];
+  for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + yo[j];
+  return nw->upload(res.data(), off.data(), m + n, x_total + y_total);
+}
+
 // similarityNW for two sets: out[i][j] = calc(x[i], y[j]) with x[i] as sequence1.  Both sets are encoded into ONE code buffer [x ; y]; the
 // device evaluates pair (p, q) of it as calc(seq[min(p, q)], seq[max(p, q)]), so rows of x against columns of y give the row-major result and
 // rows of y against columns of x the column-major one (R's NumericMatrix(m, n)) -- sequence1 is the x string either way.
@@ -2299,14 +2394,8 @@ int da_similarity_nw_cross(const uint8_t *x_residues, const int64_t *x_offsets, 
   if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
   const int64_t max_len = std::max(x_max, y_max), nt = m + n;
-  std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
-  std::vector<int64_t> off((size_t)nt + 1);
-  if (x_total) memcpy(res.data(), x_residues, (size_t)x_total);
-  if (y_total) memcpy(res.data() + x_total, y_residues, (size_t)y_total);
-  for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = x_offsets[i];
-  for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + y_offsets[j];
   NwCodes nw;
-  if ((rc = nw.upload(res.data(), off.data(), nt, x_total + y_total)) != DA_OK) return rc;
+  if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
   const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
   const int64_t r_base = column_major ? m : 0, c_base = column_major ? 0 : m;
   const bool compact = max_len <= 127 && !da::config().no_host_widen;
@@ -2319,6 +2408,98 @@ int da_similarity_nw_cross(const uint8_t *x_residues, const int64_t *x_offsets, 
                      compact ? DA_OUT_COMPACT : DA_OUT_F64, d, cols, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c_base,
                      c_base + cols);
   }, nullptr, nullptr, compact ? table.data() : nullptr);
+}
+
+
+// ---- two sets, top-k per row on the host boundary (the device part: topk_blocks) -------------------------------------------------------------
+// the selection's results to the host: idx as it is, val_out[i][t] = table[key[i][t]] -- the same table the dense calls widen with
+static int topk_to_host(const DevBuf &didx, const DevBuf &dkey, int64_t m, int top, const std::vector<double> &table, int32_t *idx_out,
+                        double *val_out) {
+  const size_t cnt = (size_t)m * (size_t)top;
+  DA_HIP_TRY(hipMemcpy(idx_out, didx.p, cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (!val_out) return DA_OK;
+  std::vector<uint16_t> key(cnt);
+  DA_HIP_TRY(hipMemcpy(key.data(), dkey.p, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  for (size_t e = 0; e < cnt; ++e) val_out[e] = table[key[e]];
+  return DA_OK;
+}
+
+int da_similarity_mh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                int64_t n, int k, int n_hash, const uint32_t *seeds, int top, int32_t *idx_out, double *val_out) {
+  int rc;
+  int64_t x_total, y_total;
+  if ((rc = mh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, idx_out, &x_total, &y_total)) != DA_OK) return rc;
+  if ((rc = topk_check(top, n)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  DeviceInput dx, dy;
+  if ((rc = dx.upload(x_residues, x_offsets, m, x_total, seeds, n_hash)) != DA_OK || (rc = dy.upload(y_residues, y_offsets, n, y_total, nullptr, 0)) != DA_OK)
+    return rc;
+  MhCrossOperand c;
+  DevBuf didx, dkey;
+  if ((rc = mh_cross_operand(dx.res.as<uint8_t>(), dx.off.as<int64_t>(), m, dy.res.as<uint8_t>(), dy.off.as<int64_t>(), n, k, n_hash,
+                             dx.seeds.as<uint32_t>(), &c, nullptr)) != DA_OK) return rc;
+  if ((rc = didx.alloc((size_t)m * (size_t)top * sizeof(int32_t))) != DA_OK || (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  if ((rc = mh_cross_topk(c, n_hash, top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr)) != DA_OK) return rc;
+  return topk_to_host(didx, dkey, m, top, mh_code_values(n_hash), idx_out, val_out);
+}
+
+// rank_out[code] = dense rank of the double value of an NW code among the codes sequences up to max_len residues can produce (dynaalign.h)
+int da_nw_code_ranks(int max_len, uint16_t *rank_out, int *distinct_out) {
+  if (!rank_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (max_len < 1 || max_len > 127) return fail(DA_ERR_BAD_ARG, "max_len must be in 1 .. 127 (got %d)", max_len);
+  std::vector<std::pair<double, int>> v;
+  for (int ln = 1; ln <= 2 * max_len; ++ln)
+    for (int mt = 0; mt <= std::min(ln, max_len); ++mt) v.emplace_back((double)mt / (double)ln, (mt << 8) | ln);   // the divide of nw_code_values
+  std::sort(v.begin(), v.end());
+  memset(rank_out, 0, 65536 * sizeof(uint16_t));
+  int rank = -1;
+  double prev = -1.0;
+  for (const auto &e : v) {
+    if (e.first != prev) { ++rank; prev = e.first; }
+    rank_out[e.second] = (uint16_t)rank;
+  }
+  if (distinct_out) *distinct_out = rank + 1;
+  return DA_OK;
+}
+
+int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                int64_t n, const char *matrix_name, int gap_open, int gap_ext, int top, int32_t *idx_out, double *val_out) {
+  const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (m <= 0) return DA_OK;                              // no rows: nothing to write
+  if (n <= 0) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = 0)", top);
+  if (!x_residues || !y_residues || !idx_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t x_total, y_total, x_max, y_max;
+  int rc;
+  if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
+  if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
+  if ((rc = topk_check(top, n)) != DA_OK) return rc;
+  for (int64_t i = 0; i < m + n; ++i) {
+    const int64_t *o = i < m ? x_offsets + i : y_offsets + (i - m);
+    if (o[1] == o[0])
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in an order",
+                  (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y");
+  }
+  const int64_t max_len = std::max(x_max, y_max);
+  if (max_len > 127) return fail(DA_ERR_UNSUPPORTED, "the NW top-k works on uint16 codes: sequences up to 127 residues");
+  if ((rc = require_device()) != DA_OK) return rc;
+  NwCodes nw;
+  if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
+  // equal values tie whatever their codes (2/4 and 3/6): the selection orders by the dense rank of a code's double value
+  std::vector<uint16_t> ranks(65536);
+  int distinct = 0;
+  if ((rc = da_nw_code_ranks((int)max_len, ranks.data(), &distinct)) != DA_OK) return rc;
+  DevBuf drank, didx, dkey;
+  if ((rc = drank.alloc(65536 * sizeof(uint16_t))) != DA_OK || (rc = didx.alloc((size_t)m * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(drank.p, ranks.data(), 65536 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  rc = topk_blocks(m, n, drank.as<uint16_t>(), bits_of(distinct - 1), top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) {   // rows of x against columns of y: x[i] is sequence1
+                     return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, false,
+                                      DA_OUT_COMPACT, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
+                   });
+  if (rc != DA_OK) return rc;
+  return topk_to_host(didx, dkey, m, top, nw_code_values(65536, 0.0), idx_out, val_out);
 }
 
 

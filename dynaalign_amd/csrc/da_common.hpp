@@ -275,6 +275,12 @@ int launch_gather_columns(const uint16_t *d_D, int64_t ld_d, const int32_t *d_ui
 size_t edges_to_csr_workspace_bytes(int64_t m, int64_t n);
 int launch_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_v, int64_t m, int64_t n, void *d_work, size_t work_bytes,
                         int64_t *d_ptr, int32_t *d_adj, uint16_t *d_codes, uint16_t *d_loops, hipStream_t stream);
+// topk_kernels.hip: per-row exact top-k of uint16 keys by (rank descending, column ascending) (da_dev_topk_rows); index and key rows have
+// their own leading dimensions.  ... and the selected MinHash counts as doubles: d_val[r * ld_val + t] = d_key[r * ld_key + t] / n_hash
+constexpr int DA_TOPK_MAX = 1024;
+int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
+                     int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, hipStream_t stream);
+int launch_topk_values(const uint16_t *d_key, int64_t ld_key, int64_t rows, int top, int n_hash, double *d_val, int64_t ld_val, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

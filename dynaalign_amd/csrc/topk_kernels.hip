@@ -1,0 +1,236 @@
+// topk_kernels.hip -- the step after the two-set rectangle for a caller that keeps, per query, only its few most similar library entries:
+// exact top-k per row of the uint16 count / code block the rectangle compare (da_dev_mh_compare_rect, da_dev_nw_rect) wrote, so that
+// m x top numbers leave the device instead of the m x n matrix.
+//
+// Order: (rank descending, column ascending), rank = d_rank[key] or the key itself -- numpy's argsort(-rank, kind = "stable")[:top].  The
+// rank table exists because equal VALUES must tie where their codes differ (NW 2/4 and 3/6, da_nw_code_ranks).
+//
+// One workgroup per row; the row is never sorted:
+//   1. radix select on the rank, two 8-bit digits (the top 8 of rank_bits, then the rest): a 256-bin LDS histogram each, read from the top
+//      by one wave -> T, the rank of the top-th element, and `above`, the number of elements above T;
+//   2. ordered compaction: every element above T, and the first top - above elements equal to T in column order -- a workgroup prefix scan
+//      per chunk of the row, so the choice among equals does not depend on scheduling;
+//   3. the <= top candidates, as 64-bit words rank : ~column : key, sorted in LDS (bitonic) and stored.
+// The row is read three times (the second and third time from L2 / MALL); rank 0 -- by far the commonest: unrelated peptides share no
+// k-mer -- is counted in a register, not with 64 lanes on one LDS word (k_upper_histogram does the same).
+#include "da_common.hpp"
+
+namespace da {
+namespace {
+
+constexpr int TK_PER = 8;                     // keys per thread per chunk: one 16-byte load
+
+// lanes below `lane` summed: inclusive wave scan by shuffles
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// ranks (r) and keys (k) of the row's columns [j0, j0 + 8); returns how many of them exist (columns < n)
+__device__ __forceinline__ int load8(const uint16_t *__restrict__ row, int64_t j0, int64_t n, bool vec, const uint16_t *__restrict__ rank,
+                                     uint32_t r[TK_PER], uint32_t k[TK_PER]) {
+  int nv;
+  if (vec && j0 + TK_PER <= n) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) k[e] = (w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
+    nv = TK_PER;
+  } else {
+    nv = j0 >= n ? 0 : (n - j0 < TK_PER ? (int)(n - j0) : TK_PER);
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) k[e] = e < nv ? (uint32_t)row[j0 + e] : 0u;
+  }
+#pragma unroll
+  for (int e = 0; e < TK_PER; ++e) r[e] = (rank && e < nv) ? (uint32_t)rank[k[e]] : k[e];
+  return nv;
+}
+
+// hist[0 .. 256) read from the top by wave 0: the bin B holding the want-th largest element (1-based) and the count in the bins above B
+__device__ __forceinline__ void pick_bin(const unsigned int *hist, uint32_t want, unsigned int *out_bin, unsigned int *out_above) {
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
+  uint32_t c[4], s = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { c[q] = hist[255 - 4 * lane - q]; s += c[q]; }
+  const uint32_t incl = wave_incl_scan(s);
+  uint32_t acc = incl - s;
+  if (acc < want && want <= incl) {            // exactly one lane when the histogram holds >= want elements
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (acc < want && want <= acc + c[q]) { *out_bin = (unsigned)(255 - 4 * lane - q); *out_above = acc; }
+      acc += c[q];
+    }
+  }
+}
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restrict__ keys, int64_t n, int64_t ld,
+                                                       const uint16_t *__restrict__ rank, int shift, int top, int32_t *__restrict__ idx,
+                                                       int64_t ld_idx, uint16_t *__restrict__ key_out, int64_t ld_key) {
+  constexpr int WAVES = THREADS / 64;
+  constexpr int CHUNK = THREADS * TK_PER;
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned long long cand[DA_TOPK_MAX];
+  __shared__ unsigned int wtot[2][WAVES];
+  __shared__ unsigned int sel[4];             // bin, above (high digit), bin, above (low digit)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint16_t *row = keys + (int64_t)blockIdx.x * ld;
+  const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+  const uint32_t lo_mask = (1u << shift) - 1u;
+  uint32_t r[TK_PER], k[TK_PER];
+
+  // ---- 1a. the high digit
+  for (int b = tid; b < 256; b += THREADS) hist[b] = 0;
+  if (tid < 4) sel[tid] = 0;
+  __syncthreads();
+  uint32_t zeros = 0;
+  for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
+    const int nv = load8(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) {
+      if (e >= nv) continue;
+      if (r[e] == 0) ++zeros;
+      else { const uint32_t h = r[e] >> shift; atomicAdd(&hist[h < 255u ? h : 255u], 1u); }
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) zeros += __shfl_down(zeros, o);
+  if (lane == 0 && zeros) atomicAdd(&hist[0], zeros);
+  __syncthreads();
+  pick_bin(hist, (uint32_t)top, &sel[0], &sel[1]);
+  __syncthreads();
+  const uint32_t B = sel[0], above_hi = sel[1];
+  uint32_t T = B, above = above_hi;
+  // ---- 1b. the low digit among the elements of bin B
+  if (shift > 0) {                             // block-uniform
+    for (int b = tid; b < 256; b += THREADS) hist[b] = 0;
+    __syncthreads();
+    zeros = 0;
+    for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
+      const int nv = load8(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
+#pragma unroll
+      for (int e = 0; e < TK_PER; ++e) {
+        if (e >= nv) continue;
+        if (r[e] == 0) { if (B == 0) ++zeros; }
+        else if ((r[e] >> shift) == B) atomicAdd(&hist[r[e] & lo_mask], 1u);
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) zeros += __shfl_down(zeros, o);
+    if (lane == 0 && zeros) atomicAdd(&hist[0], zeros);
+    __syncthreads();
+    pick_bin(hist, (uint32_t)top - above_hi, &sel[2], &sel[3]);
+    __syncthreads();
+    T = (B << shift) | sel[2];
+    above = above_hi + sel[3];
+  }
+  const uint32_t need_eq = (uint32_t)top - above;       // >= 1: the top-th element itself has rank T
+
+  // ---- 2. ordered compaction.  Per chunk one scan of (elements above T) | (elements equal to T) << 16: <= 2048 each, no carry between them
+  uint32_t gt_run = 0, eq_run = 0;
+  int buf = 0;
+  for (int64_t c0 = 0; c0 < n; c0 += CHUNK, buf ^= 1) {
+    const int64_t j0 = c0 + (int64_t)tid * TK_PER;
+    const int nv = load8(row, j0, n, vec, rank, r, k);
+    uint32_t mine = 0;
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e)
+      if (e < nv) mine += r[e] > T ? 1u : (r[e] == T ? 0x10000u : 0u);
+    const uint32_t incl = wave_incl_scan(mine);
+    if (lane == 63) wtot[buf][wave] = incl;
+    __syncthreads();                           // the other buffer is written next time: one barrier per chunk
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const uint32_t t = wtot[buf][w];
+      if (w < wave) before += t;
+      total += t;
+    }
+    uint32_t pre = before + incl - mine;
+    uint32_t gt_at = gt_run + (pre & 0xFFFFu), eq_at = eq_run + (pre >> 16);
+    if (mine) {
+#pragma unroll
+      for (int e = 0; e < TK_PER; ++e) {
+        if (e >= nv) continue;
+        const unsigned long long word = ((unsigned long long)r[e] << 48) | ((unsigned long long)(~(uint32_t)(j0 + e)) << 16) | k[e];
+        if (r[e] > T) {
+          if (gt_at < above && gt_at < (uint32_t)DA_TOPK_MAX) cand[gt_at] = word;
+          ++gt_at;
+        } else if (r[e] == T) {
+          if (eq_at < need_eq && above + eq_at < (uint32_t)DA_TOPK_MAX) cand[above + eq_at] = word;
+          ++eq_at;
+        }
+      }
+    }
+    gt_run += total & 0xFFFFu;
+    eq_run += total >> 16;
+  }
+
+  // ---- 3. sort the candidates: descending words = rank descending, then ~column descending = column ascending
+  int P = 1;
+  while (P < top) P <<= 1;
+  __syncthreads();
+  for (int s = top + tid; s < P; s += THREADS) cand[s] = 0;     // below every candidate (~column is never 0)
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < (P >> 1); t += THREADS) {
+        const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
+        const bool desc = (i & size) == 0;
+        const unsigned long long a = cand[i], b = cand[j];
+        if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
+      }
+      __syncthreads();
+    }
+  for (int t = tid; t < top; t += THREADS) {
+    const unsigned long long w = cand[t];
+    idx[(int64_t)blockIdx.x * ld_idx + t] = (int32_t)(~(uint32_t)(w >> 16));
+    key_out[(int64_t)blockIdx.x * ld_key + t] = (uint16_t)(w & 0xFFFFu);
+  }
+}
+
+// the selected MinHash counts as similarities: the reference's divide (src/minHash.cpp:174)
+__global__ __launch_bounds__(256) void k_topk_values(const uint16_t *__restrict__ key, int64_t ld_key, int64_t rows, int top, int n_hash,
+                                                     double *__restrict__ val, int64_t ld_val) {
+  const int64_t count = rows * top, stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const int64_t rr = i / top, t = i - rr * top;
+    val[rr * ld_val + t] = (double)key[rr * ld_key + t] / (double)n_hash;
+  }
+}
+
+}  // namespace
+
+int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
+                     int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, hipStream_t stream) {
+  if (rows <= 0) return DA_OK;
+  if (top < 1 || top > n) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = %lld)", top, (long long)n);
+  if (top > DA_TOPK_MAX)
+    return fail(DA_ERR_UNSUPPORTED, "top-k per row keeps its candidates in a fixed LDS buffer: top <= %d (got %d)", DA_TOPK_MAX, top);
+  if (rows > 0x7fffffffLL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
+  if (rank_bits <= 0 || rank_bits > 16) rank_bits = 16;
+  const int shift = rank_bits > 8 ? rank_bits - 8 : 0;
+  // a row of up to 1024 keys is two chunks of one wave: four times as many rows in flight per CU as with 256 threads
+  if (n <= 1024)
+    hipLaunchKernelGGL(k_topk_rows<64>, dim3((unsigned)rows), dim3(64), 0, stream, d_keys, n, ld, d_rank, shift, top, d_idx, ld_idx, d_key_out, ld_key);
+  else
+    hipLaunchKernelGGL(k_topk_rows<256>, dim3((unsigned)rows), dim3(256), 0, stream, d_keys, n, ld, d_rank, shift, top, d_idx, ld_idx, d_key_out,
+                       ld_key);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+int launch_topk_values(const uint16_t *d_key, int64_t ld_key, int64_t rows, int top, int n_hash, double *d_val, int64_t ld_val, hipStream_t stream) {
+  if (rows <= 0 || top <= 0) return DA_OK;
+  int64_t blocks = ceil_div(rows * top, 256);
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  hipLaunchKernelGGL(k_topk_values, dim3((unsigned)blocks), dim3(256), 0, stream, d_key, ld_key, rows, top, n_hash, d_val, ld_val);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+}  // namespace da

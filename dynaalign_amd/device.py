@@ -348,6 +348,46 @@ def similarity_mh_cross(dx, dy, k, n_hash, seeds, out=None):
     return out
 
 
+def topk_rows(keys, top, rank=None, rank_bits=0):
+    """Exact top-k per row of a block of uint16 keys (an int16 tensor of shape (rows, n), any row stride and base address), by
+    (rank descending, column ascending): rank = rank[key] (a 65536-entry int16 tensor of uint16 ranks, all below 2 ** rank_bits) or
+    the key itself (da_dev_topk_rows).  Returns (idx int32 (rows, top), key int16 (rows, top)): numpy's
+    argsort(-rank_of_row, kind="stable")[:top] and the keys found there."""
+    lib = _capi.load()
+    _require_cuda(keys, "keys")
+    assert keys.dim() == 2 and keys.dtype == torch.int16 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
+    rows, n = int(keys.shape[0]), int(keys.shape[1])
+    ld = int(keys.stride(0)) if rows > 1 else max(n, 1)
+    if rank is not None:
+        _require_cuda(rank, "rank table")
+        assert rank.dtype == torch.int16 and rank.numel() == 65536 and rank.is_contiguous()
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    idx = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
+    key = torch.empty((max(rows, 1), t), dtype=torch.int16, device=keys.device)
+    _call(lib.da_dev_topk_rows, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(rank_bits), int(top),
+                                     idx.data_ptr(), key.data_ptr(), t, _stream())
+    return idx[:rows], key[:rows]
+
+
+def similarity_mh_cross_topk(dx, dy, k, n_hash, seeds, top):
+    """similarityMH_cross followed by the per-row top-k selection on two device-resident sets, one C call
+    (da_dev_similarity_mh_cross_topk): (idx int32 (m, top), val float64 (m, top)).  Row i lists the `top` columns of
+    row i of similarity_mh_cross(dx, dy, ...) by value descending, then column ascending; the m x n matrix never exists --
+    row blocks of uint16 counts are selected from as they are computed.  top is NOT clamped here (1 <= top <= n)."""
+    lib = _capi.load()
+    if not torch.is_tensor(seeds):
+        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(dx.residues.device)
+    _require_cuda(dx.residues, "residues of x")
+    _require_cuda(dy.residues, "residues of y")
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    idx = torch.empty((max(dx.n, 1), t), dtype=torch.int32, device=dx.residues.device)
+    val = torch.empty((max(dx.n, 1), t), dtype=torch.float64, device=dx.residues.device)
+    _call(lib.da_dev_similarity_mh_cross_topk, dx.residues.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.residues.data_ptr(),
+                                                    dy.offsets.data_ptr(), dy.n, int(k), int(n_hash), seeds.data_ptr(), int(top),
+                                                    idx.data_ptr(), val.data_ptr(), t, _stream())
+    return idx[:dx.n], val[:dx.n]
+
+
 def mh_cross_last_route():
     """what this thread's last similarity_mh_cross call did: dict(m, n, unique_x, unique_y, dedup, plane_bits, plan_ms, codes_ms,
     k2_ms, lists_ms, expand_ms)"""

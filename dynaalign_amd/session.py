@@ -9,6 +9,7 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     S = s.similarity(idx)                                           # == similarityMH(sequences[idx], 4, 500, seed=12345)
     thr, i, j, w = s.edges(idx, thresh_p=0.8)                       # == similarityMH_edges(sequences[idx], ...)
     R = s.cross(new, idx)                                           # == similarityMH_cross(new, sequences[idx], 4, 500, seed=12345)
+    i, v = s.cross_topk(new, 10, idx)                               # == similarityMH_cross_topk(new, sequences[idx], 4, 500, 10, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
 seeds per call, src/minHash.cpp:73,137); the contract -- MinHash estimates under one hash family -- holds.
@@ -58,11 +59,11 @@ class MinHashSession:
         out = device.mh_compare(planes, m, self.n_hash)
         return SimilarityMatrix(out.cpu().numpy())
 
-    def cross(self, sequences, idx=None):
-        """New sequences against the resident set (or its subset idx): the (m, len(idx)) float64 matrix
-        similarityMH_cross(sequences, resident[idx], k, n_hash, seed=self.seed).  K1 on the new strings under the session's
-        seeds, ONE dictionary over [new ; filler ; resident[idx]] -- the new rows padded to a multiple of 128 with rows that
-        repeat real ones, so the rectangle's origins are tile-aligned -- then the rectangle compare."""
+    def _joint_operand(self, sequences, idx):
+        """The compare operand of new sequences against the resident set (or its subset idx): K1 on the new strings under the session's
+        seeds, ONE dictionary over [new ; filler ; resident[idx]] -- the new rows padded to a multiple of 128 with rows that repeat real
+        ones, so the rectangle's origins are tile-aligned.  -> (planes, m, m_pad, n): the rectangle is rows [0, m) x columns
+        [m_pad, m_pad + n) of the (m_pad + n)-row problem."""
         res, off = pack_sequences(sequences)
         m = len(off) - 1
         if m == 0:
@@ -78,9 +79,37 @@ class MinHashSession:
         if m_pad > m:
             joint[m:m_pad] = sig_new[torch.arange(m_pad - m, device=self.sig.device) % m]
         joint[m_pad:] = sig_res[:n]
-        planes = device.mh_planes(joint, m_pad + n, self.n_hash)
+        return device.mh_planes(joint, m_pad + n, self.n_hash), m, m_pad, n
+
+    def cross(self, sequences, idx=None):
+        """New sequences against the resident set (or its subset idx): the (m, len(idx)) float64 matrix
+        similarityMH_cross(sequences, resident[idx], k, n_hash, seed=self.seed): the joint operand (_joint_operand), then the
+        rectangle compare."""
+        planes, m, m_pad, n = self._joint_operand(sequences, idx)
         out = device.mh_compare_rect(planes, m_pad + n, self.n_hash, 0, m, m_pad, m_pad + n)
         return SimilarityMatrix(out.cpu().numpy()[:m, :n])
+
+    def cross_topk(self, sequences, top=10, idx=None, block_bytes=1 << 30):
+        """For every new sequence its `top` most similar resident sequences (or members of the subset idx), without the m x n matrix:
+        (index, value) = similarityMH_cross_topk(sequences, resident[idx], k, n_hash, top, seed=self.seed) -- (m, top) int32 positions
+        in idx (in the resident set when idx is None), by value descending then position ascending, and the (m, top) float64 values.
+        top is clamped to the number of columns.  The rectangle is compared into uint16 counts in row blocks of block_bytes and each
+        block goes through device.topk_rows."""
+        planes, m, m_pad, n = self._joint_operand(sequences, idx)
+        top = min(int(top), n)
+        ld = -(-n // 8) * 8
+        blk = min(max(block_bytes // (2 * ld) // 128 * 128, 128), m)
+        buf = torch.empty((blk, ld), dtype=torch.int16, device=self.sig.device)
+        out_i, out_k = [], []
+        for b0 in range(0, m, blk):
+            b1 = min(m, b0 + blk)
+            cnt = device.mh_compare_rect(planes, m_pad + n, self.n_hash, b0, b1, m_pad, m_pad + n, _capi.DA_OUT_COMPACT, out=buf[:b1 - b0, :n])
+            i, key = device.topk_rows(cnt, top, rank_bits=max(self.n_hash.bit_length(), 1))
+            out_i.append(i)
+            out_k.append(key)
+        keys = torch.cat(out_k).contiguous()
+        val = device.widen(keys, False, self.n_hash)                     # count / n_hash, the library's divide
+        return torch.cat(out_i).cpu().numpy(), val.cpu().numpy()
 
     def edges_csr(self, idx=None, thresh_p=0.8):
         """The thresholded graph of the subset as the canonical symmetric CSR clusterbreak.louvain_csr takes -- sorted ON THE DEVICE

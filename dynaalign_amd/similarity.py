@@ -8,6 +8,11 @@ and their two-set forms (no counterpart in the reference: a second set against t
     similarityMH_cross(x, y, k=4, n_hash=50)
     similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4)
 
+and the top-k forms of those (per row of x the ``top`` most similar y, never the m x n matrix)
+
+    similarityMH_cross_topk(x, y, k=4, n_hash=50, top=10)
+    similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10)
+
 Same names, argument order, defaults and error texts as the reference; the
 bodies marshal to the C ABI (include/dynaalign.h) exactly as the Rcpp glue in
 r_glue/ does.  Results are dense symmetric n x n float64 matrices with
@@ -168,6 +173,25 @@ def similarityMH_cross(x, y, k=4, n_hash=50, *, seed=None):
     return SimilarityMatrix(out[:m, :n])
 
 
+def similarityMH_cross_topk(x, y, k=4, n_hash=50, top=10, *, seed=None):
+    """For every sequence of ``x`` its ``top`` most similar sequences of ``y`` under similarityMH_cross, without the (m, n) matrix:
+    returns ``(idx, val)``, (m, top) int32 0-based positions in ``y`` and the (m, top) float64 similarities, with
+    ``idx == np.argsort(-R, axis=1, kind="stable")[:, :top]`` and ``val[i, t]`` bit for bit ``R[i, idx[i, t]]`` for
+    R = similarityMH_cross(x, y, k, n_hash, seed=seed): value descending, position ascending among equals; columns of
+    similarity 0 fill a row with fewer than ``top`` positive ones.  ``top`` is clamped to ``len(y)`` (the C ABI does not clamp) and may be
+    at most 1024.  Errors as similarityMH_cross."""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    n = len(yo) - 1
+    top = _as_int(top, "top")
+    t = min(top, n) if n > 0 else top
+    idx = np.empty((max(m, 1), max(t, 1)), np.int32)
+    val = np.empty((max(m, 1), max(t, 1)), np.float64)
+    _capi.check(lib.da_similarity_mh_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash,
+                                                seeds.ctypes.data, t, idx.ctypes.data, val.ctypes.data))
+    return idx[:m], val[:m]
+
+
 def minhash_signatures(sequences, k=4, n_hash=50, *, seed=None):
     """The (n, n_hash) uint32 signature matrix (reference src/minHash.cpp:140-157)."""
     lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
@@ -226,6 +250,35 @@ def similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
     _capi.check(lib.da_similarity_nw_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
                                            _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), out.ctypes.data, 0))
     return SimilarityMatrix(out[:m, :n])
+
+
+def similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10):
+    """For every sequence of ``x`` its ``top`` most similar sequences of ``y`` under similarityNW_cross (x[i] is sequence1), without
+    the (m, n) matrix: ``(idx, val)`` as similarityMH_cross_topk.  Equal similarities tie whatever their (matches, length): 2/4 and 3/6
+    are both 0.5 and are listed by position.  Every sequence has 1 .. 127 residues (an empty one is refused: its similarities are NaN /
+    0.0).  An empty ``x`` gives (0, top) arrays; ``top`` is clamped to ``len(y)``; an empty ``y`` is an error."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    top = _as_int(top, "top")
+    t = min(top, n) if n > 0 else top
+    idx = np.empty((max(m, 1), max(t, 1)), np.int32)
+    val = np.empty((max(m, 1), max(t, 1)), np.float64)
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    _capi.check(lib.da_similarity_nw_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
+                                                _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t, idx.ctypes.data, val.ctypes.data))
+    return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
+
+
+def nw_code_ranks(max_len=127):
+    """(ranks uint16[65536], distinct): the dense value rank of every NW code (matches << 8 | length) sequences up to max_len residues
+    can produce -- what similarityNW_cross_topk selects on (da_nw_code_ranks).  Needs no device."""
+    import ctypes
+    out = np.zeros(65536, np.uint16)
+    d = ctypes.c_int(0)
+    _capi.check(_capi.load().da_nw_code_ranks(int(max_len), out.ctypes.data, ctypes.addressof(d)))
+    return out, d.value
 
 
 def nw_pairs(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, row_begin=0, row_end=None):

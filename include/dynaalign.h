@@ -46,6 +46,7 @@ extern "C" {
 
 /* (round 4 added entry points only -- da_config_reload, da_debug_comm_cache_state, da_mh_last_route_split: the version stays)
  * (the two-set entry points -- da_similarity_*_cross, da_dev_*_rect, da_dev_similarity_mh_cross, da_mh_cross_last_route -- were added likewise)
+ * (the two-set top-k entry points -- da_similarity_*_cross_topk, da_dev_similarity_mh_cross_topk, da_dev_topk_rows, da_nw_code_ranks -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -197,6 +198,33 @@ int da_similarity_nw_cross(const uint8_t *x_residues, const int64_t *x_offsets, 
                            const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
                            const char *matrix_name, int gap_open, int gap_ext, double *out, int column_major);
 
+/* ---- two sets, top-k per row: the `top` most similar y for every x, without the m x n matrix ----
+ * R is the matrix da_similarity_mh_cross / da_similarity_nw_cross return.  Row i of the result lists `top` columns j of row i of R, ordered
+ * by R[i][j] descending and, among equal values, by j ascending: numpy's argsort(-R, axis = 1, kind = "stable")[:, :top].  Columns of
+ * similarity 0 are ordinary entries (they fill a row with fewer than `top` positive columns); no forced diagonal.
+ *   idx_out : [m][top] int32, 0-based columns;  val_out : [m][top] float64 or NULL, val[i][t] bit for bit R[i][idx[i][t]]
+ *             (MinHash (double)count / (double)n_hash, NW (double)matches / (double)length).
+ * Equal VALUES tie even when their integer codes differ (NW 2/4 and 3/6): the device selects on the dense rank of a code's double value
+ * (da_nw_code_ranks; the identity on MinHash counts), never on the raw code.
+ * Validation, before any device is needed: everything da_similarity_*_cross checks, in its order and with its texts; then top < 1 or
+ * top > n -> DA_ERR_BAD_ARG, top > 1024 -> DA_ERR_UNSUPPORTED (da_dev_topk_rows).  NW: m == 0 returns DA_OK; n == 0 with m > 0 is
+ * DA_ERR_BAD_ARG (no top satisfies 1 <= top <= 0); like da_similarity_nw_edges every sequence on both sides has 1 .. 127 residues
+ * (DA_ERR_UNSUPPORTED: the uint16 code holds an 8-bit alignment length, and an empty sequence's similarities are NaN / 0.0 -- a NaN has
+ * no place in an order).  Only m x top numbers leave the device: the rectangle is computed as uint16 codes in row blocks of
+ * DYNAALIGN_BLOCK_BYTES (sized by the column count alone) and selected from there.  Single device, the direct route only. */
+int da_similarity_mh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                                int k, int n_hash, const uint32_t *seeds, int top, int32_t *idx_out, double *val_out);
+int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                                const char *matrix_name, int gap_open, int gap_ext, int top, int32_t *idx_out, double *val_out);
+
+/* The value-rank table of the NW codes (matches << 8 | length) of sequences up to max_len (1 .. 127) residues: rank_out[code], 65536
+ * entries, is the dense rank (0 = smallest) of (double)matches / (double)length among the codes with 1 <= length <= 2 * max_len and
+ * matches <= min(length, max_len) -- equal doubles get equal ranks, a larger double a larger rank.  Codes outside that set cannot occur
+ * and get rank 0.  *distinct_out (may be NULL): the number of ranks.  Host only; needs no device. */
+int da_nw_code_ranks(int max_len, uint16_t *rank_out, int *distinct_out);
+
 /* ---- device-pointer entry points (bench / multi-GPU sharding) ------------ */
 
 /* Leading dimension (in uint32 elements) the library uses for signature
@@ -278,6 +306,28 @@ int da_dev_similarity_mh_cross(const uint8_t *d_x_residues, const int64_t *d_x_o
                                int k, int n_hash, const uint32_t *d_seeds, double *d_out, int64_t ld, void *stream);
 int da_mh_cross_last_route(int64_t *m_out, int64_t *n_out, int64_t *unique_x_out, int64_t *unique_y_out, int *route_out,
                            int *plane_bits_out, double *ms5_out);
+
+/* Exact top-k selection per row of a block of uint16 keys: d_keys holds `rows` rows of ld >= n keys.  A key's order is its rank,
+ * d_rank[key] (a 65536-entry table) or the key itself when d_rank is NULL; every rank must be < 2^rank_bits (rank_bits 1 .. 16, 0 = 16:
+ * it only places the two 8-bit digits of the radix select; ranks beyond it give a wrong selection, never an access out of bounds).
+ * For every row: d_idx[row * ld_out + t], d_key_out[row * ld_out + t], t < top, are the column and the KEY of the t-th element in
+ * (rank descending, column ascending) order -- argsort(-rank[row], kind = "stable")[:top].  1 <= top <= n; top > 1024 is
+ * DA_ERR_UNSUPPORTED (the candidates of a row are sorted in a fixed LDS buffer); ld_out >= top.  One workgroup per row, the row is never
+ * sorted: a two-level radix select finds the rank of the top-th element, an ordered compaction keeps what lies above it and the first
+ * columns equal to it, and only those <= top candidates are sorted.  Rows are read in 16-byte units where their address allows it,
+ * in 2-byte units otherwise: every ld and base address works.  Asynchronous on `stream`. */
+int da_dev_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top,
+                     int32_t *d_idx, uint16_t *d_key_out, int64_t ld_out, void *stream);
+
+/* similarityMH_cross followed by the per-row top-k selection (see da_similarity_mh_cross_topk) on two resident sets as ONE call:
+ * d_idx (int32) and d_val (float64) hold m rows of ld_out >= top elements.  The operand is da_dev_similarity_mh_cross's
+ * ([x ; filler ; y], same padding and 131 068-row rule); per row block of x, sized from DYNAALIGN_BLOCK_BYTES by the column count alone:
+ * the rectangle compare into uint16 counts, da_dev_topk_rows, the selected counts divided by n_hash.  Direct route only (no duplicate
+ * collapse, packed table, heavy / rare split or sparse route); n_hash <= 65535; one stream, which it synchronises. */
+int da_dev_similarity_mh_cross_topk(const uint8_t *d_x_residues, const int64_t *d_x_offsets, int64_t m,
+                                    const uint8_t *d_y_residues, const int64_t *d_y_offsets, int64_t n,
+                                    int k, int n_hash, const uint32_t *d_seeds, int top, int32_t *d_idx, double *d_val, int64_t ld_out,
+                                    void *stream);
 
 /* K1 + K1b + K2 as ONE call: similarityMH (src/minHash.cpp:119-188) from packed residues in HBM to the dense float64
  * n x n matrix in HBM (d_out, leading dimension ld >= n doubles; 16-byte aligned and even ld for the wide-store kernels).

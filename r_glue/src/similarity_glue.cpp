@@ -128,6 +128,31 @@ struct DeviceOpts {
   const da_opts *get() const { return set ? &opts : nullptr; }   // NULL = da_similarity_mh / _nw on the current device
 };
 
+// dim(v) <- c(rows, cols): an integer vector becomes R's integer matrix.  (A vector type without attr() -- the test-only Rcpp stand-in
+// this file is also compiled against -- takes the overload below and stays a plain column-major vector.)
+template <typename V>
+auto set_dim(V &v, int rows, int cols, int) -> decltype(v.attr("dim"), void()) {
+  IntegerVector d(2);
+  d[0] = rows;
+  d[1] = cols;
+  v.attr("dim") = d;
+}
+template <typename V>
+void set_dim(V &, int, int, long) {}
+
+// the C ABI's row-major [m][top] results as R's list(index = m x top integer matrix, 1-based; similarity = m x top numeric matrix)
+List topk_result(const std::vector<int32_t> &idx, const std::vector<double> &val, int64_t m, int top) {
+  IntegerVector index(m * top);
+  NumericMatrix similarity(m, top);
+  for (int64_t i = 0; i < m; ++i)
+    for (int t = 0; t < top; ++t) {
+      index[i + (int64_t)t * m] = idx[(size_t)(i * top + t)] + 1;   // column-major, R is 1-based
+      REAL(similarity)[i + (int64_t)t * m] = val[(size_t)(i * top + t)];
+    }
+  set_dim(index, (int)m, top, 0);
+  return List::create(_["index"] = index, _["similarity"] = similarity);
+}
+
 struct EdgesHandle {   // da_edges_free on scope exit
   da_edges *h;
   explicit EdgesHandle(da_edges *p) : h(p) {}
@@ -270,4 +295,46 @@ NumericMatrix similarityNW_cross(CharacterVector x, CharacterVector y, std::stri
                                gapExt, (m > 0 && n > 0) ? REAL(out) : nullptr, 1));
   set_dimnames_rect(out);
   return out;
+}
+
+//' @name similarityMH_cross_topk
+//' @title For every sequence of x its top most similar sequences of y (MinHash), without the length(x) by length(y) matrix
+//' @description Non-breaking addition.  With R <- similarityMH_cross(x, y, k, n_hash) under the same seeds, row i of index is
+//' order(-R[i, ], seq_along(y))[1:top] -- similarity descending, position ascending among equals, zeros filling a row with fewer than top
+//' positive entries -- and similarity[i, t] is R[i, index[i, t]].  top is clamped to length(y) and may be at most 1024.
+//' @return list(index = integer matrix, similarity = numeric matrix), both length(x) by top
+//' @export
+// [[Rcpp::export]]
+List similarityMH_cross_topk(CharacterVector x, CharacterVector y, int k = 4, int n_hash = 50, int top = 10) {
+  const Packed px(x), py(y);
+  const int64_t m = x.length(), n = y.length();
+  std::vector<uint32_t> seeds(n_hash > 0 ? n_hash : 1);
+  if (n_hash > 0) check(da_hash_family_seeds(hash_seed(), n_hash, seeds.data()));
+  if (n > 0 && top > n) top = (int)n;
+  const size_t cnt = (size_t)(m > 0 ? m : 1) * (size_t)(top > 0 ? top : 1);
+  std::vector<int32_t> idx(cnt);
+  std::vector<double> val(cnt);
+  check(da_similarity_mh_cross_topk(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, k, n_hash, seeds.data(),
+                                    top, idx.data(), val.data()));
+  return topk_result(idx, val, m, top);
+}
+
+//' @name similarityNW_cross_topk
+//' @title For every sequence of x its top most similar sequences of y (Needleman-Wunsch identity, x[i] as sequence1)
+//' @description Non-breaking addition, as similarityMH_cross_topk on similarityNW_cross(x, y, ...).  Equal similarities tie whatever their
+//' (matches, length) -- 2/4 and 3/6 -- and are listed by position.  Sequences of 1 to 127 residues.
+//' @return list(index = integer matrix, similarity = numeric matrix), both length(x) by top
+//' @export
+// [[Rcpp::export]]
+List similarityNW_cross_topk(CharacterVector x, CharacterVector y, std::string matrixName = "BLOSUM62", int gapOpen = 10, int gapExt = 4,
+                             int top = 10) {
+  const Packed px(x), py(y);
+  const int64_t m = x.length(), n = y.length();
+  if (n > 0 && top > n) top = (int)n;
+  const size_t cnt = (size_t)(m > 0 ? m : 1) * (size_t)(top > 0 ? top : 1);
+  std::vector<int32_t> idx(cnt);
+  std::vector<double> val(cnt);
+  check(da_similarity_nw_cross_topk(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, matrixName.c_str(),
+                                    gapOpen, gapExt, top, idx.data(), val.data()));
+  return topk_result(idx, val, m, top > 0 ? top : 0);
 }
