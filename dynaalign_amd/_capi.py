@@ -57,6 +57,14 @@ SIGNATURES = {
     "da_mh_cross_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "da_dev_topk_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
     "da_dev_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "da_similarity_mh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _i32, _vp, _vp, _vp]),
+    "da_similarity_nw_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp]),
+    "da_dev_rect_histogram": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "da_dev_threshold_rows_workspace_bytes": (_sz, [_i64]),
+    "da_dev_threshold_rows_count": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "da_dev_threshold_rows_emit": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "da_dev_similarity_mh_cross_edges": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                                                _vp]),
     "da_dev_nw_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_last_route": (_i32, [_vp, _vp, _vp, _vp]),
     "da_dev_similarity_mh": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),

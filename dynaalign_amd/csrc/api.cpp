@@ -2503,6 +2503,240 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
 }
 
 
+// ---- two sets, threshold form: the entries of the rectangle that pass a threshold as a sorted edge list (rect_edges_kernels.hip) ---------
+static int rect_block_check(const void *a, const void *b, const void *c, int64_t rows, int64_t n, int64_t ld, int nbins) {
+  if (rows < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (!a || !b || !c) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld < n) return fail(DA_ERR_BAD_ARG, "ld (%lld) < n (%lld)", (long long)ld, (long long)n);
+  if (nbins < 1 || nbins > 65536) return fail(DA_ERR_BAD_ARG, "nbins must be in 1 .. 65536 (got %d)", nbins);
+  return DA_OK;
+}
+int da_dev_rect_histogram(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, int nbins, uint64_t *d_hist, void *stream) {
+  int rc;
+  if ((rc = rect_block_check(d_keys, d_hist, d_hist, rows, n, ld, nbins)) != DA_OK) return rc;
+  return launch_rect_histogram(d_keys, rows, n, ld, nbins, reinterpret_cast<unsigned long long *>(d_hist), static_cast<hipStream_t>(stream));
+}
+size_t da_dev_threshold_rows_workspace_bytes(int64_t rows) { return threshold_rows_workspace_bytes(rows); }
+int da_dev_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, int64_t *d_rowptr,
+                                void *d_work, size_t work_bytes, void *stream) {
+  int rc;
+  if ((rc = rect_block_check(d_keys, d_keep, d_rowptr, rows, n, ld, nbins)) != DA_OK) return rc;
+  if (!d_work) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_threshold_rows_count(d_keys, rows, n, ld, d_keep, nbins, d_rowptr, d_work, work_bytes, static_cast<hipStream_t>(stream));
+}
+int da_dev_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, const int64_t *d_rowptr,
+                               int32_t *d_j, uint16_t *d_key_out, int64_t capacity, void *stream) {
+  int rc;
+  if ((rc = rect_block_check(d_keys, d_keep, d_rowptr, rows, n, ld, nbins)) != DA_OK) return rc;
+  if (capacity < 0) return fail(DA_ERR_BAD_ARG, "negative capacity");
+  if (capacity > 0 && (!d_j || !d_key_out)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_threshold_rows_emit(d_keys, rows, n, ld, d_keep, nbins, d_rowptr, d_j, d_key_out, capacity, static_cast<hipStream_t>(stream));
+}
+
+// the threshold argument of the *_cross_edges entry points: a quantile level in [0, 1], or any non-NaN absolute threshold
+static int thresh_arg_check(double thresh, int thresh_is_quantile) {
+  if (thresh_is_quantile) {
+    if (!(thresh >= 0.0 && thresh <= 1.0)) return fail(DA_ERR_BAD_ARG, "thresh_p must be in [0, 1]");
+  } else if (thresh != thresh) {
+    return fail(DA_ERR_BAD_ARG, "the threshold must not be NaN");
+  }
+  return DA_OK;
+}
+
+// Rows [0, m) of a two-set rectangle with n columns, thresholded block by block (blocks as topk_blocks: compute(b0, b1, d, ld) writes the
+// uint16 codes of rows [b0, b1) to the scratch block d).  values[code] is the similarity a code stands for; a code is kept when its value is
+// positive and not below the threshold.  Quantile form: a first pass of compute + histogram over all blocks gives the threshold; a single
+// block is then kept, several blocks are computed again.  Per block, in order: the per-row counts and their scan, the 8-byte total read
+// back, then sink(b0, b1, d, ld, d_keep, d_rowptr_block, total, base) -- base = the kept entries of the blocks before -- emits where it
+// wants them.  Synchronises the stream.
+typedef std::function<int(int64_t, int64_t, void *, int64_t)> RectCompute;
+typedef std::function<int(int64_t, int64_t, const uint16_t *, int64_t, const uint8_t *, const int64_t *, int64_t, int64_t)> RectSink;
+static int threshold_blocks(int64_t m, int64_t n, const std::vector<double> &values, double thresh, bool is_quantile, hipStream_t stream,
+                            const RectCompute &compute, const RectSink &sink, double *threshold_out, int64_t *n_edges_out) {
+  const int nbins = (int)values.size();
+  const int64_t ld = (n + 7) / 8 * 8;
+  const int64_t blk = std::min(block_rows(ld, sizeof(uint16_t)), m);
+  const size_t wb = threshold_rows_workspace_bytes(blk);
+  DevBuf d, keep, rowptr, work, hist;
+  int rc;
+  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint16_t))) != DA_OK || (rc = keep.alloc((size_t)nbins)) != DA_OK ||
+      (rc = rowptr.alloc((size_t)(blk + 1) * 8)) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+  double thr = thresh;
+  bool have_block = false;
+  if (is_quantile) {
+    if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;
+    DA_HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)nbins * 8, stream));
+    for (int64_t b0 = 0; b0 < m; b0 += blk) {
+      const int64_t b1 = std::min(m, b0 + blk);
+      if ((rc = compute(b0, b1, d.p, ld)) != DA_OK ||
+          (rc = launch_rect_histogram(d.as<uint16_t>(), b1 - b0, n, ld, nbins, hist.as<unsigned long long>(), stream)) != DA_OK) return rc;
+    }
+    std::vector<uint64_t> h((size_t)nbins);
+    DA_HIP_TRY(hipMemcpyAsync(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+    // order statistics need the codes in ascending order of their VALUE (MH: already so; NW: ratios, equal values side by side)
+    std::vector<int> order((size_t)nbins);
+    for (int b = 0; b < nbins; ++b) order[(size_t)b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return values[(size_t)a] < values[(size_t)b]; });
+    std::vector<uint64_t> hs((size_t)nbins);
+    std::vector<double> vs((size_t)nbins);
+    for (int b = 0; b < nbins; ++b) { hs[(size_t)b] = h[(size_t)order[(size_t)b]]; vs[(size_t)b] = values[(size_t)order[(size_t)b]]; }
+    if ((rc = da_quantile_type7(hs.data(), vs.data(), nbins, thresh, &thr)) != DA_OK) return rc;
+    have_block = blk >= m;
+  }
+  std::vector<uint8_t> kp((size_t)nbins);
+  for (int b = 0; b < nbins; ++b) kp[(size_t)b] = (values[(size_t)b] > 0.0 && values[(size_t)b] >= thr) ? 1 : 0;
+  DA_HIP_TRY(hipMemcpyAsync(keep.p, kp.data(), (size_t)nbins, hipMemcpyHostToDevice, stream));
+  int64_t base = 0;
+  for (int64_t b0 = 0; b0 < m; b0 += blk) {
+    const int64_t b1 = std::min(m, b0 + blk), rows = b1 - b0;
+    if (!have_block && (rc = compute(b0, b1, d.p, ld)) != DA_OK) return rc;
+    if ((rc = launch_threshold_rows_count(d.as<uint16_t>(), rows, n, ld, keep.as<uint8_t>(), nbins, rowptr.as<int64_t>(), work.p, wb, stream)) != DA_OK)
+      return rc;
+    int64_t total = 0;
+    DA_HIP_TRY(hipMemcpyAsync(&total, rowptr.as<int64_t>() + rows, 8, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+    if ((rc = sink(b0, b1, d.as<uint16_t>(), ld, keep.as<uint8_t>(), rowptr.as<int64_t>(), total, base)) != DA_OK) return rc;
+    base += total;
+  }
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  *threshold_out = thr;
+  *n_edges_out = base;
+  return DA_OK;
+}
+
+// a block's kept entries appended to the handle's host vectors: i = block origin + row, w = values[key] (the table the dense calls widen with)
+static int rect_block_to_host(EdgeSet &es, const std::vector<double> &values, int64_t n, int64_t b0, int64_t b1, const uint16_t *d_keys, int64_t ld,
+                              const uint8_t *d_keep, const int64_t *d_rowptr, int64_t total, int64_t base, hipStream_t stream) {
+  if (total <= 0) return DA_OK;
+  const int64_t rows = b1 - b0;
+  DevBuf dj, dkey;
+  int rc;
+  if ((rc = dj.alloc((size_t)total * 4)) != DA_OK || (rc = dkey.alloc((size_t)total * 2)) != DA_OK) return rc;
+  if ((rc = launch_threshold_rows_emit(d_keys, rows, n, ld, d_keep, (int)values.size(), d_rowptr, dj.as<int32_t>(), dkey.as<uint16_t>(), total,
+                                       stream)) != DA_OK) return rc;
+  const size_t at = (size_t)base, end = (size_t)(base + total);
+  es.i.resize(end); es.j.resize(end); es.w.resize(end);
+  std::vector<int64_t> rp((size_t)rows + 1);
+  std::vector<uint16_t> key((size_t)total);
+  DA_HIP_TRY(hipMemcpyAsync(rp.data(), d_rowptr, (size_t)(rows + 1) * 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(es.j.data() + at, dj.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(key.data(), dkey.p, (size_t)total * 2, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) es.i[at + (size_t)e] = (int32_t)(b0 + r);
+  for (int64_t e = 0; e < total; ++e) es.w[at + (size_t)e] = values[key[(size_t)e]];
+  return DA_OK;
+}
+
+int da_similarity_mh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                       const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, double thresh,
+                                       int thresh_is_quantile, da_edges **handle_out, double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    int rc;
+    int64_t x_total, y_total;
+    if ((rc = mh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, &rc, &x_total, &y_total)) != DA_OK) return rc;
+    if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+    if ((rc = require_device()) != DA_OK) return rc;
+    DeviceInput dx, dy;
+    if ((rc = dx.upload(x_residues, x_offsets, m, x_total, seeds, n_hash)) != DA_OK || (rc = dy.upload(y_residues, y_offsets, n, y_total, nullptr, 0)) != DA_OK)
+      return rc;
+    MhCrossOperand c;
+    if ((rc = mh_cross_operand(dx.res.as<uint8_t>(), dx.off.as<int64_t>(), m, dy.res.as<uint8_t>(), dy.off.as<int64_t>(), n, k, n_hash,
+                               dx.seeds.as<uint32_t>(), &c, nullptr)) != DA_OK) return rc;
+    DA_HIP_TRY(hipStreamSynchronize(nullptr));
+    c.work.release(); c.sig.release();                     // before the scratch block is sized
+    const std::vector<double> values = mh_code_values(n_hash);
+    return threshold_blocks(m, n, values, thresh, thresh_is_quantile != 0, nullptr,
+                            [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, nullptr); },
+                            [&](int64_t b0, int64_t b1, const uint16_t *dk, int64_t ld, const uint8_t *keep, const int64_t *rp, int64_t total, int64_t base) {
+                              return rect_block_to_host(es, values, n, b0, b1, dk, ld, keep, rp, total, base, nullptr);
+                            }, &es.threshold, n_edges);
+  });
+}
+
+int da_similarity_nw_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                       const int64_t *y_offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext, double thresh,
+                                       int thresh_is_quantile, da_edges **handle_out, double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+    if (mid < 0) return DA_ERR_BAD_MATRIX;
+    int rc;
+    if (m <= 0 || n <= 0) {                                // an empty rectangle: no edges; it has no quantile
+      if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+      if (thresh_is_quantile) return fail(DA_ERR_BAD_ARG, "quantile of an empty set");
+      es.threshold = thresh;
+      *n_edges = 0;
+      return DA_OK;
+    }
+    if (!x_residues || !y_residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int64_t x_total, y_total, x_max, y_max;
+    if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
+    if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
+    if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+    for (int64_t i = 0; i < m + n; ++i) {
+      const int64_t *o = i < m ? x_offsets + i : y_offsets + (i - m);
+      if (o[1] == o[0])
+        return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in a quantile",
+                    (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y");
+    }
+    const int64_t max_len = std::max(x_max, y_max);
+    if (max_len > 127) return fail(DA_ERR_UNSUPPORTED, "the NW two-set edge list works on uint16 codes: sequences up to 127 residues");
+    if ((rc = require_device()) != DA_OK) return rc;
+    NwCodes nw;
+    if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
+    // every code that can occur lies below this bound (matches <= max_len, length <= 2 * max_len), as in the square NW edge path: the
+    // histogram of short peptides stays in LDS; length 0 cannot occur (no empty sequences)
+    const int nbins = (int)((max_len << 8) | (2 * max_len)) + 1;
+    const std::vector<double> values = nw_code_values(nbins, 0.0);
+    return threshold_blocks(m, n, values, thresh, thresh_is_quantile != 0, nullptr,
+                            [&](int64_t b0, int64_t b1, void *d, int64_t ld) {   // rows of x against columns of y: x[i] is sequence1
+                              return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, false,
+                                               DA_OUT_COMPACT, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
+                            },
+                            [&](int64_t b0, int64_t b1, const uint16_t *dk, int64_t ld, const uint8_t *keep, const int64_t *rp, int64_t total, int64_t base) {
+                              return rect_block_to_host(es, values, n, b0, b1, dk, ld, keep, rp, total, base, nullptr);
+                            }, &es.threshold, n_edges);
+  });
+}
+
+int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t *d_x_offsets, int64_t m, const uint8_t *d_y_residues,
+                                     const int64_t *d_y_offsets, int64_t n, int k, int n_hash, const uint32_t *d_seeds, double thresh,
+                                     int thresh_is_quantile, int64_t *d_rowptr, int32_t *d_j, double *d_w, int64_t capacity, double *threshold_out,
+                                     int64_t *n_edges_out, void *stream_v) {
+  int rc;
+  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
+  if (!d_x_residues || !d_x_offsets || !d_y_residues || !d_y_offsets || !d_seeds || !d_rowptr || !threshold_out || !n_edges_out)
+    return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: the two-set calls take n_hash <= 65535 (got %d)", n_hash);
+  if (m > 0x7ffffff0LL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "two-set MinHash: too many sequences");
+  if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+  if (capacity < 0) return fail(DA_ERR_BAD_ARG, "negative capacity");
+  if (capacity > 0 && (!d_j || !d_w)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  MhCrossOperand c;
+  if ((rc = mh_cross_operand(d_x_residues, d_x_offsets, m, d_y_residues, d_y_offsets, n, k, n_hash, d_seeds, &c, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  c.work.release(); c.sig.release();                       // before the scratch block is sized
+  const std::vector<double> values = mh_code_values(n_hash);
+  return threshold_blocks(m, n, values, thresh, thresh_is_quantile != 0, stream,
+                          [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, stream); },
+                          [&](int64_t b0, int64_t b1, const uint16_t *dk, int64_t ld, const uint8_t *keep, const int64_t *rp, int64_t total, int64_t base) -> int {
+                            int rc2;
+                            const int64_t rows = b1 - b0;   // the last block also places the total
+                            if ((rc2 = launch_rowptr_offset(rp, rows + (b1 == m ? 1 : 0), base, d_rowptr + b0, stream)) != DA_OK) return rc2;
+                            const int64_t cnt = std::min(total, capacity - base);
+                            if (cnt <= 0) return DA_OK;
+                            DevBuf key;
+                            if ((rc2 = key.alloc((size_t)cnt * 2)) != DA_OK) return rc2;
+                            if ((rc2 = launch_threshold_rows_emit(dk, rows, n, ld, keep, n_hash + 1, rp, d_j + base, key.as<uint16_t>(), cnt, stream)) != DA_OK ||
+                                (rc2 = launch_edge_values(key.as<uint16_t>(), cnt, n_hash, d_w + base, stream)) != DA_OK) return rc2;
+                            DA_HIP_TRY(hipStreamSynchronize(stream));   // the key block goes back to the cache after this
+                            return DA_OK;
+                          }, threshold_out, n_edges_out);
+}
+
+
 // ------------------------------------------------- multi-device host entry points (SURVEY 8(b) da_opts, 8(e))
 // ONE process drives several GPUs: a host thread per device (hipSetDevice is per thread), every device holds all
 // sequences and rebuilds all signatures itself (2 MB in), the pair space is split, and every device copies ITS

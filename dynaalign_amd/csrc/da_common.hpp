@@ -144,6 +144,41 @@ __host__ __device__ inline int64_t pk_lo_bytes(int64_t U) { return (U + 127) / 1
 __host__ __device__ inline int64_t pk_row_bytes(int64_t lo_bytes) { return lo_bytes + lo_bytes / 8; }
 inline size_t pk_table_bytes(int64_t U) { return (size_t)U * (size_t)pk_row_bytes(pk_lo_bytes(U)); }
 
+// ---- device helpers the row-walking kernels share (topk_kernels.hip, rect_edges_kernels.hip): a row of uint16 keys is taken in chunks of
+// THREADS x 8 keys, eight consecutive keys (one 16-byte load where the row address allows it) per thread
+constexpr int TK_PER = 8;                     // keys per thread per chunk: one 16-byte load
+
+// lanes below `lane` summed: inclusive wave scan by shuffles
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// ranks (r) and keys (k) of the row's columns [j0, j0 + 8); returns how many of them exist (columns < n)
+__device__ __forceinline__ int load8(const uint16_t *__restrict__ row, int64_t j0, int64_t n, bool vec, const uint16_t *__restrict__ rank,
+                                     uint32_t r[TK_PER], uint32_t k[TK_PER]) {
+  int nv;
+  if (vec && j0 + TK_PER <= n) {
+    const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) k[e] = (w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
+    nv = TK_PER;
+  } else {
+    nv = j0 >= n ? 0 : (n - j0 < TK_PER ? (int)(n - j0) : TK_PER);
+#pragma unroll
+    for (int e = 0; e < TK_PER; ++e) k[e] = e < nv ? (uint32_t)row[j0 + e] : 0u;
+  }
+#pragma unroll
+  for (int e = 0; e < TK_PER; ++e) r[e] = (rank && e < nv) ? (uint32_t)rank[k[e]] : k[e];
+  return nv;
+}
+
 // Kernel launchers implemented in the .hip translation units.  All are
 // asynchronous on `stream`; argument checking is done by the C-ABI layer.
 int launch_minhash_signatures(const uint8_t *d_res, const int64_t *d_off, int64_t n,
@@ -281,6 +316,18 @@ constexpr int DA_TOPK_MAX = 1024;
 int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
                      int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, hipStream_t stream);
 int launch_topk_values(const uint16_t *d_key, int64_t ld_key, int64_t rows, int top, int n_hash, double *d_val, int64_t ld_val, hipStream_t stream);
+// rect_edges_kernels.hip: the threshold form of a two-set rectangle, on a block of `rows` rows of ld >= n uint16 keys (da_dev_rect_histogram,
+// da_dev_threshold_rows_count / _emit): histogram of the whole block; per-row count of the keys flagged in d_keep + exclusive scan -> row
+// pointers; the flagged columns of every row in ascending order at its row pointer.  ... and the kept MinHash counts as doubles
+size_t threshold_rows_workspace_bytes(int64_t rows);
+int launch_rect_histogram(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, int nbins, unsigned long long *d_hist, hipStream_t stream);
+int launch_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, int64_t *d_rowptr,
+                                void *d_work, size_t work_bytes, hipStream_t stream);
+int launch_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, const int64_t *d_rowptr,
+                               int32_t *d_j, uint16_t *d_key_out, int64_t capacity, hipStream_t stream);
+int launch_edge_values(const uint16_t *d_key, int64_t count, int n_hash, double *d_w, hipStream_t stream);
+// d_out[r] = d_in[r] + base for r < count (a block's row pointers placed into the row pointers of the whole rectangle)
+int launch_rowptr_offset(const int64_t *d_in, int64_t count, int64_t base, int64_t *d_out, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

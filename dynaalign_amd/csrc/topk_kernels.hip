@@ -18,39 +18,6 @@
 namespace da {
 namespace {
 
-constexpr int TK_PER = 8;                     // keys per thread per chunk: one 16-byte load
-
-// lanes below `lane` summed: inclusive wave scan by shuffles
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// ranks (r) and keys (k) of the row's columns [j0, j0 + 8); returns how many of them exist (columns < n)
-__device__ __forceinline__ int load8(const uint16_t *__restrict__ row, int64_t j0, int64_t n, bool vec, const uint16_t *__restrict__ rank,
-                                     uint32_t r[TK_PER], uint32_t k[TK_PER]) {
-  int nv;
-  if (vec && j0 + TK_PER <= n) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < TK_PER; ++e) k[e] = (w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
-    nv = TK_PER;
-  } else {
-    nv = j0 >= n ? 0 : (n - j0 < TK_PER ? (int)(n - j0) : TK_PER);
-#pragma unroll
-    for (int e = 0; e < TK_PER; ++e) k[e] = e < nv ? (uint32_t)row[j0 + e] : 0u;
-  }
-#pragma unroll
-  for (int e = 0; e < TK_PER; ++e) r[e] = (rank && e < nv) ? (uint32_t)rank[k[e]] : k[e];
-  return nv;
-}
-
 // hist[0 .. 256) read from the top by wave 0: the bin B holding the want-th largest element (1-based) and the count in the bins above B
 __device__ __forceinline__ void pick_bin(const unsigned int *hist, uint32_t want, unsigned int *out_bin, unsigned int *out_above) {
   if (threadIdx.x >= 64) return;

@@ -388,6 +388,78 @@ def similarity_mh_cross_topk(dx, dy, k, n_hash, seeds, top):
     return idx[:dx.n], val[:dx.n]
 
 
+def _key_block(keys):
+    """(rows, n, ld) of a block of uint16 keys held in an int16 tensor of shape (rows, n), any row stride and base address"""
+    _require_cuda(keys, "keys")
+    assert keys.dim() == 2 and keys.dtype == torch.int16 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
+    rows, n = int(keys.shape[0]), int(keys.shape[1])
+    return rows, n, (int(keys.stride(0)) if rows > 1 else max(n, 1))
+
+
+def rect_histogram(keys, nbins):
+    """uint64 histogram (int64 tensor of nbins entries) of a whole block of uint16 keys; keys >= nbins are ignored (da_dev_rect_histogram)"""
+    rows, n, ld = _key_block(keys)
+    hist = torch.zeros(int(nbins), dtype=torch.int64, device=keys.device)
+    _call(_capi.load().da_dev_rect_histogram, keys.data_ptr(), rows, n, ld, int(nbins), hist.data_ptr(), _stream())
+    return hist
+
+
+def threshold_rows(keys, keep, capacity=None):
+    """The flagged entries of a block of uint16 keys as CSR: (rowptr int64 (rows + 1), j int32, key int16 (uint16 bit pattern)) -- per row
+    the columns whose key v has keep[v] != 0 (keys >= len(keep) are never kept), ascending, row r at rowptr[r] : rowptr[r + 1]
+    (da_dev_threshold_rows_count, then da_dev_threshold_rows_emit).  capacity=None sizes j / key from the count (one 8-byte read-back);
+    otherwise they hold `capacity` slots and entries beyond it are counted in rowptr but not stored."""
+    lib = _capi.load()
+    rows, n, ld = _key_block(keys)
+    dev = keys.device
+    keep_t = keep if torch.is_tensor(keep) else torch.as_tensor(np.ascontiguousarray(keep, np.uint8))
+    keep_t = keep_t.to(dev).contiguous()
+    assert keep_t.dtype == torch.uint8
+    rowptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+    if rows > 0:
+        nbytes = int(lib.da_dev_threshold_rows_workspace_bytes(rows))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _call(lib.da_dev_threshold_rows_count, keys.data_ptr(), rows, n, ld, keep_t.data_ptr(), keep_t.numel(), rowptr.data_ptr(),
+                                                    work.data_ptr(), nbytes, _stream())
+    cap = int(rowptr[rows].item()) if capacity is None else int(capacity)
+    j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    key = torch.empty(max(cap, 1), dtype=torch.int16, device=dev)
+    if rows > 0 and cap > 0:
+        _call(lib.da_dev_threshold_rows_emit, keys.data_ptr(), rows, n, ld, keep_t.data_ptr(), keep_t.numel(), rowptr.data_ptr(), j.data_ptr(),
+                                                   key.data_ptr(), cap, _stream())
+    return rowptr, j[:cap], key[:cap]
+
+
+def similarity_mh_cross_edges(dx, dy, k, n_hash, seeds, thresh_p=None, threshold=None, capacity=None):
+    """The threshold form of similarity_mh_cross on two device-resident sets, one C call (da_dev_similarity_mh_cross_edges):
+    (threshold, rowptr int64 (m + 1), j int32, w float64) -- CSR over the rows of x of the entries with R >= threshold and R > 0, columns
+    ascending, w bit for bit R.  threshold is not None: the absolute form; otherwise the type-7 quantile thresh_p (default 0.8) of all
+    m * n entries.  With a capacity, j / w hold that many slots and rowptr is complete even when rowptr[m] exceeds it; capacity=None
+    starts from a guess and calls again when the result does not fit."""
+    lib = _capi.load()
+    if not torch.is_tensor(seeds):
+        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(dx.residues.device)
+    _require_cuda(dx.residues, "residues of x")
+    _require_cuda(dy.residues, "residues of y")
+    dev = dx.residues.device
+    thresh, is_q = (float(threshold), 0) if threshold is not None else (0.8 if thresh_p is None else float(thresh_p), 1)
+    rowptr = torch.empty(max(dx.n, 0) + 1, dtype=torch.int64, device=dev)
+    thr, cnt = ctypes.c_double(0.0), ctypes.c_int64(0)
+    cap = max(4 * max(dx.n, 0), 1 << 20) if capacity is None else int(capacity)
+    while True:
+        j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        w = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+        _call(lib.da_dev_similarity_mh_cross_edges, dx.residues.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.residues.data_ptr(),
+                                                         dy.offsets.data_ptr(), dy.n, int(k), int(n_hash), seeds.data_ptr(), thresh, is_q,
+                                                         rowptr.data_ptr(), j.data_ptr(), w.data_ptr(), cap, ctypes.addressof(thr),
+                                                         ctypes.addressof(cnt), _stream())
+        if capacity is not None or cnt.value <= cap:
+            break
+        cap = cnt.value
+    stored = min(cnt.value, max(cap, 0))
+    return thr.value, rowptr, j[:stored], w[:stored]
+
+
 def mh_cross_last_route():
     """what this thread's last similarity_mh_cross call did: dict(m, n, unique_x, unique_y, dedup, plane_bits, plan_ms, codes_ms,
     k2_ms, lists_ms, expand_ms)"""

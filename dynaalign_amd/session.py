@@ -10,6 +10,7 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     thr, i, j, w = s.edges(idx, thresh_p=0.8)                       # == similarityMH_edges(sequences[idx], ...)
     R = s.cross(new, idx)                                           # == similarityMH_cross(new, sequences[idx], 4, 500, seed=12345)
     i, v = s.cross_topk(new, 10, idx)                               # == similarityMH_cross_topk(new, sequences[idx], 4, 500, 10, seed=12345)
+    thr, ptr, j, w = s.cross_edges(new, 0.99, idx=idx)              # == similarityMH_cross_edges(new, sequences[idx], 4, 500, 0.99, seed=12345) as CSR
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
 seeds per call, src/minHash.cpp:73,137); the contract -- MinHash estimates under one hash family -- holds.
@@ -110,6 +111,51 @@ class MinHashSession:
         keys = torch.cat(out_k).contiguous()
         val = device.widen(keys, False, self.n_hash)                     # count / n_hash, the library's divide
         return torch.cat(out_i).cpu().numpy(), val.cpu().numpy()
+
+    def cross_edges(self, sequences, thresh_p=0.8, threshold=None, idx=None, block_bytes=1 << 30):
+        """The entries of cross(sequences, idx) that pass a threshold, without the m x n matrix, as CSR over the new sequences:
+        (threshold, rowptr, j, w) device tensors -- int64 (m + 1), int32 positions in idx (in the resident set when idx is None), ascending
+        within a row, and the float64 similarities -- of the entries with R >= threshold and R > 0, as
+        similarityMH_cross_edges(sequences, resident[idx], k, n_hash, thresh_p, threshold=threshold, seed=self.seed).  threshold=None: the
+        type-7 quantile thresh_p of all m * n entries (a histogram pass over the row blocks first; a rectangle of several blocks is compared
+        twice).  The rectangle is compared into uint16 counts in row blocks of block_bytes; each goes through device.threshold_rows."""
+        planes, m, m_pad, n = self._joint_operand(sequences, idx)
+        nbins = self.n_hash + 1
+        values = np.arange(nbins, dtype=np.float64) / np.float64(self.n_hash)          # src/minHash.cpp:174
+        ld = -(-n // 8) * 8
+        blk = min(max(block_bytes // (2 * ld) // 128 * 128, 128), m)
+        buf = torch.empty((blk, ld), dtype=torch.int16, device=self.sig.device)
+
+        def block(b0):
+            b1 = min(m, b0 + blk)
+            return device.mh_compare_rect(planes, m_pad + n, self.n_hash, b0, b1, m_pad, m_pad + n, _capi.DA_OUT_COMPACT, out=buf[:b1 - b0, :n])
+        kept_block = None
+        if threshold is None:
+            if not 0.0 <= float(thresh_p) <= 1.0:
+                raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "thresh_p must be in [0, 1]")
+            hist = torch.zeros(nbins, dtype=torch.int64, device=self.sig.device)
+            for b0 in range(0, m, blk):
+                kept_block = block(b0)
+                hist += device.rect_histogram(kept_block, nbins)
+            thr = quantile_type7(hist.cpu().numpy().astype(np.uint64), values, float(thresh_p))
+            if blk < m:
+                kept_block = None
+        else:
+            thr = float(threshold)
+            if thr != thr:
+                raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "the threshold must not be NaN")
+        keep = torch.from_numpy(((values > 0.0) & (values >= thr)).astype(np.uint8)).to(self.sig.device)
+        ptrs, js, keys, base = [], [], [], 0
+        for b0 in range(0, m, blk):
+            rp, j, key = device.threshold_rows(kept_block if kept_block is not None else block(b0), keep)
+            ptrs.append(rp[:-1] + base)
+            js.append(j)
+            keys.append(key)
+            base += int(rp[-1].item())
+        ptrs.append(torch.tensor([base], dtype=torch.int64, device=self.sig.device))
+        key_all = torch.cat(keys).contiguous()
+        w = device.widen(key_all, False, self.n_hash) if base else torch.empty(0, dtype=torch.float64, device=self.sig.device)
+        return thr, torch.cat(ptrs), torch.cat(js), w
 
     def edges_csr(self, idx=None, thresh_p=0.8):
         """The thresholded graph of the subset as the canonical symmetric CSR clusterbreak.louvain_csr takes -- sorted ON THE DEVICE

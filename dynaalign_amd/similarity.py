@@ -13,6 +13,11 @@ and the top-k forms of those (per row of x the ``top`` most similar y, never the
     similarityMH_cross_topk(x, y, k=4, n_hash=50, top=10)
     similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10)
 
+and the threshold forms of those (the entries that pass a threshold as a sorted edge list, never the m x n matrix)
+
+    similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, threshold=None)
+    similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, threshold=None)
+
 Same names, argument order, defaults and error texts as the reference; the
 bodies marshal to the C ABI (include/dynaalign.h) exactly as the Rcpp glue in
 r_glue/ does.  Results are dense symmetric n x n float64 matrices with
@@ -353,3 +358,39 @@ def similarityNW_edges(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, t
     go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
     return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_edges_begin(
         res.ctypes.data, off.ctypes.data, n, name, go, ge, float(thresh_p), h, thr, cnt))
+
+
+def _thresh_args(thresh_p, threshold):
+    """(thresh, thresh_is_quantile) of the *_cross_edges_begin calls: a threshold that is not None selects the absolute form"""
+    return (float(thresh_p), 1) if threshold is None else (float(threshold), 0)
+
+
+def similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, *, threshold=None, seed=None):
+    """The entries of R = similarityMH_cross(x, y, k, n_hash, seed=seed) that pass a threshold, without the (m, n) matrix:
+    ``(threshold, i, j, weight)`` with every (i, j) where ``R[i, j] >= threshold and R[i, j] > 0`` (clusterbreak's
+    ``pep.sim[pep.sim < threshold] <- 0``; a zero weight is no edge), 0-based, sorted by (i, j) -- the order of ``np.nonzero`` -- and
+    ``weight`` bit for bit ``R[i, j]``.  ``threshold=None``: the threshold is R's type-7 ``quantile(as.vector(R), thresh_p)`` over all
+    m * n entries; a ``threshold`` that is not None is taken as it is (a range query: every y within that similarity of each x) and
+    ``thresh_p`` is unused.  Errors as similarityMH_cross, then ``thresh_p`` outside [0, 1] / a NaN threshold."""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    n = len(yo) - 1
+    thresh, is_q = _thresh_args(thresh_p, threshold)
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_mh_cross_edges_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data, thresh, is_q, h, thr, cnt))
+
+
+def similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, *, threshold=None):
+    """The entries of R = similarityNW_cross(x, y, ...) (x[i] is sequence1) that pass a threshold: ``(threshold, i, j, weight)`` as
+    similarityMH_cross_edges.  Equal similarities pass or fail together whatever their (matches, length): 2/4 and 3/6 are both 0.5.
+    Every sequence has 1 .. 127 residues (an empty one is refused: a NaN has no place in a quantile).  An empty ``x`` or ``y`` gives no
+    edges in the absolute form and is an error in the quantile form (an empty set has no quantile)."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
+    thresh, is_q = _thresh_args(thresh_p, threshold)
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_cross_edges_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name, go, ge, thresh, is_q, h, thr, cnt))

@@ -47,6 +47,8 @@ extern "C" {
 /* (round 4 added entry points only -- da_config_reload, da_debug_comm_cache_state, da_mh_last_route_split: the version stays)
  * (the two-set entry points -- da_similarity_*_cross, da_dev_*_rect, da_dev_similarity_mh_cross, da_mh_cross_last_route -- were added likewise)
  * (the two-set top-k entry points -- da_similarity_*_cross_topk, da_dev_similarity_mh_cross_topk, da_dev_topk_rows, da_nw_code_ranks -- likewise)
+ * (the two-set threshold entry points -- da_similarity_*_cross_edges_begin, da_dev_similarity_mh_cross_edges, da_dev_rect_histogram,
+ *  da_dev_threshold_rows_* -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -558,6 +560,66 @@ int da_dev_shard_extract_edges(const uint16_t *d_local, int64_t ld, int64_t n, i
                                const uint8_t *d_keep, int nbins, int include_diagonal,
                                int32_t *d_i, int32_t *d_j, uint16_t *d_v, int64_t capacity,
                                uint64_t *d_count, void *stream);
+
+/* ---- two sets, threshold form: the entries of the m x n rectangle that pass a threshold, as a sorted edge list ----
+ * R is the matrix da_similarity_mh_cross / da_similarity_nw_cross return (no forced diagonal).  The result is every (i, j) with
+ * R[i][j] >= threshold and R[i][j] > 0 (clusterbreak's pep.sim[pep.sim < threshold] <- 0; a zero weight is no edge), sorted by (i, j),
+ * 0-based, weight bit for bit R[i][j]; the m x n matrix never exists.
+ *   thresh_is_quantile == 0: threshold = thresh, any non-NaN double (a range query: "every y within t of each x");
+ *   thresh_is_quantile != 0: threshold = quantile(as.vector(R), thresh), R's type 7 over all m * n entries, 0 <= thresh <= 1 -- from a
+ *                            device histogram of the uint16 counts / codes and da_quantile_type7 (NW: on the codes in ascending order of
+ *                            their value, as da_similarity_nw_edges).
+ * The decision is made on the host per count / code and uploaded as a byte table -- MinHash keep[c] = c > 0 && (double)c / (double)n_hash
+ * >= threshold, NW keep[code] = matches > 0 && (double)matches / (double)length >= threshold -- with the library's own divide, so the
+ * boundary R == threshold is exact.  *_begin fills a da_edges handle: read it with da_edges_fetch, release it with da_edges_free.
+ * Validation, before any device is needed: everything da_similarity_*_cross checks, in its order and with its texts; then the threshold
+ * argument (quantile form: thresh outside [0, 1] or NaN; absolute form: NaN -> DA_ERR_BAD_ARG); then, for NW, the limits of
+ * da_similarity_nw_cross_topk: every sequence on both sides has 1 .. 127 residues (DA_ERR_UNSUPPORTED; a NaN has no place in a quantile).
+ * NW with m == 0 or n == 0: DA_OK and no edges in the absolute form, DA_ERR_BAD_ARG "quantile of an empty set" in the quantile form.
+ * The rectangle is computed as uint16 codes in row blocks of x (operand, padding, 131 068-row rule and DYNAALIGN_BLOCK_BYTES blocking of
+ * da_similarity_*_cross_topk).  Absolute form: ONE pass -- per block the compare, the per-row counts, the 8-byte total read back, the
+ * edge buffers sized from it, the ordered emit.  Quantile form: a first pass of compare + histogram per block, the threshold on the
+ * host, then the pass above; a rectangle that fits ONE block is kept from the first pass, one cut into several blocks is compared
+ * twice.  Single device, the direct route only. */
+int da_similarity_mh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                       const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                                       int k, int n_hash, const uint32_t *seeds, double thresh, int thresh_is_quantile,
+                                       da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+int da_similarity_nw_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                       const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                                       const char *matrix_name, int gap_open, int gap_ext, double thresh, int thresh_is_quantile,
+                                       da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+
+/* The device pieces, on a block of uint16 keys: `rows` rows of ld >= n keys.  Rows are read in 16-byte units where their address allows
+ * it, in 2-byte units otherwise: every ld and base address works.  All are asynchronous on `stream`.  NULL pointers, ld < n and nbins
+ * outside 1 .. 65536 are DA_ERR_BAD_ARG; rows == 0 is DA_OK and touches nothing.
+ * da_dev_rect_histogram: d_hist[v] += the number of keys equal to v in the whole block (the caller zeroes d_hist[nbins]); keys >= nbins are
+ *   ignored.  Persistent workgroups with an LDS histogram for nbins <= 8192, global atomics beyond; key 0 is counted in a register.
+ * da_dev_threshold_rows_count: d_rowptr[r] = the number of keys v < nbins with d_keep[v] != 0 in the rows before r (an exclusive scan of
+ *   the per-row counts): the first slot of row r, and d_rowptr[rows] the block's total (int64, rows + 1 entries).  d_work:
+ *   da_dev_threshold_rows_workspace_bytes(rows) bytes.
+ * da_dev_threshold_rows_emit: for every row its kept columns in ASCENDING column order at d_j[d_rowptr[r] ...] (int32) with their keys
+ *   in d_key_out (uint16); slots >= capacity are not written (d_rowptr already says how many there are).  d_keep and the keys must be those
+ *   the count saw.  An ordered compaction -- a workgroup per row (one wave for rows of up to 1024 keys) walks it in chunks of 8 keys per
+ *   thread, scans the per-thread kept counts and carries a running base -- with no output atomic and no sort. */
+int da_dev_rect_histogram(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, int nbins, uint64_t *d_hist, void *stream);
+size_t da_dev_threshold_rows_workspace_bytes(int64_t rows);
+int da_dev_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins,
+                                int64_t *d_rowptr, void *d_work, size_t work_bytes, void *stream);
+int da_dev_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins,
+                               const int64_t *d_rowptr, int32_t *d_j, uint16_t *d_key_out, int64_t capacity, void *stream);
+
+/* The threshold form of similarityMH_cross on two resident sets as ONE call; the result is CSR over the rows of x: d_rowptr[m + 1]
+ * (int64), d_j (int32 columns, ascending within a row) and d_w (float64, bit for bit R: (double)count / (double)n_hash) with room for
+ * `capacity` entries (d_j / d_w may be NULL when capacity is 0).  *threshold_out and *n_edges_out are HOST values.  If *n_edges_out >
+ * capacity the row pointers are complete, the first `capacity` slots are filled and the call returns DA_OK: call again with larger
+ * buffers.  Operand and row blocks as da_dev_similarity_mh_cross_topk; the quantile form makes two passes (see above).  Direct route only;
+ * n_hash <= 65535; one stream, which it synchronises.  Validates like da_dev_similarity_mh_cross_topk, before it looks at a pointer. */
+int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t *d_x_offsets, int64_t m,
+                                     const uint8_t *d_y_residues, const int64_t *d_y_offsets, int64_t n,
+                                     int k, int n_hash, const uint32_t *d_seeds, double thresh, int thresh_is_quantile,
+                                     int64_t *d_rowptr, int32_t *d_j, double *d_w, int64_t capacity,
+                                     double *threshold_out, int64_t *n_edges_out, void *stream);
 
 /* ---- the caller's clustering step (reference R/clusterbreak.R:112-136, netcluster) ------------
  * igraph::cluster_louvain(graph_from_adjacency_matrix(S, mode = "upper", weighted = TRUE),

@@ -338,3 +338,56 @@ List similarityNW_cross_topk(CharacterVector x, CharacterVector y, std::string m
                                     gapOpen, gapExt, top, idx.data(), val.data()));
   return topk_result(idx, val, m, top > 0 ? top : 0);
 }
+
+namespace {
+// the handle of a *_cross_edges_begin call as list(threshold, i, j, weight), positions 1-based
+List cross_edges_result(da_edges *h, double thr, int64_t cnt) {
+  const EdgesHandle guard(h);             // released even if the allocations below throw
+  IntegerVector i(cnt), j(cnt);
+  NumericVector weight(cnt);
+  check(da_edges_fetch(h, cnt, INTEGER(i), INTEGER(j), REAL(weight)));
+  for (int64_t e = 0; e < cnt; ++e) { i[e] += 1; j[e] += 1; }   // R is 1-based
+  return List::create(_["threshold"] = thr, _["i"] = i, _["j"] = j, _["weight"] = weight);
+}
+}  // namespace
+
+//' @name similarityMH_cross_edges
+//' @title The entries of similarityMH_cross(x, y, k, n_hash) that pass a threshold, as a sorted edge list
+//' @description Non-breaking addition.  With R <- similarityMH_cross(x, y, k, n_hash) under the same seeds: every (i, j) with
+//' R[i, j] >= threshold and R[i, j] > 0, sorted by (i, j), weight = R[i, j]; the length(x) by length(y) matrix is never built.  The threshold is
+//' quantile(as.vector(R), thresh_p), or, with absolute = TRUE, thresh_p itself (a range query: every y within that similarity of each x).
+//' @return list(threshold, i, j, weight), i and j 1-based
+//' @export
+// [[Rcpp::export]]
+List similarityMH_cross_edges(CharacterVector x, CharacterVector y, int k = 4, int n_hash = 50, double thresh_p = 0.8,
+                              bool absolute = false) {
+  const Packed px(x), py(y);
+  const int64_t m = x.length(), n = y.length();
+  std::vector<uint32_t> seeds(n_hash > 0 ? n_hash : 1);
+  if (n_hash > 0) check(da_hash_family_seeds(hash_seed(), n_hash, seeds.data()));
+  double thr = 0;
+  int64_t cnt = 0;
+  da_edges *h = nullptr;
+  check(da_similarity_mh_cross_edges_begin(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, k, n_hash,
+                                           seeds.data(), thresh_p, absolute ? 0 : 1, &h, &thr, &cnt));
+  return cross_edges_result(h, thr, cnt);
+}
+
+//' @name similarityNW_cross_edges
+//' @title The entries of similarityNW_cross(x, y, ...) that pass a threshold, as a sorted edge list
+//' @description Non-breaking addition, as similarityMH_cross_edges on similarityNW_cross(x, y, ...) (x[i] is sequence1).  Sequences of 1 to 127
+//' residues.
+//' @return list(threshold, i, j, weight), i and j 1-based
+//' @export
+// [[Rcpp::export]]
+List similarityNW_cross_edges(CharacterVector x, CharacterVector y, std::string matrixName = "BLOSUM62", int gapOpen = 10, int gapExt = 4,
+                              double thresh_p = 0.8, bool absolute = false) {
+  const Packed px(x), py(y);
+  const int64_t m = x.length(), n = y.length();
+  double thr = 0;
+  int64_t cnt = 0;
+  da_edges *h = nullptr;
+  check(da_similarity_nw_cross_edges_begin(px.residues.data(), px.offsets.data(), m, py.residues.data(), py.offsets.data(), n, matrixName.c_str(),
+                                           gapOpen, gapExt, thresh_p, absolute ? 0 : 1, &h, &thr, &cnt));
+  return cross_edges_result(h, thr, cnt);
+}
