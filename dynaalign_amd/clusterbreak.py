@@ -3,6 +3,7 @@
     clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_fn=..., cluster_fn=..., cluster_wt=True)
                                                                               reference R/clusterbreak.R:180-275
     netcluster(pepmat, ...)                                                   reference R/clusterbreak.R:112-136
+    clusterconsensus(df)                                                      reference R/clusterbreak.R:309-320 (center-star, not DECIPHER)
 
 Same argument names, defaults, messages and bookkeeping as the R functions.  Per recursion level
 (``cluster_recursive``, R/clusterbreak.R:203-259):
@@ -33,7 +34,7 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["clusterbreak", "netcluster", "louvain", "threshold_edges_dense", "ClusterbreakResult"]
+__all__ = ["clusterbreak", "clusterconsensus", "netcluster", "louvain", "threshold_edges_dense", "ClusterbreakResult"]
 
 
 def louvain(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_modularity=False):
@@ -266,3 +267,107 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
                              filtered_seq=filtered)
     res.convergence, res.calls, res.levels = state["convergence"], state["itr"], levels
     return res
+
+
+CONSENSUS_SYMBOLS = "ARNDCQEGHILKMFPSTWYVBZX*-"   # tie order of clusterconsensus among symbols other than the center's
+
+
+def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
+    """One consensus sequence per cluster: the reference's signature (R/clusterbreak.R:309-320), ``df`` being rows of
+    ``(sequence, cluster_id)`` -- e.g. ``clusterbreak(...)["clustered_seq"]`` -- and the result a list of ``(cluster_id, consensus)`` in
+    first-appearance order of the ids.
+
+    This is a CENTER-STAR consensus on the library's own alignments (``nw_align``), NOT DECIPHER's AlignSeqs + ConsensusSequence, which
+    the reference calls and which is not restated here; the strings differ from the reference's in general.  For a cluster with members
+    s_0 .. s_{c-1} (input order, duplicates kept):
+
+      * c == 1: the member itself;
+      * the center is the member i with the largest ``math.fsum(matches[i, j] / length[i, j] for j != i)`` of the alignments of s_i
+        as sequence1 with s_j (a pair of two empty strings counts 0.0), ties to the lowest i -- one ``nw_align(ops=False)`` call over all
+        ordered pairs of all clusters;
+      * a second call aligns every center, as sequence1, with the other members of its cluster.  For center position p the tally holds
+        the center's residue and, per other member, the residue a D step puts opposite p, or '-' for a U step; L steps (residues
+        inserted between center positions) are ignored;
+      * the most frequent symbol wins; among tied symbols the center's residue if it is one of them, otherwise the one earliest in
+        "ARNDCQEGHILKMFPSTWYVBZX*-"; positions won by '-' are dropped.
+
+    Sequences longer than 127 residues raise the library's error (DA_ERR_UNSUPPORTED)."""
+    import math
+    from .similarity import nw_align
+    rows = df["clustered_seq"] if isinstance(df, dict) else df
+    order, members = [], {}
+    for row in rows:
+        seq, cid = row[0], row[1]
+        seq = seq.decode("latin-1") if isinstance(seq, bytes) else str(seq)
+        if cid not in members:
+            members[cid] = []
+            order.append(cid)
+        members[cid].append(seq)
+    # every member of a cluster of two or more, pooled: both calls index this one list
+    pool, start = [], {}
+    for cid in order:
+        if len(members[cid]) > 1:
+            start[cid] = len(pool)
+            pool.extend(members[cid])
+    center = {}
+    if pool:
+        pi, pj = [], []
+        for cid in start:
+            b, c = start[cid], len(members[cid])
+            for i in range(c):
+                for j in range(c):
+                    if i != j:
+                        pi.append(b + i)
+                        pj.append(b + j)
+        r = nw_align(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=False)
+        at = 0
+        for cid in start:
+            c = len(members[cid])
+            best, best_sum = 0, None
+            for i in range(c):
+                tot = math.fsum((int(r.matches[t]) / int(r.length[t])) if r.length[t] else 0.0 for t in range(at, at + c - 1))
+                at += c - 1
+                if best_sum is None or tot > best_sum:
+                    best, best_sum = i, tot
+            center[cid] = best
+        pi, pj = [], []
+        for cid in start:
+            b, c = start[cid], len(members[cid])
+            for j in range(c):
+                if j != center[cid]:
+                    pi.append(b + center[cid])
+                    pj.append(b + j)
+        r = nw_align(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=True)
+    out, at = [], 0
+    for cid in order:
+        mem = members[cid]
+        if len(mem) == 1:
+            out.append((cid, mem[0]))
+            continue
+        cen = mem[center[cid]]
+        tally = [{ch: 1} for ch in cen]
+        for j in range(len(mem)):
+            if j == center[cid]:
+                continue
+            other, ops = mem[j], r.ops[at]
+            at += 1
+            p = q = 0
+            for op in ops:
+                if op == "D":
+                    tally[p][other[q]] = tally[p].get(other[q], 0) + 1
+                    p += 1
+                    q += 1
+                elif op == "U":
+                    tally[p]["-"] = tally[p].get("-", 0) + 1
+                    p += 1
+                else:
+                    q += 1
+        cons = []
+        for p, t in enumerate(tally):
+            top = max(t.values())
+            tied = [ch for ch in t if t[ch] == top]
+            win = cen[p] if cen[p] in tied else min(tied, key=CONSENSUS_SYMBOLS.index)
+            if win != "-":
+                cons.append(win)
+        out.append((cid, "".join(cons)))
+    return out

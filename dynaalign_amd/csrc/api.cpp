@@ -2503,6 +2503,110 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
 }
 
 
+// ---- the alignment PATH of listed pairs (nw_align_kernels.hip): which residue sits opposite which, and where the gaps are -------------------
+size_t da_nw_align_workspace_bytes(int64_t pairs) { return nw_align_workspace_bytes(pairs); }
+
+int da_dev_nw_align_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, int64_t m, const uint8_t *d_y_codes, const int64_t *d_y_offsets,
+                          int64_t n, const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
+                          uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, void *d_work, size_t work_bytes,
+                          void *stream) {
+  if (pairs < 0 || m < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (pairs == 0) return DA_OK;
+  if ((d_pair_x == nullptr) != (d_pair_y == nullptr)) return fail(DA_ERR_BAD_ARG, "pair_x and pair_y must both be given or both be NULL");
+  if (!d_pair_x && (m != pairs || n != pairs)) return fail(DA_ERR_BAD_ARG, "without pair lists pair p is x[p] against y[p]: m == n == pairs");
+  if (!d_x_codes || !d_x_offsets || !d_y_codes || !d_y_offsets) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (d_ops && ld_ops < 0) return fail(DA_ERR_BAD_ARG, "negative ld_ops");
+  int rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  return launch_nw_align(d_x_codes, d_x_offsets, m, d_y_codes, d_y_offsets, n, d_pair_x, d_pair_y, 0, pairs, matrix_id, gap_open, gap_ext, d_ops, ld_ops,
+                         d_len, d_matches, d_score, d_work, work_bytes, static_cast<hipStream_t>(stream));
+}
+
+// What the reference's lazy fill would raise first with the listed pairs visited p ascending, each in calc's own order (src/pairwiseSeqAlign.cpp:
+// 238-250: sequence1[0], every character of sequence2, then sequence1[1], ...; an empty sequence1 checks nothing, an empty sequence2 still has all
+// of sequence1 checked).  first_bad(set)[i]: position of the first invalid byte of sequence i, -1 if none.
+static std::vector<int32_t> nw_first_bad(const uint8_t *res, const int64_t *off, int64_t count) {
+  static const char order[] = "ARNDCQEGHILKMFPSTWYVBZX*";
+  std::vector<int32_t> bad((size_t)count, -1);
+  for (int64_t i = 0; i < count; ++i)
+    for (int64_t p = off[i]; p < off[i + 1]; ++p)
+      if (res[p] == 0 || strchr(order, res[p]) == nullptr) { bad[(size_t)i] = (int32_t)std::min<int64_t>(p - off[i], INT32_MAX); break; }
+  return bad;
+}
+
+int da_nw_align_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                      const int32_t *pair_x, const int32_t *pair_y, int64_t pairs, const char *matrix_name, int gap_open, int gap_ext,
+                      uint8_t *ops_out, int64_t ld_ops, int32_t *len_out, int32_t *matches_out, int32_t *score_out) {
+  const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (pairs == 0) return DA_OK;                          // nothing listed: nothing to write
+  if (pairs < 0 || m < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if ((pair_x == nullptr) != (pair_y == nullptr)) return fail(DA_ERR_BAD_ARG, "pair_x and pair_y must both be given or both be NULL");
+  if (!pair_x && (m != pairs || n != pairs)) return fail(DA_ERR_BAD_ARG, "without pair lists pair p is x[p] against y[p]: m == n == pairs");
+  if (!x_residues || !y_residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t x_total, y_total, x_max, y_max;
+  int rc;
+  if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
+  auto xi = [&](int64_t p) { return pair_x ? (int64_t)pair_x[p] : p; };
+  auto yj = [&](int64_t p) { return pair_y ? (int64_t)pair_y[p] : p; };
+  for (int64_t p = 0; p < pairs; ++p) {
+    if (xi(p) < 0 || xi(p) >= m) return fail(DA_ERR_BAD_ARG, "pair %lld: index %lld is outside x (m = %lld)", (long long)p, (long long)xi(p), (long long)m);
+    if (yj(p) < 0 || yj(p) >= n) return fail(DA_ERR_BAD_ARG, "pair %lld: index %lld is outside y (n = %lld)", (long long)p, (long long)yj(p), (long long)n);
+  }
+  int64_t need = 0;
+  for (int64_t p = 0; p < pairs; ++p) {
+    const int64_t lx = x_offsets[xi(p) + 1] - x_offsets[xi(p)], ly = y_offsets[yj(p) + 1] - y_offsets[yj(p)];
+    if (lx > 127 || ly > 127)
+      return fail(DA_ERR_UNSUPPORTED, "the alignment kernel takes sequences up to 127 residues (pair %lld: %lld and %lld)", (long long)p, (long long)lx,
+                  (long long)ly);
+    need = std::max(need, lx + ly);
+  }
+  if (ops_out && ld_ops < need)
+    return fail(DA_ERR_BAD_ARG, "ld_ops = %lld is smaller than the longest listed len(x) + len(y) = %lld", (long long)ld_ops, (long long)need);
+  {
+    const std::vector<int32_t> bx = nw_first_bad(x_residues, x_offsets, m), by = nw_first_bad(y_residues, y_offsets, n);
+    for (int64_t p = 0; p < pairs; ++p) {
+      const int64_t i = xi(p), j = yj(p);
+      if (x_offsets[i + 1] == x_offsets[i]) continue;                                   // no row runs
+      const uint8_t *s1 = x_residues + x_offsets[i], *s2 = y_residues + y_offsets[j];
+      if (bx[(size_t)i] == 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)s1[0]);
+      if (by[(size_t)j] >= 0) return fail(DA_ERR_BAD_RESIDUE_SEQ2, "Invalid amino acid in sequence2: %c", (char)s2[by[(size_t)j]]);
+      if (bx[(size_t)i] > 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)s1[bx[(size_t)i]]);
+    }
+  }
+  if ((rc = require_device()) != DA_OK) return rc;
+  NwCodes nx, ny;
+  if ((rc = nx.upload(x_residues, x_offsets, m, x_total)) != DA_OK || (rc = ny.upload(y_residues, y_offsets, n, y_total)) != DA_OK) return rc;
+  DevBuf dpx, dpy, dlen, dmt, dsc, dops, work;
+  const size_t ibytes = (size_t)pairs * sizeof(int32_t);
+  if (pair_x) {
+    if ((rc = dpx.alloc(ibytes)) != DA_OK || (rc = dpy.alloc(ibytes)) != DA_OK) return rc;
+    DA_HIP_TRY(hipMemcpy(dpx.p, pair_x, ibytes, hipMemcpyHostToDevice));
+    DA_HIP_TRY(hipMemcpy(dpy.p, pair_y, ibytes, hipMemcpyHostToDevice));
+  }
+  if ((rc = dlen.alloc(ibytes)) != DA_OK || (rc = dmt.alloc(ibytes)) != DA_OK || (rc = dsc.alloc(ibytes)) != DA_OK) return rc;
+  // blocks of pairs: workspace + ops bytes of a block within DYNAALIGN_BLOCK_BYTES (half of the free memory without it), at most 2^19 pairs
+  const size_t per_pair = nw_align_workspace_bytes(64) / 64 + (ops_out ? (size_t)ld_ops : 0);
+  const int64_t blk = std::min<int64_t>(std::min<int64_t>(block_rows(1, per_pair), (int64_t)1 << 19), ceil_div(pairs, 64) * 64);
+  const size_t wbytes = nw_align_workspace_bytes(blk);
+  if ((rc = work.alloc(wbytes)) != DA_OK) return rc;
+  if (ops_out && (rc = dops.alloc((size_t)blk * (size_t)ld_ops)) != DA_OK) return rc;
+  for (int64_t b0 = 0; b0 < pairs; b0 += blk) {
+    const int64_t cnt = std::min(blk, pairs - b0);
+    rc = launch_nw_align(nx.codes.as<uint8_t>(), nx.in.off.as<int64_t>(), m, ny.codes.as<uint8_t>(), ny.in.off.as<int64_t>(), n,
+                         pair_x ? dpx.as<int32_t>() + b0 : nullptr, pair_x ? dpy.as<int32_t>() + b0 : nullptr, b0, cnt, mid, gap_open, gap_ext,
+                         ops_out ? dops.as<uint8_t>() : nullptr, ld_ops, dlen.as<int32_t>() + b0, dmt.as<int32_t>() + b0, dsc.as<int32_t>() + b0, work.p,
+                         wbytes, nullptr);
+    if (rc != DA_OK) return rc;
+    if (ops_out) DA_HIP_TRY(hipMemcpy(ops_out + (size_t)b0 * (size_t)ld_ops, dops.p, (size_t)cnt * (size_t)ld_ops, hipMemcpyDeviceToHost));
+  }
+  if (len_out) DA_HIP_TRY(hipMemcpy(len_out, dlen.p, ibytes, hipMemcpyDeviceToHost));
+  if (matches_out) DA_HIP_TRY(hipMemcpy(matches_out, dmt.p, ibytes, hipMemcpyDeviceToHost));
+  if (score_out) DA_HIP_TRY(hipMemcpy(score_out, dsc.p, ibytes, hipMemcpyDeviceToHost));
+  return sync_or_fail("the alignment kernel failed");
+}
+
+
 // ---- two sets, threshold form: the entries of the rectangle that pass a threshold as a sorted edge list (rect_edges_kernels.hip) ---------
 static int rect_block_check(const void *a, const void *b, const void *c, int64_t rows, int64_t n, int64_t ld, int nbins) {
   if (rows < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");

@@ -328,6 +328,13 @@ int launch_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, 
 int launch_edge_values(const uint16_t *d_key, int64_t count, int n_hash, double *d_w, hipStream_t stream);
 // d_out[r] = d_in[r] + base for r < count (a block's row pointers placed into the row pointers of the whole rectangle)
 int launch_rowptr_offset(const int64_t *d_in, int64_t count, int64_t base, int64_t *d_out, hipStream_t stream);
+// nw_align_kernels.hip: the alignment path of listed pairs (da_dev_nw_align_pairs), one lane per pair; entries [pair_base, pair_base + pairs) of the
+// lists (NULL lists: pair p is x[p] against y[p]); output pointers are those of entry pair_base.  Launches as many pairs as the workspace holds at a time.
+size_t nw_align_workspace_bytes(int64_t pairs);
+int launch_nw_align(const uint8_t *d_x_codes, const int64_t *d_x_off, int64_t m, const uint8_t *d_y_codes, const int64_t *d_y_off, int64_t n,
+                    const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pair_base, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
+                    uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, void *d_work, size_t work_bytes,
+                    hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

@@ -219,6 +219,52 @@ def nw_rect(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row
     return out
 
 
+def nw_align_workspace_bytes(pairs):
+    return int(_capi.load().da_nw_align_workspace_bytes(int(pairs)))
+
+
+def nw_align_pairs(dx, dy, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, pair_x=None, pair_y=None, ops=True, ld_ops=None, work=None):
+    """The alignment paths of listed pairs on the device (da_dev_nw_align_pairs): pair p aligns dx[pair_x[p]] as sequence1 with
+    dy[pair_y[p]] as sequence2; without lists pair p is dx[p] with dy[p].  dx.codes / dy.codes must be filled (nw_encode; dx may be dy);
+    pair_x / pair_y: int32 device tensors.  Returns ``(ops, length, matches, score)``: ops a (pairs, ld_ops) uint8 tensor of 'D' / 'U' /
+    'L' bytes, 0 past a row's length (None with ops=False), the others int32 tensors.  ld_ops defaults to dx.max_len + dy.max_len.
+    Nothing is checked against the lists here: a pair the kernel cannot take (an index outside its set, more than 127 residues) gets
+    length -1.  work: a uint8 device tensor of at least nw_align_workspace_bytes(64) bytes (allocated if None)."""
+    lib = _capi.load()
+    if dx.codes is None or dy.codes is None:
+        raise ValueError("call nw_encode on both sets first")
+    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
+    if mid < 0:
+        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    if (pair_x is None) != (pair_y is None):
+        raise ValueError("pair_x and pair_y must both be given or both be None")
+    dev = dx.residues.device
+    if pair_x is None:
+        if dx.n != dy.n:
+            raise ValueError("without pair lists, dx and dy must hold the same number of sequences (got %d and %d)" % (dx.n, dy.n))
+        pairs = dx.n
+    else:
+        _require_cuda(pair_x, "pair_x")
+        _require_cuda(pair_y, "pair_y")
+        if pair_x.dtype != torch.int32 or pair_y.dtype != torch.int32 or pair_x.numel() != pair_y.numel():
+            raise ValueError("pair_x and pair_y must be int32 tensors of the same length")
+        pair_x, pair_y = pair_x.contiguous(), pair_y.contiguous()
+        pairs = pair_x.numel()
+    if ld_ops is None:
+        ld_ops = max(dx.max_len + dy.max_len, 1)
+    ops_t = torch.empty((max(pairs, 1), int(ld_ops)), dtype=torch.uint8, device=dev) if ops else None
+    ln = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
+    mt = torch.empty_like(ln)
+    sc = torch.empty_like(ln)
+    if work is None:
+        work = torch.empty(max(nw_align_workspace_bytes(min(max(pairs, 64), 1 << 19)), 16), dtype=torch.uint8, device=dev)
+    _call(lib.da_dev_nw_align_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n,
+          None if pair_x is None else pair_x.data_ptr(), None if pair_y is None else pair_y.data_ptr(), pairs, mid, int(gap_open), int(gap_ext),
+          None if ops_t is None else ops_t.data_ptr(), int(ld_ops), ln.data_ptr(), mt.data_ptr(), sc.data_ptr(), work.data_ptr(),
+          work.numel(), _stream())
+    return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
+
+
 def symmetrize(mat, n, kind=DA_OUT_F64):
     _call(_capi.load().da_dev_symmetrize, mat.data_ptr(), n, mat.stride(0), kind, _stream())
     return mat

@@ -18,6 +18,10 @@ and the threshold forms of those (the entries that pass a threshold as a sorted 
     similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, threshold=None)
     similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, threshold=None)
 
+and the alignment itself for listed pairs (which residue sits opposite which: the path the reference's traceback walks)
+
+    nw_align(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, pairs=None, ops=True)
+
 Same names, argument order, defaults and error texts as the reference; the
 bodies marshal to the C ABI (include/dynaalign.h) exactly as the Rcpp glue in
 r_glue/ does.  Results are dense symmetric n x n float64 matrices with
@@ -302,6 +306,88 @@ def nw_pairs(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, row_begi
                                 _as_int(gapExt, "gapExt"), row_begin, row_end, mt.ctypes.data, ln.ctypes.data,
                                 sc.ctypes.data))
     return mt[:r, :n], ln[:r, :n], sc[:r, :n]
+
+
+class NWAlignment(tuple):
+    """Result of nw_align: a tuple ``(ops, length, matches, score)`` with the same fields as attributes."""
+    __slots__ = ()
+
+    def __new__(cls, ops, length, matches, score):
+        return tuple.__new__(cls, (ops, length, matches, score))
+
+    ops = property(lambda self: self[0])
+    length = property(lambda self: self[1])
+    matches = property(lambda self: self[2])
+    score = property(lambda self: self[3])
+
+
+def nw_align(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, pairs=None, ops=True):
+    """HOW listed pairs align under the reference's affine-gap global alignment (da_nw_align_pairs): pair p aligns ``x[i_idx[p]]`` as
+    sequence1 with ``y[j_idx[p]]`` as sequence2, ``pairs=(i_idx, j_idx)`` (0-based, repeats allowed); without ``pairs`` pair p is
+    ``x[p]`` with ``y[p]`` and ``len(x) == len(y)`` is required (ValueError otherwise).  Returns ``(ops, length, matches, score)``
+    (also as attributes):
+
+        ops      list of str over "DUL", the path from the start of both sequences to their ends -- D: x's residue opposite y's,
+                 U: x's residue opposite a gap, L: a gap opposite y's residue (``nw_align_strings`` renders it) -- or None with ops=False
+        length   int32, len(ops[p]): the reference's alignment_length        matches  int32, D steps with equal residues
+        score    int32, M[m][n] after the fill
+
+    ``matches / length`` is bit for bit ``similarityNW_cross(x, y)[i, j]``.  The path is the one the reference's traceback walks
+    (src/pairwiseSeqAlign.cpp:271-308), ties included.  Sequences have 0 .. 127 residues; errors as similarityNW_cross, raised for the
+    listed sequences only."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    if pairs is None:
+        if m != n:
+            raise ValueError("without pairs, x and y must have the same length (got %d and %d)" % (m, n))
+        px = py = None
+        count = m
+        lens = np.diff(xo) + np.diff(yo)
+    else:
+        i_idx, j_idx = pairs
+        px = np.clip(np.asarray(i_idx, np.int64).ravel(), -1, 2 ** 31 - 1).astype(np.int32)
+        py = np.clip(np.asarray(j_idx, np.int64).ravel(), -1, 2 ** 31 - 1).astype(np.int32)
+        if len(px) != len(py):
+            raise ValueError("pairs must be two index lists of the same length (got %d and %d)" % (len(px), len(py)))
+        count = len(px)
+        # only to size the ops rows: the library checks the indices themselves
+        lens = (np.diff(xo)[np.clip(px, 0, m - 1)] + np.diff(yo)[np.clip(py, 0, n - 1)]) if m > 0 and n > 0 else np.zeros(0, np.int64)
+    ld = int(min(max(int(lens.max()) if len(lens) else 0, 1), 254))
+    buf = np.zeros((max(count, 1), ld), np.uint8) if ops else None
+    ln = np.zeros(max(count, 1), np.int32)
+    mt = np.zeros_like(ln)
+    sc = np.zeros_like(ln)
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    _capi.check(lib.da_nw_align_pairs(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _capi.ptr(px), _capi.ptr(py), count,
+                                      name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), _capi.ptr(buf), ld, ln.ctypes.data,
+                                      mt.ctypes.data, sc.ctypes.data))
+    ln, mt, sc = ln[:count], mt[:count], sc[:count]
+    strings = None
+    if ops:
+        raw = buf.tobytes()
+        strings = [raw[p * ld:p * ld + int(ln[p])].decode("latin-1") for p in range(count)]
+    return NWAlignment(strings, ln, mt, sc)
+
+
+def nw_align_strings(a, b, ops):
+    """The two gapped strings of one alignment path (``nw_align``'s ops for sequence1 ``a`` and sequence2 ``b``): '-' opposite a U
+    (in the second string) or an L (in the first), both of length len(ops).  Host only."""
+    ga, gb = [], []
+    i = j = 0
+    for op in ops:
+        if op == "D":
+            ga.append(a[i]); gb.append(b[j]); i += 1; j += 1
+        elif op == "U":
+            ga.append(a[i]); gb.append("-"); i += 1
+        elif op == "L":
+            ga.append("-"); gb.append(b[j]); j += 1
+        else:
+            raise ValueError("ops holds %r: expected only 'D', 'U', 'L'" % op)
+    if i != len(a) or j != len(b):
+        raise ValueError("ops consumes %d and %d residues, the sequences have %d and %d" % (i, j, len(a), len(b)))
+    return "".join(ga), "".join(gb)
 
 
 def quantile_type7(hist, values, p):

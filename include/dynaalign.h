@@ -49,6 +49,7 @@ extern "C" {
  * (the two-set top-k entry points -- da_similarity_*_cross_topk, da_dev_similarity_mh_cross_topk, da_dev_topk_rows, da_nw_code_ranks -- likewise)
  * (the two-set threshold entry points -- da_similarity_*_cross_edges_begin, da_dev_similarity_mh_cross_edges, da_dev_rect_histogram,
  *  da_dev_threshold_rows_* -- likewise)
+ * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -226,6 +227,46 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
  * matches <= min(length, max_len) -- equal doubles get equal ranks, a larger double a larger rank.  Codes outside that set cannot occur
  * and get rank 0.  *distinct_out (may be NULL): the number of ranks.  Host only; needs no device. */
 int da_nw_code_ranks(int max_len, uint16_t *rank_out, int *distinct_out);
+
+/* ---- the alignment PATH of listed pairs: how x[i] and y[j] align, not only how similar they are ----
+ * Pair p aligns x[pair_x[p]] as sequence1 (length m1) with y[pair_y[p]] as sequence2 (length n2); pair_x == pair_y == NULL means p with p
+ * (then m == n == pairs).  The fill is the reference's (src/pairwiseSeqAlign.cpp:216-281); the decision of cell (i, j), i, j >= 1, is
+ *   D if d >= Ix && d >= Iy (d the diagonal candidate), else U if Ix >= Iy, else L   (:271-279; M[i][j] is overwritten by the winner),
+ * border cells (i, 0) are U and (0, j) are L (:228, :234).  The path starts at (m1, n2) and follows the decisions to (0, 0) -- D to (i-1, j-1),
+ * U to (i-1, j), L to (i, j-1), the reference's traceback (:284-308) -- and is returned in FORWARD order, from (0, 0) to (m1, n2), over the
+ * bytes 'D', 'U', 'L': D puts sequence1[i-1] opposite sequence2[j-1], U puts sequence1[i-1] opposite a gap, L a gap opposite sequence2[j-1].
+ *   ops_out     : [pairs][ld_ops] bytes or NULL; row p holds the path of pair p, bytes past its length are 0
+ *   len_out     : the path's length = the reference's alignment_length          matches_out : its D steps with equal residues = `matches`
+ *   score_out   : M[m1][n2] after the fill (INT32_MIN / 2 when exactly one sequence is empty, 0 when both are)
+ * (each [pairs] int32, any may be NULL).  matches / length are the two operands of similarityNW's divide for calc(x[i], y[j]).
+ * Empty sequences are legal: an all-L or all-U path; length 0 when both are empty.
+ * Validation, before any device is needed, in this order: the matrix name (DA_ERR_BAD_MATRIX); pairs == 0 returns DA_OK and writes
+ * nothing; one NULL and one non-NULL list, the NULL form with m != pairs or n != pairs, an index outside [0, m) / [0, n) -> DA_ERR_BAD_ARG;
+ * a listed sequence of more than 127 residues -> DA_ERR_UNSUPPORTED; ops_out != NULL with ld_ops smaller than the largest
+ * len(x) + len(y) over the listed pairs -> DA_ERR_BAD_ARG; then the residue error the reference's lazy fill would raise first with the pairs
+ * visited p ascending, each pair in calc's own order (seq1[0], every character of seq2, seq1[1], ...: an empty sequence1 checks nothing, an
+ * empty sequence2 still has sequence1 checked; only listed sequences are checked); then DA_ERR_NO_DEVICE.
+ * The device keeps 2 decision bits per cell plus a strip boundary per row in a workspace of da_nw_align_workspace_bytes(pairs) bytes (5 KiB
+ * per pair, in whole wavefronts of 64 pairs); the host call works in blocks of pairs whose workspace and ops bytes fit DYNAALIGN_BLOCK_BYTES
+ * (half of the free device memory without it; at most 2^19 pairs).  Single device. */
+int da_nw_align_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                      const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                      const int32_t *pair_x, const int32_t *pair_y, int64_t pairs,
+                      const char *matrix_name, int gap_open, int gap_ext,
+                      uint8_t *ops_out, int64_t ld_ops,
+                      int32_t *len_out, int32_t *matches_out, int32_t *score_out);
+size_t da_nw_align_workspace_bytes(int64_t pairs);
+/* The same on device pointers, asynchronous on `stream`: codes and offsets of x and y as da_dev_nw_encode leaves them (the two sets may be the
+ * same buffers), device pair lists or NULL, device outputs as above (the ops rows are cleared first).  d_work: at least
+ * da_nw_align_workspace_bytes(64) bytes; a workspace smaller than da_nw_align_workspace_bytes(pairs) is reused by consecutive launches of as
+ * many pairs as it holds.  The lists live on the device, so nothing is validated against them here: a pair the kernel cannot take (an index
+ * outside its set, a sequence of more than 127 residues, ld_ops < len(x) + len(y)) gets length -1, matches -1, score 0 and an empty ops row. */
+int da_dev_nw_align_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, int64_t m,
+                          const uint8_t *d_y_codes, const int64_t *d_y_offsets, int64_t n,
+                          const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pairs,
+                          int matrix_id, int gap_open, int gap_ext,
+                          uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score,
+                          void *d_work, size_t work_bytes, void *stream);
 
 /* ---- device-pointer entry points (bench / multi-GPU sharding) ------------ */
 
