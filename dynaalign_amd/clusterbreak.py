@@ -272,7 +272,7 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
 CONSENSUS_SYMBOLS = "ARNDCQEGHILKMFPSTWYVBZX*-"   # tie order of clusterconsensus among symbols other than the center's
 
 
-def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
+def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4, align_fn=None):
     """One consensus sequence per cluster: the reference's signature (R/clusterbreak.R:309-320), ``df`` being rows of
     ``(sequence, cluster_id)`` -- e.g. ``clusterbreak(...)["clustered_seq"]`` -- and the result a list of ``(cluster_id, consensus)`` in
     first-appearance order of the ids.
@@ -291,9 +291,13 @@ def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
       * the most frequent symbol wins; among tied symbols the center's residue if it is one of them, otherwise the one earliest in
         "ARNDCQEGHILKMFPSTWYVBZX*-"; positions won by '-' are dropped.
 
-    Sequences longer than 127 residues raise the library's error (DA_ERR_UNSUPPORTED)."""
+    ``align_fn`` (a hook in the style of ``clusterbreak``'s ``sim_fn`` / ``cluster_fn``): the alignment call, ``None`` for ``nw_align``.
+    It is called twice as ``align_fn(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=bool)`` and returns what ``nw_align``
+    returns.  With the default, sequences longer than 127 residues raise the library's error (DA_ERR_UNSUPPORTED);
+    ``align_fn=nw_align_long`` takes sequences of up to 1024 residues."""
     import math
-    from .similarity import nw_align
+    if align_fn is None:
+        from .similarity import nw_align as align_fn
     rows = df["clustered_seq"] if isinstance(df, dict) else df
     order, members = [], {}
     for row in rows:
@@ -319,7 +323,7 @@ def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
                     if i != j:
                         pi.append(b + i)
                         pj.append(b + j)
-        r = nw_align(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=False)
+        r = align_fn(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=False)
         at = 0
         for cid in start:
             c = len(members[cid])
@@ -337,7 +341,7 @@ def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
                 if j != center[cid]:
                     pi.append(b + center[cid])
                     pj.append(b + j)
-        r = nw_align(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=True)
+        r = align_fn(pool, pool, matrixName, gapOpen, gapExt, pairs=(pi, pj), ops=True)
     out, at = [], 0
     for cid in order:
         mem = members[cid]

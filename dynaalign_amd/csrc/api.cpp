@@ -368,7 +368,7 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 // How many result rows of n columns the device may hold at once (host-pointer paths): a multiple of 128, at least 128, whatever the
 // number of rows there are.
-int64_t block_rows(int64_t n, size_t bytes_per_elem) {
+size_t block_budget() {
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)8 << 30;
   {
@@ -379,7 +379,10 @@ int64_t block_rows(int64_t n, size_t bytes_per_elem) {
   }
   size_t budget = free_b / 2;
   if (da::config().block_bytes) budget = (size_t)da::config().block_bytes;   // DYNAALIGN_BLOCK_BYTES
-  int64_t rows = (int64_t)(budget / ((size_t)n * bytes_per_elem));
+  return budget;
+}
+int64_t block_rows(int64_t n, size_t bytes_per_elem) {
+  int64_t rows = (int64_t)(block_budget() / ((size_t)n * bytes_per_elem));
   rows = rows / 128 * 128;
   if (rows < 128) rows = 128;
   return rows;
@@ -2534,19 +2537,23 @@ static std::vector<int32_t> nw_first_bad(const uint8_t *res, const int64_t *off,
   return bad;
 }
 
-int da_nw_align_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
-                      const int32_t *pair_x, const int32_t *pair_y, int64_t pairs, const char *matrix_name, int gap_open, int gap_ext,
-                      uint8_t *ops_out, int64_t ld_ops, int32_t *len_out, int32_t *matches_out, int32_t *score_out) {
+// Everything da_nw_align_pairs and da_nw_align_long_pairs check before a device is needed, in the documented order; they differ in the longest
+// sequence they take.  *nothing: pairs == 0 (DA_OK, nothing to write).
+static int nw_align_validate(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                             int64_t n, const int32_t *pair_x, const int32_t *pair_y, int64_t pairs, const char *matrix_name, const uint8_t *ops_out,
+                             int64_t ld_ops, int max_residues, int *mid_out, int64_t *x_total, int64_t *y_total, bool *nothing) {
+  *nothing = false;
   const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
   if (mid < 0) return DA_ERR_BAD_MATRIX;
-  if (pairs == 0) return DA_OK;                          // nothing listed: nothing to write
+  *mid_out = mid;
+  if (pairs == 0) { *nothing = true; return DA_OK; }     // nothing listed: nothing to write
   if (pairs < 0 || m < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative count");
   if ((pair_x == nullptr) != (pair_y == nullptr)) return fail(DA_ERR_BAD_ARG, "pair_x and pair_y must both be given or both be NULL");
   if (!pair_x && (m != pairs || n != pairs)) return fail(DA_ERR_BAD_ARG, "without pair lists pair p is x[p] against y[p]: m == n == pairs");
   if (!x_residues || !y_residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  int64_t x_total, y_total, x_max, y_max;
+  int64_t x_max, y_max;
   int rc;
-  if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
+  if ((rc = check_offsets(x_offsets, m, x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, y_total, &y_max)) != DA_OK) return rc;
   auto xi = [&](int64_t p) { return pair_x ? (int64_t)pair_x[p] : p; };
   auto yj = [&](int64_t p) { return pair_y ? (int64_t)pair_y[p] : p; };
   for (int64_t p = 0; p < pairs; ++p) {
@@ -2556,24 +2563,33 @@ int da_nw_align_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64
   int64_t need = 0;
   for (int64_t p = 0; p < pairs; ++p) {
     const int64_t lx = x_offsets[xi(p) + 1] - x_offsets[xi(p)], ly = y_offsets[yj(p) + 1] - y_offsets[yj(p)];
-    if (lx > 127 || ly > 127)
-      return fail(DA_ERR_UNSUPPORTED, "the alignment kernel takes sequences up to 127 residues (pair %lld: %lld and %lld)", (long long)p, (long long)lx,
-                  (long long)ly);
+    if (lx > max_residues || ly > max_residues)
+      return fail(DA_ERR_UNSUPPORTED, "the alignment kernel takes sequences up to %d residues (pair %lld: %lld and %lld)", max_residues, (long long)p,
+                  (long long)lx, (long long)ly);
     need = std::max(need, lx + ly);
   }
   if (ops_out && ld_ops < need)
     return fail(DA_ERR_BAD_ARG, "ld_ops = %lld is smaller than the longest listed len(x) + len(y) = %lld", (long long)ld_ops, (long long)need);
-  {
-    const std::vector<int32_t> bx = nw_first_bad(x_residues, x_offsets, m), by = nw_first_bad(y_residues, y_offsets, n);
-    for (int64_t p = 0; p < pairs; ++p) {
-      const int64_t i = xi(p), j = yj(p);
-      if (x_offsets[i + 1] == x_offsets[i]) continue;                                   // no row runs
-      const uint8_t *s1 = x_residues + x_offsets[i], *s2 = y_residues + y_offsets[j];
-      if (bx[(size_t)i] == 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)s1[0]);
-      if (by[(size_t)j] >= 0) return fail(DA_ERR_BAD_RESIDUE_SEQ2, "Invalid amino acid in sequence2: %c", (char)s2[by[(size_t)j]]);
-      if (bx[(size_t)i] > 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)s1[bx[(size_t)i]]);
-    }
+  const std::vector<int32_t> bx = nw_first_bad(x_residues, x_offsets, m), by = nw_first_bad(y_residues, y_offsets, n);
+  for (int64_t p = 0; p < pairs; ++p) {
+    const int64_t i = xi(p), j = yj(p);
+    if (x_offsets[i + 1] == x_offsets[i]) continue;                                   // no row runs
+    const uint8_t *s1 = x_residues + x_offsets[i], *s2 = y_residues + y_offsets[j];
+    if (bx[(size_t)i] == 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)s1[0]);
+    if (by[(size_t)j] >= 0) return fail(DA_ERR_BAD_RESIDUE_SEQ2, "Invalid amino acid in sequence2: %c", (char)s2[by[(size_t)j]]);
+    if (bx[(size_t)i] > 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", (char)s1[bx[(size_t)i]]);
   }
+  return DA_OK;
+}
+
+int da_nw_align_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                      const int32_t *pair_x, const int32_t *pair_y, int64_t pairs, const char *matrix_name, int gap_open, int gap_ext,
+                      uint8_t *ops_out, int64_t ld_ops, int32_t *len_out, int32_t *matches_out, int32_t *score_out) {
+  int mid = 0, rc;
+  int64_t x_total = 0, y_total = 0;
+  bool nothing = false;
+  if ((rc = nw_align_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, pair_x, pair_y, pairs, matrix_name, ops_out, ld_ops, 127, &mid,
+                              &x_total, &y_total, &nothing)) != DA_OK || nothing) return rc;
   if ((rc = require_device()) != DA_OK) return rc;
   NwCodes nx, ny;
   if ((rc = nx.upload(x_residues, x_offsets, m, x_total)) != DA_OK || (rc = ny.upload(y_residues, y_offsets, n, y_total)) != DA_OK) return rc;
@@ -2604,6 +2620,119 @@ int da_nw_align_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64
   if (matches_out) DA_HIP_TRY(hipMemcpy(matches_out, dmt.p, ibytes, hipMemcpyDeviceToHost));
   if (score_out) DA_HIP_TRY(hipMemcpy(score_out, dsc.p, ibytes, hipMemcpyDeviceToHost));
   return sync_or_fail("the alignment kernel failed");
+}
+
+// ---- the same for sequences of up to 1024 residues (nw_align_long_kernels.hip): one wavefront per pair --------------------------------------
+size_t da_nw_align_long_workspace_bytes(int64_t pairs, int64_t max_len) { return nw_align_long_workspace_bytes(pairs, max_len); }
+
+int da_dev_nw_align_long_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, int64_t m, const uint8_t *d_y_codes, const int64_t *d_y_offsets,
+                               int64_t n, const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
+                               uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, int64_t max_len, void *d_work,
+                               size_t work_bytes, void *stream) {
+  if (pairs < 0 || m < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (pairs == 0) return DA_OK;
+  if ((d_pair_x == nullptr) != (d_pair_y == nullptr)) return fail(DA_ERR_BAD_ARG, "pair_x and pair_y must both be given or both be NULL");
+  if (!d_pair_x && (m != pairs || n != pairs)) return fail(DA_ERR_BAD_ARG, "without pair lists pair p is x[p] against y[p]: m == n == pairs");
+  if (!d_x_codes || !d_x_offsets || !d_y_codes || !d_y_offsets) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (d_ops && ld_ops < 0) return fail(DA_ERR_BAD_ARG, "negative ld_ops");
+  if (max_len < 0) return fail(DA_ERR_BAD_ARG, "negative max_len");
+  if (d_ops && (!d_work || work_bytes < nw_align_long_slot_bytes(max_len)))
+    return fail(DA_ERR_BAD_ARG, "the alignment workspace holds less than one slot of (max_len + 63) * 256 bytes (%zu bytes; da_nw_align_long_workspace_bytes)",
+                d_work ? work_bytes : (size_t)0);
+  int rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  return launch_nw_align_long(d_x_codes, d_x_offsets, m, d_y_codes, d_y_offsets, n, d_pair_x, d_pair_y, 0, pairs, matrix_id, gap_open, gap_ext, d_ops,
+                              ld_ops, d_len, d_matches, d_score, max_len, d_work, work_bytes, static_cast<hipStream_t>(stream));
+}
+
+int da_nw_align_long_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                           int64_t n, const int32_t *pair_x, const int32_t *pair_y, int64_t pairs, const char *matrix_name, int gap_open, int gap_ext,
+                           uint8_t *ops_out, int64_t ld_ops, int32_t *len_out, int32_t *matches_out, int32_t *score_out) {
+  int mid = 0, rc;
+  int64_t x_total = 0, y_total = 0;
+  bool nothing = false;
+  if ((rc = nw_align_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, pair_x, pair_y, pairs, matrix_name, ops_out, ld_ops, 1024, &mid,
+                              &x_total, &y_total, &nothing)) != DA_OK || nothing) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  NwCodes nx, ny;
+  if ((rc = nx.upload(x_residues, x_offsets, m, x_total)) != DA_OK || (rc = ny.upload(y_residues, y_offsets, n, y_total)) != DA_OK) return rc;
+  // the split: pairs with both sequences within the lane-per-pair kernels' 127 residues go there, every other pair takes a wavefront
+  struct Group { std::vector<int32_t> px, py; std::vector<int64_t> at; };
+  Group g[2];                                              // 0 short, 1 long
+  int64_t long_max = 0;
+  for (int64_t p = 0; p < pairs; ++p) {
+    const int64_t i = pair_x ? (int64_t)pair_x[p] : p, j = pair_y ? (int64_t)pair_y[p] : p;
+    const int64_t lx = x_offsets[i + 1] - x_offsets[i], ly = y_offsets[j + 1] - y_offsets[j];
+    Group &t = g[lx > 127 || ly > 127];
+    if (&t == &g[1]) long_max = std::max(long_max, std::max(lx, ly));
+    t.px.push_back((int32_t)i); t.py.push_back((int32_t)j); t.at.push_back(p);
+  }
+  const size_t budget = block_budget();                    // DYNAALIGN_BLOCK_BYTES, or half of the free memory
+  std::vector<uint8_t> stage;
+  std::vector<int32_t> ibuf;
+  for (int k = 0; k < 2; ++k) {
+    const int64_t cnt_k = (int64_t)g[k].at.size();
+    if (cnt_k == 0) continue;
+    const bool whole = cnt_k == pairs;                     // the listed order is the group's order: results go straight to the caller
+    DevBuf dpx, dpy, dlen, dmt, dsc, dops, work;
+    const size_t ibytes = (size_t)cnt_k * sizeof(int32_t);
+    if ((rc = dpx.alloc(ibytes)) != DA_OK || (rc = dpy.alloc(ibytes)) != DA_OK || (rc = dlen.alloc(ibytes)) != DA_OK ||
+        (rc = dmt.alloc(ibytes)) != DA_OK || (rc = dsc.alloc(ibytes)) != DA_OK) return rc;
+    DA_HIP_TRY(hipMemcpy(dpx.p, g[k].px.data(), ibytes, hipMemcpyHostToDevice));
+    DA_HIP_TRY(hipMemcpy(dpy.p, g[k].py.data(), ibytes, hipMemcpyHostToDevice));
+    // blocks of pairs, as in da_nw_align_pairs: ops rows (and the short kernels' per-pair workspace) of a block within the budget.  The
+    // wavefront kernel's workspace does not grow with the pairs: as many slots as fit half of the budget, at least one.
+    int64_t blk;
+    size_t wbytes = 0;
+    if (k == 0) {
+      const size_t per_pair = nw_align_workspace_bytes(64) / 64 + (ops_out ? (size_t)ld_ops : 0);
+      blk = std::min<int64_t>(std::min<int64_t>(block_rows(1, per_pair), (int64_t)1 << 19), ceil_div(cnt_k, 64) * 64);
+      wbytes = nw_align_workspace_bytes(blk);
+    } else {
+      blk = cnt_k;
+      if (ops_out) {
+        const size_t slot = nw_align_long_slot_bytes(long_max);
+        const int64_t slots = std::max<int64_t>(1, std::min<int64_t>((int64_t)(budget / 2 / slot), cnt_k));
+        wbytes = std::min(nw_align_long_workspace_bytes(cnt_k, long_max), (size_t)slots * slot);
+        blk = std::min<int64_t>(std::min<int64_t>(block_rows(1, 2 * (size_t)std::max<int64_t>(ld_ops, 1)), (int64_t)1 << 19), cnt_k);
+      }
+    }
+    if (wbytes && (rc = work.alloc(wbytes)) != DA_OK) return rc;
+    if (ops_out && (rc = dops.alloc((size_t)blk * (size_t)ld_ops)) != DA_OK) return rc;
+    for (int64_t b0 = 0; b0 < cnt_k; b0 += blk) {
+      const int64_t cnt = std::min(blk, cnt_k - b0);
+      if (k == 0)
+        rc = launch_nw_align(nx.codes.as<uint8_t>(), nx.in.off.as<int64_t>(), m, ny.codes.as<uint8_t>(), ny.in.off.as<int64_t>(), n,
+                             dpx.as<int32_t>() + b0, dpy.as<int32_t>() + b0, b0, cnt, mid, gap_open, gap_ext, ops_out ? dops.as<uint8_t>() : nullptr,
+                             ld_ops, dlen.as<int32_t>() + b0, dmt.as<int32_t>() + b0, dsc.as<int32_t>() + b0, work.p, wbytes, nullptr);
+      else
+        rc = launch_nw_align_long(nx.codes.as<uint8_t>(), nx.in.off.as<int64_t>(), m, ny.codes.as<uint8_t>(), ny.in.off.as<int64_t>(), n,
+                                  dpx.as<int32_t>() + b0, dpy.as<int32_t>() + b0, b0, cnt, mid, gap_open, gap_ext,
+                                  ops_out ? dops.as<uint8_t>() : nullptr, ld_ops, dlen.as<int32_t>() + b0, dmt.as<int32_t>() + b0,
+                                  dsc.as<int32_t>() + b0, long_max, work.p, wbytes, nullptr);
+      if (rc != DA_OK) return rc;
+      if (!ops_out) continue;
+      if (whole) {
+        DA_HIP_TRY(hipMemcpy(ops_out + (size_t)b0 * (size_t)ld_ops, dops.p, (size_t)cnt * (size_t)ld_ops, hipMemcpyDeviceToHost));
+      } else {
+        stage.resize((size_t)cnt * (size_t)ld_ops);
+        DA_HIP_TRY(hipMemcpy(stage.data(), dops.p, stage.size(), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < cnt; ++r)
+          memcpy(ops_out + (size_t)g[k].at[(size_t)(b0 + r)] * (size_t)ld_ops, stage.data() + (size_t)r * (size_t)ld_ops, (size_t)ld_ops);
+      }
+    }
+    int32_t *outs[3] = {len_out, matches_out, score_out};
+    DevBuf *src[3] = {&dlen, &dmt, &dsc};
+    for (int f = 0; f < 3; ++f) {
+      if (!outs[f]) continue;
+      if (whole) { DA_HIP_TRY(hipMemcpy(outs[f], src[f]->p, ibytes, hipMemcpyDeviceToHost)); continue; }
+      ibuf.resize((size_t)cnt_k);
+      DA_HIP_TRY(hipMemcpy(ibuf.data(), src[f]->p, ibytes, hipMemcpyDeviceToHost));
+      for (int64_t r = 0; r < cnt_k; ++r) outs[f][g[k].at[(size_t)r]] = ibuf[(size_t)r];
+    }
+    if ((rc = sync_or_fail("the alignment kernel failed")) != DA_OK) return rc;
+  }
+  return DA_OK;
 }
 
 

@@ -335,6 +335,14 @@ int launch_nw_align(const uint8_t *d_x_codes, const int64_t *d_x_off, int64_t m,
                     const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pair_base, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
                     uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, void *d_work, size_t work_bytes,
                     hipStream_t stream);
+// nw_align_long_kernels.hip: the same for sequences of up to 1024 residues (da_dev_nw_align_long_pairs), one wavefront per pair in one persistent
+// launch; a slot of nw_align_long_slot_bytes(max_len) bytes per wave in flight, none without d_ops.
+size_t nw_align_long_slot_bytes(int64_t max_len);
+size_t nw_align_long_workspace_bytes(int64_t pairs, int64_t max_len);
+int launch_nw_align_long(const uint8_t *d_x_codes, const int64_t *d_x_off, int64_t m, const uint8_t *d_y_codes, const int64_t *d_y_off, int64_t n,
+                         const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pair_base, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
+                         uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, int64_t max_len, void *d_work,
+                         size_t work_bytes, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

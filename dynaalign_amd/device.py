@@ -265,6 +265,56 @@ def nw_align_pairs(dx, dy, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, pair_
     return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
 
 
+def nw_align_long_workspace_bytes(pairs, max_len):
+    return int(_capi.load().da_nw_align_long_workspace_bytes(int(pairs), int(max_len)))
+
+
+def nw_align_long_pairs(dx, dy, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, pair_x=None, pair_y=None, ops=True, ld_ops=None, max_len=None,
+                        work=None):
+    """``nw_align_pairs`` for sequences of up to 1024 residues (da_dev_nw_align_long_pairs): one wavefront per pair, every pair, short
+    ones included.  Arguments and result as ``nw_align_pairs``.  max_len sizes the slots of the workspace (None: the longest sequence of
+    the two sets, from their offsets); a pair with a sequence over max_len, over 1024 residues, an index outside its set or
+    ld_ops < len(x) + len(y) gets length -1.  work: a uint8 device tensor of at least nw_align_long_workspace_bytes(1, max_len) bytes
+    (allocated if None; a smaller one than nw_align_long_workspace_bytes(pairs, max_len) means fewer wavefronts in flight); not needed
+    with ops=False."""
+    lib = _capi.load()
+    if dx.codes is None or dy.codes is None:
+        raise ValueError("call nw_encode on both sets first")
+    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
+    if mid < 0:
+        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    if (pair_x is None) != (pair_y is None):
+        raise ValueError("pair_x and pair_y must both be given or both be None")
+    dev = dx.residues.device
+    if pair_x is None:
+        if dx.n != dy.n:
+            raise ValueError("without pair lists, dx and dy must hold the same number of sequences (got %d and %d)" % (dx.n, dy.n))
+        pairs = dx.n
+    else:
+        _require_cuda(pair_x, "pair_x")
+        _require_cuda(pair_y, "pair_y")
+        if pair_x.dtype != torch.int32 or pair_y.dtype != torch.int32 or pair_x.numel() != pair_y.numel():
+            raise ValueError("pair_x and pair_y must be int32 tensors of the same length")
+        pair_x, pair_y = pair_x.contiguous(), pair_y.contiguous()
+        pairs = pair_x.numel()
+    if max_len is None:
+        max_len = max(int(dx.max_len), int(dy.max_len))
+    max_len = int(max_len)
+    if ld_ops is None:
+        ld_ops = max(dx.max_len + dy.max_len, 1)
+    ops_t = torch.empty((max(pairs, 1), int(ld_ops)), dtype=torch.uint8, device=dev) if ops else None
+    ln = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
+    mt = torch.empty_like(ln)
+    sc = torch.empty_like(ln)
+    if work is None and ops:
+        work = torch.empty(max(nw_align_long_workspace_bytes(pairs, max_len), 16), dtype=torch.uint8, device=dev)
+    _call(lib.da_dev_nw_align_long_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n,
+          None if pair_x is None else pair_x.data_ptr(), None if pair_y is None else pair_y.data_ptr(), pairs, mid, int(gap_open), int(gap_ext),
+          None if ops_t is None else ops_t.data_ptr(), int(ld_ops), ln.data_ptr(), mt.data_ptr(), sc.data_ptr(), max_len,
+          None if work is None else work.data_ptr(), 0 if work is None else work.numel(), _stream())
+    return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
+
+
 def symmetrize(mat, n, kind=DA_OUT_F64):
     _call(_capi.load().da_dev_symmetrize, mat.data_ptr(), n, mat.stride(0), kind, _stream())
     return mat

@@ -21,6 +21,7 @@ and the threshold forms of those (the entries that pass a threshold as a sorted 
 and the alignment itself for listed pairs (which residue sits opposite which: the path the reference's traceback walks)
 
     nw_align(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, pairs=None, ops=True)
+    nw_align_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, pairs=None, ops=True)
 
 Same names, argument order, defaults and error texts as the reference; the
 bodies marshal to the C ABI (include/dynaalign.h) exactly as the Rcpp glue in
@@ -335,6 +336,19 @@ def nw_align(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, pairs=None, o
     ``matches / length`` is bit for bit ``similarityNW_cross(x, y)[i, j]``.  The path is the one the reference's traceback walks
     (src/pairwiseSeqAlign.cpp:271-308), ties included.  Sequences have 0 .. 127 residues; errors as similarityNW_cross, raised for the
     listed sequences only."""
+    return _nw_align_call("da_nw_align_pairs", 254, x, y, matrixName, gapOpen, gapExt, pairs, ops)
+
+
+def nw_align_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, pairs=None, ops=True):
+    """``nw_align`` for sequences of 0 .. 1024 residues (da_nw_align_long_pairs): the same arguments, the same result, the same errors.
+    Listed pairs with both sequences of at most 127 residues run through ``nw_align``'s kernels, every other pair takes one wavefront
+    (``k_nw_align_long``); the results come back in listed order.  The ops rows are as long as the longest listed ``len(x) + len(y)``.
+    ``clusterconsensus(rows, align_fn=nw_align_long)`` builds consensus sequences with it."""
+    return _nw_align_call("da_nw_align_long_pairs", None, x, y, matrixName, gapOpen, gapExt, pairs, ops)
+
+
+def _nw_align_call(entry, ld_cap, x, y, matrixName, gapOpen, gapExt, pairs, ops):
+    """nw_align / nw_align_long: marshal, call ``entry``, cut the ops rows into strings.  ld_cap: upper bound of the ops row length."""
     lib = _capi.load()
     xr, xo = pack_sequences(x)
     yr, yo = pack_sequences(y)
@@ -354,15 +368,17 @@ def nw_align(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, pairs=None, o
         count = len(px)
         # only to size the ops rows: the library checks the indices themselves
         lens = (np.diff(xo)[np.clip(px, 0, m - 1)] + np.diff(yo)[np.clip(py, 0, n - 1)]) if m > 0 and n > 0 else np.zeros(0, np.int64)
-    ld = int(min(max(int(lens.max()) if len(lens) else 0, 1), 254))
+    ld = max(int(lens.max()) if len(lens) else 0, 1)
+    if ld_cap is not None:
+        ld = min(ld, ld_cap)
     buf = np.zeros((max(count, 1), ld), np.uint8) if ops else None
     ln = np.zeros(max(count, 1), np.int32)
     mt = np.zeros_like(ln)
     sc = np.zeros_like(ln)
     name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
-    _capi.check(lib.da_nw_align_pairs(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _capi.ptr(px), _capi.ptr(py), count,
-                                      name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), _capi.ptr(buf), ld, ln.ctypes.data,
-                                      mt.ctypes.data, sc.ctypes.data))
+    _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _capi.ptr(px), _capi.ptr(py), count,
+                                    name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), _capi.ptr(buf), ld, ln.ctypes.data,
+                                    mt.ctypes.data, sc.ctypes.data))
     ln, mt, sc = ln[:count], mt[:count], sc[:count]
     strings = None
     if ops:

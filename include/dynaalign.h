@@ -49,7 +49,7 @@ extern "C" {
  * (the two-set top-k entry points -- da_similarity_*_cross_topk, da_dev_similarity_mh_cross_topk, da_dev_topk_rows, da_nw_code_ranks -- likewise)
  * (the two-set threshold entry points -- da_similarity_*_cross_edges_begin, da_dev_similarity_mh_cross_edges, da_dev_rect_histogram,
  *  da_dev_threshold_rows_* -- likewise)
- * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes -- likewise)
+ * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes and their _long forms -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -267,6 +267,39 @@ int da_dev_nw_align_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, 
                           int matrix_id, int gap_open, int gap_ext,
                           uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score,
                           void *d_work, size_t work_bytes, void *stream);
+
+/* ---- the same for sequences of up to 1024 residues: one wavefront per pair (nw_align_long_kernels.hip) ----
+ * da_nw_align_long_pairs has the contract of da_nw_align_pairs, word for word -- arguments, outputs, the validation order and its texts, the
+ * reference's lazy residue error, pairs == 0, the NULL-list form, the ld_ops check, DA_ERR_NO_DEVICE last -- with one change: the length
+ * refusal (DA_ERR_UNSUPPORTED) is for a listed sequence of more than 1024 residues.  Listed pairs with both sequences of at most 127 residues run
+ * through the lane-per-pair kernels of da_nw_align_pairs, every other pair through k_nw_align_long; results come back in listed order.  The
+ * host call works in blocks of pairs whose ops rows fit DYNAALIGN_BLOCK_BYTES (half of the free device memory without it).  Single device.
+ * k_nw_align_long: the fill is the anti-diagonal sweep of the similarity kernel for 65 .. 1024 residues (lane l owns W columns of sequence2,
+ * W the smallest of 1, 2, 3, 4, 6, 8, 9, 12, 16 with 64 W >= len(sequence2)); length, matches and score come out of its (matches, length)
+ * payload.  With ops it also stores one 32-bit word of 2-bit decisions per lane and step, [step][lane], into the wave's SLOT of
+ * (max_len + 63) * 256 bytes and then walks the pair back itself through a window of steps in LDS.  The grid is persistent: wave s takes pairs
+ * s, s + slots, ... and reuses slot s, so the workspace does not grow with the number of pairs. */
+int da_nw_align_long_pairs(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                           const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                           const int32_t *pair_x, const int32_t *pair_y, int64_t pairs,
+                           const char *matrix_name, int gap_open, int gap_ext,
+                           uint8_t *ops_out, int64_t ld_ops,
+                           int32_t *len_out, int32_t *matches_out, int32_t *score_out);
+/* Bytes for min(pairs, 3072) slots of sequences up to max_len (clamped to 1024) residues: 3072 is the number of wavefronts resident on one
+ * device.  0 for pairs <= 0 or max_len < 0.  Needs no device. */
+size_t da_nw_align_long_workspace_bytes(int64_t pairs, int64_t max_len);
+/* On device pointers, asynchronous on `stream`, arguments as da_dev_nw_align_pairs plus max_len, which sizes the slots.  The lists live on
+ * the device, so EVERY pair goes through the wavefront-per-pair kernel, short ones included.  With d_ops, d_work must hold at least one slot
+ * ((max_len + 63) * 256 bytes, max_len clamped to 1024), else DA_ERR_BAD_ARG; a workspace smaller than
+ * da_nw_align_long_workspace_bytes(pairs, max_len) only means fewer wavefronts in flight.  With d_ops == NULL no decision is stored, no walk
+ * runs and d_work may be NULL.  A pair the kernel cannot take (an index outside its set, a sequence over max_len or over 1024 residues,
+ * ld_ops < len(x) + len(y)) gets length -1, matches -1, score 0 and an empty ops row. */
+int da_dev_nw_align_long_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, int64_t m,
+                               const uint8_t *d_y_codes, const int64_t *d_y_offsets, int64_t n,
+                               const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pairs,
+                               int matrix_id, int gap_open, int gap_ext,
+                               uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score,
+                               int64_t max_len, void *d_work, size_t work_bytes, void *stream);
 
 /* ---- device-pointer entry points (bench / multi-GPU sharding) ------------ */
 
