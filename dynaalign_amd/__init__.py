@@ -16,10 +16,11 @@ from .similarity import (  # noqa: F401
     pack_sequences, quantile_type7, set_option, similarityMH, similarityMH_cross, similarityMH_edges, similarityNW, similarityNW_cross, similarityNW_edges,
     nw_code_ranks, similarityMH_cross_topk, similarityNW_cross_topk, similarityMH_cross_edges, similarityNW_cross_edges,
     NWAlignment, nw_align, nw_align_long, nw_align_strings,
+    nw_value_ranks, similarityNW_edges_long, similarityNW_cross_edges_long,
 )
 
 __all__ = [
     "clusterbreak", "clusterconsensus", "netcluster", "louvain", "louvain_csr", "nw_align", "nw_align_long", "nw_align_strings", "NWAlignment",
-    "similarityMH", "similarityNW", "similarityMH_cross", "similarityNW_cross", "similarityMH_cross_topk", "similarityNW_cross_topk", "similarityMH_cross_edges", "similarityNW_cross_edges", "nw_code_ranks", "similarityMH_edges", "similarityNW_edges", "quantile_type7", "minhash_signatures", "mh_counts", "nw_pairs", "hash_family_seeds",
+    "similarityMH", "similarityNW", "similarityMH_cross", "similarityNW_cross", "similarityMH_cross_topk", "similarityNW_cross_topk", "similarityMH_cross_edges", "similarityNW_cross_edges", "nw_code_ranks", "similarityMH_edges", "similarityNW_edges", "similarityNW_edges_long", "similarityNW_cross_edges_long", "nw_value_ranks", "quantile_type7", "minhash_signatures", "mh_counts", "nw_pairs", "hash_family_seeds",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

@@ -72,6 +72,13 @@ SIGNATURES = {
     "da_dev_threshold_rows_emit": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "da_dev_similarity_mh_cross_edges": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
                                                 _vp]),
+    "da_similarity_nw_edges_long_begin": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _vp, _vp, _vp]),
+    "da_similarity_nw_cross_edges_long_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp]),
+    "da_nw_value_ranks": (_i32, [_i32, _vp, _vp, _vp]),
+    "da_dev_nw_codes_to_ranks": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "da_dev_rank_histogram": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _vp]),
+    "da_dev_threshold_ranks_count": (_i32, [_vp, _i64, _i64, _i64, _u32, _i64, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "da_dev_threshold_ranks_emit": (_i32, [_vp, _i64, _i64, _i64, _u32, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "da_dev_nw_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_last_route": (_i32, [_vp, _vp, _vp, _vp]),
     "da_dev_similarity_mh": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),

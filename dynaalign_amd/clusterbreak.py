@@ -14,11 +14,13 @@ Same argument names, defaults, messages and bookkeeping as the R functions.  Per
     c.index   <- netcluster(pep.sim, ...)                             :222   upper triangle incl. the 1.0 diagonal
     sizes, id.itr (> size_max), id.rm (< size_min), labels "<itr>.<cluster>", recursion   :224-254
 
-Two ways to produce a level's thresholded graph, with identical results:
+Three ways to produce a level's thresholded graph, with identical results:
 
   * ``sim_fn`` (the reference's contract): any function sequences -> dense symmetric matrix.  The three R
     statements above are restated literally in `threshold_edges_dense`.  Works with ``similarityMH`` /
     ``similarityNW`` of this package, or -- in the tests -- with the CPU oracle.
+  * ``edges_fn``: any function sequences -> (threshold, i, j, weight), the same graph as an edge list (``similarityNW_edges_long``: the
+    alignment identity of sequences up to 1024 residues, thresholded on the device).
   * ``session`` (device fast path): a `MinHashSession` keeps the signatures of all sequences in HBM; a level is
     K1b + K2 + histogram + exact type-7 quantile + edge extraction on the index subset (`MinHashSession.edges`),
     and only the surviving edges leave the GPU.  The dense matrix never exists (80 GB at N = 100k).
@@ -169,12 +171,15 @@ class ClusterbreakResult(dict):
 
 
 def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_fn=None, cluster_fn=None,
-                 cluster_wt=True, *, session=None, cluster_seed=0, verbose=False, log=None):
+                 cluster_wt=True, *, session=None, edges_fn=None, cluster_seed=0, verbose=False, log=None):
     """Recursive quantile-threshold + Louvain splitting, reference clusterbreak (R/clusterbreak.R:180-275).
 
     pep        sequences (character vector)
     sim_fn     sequences -> similarity matrix; default = the reference's default, similarityMH(x, k=2, n_hash=50)
     session    a MinHashSession over `pep`: levels then run on the device edge path and sim_fn is not used
+    edges_fn   sequences -> (threshold, i, j, weight), the thresholded graph of a level as an edge list (i <= j, the diagonal included,
+               0-based): called on every level's sequences in place of sim_fn + threshold_edges_dense, e.g.
+               ``lambda s: similarityNW_edges_long(s, thresh_p=0.8)``; a level of fewer than 2 sequences does not call it
     cluster_fn (n, i, j, w, seed=, weights=) -> ids; default `louvain` with resolution 1.05
     cluster_seed  call number c of the recursion clusters with seed cluster_seed + c (the reference draws from
                R's global RNG instead)
@@ -186,7 +191,9 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
         raise ValueError("empty input sequence vector")                                  # :192-194
     if session is not None and session.n != len(pep):
         raise ValueError("session holds %d sequences, pep has %d" % (session.n, len(pep)))
-    if sim_fn is None and session is None:
+    if edges_fn is not None and session is not None:
+        raise ValueError("edges_fn and session both produce a level's edge list: give one of them")
+    if sim_fn is None and session is None and edges_fn is None:
         from .similarity import similarityMH
         sim_fn = lambda x: similarityMH(x, k=2, n_hash=50)                               # noqa: E731  (:185)
     import os
@@ -202,9 +209,12 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
 
     def level_edges(idx):
         m = len(idx)
-        if session is not None:
+        if session is not None or edges_fn is not None:
             if m < 2:                          # quantile(numeric(0)) is NA: nothing is removed, the 1.0 diagonal stays
                 return float("nan"), np.zeros(m, np.int32), np.zeros(m, np.int32), np.ones(m, np.float64)
+            if edges_fn is not None:
+                thr, ei, ej, ew = edges_fn([pep[t] for t in idx])
+                return float(thr), np.asarray(ei, np.int32), np.asarray(ej, np.int32), np.asarray(ew, np.float64)
             return session.edges(idx, thresh_p, sort=False)
         return threshold_edges_dense(sim_fn([pep[t] for t in idx]), thresh_p)
 

@@ -2970,6 +2970,260 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
 }
 
 
+// ---- NW threshold form for sequences of up to 1024 residues: 32-bit keys (nw_edges_long_kernels.hip) ------------------------------------------
+// The value table of the PACK32 codes (matches << 16 | length) of sequences up to max_len residues: the distinct doubles
+// (double)matches / (double)length, ascending, and rank[length * (max_len + 1) + matches] = the dense rank of that value.
+}  // extern "C"  (reopened below)
+namespace {
+struct NwValueTable {
+  int max_len = 0;
+  std::vector<double> values;
+  std::vector<uint32_t> rank;   // (2 * max_len + 1) * (max_len + 1) entries; row length = 0 is unused (rank 0)
+};
+// the table of the last max_len asked for is kept: building it is a sort of up to 2.1e6 doubles
+std::shared_ptr<const NwValueTable> nw_value_table(int max_len) {
+  static std::mutex mu;
+  static std::shared_ptr<const NwValueTable> last;
+  std::lock_guard<std::mutex> g(mu);
+  if (last && last->max_len == max_len) return last;
+  auto t = std::make_shared<NwValueTable>();
+  t->max_len = max_len;
+  const size_t w = (size_t)max_len + 1;
+  std::vector<std::pair<double, uint32_t>> v;
+  v.reserve((size_t)(2 * max_len) * w);
+  for (int ln = 1; ln <= 2 * max_len; ++ln)
+    for (int mt = 0; mt <= std::min(ln, max_len); ++mt)
+      v.emplace_back((double)mt / (double)ln, (uint32_t)((size_t)ln * w + (size_t)mt));   // the divide of nw_ratio / nw_code_values
+  std::sort(v.begin(), v.end());
+  t->rank.assign((size_t)(2 * max_len + 1) * w, 0u);
+  for (const auto &e : v) {
+    if (t->values.empty() || e.first != t->values.back()) t->values.push_back(e.first);
+    t->rank[e.second] = (uint32_t)(t->values.size() - 1);
+  }
+  last = t;
+  return last;
+}
+}  // namespace
+extern "C" {
+
+int da_nw_value_ranks(int max_len, double *values_out, int64_t *n_values_out, uint32_t *rank_out) {
+  if (!n_values_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (max_len < 1 || max_len > 1024) return fail(DA_ERR_BAD_ARG, "max_len must be in 1 .. 1024 (got %d)", max_len);
+  if ((values_out == nullptr) != (rank_out == nullptr)) return fail(DA_ERR_BAD_ARG, "values_out and rank_out must both be given or both be NULL");
+  const auto t = nw_value_table(max_len);
+  *n_values_out = (int64_t)t->values.size();
+  if (!values_out) return DA_OK;                           // size query
+  memcpy(values_out, t->values.data(), t->values.size() * sizeof(double));
+  memcpy(rank_out, t->rank.data(), t->rank.size() * sizeof(uint32_t));
+  return DA_OK;
+}
+
+static int rank_block_check(const void *a, const void *b, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int64_t row_begin, int64_t col_begin) {
+  if (rows < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (!a || !b) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld < n) return fail(DA_ERR_BAD_ARG, "ld (%lld) < n (%lld)", (long long)ld, (long long)n);
+  if (nbins < 1 || nbins > 0x7fffffffLL) return fail(DA_ERR_BAD_ARG, "nbins must be in 1 .. 2^31 - 1 (got %lld)", (long long)nbins);
+  if (row_begin < 0 || col_begin < 0) return fail(DA_ERR_BAD_ARG, "negative block origin");
+  return DA_OK;
+}
+int da_dev_nw_codes_to_ranks(const uint32_t *d_codes, int64_t rows, int64_t n, int64_t ld, int max_len, const uint32_t *d_rank, uint32_t *d_out,
+                             int64_t ld_out, void *stream) {
+  int rc;
+  if ((rc = rank_block_check(d_codes, d_rank, rows, n, ld, 1, 0, 0)) != DA_OK) return rc;
+  if (!d_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld_out < n) return fail(DA_ERR_BAD_ARG, "ld (%lld) < n (%lld)", (long long)ld_out, (long long)n);
+  if (max_len < 1 || max_len > 1024) return fail(DA_ERR_BAD_ARG, "max_len must be in 1 .. 1024 (got %d)", max_len);
+  return launch_nw_codes_to_ranks(d_codes, rows, n, ld, max_len, d_rank, d_out, ld_out, static_cast<hipStream_t>(stream));
+}
+int da_dev_rank_histogram(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, uint64_t *d_hist, int triangle,
+                          int64_t row_begin, int64_t col_begin, void *stream) {
+  int rc;
+  if ((rc = rank_block_check(d_keys, d_hist, rows, n, ld, nbins, row_begin, col_begin)) != DA_OK) return rc;
+  return launch_rank_histogram(d_keys, rows, n, ld, nbins, reinterpret_cast<unsigned long long *>(d_hist), triangle != 0, row_begin, col_begin,
+                               static_cast<hipStream_t>(stream));
+}
+int da_dev_threshold_ranks_count(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, int triangle,
+                                 int64_t row_begin, int64_t col_begin, int64_t *d_rowptr, void *d_work, size_t work_bytes, void *stream) {
+  int rc;
+  if ((rc = rank_block_check(d_keys, d_rowptr, rows, n, ld, nbins, row_begin, col_begin)) != DA_OK) return rc;
+  if (!d_work) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_threshold_ranks_count(d_keys, rows, n, ld, r_min, nbins, triangle != 0, row_begin, col_begin, d_rowptr, d_work, work_bytes,
+                                      static_cast<hipStream_t>(stream));
+}
+int da_dev_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, int triangle,
+                                int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out, int64_t capacity,
+                                void *stream) {
+  int rc;
+  if ((rc = rank_block_check(d_keys, d_rowptr, rows, n, ld, nbins, row_begin, col_begin)) != DA_OK) return rc;
+  if (capacity < 0) return fail(DA_ERR_BAD_ARG, "negative capacity");
+  if (capacity > 0 && (!d_j || !d_key_out)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_threshold_ranks_emit(d_keys, rows, n, ld, r_min, nbins, triangle != 0, row_begin, col_begin, d_rowptr, d_j, d_key_out, capacity,
+                                     static_cast<hipStream_t>(stream));
+}
+
+// Rows [0, m) of an NW problem thresholded block by block on value ranks.  square: the problem is the n x n matrix of one set (m == n), a
+// block holds rows [b0, b1) against columns [b0, n), the histogram takes the strict upper triangle and the edges the triangle with the
+// diagonal; otherwise it is the m x n rectangle.  compute(b0, b1, c0, d, ld, whole) writes the PACK32 codes of rows [b0, b1), columns from c0
+// on, to d (`whole`: the block is the entire square -- the symmetric sweep fills it at half the DP).  Quantile form: a first pass of compute
+// + ranks + histogram gives the threshold; a single block is then kept, several are computed again.  Per block: ranks, the per-row counts
+// and their scan, the 8-byte total read back, the ordered emit, and the kept (column, rank) pairs to the handle's host vectors, w =
+// values[rank].  Synchronises the stream.
+typedef std::function<int(int64_t, int64_t, int64_t, void *, int64_t, bool)> RankCompute;
+static int rank_threshold_blocks(int64_t m, int64_t n, bool square, int max_len, double thresh, bool is_quantile, hipStream_t stream,
+                                 const RankCompute &compute, EdgeSet &es, int64_t *n_edges_out) {
+  const auto table = nw_value_table(max_len);
+  const std::vector<double> &values = table->values;
+  const int64_t nbins = (int64_t)values.size();
+  const int64_t ld = (n + 3) / 4 * 4;
+  // rows per block: a multiple of 8 (the tile of the wavefront kernels), at least 8 -- a row of long sequences is a lot of DP, so the
+  // blocks follow the budget closely instead of block_rows' 128-row units
+  const int64_t blk = std::min(std::max<int64_t>((int64_t)(block_budget() / ((size_t)ld * sizeof(uint32_t))) / 8 * 8, 8), m);
+  const bool whole = square && blk >= m;
+  const size_t wb = threshold_rows_workspace_bytes(blk);
+  DevBuf d, drank, rowptr, work, hist;
+  int rc;
+  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint32_t))) != DA_OK || (rc = drank.alloc(table->rank.size() * sizeof(uint32_t))) != DA_OK ||
+      (rc = rowptr.alloc((size_t)(blk + 1) * 8)) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpyAsync(drank.p, table->rank.data(), table->rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  auto ranks_of = [&](int64_t b0, int64_t b1) -> int {    // the block's codes, then its ranks in place
+    const int64_t c0 = square ? b0 : 0;
+    int rc2;
+    if ((rc2 = compute(b0, b1, c0, d.p, ld, whole)) != DA_OK) return rc2;
+    return launch_nw_codes_to_ranks(d.as<uint32_t>(), b1 - b0, n - c0, ld, max_len, drank.as<uint32_t>(), d.as<uint32_t>(), ld, stream);
+  };
+  double thr = thresh;
+  bool have_block = false;
+  if (is_quantile) {
+    if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;
+    DA_HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)nbins * 8, stream));
+    for (int64_t b0 = 0; b0 < m; b0 += blk) {
+      const int64_t b1 = std::min(m, b0 + blk), c0 = square ? b0 : 0;
+      if ((rc = ranks_of(b0, b1)) != DA_OK ||
+          (rc = launch_rank_histogram(d.as<uint32_t>(), b1 - b0, n - c0, ld, nbins, hist.as<unsigned long long>(), square, b0, c0, stream)) != DA_OK)
+        return rc;
+    }
+    std::vector<uint64_t> h((size_t)nbins);
+    DA_HIP_TRY(hipMemcpyAsync(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+    hist.release();
+    if ((rc = da_quantile_type7(h.data(), values.data(), (int)nbins, thresh, &thr)) != DA_OK) return rc;   // ranks ARE the ascending value order
+    have_block = blk >= m;
+  }
+  // kept: value >= threshold and value > 0, i.e. rank >= max(r_thr, 1), r_thr the smallest rank whose value is >= threshold
+  const int64_t r_thr = std::lower_bound(values.begin(), values.end(), thr) - values.begin();
+  const uint32_t r_min = (uint32_t)std::max<int64_t>(r_thr, 1);
+  int64_t base = 0;
+  std::vector<int64_t> rp;
+  std::vector<uint32_t> key;
+  for (int64_t b0 = 0; b0 < m; b0 += blk) {
+    const int64_t b1 = std::min(m, b0 + blk), rows = b1 - b0, c0 = square ? b0 : 0;
+    if (!have_block && (rc = ranks_of(b0, b1)) != DA_OK) return rc;
+    if ((rc = launch_threshold_ranks_count(d.as<uint32_t>(), rows, n - c0, ld, r_min, nbins, square, b0, c0, rowptr.as<int64_t>(), work.p, wb,
+                                           stream)) != DA_OK) return rc;
+    int64_t total = 0;
+    DA_HIP_TRY(hipMemcpyAsync(&total, rowptr.as<int64_t>() + rows, 8, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+    if (total <= 0) continue;
+    DevBuf dj, dkey;
+    if ((rc = dj.alloc((size_t)total * 4)) != DA_OK || (rc = dkey.alloc((size_t)total * 4)) != DA_OK) return rc;
+    if ((rc = launch_threshold_ranks_emit(d.as<uint32_t>(), rows, n - c0, ld, r_min, nbins, square, b0, c0, rowptr.as<int64_t>(), dj.as<int32_t>(),
+                                          dkey.as<uint32_t>(), total, stream)) != DA_OK) return rc;
+    const size_t at = (size_t)base, end = (size_t)(base + total);
+    es.i.resize(end); es.j.resize(end); es.w.resize(end);
+    rp.resize((size_t)rows + 1);
+    key.resize((size_t)total);
+    DA_HIP_TRY(hipMemcpyAsync(rp.data(), rowptr.p, (size_t)(rows + 1) * 8, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipMemcpyAsync(es.j.data() + at, dj.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipMemcpyAsync(key.data(), dkey.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+    for (int64_t r = 0; r < rows; ++r)
+      for (int64_t e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) es.i[at + (size_t)e] = (int32_t)(b0 + r);
+    for (int64_t e = 0; e < total; ++e) {
+      es.j[at + (size_t)e] += (int32_t)c0;                 // the emit's columns are local to the block
+      es.w[at + (size_t)e] = values[key[(size_t)e]];
+    }
+    base += total;
+  }
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  es.threshold = thr;
+  *n_edges_out = base;
+  return DA_OK;
+}
+
+// da_similarity_nw_edges_begin for sequences of up to 1024 residues: the same validation, the same result
+int da_similarity_nw_edges_long_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                                      double thresh_p, da_edges **handle_out, double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    const int mid = da_matrix_id(matrix_name);  // reference :338 -> :190-206, before anything else
+    if (mid < 0) return DA_ERR_BAD_MATRIX;
+    if (!residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    if (n < 2) return fail(DA_ERR_BAD_ARG, "the threshold is a quantile of the strict upper triangle: need >= 2 sequences");
+    if (!(thresh_p >= 0.0 && thresh_p <= 1.0)) return fail(DA_ERR_BAD_ARG, "thresh_p must be in [0, 1]");
+    int64_t total, max_len;
+    int rc;
+    if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+    if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
+    for (int64_t i = 0; i < n; ++i)
+      if (offsets[i + 1] == offsets[i])
+        return fail(DA_ERR_UNSUPPORTED, "sequence %lld is empty: its similarities are 0/0 = NaN and R's quantile() refuses NaN",
+                    (long long)(i + 1));
+    if (max_len > 1024) return fail(DA_ERR_UNSUPPORTED, "the long NW edge list works on 32-bit value ranks: sequences up to 1024 residues");
+    if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "too many sequences");
+    if ((rc = require_device()) != DA_OK) return rc;
+    NwCodes nw;
+    if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+    return rank_threshold_blocks(n, n, true, (int)max_len, thresh_p, true, nullptr,
+                                 [&](int64_t b0, int64_t b1, int64_t c0, void *d, int64_t ld, bool whole) {
+                                   if (whole)   // the entire square in one block: the symmetric sweep computes every pair once and mirrors it
+                                     return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, true,
+                                                      DA_OUT_PACK32, d, ld, nullptr, 0, nullptr);
+                                   return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, false,
+                                                    DA_OUT_PACK32, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c0, n);
+                                 }, es, n_edges);
+  });
+}
+
+// da_similarity_nw_cross_edges_begin for sequences of up to 1024 residues
+int da_similarity_nw_cross_edges_long_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                            const int64_t *y_offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext, double thresh,
+                                            int thresh_is_quantile, da_edges **handle_out, double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+    if (mid < 0) return DA_ERR_BAD_MATRIX;
+    int rc;
+    if (m <= 0 || n <= 0) {                                // an empty rectangle: no edges; it has no quantile
+      if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+      if (thresh_is_quantile) return fail(DA_ERR_BAD_ARG, "quantile of an empty set");
+      es.threshold = thresh;
+      *n_edges = 0;
+      return DA_OK;
+    }
+    if (!x_residues || !y_residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int64_t x_total, y_total, x_max, y_max;
+    if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
+    if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
+    if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+    for (int64_t i = 0; i < m + n; ++i) {
+      const int64_t *o = i < m ? x_offsets + i : y_offsets + (i - m);
+      if (o[1] == o[0])
+        return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in a quantile",
+                    (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y");
+    }
+    const int64_t max_len = std::max(x_max, y_max);
+    if (max_len > 1024) return fail(DA_ERR_UNSUPPORTED, "the long NW two-set edge list works on 32-bit value ranks: sequences up to 1024 residues");
+    if (m > 0x7ffffff0LL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "too many sequences");
+    if ((rc = require_device()) != DA_OK) return rc;
+    NwCodes nw;
+    if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
+    return rank_threshold_blocks(m, n, false, (int)max_len, thresh, thresh_is_quantile != 0, nullptr,
+                                 [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {   // rows of x against columns of y: x[i] is sequence1
+                                   return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, false,
+                                                    DA_OUT_PACK32, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
+                                 }, es, n_edges);
+  });
+}
+
+
 // ------------------------------------------------- multi-device host entry points (SURVEY 8(b) da_opts, 8(e))
 // ONE process drives several GPUs: a host thread per device (hipSetDevice is per thread), every device holds all
 // sequences and rebuilds all signatures itself (2 MB in), the pair space is split, and every device copies ITS

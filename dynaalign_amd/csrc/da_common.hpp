@@ -325,6 +325,19 @@ int launch_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n,
                                 void *d_work, size_t work_bytes, hipStream_t stream);
 int launch_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, const int64_t *d_rowptr,
                                int32_t *d_j, uint16_t *d_key_out, int64_t capacity, hipStream_t stream);
+int threshold_rows_scan(void *d_work, size_t work_bytes, int64_t rows, int64_t *d_rowptr, hipStream_t stream);
+// nw_edges_long_kernels.hip: the same steps on blocks of uint32 keys -- PACK32 codes (matches << 16 | length) to value ranks through the table of
+// da_nw_value_ranks, the rank histogram, and the ordered compaction of the keys >= r_min.  triangle: the block is rows [row_begin, ...) x
+// columns [col_begin, ...) of a square problem; the histogram counts global column > global row, count / emit keep global column >= global row.
+int launch_nw_codes_to_ranks(const uint32_t *d_codes, int64_t rows, int64_t n, int64_t ld, int max_len, const uint32_t *d_rank, uint32_t *d_out,
+                             int64_t ld_out, hipStream_t stream);
+int launch_rank_histogram(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, unsigned long long *d_hist, bool triangle,
+                          int64_t row_begin, int64_t col_begin, hipStream_t stream);
+int launch_threshold_ranks_count(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, bool triangle,
+                                 int64_t row_begin, int64_t col_begin, int64_t *d_rowptr, void *d_work, size_t work_bytes, hipStream_t stream);
+int launch_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, bool triangle,
+                                int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out, int64_t capacity,
+                                hipStream_t stream);
 int launch_edge_values(const uint16_t *d_key, int64_t count, int n_hash, double *d_w, hipStream_t stream);
 // d_out[r] = d_in[r] + base for r < count (a block's row pointers placed into the row pointers of the whole rectangle)
 int launch_rowptr_offset(const int64_t *d_in, int64_t count, int64_t base, int64_t *d_out, hipStream_t stream);

@@ -189,6 +189,15 @@ size_t threshold_rows_workspace_bytes(int64_t rows) {
   return up256((size_t)(rows + 1) * 8) + up256(temp) + 256;
 }
 
+// d_rowptr = exclusive scan of the rows + 1 per-row counts at the head of the workspace (the last one 0); the scan's scratch follows them
+int threshold_rows_scan(void *d_work, size_t work_bytes, int64_t rows, int64_t *d_rowptr, hipStream_t stream) {
+  long long *cnt = static_cast<long long *>(d_work);
+  char *w = static_cast<char *>(d_work) + up256((size_t)(rows + 1) * 8);
+  size_t temp = work_bytes - up256((size_t)(rows + 1) * 8);
+  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w, temp, cnt, reinterpret_cast<long long *>(d_rowptr), (int)(rows + 1), stream));
+  return DA_OK;
+}
+
 int launch_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, int64_t *d_rowptr,
                                 void *d_work, size_t work_bytes, hipStream_t stream) {
   if (rows <= 0) return DA_OK;
@@ -198,16 +207,13 @@ int launch_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n,
   if (rows + 1 > 0x7fffffffLL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
   if (!d_work || work_bytes < threshold_rows_workspace_bytes(rows)) return fail(DA_ERR_BAD_ARG, "threshold rows: workspace too small");
   long long *cnt = static_cast<long long *>(d_work);
-  char *w = static_cast<char *>(d_work) + up256((size_t)(rows + 1) * 8);
-  size_t temp = work_bytes - up256((size_t)(rows + 1) * 8);
   DA_HIP_TRY(hipMemsetAsync(cnt + rows, 0, 8, stream));
   if (n <= 1024)
     hipLaunchKernelGGL(k_threshold_count<64>, dim3((unsigned)rows), dim3(64), 0, stream, d_keys, n, ld, d_keep, nbins, cnt);
   else
     hipLaunchKernelGGL(k_threshold_count<RE_THREADS>, dim3((unsigned)rows), dim3(RE_THREADS), 0, stream, d_keys, n, ld, d_keep, nbins, cnt);
   DA_HIP_TRY(hipGetLastError());
-  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w, temp, cnt, reinterpret_cast<long long *>(d_rowptr), (int)(rows + 1), stream));
-  return DA_OK;
+  return threshold_rows_scan(d_work, work_bytes, rows, d_rowptr, stream);
 }
 
 int launch_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, const int64_t *d_rowptr,

@@ -526,6 +526,61 @@ def threshold_rows(keys, keep, capacity=None):
     return rowptr, j[:cap], key[:cap]
 
 
+def _rank_block(keys):
+    """(rows, n, ld) of a block of uint32 keys held in an int32 tensor of shape (rows, n), any row stride and base address"""
+    _require_cuda(keys, "keys")
+    assert keys.dim() == 2 and keys.dtype == torch.int32 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
+    rows, n = int(keys.shape[0]), int(keys.shape[1])
+    return rows, n, (int(keys.stride(0)) if rows > 1 else max(n, 1))
+
+
+def nw_codes_to_ranks(codes, rank, max_len, out=None):
+    """The value ranks of a block of PACK32 codes (matches << 16 | length; an int32 tensor (rows, n)) through ``rank``, the table of
+    ``nw_value_ranks(max_len)`` as a flat int32 tensor on the device: a code outside the table's domain gets rank 0
+    (da_dev_nw_codes_to_ranks).  ``out=None`` returns a new tensor, ``out=codes`` converts in place."""
+    rows, n, ld = _rank_block(codes)
+    _require_cuda(rank, "rank table")
+    ml = int(max_len)
+    assert rank.dtype == torch.int32 and rank.is_contiguous() and rank.numel() == (2 * ml + 1) * (ml + 1)
+    if out is None:
+        out = torch.empty((rows, n), dtype=torch.int32, device=codes.device)
+    orows, on, old = _rank_block(out)
+    assert (orows, on) == (rows, n)
+    _call(_capi.load().da_dev_nw_codes_to_ranks, codes.data_ptr(), rows, n, ld, ml, rank.data_ptr(), out.data_ptr(), old, _stream())
+    return out
+
+
+def rank_histogram(keys, nbins, triangle=False, row_begin=0, col_begin=0):
+    """uint64 histogram (int64 tensor of nbins entries) of a block of uint32 keys; keys >= nbins are ignored (da_dev_rank_histogram).
+    triangle: the block is rows row_begin ... x columns col_begin ... of a square problem and only global column > global row counts."""
+    rows, n, ld = _rank_block(keys)
+    hist = torch.zeros(int(nbins), dtype=torch.int64, device=keys.device)
+    _call(_capi.load().da_dev_rank_histogram, keys.data_ptr(), rows, n, ld, int(nbins), hist.data_ptr(), int(bool(triangle)), int(row_begin),
+          int(col_begin), _stream())
+    return hist
+
+
+def threshold_ranks(keys, r_min, nbins, triangle=False, row_begin=0, col_begin=0, capacity=None):
+    """The entries of a block of uint32 keys with r_min <= key < nbins as CSR: (rowptr int64 (rows + 1), j int32, key int32 (uint32 bit
+    pattern)) -- per row the kept columns (local to the block), ascending (da_dev_threshold_ranks_count, then da_dev_threshold_ranks_emit).
+    triangle: only global column >= global row, the diagonal included.  capacity as in ``threshold_rows``."""
+    lib = _capi.load()
+    rows, n, ld = _rank_block(keys)
+    dev = keys.device
+    rowptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+    mask = (int(r_min), int(nbins), int(bool(triangle)), int(row_begin), int(col_begin))
+    if rows > 0:
+        nbytes = int(lib.da_dev_threshold_rows_workspace_bytes(rows))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _call(lib.da_dev_threshold_ranks_count, keys.data_ptr(), rows, n, ld, *mask, rowptr.data_ptr(), work.data_ptr(), nbytes, _stream())
+    cap = int(rowptr[rows].item()) if capacity is None else int(capacity)
+    j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    key = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+    if rows > 0 and cap > 0:
+        _call(lib.da_dev_threshold_ranks_emit, keys.data_ptr(), rows, n, ld, *mask, rowptr.data_ptr(), j.data_ptr(), key.data_ptr(), cap, _stream())
+    return rowptr, j[:cap], key[:cap]
+
+
 def similarity_mh_cross_edges(dx, dy, k, n_hash, seeds, thresh_p=None, threshold=None, capacity=None):
     """The threshold form of similarity_mh_cross on two device-resident sets, one C call (da_dev_similarity_mh_cross_edges):
     (threshold, rowptr int64 (m + 1), j int32, w float64) -- CSR over the rows of x of the entries with R >= threshold and R > 0, columns

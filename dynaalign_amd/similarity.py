@@ -18,6 +18,11 @@ and the threshold forms of those (the entries that pass a threshold as a sorted 
     similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, threshold=None)
     similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, threshold=None)
 
+and the NW threshold forms for sequences of up to 1024 residues (32-bit value ranks on the device in place of the uint16 code)
+
+    similarityNW_edges_long(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8)
+    similarityNW_cross_edges_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, threshold=None)
+
 and the alignment itself for listed pairs (which residue sits opposite which: the path the reference's traceback walks)
 
     nw_align(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, pairs=None, ops=True)
@@ -291,6 +296,21 @@ def nw_code_ranks(max_len=127):
     return out, d.value
 
 
+def nw_value_ranks(max_len=1024):
+    """(values float64[D], rank uint32[2 * max_len + 1, max_len + 1]): the distinct values ``matches / length`` that sequences of up to max_len
+    (1 .. 1024) residues can produce, ascending, and ``rank[length, matches]``, the dense rank of that value -- what the *_edges_long calls
+    order and threshold on (da_nw_value_ranks).  Equal doubles share a rank (128/256 and 150/300); rank 0 is the value 0.0.  Needs no device."""
+    import ctypes
+    lib = _capi.load()
+    ml = int(max_len)
+    d = ctypes.c_int64(0)
+    _capi.check(lib.da_nw_value_ranks(ml, None, ctypes.addressof(d), None))
+    values = np.empty(d.value, np.float64)
+    rank = np.empty((2 * ml + 1, ml + 1), np.uint32)
+    _capi.check(lib.da_nw_value_ranks(ml, values.ctypes.data, ctypes.addressof(d), rank.ctypes.data))
+    return values, rank
+
+
 def nw_pairs(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, row_begin=0, row_end=None):
     """(matches, length, score) int32 arrays for a row block: the integers the
     reference divides at src/pairwiseSeqAlign.cpp:311, plus M[m][n]."""
@@ -462,6 +482,19 @@ def similarityNW_edges(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, t
         res.ctypes.data, off.ctypes.data, n, name, go, ge, float(thresh_p), h, thr, cnt))
 
 
+def similarityNW_edges_long(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8):
+    """``similarityNW_edges`` for sequences of 1 .. 1024 residues (da_similarity_nw_edges_long_begin): the same arguments, the same result,
+    the same errors.  The device thresholds 32-bit value ranks (``nw_value_ranks``) of the packed (matches, length) pairs; the dense matrix
+    never exists.  ``clusterbreak(pep, edges_fn=lambda s: similarityNW_edges_long(s, thresh_p=0.8), thresh_p=0.8)`` clusters with it."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_edges_long_begin(
+        res.ctypes.data, off.ctypes.data, n, name, go, ge, float(thresh_p), h, thr, cnt))
+
+
 def _thresh_args(thresh_p, threshold):
     """(thresh, thresh_is_quantile) of the *_cross_edges_begin calls: a threshold that is not None selects the absolute form"""
     return (float(thresh_p), 1) if threshold is None else (float(threshold), 0)
@@ -495,4 +528,18 @@ def similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, 
     go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
     thresh, is_q = _thresh_args(thresh_p, threshold)
     return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_cross_edges_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name, go, ge, thresh, is_q, h, thr, cnt))
+
+
+def similarityNW_cross_edges_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, *, threshold=None):
+    """``similarityNW_cross_edges`` for sequences of 1 .. 1024 residues (da_similarity_nw_cross_edges_long_begin): the same arguments, the
+    same result, the same errors."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
+    thresh, is_q = _thresh_args(thresh_p, threshold)
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_cross_edges_long_begin(
         xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name, go, ge, thresh, is_q, h, thr, cnt))

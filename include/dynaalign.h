@@ -695,6 +695,66 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
                                      int64_t *d_rowptr, int32_t *d_j, double *d_w, int64_t capacity,
                                      double *threshold_out, int64_t *n_edges_out, void *stream);
 
+/* ---- the NW threshold forms for sequences of up to 1024 residues: 32-bit value ranks in place of the uint16 code ----
+ * da_similarity_nw_edges_long_begin has the contract of da_similarity_nw_edges_begin word for word -- arguments, the da_edges handle, the
+ * validation order and its texts (matrix name, NULL, n < 2, thresh_p, offsets, residues, an empty sequence, DA_ERR_NO_DEVICE last), the result:
+ * threshold = R's type-7 quantile of the strict upper triangle of similarityNW(x), the edges every (i, j), i <= j, diagonal included, with
+ * R >= threshold and R > 0, sorted by (i, j), weights bit for bit -- with ONE change: the length refusal (DA_ERR_UNSUPPORTED) is for a
+ * sequence of more than 1024 residues.  da_similarity_nw_cross_edges_long_begin is da_similarity_nw_cross_edges_begin in the same way (both
+ * forms, the empty-rectangle rules, x[i] is sequence1): 1 .. 1024 residues on both sides.
+ * The DP writes DA_OUT_PACK32 codes (matches << 16 | length) in row blocks -- rows [b0, b1) against columns [b0, n) of the square problem,
+ * or against the columns of y -- of DYNAALIGN_BLOCK_BYTES at 4 bytes per element (half the free device memory without it; a multiple of 8
+ * rows, at least 8); a square problem
+ * that fits one block runs the symmetric sweep, every pair once.  Each code is replaced by the dense rank of its double value
+ * (da_nw_value_ranks: equal values from different codes, 128/256 and 150/300, are ONE rank), and histogram, keep decision and emitted key
+ * work on ranks: threshold = da_quantile_type7(histogram, values); kept = rank >= max(r_thr, 1), r_thr the smallest rank whose value is >=
+ * threshold, so the boundary R == threshold is exact; weight = values[rank].  Quantile form: a problem that fits one block stays resident
+ * between the histogram and the emit pass, one cut into several blocks runs the DP twice; the absolute form makes one pass.  No top-k, no
+ * duplicate route, single device. */
+int da_similarity_nw_edges_long_begin(const uint8_t *residues, const int64_t *offsets, int64_t n,
+                                      const char *matrix_name, int gap_open, int gap_ext, double thresh_p,
+                                      da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+int da_similarity_nw_cross_edges_long_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                            const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                                            const char *matrix_name, int gap_open, int gap_ext, double thresh, int thresh_is_quantile,
+                                            da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+
+/* The value table of the NW codes of sequences up to max_len (1 .. 1024) residues.  Over 1 <= length <= 2 * max_len, 0 <= matches <=
+ * min(length, max_len): values_out[D] = the distinct doubles (double)matches / (double)length, ascending (values_out[0] = 0.0), and
+ * rank_out[length * (max_len + 1) + matches] (uint32, (2 * max_len + 1) * (max_len + 1) entries) = the dense rank of that double: equal
+ * doubles get equal ranks, a larger double a larger rank, rank 0 <=> matches == 0.  Entries outside that set (length 0, matches > length)
+ * are 0.  *n_values_out = D (1 301 496 at 1024).  values_out == rank_out == NULL: size query.  Host only; needs no device. */
+int da_nw_value_ranks(int max_len, double *values_out, int64_t *n_values_out, uint32_t *rank_out);
+
+/* The device pieces, on a block of uint32 keys: `rows` rows of ld >= n keys, read in 16-byte units where a row's address allows it and in
+ * 4-byte units otherwise: every ld and 4-byte-aligned base works.  All are asynchronous on `stream`.  NULL pointers, ld < n, nbins outside
+ * 1 .. 2^31 - 1 and a negative row_begin / col_begin are DA_ERR_BAD_ARG; rows == 0 is DA_OK and touches nothing.
+ * triangle != 0: the block is rows [row_begin, row_begin + rows) x columns [col_begin, col_begin + n) of a square problem and an element's
+ *   global position decides whether it is looked at; triangle == 0: the whole rectangle (row_begin / col_begin unused).
+ * da_dev_nw_codes_to_ranks: d_out[r][c] = d_rank[length * (max_len + 1) + matches] of the PACK32 code d_codes[r][c] (d_rank: the table of
+ *   da_nw_value_ranks(max_len) on the device); a code outside the table's domain (length 0, length > 2 * max_len, matches > max_len, matches
+ *   > length) gets rank 0 and reads nothing.  d_out == d_codes (with ld_out == ld) is allowed.
+ * da_dev_rank_histogram: d_hist[v] += the number of keys equal to v (the caller zeroes uint64 d_hist[nbins]); keys >= nbins are ignored.
+ *   triangle: only elements with global column > global row (the strict upper triangle) are counted.  Equal keys are merged before any
+ *   atomic -- within a wave (one lane adds the count of all lanes holding its key), then in a 4096-slot LDS cache per workgroup that is
+ *   flushed once -- so a block that is mostly one key does not serialise on its bin.
+ * da_dev_threshold_ranks_count: d_rowptr[r] = the number of kept elements in the rows before r (int64, rows + 1 entries; d_rowptr[rows] is
+ *   the block's total); kept: r_min <= key < nbins, and with triangle global column >= global row (the diagonal INCLUDED).  d_work:
+ *   da_dev_threshold_rows_workspace_bytes(rows) bytes.
+ * da_dev_threshold_ranks_emit: for every row its kept columns -- LOCAL to the block, 0 .. n - 1 -- in ASCENDING order at
+ *   d_j[d_rowptr[r] ...] (int32) with their keys in d_key_out (uint32); slots >= capacity are not written.  Same arguments as the count.
+ *   A workgroup per row (one wave for rows of up to 1024 keys), 4 keys per thread per chunk, no output atomic and no sort; a row without
+ *   an edge is not read again, and the part of a row left of the diagonal is not read at all. */
+int da_dev_nw_codes_to_ranks(const uint32_t *d_codes, int64_t rows, int64_t n, int64_t ld, int max_len, const uint32_t *d_rank,
+                             uint32_t *d_out, int64_t ld_out, void *stream);
+int da_dev_rank_histogram(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, uint64_t *d_hist, int triangle,
+                          int64_t row_begin, int64_t col_begin, void *stream);
+int da_dev_threshold_ranks_count(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, int triangle,
+                                 int64_t row_begin, int64_t col_begin, int64_t *d_rowptr, void *d_work, size_t work_bytes, void *stream);
+int da_dev_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, int triangle,
+                                int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out,
+                                int64_t capacity, void *stream);
+
 /* ---- the caller's clustering step (reference R/clusterbreak.R:112-136, netcluster) ------------
  * igraph::cluster_louvain(graph_from_adjacency_matrix(S, mode = "upper", weighted = TRUE),
  *                         weights = E(g)$weight, resolution = 1.05)$membership
