@@ -79,6 +79,12 @@ SIGNATURES = {
     "da_dev_rank_histogram": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _vp]),
     "da_dev_threshold_ranks_count": (_i32, [_vp, _i64, _i64, _i64, _u32, _i64, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
     "da_dev_threshold_ranks_emit": (_i32, [_vp, _i64, _i64, _i64, _u32, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "da_stats_from_histogram": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "da_similarity_mh_stats": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "da_similarity_nw_stats": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
+    "da_similarity_nw_stats_long": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
+    "da_dev_upper_extrema": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "da_dev_upper_extrema32": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "da_dev_nw_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_last_route": (_i32, [_vp, _vp, _vp, _vp]),
     "da_dev_similarity_mh": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
@@ -134,6 +140,16 @@ class DaUniquePlan(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("n", C.c_int64), ("unique", C.c_int64),
                 ("d_uidx", C.c_void_p), ("d_ufirst", C.c_void_p), ("d_ulast", C.c_void_p), ("d_ubytes", C.c_void_p),
                 ("d_uoffsets", C.c_void_p), ("d_minfirst", C.c_void_p), ("d_maxlast", C.c_void_p)]
+
+
+class DaSimilarityStats(C.Structure):
+    """struct da_similarity_stats (include/dynaalign.h)"""
+    _fields_ = [("mean_similarity", C.c_double), ("median_similarity", C.c_double), ("min_similarity", C.c_double),
+                ("max_similarity", C.c_double), ("pairs", C.c_int64), ("most_similar_pair", C.c_int64 * 2),
+                ("least_similar_pair", C.c_int64 * 2), ("most_similar_upper", C.c_int64 * 2), ("least_similar_upper", C.c_int64 * 2)]
+
+
+ROW_EXTREMA_WORDS = 5   # struct da_row_extrema: {min_key, min_col, max_key, max_col, diag_key}, 32 bits each
 
 
 class DaOpts(C.Structure):

@@ -1724,6 +1724,38 @@ int da_quantile_type7(const uint64_t *hist, const double *values, int nbins, dou
   return DA_OK;
 }
 
+// mean, median, min and max of the multiset {values[b] x hist[b]}, values ascending (dynaalign.h): the numbers of the reference's
+// compute_similarity_stats (R/similarity.R:22-25) from a histogram.  The median is R's / numpy's, the plain average of the two middle
+// elements; the mean is one long double sum over the bins.
+int da_stats_from_histogram(const uint64_t *hist, const double *values, int64_t nbins, double *mean_out, double *median_out, double *min_out,
+                            double *max_out) {
+  if (!hist || !values || nbins <= 0) return fail(DA_ERR_BAD_ARG, "bad statistics arguments");
+  uint64_t total = 0;
+  int64_t lo = -1, hi = -1;
+  long double sum = 0.0L;
+  for (int64_t b = 0; b < nbins; ++b) {
+    if (!hist[b]) continue;
+    if (lo < 0) lo = b;
+    hi = b;
+    total += hist[b];
+    sum += (long double)hist[b] * (long double)values[b];
+  }
+  if (total == 0) return fail(DA_ERR_BAD_ARG, "statistics of an empty set");
+  auto at = [&](uint64_t pos) {   // pos: 0-based rank
+    uint64_t cum = 0;
+    for (int64_t b = lo; b <= hi; ++b) {
+      cum += hist[b];
+      if (pos < cum) return values[b];
+    }
+    return values[hi];
+  };
+  if (mean_out) *mean_out = (double)(sum / (long double)total);
+  if (median_out) *median_out = (total & 1) ? at((total - 1) / 2) : (at(total / 2 - 1) + at(total / 2)) / 2.0;
+  if (min_out) *min_out = values[lo];
+  if (max_out) *max_out = values[hi];
+  return DA_OK;
+}
+
 static int nw_validate(const uint8_t *residues, const int64_t *offsets, int64_t n);
 
 // Shared tail of the *_edges entry points: d_cnt is the dense n x n uint16 code matrix, d_hist the
@@ -3221,6 +3253,237 @@ int da_similarity_nw_cross_edges_long_begin(const uint8_t *x_residues, const int
                                                     DA_OUT_PACK32, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
                                  }, es, n_edges);
   });
+}
+
+// ---- summary statistics without the matrix on the host (reference R/similarity.R:11-34; dynaalign.h) ---------------------------------------
+static int extrema_block_check(const void *keys, const void *rec, int64_t rows, int64_t n, int64_t ld, int64_t row_begin, int64_t col_begin) {
+  return rank_block_check(keys, rec, rows, n, ld, 1, row_begin, col_begin);
+}
+int da_dev_upper_extrema(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int64_t row_begin, int64_t col_begin,
+                         da_row_extrema *d_records, void *stream) {
+  int rc;
+  if ((rc = extrema_block_check(d_keys, d_records, rows, n, ld, row_begin, col_begin)) != DA_OK) return rc;
+  return launch_upper_extrema(d_keys, rows, n, ld, d_rank, row_begin, col_begin, d_records, static_cast<hipStream_t>(stream));
+}
+int da_dev_upper_extrema32(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t row_begin, int64_t col_begin,
+                           da_row_extrema *d_records, void *stream) {
+  int rc;
+  if ((rc = extrema_block_check(d_keys, d_records, rows, n, ld, row_begin, col_begin)) != DA_OK) return rc;
+  return launch_upper_extrema32(d_keys, rows, n, ld, row_begin, col_begin, d_records, static_cast<hipStream_t>(stream));
+}
+}  // extern "C"  (reopened below)
+
+namespace {
+// The host side of the statistics: the histogram of the strict upper triangle over value ranks (values ascending, one bin per distinct
+// value) gives the four numbers; the per-row records of k_upper_extrema, rows ascending with GLOBAL columns, give the positions.
+struct StatsFold {
+  std::vector<da_row_extrema> rec;
+  // the records of rows [rec.size(), rec.size() + rows) of the square, as the kernel wrote them for a block whose first column is col_begin
+  void add_block(const da_row_extrema *r, int64_t rows, int64_t col_begin) {
+    for (int64_t i = 0; i < rows; ++i) {
+      da_row_extrema e = r[i];
+      if (e.min_col >= 0) e.min_col += (int32_t)col_begin;
+      if (e.max_col >= 0) e.max_col += (int32_t)col_begin;
+      rec.push_back(e);
+    }
+  }
+  // want_max: positions of the largest rank, else of the smallest.  upper: the first (i, j), i < j, in row-major order holding it.  pair: R's
+  // which(S == v, arr.ind = TRUE)[1, ] -- the first position in column-major order over the whole matrix, which by symmetry is (c, r) for
+  // the first (r, c) in row-major order among the diagonal and the strict upper triangle: going over the rows, r itself when the diagonal
+  // holds v, the row's recorded column when the row's extreme is v.
+  bool positions(bool want_max, uint32_t *rank_out, int64_t upper[2], int64_t pair[2]) const {
+    bool any = false;
+    uint32_t ext = 0;
+    for (const da_row_extrema &e : rec) {
+      if (e.min_col < 0) continue;
+      const uint32_t v = want_max ? e.max_key : e.min_key;
+      if (!any || (want_max ? v > ext : v < ext)) { ext = v; any = true; }
+    }
+    if (!any) return false;
+    bool have_upper = false, have_pair = false;
+    for (size_t r = 0; r < rec.size() && !(have_upper && have_pair); ++r) {
+      const da_row_extrema &e = rec[r];
+      const bool row_has = e.min_col >= 0 && (want_max ? e.max_key : e.min_key) == ext;
+      const int64_t col = want_max ? e.max_col : e.min_col;
+      if (!have_upper && row_has) { upper[0] = (int64_t)r; upper[1] = col; have_upper = true; }
+      if (!have_pair) {
+        if (e.diag_key != 0xFFFFFFFFu && e.diag_key == ext) { pair[0] = pair[1] = (int64_t)r; have_pair = true; }
+        else if (row_has) { pair[0] = col; pair[1] = (int64_t)r; have_pair = true; }
+      }
+    }
+    *rank_out = ext;
+    return have_upper && have_pair;
+  }
+  int finish(const std::vector<uint64_t> &hist, const double *values, int64_t n, da_similarity_stats *out) const {
+    int rc;
+    da_similarity_stats s;
+    memset(&s, 0, sizeof s);
+    if ((rc = da_stats_from_histogram(hist.data(), values, (int64_t)hist.size(), &s.mean_similarity, &s.median_similarity, &s.min_similarity,
+                                      &s.max_similarity)) != DA_OK) return rc;
+    s.pairs = n * (n - 1) / 2;
+    uint32_t rmin = 0, rmax = 0;
+    if (!positions(false, &rmin, s.least_similar_upper, s.least_similar_pair) || !positions(true, &rmax, s.most_similar_upper, s.most_similar_pair))
+      return fail(DA_ERR_HIP, "the extrema pass found no element above the diagonal");
+    uint64_t total = 0;
+    for (uint64_t h : hist) total += h;
+    // the two passes read the same triangle: they must agree on its size and its extremes
+    if ((int64_t)total != s.pairs || rmin >= hist.size() || rmax >= hist.size() || values[rmin] != s.min_similarity || values[rmax] != s.max_similarity)
+      return fail(DA_ERR_HIP, "statistics mismatch: the histogram holds %llu pairs in [%g, %g], the extrema pass found [%g, %g] over %lld",
+                  (unsigned long long)total, s.min_similarity, s.max_similarity, rmin < hist.size() ? values[rmin] : -1.0,
+                  rmax < hist.size() ? values[rmax] : -1.0, (long long)s.pairs);
+    *out = s;
+    return DA_OK;
+  }
+};
+
+// the records of one block to the host fold (synchronises the stream)
+int fold_block(StatsFold &fold, const DevBuf &drec, int64_t rows, int64_t col_begin, hipStream_t stream) {
+  std::vector<da_row_extrema> h((size_t)rows);
+  DA_HIP_TRY(hipMemcpyAsync(h.data(), drec.p, (size_t)rows * sizeof(da_row_extrema), hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  fold.add_block(h.data(), rows, col_begin);
+  return DA_OK;
+}
+
+// what the two NW calls check, in the order of nw_edges_core (matrix name first, DA_ERR_NO_DEVICE last)
+int nw_stats_validate(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, const da_similarity_stats *out,
+                      int64_t len_limit, int *mid_out, int64_t *total, int64_t *max_len) {
+  const int mid = da_matrix_id(matrix_name);  // reference :338 -> :190-206, before anything else
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (!residues || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (n < 2) return fail(DA_ERR_BAD_ARG, "the statistics are over the strict upper triangle: need >= 2 sequences");
+  int rc;
+  if ((rc = check_offsets(offsets, n, total, max_len)) != DA_OK) return rc;
+  if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] == offsets[i])
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld is empty: its similarities are 0/0 = NaN and R's median() of them is NA", (long long)(i + 1));
+  if (*max_len > len_limit)
+    return len_limit == 127 ? fail(DA_ERR_UNSUPPORTED, "the NW statistics work on uint16 codes: sequences up to 127 residues")
+                            : fail(DA_ERR_UNSUPPORTED, "the long NW statistics work on 32-bit value ranks: sequences up to 1024 residues");
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "too many sequences");
+  *mid_out = mid;
+  return require_device();
+}
+}  // namespace
+
+extern "C" {
+
+// mh_edges_core's pipeline up to and including the histogram, then the extrema of the same resident count matrix
+int da_similarity_mh_stats(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds,
+                           da_similarity_stats *out) {
+  int rc = validate_mh(n, k, n_hash);
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (n < 2) return fail(DA_ERR_BAD_ARG, "the statistics are over the strict upper triangle: need >= 2 sequences");
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: n_hash <= 65535 (got %d)", n_hash);
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "too many sequences");
+  if ((rc = require_device()) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf cnt, hist, drec;
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash)) != DA_OK) return rc;
+  if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK) return rc;   // uint16 counts stay on the device
+  const int nbins = n_hash + 1;
+  if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK || (rc = drec.alloc((size_t)n * sizeof(da_row_extrema))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemset(hist.p, 0, (size_t)nbins * 8));
+  if ((rc = mh.build(k, 0, n_hash)) != DA_OK || (rc = mh.finish()) != DA_OK) return rc;
+  if ((rc = launch_mh_compare(mh.planes.as<uint32_t>(), n, n_hash, 0, n, true, DA_OUT_COMPACT, cnt.p, n, nullptr, mh.bits)) != DA_OK)
+    return rc;
+  if ((rc = launch_upper_histogram(cnt.as<uint16_t>(), n, n, nbins, hist.as<unsigned long long>(), nullptr)) != DA_OK) return rc;
+  if ((rc = launch_upper_extrema(cnt.as<uint16_t>(), n, n, n, nullptr, 0, 0, drec.as<da_row_extrema>(), nullptr)) != DA_OK) return rc;
+  std::vector<uint64_t> h((size_t)nbins);
+  DA_HIP_TRY(hipMemcpy(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost));
+  StatsFold fold;
+  if ((rc = fold_block(fold, drec, n, 0, nullptr)) != DA_OK) return rc;
+  return fold.finish(h, mh_code_values(n_hash).data(), n, out);      // a count is its own rank
+}
+
+// nw_edges_core's pipeline (duplicate collapse and prefix sharing of nw_full_symmetric) up to and including the histogram of the codes;
+// bins of equal value are merged on the host (R's median sees values), and the extrema compare through the same code -> rank table
+int da_similarity_nw_stats(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                           da_similarity_stats *out) {
+  int mid = 0, rc;
+  int64_t total = 0, max_len = 0;
+  if ((rc = nw_stats_validate(residues, offsets, n, matrix_name, out, 127, &mid, &total, &max_len)) != DA_OK) return rc;
+  NwCodes nw;
+  DevBuf cnt, hist, drank, drec;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+  if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK) return rc;      // uint16 codes stay on the device
+  const int nbins = (int)((max_len << 8) | (2 * max_len)) + 1;              // matches <= max_len, length <= 2 * max_len
+  std::vector<uint16_t> ranks(65536);
+  int distinct = 0;
+  if ((rc = da_nw_code_ranks((int)max_len, ranks.data(), &distinct)) != DA_OK) return rc;
+  if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK || (rc = drank.alloc(65536 * sizeof(uint16_t))) != DA_OK ||
+      (rc = drec.alloc((size_t)n * sizeof(da_row_extrema))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemset(hist.p, 0, (size_t)nbins * 8));
+  DA_HIP_TRY(hipMemcpy(drank.p, ranks.data(), 65536 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  if ((rc = nw_full_symmetric(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, total, max_len, mid, gap_open, gap_ext, DA_OUT_COMPACT,
+                              cnt.p, n, nullptr)) != DA_OK) return rc;
+  if ((rc = launch_upper_histogram(cnt.as<uint16_t>(), n, n, nbins, hist.as<unsigned long long>(), nullptr)) != DA_OK) return rc;
+  if ((rc = launch_upper_extrema(cnt.as<uint16_t>(), n, n, n, drank.as<uint16_t>(), 0, 0, drec.as<da_row_extrema>(), nullptr)) != DA_OK) return rc;
+  std::vector<uint64_t> h((size_t)nbins);
+  DA_HIP_TRY(hipMemcpy(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost));
+  // codes -> value ranks: one bin per distinct value, ascending (length 0 cannot occur: no empty sequences)
+  const std::vector<double> code_values = nw_code_values(nbins, 0.0);
+  std::vector<uint64_t> hr((size_t)distinct, 0);
+  std::vector<double> values((size_t)distinct, 0.0);
+  for (int ln = 1; ln <= 2 * (int)max_len; ++ln)
+    for (int mt = 0; mt <= std::min(ln, (int)max_len); ++mt) {
+      const int code = (mt << 8) | ln;
+      values[ranks[(size_t)code]] = code_values[(size_t)code];
+      hr[ranks[(size_t)code]] += h[(size_t)code];
+    }
+  StatsFold fold;
+  if ((rc = fold_block(fold, drec, n, 0, nullptr)) != DA_OK) return rc;
+  return fold.finish(hr, values.data(), n, out);
+}
+
+// The first pass of rank_threshold_blocks -- per block the DP (PACK32), the value ranks in place, the histogram of the strict upper triangle
+// -- with the extrema of the block behind it and its records taken to the host: ONE pass of the DP whatever the number of blocks.
+int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                                da_similarity_stats *out) {
+  int mid = 0, rc;
+  int64_t total = 0, max_len = 0;
+  if ((rc = nw_stats_validate(residues, offsets, n, matrix_name, out, 1024, &mid, &total, &max_len)) != DA_OK) return rc;
+  NwCodes nw;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+  hipStream_t stream = nullptr;
+  const auto table = nw_value_table((int)max_len);
+  const std::vector<double> &values = table->values;
+  const int64_t nbins = (int64_t)values.size();
+  const int64_t ld = (n + 3) / 4 * 4;
+  // rows per block as rank_threshold_blocks: a multiple of 8, at least 8, following the budget
+  const int64_t blk = std::min(std::max<int64_t>((int64_t)(block_budget() / ((size_t)ld * sizeof(uint32_t))) / 8 * 8, 8), n);
+  const bool whole = blk >= n;
+  DevBuf d, drank, hist, drec;
+  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint32_t))) != DA_OK || (rc = drank.alloc(table->rank.size() * sizeof(uint32_t))) != DA_OK ||
+      (rc = hist.alloc((size_t)nbins * 8)) != DA_OK || (rc = drec.alloc((size_t)blk * sizeof(da_row_extrema))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpyAsync(drank.p, table->rank.data(), table->rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  DA_HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)nbins * 8, stream));
+  StatsFold fold;
+  fold.rec.reserve((size_t)n);
+  for (int64_t b0 = 0; b0 < n; b0 += blk) {
+    const int64_t b1 = std::min(n, b0 + blk), rows = b1 - b0, c0 = b0, cols = n - c0;   // rows [b0, b1) against columns [b0, n)
+    if (whole)   // the entire square in one block: the symmetric sweep computes every pair once and mirrors it
+      rc = launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, true, DA_OUT_PACK32, d.p, ld, nullptr, 0,
+                     stream);
+    else
+      rc = launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, false, DA_OUT_PACK32, d.p, ld, nullptr,
+                     0, stream, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c0, n);
+    if (rc != DA_OK) return rc;
+    if ((rc = launch_nw_codes_to_ranks(d.as<uint32_t>(), rows, cols, ld, (int)max_len, drank.as<uint32_t>(), d.as<uint32_t>(), ld, stream)) != DA_OK ||
+        (rc = launch_rank_histogram(d.as<uint32_t>(), rows, cols, ld, nbins, hist.as<unsigned long long>(), true, b0, c0, stream)) != DA_OK ||
+        (rc = launch_upper_extrema32(d.as<uint32_t>(), rows, cols, ld, b0, c0, drec.as<da_row_extrema>(), stream)) != DA_OK ||
+        (rc = fold_block(fold, drec, rows, c0, stream)) != DA_OK)
+      return rc;
+  }
+  std::vector<uint64_t> h((size_t)nbins);
+  DA_HIP_TRY(hipMemcpyAsync(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  return fold.finish(h, values.data(), n, out);      // ranks ARE the ascending value order
 }
 
 

@@ -338,6 +338,12 @@ int launch_threshold_ranks_count(const uint32_t *d_keys, int64_t rows, int64_t n
 int launch_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, bool triangle,
                                 int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out, int64_t capacity,
                                 hipStream_t stream);
+// stats_kernels.hip: per row of a block of keys (the origin convention of launch_rank_histogram), over the elements with global column > global
+// row, the smallest and the largest rank with the first local column holding each, and the rank of the diagonal element (da_dev_upper_extrema[32])
+int launch_upper_extrema(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int64_t row_begin, int64_t col_begin,
+                         da_row_extrema *d_rec, hipStream_t stream);
+int launch_upper_extrema32(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t row_begin, int64_t col_begin, da_row_extrema *d_rec,
+                           hipStream_t stream);
 int launch_edge_values(const uint16_t *d_key, int64_t count, int n_hash, double *d_w, hipStream_t stream);
 // d_out[r] = d_in[r] + base for r < count (a block's row pointers placed into the row pointers of the whole rectangle)
 int launch_rowptr_offset(const int64_t *d_in, int64_t count, int64_t base, int64_t *d_out, hipStream_t stream);

@@ -581,6 +581,32 @@ def threshold_ranks(keys, r_min, nbins, triangle=False, row_begin=0, col_begin=0
     return rowptr, j[:cap], key[:cap]
 
 
+def upper_extrema(keys, n, rank=None, row_begin=0, col_begin=0):
+    """Per row of a block of keys -- rows row_begin ... x columns col_begin ... col_begin + n of a square problem, held in the first n columns
+    of an int16 (uint16 keys) or int32 (uint32 value ranks) tensor with any row stride and base address -- the extremes of the elements whose
+    global column is greater than the global row: an int32 tensor (rows, 5) of {min, first local column of the min, max, first local column
+    of the max, diagonal element} (struct da_row_extrema; the ranks are uint32 bit patterns, a column is -1 where the row has no such
+    element, the diagonal 0xFFFFFFFF where it lies outside the block).  rank: the 65536-entry int16 table of ``nw_code_ranks`` on the device,
+    uint16 keys only -- the comparison is then on rank[key] and the record holds ranks (da_dev_upper_extrema / da_dev_upper_extrema32)."""
+    lib = _capi.load()
+    _require_cuda(keys, "keys")
+    assert keys.dim() == 2 and keys.dtype in (torch.int16, torch.int32) and (keys.shape[1] <= 1 or keys.stride(1) == 1)
+    rows, n = int(keys.shape[0]), int(n)
+    assert 0 <= n <= keys.shape[1]
+    ld = int(keys.stride(0)) if rows > 1 else max(n, 1)
+    rec = torch.empty((max(rows, 1), _capi.ROW_EXTREMA_WORDS), dtype=torch.int32, device=keys.device)
+    if keys.dtype == torch.int16:
+        if rank is not None:
+            _require_cuda(rank, "rank table")
+            assert rank.dtype == torch.int16 and rank.numel() == 65536 and rank.is_contiguous()
+        _call(lib.da_dev_upper_extrema, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(row_begin), int(col_begin),
+              rec.data_ptr(), _stream())
+    else:
+        assert rank is None, "uint32 keys are value ranks already"
+        _call(lib.da_dev_upper_extrema32, keys.data_ptr(), rows, n, ld, int(row_begin), int(col_begin), rec.data_ptr(), _stream())
+    return rec[:rows]
+
+
 def similarity_mh_cross_edges(dx, dy, k, n_hash, seeds, thresh_p=None, threshold=None, capacity=None):
     """The threshold form of similarity_mh_cross on two device-resident sets, one C call (da_dev_similarity_mh_cross_edges):
     (threshold, rowptr int64 (m + 1), j int32, w float64) -- CSR over the rows of x of the entries with R >= threshold and R > 0, columns

@@ -11,6 +11,7 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     R = s.cross(new, idx)                                           # == similarityMH_cross(new, sequences[idx], 4, 500, seed=12345)
     i, v = s.cross_topk(new, 10, idx)                               # == similarityMH_cross_topk(new, sequences[idx], 4, 500, 10, seed=12345)
     thr, ptr, j, w = s.cross_edges(new, 0.99, idx=idx)              # == similarityMH_cross_edges(new, sequences[idx], 4, 500, 0.99, seed=12345) as CSR
+    st = s.stats(idx)                                               # == similarityMH_stats(sequences[idx], 4, 500, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
 seeds per call, src/minHash.cpp:73,137); the contract -- MinHash estimates under one hash family -- holds.
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _capi, device
-from .similarity import SimilarityMatrix, hash_family_seeds, pack_sequences, quantile_type7, _resolve_seed
+from .similarity import SimilarityMatrix, hash_family_seeds, pack_sequences, quantile_type7, stats_from_records, _resolve_seed
 
 
 class MinHashSession:
@@ -218,3 +219,17 @@ class MinHashSession:
             return thr, ei, ej, values[ev]
         order = np.lexsort((ej, ei))
         return thr, ei[order], ej[order], values[ev[order]]
+
+    def stats(self, idx=None):
+        """compute_similarity_stats of the subset's similarity matrix without that matrix on the host (``SimilarityStats``, positions in
+        idx), as similarityMH_stats(sequences[idx], k, n_hash, seed=self.seed): the uint16 counts, the histogram of their strict upper
+        triangle, and every row's extremes with their first columns (device.upper_extrema)."""
+        planes, m = self.planes(idx)
+        if m < 2:
+            raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "the statistics are over the strict upper triangle: need >= 2 sequences")
+        cnt = device.mh_compare(planes, m, self.n_hash, kind=_capi.DA_OUT_COMPACT)
+        nbins = self.n_hash + 1
+        hist = device.upper_histogram(cnt, m, nbins)
+        rec = device.upper_extrema(cnt, m)
+        values = np.arange(nbins, dtype=np.float64) / self.n_hash           # src/minHash.cpp:174
+        return stats_from_records(hist.cpu().numpy().astype(np.uint64), values, rec.cpu().numpy())

@@ -543,3 +543,149 @@ def similarityNW_cross_edges_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapEx
     thresh, is_q = _thresh_args(thresh_p, threshold)
     return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_cross_edges_long_begin(
         xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name, go, ge, thresh, is_q, h, thr, cnt))
+
+
+# ---- summary statistics (reference R/similarity.R:11-34) --------------------------------------------------------------------------------------
+
+_STATS_FIELDS = ("mean_similarity", "median_similarity", "min_similarity", "max_similarity", "most_similar_pair", "least_similar_pair",
+                 "most_similar_upper", "least_similar_upper")
+
+
+class SimilarityStats(tuple):
+    """The reference's ``similarity_stats`` list as a named tuple: ``mean_similarity``, ``median_similarity``, ``min_similarity``,
+    ``max_similarity`` (floats) and ``most_similar_pair``, ``least_similar_pair`` -- R's ``which(X == v, arr.ind = TRUE)[1, ]`` as a 0-based
+    ``(row, col)``: the first position in column-major order over the WHOLE matrix holding the extreme of the strict upper triangle, so
+    ``(0, 0)`` when the maximum equals the diagonal -- plus two fields the reference lacks, ``most_similar_upper`` and
+    ``least_similar_upper``: the first ``(i, j)`` with i < j in row-major order holding it."""
+    __slots__ = ()
+    _fields = _STATS_FIELDS
+
+    def __new__(cls, *values):
+        if len(values) != len(_STATS_FIELDS):
+            raise TypeError("SimilarityStats takes %d values" % len(_STATS_FIELDS))
+        return tuple.__new__(cls, values)
+
+    def _asdict(self):
+        return dict(zip(_STATS_FIELDS, self))
+
+    def __repr__(self):
+        return "SimilarityStats(%s)" % ", ".join("%s=%r" % kv for kv in zip(_STATS_FIELDS, self))
+
+
+for _i, _name in enumerate(_STATS_FIELDS):
+    setattr(SimilarityStats, _name, property(lambda self, _i=_i: self[_i]))
+del _i, _name
+
+
+def stats_from_histogram(hist, values):
+    """(mean, median, min, max) of {values[b] repeated hist[b] times}, values ascending (da_stats_from_histogram): the median is R's /
+    numpy's -- the plain average of the two middle elements for an even count -- and the mean one long double sum over the bins, within
+    2 ** -42 relative of the exact mean of the doubles (not R's two-pass ``mean()`` bit for bit).  Needs no device."""
+    lib = _capi.load()
+    h = np.ascontiguousarray(hist, np.uint64)
+    v = np.ascontiguousarray(values, np.float64)
+    if h.shape != v.shape or h.ndim != 1:
+        raise ValueError("hist and values must be one-dimensional and of one length")
+    out = np.zeros(4, np.float64)
+    _capi.check(lib.da_stats_from_histogram(h.ctypes.data, v.ctypes.data, len(h), out[0:].ctypes.data, out[1:].ctypes.data,
+                                            out[2:].ctypes.data, out[3:].ctypes.data))
+    return tuple(float(x) for x in out)
+
+
+def compute_similarity_stats(X):
+    """The reference's ``compute_similarity_stats`` (R/similarity.R:11-34) on a dense matrix, in numpy: mean, median, min and max of the strict
+    upper triangle and the positions of the most and the least similar pair (``SimilarityStats``).  Its two checks: "Input must be a
+    matrix" for anything but a two-dimensional array, and a warning when X is not symmetric.  The definitions are those of the device
+    calls (``similarityMH_stats`` ...), which this function is what they are measured against: the median is ``np.median``'s, the mean
+    the long double sum over the distinct values (``stats_from_histogram``).  A matrix without a strict upper triangle or with a NaN in
+    it has no statistics here (ValueError); the reference returns NA for those and then fails on the subscript."""
+    import warnings
+    if not isinstance(X, np.ndarray) or X.ndim != 2:
+        raise ValueError("Input must be a matrix")
+    A = np.asarray(X, np.float64)
+    rows, cols = A.shape
+    eps100 = 100 * np.finfo(np.float64).eps                               # isSymmetric's tolerance
+    if rows != cols or not (np.array_equal(A, A.T) or np.allclose(A, A.T, rtol=eps100, atol=0.0, equal_nan=True)):
+        warnings.warn("Input matrix is not symmetric. Results may be unexpected.")
+    U = np.concatenate([A[i, i + 1:] for i in range(min(rows, cols))]) if cols > 1 else np.zeros(0)   # the triangle without an index array
+    if U.size == 0:
+        raise ValueError("the matrix has no strict upper triangle: need >= 2 sequences")
+    if np.isnan(U).any():
+        raise ValueError("the strict upper triangle holds NaN")
+    values, counts = np.unique(U, return_counts=True)
+    mean, median, lo, hi = stats_from_histogram(counts, values)
+
+    def first(v):
+        c, r = divmod(int(np.argmax((A.T == v).ravel())), rows)           # column-major over the whole matrix: the first True of the transpose
+        i, j = divmod(int(np.argmax(np.triu(A == v, 1).ravel())), cols)
+        return (r, c), (i, j)
+    most, most_upper = first(hi)
+    least, least_upper = first(lo)
+    return SimilarityStats(mean, median, lo, hi, most, least, most_upper, least_upper)
+
+
+def _stats_result(s):
+    """struct da_similarity_stats -> SimilarityStats"""
+    return SimilarityStats(s.mean_similarity, s.median_similarity, s.min_similarity, s.max_similarity, tuple(s.most_similar_pair),
+                           tuple(s.least_similar_pair), tuple(s.most_similar_upper), tuple(s.least_similar_upper))
+
+
+def stats_from_records(hist, values, records):
+    """``SimilarityStats`` from the two device passes over a resident n x n matrix of ranks: ``hist`` the histogram of its strict upper
+    triangle over ``values`` (ascending, one per rank) and ``records`` the (n, 5) array of ``device.upper_extrema`` for the whole square
+    (row_begin = col_begin = 0).  The host reduction of the C calls, in numpy."""
+    rec = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 5)
+    mean, median, lo, hi = stats_from_histogram(hist, values)
+    col = rec[:, [1, 3]].view(np.int32)
+    has = col[:, 0] >= 0
+    rows = np.arange(len(rec))
+    out = []
+    for want_max in (True, False):
+        key, c = (rec[:, 2], col[:, 1]) if want_max else (rec[:, 0], col[:, 0])
+        ext = key[has].max() if want_max else key[has].min()
+        row_has = has & (key == ext)
+        i = int(rows[row_has][0])
+        upper = (i, int(c[i]))
+        cand = row_has | (rec[:, 4] == ext)                               # rows ascending: the diagonal first, then the row's column
+        r = int(rows[cand][0])
+        pair = (r, r) if rec[r, 4] == ext else (int(c[r]), r)             # (c, r): column-major over the whole matrix, by symmetry
+        if np.float64(values[int(ext)]) != (hi if want_max else lo):
+            raise _capi.DynaAlignError(_capi.DA_ERR_HIP, "statistics mismatch between the histogram and the extrema pass")
+        out += [pair, upper]
+    return SimilarityStats(mean, median, lo, hi, out[0], out[2], out[1], out[3])
+
+
+def similarityMH_stats(sequences, k=4, n_hash=50, *, seed=None):
+    """``compute_similarity_stats(similarityMH(sequences, k, n_hash, seed=seed))`` without the matrix on the host: the uint16 counts stay on
+    the device, a histogram of the strict upper triangle gives mean, median, min and max, and one more pass gives every row's extremes
+    with their first columns, from which the positions follow (da_similarity_mh_stats).  Errors as similarityMH_edges."""
+    import ctypes
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    s = _capi.DaSimilarityStats()
+    _capi.check(lib.da_similarity_mh_stats(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, ctypes.addressof(s)))
+    return _stats_result(s)
+
+
+def _nw_stats(entry, sequences, matrixName, gapOpen, gapExt):
+    import ctypes
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    s = _capi.DaSimilarityStats()
+    _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"),
+                                    ctypes.addressof(s)))
+    return _stats_result(s)
+
+
+def similarityNW_stats(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
+    """``compute_similarity_stats(similarityNW(sequences, ...))`` without the matrix on the host (da_similarity_nw_stats).  Equal similarities
+    are one value whatever their (matches, length): 1/2 and 2/4 tie, for the median and for the positions.  The diagonal is what the
+    alignment of a sequence with itself gives, not always 1.0.  Sequences of 1 .. 127 residues; errors as similarityNW_edges."""
+    return _nw_stats("da_similarity_nw_stats", sequences, matrixName, gapOpen, gapExt)
+
+
+def similarityNW_stats_long(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
+    """``similarityNW_stats`` for sequences of 1 .. 1024 residues (da_similarity_nw_stats_long): the same arguments, the same result, the same
+    errors.  One pass of the alignment in row blocks, on 32-bit value ranks (``nw_value_ranks``)."""
+    return _nw_stats("da_similarity_nw_stats_long", sequences, matrixName, gapOpen, gapExt)

@@ -755,6 +755,79 @@ int da_dev_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n,
                                 int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out,
                                 int64_t capacity, void *stream);
 
+/* ---- summary statistics of a similarity matrix that never leaves the device (reference R/similarity.R:11-34, compute_similarity_stats) ----
+ * S is the n x n matrix da_similarity_mh / da_similarity_nw return for the same arguments, U the P = n (n - 1) / 2 values of its strict
+ * upper triangle.
+ *   min_similarity, max_similarity   min(U), max(U), bit for bit.
+ *   median_similarity                with u = sort(U): u[(P - 1) / 2] for odd P, (u[P / 2 - 1] + u[P / 2]) / 2 in double arithmetic for even P
+ *                                    (R's median(); numpy's np.median).  NOT da_quantile_type7(0.5), whose (1 - h) lo + h hi can differ in
+ *                                    the last bit.
+ *   mean_similarity                  sum over the occupied values, ascending, of count * value, accumulated in long double, divided by P
+ *                                    and rounded to double: within 2^-42 relative of the exact mean of the doubles.  R's mean() is a two-pass
+ *                                    long double sum over the elements; the two are not bit-identical.
+ *   most_similar_pair                R's which(S == max(U), arr.ind = TRUE)[1, ] as 0-based (row, col): the first position in COLUMN-MAJOR
+ *                                    order over the WHOLE matrix -- diagonal and lower triangle included -- where S equals max(U); equality
+ *                                    is of values (NW's 1/2 and 2/4 are equal).  When a MinHash set holds two sequences with identical
+ *                                    signatures, max(U) = 1.0 = S[0][0] and the answer is (0, 0): the reference's behaviour.
+ *   least_similar_pair               the same with min(U).
+ *   most_similar_upper,              not in the reference: the first (i, j), i < j, in ROW-MAJOR order where S[i][j] equals max(U) / min(U)
+ *   least_similar_upper              -- the real pair where the reference's rule lands on the diagonal.
+ * The diagonal: MinHash 1.0 (src/minHash.cpp:161); NW whatever the DP gives for (i, i), read from the matrix. */
+typedef struct da_similarity_stats {
+  double mean_similarity, median_similarity, min_similarity, max_similarity;
+  int64_t pairs;                       /* P */
+  int64_t most_similar_pair[2], least_similar_pair[2];     /* (row, col), 0-based */
+  int64_t most_similar_upper[2], least_similar_upper[2];
+} da_similarity_stats;
+
+/* The four numbers from a histogram: the multiset {values[b] repeated hist[b] times}, values ascending; hist must not be all zero.  Any
+ * output pointer may be NULL.  Host arithmetic as defined above; needs no device. */
+int da_stats_from_histogram(const uint64_t *hist, const double *values, int64_t nbins, double *mean_out, double *median_out,
+                            double *min_out, double *max_out);
+
+/* The statistics of similarityMH / similarityNW without the matrix on the host: the compare (or the DP) writes uint16 counts / codes that
+ * stay on the device, the histogram of the strict upper triangle gives the four numbers (NW: bins of equal value are merged first), and
+ * one more pass (da_dev_upper_extrema) gives every row's extremes with their first columns, 20 bytes a row, from which the host takes the
+ * positions.  Validation, before any device is needed, in the order of da_similarity_mh_edges / da_similarity_nw_edges:
+ *   MinHash: the reference's three checks, NULL pointers, n < 2, n_hash > 65535 (DA_ERR_UNSUPPORTED), the offsets;
+ *   NW: the matrix name, NULL pointers, n < 2, the offsets, the residues (the reference's first-raised message), an empty sequence
+ *       (DA_ERR_UNSUPPORTED: its similarities are NaN and R's median() gives NA), a sequence of more than 127 residues -- 1024 for
+ *       da_similarity_nw_stats_long (DA_ERR_UNSUPPORTED);
+ * DA_ERR_NO_DEVICE comes last.  da_similarity_nw_stats takes the duplicate collapse and the prefix sharing of da_similarity_nw.
+ * da_similarity_nw_stats_long works on 32-bit value ranks (da_nw_value_ranks) in row blocks of DYNAALIGN_BLOCK_BYTES like
+ * da_similarity_nw_edges_long_begin, with ONE pass of the DP whatever the number of blocks; a square that fits one block runs the
+ * symmetric sweep.  Single device; no duplicate route for MinHash (the direct compare). */
+int da_similarity_mh_stats(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds,
+                           da_similarity_stats *out);
+int da_similarity_nw_stats(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                           da_similarity_stats *out);
+int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open,
+                                int gap_ext, da_similarity_stats *out);
+
+/* The device piece.  The block: `rows` rows of ld >= n keys, rows [row_begin, row_begin + rows) x columns [col_begin, col_begin + n) of a
+ * square problem (the origin convention of da_dev_rank_histogram).  d_records[r], for the elements of row r whose global column is
+ * greater than the global row: the smallest and the largest rank and the smallest block-local column holding each; a row without such an
+ * element has min_col = max_col = -1 (min_key = 0xFFFFFFFF, max_key = 0).  diag_key is the rank of the element at global column ==
+ * global row, 0xFFFFFFFF when it lies outside the block.
+ *   da_dev_upper_extrema: uint16 keys; rank = d_rank[key] with d_rank the 65 536-entry table of da_nw_code_ranks on the device (as
+ *     da_dev_topk_rows uses it), or the key itself when d_rank is NULL (MinHash counts).
+ *   da_dev_upper_extrema32: uint32 keys that are value ranks already (da_dev_nw_codes_to_ranks).
+ * A workgroup per row (one wave when no row has more than 1024 such elements); 16-byte loads where a row's address allows it, single keys
+ * otherwise: every ld and naturally aligned base works.  What lies left of the diagonal is not read in whole chunks, apart from the
+ * diagonal element.  No atomics.  Asynchronous on `stream`; NULL pointers, ld < n, a negative shape or origin are DA_ERR_BAD_ARG;
+ * rows == 0 is DA_OK and touches nothing. */
+typedef struct da_row_extrema {
+  uint32_t min_key;
+  int32_t min_col;
+  uint32_t max_key;
+  int32_t max_col;
+  uint32_t diag_key;
+} da_row_extrema;
+int da_dev_upper_extrema(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int64_t row_begin,
+                         int64_t col_begin, da_row_extrema *d_records, void *stream);
+int da_dev_upper_extrema32(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t row_begin, int64_t col_begin,
+                           da_row_extrema *d_records, void *stream);
+
 /* ---- the caller's clustering step (reference R/clusterbreak.R:112-136, netcluster) ------------
  * igraph::cluster_louvain(graph_from_adjacency_matrix(S, mode = "upper", weighted = TRUE),
  *                         weights = E(g)$weight, resolution = 1.05)$membership
