@@ -1525,8 +1525,8 @@ int da_dev_nw_rect(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, 
   if (col_begin < 0 || col_end > n || col_begin > col_end) return fail(DA_ERR_BAD_ARG, "bad column range");
   if (ld < col_end - col_begin) return fail(DA_ERR_BAD_ARG, "leading dimension < columns");
   if (kind != DA_OUT_F64 && kind != DA_OUT_COMPACT && kind != DA_OUT_PACK32) return fail(DA_ERR_BAD_ARG, "bad output kind");
-  return launch_nw(d_codes, d_offsets, n, max_len, matrix_id, gap_open, gap_ext, row_begin, row_end, false, kind, d_out, ld, nullptr, 0,
-                   static_cast<hipStream_t>(stream), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, col_begin, col_end);
+  return launch_nw_rect(d_codes, d_offsets, n, max_len, matrix_id, gap_open, gap_ext, row_begin, row_end, col_begin, col_end, kind, d_out, ld,
+                        static_cast<hipStream_t>(stream));
 }
 
 int da_dev_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, void *stream) {
@@ -2402,17 +2402,55 @@ static int nw_cross_validate(const uint8_t *xr, const int64_t *xo, int64_t m, co
   return DA_OK;
 }
 
-// the two sets as ONE encoded code buffer [x ; y] on the device (m + n sequences)
-static int nw_upload_joint(const uint8_t *xr, const int64_t *xo, int64_t m, int64_t x_total, const uint8_t *yr, const int64_t *yo, int64_t n,
-                           int64_t y_total, NwCodes *nw) {
-  std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
-  std::vector<int64_t> off((size_t)(m + n) + 1);
-  if (x_total) memcpy(res.data(), xr, (size_t)x_total);
-  if (y_total) memcpy(res.data() + x_total, yr, (size_t)y_total);
-  for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = xo[i];
-  for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + yo[j];
-  return nw->upload(res.data(), off.data(), m + n, x_total + y_total);
-}
+// What the NW two-set host calls share once their own empty shapes are dealt with, in the documented order.  check(): NULL pointers, the
+// offsets, the residues (nw_cross_validate), the caller's own argument checks (`extra`), then -- for the calls that order the values
+// (nan_tail: "an order", "a quantile"; NULL: empty sequences are accepted) -- no empty sequence, and the longest sequence against len_limit
+// (0: none) with the caller's limit_text.  upload(): DA_ERR_NO_DEVICE last, then the two sets as ONE encoded code buffer [x ; y] on the device
+// (m + n sequences), of which the device evaluates pair (p, q) as calc(seq[min(p, q)], seq[max(p, q)]): sequence1 is the x string either way.
+struct NwCross {
+  const uint8_t *xr, *yr;
+  const int64_t *xo, *yo;
+  int64_t m, n;
+  int mid, gap_open, gap_ext;
+  int64_t x_total = 0, y_total = 0, max_len = 0;
+  NwCodes nw;
+  int check(bool out_ok, const std::function<int()> &extra, const char *nan_tail, int64_t len_limit, const char *limit_text) {
+    if (!xr || !yr || !out_ok) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int64_t x_max, y_max;
+    int rc;
+    if ((rc = check_offsets(xo, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(yo, n, &y_total, &y_max)) != DA_OK) return rc;
+    if ((rc = nw_cross_validate(xr, xo, m, yr, yo, n)) != DA_OK) return rc;
+    if (extra && (rc = extra()) != DA_OK) return rc;
+    for (int64_t i = 0; nan_tail && i < m + n; ++i) {
+      const int64_t *o = i < m ? xo + i : yo + (i - m);
+      if (o[1] == o[0])
+        return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in %s",
+                    (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y", nan_tail);
+    }
+    max_len = std::max(x_max, y_max);
+    if (len_limit && max_len > len_limit) return fail(DA_ERR_UNSUPPORTED, "%s", limit_text);
+    return DA_OK;
+  }
+  int upload() {
+    int rc;
+    if ((rc = require_device()) != DA_OK) return rc;
+    std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
+    std::vector<int64_t> off((size_t)(m + n) + 1);
+    if (x_total) memcpy(res.data(), xr, (size_t)x_total);
+    if (y_total) memcpy(res.data() + x_total, yr, (size_t)y_total);
+    for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = xo[i];
+    for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + yo[j];
+    return nw.upload(res.data(), off.data(), m + n, x_total + y_total);
+  }
+  // rows [b0, b1) of x against the columns of y (the row-major m x n result) ...
+  int rows(int64_t b0, int64_t b1, int kind, void *d, int64_t ld, hipStream_t stream) const {
+    return launch_nw_rect(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, m, m + n, kind, d, ld, stream);
+  }
+  // ... and rows [b0, b1) of y against the columns of x: its transpose, R's column-major NumericMatrix(m, n)
+  int rows_of_y(int64_t b0, int64_t b1, int kind, void *d, int64_t ld, hipStream_t stream) const {
+    return launch_nw_rect(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, m + b0, m + b1, 0, m, kind, d, ld, stream);
+  }
+};
 
 // similarityNW for two sets: out[i][j] = calc(x[i], y[j]) with x[i] as sequence1.  Both sets are encoded into ONE code buffer [x ; y]; the
 // device evaluates pair (p, q) of it as calc(seq[min(p, q)], seq[max(p, q)]), so rows of x against columns of y give the row-major result and
@@ -2422,26 +2460,18 @@ int da_similarity_nw_cross(const uint8_t *x_residues, const int64_t *x_offsets, 
   const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
   if (mid < 0) return DA_ERR_BAD_MATRIX;
   if (m <= 0 || n <= 0) return DA_OK;                    // an m x 0 or 0 x n matrix: nothing to write
-  if (!x_residues || !y_residues || !out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  int64_t x_total, y_total, x_max, y_max;
+  NwCross c{x_residues, y_residues, x_offsets, y_offsets, m, n, mid, gap_open, gap_ext};
   int rc;
-  if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
-  if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
-  if ((rc = require_device()) != DA_OK) return rc;
-  const int64_t max_len = std::max(x_max, y_max), nt = m + n;
-  NwCodes nw;
-  if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
+  if ((rc = c.check(out != nullptr, nullptr, nullptr, 0, nullptr)) != DA_OK || (rc = c.upload()) != DA_OK) return rc;
   const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
-  const int64_t r_base = column_major ? m : 0, c_base = column_major ? 0 : m;
-  const bool compact = max_len <= 127 && !da::config().no_host_widen;
+  const bool compact = c.max_len <= 127 && !da::config().no_host_widen;
   const uint64_t nan_bits = 0xFFF8000000000000ULL;        // 0/0 as the reference's x86 host produces it
   double nan;
   memcpy(&nan, &nan_bits, 8);
   const std::vector<double> table = compact ? nw_code_values(65536, nan) : std::vector<double>();
   return rows_to_host(cols, 0, rows, compact ? sizeof(uint16_t) : sizeof(double), out, [&](int64_t b0, int64_t b1, void *d) {
-    return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), nt, max_len, mid, gap_open, gap_ext, r_base + b0, r_base + b1, false,
-                     compact ? DA_OUT_COMPACT : DA_OUT_F64, d, cols, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c_base,
-                     c_base + cols);
+    const int kind = compact ? DA_OUT_COMPACT : DA_OUT_F64;
+    return column_major ? c.rows_of_y(b0, b1, kind, d, cols, nullptr) : c.rows(b0, b1, kind, d, cols, nullptr);
   }, nullptr, nullptr, compact ? table.data() : nullptr);
 }
 
@@ -2503,23 +2533,11 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
   if (mid < 0) return DA_ERR_BAD_MATRIX;
   if (m <= 0) return DA_OK;                              // no rows: nothing to write
   if (n <= 0) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = 0)", top);
-  if (!x_residues || !y_residues || !idx_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-  int64_t x_total, y_total, x_max, y_max;
+  NwCross c{x_residues, y_residues, x_offsets, y_offsets, m, n, mid, gap_open, gap_ext};
   int rc;
-  if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
-  if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
-  if ((rc = topk_check(top, n)) != DA_OK) return rc;
-  for (int64_t i = 0; i < m + n; ++i) {
-    const int64_t *o = i < m ? x_offsets + i : y_offsets + (i - m);
-    if (o[1] == o[0])
-      return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in an order",
-                  (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y");
-  }
-  const int64_t max_len = std::max(x_max, y_max);
-  if (max_len > 127) return fail(DA_ERR_UNSUPPORTED, "the NW top-k works on uint16 codes: sequences up to 127 residues");
-  if ((rc = require_device()) != DA_OK) return rc;
-  NwCodes nw;
-  if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
+  if ((rc = c.check(idx_out != nullptr, [&] { return topk_check(top, n); }, "an order", 127,
+                    "the NW top-k works on uint16 codes: sequences up to 127 residues")) != DA_OK || (rc = c.upload()) != DA_OK) return rc;
+  const int64_t max_len = c.max_len;
   // equal values tie whatever their codes (2/4 and 3/6): the selection orders by the dense rank of a code's double value
   std::vector<uint16_t> ranks(65536);
   int distinct = 0;
@@ -2529,10 +2547,7 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
       (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
   DA_HIP_TRY(hipMemcpy(drank.p, ranks.data(), 65536 * sizeof(uint16_t), hipMemcpyHostToDevice));
   rc = topk_blocks(m, n, drank.as<uint16_t>(), bits_of(distinct - 1), top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
-                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) {   // rows of x against columns of y: x[i] is sequence1
-                     return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, false,
-                                      DA_OUT_COMPACT, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
-                   });
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return c.rows(b0, b1, DA_OUT_COMPACT, d, ld, nullptr); });
   if (rc != DA_OK) return rc;
   return topk_to_host(didx, dkey, m, top, nw_code_values(65536, 0.0), idx_out, val_out);
 }
@@ -2808,24 +2823,25 @@ static int thresh_arg_check(double thresh, int thresh_is_quantile) {
   return DA_OK;
 }
 
-// Rows [0, m) of a two-set rectangle with n columns, thresholded block by block (blocks as topk_blocks: compute(b0, b1, d, ld) writes the
-// uint16 codes of rows [b0, b1) to the scratch block d).  values[code] is the similarity a code stands for; a code is kept when its value is
-// positive and not below the threshold.  Quantile form: a first pass of compute + histogram over all blocks gives the threshold; a single
-// block is then kept, several blocks are computed again.  Per block, in order: the per-row counts and their scan, the 8-byte total read
-// back, then sink(b0, b1, d, ld, d_keep, d_rowptr_block, total, base) -- base = the kept entries of the blocks before -- emits where it
-// wants them.  Synchronises the stream.
-typedef std::function<int(int64_t, int64_t, void *, int64_t)> RectCompute;
-typedef std::function<int(int64_t, int64_t, const uint16_t *, int64_t, const uint8_t *, const int64_t *, int64_t, int64_t)> RectSink;
-static int threshold_blocks(int64_t m, int64_t n, const std::vector<double> &values, double thresh, bool is_quantile, hipStream_t stream,
-                            const RectCompute &compute, const RectSink &sink, double *threshold_out, int64_t *n_edges_out) {
-  const int nbins = (int)values.size();
-  const int64_t ld = (n + 7) / 8 * 8;
-  const int64_t blk = std::min(block_rows(ld, sizeof(uint16_t)), m);
+// ---- the two-pass threshold driver, written once for uint16 codes with a keep table (CodeKeys) and uint32 value ranks (RankKeys) ----------
+}  // extern "C"  (reopened below)
+namespace {
+// Rows [0, m) of a problem thresholded block by block.  `keys` owns the scratch block of keys.blk rows and knows its key type: produce(b0, b1)
+// fills it with the keys of rows [b0, b1) (columns from c0(b0) on), histogram() adds the block to the device histogram of bins() bins,
+// quantile() turns the histogram into the threshold, set_threshold() into the keep decision, count() / emit() are the two steps of the
+// ordered compaction.  Quantile form: a first pass of produce + histogram over all blocks gives the threshold; a single block is then kept,
+// several are produced again.  Per block, in order: the per-row counts and their scan, the 8-byte total read back, then
+// sink(b0, b1, d_rowptr_block, total, base) -- base = the kept entries of the blocks before -- emits where it wants them.  Works on, and
+// synchronises, keys.stream.
+typedef std::function<int(int64_t, int64_t, const int64_t *, int64_t, int64_t)> BlockSink;
+template <typename Keys>
+int threshold_blocks(Keys &keys, int64_t m, double thresh, bool is_quantile, const BlockSink &sink, double *threshold_out, int64_t *n_edges_out) {
+  const hipStream_t stream = keys.stream;
+  const int64_t blk = keys.blk, nbins = keys.bins();
   const size_t wb = threshold_rows_workspace_bytes(blk);
-  DevBuf d, keep, rowptr, work, hist;
+  DevBuf rowptr, work, hist;
   int rc;
-  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint16_t))) != DA_OK || (rc = keep.alloc((size_t)nbins)) != DA_OK ||
-      (rc = rowptr.alloc((size_t)(blk + 1) * 8)) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+  if ((rc = rowptr.alloc((size_t)(blk + 1) * 8)) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
   double thr = thresh;
   bool have_block = false;
   if (is_quantile) {
@@ -2833,35 +2849,25 @@ static int threshold_blocks(int64_t m, int64_t n, const std::vector<double> &val
     DA_HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)nbins * 8, stream));
     for (int64_t b0 = 0; b0 < m; b0 += blk) {
       const int64_t b1 = std::min(m, b0 + blk);
-      if ((rc = compute(b0, b1, d.p, ld)) != DA_OK ||
-          (rc = launch_rect_histogram(d.as<uint16_t>(), b1 - b0, n, ld, nbins, hist.as<unsigned long long>(), stream)) != DA_OK) return rc;
+      if ((rc = keys.produce(b0, b1)) != DA_OK || (rc = keys.histogram(b0, b1, hist.as<unsigned long long>())) != DA_OK) return rc;
     }
     std::vector<uint64_t> h((size_t)nbins);
     DA_HIP_TRY(hipMemcpyAsync(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, stream));
     DA_HIP_TRY(hipStreamSynchronize(stream));
-    // order statistics need the codes in ascending order of their VALUE (MH: already so; NW: ratios, equal values side by side)
-    std::vector<int> order((size_t)nbins);
-    for (int b = 0; b < nbins; ++b) order[(size_t)b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return values[(size_t)a] < values[(size_t)b]; });
-    std::vector<uint64_t> hs((size_t)nbins);
-    std::vector<double> vs((size_t)nbins);
-    for (int b = 0; b < nbins; ++b) { hs[(size_t)b] = h[(size_t)order[(size_t)b]]; vs[(size_t)b] = values[(size_t)order[(size_t)b]]; }
-    if ((rc = da_quantile_type7(hs.data(), vs.data(), nbins, thresh, &thr)) != DA_OK) return rc;
+    hist.release();
+    if ((rc = keys.quantile(h, thresh, &thr)) != DA_OK) return rc;
     have_block = blk >= m;
   }
-  std::vector<uint8_t> kp((size_t)nbins);
-  for (int b = 0; b < nbins; ++b) kp[(size_t)b] = (values[(size_t)b] > 0.0 && values[(size_t)b] >= thr) ? 1 : 0;
-  DA_HIP_TRY(hipMemcpyAsync(keep.p, kp.data(), (size_t)nbins, hipMemcpyHostToDevice, stream));
+  if ((rc = keys.set_threshold(thr)) != DA_OK) return rc;
   int64_t base = 0;
   for (int64_t b0 = 0; b0 < m; b0 += blk) {
     const int64_t b1 = std::min(m, b0 + blk), rows = b1 - b0;
-    if (!have_block && (rc = compute(b0, b1, d.p, ld)) != DA_OK) return rc;
-    if ((rc = launch_threshold_rows_count(d.as<uint16_t>(), rows, n, ld, keep.as<uint8_t>(), nbins, rowptr.as<int64_t>(), work.p, wb, stream)) != DA_OK)
-      return rc;
+    if (!have_block && (rc = keys.produce(b0, b1)) != DA_OK) return rc;
+    if ((rc = keys.count(b0, b1, rowptr.as<int64_t>(), work.p, wb)) != DA_OK) return rc;
     int64_t total = 0;
     DA_HIP_TRY(hipMemcpyAsync(&total, rowptr.as<int64_t>() + rows, 8, hipMemcpyDeviceToHost, stream));
     DA_HIP_TRY(hipStreamSynchronize(stream));
-    if ((rc = sink(b0, b1, d.as<uint16_t>(), ld, keep.as<uint8_t>(), rowptr.as<int64_t>(), total, base)) != DA_OK) return rc;
+    if ((rc = sink(b0, b1, rowptr.as<int64_t>(), total, base)) != DA_OK) return rc;
     base += total;
   }
   DA_HIP_TRY(hipStreamSynchronize(stream));
@@ -2870,29 +2876,93 @@ static int threshold_blocks(int64_t m, int64_t n, const std::vector<double> &val
   return DA_OK;
 }
 
-// a block's kept entries appended to the handle's host vectors: i = block origin + row, w = values[key] (the table the dense calls widen with)
-static int rect_block_to_host(EdgeSet &es, const std::vector<double> &values, int64_t n, int64_t b0, int64_t b1, const uint16_t *d_keys, int64_t ld,
-                              const uint8_t *d_keep, const int64_t *d_rowptr, int64_t total, int64_t base, hipStream_t stream) {
-  if (total <= 0) return DA_OK;
-  const int64_t rows = b1 - b0;
-  DevBuf dj, dkey;
-  int rc;
-  if ((rc = dj.alloc((size_t)total * 4)) != DA_OK || (rc = dkey.alloc((size_t)total * 2)) != DA_OK) return rc;
-  if ((rc = launch_threshold_rows_emit(d_keys, rows, n, ld, d_keep, (int)values.size(), d_rowptr, dj.as<int32_t>(), dkey.as<uint16_t>(), total,
-                                       stream)) != DA_OK) return rc;
+// a block's emitted entries appended to the handle's host vectors: i = block origin + row, j = the emit's block-local column + c0,
+// w = values[key] (the table the dense calls widen with)
+template <typename Key>
+int block_to_host(EdgeSet &es, const std::vector<double> &values, int64_t b0, int64_t rows, int64_t c0, const int64_t *d_rowptr, const int32_t *d_j,
+                  const Key *d_key, int64_t total, int64_t base, hipStream_t stream) {
   const size_t at = (size_t)base, end = (size_t)(base + total);
   es.i.resize(end); es.j.resize(end); es.w.resize(end);
   std::vector<int64_t> rp((size_t)rows + 1);
-  std::vector<uint16_t> key((size_t)total);
+  std::vector<Key> key((size_t)total);
   DA_HIP_TRY(hipMemcpyAsync(rp.data(), d_rowptr, (size_t)(rows + 1) * 8, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipMemcpyAsync(es.j.data() + at, dj.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipMemcpyAsync(key.data(), dkey.p, (size_t)total * 2, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(es.j.data() + at, d_j, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(key.data(), d_key, (size_t)total * sizeof(Key), hipMemcpyDeviceToHost, stream));
   DA_HIP_TRY(hipStreamSynchronize(stream));
   for (int64_t r = 0; r < rows; ++r)
     for (int64_t e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) es.i[at + (size_t)e] = (int32_t)(b0 + r);
-  for (int64_t e = 0; e < total; ++e) es.w[at + (size_t)e] = values[key[(size_t)e]];
+  for (int64_t e = 0; e < total; ++e) {
+    es.j[at + (size_t)e] += (int32_t)c0;
+    es.w[at + (size_t)e] = values[key[(size_t)e]];
+  }
   return DA_OK;
 }
+// the host route: the keys' scratch block, then the driver with a sink that emits each block and appends it to the handle
+template <typename Keys>
+int edges_to_host(Keys &keys, int64_t m, double thresh, bool is_quantile, EdgeSet &es, int64_t *n_edges) {
+  typedef typename Keys::Key Key;
+  int rc;
+  if ((rc = keys.init()) != DA_OK) return rc;
+  return threshold_blocks(keys, m, thresh, is_quantile, [&](int64_t b0, int64_t b1, const int64_t *d_rowptr, int64_t total, int64_t base) -> int {
+    if (total <= 0) return DA_OK;
+    DevBuf dj, dkey;
+    int rc2;
+    if ((rc2 = dj.alloc((size_t)total * 4)) != DA_OK || (rc2 = dkey.alloc((size_t)total * sizeof(Key))) != DA_OK ||
+        (rc2 = keys.emit(b0, b1, d_rowptr, dj.as<int32_t>(), dkey.as<Key>(), total)) != DA_OK) return rc2;
+    return block_to_host<Key>(es, keys.values, b0, b1 - b0, keys.c0(b0), d_rowptr, dj.as<int32_t>(), dkey.as<Key>(), total, base, keys.stream);
+  }, &es.threshold, n_edges);
+}
+
+// uint16 counts / codes of an m x n rectangle (blocks as topk_blocks: compute(b0, b1, d, ld) writes the codes of rows [b0, b1) to the scratch
+// block d).  values[code] is the similarity a code stands for; a code is kept when its value is positive and not below the threshold.
+typedef std::function<int(int64_t, int64_t, void *, int64_t)> RectCompute;
+struct CodeKeys {
+  typedef uint16_t Key;
+  const std::vector<double> &values;
+  const RectCompute compute;
+  const hipStream_t stream;
+  const int64_t n, ld, blk;
+  DevBuf d, keep;
+  std::vector<uint8_t> kp;                    // the host image of keep[]: alive until the copy has run
+  CodeKeys(int64_t m, int64_t n_, const std::vector<double> &values_, const RectCompute &compute_, hipStream_t stream_)
+      : values(values_), compute(compute_), stream(stream_), n(n_), ld((n_ + 7) / 8 * 8), blk(std::min(block_rows(ld, sizeof(uint16_t)), m)) {}
+  int init() {
+    int rc;
+    if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint16_t))) != DA_OK) return rc;
+    return keep.alloc(values.size());
+  }
+  int64_t bins() const { return (int64_t)values.size(); }
+  int64_t c0(int64_t) const { return 0; }
+  int produce(int64_t b0, int64_t b1) { return compute(b0, b1, d.p, ld); }
+  int histogram(int64_t b0, int64_t b1, unsigned long long *d_hist) {
+    return launch_rect_histogram(d.as<uint16_t>(), b1 - b0, n, ld, (int)bins(), d_hist, stream);
+  }
+  int quantile(const std::vector<uint64_t> &h, double p, double *thr) const {
+    // order statistics need the codes in ascending order of their VALUE (MH: already so; NW: ratios, equal values side by side)
+    const int nbins = (int)bins();
+    std::vector<int> order((size_t)nbins);
+    for (int b = 0; b < nbins; ++b) order[(size_t)b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return values[(size_t)a] < values[(size_t)b]; });
+    std::vector<uint64_t> hs((size_t)nbins);
+    std::vector<double> vs((size_t)nbins);
+    for (int b = 0; b < nbins; ++b) { hs[(size_t)b] = h[(size_t)order[(size_t)b]]; vs[(size_t)b] = values[(size_t)order[(size_t)b]]; }
+    return da_quantile_type7(hs.data(), vs.data(), nbins, p, thr);
+  }
+  int set_threshold(double thr) {
+    kp.resize(values.size());
+    for (size_t b = 0; b < kp.size(); ++b) kp[b] = (values[b] > 0.0 && values[b] >= thr) ? 1 : 0;
+    DA_HIP_TRY(hipMemcpyAsync(keep.p, kp.data(), kp.size(), hipMemcpyHostToDevice, stream));
+    return DA_OK;
+  }
+  int count(int64_t b0, int64_t b1, int64_t *d_rowptr, void *d_work, size_t work_bytes) {
+    return launch_threshold_rows_count(d.as<uint16_t>(), b1 - b0, n, ld, keep.as<uint8_t>(), (int)bins(), d_rowptr, d_work, work_bytes, stream);
+  }
+  int emit(int64_t b0, int64_t b1, const int64_t *d_rowptr, int32_t *d_j, uint16_t *d_key, int64_t capacity) {
+    return launch_threshold_rows_emit(d.as<uint16_t>(), b1 - b0, n, ld, keep.as<uint8_t>(), (int)bins(), d_rowptr, d_j, d_key, capacity, stream);
+  }
+};
+}  // namespace
+extern "C" {
 
 int da_similarity_mh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
                                        const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, double thresh,
@@ -2912,11 +2982,9 @@ int da_similarity_mh_cross_edges_begin(const uint8_t *x_residues, const int64_t 
     DA_HIP_TRY(hipStreamSynchronize(nullptr));
     c.work.release(); c.sig.release();                     // before the scratch block is sized
     const std::vector<double> values = mh_code_values(n_hash);
-    return threshold_blocks(m, n, values, thresh, thresh_is_quantile != 0, nullptr,
-                            [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, nullptr); },
-                            [&](int64_t b0, int64_t b1, const uint16_t *dk, int64_t ld, const uint8_t *keep, const int64_t *rp, int64_t total, int64_t base) {
-                              return rect_block_to_host(es, values, n, b0, b1, dk, ld, keep, rp, total, base, nullptr);
-                            }, &es.threshold, n_edges);
+    CodeKeys keys(m, n, values, [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, nullptr); },
+                  nullptr);
+    return edges_to_host(keys, m, thresh, thresh_is_quantile != 0, es, n_edges);
   });
 }
 
@@ -2934,34 +3002,16 @@ int da_similarity_nw_cross_edges_begin(const uint8_t *x_residues, const int64_t 
       *n_edges = 0;
       return DA_OK;
     }
-    if (!x_residues || !y_residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-    int64_t x_total, y_total, x_max, y_max;
-    if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
-    if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
-    if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
-    for (int64_t i = 0; i < m + n; ++i) {
-      const int64_t *o = i < m ? x_offsets + i : y_offsets + (i - m);
-      if (o[1] == o[0])
-        return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in a quantile",
-                    (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y");
-    }
-    const int64_t max_len = std::max(x_max, y_max);
-    if (max_len > 127) return fail(DA_ERR_UNSUPPORTED, "the NW two-set edge list works on uint16 codes: sequences up to 127 residues");
-    if ((rc = require_device()) != DA_OK) return rc;
-    NwCodes nw;
-    if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
+    NwCross c{x_residues, y_residues, x_offsets, y_offsets, m, n, mid, gap_open, gap_ext};
+    if ((rc = c.check(true, [&] { return thresh_arg_check(thresh, thresh_is_quantile); }, "a quantile", 127,
+                      "the NW two-set edge list works on uint16 codes: sequences up to 127 residues")) != DA_OK || (rc = c.upload()) != DA_OK) return rc;
+    const int64_t max_len = c.max_len;
     // every code that can occur lies below this bound (matches <= max_len, length <= 2 * max_len), as in the square NW edge path: the
     // histogram of short peptides stays in LDS; length 0 cannot occur (no empty sequences)
     const int nbins = (int)((max_len << 8) | (2 * max_len)) + 1;
     const std::vector<double> values = nw_code_values(nbins, 0.0);
-    return threshold_blocks(m, n, values, thresh, thresh_is_quantile != 0, nullptr,
-                            [&](int64_t b0, int64_t b1, void *d, int64_t ld) {   // rows of x against columns of y: x[i] is sequence1
-                              return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, false,
-                                               DA_OUT_COMPACT, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
-                            },
-                            [&](int64_t b0, int64_t b1, const uint16_t *dk, int64_t ld, const uint8_t *keep, const int64_t *rp, int64_t total, int64_t base) {
-                              return rect_block_to_host(es, values, n, b0, b1, dk, ld, keep, rp, total, base, nullptr);
-                            }, &es.threshold, n_edges);
+    CodeKeys keys(m, n, values, [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return c.rows(b0, b1, DA_OUT_COMPACT, d, ld, nullptr); }, nullptr);
+    return edges_to_host(keys, m, thresh, thresh_is_quantile != 0, es, n_edges);
   });
 }
 
@@ -2984,9 +3034,11 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
   DA_HIP_TRY(hipStreamSynchronize(stream));
   c.work.release(); c.sig.release();                       // before the scratch block is sized
   const std::vector<double> values = mh_code_values(n_hash);
-  return threshold_blocks(m, n, values, thresh, thresh_is_quantile != 0, stream,
-                          [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, stream); },
-                          [&](int64_t b0, int64_t b1, const uint16_t *dk, int64_t ld, const uint8_t *keep, const int64_t *rp, int64_t total, int64_t base) -> int {
+  CodeKeys keys(m, n, values, [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return mh_cross_compare(c, n_hash, b0, b1, DA_OUT_COMPACT, d, ld, stream); },
+                stream);
+  if ((rc = keys.init()) != DA_OK) return rc;
+  // the device-resident sink: the block's row pointers placed into the caller's, its entries emitted straight behind those of the blocks before
+  return threshold_blocks(keys, m, thresh, thresh_is_quantile != 0, [&](int64_t b0, int64_t b1, const int64_t *rp, int64_t total, int64_t base) -> int {
                             int rc2;
                             const int64_t rows = b1 - b0;   // the last block also places the total
                             if ((rc2 = launch_rowptr_offset(rp, rows + (b1 == m ? 1 : 0), base, d_rowptr + b0, stream)) != DA_OK) return rc2;
@@ -2994,7 +3046,7 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
                             if (cnt <= 0) return DA_OK;
                             DevBuf key;
                             if ((rc2 = key.alloc((size_t)cnt * 2)) != DA_OK) return rc2;
-                            if ((rc2 = launch_threshold_rows_emit(dk, rows, n, ld, keep, n_hash + 1, rp, d_j + base, key.as<uint16_t>(), cnt, stream)) != DA_OK ||
+                            if ((rc2 = keys.emit(b0, b1, rp, d_j + base, key.as<uint16_t>(), cnt)) != DA_OK ||
                                 (rc2 = launch_edge_values(key.as<uint16_t>(), cnt, n_hash, d_w + base, stream)) != DA_OK) return rc2;
                             DA_HIP_TRY(hipStreamSynchronize(stream));   // the key block goes back to the cache after this
                             return DA_OK;
@@ -3093,94 +3145,80 @@ int da_dev_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n,
                                      static_cast<hipStream_t>(stream));
 }
 
-// Rows [0, m) of an NW problem thresholded block by block on value ranks.  square: the problem is the n x n matrix of one set (m == n), a
-// block holds rows [b0, b1) against columns [b0, n), the histogram takes the strict upper triangle and the edges the triangle with the
-// diagonal; otherwise it is the m x n rectangle.  compute(b0, b1, c0, d, ld, whole) writes the PACK32 codes of rows [b0, b1), columns from c0
-// on, to d (`whole`: the block is the entire square -- the symmetric sweep fills it at half the DP).  Quantile form: a first pass of compute
-// + ranks + histogram gives the threshold; a single block is then kept, several are computed again.  Per block: ranks, the per-row counts
-// and their scan, the 8-byte total read back, the ordered emit, and the kept (column, rank) pairs to the handle's host vectors, w =
-// values[rank].  Synchronises the stream.
+}  // extern "C"  (reopened below)
+namespace {
+// The scratch block of an NW problem on value ranks, and what fills it.  square: the problem is the n x n matrix of one set (m == n) and a
+// block holds rows [b0, b1) against columns [b0, n); otherwise it is the m x n rectangle.  compute(b0, b1, c0, d, ld, whole) writes the
+// PACK32 codes of rows [b0, b1), columns from c0 on, to d (`whole`: the block is the entire square -- the symmetric sweep fills it at half
+// the DP).  Rows per block: a multiple of 8 (the tile of the wavefront kernels), at least 8 -- a row of long sequences is a lot of DP, so the
+// blocks follow the budget closely instead of block_rows' 128-row units.
 typedef std::function<int(int64_t, int64_t, int64_t, void *, int64_t, bool)> RankCompute;
-static int rank_threshold_blocks(int64_t m, int64_t n, bool square, int max_len, double thresh, bool is_quantile, hipStream_t stream,
-                                 const RankCompute &compute, EdgeSet &es, int64_t *n_edges_out) {
-  const auto table = nw_value_table(max_len);
-  const std::vector<double> &values = table->values;
-  const int64_t nbins = (int64_t)values.size();
-  const int64_t ld = (n + 3) / 4 * 4;
-  // rows per block: a multiple of 8 (the tile of the wavefront kernels), at least 8 -- a row of long sequences is a lot of DP, so the
-  // blocks follow the budget closely instead of block_rows' 128-row units
-  const int64_t blk = std::min(std::max<int64_t>((int64_t)(block_budget() / ((size_t)ld * sizeof(uint32_t))) / 8 * 8, 8), m);
-  const bool whole = square && blk >= m;
-  const size_t wb = threshold_rows_workspace_bytes(blk);
-  DevBuf d, drank, rowptr, work, hist;
-  int rc;
-  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint32_t))) != DA_OK || (rc = drank.alloc(table->rank.size() * sizeof(uint32_t))) != DA_OK ||
-      (rc = rowptr.alloc((size_t)(blk + 1) * 8)) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
-  DA_HIP_TRY(hipMemcpyAsync(drank.p, table->rank.data(), table->rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-  auto ranks_of = [&](int64_t b0, int64_t b1) -> int {    // the block's codes, then its ranks in place
-    const int64_t c0 = square ? b0 : 0;
-    int rc2;
-    if ((rc2 = compute(b0, b1, c0, d.p, ld, whole)) != DA_OK) return rc2;
-    return launch_nw_codes_to_ranks(d.as<uint32_t>(), b1 - b0, n - c0, ld, max_len, drank.as<uint32_t>(), d.as<uint32_t>(), ld, stream);
-  };
-  double thr = thresh;
-  bool have_block = false;
-  if (is_quantile) {
-    if ((rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;
-    DA_HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)nbins * 8, stream));
-    for (int64_t b0 = 0; b0 < m; b0 += blk) {
-      const int64_t b1 = std::min(m, b0 + blk), c0 = square ? b0 : 0;
-      if ((rc = ranks_of(b0, b1)) != DA_OK ||
-          (rc = launch_rank_histogram(d.as<uint32_t>(), b1 - b0, n - c0, ld, nbins, hist.as<unsigned long long>(), square, b0, c0, stream)) != DA_OK)
-        return rc;
-    }
-    std::vector<uint64_t> h((size_t)nbins);
-    DA_HIP_TRY(hipMemcpyAsync(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    hist.release();
-    if ((rc = da_quantile_type7(h.data(), values.data(), (int)nbins, thresh, &thr)) != DA_OK) return rc;   // ranks ARE the ascending value order
-    have_block = blk >= m;
+struct RankBlocks {
+  const std::shared_ptr<const NwValueTable> table;
+  const std::vector<double> &values;          // ascending: a rank indexes it
+  const RankCompute compute;
+  const hipStream_t stream;
+  const bool square;
+  const int max_len;
+  const int64_t n, ld, blk;
+  const bool whole;
+  DevBuf d, drank;
+  RankBlocks(int64_t m, int64_t n_, bool square_, int max_len_, const RankCompute &compute_, hipStream_t stream_)
+      : table(nw_value_table(max_len_)), values(table->values), compute(compute_), stream(stream_), square(square_), max_len(max_len_), n(n_),
+        ld((n_ + 3) / 4 * 4), blk(std::min(std::max<int64_t>((int64_t)(block_budget() / ((size_t)ld * sizeof(uint32_t))) / 8 * 8, 8), m)),
+        whole(square_ && blk >= m) {}
+  int init() {
+    int rc;
+    if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint32_t))) != DA_OK || (rc = drank.alloc(table->rank.size() * sizeof(uint32_t))) != DA_OK) return rc;
+    DA_HIP_TRY(hipMemcpyAsync(drank.p, table->rank.data(), table->rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    return DA_OK;
+  }
+  int64_t bins() const { return (int64_t)values.size(); }
+  int64_t c0(int64_t b0) const { return square ? b0 : 0; }
+  int ranks_of(int64_t b0, int64_t b1) {      // the block's codes, then its ranks in place
+    int rc;
+    if ((rc = compute(b0, b1, c0(b0), d.p, ld, whole)) != DA_OK) return rc;
+    return launch_nw_codes_to_ranks(d.as<uint32_t>(), b1 - b0, n - c0(b0), ld, max_len, drank.as<uint32_t>(), d.as<uint32_t>(), ld, stream);
+  }
+  // hist[rank] += occurrences in the block -- of the strict upper triangle when the problem is square
+  int histogram(int64_t b0, int64_t b1, unsigned long long *d_hist) {
+    return launch_rank_histogram(d.as<uint32_t>(), b1 - b0, n - c0(b0), ld, bins(), d_hist, square, b0, c0(b0), stream);
+  }
+};
+// ... as the keys of threshold_blocks: the edges take the rectangle, or the triangle WITH the diagonal; w = values[rank]
+struct RankKeys : RankBlocks {
+  typedef uint32_t Key;
+  uint32_t r_min = 1;
+  using RankBlocks::RankBlocks;
+  int produce(int64_t b0, int64_t b1) { return ranks_of(b0, b1); }
+  int quantile(const std::vector<uint64_t> &h, double p, double *thr) const {   // ranks ARE the ascending value order
+    return da_quantile_type7(h.data(), values.data(), (int)bins(), p, thr);
   }
   // kept: value >= threshold and value > 0, i.e. rank >= max(r_thr, 1), r_thr the smallest rank whose value is >= threshold
-  const int64_t r_thr = std::lower_bound(values.begin(), values.end(), thr) - values.begin();
-  const uint32_t r_min = (uint32_t)std::max<int64_t>(r_thr, 1);
-  int64_t base = 0;
-  std::vector<int64_t> rp;
-  std::vector<uint32_t> key;
-  for (int64_t b0 = 0; b0 < m; b0 += blk) {
-    const int64_t b1 = std::min(m, b0 + blk), rows = b1 - b0, c0 = square ? b0 : 0;
-    if (!have_block && (rc = ranks_of(b0, b1)) != DA_OK) return rc;
-    if ((rc = launch_threshold_ranks_count(d.as<uint32_t>(), rows, n - c0, ld, r_min, nbins, square, b0, c0, rowptr.as<int64_t>(), work.p, wb,
-                                           stream)) != DA_OK) return rc;
-    int64_t total = 0;
-    DA_HIP_TRY(hipMemcpyAsync(&total, rowptr.as<int64_t>() + rows, 8, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    if (total <= 0) continue;
-    DevBuf dj, dkey;
-    if ((rc = dj.alloc((size_t)total * 4)) != DA_OK || (rc = dkey.alloc((size_t)total * 4)) != DA_OK) return rc;
-    if ((rc = launch_threshold_ranks_emit(d.as<uint32_t>(), rows, n - c0, ld, r_min, nbins, square, b0, c0, rowptr.as<int64_t>(), dj.as<int32_t>(),
-                                          dkey.as<uint32_t>(), total, stream)) != DA_OK) return rc;
-    const size_t at = (size_t)base, end = (size_t)(base + total);
-    es.i.resize(end); es.j.resize(end); es.w.resize(end);
-    rp.resize((size_t)rows + 1);
-    key.resize((size_t)total);
-    DA_HIP_TRY(hipMemcpyAsync(rp.data(), rowptr.p, (size_t)(rows + 1) * 8, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipMemcpyAsync(es.j.data() + at, dj.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipMemcpyAsync(key.data(), dkey.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-    for (int64_t r = 0; r < rows; ++r)
-      for (int64_t e = rp[(size_t)r]; e < rp[(size_t)r + 1]; ++e) es.i[at + (size_t)e] = (int32_t)(b0 + r);
-    for (int64_t e = 0; e < total; ++e) {
-      es.j[at + (size_t)e] += (int32_t)c0;                 // the emit's columns are local to the block
-      es.w[at + (size_t)e] = values[key[(size_t)e]];
-    }
-    base += total;
+  int set_threshold(double thr) {
+    r_min = (uint32_t)std::max<int64_t>(std::lower_bound(values.begin(), values.end(), thr) - values.begin(), 1);
+    return DA_OK;
   }
-  DA_HIP_TRY(hipStreamSynchronize(stream));
-  es.threshold = thr;
-  *n_edges_out = base;
-  return DA_OK;
+  int count(int64_t b0, int64_t b1, int64_t *d_rowptr, void *d_work, size_t work_bytes) {
+    return launch_threshold_ranks_count(d.as<uint32_t>(), b1 - b0, n - c0(b0), ld, r_min, bins(), square, b0, c0(b0), d_rowptr, d_work, work_bytes, stream);
+  }
+  int emit(int64_t b0, int64_t b1, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key, int64_t capacity) {
+    return launch_threshold_ranks_emit(d.as<uint32_t>(), b1 - b0, n - c0(b0), ld, r_min, bins(), square, b0, c0(b0), d_rowptr, d_j, d_key, capacity,
+                                       stream);
+  }
+};
+// the PACK32 codes of one set's square: the whole of it by the symmetric sweep (every pair computed once and mirrored), else rows [b0, b1)
+// against columns [c0, n)
+RankCompute nw_square_codes(const NwCodes &nw, int64_t n, int64_t max_len, int mid, int gap_open, int gap_ext, hipStream_t stream) {
+  return [=, &nw](int64_t b0, int64_t b1, int64_t c0, void *d, int64_t ld, bool whole) {
+    if (whole)
+      return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, true, DA_OUT_PACK32, d, ld, nullptr, 0,
+                       stream);
+    return launch_nw_rect(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, c0, n, DA_OUT_PACK32, d, ld, stream);
+  };
 }
+}  // namespace
+extern "C" {
 
 // da_similarity_nw_edges_begin for sequences of up to 1024 residues: the same validation, the same result
 int da_similarity_nw_edges_long_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
@@ -3204,14 +3242,8 @@ int da_similarity_nw_edges_long_begin(const uint8_t *residues, const int64_t *of
     if ((rc = require_device()) != DA_OK) return rc;
     NwCodes nw;
     if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
-    return rank_threshold_blocks(n, n, true, (int)max_len, thresh_p, true, nullptr,
-                                 [&](int64_t b0, int64_t b1, int64_t c0, void *d, int64_t ld, bool whole) {
-                                   if (whole)   // the entire square in one block: the symmetric sweep computes every pair once and mirrors it
-                                     return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, true,
-                                                      DA_OUT_PACK32, d, ld, nullptr, 0, nullptr);
-                                   return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, false,
-                                                    DA_OUT_PACK32, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c0, n);
-                                 }, es, n_edges);
+    RankKeys keys(n, n, true, (int)max_len, nw_square_codes(nw, n, max_len, mid, gap_open, gap_ext, nullptr), nullptr);
+    return edges_to_host(keys, n, thresh_p, true, es, n_edges);
   });
 }
 
@@ -3230,28 +3262,15 @@ int da_similarity_nw_cross_edges_long_begin(const uint8_t *x_residues, const int
       *n_edges = 0;
       return DA_OK;
     }
-    if (!x_residues || !y_residues) return fail(DA_ERR_BAD_ARG, "NULL pointer");
-    int64_t x_total, y_total, x_max, y_max;
-    if ((rc = check_offsets(x_offsets, m, &x_total, &x_max)) != DA_OK || (rc = check_offsets(y_offsets, n, &y_total, &y_max)) != DA_OK) return rc;
-    if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
-    if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
-    for (int64_t i = 0; i < m + n; ++i) {
-      const int64_t *o = i < m ? x_offsets + i : y_offsets + (i - m);
-      if (o[1] == o[0])
-        return fail(DA_ERR_UNSUPPORTED, "sequence %lld of %s is empty: its similarities are NaN / 0.0 and a NaN has no place in a quantile",
-                    (long long)((i < m ? i : i - m) + 1), i < m ? "x" : "y");
-    }
-    const int64_t max_len = std::max(x_max, y_max);
-    if (max_len > 1024) return fail(DA_ERR_UNSUPPORTED, "the long NW two-set edge list works on 32-bit value ranks: sequences up to 1024 residues");
+    NwCross c{x_residues, y_residues, x_offsets, y_offsets, m, n, mid, gap_open, gap_ext};
+    if ((rc = c.check(true, [&] { return thresh_arg_check(thresh, thresh_is_quantile); }, "a quantile", 1024,
+                      "the long NW two-set edge list works on 32-bit value ranks: sequences up to 1024 residues")) != DA_OK) return rc;
     if (m > 0x7ffffff0LL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "too many sequences");
-    if ((rc = require_device()) != DA_OK) return rc;
-    NwCodes nw;
-    if ((rc = nw_upload_joint(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, &nw)) != DA_OK) return rc;
-    return rank_threshold_blocks(m, n, false, (int)max_len, thresh, thresh_is_quantile != 0, nullptr,
-                                 [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {   // rows of x against columns of y: x[i] is sequence1
-                                   return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), m + n, max_len, mid, gap_open, gap_ext, b0, b1, false,
-                                                    DA_OUT_PACK32, d, ld, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, m, m + n);
-                                 }, es, n_edges);
+    if ((rc = c.upload()) != DA_OK) return rc;
+    RankKeys keys(m, n, false, (int)c.max_len, [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {
+      return c.rows(b0, b1, DA_OUT_PACK32, d, ld, nullptr);
+    }, nullptr);
+    return edges_to_host(keys, m, thresh, thresh_is_quantile != 0, es, n_edges);
   });
 }
 
@@ -3441,8 +3460,8 @@ int da_similarity_nw_stats(const uint8_t *residues, const int64_t *offsets, int6
   return fold.finish(hr, values.data(), n, out);
 }
 
-// The first pass of rank_threshold_blocks -- per block the DP (PACK32), the value ranks in place, the histogram of the strict upper triangle
-// -- with the extrema of the block behind it and its records taken to the host: ONE pass of the DP whatever the number of blocks.
+// The first pass of the long NW edge list (RankBlocks: per block the DP (PACK32), the value ranks in place, the histogram of the strict upper
+// triangle) with the extrema of the block behind it and its records taken to the host: ONE pass of the DP whatever the number of blocks.
 int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
                                 da_similarity_stats *out) {
   int mid = 0, rc;
@@ -3451,32 +3470,19 @@ int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets,
   NwCodes nw;
   if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
   hipStream_t stream = nullptr;
-  const auto table = nw_value_table((int)max_len);
-  const std::vector<double> &values = table->values;
-  const int64_t nbins = (int64_t)values.size();
-  const int64_t ld = (n + 3) / 4 * 4;
-  // rows per block as rank_threshold_blocks: a multiple of 8, at least 8, following the budget
-  const int64_t blk = std::min(std::max<int64_t>((int64_t)(block_budget() / ((size_t)ld * sizeof(uint32_t))) / 8 * 8, 8), n);
-  const bool whole = blk >= n;
-  DevBuf d, drank, hist, drec;
-  if ((rc = d.alloc((size_t)blk * (size_t)ld * sizeof(uint32_t))) != DA_OK || (rc = drank.alloc(table->rank.size() * sizeof(uint32_t))) != DA_OK ||
-      (rc = hist.alloc((size_t)nbins * 8)) != DA_OK || (rc = drec.alloc((size_t)blk * sizeof(da_row_extrema))) != DA_OK) return rc;
-  DA_HIP_TRY(hipMemcpyAsync(drank.p, table->rank.data(), table->rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  RankBlocks keys(n, n, true, (int)max_len, nw_square_codes(nw, n, max_len, mid, gap_open, gap_ext, stream), stream);
+  const int64_t nbins = keys.bins();
+  const std::vector<double> &values = keys.values;
+  DevBuf hist, drec;
+  if ((rc = keys.init()) != DA_OK || (rc = hist.alloc((size_t)nbins * 8)) != DA_OK ||
+      (rc = drec.alloc((size_t)keys.blk * sizeof(da_row_extrema))) != DA_OK) return rc;
   DA_HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)nbins * 8, stream));
   StatsFold fold;
   fold.rec.reserve((size_t)n);
-  for (int64_t b0 = 0; b0 < n; b0 += blk) {
-    const int64_t b1 = std::min(n, b0 + blk), rows = b1 - b0, c0 = b0, cols = n - c0;   // rows [b0, b1) against columns [b0, n)
-    if (whole)   // the entire square in one block: the symmetric sweep computes every pair once and mirrors it
-      rc = launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, true, DA_OUT_PACK32, d.p, ld, nullptr, 0,
-                     stream);
-    else
-      rc = launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, false, DA_OUT_PACK32, d.p, ld, nullptr,
-                     0, stream, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, c0, n);
-    if (rc != DA_OK) return rc;
-    if ((rc = launch_nw_codes_to_ranks(d.as<uint32_t>(), rows, cols, ld, (int)max_len, drank.as<uint32_t>(), d.as<uint32_t>(), ld, stream)) != DA_OK ||
-        (rc = launch_rank_histogram(d.as<uint32_t>(), rows, cols, ld, nbins, hist.as<unsigned long long>(), true, b0, c0, stream)) != DA_OK ||
-        (rc = launch_upper_extrema32(d.as<uint32_t>(), rows, cols, ld, b0, c0, drec.as<da_row_extrema>(), stream)) != DA_OK ||
+  for (int64_t b0 = 0; b0 < n; b0 += keys.blk) {
+    const int64_t b1 = std::min(n, b0 + keys.blk), rows = b1 - b0, c0 = keys.c0(b0);   // rows [b0, b1) against columns [b0, n)
+    if ((rc = keys.ranks_of(b0, b1)) != DA_OK || (rc = keys.histogram(b0, b1, hist.as<unsigned long long>())) != DA_OK ||
+        (rc = launch_upper_extrema32(keys.d.as<uint32_t>(), rows, n - c0, keys.ld, b0, c0, drec.as<da_row_extrema>(), stream)) != DA_OK ||
         (rc = fold_block(fold, drec, rows, c0, stream)) != DA_OK)
       return rc;
   }

@@ -60,6 +60,11 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
   } while (0)
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// a block of `rows` rows of n keys, one workgroup per row and 32-bit chunk arithmetic: what one launch of a row-walking kernel takes
+inline int block_shape_ok(int64_t rows, int64_t n) {
+  if (rows > 0x7fffffffLL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
+  return DA_OK;
+}
 
 // Folded layout of one rank's shard (row-sharded multi-GPU path).  Rank p owns tile rows
 // t = q*world + p (q = 0..Q-1) and only their part right of the diagonal is valid, so local
@@ -144,41 +149,6 @@ __host__ __device__ inline int64_t pk_lo_bytes(int64_t U) { return (U + 127) / 1
 __host__ __device__ inline int64_t pk_row_bytes(int64_t lo_bytes) { return lo_bytes + lo_bytes / 8; }
 inline size_t pk_table_bytes(int64_t U) { return (size_t)U * (size_t)pk_row_bytes(pk_lo_bytes(U)); }
 
-// ---- device helpers the row-walking kernels share (topk_kernels.hip, rect_edges_kernels.hip): a row of uint16 keys is taken in chunks of
-// THREADS x 8 keys, eight consecutive keys (one 16-byte load where the row address allows it) per thread
-constexpr int TK_PER = 8;                     // keys per thread per chunk: one 16-byte load
-
-// lanes below `lane` summed: inclusive wave scan by shuffles
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// ranks (r) and keys (k) of the row's columns [j0, j0 + 8); returns how many of them exist (columns < n)
-__device__ __forceinline__ int load8(const uint16_t *__restrict__ row, int64_t j0, int64_t n, bool vec, const uint16_t *__restrict__ rank,
-                                     uint32_t r[TK_PER], uint32_t k[TK_PER]) {
-  int nv;
-  if (vec && j0 + TK_PER <= n) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int e = 0; e < TK_PER; ++e) k[e] = (w[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
-    nv = TK_PER;
-  } else {
-    nv = j0 >= n ? 0 : (n - j0 < TK_PER ? (int)(n - j0) : TK_PER);
-#pragma unroll
-    for (int e = 0; e < TK_PER; ++e) k[e] = e < nv ? (uint32_t)row[j0 + e] : 0u;
-  }
-#pragma unroll
-  for (int e = 0; e < TK_PER; ++e) r[e] = (rank && e < nv) ? (uint32_t)rank[k[e]] : k[e];
-  return nv;
-}
-
 // Kernel launchers implemented in the .hip translation units.  All are
 // asynchronous on `stream`; argument checking is done by the C-ABI layer.
 int launch_minhash_signatures(const uint8_t *d_res, const int64_t *d_off, int64_t n,
@@ -252,6 +222,12 @@ int launch_nw(const uint8_t *d_codes, const int64_t *d_off, int64_t n, int64_t m
               const int32_t *ord_first = nullptr, const int32_t *ord_minfirst = nullptr, const int32_t *ord_maxlast = nullptr,
               const int32_t *ord_perm = nullptr, const uint8_t *ord_lcp = nullptr,   // ord_perm / ord_lcp: launch_nw_sort_unique (prefix sharing)
               int64_t col_begin = 0, int64_t col_end = -1);                          // row-block mode: only the columns [col_begin, col_end) (-1: n)
+// the row-block mode by name: rows [r0, r1) x columns [c0, c1) of the pair space, no scores, no shard, no ordering
+inline int launch_nw_rect(const uint8_t *d_codes, const int64_t *d_off, int64_t n, int64_t max_len, int matrix_id, int gap_open, int gap_ext,
+                          int64_t r0, int64_t r1, int64_t c0, int64_t c1, int kind, void *d_out, int64_t ld, hipStream_t stream) {
+  return launch_nw(d_codes, d_off, n, max_len, matrix_id, gap_open, gap_ext, r0, r1, false, kind, d_out, ld, nullptr, 0, stream, 0, 0, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, c0, c1);
+}
 // nw_kernels.hip: lexicographic order of (unique) sequences of <= 24 residues + the common prefix of sorted neighbours, for the ordered DP
 size_t nw_sort_unique_workspace_bytes(int64_t n);
 int launch_nw_sort_unique(const uint8_t *d_codes, const int64_t *d_off, int64_t n, void *d_work, size_t work_bytes, const int32_t **perm_out,
@@ -325,10 +301,10 @@ int launch_threshold_rows_count(const uint16_t *d_keys, int64_t rows, int64_t n,
                                 void *d_work, size_t work_bytes, hipStream_t stream);
 int launch_threshold_rows_emit(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint8_t *d_keep, int nbins, const int64_t *d_rowptr,
                                int32_t *d_j, uint16_t *d_key_out, int64_t capacity, hipStream_t stream);
-int threshold_rows_scan(void *d_work, size_t work_bytes, int64_t rows, int64_t *d_rowptr, hipStream_t stream);
-// nw_edges_long_kernels.hip: the same steps on blocks of uint32 keys -- PACK32 codes (matches << 16 | length) to value ranks through the table of
-// da_nw_value_ranks, the rank histogram, and the ordered compaction of the keys >= r_min.  triangle: the block is rows [row_begin, ...) x
-// columns [col_begin, ...) of a square problem; the histogram counts global column > global row, count / emit keep global column >= global row.
+// the same steps on blocks of uint32 keys -- PACK32 codes (matches << 16 | length) to value ranks through the table of da_nw_value_ranks and
+// the rank histogram (nw_edges_long_kernels.hip), and the ordered compaction of the keys >= r_min (rect_edges_kernels.hip).  triangle: the
+// block is rows [row_begin, ...) x columns [col_begin, ...) of a square problem; the histogram counts global column > global row, count /
+// emit keep global column >= global row.
 int launch_nw_codes_to_ranks(const uint32_t *d_codes, int64_t rows, int64_t n, int64_t ld, int max_len, const uint32_t *d_rank, uint32_t *d_out,
                              int64_t ld_out, hipStream_t stream);
 int launch_rank_histogram(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, unsigned long long *d_hist, bool triangle,

@@ -9,11 +9,11 @@
 //      before any atomic: within a wave by two rounds of leader election (one lane adds the population count of its key), within a
 //      workgroup by a direct-mapped LDS cache of 4096 (tag, count) slots that is flushed once, and only what misses both goes to a
 //      global atomic of its own;
-//   3. k_rank_count / k_rank_emit: the 32-bit twins of k_threshold_count / k_threshold_emit (rect_edges_kernels.hip).  The keep decision is
-//      one compare, rank >= r_min; the mask is the rectangle or the upper triangle INCLUDING the diagonal.  The workgroup owns a row, the
-//      slot of an entry depends on the data alone: no output atomic, no sort.
-// Rows are read in 16-byte units where their address allows it and in 4-byte units otherwise: every ld and 4-byte-aligned base works.
+//   3. the ordered compaction is k_threshold_count / k_threshold_emit (rect_edges_kernels.hip) on uint32 keys with the KeepRanks policy:
+//      the keep decision is one compare, rank >= r_min; the mask is the rectangle or the upper triangle INCLUDING the diagonal.
+// Rows are read through KeyRow<uint32_t> (row_keys.hpp): every ld and 4-byte-aligned base works.
 #include "da_common.hpp"
+#include "row_keys.hpp"
 
 #include <algorithm>
 
@@ -21,25 +21,10 @@ namespace da {
 namespace {
 
 constexpr int RK_THREADS = 256;
-constexpr int RK_PER = 4;                      // keys per thread per chunk: one 16-byte load
+constexpr int RK_PER = KeyRow<uint32_t>::PER;
 constexpr int RK_WAVE_KEYS = 64 * RK_PER;      // what one wave takes per step of the histogram
 constexpr int RK_CACHE = 4096;                 // slots of the workgroup's (tag, count) cache: 32 KiB
 constexpr uint32_t RK_EMPTY = 0xFFFFFFFFu;
-
-// k[e] = key of column j0 + e of the row for e < nv (the return value), 0 beyond
-__device__ __forceinline__ int load4(const uint32_t *__restrict__ row, int64_t j0, int64_t n, bool vec, uint32_t k[RK_PER]) {
-  int nv;
-  if (vec && j0 + RK_PER <= n) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
-    k[0] = v.x; k[1] = v.y; k[2] = v.z; k[3] = v.w;
-    nv = RK_PER;
-  } else {
-    nv = j0 >= n ? 0 : (n - j0 < RK_PER ? (int)(n - j0) : RK_PER);
-#pragma unroll
-    for (int e = 0; e < RK_PER; ++e) k[e] = e < nv ? row[j0 + e] : 0u;
-  }
-  return nv;
-}
 
 // out[r][c] = rank[length * (max_len + 1) + matches] of code[r][c] = matches << 16 | length; a code outside the table's domain -> 0.
 // In place allowed: every element is read and written by the same thread.
@@ -89,7 +74,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_histogram(const uint32_t *_
     const uint32_t *row = keys + rr * ld;
     const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
     const int64_t j0 = c0 + (int64_t)lane * RK_PER;
-    const int nv = load4(row, j0, n, vec, k);
+    const int nv = KeyRow<uint32_t>::load(row, j0, n, vec, k);
 #pragma unroll
     for (int e = 0; e < RK_PER; ++e) {
       const uint32_t v = k[e];
@@ -114,110 +99,13 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_histogram(const uint32_t *_
     if (cnt[s]) atomicAdd(&hist[tag[s]], (unsigned long long)cnt[s]);
 }
 
-// bit e set: column j0 + e exists, lies in the mask (local column >= first) and its key passes
-__device__ __forceinline__ uint32_t kept_mask32(const uint32_t k[RK_PER], int nv, int64_t j0, int64_t first, uint32_t r_min, uint32_t nbins) {
-  uint32_t mask = 0;
-#pragma unroll
-  for (int e = 0; e < RK_PER; ++e) {
-    const bool kp = e < nv && j0 + e >= first && k[e] >= r_min && k[e] < nbins;
-    mask |= (kp ? 1u : 0u) << e;
-  }
-  return mask;
-}
-
-// first local column of the mask in row `r` of the block: 0 for the rectangle, the diagonal (global column >= global row) for the triangle
-__device__ __forceinline__ int64_t mask_first(int tri, int64_t row_begin, int64_t col_begin, int64_t r) {
-  const int64_t f = tri ? row_begin + r - col_begin : 0;
-  return f > 0 ? f : 0;
-}
-
-// cnt[row] = number of kept keys of the row; one workgroup (THREADS = 64: one wave) per row
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_rank_count(const uint32_t *__restrict__ keys, int64_t n, int64_t ld, uint32_t r_min, uint32_t nbins,
-                                                        int tri, int64_t row_begin, int64_t col_begin, long long *__restrict__ cnt) {
-  constexpr int WAVES = THREADS / 64;
-  constexpr int CHUNK = THREADS * RK_PER;
-  __shared__ unsigned int wsum[WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t *row = keys + (int64_t)blockIdx.x * ld;
-  const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
-  const int64_t first = mask_first(tri, row_begin, col_begin, blockIdx.x);
-  uint32_t k[RK_PER], mine = 0;
-  for (int64_t c0 = first / CHUNK * CHUNK; c0 < n; c0 += CHUNK) {   // chunks left of the mask are not read
-    const int64_t j0 = c0 + (int64_t)tid * RK_PER;
-    const int nv = load4(row, j0, n, vec, k);
-    mine += (uint32_t)__popc(kept_mask32(k, nv, j0, first, r_min, nbins));
-  }
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
-  if (lane == 0) wsum[wave] = mine;
-  __syncthreads();
-  if (tid == 0) {
-    long long total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) total += wsum[w];
-    cnt[blockIdx.x] = total;
-  }
-}
-
-// the kept columns of the row (local to the block), ascending, at slots rowptr[row] ...; slots >= capacity are not written
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_rank_emit(const uint32_t *__restrict__ keys, int64_t n, int64_t ld, uint32_t r_min, uint32_t nbins,
-                                                       int tri, int64_t row_begin, int64_t col_begin, const long long *__restrict__ rowptr,
-                                                       int32_t *__restrict__ out_j, uint32_t *__restrict__ out_key, long long capacity) {
-  constexpr int WAVES = THREADS / 64;
-  constexpr int CHUNK = THREADS * RK_PER;
-  __shared__ unsigned int wtot[2][WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  long long base = rowptr[blockIdx.x];
-  if (rowptr[blockIdx.x + 1] == base || base >= capacity) return;   // block-uniform: a row without an edge is not read again
-  const uint32_t *row = keys + (int64_t)blockIdx.x * ld;
-  const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
-  const int64_t first = mask_first(tri, row_begin, col_begin, blockIdx.x);
-  uint32_t k[RK_PER];
-  int buf = 0;
-  for (int64_t c0 = first / CHUNK * CHUNK; c0 < n; c0 += CHUNK, buf ^= 1) {
-    const int64_t j0 = c0 + (int64_t)tid * RK_PER;
-    const int nv = load4(row, j0, n, vec, k);
-    const uint32_t mask = kept_mask32(k, nv, j0, first, r_min, nbins);
-    const uint32_t mine = (uint32_t)__popc(mask);
-    const uint32_t incl = wave_incl_scan(mine);
-    if (lane == 63) wtot[buf][wave] = incl;
-    __syncthreads();                           // the other buffer is written next time: one barrier per chunk
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      const uint32_t t = wtot[buf][w];
-      if (w < wave) before += t;
-      total += t;
-    }
-    if (mine) {
-      long long slot = base + before + incl - mine;
-#pragma unroll
-      for (int e = 0; e < RK_PER; ++e) {
-        if (!(mask & (1u << e))) continue;
-        if (slot < capacity) {
-          out_j[slot] = (int32_t)(j0 + e);
-          out_key[slot] = k[e];
-        }
-        ++slot;
-      }
-    }
-    base += total;
-  }
-}
-
-int rank_block_shape_ok(int64_t rows, int64_t n) {
-  if (rows > 0x7fffffffLL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
-  return DA_OK;
-}
-
 }  // namespace
 
 int launch_nw_codes_to_ranks(const uint32_t *d_codes, int64_t rows, int64_t n, int64_t ld, int max_len, const uint32_t *d_rank, uint32_t *d_out,
                              int64_t ld_out, hipStream_t stream) {
   if (rows <= 0 || n <= 0) return DA_OK;
   int rc;
-  if ((rc = rank_block_shape_ok(rows, n)) != DA_OK) return rc;
+  if ((rc = block_shape_ok(rows, n)) != DA_OK) return rc;
   const int64_t per_row = ceil_div(n, RK_THREADS), units = rows * per_row;
   const unsigned grid = (unsigned)std::min<int64_t>(units, 256 * 32);
   hipLaunchKernelGGL(k_codes_to_ranks, dim3(grid), dim3(RK_THREADS), 0, stream, d_codes, n, ld, max_len, d_rank, d_out, ld_out, per_row, units);
@@ -229,7 +117,7 @@ int launch_rank_histogram(const uint32_t *d_keys, int64_t rows, int64_t n, int64
                           int64_t row_begin, int64_t col_begin, hipStream_t stream) {
   if (rows <= 0 || n <= 0) return DA_OK;
   int rc;
-  if ((rc = rank_block_shape_ok(rows, n)) != DA_OK) return rc;
+  if ((rc = block_shape_ok(rows, n)) != DA_OK) return rc;
   const int64_t per_row = ceil_div(n, RK_WAVE_KEYS), units = rows * per_row;
   const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(units, RK_THREADS / 64), 256 * 16);
   // the cache counts in 32 bits: a workgroup takes ceil(units / waves) units of 256 keys
@@ -241,45 +129,6 @@ int launch_rank_histogram(const uint32_t *d_keys, int64_t rows, int64_t n, int64
   else
     hipLaunchKernelGGL(k_rank_histogram<false>, dim3(grid), dim3(RK_THREADS), 0, stream, d_keys, n, ld, (uint32_t)nbins, d_hist, per_row, units,
                        row_begin, col_begin);
-  DA_HIP_TRY(hipGetLastError());
-  return DA_OK;
-}
-
-// workspace: threshold_rows_workspace_bytes(rows) -- the per-row counts + the scan's scratch, as the 16-bit twin
-int launch_threshold_ranks_count(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, bool triangle,
-                                 int64_t row_begin, int64_t col_begin, int64_t *d_rowptr, void *d_work, size_t work_bytes, hipStream_t stream) {
-  if (rows <= 0) return DA_OK;
-  int rc;
-  if ((rc = rank_block_shape_ok(rows, n)) != DA_OK) return rc;
-  if (n <= 0) { DA_HIP_TRY(hipMemsetAsync(d_rowptr, 0, (size_t)(rows + 1) * 8, stream)); return DA_OK; }
-  if (rows + 1 > 0x7fffffffLL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
-  if (!d_work || work_bytes < threshold_rows_workspace_bytes(rows)) return fail(DA_ERR_BAD_ARG, "threshold ranks: workspace too small");
-  long long *cnt = static_cast<long long *>(d_work);
-  DA_HIP_TRY(hipMemsetAsync(cnt + rows, 0, 8, stream));
-  const int tri = triangle ? 1 : 0;
-  if (n <= 1024)
-    hipLaunchKernelGGL(k_rank_count<64>, dim3((unsigned)rows), dim3(64), 0, stream, d_keys, n, ld, r_min, (uint32_t)nbins, tri, row_begin, col_begin, cnt);
-  else
-    hipLaunchKernelGGL(k_rank_count<RK_THREADS>, dim3((unsigned)rows), dim3(RK_THREADS), 0, stream, d_keys, n, ld, r_min, (uint32_t)nbins, tri,
-                       row_begin, col_begin, cnt);
-  DA_HIP_TRY(hipGetLastError());
-  return threshold_rows_scan(d_work, work_bytes, rows, d_rowptr, stream);
-}
-
-int launch_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, bool triangle,
-                                int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out, int64_t capacity,
-                                hipStream_t stream) {
-  if (rows <= 0 || n <= 0 || capacity <= 0) return DA_OK;
-  int rc;
-  if ((rc = rank_block_shape_ok(rows, n)) != DA_OK) return rc;
-  const long long *rp = reinterpret_cast<const long long *>(d_rowptr);
-  const int tri = triangle ? 1 : 0;
-  if (n <= 1024)
-    hipLaunchKernelGGL(k_rank_emit<64>, dim3((unsigned)rows), dim3(64), 0, stream, d_keys, n, ld, r_min, (uint32_t)nbins, tri, row_begin, col_begin, rp,
-                       d_j, d_key_out, (long long)capacity);
-  else
-    hipLaunchKernelGGL(k_rank_emit<RK_THREADS>, dim3((unsigned)rows), dim3(RK_THREADS), 0, stream, d_keys, n, ld, r_min, (uint32_t)nbins, tri,
-                       row_begin, col_begin, rp, d_j, d_key_out, (long long)capacity);
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }

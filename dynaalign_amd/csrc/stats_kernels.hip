@@ -7,45 +7,20 @@
 // of the row's diagonal element.  The reduction over the rows is host arithmetic on those records (api.cpp, stats_fold).
 //   uint16 keys: MinHash counts (the key is its own rank) or NW codes ordered through the 65 536-entry table of da_nw_code_ranks;
 //   uint32 keys: value ranks already (da_dev_nw_codes_to_ranks).
-// The shape is k_threshold_count / k_rank_count's: the workgroup owns a row (one wave when no row has more than 1024 masked keys), a thread
+// The shape is k_threshold_count's: the workgroup owns a row (one wave when no row has more than 1024 masked keys), a thread
 // takes 16 bytes per chunk where the row's address allows it and single keys otherwise, and what lies left of the diagonal is not read
 // -- whole chunks by the loop's start, 16-byte units inside the first chunk by a test -- apart from the diagonal element itself.  A thread
 // meets its columns in ascending order, so a strict compare keeps the first; between threads (rank, column) travel as one 64-bit word whose
 // order is the rule -- min of rank << 32 | column, max of rank << 32 | ~column -- through shuffles, then LDS.  No atomics, no scratch.
 #include "da_common.hpp"
+#include "row_keys.hpp"
 
 namespace da {
 namespace {
 
 constexpr int SX_THREADS = 256;
-constexpr int SX_WAVE_SPAN = 1024;            // masked keys of a row up to which one wave owns it (k_rank_count's rule)
+constexpr int SX_WAVE_SPAN = 1024;            // masked keys of a row up to which one wave owns it (k_threshold_count's rule)
 constexpr uint32_t SX_NONE = 0xFFFFFFFFu;
-
-template <typename Key> struct SxPer;
-template <> struct SxPer<uint16_t> { static constexpr int value = TK_PER; };
-template <> struct SxPer<uint32_t> { static constexpr int value = 4; };
-
-// r[e] = rank of column j0 + e of the row for e < nv (the return value)
-__device__ __forceinline__ int sx_load(const uint16_t *__restrict__ row, int64_t j0, int64_t n, bool vec, const uint16_t *__restrict__ rank,
-                                       uint32_t r[TK_PER]) {
-  uint32_t k[TK_PER];
-  return load8(row, j0, n, vec, rank, r, k);
-}
-__device__ __forceinline__ int sx_load(const uint32_t *__restrict__ row, int64_t j0, int64_t n, bool vec, const uint16_t *, uint32_t r[4]) {
-  int nv;
-  if (vec && j0 + 4 <= n) {
-    const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
-    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-    nv = 4;
-  } else {
-    nv = j0 >= n ? 0 : (n - j0 < 4 ? (int)(n - j0) : 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) r[e] = e < nv ? row[j0 + e] : 0u;
-  }
-  return nv;
-}
-__device__ __forceinline__ uint32_t sx_rank(uint16_t key, const uint16_t *__restrict__ rank) { return rank ? (uint32_t)rank[key] : (uint32_t)key; }
-__device__ __forceinline__ uint32_t sx_rank(uint32_t key, const uint16_t *) { return key; }
 
 __device__ __forceinline__ unsigned long long sx_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned long long sx_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
@@ -53,7 +28,7 @@ __device__ __forceinline__ unsigned long long sx_max(unsigned long long a, unsig
 template <typename Key, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_upper_extrema(const Key *__restrict__ keys, int64_t n, int64_t ld, const uint16_t *__restrict__ rank,
                                                            int64_t row_begin, int64_t col_begin, da_row_extrema *__restrict__ rec) {
-  constexpr int PER = SxPer<Key>::value;
+  constexpr int PER = KeyRow<Key>::PER;
   constexpr int WAVES = THREADS / 64;
   constexpr int CHUNK = THREADS * PER;
   __shared__ unsigned long long wmin[WAVES], wmax[WAVES];
@@ -63,11 +38,11 @@ __global__ __launch_bounds__(THREADS) void k_upper_extrema(const Key *__restrict
   const int64_t diag = row_begin + (int64_t)blockIdx.x - col_begin;   // local column of the element on the global diagonal
   const int64_t first = diag + 1 > 0 ? diag + 1 : 0;                  // first masked local column: global column > global row
   uint32_t mn = SX_NONE, mn_c = SX_NONE, mx = 0, mx_c = SX_NONE;      // *_c == SX_NONE: nothing seen yet
-  uint32_t r[PER];
+  uint32_t r[PER], k[PER];
   for (int64_t c0 = first / CHUNK * CHUNK; c0 < n; c0 += CHUNK) {     // chunks left of the mask are not read
     const int64_t j0 = c0 + (int64_t)tid * PER;
     if (j0 + PER <= first) continue;                                  // nor the units of the first chunk that end before it
-    const int nv = sx_load(row, j0, n, vec, rank, r);
+    const int nv = KeyRow<Key>::load(row, j0, n, vec, rank, r, k);
 #pragma unroll
     for (int e = 0; e < PER; ++e) {
       if (e >= nv || j0 + e < first) continue;
@@ -94,7 +69,7 @@ __global__ __launch_bounds__(THREADS) void k_upper_extrema(const Key *__restrict
     out.min_col = (int32_t)(uint32_t)kmin;                            // -1 when the row has no masked element
     out.max_key = (uint32_t)(kmax >> 32);
     out.max_col = (int32_t)~(uint32_t)kmax;                           // likewise
-    out.diag_key = diag >= 0 && diag < n ? sx_rank(row[diag], rank) : SX_NONE;
+    out.diag_key = diag >= 0 && diag < n ? KeyRow<Key>::rank_of(row[diag], rank) : SX_NONE;
     rec[blockIdx.x] = out;
   }
 }
@@ -103,7 +78,8 @@ template <typename Key>
 int launch_extrema(const Key *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int64_t row_begin, int64_t col_begin,
                    da_row_extrema *d_rec, hipStream_t stream) {
   if (rows <= 0) return DA_OK;
-  if (rows > 0x7fffffffLL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
+  int rc;
+  if ((rc = block_shape_ok(rows, n)) != DA_OK) return rc;
   // the longest masked span is the first row's
   const int64_t first0 = row_begin + 1 - col_begin, span = n - (first0 > 0 ? first0 : 0);
   if (span <= SX_WAVE_SPAN)

@@ -14,6 +14,7 @@
 // The row is read three times (the second and third time from L2 / MALL); rank 0 -- by far the commonest: unrelated peptides share no
 // k-mer -- is counted in a register, not with 64 lanes on one LDS word (k_upper_histogram does the same).
 #include "da_common.hpp"
+#include "row_keys.hpp"
 
 namespace da {
 namespace {
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
   __syncthreads();
   uint32_t zeros = 0;
   for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
-    const int nv = load8(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
+    const int nv = KeyRow<uint16_t>::load(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
 #pragma unroll
     for (int e = 0; e < TK_PER; ++e) {
       if (e >= nv) continue;
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
     __syncthreads();
     zeros = 0;
     for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
-      const int nv = load8(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
+      const int nv = KeyRow<uint16_t>::load(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
 #pragma unroll
       for (int e = 0; e < TK_PER; ++e) {
         if (e >= nv) continue;
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
   int buf = 0;
   for (int64_t c0 = 0; c0 < n; c0 += CHUNK, buf ^= 1) {
     const int64_t j0 = c0 + (int64_t)tid * TK_PER;
-    const int nv = load8(row, j0, n, vec, rank, r, k);
+    const int nv = KeyRow<uint16_t>::load(row, j0, n, vec, rank, r, k);
     uint32_t mine = 0;
 #pragma unroll
     for (int e = 0; e < TK_PER; ++e)
@@ -178,7 +179,8 @@ int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld
   if (top < 1 || top > n) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = %lld)", top, (long long)n);
   if (top > DA_TOPK_MAX)
     return fail(DA_ERR_UNSUPPORTED, "top-k per row keeps its candidates in a fixed LDS buffer: top <= %d (got %d)", DA_TOPK_MAX, top);
-  if (rows > 0x7fffffffLL || n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "key block too large for one launch");
+  int rc;
+  if ((rc = block_shape_ok(rows, n)) != DA_OK) return rc;
   if (rank_bits <= 0 || rank_bits > 16) rank_bits = 16;
   const int shift = rank_bits > 8 ? rank_bits - 8 : 0;
   // a row of up to 1024 keys is two chunks of one wave: four times as many rows in flight per CU as with 256 threads

@@ -370,6 +370,50 @@ def test_pieces_many_rows_and_a_hot_key(da):
         run_rank_pieces(keys, 4000, 2000, n + 4 - n % 4, 0, True, 500, 0)
 
 
+@pytest.mark.parametrize("n", [1, 1024, 1025])
+def test_pieces_the_16_bit_and_the_32_bit_instantiation_agree(da, n):
+    """One block of keys below 65 536 through da_dev_threshold_rows_count / _emit as uint16 with keep[v] = (v >= r_min) and through
+    da_dev_threshold_ranks_count / _emit as uint32 (rectangle, the same r_min): the same row pointers, columns and keys, element for element.
+    n = 1: a lone tail; 1024 / 1025: the two sides of the one-wave / 256-thread switch.  ld = n + 3 and a base one key into the allocation put
+    rows off the 16-byte boundary (the single-key loads); the capacity is one below the total, so the last slot stays as it was."""
+    from dynaalign_amd import _capi, device
+    lib = _capi.load()
+    rng = np.random.RandomState(500 + n)
+    rows, ld, nbins, r_min = 3, n + 3, 65536, 40000
+    keys = rng.randint(0, nbins, (rows, n)).astype(np.uint32)
+    keys[rng.rand(rows, n) < 0.3] = 0                               # key 0: the 16-bit form decides it from a register
+    keys[:, -1] = nbins - 1 - np.arange(rows)                       # every row keeps its last column: the total is at least 3
+    keep = (np.arange(nbins) >= r_min).astype(np.uint8)
+    _, v16 = strided(rows, n, ld, torch.int16, 1)
+    _, v32 = strided(rows, n, ld, torch.int32, 1)
+    v16.copy_(torch.from_numpy(keys.astype(np.uint16).view(np.int16)).cuda())
+    v32.copy_(torch.from_numpy(keys.view(np.int32)).cuda())
+    keep_t = torch.from_numpy(keep).cuda()
+    p16, j16, k16 = device.threshold_rows(v16, keep_t)
+    p32, j32, k32 = device.threshold_ranks(v32, r_min, nbins)
+    torch.cuda.synchronize()
+    want_ptr = np.concatenate([[0], np.cumsum((keys >= r_min).sum(axis=1))])
+    total = int(want_ptr[-1])
+    assert total >= 3
+    want_j, want_key = np.nonzero(keys >= r_min)[1], keys[keys >= r_min]      # row-major: rows ascending, columns ascending within a row
+    assert np.array_equal(p16.cpu().numpy(), want_ptr) and np.array_equal(p32.cpu().numpy(), want_ptr)
+    assert np.array_equal(j16.cpu().numpy(), j32.cpu().numpy()) and np.array_equal(j32.cpu().numpy(), want_j)
+    assert np.array_equal(k16.cpu().numpy().view(np.uint16).astype(np.uint32), u32(k32)) and np.array_equal(u32(k32), want_key)
+    stream = torch.cuda.current_stream().cuda_stream
+    dj16, dj32, dk32 = (torch.full((total + 4,), -7, dtype=torch.int32, device="cuda") for _ in range(3))
+    dk16 = torch.full((total + 4,), -7, dtype=torch.int16, device="cuda")
+    _capi.check(lib.da_dev_threshold_rows_emit(v16.data_ptr(), rows, n, ld, keep_t.data_ptr(), nbins, p16.data_ptr(), dj16.data_ptr(), dk16.data_ptr(),
+                                               total - 1, stream))
+    _capi.check(lib.da_dev_threshold_ranks_emit(v32.data_ptr(), rows, n, ld, r_min, nbins, 0, 0, 0, p32.data_ptr(), dj32.data_ptr(), dk32.data_ptr(),
+                                                total - 1, stream))
+    torch.cuda.synchronize()
+    assert np.array_equal(dj16.cpu().numpy(), dj32.cpu().numpy())   # the sentinels behind the capacity included
+    assert np.array_equal(dj16[:total - 1].cpu().numpy(), j16[:total - 1].cpu().numpy())
+    assert np.array_equal(dk16[:total - 1].cpu().numpy().view(np.uint16).astype(np.uint32), u32(dk32[:total - 1]))
+    assert np.array_equal(dk16[:total - 1].cpu().numpy(), k16[:total - 1].cpu().numpy())
+    assert bool((dj16[total - 1:] == -7).all()) and bool((dk16[total - 1:] == -7).all()) and bool((dk32[total - 1:] == -7).all())
+
+
 @pytest.mark.parametrize("max_len", [3, 127, 1024])
 def test_codes_to_ranks_against_the_host_table(da, max_len):
     from dynaalign_amd import device, nw_value_ranks

@@ -27,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 MATRIX, GO, GE, P, LEN_HA = "BLOSUM62", 10, 4, 0.8, 566
-NEW_KERNELS = ("k_codes_to_ranks", "k_rank_histogram", "k_rank_count", "k_rank_emit")
+NEW_KERNELS = ("k_codes_to_ranks", "k_rank_histogram", "k_threshold_count", "k_threshold_emit")
 
 
 def stats(ms):
