@@ -17,6 +17,7 @@ DA_ERR_EMPTY_INPUT, DA_ERR_BAD_K, DA_ERR_BAD_NHASH, DA_ERR_BAD_MATRIX = 1, 2, 3,
 DA_ERR_BAD_RESIDUE_SEQ1, DA_ERR_BAD_RESIDUE_SEQ2, DA_ERR_NOMEM, DA_ERR_NO_DEVICE = 5, 6, 7, 8
 DA_ERR_HIP, DA_ERR_UNSUPPORTED, DA_ERR_BAD_ARG = 9, 10, 11
 DA_OUT_F64, DA_OUT_COMPACT, DA_OUT_PACK32 = 0, 1, 2
+DA_KNN_UNION, DA_KNN_MUTUAL = 0, 1   # da_dev_knn_edges: which pairs of the nearest-neighbour lists become edges
 DA_TOPK_MAX = 1024   # da_dev_topk_rows: the candidates of a row are sorted in a fixed LDS buffer
 
 _vp, _i64, _i32, _u32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_uint32, C.c_size_t
@@ -63,6 +64,12 @@ SIGNATURES = {
     "da_dev_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "da_mh_cross_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "da_dev_topk_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "da_dev_topk_rows_self": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "da_similarity_mh_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "da_similarity_nw_knn": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "da_dev_similarity_mh_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
+    "da_dev_knn_edges_bytes": (_sz, [_i64, _i32]),
+    "da_dev_knn_edges": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "da_dev_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
     "da_similarity_mh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _i32, _vp, _vp, _vp]),
     "da_similarity_nw_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp]),

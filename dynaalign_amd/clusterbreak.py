@@ -164,6 +164,18 @@ def _run_cluster_fn(cluster_fn, n, i, j, w, cluster_wt, seed):
     return out.astype(np.int64)
 
 
+def _csr_to_edges(ptr, adj, codes, loops, values):
+    """the symmetric CSR of MinHashSession.edges_csr / knn_csr as the edge list (i <= j, weight) sorted by (i, j), self-loops included"""
+    n = len(ptr) - 1
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+    up = adj > rows
+    ei, ej, ew = rows[up], adj[up].astype(np.int64), values[codes[up]]
+    has = np.nonzero(loops != 0xFFFF)[0]
+    ei, ej, ew = np.concatenate([ei, has]), np.concatenate([ej, has]), np.concatenate([ew, values[loops[has]]])
+    order = np.lexsort((ej, ei))
+    return ei[order].astype(np.int32), ej[order].astype(np.int32), ew[order]
+
+
 class ClusterbreakResult(dict):
     """list(clustered_seq = <n x 2: sequence, "<itr>.<cluster>">, filtered_seq = <sequences>) of the reference
     (R/clusterbreak.R:257-258), plus bookkeeping the reference only prints: .convergence (1 / 0, :200,:213),
@@ -171,7 +183,7 @@ class ClusterbreakResult(dict):
 
 
 def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_fn=None, cluster_fn=None,
-                 cluster_wt=True, *, session=None, edges_fn=None, cluster_seed=0, verbose=False, log=None):
+                 cluster_wt=True, *, session=None, edges_fn=None, cluster_seed=0, verbose=False, log=None, knn=None, knn_mode="union"):
     """Recursive quantile-threshold + Louvain splitting, reference clusterbreak (R/clusterbreak.R:180-275).
 
     pep        sequences (character vector)
@@ -181,6 +193,10 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
                0-based): called on every level's sequences in place of sim_fn + threshold_edges_dense, e.g.
                ``lambda s: similarityNW_edges_long(s, thresh_p=0.8)``; a level of fewer than 2 sequences does not call it
     cluster_fn (n, i, j, w, seed=, weights=) -> ids; default `louvain` with resolution 1.05
+    knn        with a session: a level of m >= 2 sequences clusters on the kNN graph session.knn_csr(idx, min(knn, m - 1), knn_mode) -- at most
+               m * knn edges in place of the quantile's fixed share of m^2 (thresh_p is not used); knn_mode "union" or "mutual".  Without a
+               session give the graph as ``edges_fn=lambda s: similarityMH_knn_edges(s, k, n_hash, top, mode)``.  The memberships are not
+               those of the quantile threshold: it is another graph.  None (default): the quantile threshold
     cluster_seed  call number c of the recursion clusters with seed cluster_seed + c (the reference draws from
                R's global RNG instead)
     """
@@ -193,6 +209,14 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
         raise ValueError("session holds %d sequences, pep has %d" % (session.n, len(pep)))
     if edges_fn is not None and session is not None:
         raise ValueError("edges_fn and session both produce a level's edge list: give one of them")
+    if knn is not None:
+        if session is None:
+            raise ValueError("knn needs a session; without one give the kNN graph as edges_fn=lambda s: similarityMH_knn_edges(s, k, n_hash, top, mode)")
+        if knn_mode not in ("union", "mutual"):
+            raise ValueError("knn_mode must be 'union' or 'mutual'")
+        knn = int(knn)
+        if knn < 1:
+            raise ValueError("knn must be at least 1")
     if sim_fn is None and session is None and edges_fn is None:
         from .similarity import similarityMH
         sim_fn = lambda x: similarityMH(x, k=2, n_hash=50)                               # noqa: E731  (:185)
@@ -215,6 +239,9 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
             if edges_fn is not None:
                 thr, ei, ej, ew = edges_fn([pep[t] for t in idx])
                 return float(thr), np.asarray(ei, np.int32), np.asarray(ej, np.int32), np.asarray(ew, np.float64)
+            if knn is not None:
+                thr, _, ptr, adj, codes, loops, values = session.knn_csr(idx, min(knn, m - 1), knn_mode)
+                return (thr,) + _csr_to_edges(ptr, adj, codes, loops, values)
             return session.edges(idx, thresh_p, sort=False)
         return threshold_edges_dense(sim_fn([pep[t] for t in idx]), thresh_p)
 
@@ -229,7 +256,10 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
         seed_c = (int(cluster_seed) + itr) & 0xFFFFFFFF
         if csr_path and m >= 2:
             # device edge path + built-in Louvain: the graph arrives as canonical CSR sorted on the device (same graph, same result)
-            thr, n_edges, ptr, adj, codes, loops, values = session.edges_csr(idx, thresh_p)
+            if knn is not None:
+                thr, n_edges, ptr, adj, codes, loops, values = session.knn_csr(idx, min(knn, m - 1), knn_mode)
+            else:
+                thr, n_edges, ptr, adj, codes, loops, values = session.edges_csr(idx, thresh_p)
             t1 = time.perf_counter()
             c_index = louvain_csr(m, ptr, adj, codes, loops, values, seed=seed_c, weights=True).astype(np.int64)   # :222 (built-in: see _run_cluster_fn)
             del ptr, adj, codes, loops

@@ -1233,10 +1233,31 @@ int da_dev_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld
   return launch_topk_rows(d_keys, rows, n, ld, d_rank, rank_bits, top, d_idx, ld_out, d_key_out, ld_out, static_cast<hipStream_t>(stream));
 }
 
+// the same selection with every row's own column left out: row r of the block owns column self_col0 + r (dynaalign.h)
+int da_dev_topk_rows_self(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int64_t self_col0,
+                          int32_t *d_idx, uint16_t *d_key_out, int64_t ld_out, uint16_t *d_self_key, void *stream) {
+  if (rows < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (rows == 0) return DA_OK;
+  if (!d_keys || !d_idx || !d_key_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld < n) return fail(DA_ERR_BAD_ARG, "ld (%lld) < n (%lld)", (long long)ld, (long long)n);
+  if (rank_bits < 0 || rank_bits > 16) return fail(DA_ERR_BAD_ARG, "rank_bits must be 0 .. 16 (got %d)", rank_bits);
+  if (top >= 1 && top <= n - 1 && top <= DA_TOPK_MAX && ld_out < top) return fail(DA_ERR_BAD_ARG, "ld_out (%lld) < top (%d)", (long long)ld_out, top);
+  return launch_topk_rows_self(d_keys, rows, n, ld, d_rank, rank_bits, top, self_col0, d_idx, ld_out, d_key_out, ld_out, d_self_key,
+                               static_cast<hipStream_t>(stream));
+}
+
 namespace {
 // 1 <= top <= n (DA_ERR_BAD_ARG), top <= DA_TOPK_MAX (DA_ERR_UNSUPPORTED): what every top-k entry point says after its own validation
 int topk_check(int top, int64_t n) {
   if (top < 1 || top > n) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = %lld)", top, (long long)n);
+  if (top > DA_TOPK_MAX)
+    return fail(DA_ERR_UNSUPPORTED, "top-k per row keeps its candidates in a fixed LDS buffer: top <= %d (got %d)", DA_TOPK_MAX, top);
+  return DA_OK;
+}
+// the one-set lists: a second sequence, 1 <= top <= n - 1 (DA_ERR_BAD_ARG), top <= DA_TOPK_MAX (DA_ERR_UNSUPPORTED, topk_check's text)
+int knn_check(int top, int64_t n) {
+  if (n < 2) return fail(DA_ERR_BAD_ARG, "a nearest neighbour needs a second sequence");
+  if (top < 1 || top > n - 1) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n - 1 (got top = %d, n = %lld)", top, (long long)n);
   if (top > DA_TOPK_MAX)
     return fail(DA_ERR_UNSUPPORTED, "top-k per row keeps its candidates in a fixed LDS buffer: top <= %d (got %d)", DA_TOPK_MAX, top);
   return DA_OK;
@@ -1249,9 +1270,11 @@ int bits_of(int64_t max_value) {
 // Rows [0, m) of a two-set rectangle with n columns, selected block by block: compute(b0, b1, d, ld) writes the uint16 codes of rows [b0, b1)
 // to the scratch block d (leading dimension ld: n rounded up to a multiple of 8, so that rows are read in 16-byte units), then
 // da_dev_topk_rows' kernel takes `top` of every row into d_idx / d_key.  The block is sized like rows_to_host's: by the column count alone.
-// Synchronises the stream (the scratch block goes back to the cache).
+// Synchronises the stream (the scratch block goes back to the cache).  self: the rectangle is the square problem's own rows (m == n, columns
+// [0, n)), so the block starting at row b0 runs the self form of the selection with self_col0 = b0; d_self_key (may be NULL) receives the diagonal keys.
 int topk_blocks(int64_t m, int64_t n, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx, int64_t ld_idx, uint16_t *d_key,
-                int64_t ld_key, hipStream_t stream, const std::function<int(int64_t, int64_t, void *, int64_t)> &compute) {
+                int64_t ld_key, hipStream_t stream, const std::function<int(int64_t, int64_t, void *, int64_t)> &compute, bool self = false,
+                uint16_t *d_self_key = nullptr) {
   const int64_t ld = (n + 7) / 8 * 8;
   const int64_t blk = std::min(block_rows(ld, sizeof(uint16_t)), m);
   DevBuf d;
@@ -1260,11 +1283,31 @@ int topk_blocks(int64_t m, int64_t n, const uint16_t *d_rank, int rank_bits, int
   for (int64_t b0 = 0; b0 < m; b0 += blk) {
     const int64_t b1 = std::min(m, b0 + blk);
     if ((rc = compute(b0, b1, d.p, ld)) != DA_OK) return rc;
-    if ((rc = launch_topk_rows(d.as<uint16_t>(), b1 - b0, n, ld, d_rank, rank_bits, top, d_idx + b0 * ld_idx, ld_idx, d_key + b0 * ld_key, ld_key,
-                               stream)) != DA_OK) return rc;
+    rc = self ? launch_topk_rows_self(d.as<uint16_t>(), b1 - b0, n, ld, d_rank, rank_bits, top, b0, d_idx + b0 * ld_idx, ld_idx, d_key + b0 * ld_key,
+                                      ld_key, d_self_key ? d_self_key + b0 : nullptr, stream)
+              : launch_topk_rows(d.as<uint16_t>(), b1 - b0, n, ld, d_rank, rank_bits, top, d_idx + b0 * ld_idx, ld_idx, d_key + b0 * ld_key, ld_key, stream);
+    if (rc != DA_OK) return rc;
   }
   DA_HIP_TRY(hipStreamSynchronize(stream));
   return DA_OK;
+}
+// The nearest-neighbour lists of ONE resident set: K1 once on its n sequences, the planes once (no joint operand, no padding rows), then the
+// rows [b0, b1) x columns [0, n) of the square problem block by block through the self form of the selection.
+int mh_knn_lists(const uint8_t *d_res, const int64_t *d_off, int64_t n, int k, int n_hash, const uint32_t *d_seeds, int top, int32_t *d_idx,
+                 int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream) {
+  int rc, bits = 32;
+  const int64_t lds = sig_ld_for(n_hash);
+  const size_t wb = mh_planes_workspace_bytes(n, n_hash);
+  DevBuf sig, planes, work;
+  if ((rc = sig.alloc((size_t)n * lds * sizeof(uint32_t))) != DA_OK ||
+      (rc = planes.alloc((size_t)mh_planes_words(n, n_hash) * sizeof(uint32_t))) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+  if ((rc = launch_minhash_signatures(d_res, d_off, n, k, n_hash, d_seeds, sig.as<uint32_t>(), lds, stream)) != DA_OK ||
+      (rc = build_planes(sig.as<uint32_t>(), lds, n, n_hash, 0, work.p, wb, planes.as<uint32_t>(), &bits, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  work.release(); sig.release();                         // before the scratch block is sized
+  return topk_blocks(n, n, nullptr, bits_of(n_hash), top, d_idx, ld_idx, d_key, ld_key, stream, [&](int64_t b0, int64_t b1, void *d, int64_t ld) {
+    return launch_mh_compare_rect(planes.as<uint32_t>(), n, n_hash, b0, b1, 0, n, DA_OUT_COMPACT, d, ld, stream, bits);
+  }, true);
 }
 int mh_cross_topk(MhCrossOperand &c, int n_hash, int top, int32_t *d_idx, int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream) {
   DA_HIP_TRY(hipStreamSynchronize(stream));
@@ -1294,6 +1337,41 @@ int da_dev_similarity_mh_cross_topk(const uint8_t *d_x_residues, const int64_t *
   if ((rc = launch_topk_values(key.as<uint16_t>(), top, m, top, n_hash, d_val, ld_out, stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipStreamSynchronize(stream));              // the key block goes back to the cache after this
   return DA_OK;
+}
+
+// ---- one set against itself: every sequence's `top` nearest other sequences, and the graph those lists define ---------------------------------
+int da_dev_similarity_mh_knn(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int k, int n_hash, const uint32_t *d_seeds, int top,
+                             int32_t *d_idx, double *d_val, int64_t ld_out, void *stream_v) {
+  int rc;
+  if ((rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;
+  if (!d_residues || !d_offsets || !d_seeds || !d_idx || !d_val) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if ((rc = knn_check(top, n)) != DA_OK) return rc;
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: n_hash <= 65535 (got %d)", n_hash);
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "nearest-neighbour lists: too many sequences");
+  if (ld_out < top) return fail(DA_ERR_BAD_ARG, "ld_out (%lld) < top (%d)", (long long)ld_out, top);
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  DevBuf key;
+  if ((rc = key.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  if ((rc = mh_knn_lists(d_residues, d_offsets, n, k, n_hash, d_seeds, top, d_idx, ld_out, key.as<uint16_t>(), top, stream)) != DA_OK) return rc;
+  if ((rc = launch_topk_values(key.as<uint16_t>(), top, n, top, n_hash, d_val, ld_out, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));              // the key block goes back to the cache after this
+  return DA_OK;
+}
+
+size_t da_dev_knn_edges_bytes(int64_t n, int top) { return knn_edges_workspace_bytes(n, top); }
+
+int da_dev_knn_edges(const int32_t *d_idx, const uint16_t *d_key, int64_t ld, int64_t n, int top, int mode, int is_nw, const uint16_t *d_self_key,
+                     int self_code, int loops, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_v, uint64_t *d_count,
+                     void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (top < 1 || top > DA_TOPK_MAX) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. %d (got %d)", DA_TOPK_MAX, top);
+  if (ld < top) return fail(DA_ERR_BAD_ARG, "ld (%lld) < top (%d)", (long long)ld, top);
+  if (mode != DA_KNN_UNION && mode != DA_KNN_MUTUAL) return fail(DA_ERR_BAD_ARG, "mode must be DA_KNN_UNION or DA_KNN_MUTUAL (got %d)", mode);
+  if (self_code < 0 || self_code > 65535) return fail(DA_ERR_BAD_ARG, "self_code must be a uint16 code (got %d)", self_code);
+  if (!d_idx || !d_key || !d_work || !d_i || !d_j || !d_v || !d_count) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (reinterpret_cast<uintptr_t>(d_work) & 255) return fail(DA_ERR_BAD_ARG, "workspace must be 256-byte aligned");
+  return launch_knn_edges(d_idx, d_key, ld, n, top, mode == DA_KNN_MUTUAL, is_nw != 0, d_self_key, self_code, loops != 0, d_work, work_bytes, d_i, d_j,
+                          d_v, d_count, static_cast<hipStream_t>(stream));
 }
 
 // ---- pieces of the duplicate-collapsing routes for callers that orchestrate the steps themselves (the one-process-per-GPU
@@ -2552,6 +2630,68 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
   return topk_to_host(didx, dkey, m, top, nw_code_values(65536, 0.0), idx_out, val_out);
 }
 
+
+// ---- one set, nearest-neighbour lists on the host boundary: row i lists the `top` columns j != i of the square matrix (dynaalign.h) -------------
+int da_similarity_mh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int top,
+                         int32_t *idx_out, double *val_out) {
+  int rc = validate_mh(n, k, n_hash);                    // the checks of da_similarity_mh, in its order
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !idx_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = knn_check(top, n)) != DA_OK) return rc;
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the compare kernel counts in 16 bits: n_hash <= 65535 (got %d)", n_hash);
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "nearest-neighbour lists: too many sequences");
+  if ((rc = require_device()) != DA_OK) return rc;
+  DeviceInput in;
+  DevBuf didx, dkey;
+  if ((rc = in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = didx.alloc((size_t)n * (size_t)top * sizeof(int32_t))) != DA_OK || (rc = dkey.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  if ((rc = mh_knn_lists(in.res.as<uint8_t>(), in.off.as<int64_t>(), n, k, n_hash, in.seeds.as<uint32_t>(), top, didx.as<int32_t>(), top,
+                         dkey.as<uint16_t>(), top, nullptr)) != DA_OK) return rc;
+  return topk_to_host(didx, dkey, n, top, mh_code_values(n_hash), idx_out, val_out);
+}
+
+int da_similarity_nw_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext, int top,
+                         int32_t *idx_out, double *val_out, double *diag_out) {
+  const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (!residues || !idx_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int rc;
+  if ((rc = knn_check(top, n)) != DA_OK) return rc;      // where da_similarity_nw_edges checks n >= 2 and thresh_p
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] == offsets[i])
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld is empty: its similarities are 0/0 = NaN and a NaN has no place in an order", (long long)(i + 1));
+  if (max_len > 127) return fail(DA_ERR_UNSUPPORTED, "the NW nearest-neighbour lists work on uint16 codes: sequences up to 127 residues");
+  if ((rc = require_device()) != DA_OK) return rc;
+  NwCodes nw;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+  // equal values tie whatever their codes (2/4 and 3/6): the selection orders by the dense rank of a code's double value
+  std::vector<uint16_t> ranks(65536);
+  int distinct = 0;
+  if ((rc = da_nw_code_ranks((int)max_len, ranks.data(), &distinct)) != DA_OK) return rc;
+  DevBuf drank, didx, dkey, dself;
+  if ((rc = drank.alloc(65536 * sizeof(uint16_t))) != DA_OK || (rc = didx.alloc((size_t)n * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK || (rc = dself.alloc((size_t)n * sizeof(uint16_t))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(drank.p, ranks.data(), 65536 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  // on ONE code buffer pair (p, q) is calc(seq[min(p, q)], seq[max(p, q)]): rows [b0, b1) x columns [0, n) are rows of the mirrored square matrix
+  rc = topk_blocks(n, n, drank.as<uint16_t>(), bits_of(distinct - 1), top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) {
+                     return launch_nw_rect(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, 0, n, DA_OUT_COMPACT,
+                                           d, ld, nullptr);
+                   }, true, dself.as<uint16_t>());
+  if (rc != DA_OK) return rc;
+  const std::vector<double> table = nw_code_values(65536, 0.0);
+  if (diag_out) {
+    std::vector<uint16_t> sk((size_t)n);
+    DA_HIP_TRY(hipMemcpy(sk.data(), dself.p, (size_t)n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) diag_out[i] = table[sk[(size_t)i]];
+  }
+  return topk_to_host(didx, dkey, n, top, table, idx_out, val_out);
+}
 
 // ---- the alignment PATH of listed pairs (nw_align_kernels.hip): which residue sits opposite which, and where the gaps are -------------------
 size_t da_nw_align_workspace_bytes(int64_t pairs) { return nw_align_workspace_bytes(pairs); }

@@ -286,11 +286,21 @@ int launch_gather_columns(const uint16_t *d_D, int64_t ld_d, const int32_t *d_ui
 size_t edges_to_csr_workspace_bytes(int64_t m, int64_t n);
 int launch_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_v, int64_t m, int64_t n, void *d_work, size_t work_bytes,
                         int64_t *d_ptr, int32_t *d_adj, uint16_t *d_codes, uint16_t *d_loops, hipStream_t stream);
+// graph_kernels.hip: nearest-neighbour lists (n rows of ld >= top columns and their uint16 keys) -> the (i <= j, code) edge list of their union /
+// mutual kNN graph, the diagonal first in every row's share when `loops` (da_dev_knn_edges); d_i / d_j / d_v hold n * (top + loops) entries
+size_t knn_edges_workspace_bytes(int64_t n, int top);
+int launch_knn_edges(const int32_t *d_idx, const uint16_t *d_key, int64_t ld, int64_t n, int top, bool mutual, bool is_nw, const uint16_t *d_self_key,
+                     int self_code, bool loops, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_v, uint64_t *d_count,
+                     hipStream_t stream);
 // topk_kernels.hip: per-row exact top-k of uint16 keys by (rank descending, column ascending) (da_dev_topk_rows); index and key rows have
 // their own leading dimensions.  ... and the selected MinHash counts as doubles: d_val[r * ld_val + t] = d_key[r * ld_key + t] / n_hash
 constexpr int DA_TOPK_MAX = 1024;
 int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
                      int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, hipStream_t stream);
+// ... with every row's own column left out of the selection: the block's row r owns column self_col0 + r (a row block of a square problem), and
+// its key goes to d_self_key[r] when that pointer is given; 1 <= top <= n - 1 (da_dev_topk_rows_self)
+int launch_topk_rows_self(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int64_t self_col0,
+                          int32_t *d_idx, int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, uint16_t *d_self_key, hipStream_t stream);
 int launch_topk_values(const uint16_t *d_key, int64_t ld_key, int64_t rows, int top, int n_hash, double *d_val, int64_t ld_val, hipStream_t stream);
 // rect_edges_kernels.hip: the threshold form of a two-set rectangle, on a block of `rows` rows of ld >= n uint16 keys (da_dev_rect_histogram,
 // da_dev_threshold_rows_count / _emit): histogram of the whole block; per-row count of the keys flagged in d_keep + exclusive scan -> row

@@ -266,6 +266,87 @@ int launch_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *
   return DA_OK;
 }
 
+// ---- nearest-neighbour lists -> the (i <= j, code) edge list of their kNN graph (da_dev_knn_edges) -------------------------------------------
+// Row r of idx / key (n rows of ld >= top entries) lists r's neighbours and their uint16 keys; an entry is live when its key stands for a
+// value > 0.  in(i, j): j appears live in row i.  union keeps the pair {i, j} when in(i, j) or in(j, i), mutual when both hold.  One wave per
+// source row r decides, for t ascending, which pairs r is responsible for -- so every pair is emitted exactly once, at a position that depends
+// on the data alone (count pass, exclusive scan, emit pass; no output atomic):
+//   union,  j > r: (r, j);   union, j < r: (j, r) unless in(j, r), in which case row j has emitted it;   mutual: (r, j) when j > r and in(j, r).
+// The membership test in(j, r) is a scan of row j's `top` entries by the 64 lanes; it does not rely on the lists being symmetric.
+namespace {
+constexpr int KNN_THREADS = 256;
+__device__ __forceinline__ bool knn_live(uint32_t key, int is_nw) { return (is_nw ? (key >> 8) : key) != 0; }
+
+template <bool EMIT>
+__global__ __launch_bounds__(KNN_THREADS) void k_knn_edges(const int32_t *__restrict__ idx, const uint16_t *__restrict__ key, int64_t ld, int64_t n, int top,
+                                                           int mutual, int is_nw, const uint16_t *__restrict__ self_key, uint32_t self_code, int loops,
+                                                           long long *__restrict__ cnt, const long long *__restrict__ rowptr, int32_t *__restrict__ out_i,
+                                                           int32_t *__restrict__ out_j, uint16_t *__restrict__ out_v) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * (KNN_THREADS / 64) + (threadIdx.x >> 6);
+  if (r >= n) return;                            // wave-uniform
+  long long at = EMIT ? rowptr[r] : 0;
+  if (loops) {
+    if (EMIT && lane == 0) { out_i[at] = (int32_t)r; out_j[at] = (int32_t)r; out_v[at] = self_key ? self_key[r] : (uint16_t)self_code; }
+    ++at;
+  }
+  for (int t = 0; t < top; ++t) {
+    const int64_t j = idx[r * ld + t];           // the same address in every lane
+    const uint32_t kv = key[r * ld + t];
+    if (!knn_live(kv, is_nw) || j < 0 || j >= n || j == r) continue;
+    bool in = false;
+    if (mutual ? j > r : j < r) {                // in(j, r)?
+      for (int s0 = 0; s0 < top && !in; s0 += 64) {
+        const int s = s0 + lane;
+        const bool hit = s < top && idx[j * ld + s] == (int32_t)r && knn_live(key[j * ld + s], is_nw);
+        in = __any(hit) != 0;
+      }
+    }
+    const bool emit = mutual ? (j > r && in) : (j > r || !in);
+    if (!emit) continue;
+    if (EMIT && lane == 0) {
+      out_i[at] = (int32_t)(j > r ? r : j);
+      out_j[at] = (int32_t)(j > r ? j : r);
+      out_v[at] = (uint16_t)kv;
+    }
+    ++at;
+  }
+  if (!EMIT && lane == 0) cnt[r] = at;
+}
+size_t knn_up256(size_t b) { return (b + 255) / 256 * 256; }
+}  // namespace
+
+// workspace: the per-row counts and the row pointers (n + 1 int64 each) + the scan's own scratch
+size_t knn_edges_workspace_bytes(int64_t n, int top) {
+  if (n <= 0) return 256;
+  size_t temp = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, temp, (const long long *)nullptr, (long long *)nullptr, (int)(n + 1), nullptr);
+  return 2 * knn_up256((size_t)(n + 1) * 8) + knn_up256(temp) + 256;
+}
+
+int launch_knn_edges(const int32_t *d_idx, const uint16_t *d_key, int64_t ld, int64_t n, int top, bool mutual, bool is_nw, const uint16_t *d_self_key,
+                     int self_code, bool loops, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_v, uint64_t *d_count,
+                     hipStream_t stream) {
+  if (n <= 0) return DA_OK;
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "edge indices are int32");
+  if (work_bytes < knn_edges_workspace_bytes(n, top)) return fail(DA_ERR_BAD_ARG, "kNN edges: workspace too small");
+  char *w = static_cast<char *>(d_work);
+  long long *cnt = reinterpret_cast<long long *>(w); w += knn_up256((size_t)(n + 1) * 8);
+  long long *rowptr = reinterpret_cast<long long *>(w); w += knn_up256((size_t)(n + 1) * 8);
+  size_t temp = work_bytes - (size_t)(w - static_cast<char *>(d_work));
+  const dim3 grid((unsigned)ceil_div(n, KNN_THREADS / 64));
+  DA_HIP_TRY(hipMemsetAsync(cnt + n, 0, 8, stream));
+  hipLaunchKernelGGL(k_knn_edges<false>, grid, dim3(KNN_THREADS), 0, stream, d_idx, d_key, ld, n, top, mutual ? 1 : 0, is_nw ? 1 : 0, d_self_key,
+                     (uint32_t)self_code, loops ? 1 : 0, cnt, (const long long *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (uint16_t *)nullptr);
+  DA_HIP_TRY(hipGetLastError());
+  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(w, temp, cnt, rowptr, (int)(n + 1), stream));
+  hipLaunchKernelGGL(k_knn_edges<true>, grid, dim3(KNN_THREADS), 0, stream, d_idx, d_key, ld, n, top, mutual ? 1 : 0, is_nw ? 1 : 0, d_self_key,
+                     (uint32_t)self_code, loops ? 1 : 0, (long long *)nullptr, rowptr, d_i, d_j, d_v);
+  DA_HIP_TRY(hipGetLastError());
+  DA_HIP_TRY(hipMemcpyAsync(d_count, rowptr + n, 8, hipMemcpyDeviceToDevice, stream));   // the total: the last row pointer
+  return DA_OK;
+}
+
 static Layout make_layout(int64_t n, int rank, int world, const int32_t *rowmap = nullptr) {
   Layout lay;
   lay.g = shard_geom(n, world > 0 ? world : 1, G_TILE);

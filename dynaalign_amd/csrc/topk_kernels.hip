@@ -37,10 +37,14 @@ __device__ __forceinline__ void pick_bin(const unsigned int *hist, uint32_t want
   }
 }
 
-template <int THREADS>
+// SELF: the block's row r owns column self_col0 + r (a row block of a square problem) and that element is absent from all three passes, so
+// T, above, need_eq and the choice among equals are those of the row without it; its key goes to self_key[r] when that pointer is given (the
+// NW diagonal).  An own column outside [0, n) excludes nothing.
+template <int THREADS, bool SELF>
 __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restrict__ keys, int64_t n, int64_t ld,
                                                        const uint16_t *__restrict__ rank, int shift, int top, int32_t *__restrict__ idx,
-                                                       int64_t ld_idx, uint16_t *__restrict__ key_out, int64_t ld_key) {
+                                                       int64_t ld_idx, uint16_t *__restrict__ key_out, int64_t ld_key, int64_t self_col0,
+                                                       uint16_t *__restrict__ self_key) {
   constexpr int WAVES = THREADS / 64;
   constexpr int CHUNK = THREADS * TK_PER;
   __shared__ unsigned int hist[256];
@@ -52,6 +56,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
   const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
   const uint32_t lo_mask = (1u << shift) - 1u;
   uint32_t r[TK_PER], k[TK_PER];
+  const int64_t own = SELF ? self_col0 + (int64_t)blockIdx.x : -1;   // e == own - j0 names the own element inside a thread's TK_PER columns
 
   // ---- 1a. the high digit
   for (int b = tid; b < 256; b += THREADS) hist[b] = 0;
@@ -59,10 +64,15 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
   __syncthreads();
   uint32_t zeros = 0;
   for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
-    const int nv = KeyRow<uint16_t>::load(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
+    const int64_t j0 = c0 + (int64_t)tid * TK_PER;
+    const int nv = KeyRow<uint16_t>::load(row, j0, n, vec, rank, r, k);
 #pragma unroll
     for (int e = 0; e < TK_PER; ++e) {
       if (e >= nv) continue;
+      if (SELF && own - j0 == e) {
+        if (self_key) self_key[blockIdx.x] = (uint16_t)k[e];
+        continue;
+      }
       if (r[e] == 0) ++zeros;
       else { const uint32_t h = r[e] >> shift; atomicAdd(&hist[h < 255u ? h : 255u], 1u); }
     }
@@ -80,10 +90,12 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
     __syncthreads();
     zeros = 0;
     for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
-      const int nv = KeyRow<uint16_t>::load(row, c0 + (int64_t)tid * TK_PER, n, vec, rank, r, k);
+      const int64_t j0 = c0 + (int64_t)tid * TK_PER;
+      const int nv = KeyRow<uint16_t>::load(row, j0, n, vec, rank, r, k);
 #pragma unroll
       for (int e = 0; e < TK_PER; ++e) {
         if (e >= nv) continue;
+        if (SELF && own - j0 == e) continue;
         if (r[e] == 0) { if (B == 0) ++zeros; }
         else if ((r[e] >> shift) == B) atomicAdd(&hist[r[e] & lo_mask], 1u);
       }
@@ -107,7 +119,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
     uint32_t mine = 0;
 #pragma unroll
     for (int e = 0; e < TK_PER; ++e)
-      if (e < nv) mine += r[e] > T ? 1u : (r[e] == T ? 0x10000u : 0u);
+      if (e < nv && !(SELF && own - j0 == e)) mine += r[e] > T ? 1u : (r[e] == T ? 0x10000u : 0u);
     const uint32_t incl = wave_incl_scan(mine);
     if (lane == 63) wtot[buf][wave] = incl;
     __syncthreads();                           // the other buffer is written next time: one barrier per chunk
@@ -123,7 +135,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
     if (mine) {
 #pragma unroll
       for (int e = 0; e < TK_PER; ++e) {
-        if (e >= nv) continue;
+        if (e >= nv || (SELF && own - j0 == e)) continue;
         const unsigned long long word = ((unsigned long long)r[e] << 48) | ((unsigned long long)(~(uint32_t)(j0 + e)) << 16) | k[e];
         if (r[e] > T) {
           if (gt_at < above && gt_at < (uint32_t)DA_TOPK_MAX) cand[gt_at] = word;
@@ -173,10 +185,14 @@ __global__ __launch_bounds__(256) void k_topk_values(const uint16_t *__restrict_
 
 }  // namespace
 
-int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
-                     int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, hipStream_t stream) {
+namespace {
+int topk_rows_launch(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
+                     int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, bool self, int64_t self_col0, uint16_t *d_self_key, hipStream_t stream) {
   if (rows <= 0) return DA_OK;
-  if (top < 1 || top > n) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = %lld)", top, (long long)n);
+  if (self) {
+    if (top < 1 || top > n - 1)
+      return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n - 1 when a row's own column is excluded (got top = %d, n = %lld)", top, (long long)n);
+  } else if (top < 1 || top > n) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = %lld)", top, (long long)n);
   if (top > DA_TOPK_MAX)
     return fail(DA_ERR_UNSUPPORTED, "top-k per row keeps its candidates in a fixed LDS buffer: top <= %d (got %d)", DA_TOPK_MAX, top);
   int rc;
@@ -184,13 +200,23 @@ int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld
   if (rank_bits <= 0 || rank_bits > 16) rank_bits = 16;
   const int shift = rank_bits > 8 ? rank_bits - 8 : 0;
   // a row of up to 1024 keys is two chunks of one wave: four times as many rows in flight per CU as with 256 threads
-  if (n <= 1024)
-    hipLaunchKernelGGL(k_topk_rows<64>, dim3((unsigned)rows), dim3(64), 0, stream, d_keys, n, ld, d_rank, shift, top, d_idx, ld_idx, d_key_out, ld_key);
-  else
-    hipLaunchKernelGGL(k_topk_rows<256>, dim3((unsigned)rows), dim3(256), 0, stream, d_keys, n, ld, d_rank, shift, top, d_idx, ld_idx, d_key_out,
-                       ld_key);
+  const bool wave = n <= 1024;
+  auto kernel = wave ? (self ? k_topk_rows<64, true> : k_topk_rows<64, false>) : (self ? k_topk_rows<256, true> : k_topk_rows<256, false>);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)rows), dim3(wave ? 64 : 256), 0, stream, d_keys, n, ld, d_rank, shift, top, d_idx, ld_idx, d_key_out, ld_key,
+                     self_col0, d_self_key);
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
+}
+}  // namespace
+
+int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int32_t *d_idx,
+                     int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, hipStream_t stream) {
+  return topk_rows_launch(d_keys, rows, n, ld, d_rank, rank_bits, top, d_idx, ld_idx, d_key_out, ld_key, false, 0, nullptr, stream);
+}
+
+int launch_topk_rows_self(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int64_t self_col0,
+                          int32_t *d_idx, int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, uint16_t *d_self_key, hipStream_t stream) {
+  return topk_rows_launch(d_keys, rows, n, ld, d_rank, rank_bits, top, d_idx, ld_idx, d_key_out, ld_key, true, self_col0, d_self_key, stream);
 }
 
 int launch_topk_values(const uint16_t *d_key, int64_t ld_key, int64_t rows, int top, int n_hash, double *d_val, int64_t ld_val, hipStream_t stream) {

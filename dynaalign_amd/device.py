@@ -444,11 +444,14 @@ def similarity_mh_cross(dx, dy, k, n_hash, seeds, out=None):
     return out
 
 
-def topk_rows(keys, top, rank=None, rank_bits=0):
+def topk_rows(keys, top, rank=None, rank_bits=0, self_col0=None, want_self=False):
     """Exact top-k per row of a block of uint16 keys (an int16 tensor of shape (rows, n), any row stride and base address), by
     (rank descending, column ascending): rank = rank[key] (a 65536-entry int16 tensor of uint16 ranks, all below 2 ** rank_bits) or
     the key itself (da_dev_topk_rows).  Returns (idx int32 (rows, top), key int16 (rows, top)): numpy's
-    argsort(-rank_of_row, kind="stable")[:top] and the keys found there."""
+    argsort(-rank_of_row, kind="stable")[:top] and the keys found there.
+    self_col0: the block is rows [self_col0, self_col0 + rows) of a square problem and row r's own column self_col0 + r is left out of
+    its selection (da_dev_topk_rows_self; 1 <= top <= n - 1); with want_self a third result, int16 (rows,), holds the key found at the
+    own column (rows whose own column is outside [0, n) keep 0)."""
     lib = _capi.load()
     _require_cuda(keys, "keys")
     assert keys.dim() == 2 and keys.dtype == torch.int16 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
@@ -460,9 +463,65 @@ def topk_rows(keys, top, rank=None, rank_bits=0):
     t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
     idx = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
     key = torch.empty((max(rows, 1), t), dtype=torch.int16, device=keys.device)
-    _call(lib.da_dev_topk_rows, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(rank_bits), int(top),
-                                     idx.data_ptr(), key.data_ptr(), t, _stream())
-    return idx[:rows], key[:rows]
+    if self_col0 is None:
+        if want_self:
+            raise ValueError("want_self needs self_col0")
+        _call(lib.da_dev_topk_rows, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(rank_bits), int(top),
+                                         idx.data_ptr(), key.data_ptr(), t, _stream())
+        return idx[:rows], key[:rows]
+    own = torch.zeros(max(rows, 1), dtype=torch.int16, device=keys.device) if want_self else None
+    _call(lib.da_dev_topk_rows_self, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(rank_bits), int(top),
+                                          int(self_col0), idx.data_ptr(), key.data_ptr(), t, None if own is None else own.data_ptr(), _stream())
+    return (idx[:rows], key[:rows], own[:rows]) if want_self else (idx[:rows], key[:rows])
+
+
+def similarity_mh_knn(ds, k, n_hash, seeds, top):
+    """The nearest-neighbour lists of a device-resident set, one C call (da_dev_similarity_mh_knn): (idx int32 (n, top), val float64
+    (n, top)).  Row i lists the `top` columns j != i of row i of similarity_mh(ds, ...) by value descending, then column ascending; the
+    n x n matrix never exists.  top is NOT clamped here (1 <= top <= n - 1)."""
+    lib = _capi.load()
+    if not torch.is_tensor(seeds):
+        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(ds.residues.device)
+    _require_cuda(ds.residues, "residues")
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    idx = torch.empty((max(ds.n, 1), t), dtype=torch.int32, device=ds.residues.device)
+    val = torch.empty((max(ds.n, 1), t), dtype=torch.float64, device=ds.residues.device)
+    _call(lib.da_dev_similarity_mh_knn, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, int(k), int(n_hash), seeds.data_ptr(), int(top),
+                                             idx.data_ptr(), val.data_ptr(), t, _stream())
+    return idx[:ds.n], val[:ds.n]
+
+
+def knn_edges(idx, key, mode="union", is_nw=False, self_key=None, self_code=0, loops=True):
+    """Nearest-neighbour lists -> the (i <= j, code) edge list of their kNN graph on the device (da_dev_knn_edges).  idx int32 (n, top) and
+    key int16 (n, top) (uint16 bit pattern) as topk_rows with self_col0 returns them; an entry is live when its key stands for a value > 0
+    (key != 0, or key >> 8 != 0 with is_nw).  mode "union" keeps {i, j} when j is in i's list or i in j's, "mutual" when both.  loops: every
+    vertex also gets (r, r, self_key[r]), or (r, r, self_code) without self_key.  Returns (ei int32, ej int32, ev int16, n_edges) with
+    ei <= ej, grouped by emitting row (NOT sorted by (i, j)): what edges_to_csr takes."""
+    lib = _capi.load()
+    _require_cuda(idx, "idx")
+    _require_cuda(key, "key")
+    if mode not in ("union", "mutual"):
+        raise ValueError("mode must be 'union' or 'mutual'")
+    assert idx.dim() == 2 and idx.dtype == torch.int32 and key.dtype == torch.int16 and key.shape == idx.shape
+    idx, key = idx.contiguous(), key.contiguous()
+    n, top = int(idx.shape[0]), int(idx.shape[1])
+    dev = idx.device
+    if self_key is not None:
+        _require_cuda(self_key, "self_key")
+        self_key = self_key.contiguous()
+        assert self_key.dtype == torch.int16 and self_key.numel() == n
+    cap = max(n * (top + (1 if loops else 0)), 1)
+    nbytes = int(lib.da_dev_knn_edges_bytes(n, top))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ei = torch.empty(cap, dtype=torch.int32, device=dev)
+    ej = torch.empty(cap, dtype=torch.int32, device=dev)
+    ev = torch.empty(cap, dtype=torch.int16, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    _call(lib.da_dev_knn_edges, idx.data_ptr(), key.data_ptr(), top, n, top, _capi.DA_KNN_MUTUAL if mode == "mutual" else _capi.DA_KNN_UNION,
+                                     1 if is_nw else 0, None if self_key is None else self_key.data_ptr(), int(self_code), 1 if loops else 0,
+                                     work.data_ptr(), nbytes, ei.data_ptr(), ej.data_ptr(), ev.data_ptr(), count.data_ptr(), _stream())
+    m = int(count.item())
+    return ei[:m], ej[:m], ev[:m], m
 
 
 def similarity_mh_cross_topk(dx, dy, k, n_hash, seeds, top):

@@ -11,6 +11,8 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     R = s.cross(new, idx)                                           # == similarityMH_cross(new, sequences[idx], 4, 500, seed=12345)
     i, v = s.cross_topk(new, 10, idx)                               # == similarityMH_cross_topk(new, sequences[idx], 4, 500, 10, seed=12345)
     thr, ptr, j, w = s.cross_edges(new, 0.99, idx=idx)              # == similarityMH_cross_edges(new, sequences[idx], 4, 500, 0.99, seed=12345) as CSR
+    i, v = s.knn(10, idx)                                           # == similarityMH_knn(sequences[idx], 4, 500, 10, seed=12345)
+    thr, m, ptr, adj, codes, loops, values = s.knn_csr(idx, 10)     # the kNN graph of those lists as CSR (== similarityMH_knn_edges(...))
     st = s.stats(idx)                                               # == similarityMH_stats(sequences[idx], 4, 500, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
@@ -157,6 +159,48 @@ class MinHashSession:
         key_all = torch.cat(keys).contiguous()
         w = device.widen(key_all, False, self.n_hash) if base else torch.empty(0, dtype=torch.float64, device=self.sig.device)
         return thr, torch.cat(ptrs), torch.cat(js), w
+
+    def _knn_lists(self, idx, top, block_bytes):
+        """device tensors (idx int32 (m, top), key int16 (m, top)) of the subset's nearest-neighbour lists, and m: subset -> planes -> row
+        blocks of the square problem (rows [b0, b1) x columns [0, m)) -> device.topk_rows with self_col0 = b0"""
+        planes, m = self.planes(idx)
+        if m < 2:
+            raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "a nearest neighbour needs a second sequence")
+        top = min(int(top), m - 1)
+        ld = -(-m // 8) * 8
+        blk = min(max(block_bytes // (2 * ld) // 128 * 128, 128), m)
+        buf = torch.empty((blk, ld), dtype=torch.int16, device=self.sig.device)
+        out_i, out_k = [], []
+        for b0 in range(0, m, blk):
+            b1 = min(m, b0 + blk)
+            cnt = device.mh_compare_rect(planes, m, self.n_hash, b0, b1, 0, m, _capi.DA_OUT_COMPACT, out=buf[:b1 - b0, :m])
+            i, key = device.topk_rows(cnt, top, rank_bits=max(self.n_hash.bit_length(), 1), self_col0=b0)
+            out_i.append(i)
+            out_k.append(key)
+        return torch.cat(out_i).contiguous(), torch.cat(out_k).contiguous(), m
+
+    def knn(self, top=10, idx=None, block_bytes=1 << 30):
+        """For every resident sequence (or member of the subset idx) its `top` most similar OTHER ones, without the matrix: (index, value) =
+        similarityMH_knn(sequences[idx], k, n_hash, top, seed=self.seed) -- (m, top) int32 positions in idx, by value descending then
+        position ascending, the row's own position left out, and the (m, top) float64 values.  top is clamped to m - 1.  The signatures are
+        resident: a call is K1b on the subset, the square problem's rows in blocks of block_bytes as uint16 counts, and the self form of
+        device.topk_rows on each block."""
+        i, key, _ = self._knn_lists(idx, top, block_bytes)
+        val = device.widen(key, False, self.n_hash)                      # count / n_hash, the library's divide
+        return i.cpu().numpy(), val.cpu().numpy()
+
+    def knn_csr(self, idx=None, top=10, mode="union"):
+        """The kNN graph of the subset (knn_graph of knn(top, idx) with the 1.0 diagonal) as the canonical symmetric CSR edges_csr returns --
+        lists -> device.knn_edges -> device.edges_to_csr, all on the device: (threshold, n_edges, ptr, adj, codes, loop_codes, values) with
+        weight of entry k = values[codes[k]]; n_edges counts i <= j entries, the diagonal included.  The threshold slot holds the smallest
+        off-diagonal weight kept, NaN when none."""
+        i, key, m = self._knn_lists(idx, top, 1 << 30)
+        ei, ej, ev, got = device.knn_edges(i, key, mode, is_nw=False, self_code=self.n_hash, loops=True)
+        ptr, adj, codes, loops = device.edges_to_csr(ei, ej, ev, got, m)
+        values = np.arange(self.n_hash + 1, dtype=np.float64) / self.n_hash           # src/minHash.cpp:174
+        codes_h = codes.cpu().numpy().view(np.uint16)
+        thr = float(values[int(codes_h.min())]) if len(codes_h) else float("nan")
+        return thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes_h, loops.cpu().numpy().view(np.uint16), values
 
     def edges_csr(self, idx=None, thresh_p=0.8):
         """The thresholded graph of the subset as the canonical symmetric CSR clusterbreak.louvain_csr takes -- sorted ON THE DEVICE

@@ -13,6 +13,12 @@ and the top-k forms of those (per row of x the ``top`` most similar y, never the
     similarityMH_cross_topk(x, y, k=4, n_hash=50, top=10)
     similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10)
 
+and the top-k form of ONE set against itself (per sequence its ``top`` most similar other sequences, and the kNN graph of those lists)
+
+    similarityMH_knn(sequences, k=4, n_hash=50, top=10)            similarityMH_knn_edges(..., top=10, mode="union")
+    similarityNW_knn(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10)     similarityNW_knn_edges(..., top=10, mode="union")
+    knn_dense(S, top), knn_graph(idx, val, diag=None, mode="union")   the definitions in numpy
+
 and the threshold forms of those (the entries that pass a threshold as a sorted edge list, never the m x n matrix)
 
     similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, threshold=None)
@@ -284,6 +290,122 @@ def similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, t
     _capi.check(lib.da_similarity_nw_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
                                                 _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t, idx.ctypes.data, val.ctypes.data))
     return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
+
+
+def similarityMH_knn(sequences, k=4, n_hash=50, top=10, *, seed=None):
+    """For every sequence its ``top`` most similar OTHER sequences under similarityMH, without the (n, n) matrix: ``(idx, val)``, (n, top)
+    int32 0-based positions and the (n, top) float64 similarities, with ``(idx, val) == knn_dense(similarityMH(sequences, k, n_hash,
+    seed=seed), top)``: value descending, position ascending among equals, the row's own position left out; columns of similarity 0 fill a
+    row.  ``top`` is clamped to ``len(sequences) - 1`` (the C ABI does not clamp) and may be at most 1024.  Byte-identical sequences fill each
+    other's lists at 1.0: pass distinct sequences.  Errors as similarityMH, then "a nearest neighbour needs a second sequence"."""
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    top = _as_int(top, "top")
+    t = min(top, n - 1) if n >= 2 else top
+    idx = np.empty((max(n, 1), max(t, 1)), np.int32)
+    val = np.empty((max(n, 1), max(t, 1)), np.float64)
+    _capi.check(lib.da_similarity_mh_knn(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, t, idx.ctypes.data, val.ctypes.data))
+    return idx[:n], val[:n]
+
+
+def _nw_knn(sequences, matrixName, gapOpen, gapExt, top):
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    top = _as_int(top, "top")
+    t = min(top, n - 1) if n >= 2 else top
+    idx = np.empty((max(n, 1), max(t, 1)), np.int32)
+    val = np.empty((max(n, 1), max(t, 1)), np.float64)
+    diag = np.empty(max(n, 1), np.float64)
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    _capi.check(lib.da_similarity_nw_knn(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t,
+                                         idx.ctypes.data, val.ctypes.data, diag.ctypes.data))
+    return idx[:n], val[:n], diag[:n]
+
+
+def similarityNW_knn(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10):
+    """For every sequence its ``top`` most similar OTHER sequences under similarityNW, without the (n, n) matrix: ``(idx, val)`` as
+    similarityMH_knn, ``== knn_dense(similarityNW(sequences, ...), top)``.  Equal similarities tie whatever their (matches, length).  Every
+    sequence has 1 .. 127 residues (an empty one is refused); ``top`` is clamped to ``len(sequences) - 1``."""
+    idx, val, _ = _nw_knn(sequences, matrixName, gapOpen, gapExt, top)
+    return idx, val
+
+
+def knn_dense(S, top):
+    """The nearest-neighbour lists of a dense symmetric similarity matrix, the definition in numpy: ``(idx, val)`` with
+    ``idx = argsort(-S', axis=1, kind="stable")[:, :top]`` for S' = S with its diagonal at -inf (int32) and ``val[i, t] = S[i, idx[i, t]]``.
+    1 <= top <= n - 1.  The counterpart of similarityMH_knn / similarityNW_knn, as compute_similarity_stats is of the *_stats calls."""
+    S = np.asarray(S, np.float64)
+    if S.ndim != 2 or S.shape[0] != S.shape[1]:
+        raise ValueError("Input must be a square pairwise similarity matrix")
+    n = S.shape[0]
+    top = _as_int(top, "top")
+    if n < 2:
+        raise ValueError("a nearest neighbour needs a second sequence")
+    if not 1 <= top <= n - 1:
+        raise ValueError("top must be in 1 .. n - 1 (got top = %d, n = %d)" % (top, n))
+    M = np.array(S, np.float64)
+    np.fill_diagonal(M, -np.inf)
+    idx = np.argsort(-M, axis=1, kind="stable")[:, :top]
+    return idx.astype(np.int32), np.take_along_axis(np.asarray(S, np.float64), idx, axis=1)
+
+
+def knn_graph(idx, val, diag=None, mode="union"):
+    """Nearest-neighbour lists -> the edge list ``(i, j, w)`` of their kNN graph, i <= j, sorted by (i, j), pure numpy.  An entry (i -> j) is live
+    when ``val > 0``; ``mode="union"`` keeps the pair {i, j} when j is live in row i or i is live in row j, ``"mutual"`` when both hold; the
+    weight is the listed value.  ``diag`` (n values, or a scalar) adds the entries (i, i, diag[i]); ``diag=None`` adds none.  This is the
+    adjacency netcluster builds from the similarity matrix with every off-diagonal entry outside the kNN relation set to 0, in the form
+    ``clusterbreak(edges_fn=)`` takes."""
+    if mode not in ("union", "mutual"):
+        raise ValueError("mode must be 'union' or 'mutual'")
+    idx = np.asarray(idx, np.int64)
+    val = np.asarray(val, np.float64)
+    if idx.ndim != 2 or idx.shape != val.shape:
+        raise ValueError("idx and val must be (n, top) arrays of one shape")
+    n = idx.shape[0]
+    rows = np.repeat(np.arange(n, dtype=np.int64), idx.shape[1])
+    cols, w = idx.ravel(), val.ravel()
+    live = (w > 0) & (cols != rows)
+    rows, cols, w = rows[live], cols[live], w[live]
+    lo, hi = np.minimum(rows, cols), np.maximum(rows, cols)
+    pair = lo * n + hi
+    order = np.argsort(pair, kind="stable")
+    pair, w = pair[order], w[order]
+    first = np.ones(len(pair), bool)
+    first[1:] = pair[1:] != pair[:-1]
+    if mode == "mutual":                       # a pair listed from both sides appears twice
+        twice = np.zeros(len(pair), bool)
+        twice[:-1] = pair[1:] == pair[:-1]
+        first &= twice
+    pair, w = pair[first], w[first]
+    ei, ej = pair // max(n, 1), pair % max(n, 1)
+    if diag is not None:
+        d = np.broadcast_to(np.asarray(diag, np.float64), (n,))
+        ei = np.concatenate([ei, np.arange(n, dtype=np.int64)])
+        ej = np.concatenate([ej, np.arange(n, dtype=np.int64)])
+        w = np.concatenate([w, d])
+        order = np.lexsort((ej, ei))
+        ei, ej, w = ei[order], ej[order], w[order]
+    return ei.astype(np.int32), ej.astype(np.int32), np.ascontiguousarray(w, np.float64)
+
+
+def _knn_edges_result(idx, val, diag, mode):
+    ei, ej, w = knn_graph(idx, val, diag, mode)
+    off = w[ei != ej]
+    return (float(off.min()) if len(off) else float("nan")), ei, ej, w
+
+
+def similarityMH_knn_edges(sequences, k=4, n_hash=50, top=10, mode="union", *, seed=None):
+    """The kNN graph of similarityMH_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``: knn_graph of the lists with the 1.0
+    diagonal of similarityMH.  The ``threshold`` slot holds the smallest off-diagonal weight kept, NaN when none."""
+    idx, val = similarityMH_knn(sequences, k, n_hash, top, seed=seed)
+    return _knn_edges_result(idx, val, 1.0, mode)
+
+
+def similarityNW_knn_edges(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10, mode="union"):
+    """The kNN graph of similarityNW_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``; the diagonal is what the DP gives for a
+    sequence against itself.  The ``threshold`` slot holds the smallest off-diagonal weight kept, NaN when none."""
+    idx, val, diag = _nw_knn(sequences, matrixName, gapOpen, gapExt, top)
+    return _knn_edges_result(idx, val, diag, mode)
 
 
 def nw_code_ranks(max_len=127):

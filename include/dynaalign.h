@@ -47,6 +47,7 @@ extern "C" {
 /* (round 4 added entry points only -- da_config_reload, da_debug_comm_cache_state, da_mh_last_route_split: the version stays)
  * (the two-set entry points -- da_similarity_*_cross, da_dev_*_rect, da_dev_similarity_mh_cross, da_mh_cross_last_route -- were added likewise)
  * (the two-set top-k entry points -- da_similarity_*_cross_topk, da_dev_similarity_mh_cross_topk, da_dev_topk_rows, da_nw_code_ranks -- likewise)
+ * (the one-set nearest-neighbour entry points -- da_similarity_*_knn, da_dev_similarity_mh_knn, da_dev_topk_rows_self, da_dev_knn_edges[_bytes] -- likewise)
  * (the two-set threshold entry points -- da_similarity_*_cross_edges_begin, da_dev_similarity_mh_cross_edges, da_dev_rect_histogram,
  *  da_dev_threshold_rows_* -- likewise)
  * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes and their _long forms -- likewise)
@@ -228,6 +229,27 @@ int da_similarity_nw_cross_topk(const uint8_t *x_residues, const int64_t *x_offs
  * and get rank 0.  *distinct_out (may be NULL): the number of ranks.  Host only; needs no device. */
 int da_nw_code_ranks(int max_len, uint16_t *rank_out, int *distinct_out);
 
+/* ---- one set, nearest-neighbour lists: for every sequence its `top` most similar OTHER sequences, without the n x n matrix ----
+ * S is the matrix da_similarity_mh / da_similarity_nw return (n x n, symmetric).  Row i of the result lists the `top` columns j != i ordered
+ * by S[i][j] descending and, among equal values, by j ascending: numpy's argsort(-S', axis = 1, kind = "stable")[:, :top] with S' = S whose
+ * diagonal is -inf.  Columns of similarity 0 are ordinary entries (they fill a row, in position order); equal values tie even when their NW
+ * codes differ (selection on da_nw_code_ranks, as in the two-set form).
+ *   idx_out : [n][top] int32, 0-based;  val_out : [n][top] float64 or NULL, val[i][t] bit for bit S[i][idx[i][t]];
+ *   diag_out (NW only, may be NULL): [n] float64, S[i][i] as the DP gives it (the MinHash diagonal is 1.0 by the reference's forced diagonal).
+ * This is NOT da_similarity_*_cross_topk(x, x, top + 1) with the first column dropped: among byte-identical or equally similar sequences a
+ * row's own column is not the first of its ties.  Byte-identical strings fill each other's lists at 1.0: pass distinct sequences.
+ * Validation, before any device is needed.  MinHash: what da_similarity_mh checks, in its order and with its texts (n, k, n_hash, NULL pointers,
+ * offsets); then n < 2 -> DA_ERR_BAD_ARG ("a nearest neighbour needs a second sequence"); top < 1 or top > n - 1 -> DA_ERR_BAD_ARG; top > 1024 ->
+ * DA_ERR_UNSUPPORTED; n_hash > 65535 -> DA_ERR_UNSUPPORTED.  NW: the order of da_similarity_nw_edges -- matrix name, NULL pointers, n < 2 and
+ * `top` (where that call checks thresh_p), offsets, residues, then every sequence has 1 .. 127 residues (DA_ERR_UNSUPPORTED).  `top` is not clamped.
+ * Route: K1 and the planes once on the n sequences (no joint operand, no padding rows), the square problem's rows [b0, b1) x columns [0, n) as
+ * uint16 codes in row blocks of DYNAALIGN_BLOCK_BYTES, and da_dev_topk_rows_self on each block with self_col0 = b0.  NW: on one code buffer pair
+ * (p, q) is calc(seq[min(p, q)], seq[max(p, q)]), so those rows are rows of the mirrored square matrix.  Single device, the direct route only. */
+int da_similarity_mh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int top,
+                         int32_t *idx_out, double *val_out);
+int da_similarity_nw_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                         int top, int32_t *idx_out, double *val_out, double *diag_out);
+
 /* ---- the alignment PATH of listed pairs: how x[i] and y[j] align, not only how similar they are ----
  * Pair p aligns x[pair_x[p]] as sequence1 (length m1) with y[pair_y[p]] as sequence2 (length n2); pair_x == pair_y == NULL means p with p
  * (then m == n == pairs).  The fill is the reference's (src/pairwiseSeqAlign.cpp:216-281); the decision of cell (i, j), i, j >= 1, is
@@ -404,6 +426,37 @@ int da_dev_similarity_mh_cross_topk(const uint8_t *d_x_residues, const int64_t *
                                     const uint8_t *d_y_residues, const int64_t *d_y_offsets, int64_t n,
                                     int k, int n_hash, const uint32_t *d_seeds, int top, int32_t *d_idx, double *d_val, int64_t ld_out,
                                     void *stream);
+
+/* da_dev_topk_rows with every row's own column left out of the selection: the block is rows [self_col0, self_col0 + rows) of a square problem,
+ * so its row r owns column self_col0 + r, and that element is absent from the radix select, from the ordered compaction and from the choice
+ * among equals -- the result is argsort(-rank[row], kind = "stable")[:top] of the row without it.  d_self_key (may be NULL): uint16[rows], receives
+ * the key found at the own column (the NW diagonal).  A row whose own column falls outside [0, n) excludes nothing and leaves its d_self_key
+ * entry unwritten.  1 <= top <= n - 1 (DA_ERR_BAD_ARG); everything else as da_dev_topk_rows. */
+int da_dev_topk_rows_self(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top,
+                          int64_t self_col0, int32_t *d_idx, uint16_t *d_key_out, int64_t ld_out, uint16_t *d_self_key, void *stream);
+
+/* da_similarity_mh_knn on a resident set as ONE call: d_idx (int32) and d_val (float64) hold n rows of ld_out >= top elements.  Validates like
+ * da_similarity_mh_knn (n, k, n_hash, NULL pointers, n < 2, top, n_hash > 65535, ld_out) before it touches the device; one stream, which it
+ * synchronises. */
+int da_dev_similarity_mh_knn(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int k, int n_hash, const uint32_t *d_seeds,
+                             int top, int32_t *d_idx, double *d_val, int64_t ld_out, void *stream);
+
+/* Nearest-neighbour lists -> the edge list of their kNN graph, on the device.  d_idx / d_key: n rows of ld >= top entries (top <= 1024), row r
+ * listing r's neighbours and the uint16 keys found there (what da_dev_topk_rows_self wrote).  An entry (r -> j) is live when its key stands for
+ * a value > 0: key != 0, or key >> 8 != 0 with is_nw (the convention of da_dev_widen).  in(i, j): j appears live in row i.
+ *   mode DA_KNN_UNION keeps the pair {i, j} when in(i, j) or in(j, i); DA_KNN_MUTUAL when both hold.
+ * Output: (d_i[e] <= d_j[e], d_v[e]) -- the key of the entry that produced it -- and *d_count (uint64) = the number of entries, in the form
+ * da_dev_edges_to_csr takes.  With `loops` every vertex r also gets (r, r, d_self_key[r]), or (r, r, self_code) when d_self_key is NULL (MinHash:
+ * n_hash).  d_i / d_j / d_v must hold n * (top + (loops ? 1 : 0)) entries.  One wave per source row; every pair is emitted by exactly one row
+ * (union: row min(i, j) when in(min, max), else row max; mutual: row min), at a position given by a count pass and an exclusive scan -- no output
+ * atomic, so the list depends on the data alone.  It is grouped by emitting row, not sorted by (i, j).  The membership test scans row j's entries;
+ * it does not rely on the lists being symmetric.  d_work: da_dev_knn_edges_bytes(n, top) bytes, 256-byte aligned.  Asynchronous on `stream`. */
+#define DA_KNN_UNION 0
+#define DA_KNN_MUTUAL 1
+size_t da_dev_knn_edges_bytes(int64_t n, int top);
+int da_dev_knn_edges(const int32_t *d_idx, const uint16_t *d_key, int64_t ld, int64_t n, int top, int mode, int is_nw,
+                     const uint16_t *d_self_key, int self_code, int loops, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j,
+                     uint16_t *d_v, uint64_t *d_count, void *stream);
 
 /* K1 + K1b + K2 as ONE call: similarityMH (src/minHash.cpp:119-188) from packed residues in HBM to the dense float64
  * n x n matrix in HBM (d_out, leading dimension ld >= n doubles; 16-byte aligned and even ld for the wide-store kernels).
