@@ -19,6 +19,7 @@ from .similarity import (  # noqa: F401
     nw_value_ranks, similarityNW_edges_long, similarityNW_cross_edges_long,
     SimilarityStats, compute_similarity_stats, stats_from_histogram, similarityMH_stats, similarityNW_stats, similarityNW_stats_long,
     similarityMH_knn, similarityNW_knn, knn_dense, knn_graph, similarityMH_knn_edges, similarityNW_knn_edges,
+    similarityNW_knn_long, similarityNW_knn_edges_long, similarityNW_cross_topk_long,
 )
 
 __all__ = [
@@ -26,5 +27,6 @@ __all__ = [
     "similarityMH", "similarityNW", "similarityMH_cross", "similarityNW_cross", "similarityMH_cross_topk", "similarityNW_cross_topk", "similarityMH_cross_edges", "similarityNW_cross_edges", "nw_code_ranks", "similarityMH_edges", "similarityNW_edges", "similarityNW_edges_long", "similarityNW_cross_edges_long", "nw_value_ranks", "quantile_type7", "minhash_signatures", "mh_counts", "nw_pairs", "hash_family_seeds",
     "SimilarityStats", "compute_similarity_stats", "stats_from_histogram", "similarityMH_stats", "similarityNW_stats", "similarityNW_stats_long",
     "similarityMH_knn", "similarityNW_knn", "knn_dense", "knn_graph", "similarityMH_knn_edges", "similarityNW_knn_edges",
+    "similarityNW_knn_long", "similarityNW_knn_edges_long", "similarityNW_cross_topk_long",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

@@ -89,6 +89,10 @@ SIGNATURES = {
     "da_stats_from_histogram": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "da_similarity_mh_stats": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "da_similarity_nw_stats": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
+    "da_dev_topk_ranks": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
+    "da_dev_topk_ranks_self": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "da_similarity_nw_knn_long": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "da_similarity_nw_cross_topk_long": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp]),
     "da_similarity_nw_stats_long": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
     "da_dev_upper_extrema": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "da_dev_upper_extrema32": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),

@@ -3285,6 +3285,27 @@ int da_dev_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n,
                                      static_cast<hipStream_t>(stream));
 }
 
+// exact top-k per row of a block of value ranks (topk_kernels.hip: k_topk_ranks), and the same with every row's own column left out
+int da_dev_topk_ranks(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int top, int32_t *d_idx, uint32_t *d_key_out,
+                      int64_t ld_out, void *stream) {
+  int rc;
+  if ((rc = rank_block_check(d_keys, d_idx, rows, n, ld, nbins, 0, 0)) != DA_OK) return rc;
+  if (!d_key_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (rows == 0) return DA_OK;
+  if (top >= 1 && top <= n && top <= DA_TOPK_MAX && ld_out < top) return fail(DA_ERR_BAD_ARG, "ld_out (%lld) < top (%d)", (long long)ld_out, top);
+  return launch_topk_ranks(d_keys, rows, n, ld, nbins, top, d_idx, ld_out, d_key_out, ld_out, static_cast<hipStream_t>(stream));
+}
+int da_dev_topk_ranks_self(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int top, int64_t self_col0, int32_t *d_idx,
+                           uint32_t *d_key_out, int64_t ld_out, uint32_t *d_self_key, void *stream) {
+  int rc;
+  if ((rc = rank_block_check(d_keys, d_idx, rows, n, ld, nbins, 0, 0)) != DA_OK) return rc;
+  if (!d_key_out) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (rows == 0) return DA_OK;
+  if (top >= 1 && top <= n - 1 && top <= DA_TOPK_MAX && ld_out < top) return fail(DA_ERR_BAD_ARG, "ld_out (%lld) < top (%d)", (long long)ld_out, top);
+  return launch_topk_ranks_self(d_keys, rows, n, ld, nbins, top, self_col0, d_idx, ld_out, d_key_out, ld_out, d_self_key,
+                                static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"  (reopened below)
 namespace {
 // The scratch block of an NW problem on value ranks, and what fills it.  square: the problem is the n x n matrix of one set (m == n) and a
@@ -3412,6 +3433,100 @@ int da_similarity_nw_cross_edges_long_begin(const uint8_t *x_residues, const int
     }, nullptr);
     return edges_to_host(keys, m, thresh, thresh_is_quantile != 0, es, n_edges);
   });
+}
+
+// ---- nearest-neighbour lists and top-k for sequences of up to 1024 residues: the selection on 32-bit value ranks (k_topk_ranks) -----------------
+}  // extern "C"  (reopened below)
+namespace {
+// Rows [0, m) of the problem `keys` fills, selected block by block: per block the DP (PACK32), the value ranks in place, `top` of every row
+// into [m][top] index and rank buffers; then idx as it is, val = values[rank] -- the library's divide bit for bit, as in the edge path.  self:
+// the rows are the square problem's own (all n columns) and a block starting at row b0 runs the self form with self_col0 = b0;
+// diag = values[the own column's rank].
+int rank_topk_to_host(RankBlocks &keys, int64_t m, int top, bool self, int32_t *idx_out, double *val_out, double *diag_out) {
+  const hipStream_t stream = keys.stream;
+  const size_t cnt = (size_t)m * (size_t)top;
+  DevBuf didx, dkey, dself;
+  int rc;
+  if ((rc = keys.init()) != DA_OK || (rc = didx.alloc(cnt * sizeof(int32_t))) != DA_OK || (rc = dkey.alloc(cnt * sizeof(uint32_t))) != DA_OK) return rc;
+  if (self && (rc = dself.alloc((size_t)m * sizeof(uint32_t))) != DA_OK) return rc;
+  for (int64_t b0 = 0; b0 < m; b0 += keys.blk) {
+    const int64_t b1 = std::min(m, b0 + keys.blk);
+    if ((rc = keys.ranks_of(b0, b1)) != DA_OK) return rc;
+    rc = self ? launch_topk_ranks_self(keys.d.as<uint32_t>(), b1 - b0, keys.n, keys.ld, keys.bins(), top, b0, didx.as<int32_t>() + b0 * top, top,
+                                       dkey.as<uint32_t>() + b0 * top, top, dself.as<uint32_t>() + b0, stream)
+              : launch_topk_ranks(keys.d.as<uint32_t>(), b1 - b0, keys.n, keys.ld, keys.bins(), top, didx.as<int32_t>() + b0 * top, top,
+                                  dkey.as<uint32_t>() + b0 * top, top, stream);
+    if (rc != DA_OK) return rc;
+  }
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  DA_HIP_TRY(hipMemcpy(idx_out, didx.p, cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  const std::vector<double> &values = keys.values;
+  std::vector<uint32_t> rk;
+  if (val_out) {
+    rk.resize(cnt);
+    DA_HIP_TRY(hipMemcpy(rk.data(), dkey.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < cnt; ++e) val_out[e] = values[std::min<size_t>(rk[e], values.size() - 1)];
+  }
+  if (self && diag_out) {
+    rk.resize((size_t)m);
+    DA_HIP_TRY(hipMemcpy(rk.data(), dself.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < m; ++i) diag_out[i] = values[std::min<size_t>(rk[(size_t)i], values.size() - 1)];
+  }
+  return DA_OK;
+}
+// the PACK32 codes of FULL rows of one set's square, columns [0, n): the whole of it by the symmetric sweep (every pair computed once and
+// mirrored, the diagonal included), else rows [b0, b1) through the rectangle form, where pair (p, q) is calc(seq[min], seq[max]) -- so a
+// square cut into blocks computes every pair twice, once in each of its two rows' blocks
+RankCompute nw_full_row_codes(const NwCodes &nw, int64_t n, int64_t max_len, int mid, int gap_open, int gap_ext, hipStream_t stream) {
+  return [=, &nw](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {
+    if (b0 == 0 && b1 == n)
+      return launch_nw(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, 0, n, true, DA_OUT_PACK32, d, ld, nullptr, 0,
+                       stream);
+    return launch_nw_rect(nw.codes.as<uint8_t>(), nw.in.off.as<int64_t>(), n, max_len, mid, gap_open, gap_ext, b0, b1, 0, n, DA_OUT_PACK32, d, ld, stream);
+  };
+}
+}  // namespace
+extern "C" {
+
+// da_similarity_nw_knn for sequences of up to 1024 residues: the same validation, the same result
+int da_similarity_nw_knn_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext, int top,
+                              int32_t *idx_out, double *val_out, double *diag_out) {
+  const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (!residues || !idx_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int rc;
+  if ((rc = knn_check(top, n)) != DA_OK) return rc;      // where da_similarity_nw_edges checks n >= 2 and thresh_p
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (offsets[i + 1] == offsets[i])
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld is empty: its similarities are 0/0 = NaN and a NaN has no place in an order", (long long)(i + 1));
+  if (max_len > 1024)
+    return fail(DA_ERR_UNSUPPORTED, "the long NW nearest-neighbour lists work on 32-bit value ranks: sequences up to 1024 residues");
+  if ((rc = require_device()) != DA_OK) return rc;
+  NwCodes nw;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+  // not `square`: a block holds all n columns of its rows
+  RankBlocks keys(n, n, false, (int)max_len, nw_full_row_codes(nw, n, max_len, mid, gap_open, gap_ext, nullptr), nullptr);
+  return rank_topk_to_host(keys, n, top, true, idx_out, val_out, diag_out);
+}
+
+// da_similarity_nw_cross_topk for sequences of up to 1024 residues
+int da_similarity_nw_cross_topk_long(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                     int64_t n, const char *matrix_name, int gap_open, int gap_ext, int top, int32_t *idx_out, double *val_out) {
+  const int mid = da_matrix_id(matrix_name);             // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (m <= 0) return DA_OK;                              // no rows: nothing to write
+  if (n <= 0) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = 0)", top);
+  NwCross c{x_residues, y_residues, x_offsets, y_offsets, m, n, mid, gap_open, gap_ext};
+  int rc;
+  if ((rc = c.check(idx_out != nullptr, [&] { return topk_check(top, n); }, "an order", 1024,
+                    "the long NW top-k works on 32-bit value ranks: sequences up to 1024 residues")) != DA_OK || (rc = c.upload()) != DA_OK) return rc;
+  RankBlocks keys(m, n, false, (int)c.max_len, [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {
+    return c.rows(b0, b1, DA_OUT_PACK32, d, ld, nullptr);
+  }, nullptr);
+  return rank_topk_to_host(keys, m, top, false, idx_out, val_out, nullptr);
 }
 
 // ---- summary statistics without the matrix on the host (reference R/similarity.R:11-34; dynaalign.h) ---------------------------------------

@@ -301,6 +301,11 @@ int launch_topk_rows(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld
 // its key goes to d_self_key[r] when that pointer is given; 1 <= top <= n - 1 (da_dev_topk_rows_self)
 int launch_topk_rows_self(const uint16_t *d_keys, int64_t rows, int64_t n, int64_t ld, const uint16_t *d_rank, int rank_bits, int top, int64_t self_col0,
                           int32_t *d_idx, int64_t ld_idx, uint16_t *d_key_out, int64_t ld_key, uint16_t *d_self_key, hipStream_t stream);
+// ... and the same selection on uint32 keys that are value ranks below nbins (da_dev_topk_ranks[_self]): nbins only places the 8-bit digits
+int launch_topk_ranks(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int top, int32_t *d_idx, int64_t ld_idx,
+                      uint32_t *d_key_out, int64_t ld_key, hipStream_t stream);
+int launch_topk_ranks_self(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int top, int64_t self_col0, int32_t *d_idx,
+                           int64_t ld_idx, uint32_t *d_key_out, int64_t ld_key, uint32_t *d_self_key, hipStream_t stream);
 int launch_topk_values(const uint16_t *d_key, int64_t ld_key, int64_t rows, int top, int n_hash, double *d_val, int64_t ld_val, hipStream_t stream);
 // rect_edges_kernels.hip: the threshold form of a two-set rectangle, on a block of `rows` rows of ld >= n uint16 keys (da_dev_rect_histogram,
 // da_dev_threshold_rows_count / _emit): histogram of the whole block; per-row count of the keys flagged in d_keep + exclusive scan -> row

@@ -475,6 +475,31 @@ def topk_rows(keys, top, rank=None, rank_bits=0, self_col0=None, want_self=False
     return (idx[:rows], key[:rows], own[:rows]) if want_self else (idx[:rows], key[:rows])
 
 
+def topk_ranks(keys, top, nbins, self_col0=None, want_self=False):
+    """Exact top-k per row of a block of uint32 value ranks (an int32 tensor of shape (rows, n) holding the uint32 bit patterns, any row
+    stride and base address; every key < nbins), by (rank descending, column ascending) (da_dev_topk_ranks).  Returns (idx int32
+    (rows, top), key int32 (rows, top)): numpy's argsort(-row, kind="stable")[:top] and the ranks found there.  nbins only places the
+    digits of the radix select.  self_col0 / want_self as in topk_rows (da_dev_topk_ranks_self; 1 <= top <= n - 1): the third result,
+    int32 (rows,), holds the rank found at the own column (rows whose own column is outside [0, n) keep 0)."""
+    lib = _capi.load()
+    _require_cuda(keys, "keys")
+    assert keys.dim() == 2 and keys.dtype == torch.int32 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
+    rows, n = int(keys.shape[0]), int(keys.shape[1])
+    ld = int(keys.stride(0)) if rows > 1 else max(n, 1)
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    idx = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
+    key = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
+    if self_col0 is None:
+        if want_self:
+            raise ValueError("want_self needs self_col0")
+        _call(lib.da_dev_topk_ranks, keys.data_ptr(), rows, n, ld, int(nbins), int(top), idx.data_ptr(), key.data_ptr(), t, _stream())
+        return idx[:rows], key[:rows]
+    own = torch.zeros(max(rows, 1), dtype=torch.int32, device=keys.device) if want_self else None
+    _call(lib.da_dev_topk_ranks_self, keys.data_ptr(), rows, n, ld, int(nbins), int(top), int(self_col0), idx.data_ptr(), key.data_ptr(), t,
+                                           None if own is None else own.data_ptr(), _stream())
+    return (idx[:rows], key[:rows], own[:rows]) if want_self else (idx[:rows], key[:rows])
+
+
 def similarity_mh_knn(ds, k, n_hash, seeds, top):
     """The nearest-neighbour lists of a device-resident set, one C call (da_dev_similarity_mh_knn): (idx int32 (n, top), val float64
     (n, top)).  Row i lists the `top` columns j != i of row i of similarity_mh(ds, ...) by value descending, then column ascending; the

@@ -17,6 +17,7 @@ and the top-k form of ONE set against itself (per sequence its ``top`` most simi
 
     similarityMH_knn(sequences, k=4, n_hash=50, top=10)            similarityMH_knn_edges(..., top=10, mode="union")
     similarityNW_knn(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10)     similarityNW_knn_edges(..., top=10, mode="union")
+    similarityNW_knn_long(...), similarityNW_knn_edges_long(...), similarityNW_cross_topk_long(...)    the same for 1 .. 1024 residues
     knn_dense(S, top), knn_graph(idx, val, diag=None, mode="union")   the definitions in numpy
 
 and the threshold forms of those (the entries that pass a threshold as a sorted edge list, never the m x n matrix)
@@ -273,11 +274,7 @@ def similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
     return SimilarityMatrix(out[:m, :n])
 
 
-def similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10):
-    """For every sequence of ``x`` its ``top`` most similar sequences of ``y`` under similarityNW_cross (x[i] is sequence1), without
-    the (m, n) matrix: ``(idx, val)`` as similarityMH_cross_topk.  Equal similarities tie whatever their (matches, length): 2/4 and 3/6
-    are both 0.5 and are listed by position.  Every sequence has 1 .. 127 residues (an empty one is refused: its similarities are NaN /
-    0.0).  An empty ``x`` gives (0, top) arrays; ``top`` is clamped to ``len(y)``; an empty ``y`` is an error."""
+def _nw_cross_topk(entry, x, y, matrixName, gapOpen, gapExt, top):
     lib = _capi.load()
     xr, xo = pack_sequences(x)
     yr, yo = pack_sequences(y)
@@ -287,9 +284,24 @@ def similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, t
     idx = np.empty((max(m, 1), max(t, 1)), np.int32)
     val = np.empty((max(m, 1), max(t, 1)), np.float64)
     name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
-    _capi.check(lib.da_similarity_nw_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
-                                                _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t, idx.ctypes.data, val.ctypes.data))
+    _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
+                                    _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t, idx.ctypes.data, val.ctypes.data))
     return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
+
+
+def similarityNW_cross_topk(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10):
+    """For every sequence of ``x`` its ``top`` most similar sequences of ``y`` under similarityNW_cross (x[i] is sequence1), without
+    the (m, n) matrix: ``(idx, val)`` as similarityMH_cross_topk.  Equal similarities tie whatever their (matches, length): 2/4 and 3/6
+    are both 0.5 and are listed by position.  Every sequence has 1 .. 127 residues (an empty one is refused: its similarities are NaN /
+    0.0).  An empty ``x`` gives (0, top) arrays; ``top`` is clamped to ``len(y)``; an empty ``y`` is an error."""
+    return _nw_cross_topk("da_similarity_nw_cross_topk", x, y, matrixName, gapOpen, gapExt, top)
+
+
+def similarityNW_cross_topk_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10):
+    """``similarityNW_cross_topk`` for sequences of 1 .. 1024 residues (da_similarity_nw_cross_topk_long): the same arguments, the same
+    result, the same errors.  The selection works on 32-bit value ranks (nw_value_ranks), so 128/256 and 150/300 tie and are listed by
+    position; the (m, n) matrix never exists."""
+    return _nw_cross_topk("da_similarity_nw_cross_topk_long", x, y, matrixName, gapOpen, gapExt, top)
 
 
 def similarityMH_knn(sequences, k=4, n_hash=50, top=10, *, seed=None):
@@ -307,7 +319,7 @@ def similarityMH_knn(sequences, k=4, n_hash=50, top=10, *, seed=None):
     return idx[:n], val[:n]
 
 
-def _nw_knn(sequences, matrixName, gapOpen, gapExt, top):
+def _nw_knn(entry, sequences, matrixName, gapOpen, gapExt, top):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
@@ -317,8 +329,8 @@ def _nw_knn(sequences, matrixName, gapOpen, gapExt, top):
     val = np.empty((max(n, 1), max(t, 1)), np.float64)
     diag = np.empty(max(n, 1), np.float64)
     name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
-    _capi.check(lib.da_similarity_nw_knn(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t,
-                                         idx.ctypes.data, val.ctypes.data, diag.ctypes.data))
+    _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t,
+                                    idx.ctypes.data, val.ctypes.data, diag.ctypes.data))
     return idx[:n], val[:n], diag[:n]
 
 
@@ -326,7 +338,15 @@ def similarityNW_knn(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top
     """For every sequence its ``top`` most similar OTHER sequences under similarityNW, without the (n, n) matrix: ``(idx, val)`` as
     similarityMH_knn, ``== knn_dense(similarityNW(sequences, ...), top)``.  Equal similarities tie whatever their (matches, length).  Every
     sequence has 1 .. 127 residues (an empty one is refused); ``top`` is clamped to ``len(sequences) - 1``."""
-    idx, val, _ = _nw_knn(sequences, matrixName, gapOpen, gapExt, top)
+    idx, val, _ = _nw_knn("da_similarity_nw_knn", sequences, matrixName, gapOpen, gapExt, top)
+    return idx, val
+
+
+def similarityNW_knn_long(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10):
+    """``similarityNW_knn`` for sequences of 1 .. 1024 residues (da_similarity_nw_knn_long): the same arguments, the same result
+    ``== knn_dense(similarityNW(sequences, ...), top)``, the same errors.  The selection works on 32-bit value ranks (nw_value_ranks); the
+    (n, n) matrix never exists.  A set that does not fit one block of DYNAALIGN_BLOCK_BYTES computes every pair twice."""
+    idx, val, _ = _nw_knn("da_similarity_nw_knn_long", sequences, matrixName, gapOpen, gapExt, top)
     return idx, val
 
 
@@ -404,7 +424,14 @@ def similarityMH_knn_edges(sequences, k=4, n_hash=50, top=10, mode="union", *, s
 def similarityNW_knn_edges(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10, mode="union"):
     """The kNN graph of similarityNW_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``; the diagonal is what the DP gives for a
     sequence against itself.  The ``threshold`` slot holds the smallest off-diagonal weight kept, NaN when none."""
-    idx, val, diag = _nw_knn(sequences, matrixName, gapOpen, gapExt, top)
+    idx, val, diag = _nw_knn("da_similarity_nw_knn", sequences, matrixName, gapOpen, gapExt, top)
+    return _knn_edges_result(idx, val, diag, mode)
+
+
+def similarityNW_knn_edges_long(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, top=10, mode="union"):
+    """``similarityNW_knn_edges`` for sequences of 1 .. 1024 residues: the kNN graph of similarityNW_knn_long with the DP's diagonal.
+    ``clusterbreak(pep, edges_fn=lambda s: similarityNW_knn_edges_long(s, top=10))`` clusters full-length proteins on it."""
+    idx, val, diag = _nw_knn("da_similarity_nw_knn_long", sequences, matrixName, gapOpen, gapExt, top)
     return _knn_edges_result(idx, val, diag, mode)
 
 

@@ -762,8 +762,8 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
  * (da_nw_value_ranks: equal values from different codes, 128/256 and 150/300, are ONE rank), and histogram, keep decision and emitted key
  * work on ranks: threshold = da_quantile_type7(histogram, values); kept = rank >= max(r_thr, 1), r_thr the smallest rank whose value is >=
  * threshold, so the boundary R == threshold is exact; weight = values[rank].  Quantile form: a problem that fits one block stays resident
- * between the histogram and the emit pass, one cut into several blocks runs the DP twice; the absolute form makes one pass.  No top-k, no
- * duplicate route, single device. */
+ * between the histogram and the emit pass, one cut into several blocks runs the DP twice; the absolute form makes one pass.  No
+ * duplicate route, single device.  (Top-k on the same ranks: da_similarity_nw_knn_long, below.) */
 int da_similarity_nw_edges_long_begin(const uint8_t *residues, const int64_t *offsets, int64_t n,
                                       const char *matrix_name, int gap_open, int gap_ext, double thresh_p,
                                       da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
@@ -807,6 +807,39 @@ int da_dev_threshold_ranks_count(const uint32_t *d_keys, int64_t rows, int64_t n
 int da_dev_threshold_ranks_emit(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, uint32_t r_min, int64_t nbins, int triangle,
                                 int64_t row_begin, int64_t col_begin, const int64_t *d_rowptr, int32_t *d_j, uint32_t *d_key_out,
                                 int64_t capacity, void *stream);
+
+/* ---- nearest-neighbour lists and top-k for sequences of up to 1024 residues, on 32-bit value ranks ----
+ * da_dev_topk_ranks: exact top-k per row of a block of uint32 keys that ARE value ranks (what da_dev_nw_codes_to_ranks leaves): `rows` rows
+ * of ld >= n keys, every ld and every 4-byte-aligned base.  Row r of d_idx (int32) / d_key_out (uint32), ld_out >= top elements a row, lists
+ * the `top` columns of row r by (rank descending, column ascending) -- numpy's argsort(-row, kind = "stable")[:top] -- and the ranks found
+ * there.  nbins (1 .. 2^31 - 1) only places the digits of the radix select: ceil(bits of (nbins - 1) / 8) 8-bit digits, most significant
+ * first.  Keys must be < nbins; a key beyond the digits is taken as the largest value they hold: a wrong selection, never an access out of
+ * bounds.  The key block is only read.  1 <= top <= n (DA_ERR_BAD_ARG), top <= 1024 (DA_ERR_UNSUPPORTED, da_dev_topk_rows' sentence); NULL
+ * pointers, ld < n, ld_out < top, a negative shape and nbins outside its range are DA_ERR_BAD_ARG; rows == 0 is DA_OK and touches nothing.
+ * One workgroup per row (one wave for n <= 1024), the row read once per digit and once more (k_topk_ranks).  Asynchronous on `stream`.
+ * da_dev_topk_ranks_self: the block is rows [self_col0, self_col0 + rows) of a square problem and row r's own column self_col0 + r is absent
+ * from its selection; d_self_key[r] (may be NULL) receives the rank found there, and is left untouched where the own column is outside
+ * [0, n).  1 <= top <= n - 1.  Everything else as above (da_dev_topk_rows_self on 32-bit ranks). */
+int da_dev_topk_ranks(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int top,
+                      int32_t *d_idx, uint32_t *d_key_out, int64_t ld_out, void *stream);
+int da_dev_topk_ranks_self(const uint32_t *d_keys, int64_t rows, int64_t n, int64_t ld, int64_t nbins, int top, int64_t self_col0,
+                           int32_t *d_idx, uint32_t *d_key_out, int64_t ld_out, uint32_t *d_self_key, void *stream);
+
+/* da_similarity_nw_knn and da_similarity_nw_cross_topk for sequences of 1 .. 1024 residues: the same arguments, the same results (idx, val
+ * and diag bit for bit where both apply), the same validation in the same order and with the same texts, DA_ERR_NO_DEVICE last; the one
+ * difference is the length refusal, DA_ERR_UNSUPPORTED for a sequence of more than 1024 residues.  `top` is not clamped; val_out / diag_out
+ * may be NULL.  Route: upload and encode once; per row block of DYNAALIGN_BLOCK_BYTES (4 bytes a key, a multiple of 8 rows, at least 8) the
+ * DP as PACK32 codes, the value ranks in place (da_nw_value_ranks of the call's longest sequence: 128/256 and 150/300 are ONE rank),
+ * da_dev_topk_ranks[_self] into [rows][top] index and rank buffers; val = values[rank] and diag = values[own rank] on the host, the
+ * library's divide bit for bit.  Only the lists leave the device.  The one-set form needs FULL rows of the square: a square that fits one
+ * block runs the symmetric sweep (every pair once, mirrored, the diagonal included); one cut into blocks runs rows [b0, b1) x columns
+ * [0, n) with self_col0 = b0 and so computes EVERY PAIR TWICE, once in each of its two rows' blocks -- the price of leaving with the lists
+ * only.  Single device; no duplicate route; no device-pointer form. */
+int da_similarity_nw_knn_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                              int top, int32_t *idx_out, double *val_out, double *diag_out);
+int da_similarity_nw_cross_topk_long(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                     const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                                     const char *matrix_name, int gap_open, int gap_ext, int top, int32_t *idx_out, double *val_out);
 
 /* ---- summary statistics of a similarity matrix that never leaves the device (reference R/similarity.R:11-34, compute_similarity_stats) ----
  * S is the n x n matrix da_similarity_mh / da_similarity_nw return for the same arguments, U the P = n (n - 1) / 2 values of its strict
