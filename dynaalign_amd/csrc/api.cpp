@@ -420,6 +420,7 @@ Config parse_config() {
   c.mh_pipe_step = (int)std::max<int64_t>(0, env_i64("DYNAALIGN_MH_PIPE_STEP", 0));
   c.mh_pipe_wg = (int)std::max<int64_t>(0, std::min<int64_t>(4, env_i64("DYNAALIGN_MH_PIPE_WG", 0)));
   c.mh_pipe_head = (int)std::max<int64_t>(0, env_i64("DYNAALIGN_MH_PIPE_HEAD", 0));
+  c.mh_expand_zones = (int)env_i64("DYNAALIGN_MH_EXPAND_ZONES", 0);
   const int pb = (int)env_i64("DYNAALIGN_PLANE_BITS", 0);
   c.plane_bits = (pb == 32 || pb == 16 || pb == 15 || pb == 14 || pb == 12) ? pb : 0;
   c.k2_no_asm = env_flag("DYNAALIGN_K2_NO_ASM");
@@ -924,8 +925,9 @@ static int mh_rows_pipe(const MhCall &k) {
     const hipStream_t es = alt ? pr->alt[ci & 1] : stream;
     DA_HIP_TRY(hipStreamWaitEvent(es, pe[3 * ci], 0));
     DA_HIP_TRY(hipEventRecord(pe[3 * ci + 1], es));
-    if ((rc = launch_expand_stream_rows(k.dtab, k.ld_d, k.d.p.uidx, k.n, U, k.n_hash, k.out, k.ld, k.ex, cuts[ci] * 1024, cuts[ci + 1] * 1024, es,
-                                        (int)ci, k.pk)) != DA_OK) return rc;
+    // (the launches share the lists' ticket counters: this one takes the items of the finished table rows that the earlier ones left, the last
+    // one whatever remains, its workgroups filling the CUs as older ones leave)
+    if ((rc = launch_expand_stream_rows(k.dtab, k.ld_d, k.d.p.uidx, k.n, U, k.n_hash, k.out, k.ld, k.ex, cuts[ci + 1] * 1024, es, k.pk)) != DA_OK) return rc;
     DA_HIP_TRY(hipEventRecord(pe[3 * ci + 2], es));
   }
   if (alt) for (size_t ci = (C >= 2 ? C - 2 : 0); ci < C; ++ci) DA_HIP_TRY(hipStreamWaitEvent(stream, pe[3 * ci + 2], 0));

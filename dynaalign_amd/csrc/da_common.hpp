@@ -26,6 +26,7 @@ struct Config {
   int64_t mh_hybrid_min_n = -1;                            // -1: the built-in rule
   int mh_expand = 0;                                       // 0 default (first form whose shape test passes), 1 rows, 2 rowspipe, 3 pipe, 4 tiles
   int mh_pipe_step = 0, mh_pipe_wg = 0, mh_pipe_head = 0;  // 0: the built-in schedule
+  int mh_expand_zones = 0;                                 // row expansion: 1 = one item list and ticket counter, else one per eighth of the output rows
   int plane_bits = 0;                                      // lower bound on the code planes: 0 / 12 / 14 / 15 / 16, 32 = raw signature bits
   // compare kernels
   bool k2_no_asm = false, k2_persist = false;
@@ -266,7 +267,7 @@ int launch_expand_stream_rect(const uint16_t *d_D, int64_t ld_d, const int32_t *
                               int64_t U_y, int n_hash, double *d_out, int64_t ld, void *d_scratch, hipStream_t stream,
                               hipEvent_t after_lists = nullptr);
 int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
-                              void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no,   // launch_no: 0 .. 127, distinct per launch of a call
+                              void *d_scratch, int64_t row_end, hipStream_t stream,   // the items below table row row_end that earlier launches left
                               bool pk = false);
 int launch_expand_rows(const uint16_t *d_F, int64_t ld_f, const int32_t *d_uidx, int64_t n, bool is_nw, int n_hash, int nw_max_len,
                        double *d_out, int64_t ld, int64_t band_begin, int64_t band_end, hipStream_t stream);

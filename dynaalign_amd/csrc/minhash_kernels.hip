@@ -1986,25 +1986,48 @@ __global__ __launch_bounds__(256, 4) void k_expand_rows(const uint16_t *__restri
 // itself: for every column pair (j, j + 1) the two counts D[r][u(j)], D[r][u(j + 1)] come out of LDS, go through the count -> double table
 // (also LDS, built with the reference's divide) and leave as one 16-byte streaming store per copy of r.  Every element of the result is
 // written exactly once (diagonal and borders included: no second kernel), a wave-instruction covers 1 KiB of one output row, and the
-// only global reads are the table rows (4 GB) and the id map (L2-resident).  Work items are (unique row, up to ES_COPIES of its copies),
-// listed by k_es_items so that a string with thousands of copies is spread over many workgroups.
-constexpr int ES_THREADS = 1024, ES_COPIES = 4, ES_TICKETS = 128;   // (ticket counters: one per launch of a call, launch_expand_stream_rows' `launch_no`)
-__global__ __launch_bounds__(256) void k_es_count(const int32_t *__restrict__ uidx, int n, uint32_t *__restrict__ cnt) {
+// only global reads are the table rows (4 GB) and the id map (L2-resident).
+// Work items and how they are dealt.  The output rows are cut into `zones` contiguous ranges of Z = ceil(rows / zones) rows (ES_ZONES = 8, one
+// per XCD; 1 = no zoning).  An item is (unique row, up to ES_COPIES of its copies inside ONE zone); the copies of every (zone, id) are counted,
+// scanned and listed under the key zone * U + id, so every zone owns a contiguous item list in table-row order and zstart[zone * U + r] is where
+// the items of table row r begin in it.  One ticket counter per zone serves all launches of a call: a workgroup takes items of the zone of its
+// XCD and, when none is admissible there, of the following zones; a launch on the table rows below row_end may take item k of zone z only
+// while k < zstart[z * U + row_end], which a bounded compare-and-swap enforces (the table rows past row_end may not be written yet).
+constexpr int ES_THREADS = 1024, ES_COPIES = 4, ES_ZONES = 8, ES_BATCH = 16;  // (ES_BATCH: items per ticket at most, with ES_ZONES counters)
+// (the counts, cursors and ticket counters: 2.9 MB at U = 44 931, for which the runtime's fill takes 0.16 ms of the call's serial head)
+__global__ __launch_bounds__(256) void k_es_zero(uint32_t *__restrict__ w, int words) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) atomicAdd(&cnt[uidx[i]], 1u);
+  if (i < words) w[i] = 0u;
 }
-// exclusive scans of cnt[] (-> cstart: where the positions of id u start) and of ceil(cnt / ES_COPIES) (-> istart: its work items), one
-// workgroup, both sums in the halves of a 64-bit word; cstart[U] = n, istart[U] = number of items
-__global__ __launch_bounds__(1024) void k_es_scan(const uint32_t *__restrict__ cnt, int U, uint32_t *__restrict__ cstart, uint32_t *__restrict__ istart) {
+__global__ __launch_bounds__(256) void k_es_count(const int32_t *__restrict__ uidx, int n, int U, int Z, uint32_t *__restrict__ cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) atomicAdd(&cnt[(i / Z) * U + uidx[i]], 1u);
+}
+// exclusive scans over the K = zones * U keys of cnt[] (-> cstart: where the positions of a key start) and of ceil(cnt / ES_COPIES) (-> zstart:
+// its work items), both sums in the halves of a 64-bit word, in three steps: block sums, their scan by one workgroup, the scan inside every
+// block; cstart[K] = n, zstart[K] = number of items
+__device__ __forceinline__ uint64_t es_scan_load(const uint32_t *__restrict__ cnt, int K, int i) {
+  const uint32_t c = i < K ? cnt[i] : 0u;
+  return (uint64_t)c | ((uint64_t)((c + ES_COPIES - 1) / ES_COPIES) << 32);
+}
+__global__ __launch_bounds__(1024) void k_es_scan_sums(const uint32_t *__restrict__ cnt, int K, uint64_t *__restrict__ bsum) {
+  __shared__ uint64_t wsum[16];
+  uint64_t x = es_scan_load(cnt, K, blockIdx.x * 1024 + threadIdx.x);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = x;
+  __syncthreads();
+  if (threadIdx.x == 0) { uint64_t t = 0; for (int w = 0; w < 16; ++w) t += wsum[w]; bsum[blockIdx.x] = t; }
+}
+__global__ __launch_bounds__(1024) void k_es_scan_offsets(uint64_t *__restrict__ bsum, int nblocks) {   // in place: exclusive scan; bsum[nblocks] = total
   __shared__ uint64_t wsum[16];
   __shared__ uint64_t carry_s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (tid == 0) carry_s = 0;
   __syncthreads();
-  for (int base = 0; base < U; base += 1024) {
-    const int u = base + tid;
-    const uint32_t c = u < U ? cnt[u] : 0u;
-    const uint64_t v = (uint64_t)c | ((uint64_t)((c + ES_COPIES - 1) / ES_COPIES) << 32);
+  for (int base = 0; base < nblocks; base += 1024) {
+    const int i = base + tid;
+    const uint64_t v = i < nblocks ? bsum[i] : 0;
     uint64_t x = v;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -2016,29 +2039,45 @@ __global__ __launch_bounds__(1024) void k_es_scan(const uint32_t *__restrict__ c
     uint64_t woff = 0;
     for (int w = 0; w < wave; ++w) woff += wsum[w];
     const uint64_t carry = carry_s;
-    if (u < U) {
-      const uint64_t e = carry + woff + x - v;
-      cstart[u] = (uint32_t)e;
-      istart[u] = (uint32_t)(e >> 32);
-    }
+    if (i < nblocks) bsum[i] = carry + woff + x - v;
     __syncthreads();
     if (tid == 1023) carry_s = carry + woff + x;
     __syncthreads();
   }
-  if (tid == 0) { cstart[U] = (uint32_t)carry_s; istart[U] = (uint32_t)(carry_s >> 32); }
+  if (tid == 0) bsum[nblocks] = carry_s;
 }
-// positions of every id's copies (any order inside an id: the copies receive identical values) and the item list
-__global__ __launch_bounds__(256) void k_es_fill(const int32_t *__restrict__ uidx, int n, int U, const uint32_t *__restrict__ cstart,
-                                                 const uint32_t *__restrict__ istart, uint32_t *__restrict__ cursor, int32_t *__restrict__ cpos,
+__global__ __launch_bounds__(1024) void k_es_scan_apply(const uint32_t *__restrict__ cnt, int K, const uint64_t *__restrict__ bsum,
+                                                        uint32_t *__restrict__ cstart, uint32_t *__restrict__ zstart) {
+  __shared__ uint64_t wsum[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x * 1024 + tid;
+  const uint64_t v = es_scan_load(cnt, K, i);
+  uint64_t x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint64_t y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  uint64_t woff = bsum[blockIdx.x];
+  for (int w = 0; w < wave; ++w) woff += wsum[w];
+  const uint64_t e = woff + x - v;
+  if (i < K) { cstart[i] = (uint32_t)e; zstart[i] = (uint32_t)(e >> 32); }
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) { const uint64_t t = bsum[gridDim.x]; cstart[K] = (uint32_t)t; zstart[K] = (uint32_t)(t >> 32); }
+}
+// positions of every key's copies (any order inside a key: the copies receive identical values) and the item lists: (id, first copy of the key)
+__global__ __launch_bounds__(256) void k_es_fill(const int32_t *__restrict__ uidx, int n, int U, int Z, int K, const uint32_t *__restrict__ cstart,
+                                                 const uint32_t *__restrict__ zstart, uint32_t *__restrict__ cursor, int32_t *__restrict__ cpos,
                                                  int2 *__restrict__ items) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
-    const int u = uidx[i];
-    cpos[cstart[u] + atomicAdd(&cursor[u], 1u)] = i;
+    const int key = (i / Z) * U + uidx[i];
+    cpos[cstart[key] + atomicAdd(&cursor[key], 1u)] = i;
   }
-  if (i < U) {
-    const uint32_t first = istart[i], cnt = istart[i + 1] - first;
-    for (uint32_t q = 0; q < cnt; ++q) items[first + q] = make_int2(i, (int)(q * ES_COPIES));
+  if (i < K) {
+    const uint32_t first = zstart[i], cnt = zstart[i + 1] - first;
+    for (uint32_t q = 0; q < cnt; ++q) items[first + q] = make_int2(i % U, (int)(q * ES_COPIES));
   }
 }
 // count / n_hash without a table and without the division sequence: with r = RN(1 / b), q0 = RN(a r), e = a - q0 b (exact in one FMA),
@@ -2063,9 +2102,9 @@ template <int FMT, int NQ>                    // NQ: 16-byte units of a table ro
 __global__ __launch_bounds__(ES_THREADS, 8)   // <= 64 VGPRs: the 4 waves per SIMD of one workgroup leave 256 VGPRs = two K2 waves
 void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t *__restrict__ uidx,
                                                               const uint32_t *__restrict__ cstart, const int32_t *__restrict__ cpos,
-                                                              const int2 *__restrict__ items, const uint32_t *__restrict__ istart, int row_begin,
+                                                              const int2 *__restrict__ items, const uint32_t *__restrict__ zstart, int U, int zones,
                                                               int row_end, int n, int n_hash, double *__restrict__ out, int64_t ld,
-                                                              uint32_t *__restrict__ ticket) {
+                                                              uint32_t *ticket, int max_batch) {
   extern __shared__ __attribute__((aligned(16))) unsigned char es_lds[];   // the table row
 #ifdef ES_PRIO
   __builtin_amdgcn_s_setprio(ES_PRIO);   // (experiment: issue priority of the storing waves beside the compare's, which run their loop at priority 2)
@@ -2079,7 +2118,6 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
     if (!PACKED) return row[c];
     return (uint32_t)row_lo[c] | ((((uint32_t)row_hi[c >> 3] >> (c & 7)) & 1u) << 8);
   };
-  const int n_items = (int)istart[row_end];                          // the items of the table rows [row_begin, row_end)
   const int64_t row_bytes = FMT == ES_PK ? pk_row_bytes(ld_d) : 2 * ld_d;
   const int units = (int)(row_bytes >> 4);
   uint4 pre[NQ];
@@ -2091,18 +2129,49 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
       pre[q] = u < units ? src_[u] : make_uint4(0, 0, 0, 0);                                            \
     }                                                                                                   \
   }
-  // a workgroup's first item is its block index, the following ones come from a ticket counter: items carry 1 ... ES_COPIES output rows, a
-  // static deal leaves the slowest workgroup ~8 % behind the mean
-  __shared__ int s_next;
-  const int base = (int)istart[row_begin];
-  int k = base + (int)blockIdx.x;
-  int2 it = k < n_items ? items[k] : make_int2(0, 0);
-  if (k < n_items) ES_FETCH(it.x)
+  // Items come from the call's per-zone ticket counters (thread 0; items carry 1 ... ES_COPIES output rows, a static deal leaves the slowest
+  // workgroup ~8 % behind the mean): first the zone of this workgroup's XCD, then the following ones.  The XCC id only chooses where to look
+  // first -- any value gives the same matrix.  Tickets are taken by compare-and-swap and only below the zone's limit for row_end, so no item
+  // of a table row that this launch may not read yet can be taken; a workgroup that finds no admissible item in any zone leaves (the items
+  // past the limits belong to the launches that follow).  A counter hands out one successful compare-and-swap per round trip -- far fewer
+  // than the items per microsecond of a call -- and the workgroup waits for its ticket, so a ticket is a batch of consecutive items of the
+  // zone: what is left of the ZONE / the workgroups per counter (guided self-scheduling: single items only at the very end of the call), at
+  // most max_batch, and never past the launch's limit -- what a launch leaves below its limit is the next launch's, so it need not be dealt
+  // finely (tools/ubench/store_bw, `mixed` lines).
+  __shared__ int s_next, s_end, s_zone;
+  unsigned home;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(home));
+  home = (home & 7u) % (unsigned)zones;
+  const uint32_t home_z0 = zstart[home * U], home_lim = zstart[home * U + row_end] - home_z0,   // (the own zone's limits: read once)
+                 home_all = zstart[home * U + U] - home_z0;
+  const uint32_t share = max(1u, gridDim.x / (unsigned)zones);
+  auto take = [&]() {
+    int tz = -1, tk = 0, te = 0;
+    for (int t = 0; t < zones && tz < 0; ++t) {
+      const int z = (int)((home + (unsigned)t) % (unsigned)zones);
+      const uint32_t z0 = t ? zstart[z * U] : home_z0, lim = t ? zstart[z * U + row_end] - z0 : home_lim,
+                     all = t ? zstart[z * U + U] - z0 : home_all;
+      uint32_t cur = __hip_atomic_load(&ticket[z], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      while (cur < lim) {
+        const uint32_t b = min(min((uint32_t)max_batch, lim - cur), max(1u, (all - cur) / share));   // 1 <= b <= lim - cur
+        const uint32_t old = atomicCAS(&ticket[z], cur, cur + b);
+        if (old == cur) { tz = z; tk = (int)(z0 + cur); te = tk + (int)b; break; }
+        cur = old;
+      }
+    }
+    s_zone = tz; s_next = tk; s_end = te;
+  };
+  if (tid == 0) take();
+  __syncthreads();
+  int z = __builtin_amdgcn_readfirstlane(s_zone), k = __builtin_amdgcn_readfirstlane(s_next), k_end = __builtin_amdgcn_readfirstlane(s_end);
+  int2 it = z >= 0 ? items[k] : make_int2(0, 0);
+  if (z >= 0) ES_FETCH(it.x)
   const int2 *u2 = reinterpret_cast<const int2 *>(uidx);
   const int j2_end = n >> 1;
-  while (k < n_items) {
-    __syncthreads();                                                 // the previous item's reads have left the LDS row
-    if (tid == 0) s_next = base + (int)gridDim.x + (int)atomicAdd(ticket, 1u);
+  while (z >= 0) {
+    __syncthreads();                                                 // the previous item's reads have left the LDS row (and s_zone / s_next)
+    const bool more = k + 1 < k_end;                                 // the batch holds another item: no ticket
+    if (tid == 0 && !more) take();
     uint4 *dst = reinterpret_cast<uint4 *>(row);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -2119,14 +2188,17 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
     }
     __syncthreads();
     // this item's output rows (wave-uniform), then the next item's table row on its way while this one is expanded
-    const uint32_t c0 = cstart[it.x] + (uint32_t)it.y, c_end = cstart[it.x + 1];
+    const int key = z * U + it.x;
+    const uint32_t c0 = cstart[key] + (uint32_t)it.y, c_end = cstart[key + 1];
     const int ncop = (int)min((uint32_t)ES_COPIES, c_end - c0);
     double *orow[ES_COPIES];
 #pragma unroll
     for (int q = 0; q < ES_COPIES; ++q) orow[q] = out + (int64_t)cpos[c0 + (uint32_t)min(q, ncop - 1)] * ld;
-    const int kn = __builtin_amdgcn_readfirstlane(s_next);          // wave-uniform: the item, its output rows and the next table row's address stay scalar
+    // (wave-uniform: the item, its output rows and the next table row's address stay scalar)
+    const int zn = more ? z : __builtin_amdgcn_readfirstlane(s_zone), kn = more ? k + 1 : __builtin_amdgcn_readfirstlane(s_next);
+    if (!more) k_end = __builtin_amdgcn_readfirstlane(s_end);
     int2 itn = make_int2(0, 0);
-    if (kn < n_items) { itn = items[kn]; ES_FETCH(itn.x) }
+    if (zn >= 0) { itn = items[kn]; ES_FETCH(itn.x) }
 #pragma unroll 4
     for (int j2 = tid; j2 < j2_end; j2 += ES_THREADS) {
       const int2 c = u2[j2];
@@ -2141,6 +2213,7 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
       for (int q = 0; q < ncop; ++q) orow[q][n - 1] = v;
     }
     it = itn;
+    z = zn;
     k = kn;
   }
 #undef ES_FETCH
@@ -2157,46 +2230,78 @@ extern "C" int da_debug_ratio_check(int n_hash, double *d_out, void *stream) {  
   return DA_OK;
 }
 bool expand_stream_packed(int n_hash) { return n_hash <= 511; }   // counts fit 9 bits: byte + bit plane in LDS
-size_t expand_stream_scratch_bytes(int64_t n, int64_t U) {
-  // cnt[U] + cursor[U] (zeroed together), cstart[U + 1], istart[U + 1], cpos[n], items[U + n / ES_COPIES + 1]
-  return ((size_t)(4 * U + 8 + ES_TICKETS) * 4 + (size_t)n * 4 + (size_t)(U + n / ES_COPIES + 2) * 8 + 1024);
-}
-struct EsLists { uint32_t *cnt, *cursor, *ticket, *cstart, *istart; int32_t *cpos; int2 *items; };
-static EsLists es_layout(void *d_scratch, int64_t n, int64_t U) {
+// the zones of a call: ES_ZONES, or 1 (DYNAALIGN_MH_EXPAND_ZONES=1: one item list and one counter, for A / B timings)
+static int es_zones() { return config().mh_expand_zones == 1 ? 1 : ES_ZONES; }
+struct EsLists { uint32_t *cnt, *cursor, *ticket, *cstart, *zstart; int32_t *cpos; int2 *items; uint64_t *bsum; int zones, Z, K; size_t bytes; };
+// K = zones * U keys: cnt[K] + cursor[K] + ticket[ES_ZONES] (zeroed together), cstart[K + 1], zstart[K + 1], cpos[n], items[min(n, K) + n /
+// ES_COPIES + 2] (a key with c copies has ceil(c / ES_COPIES) items), bsum[ceil(K / 1024) + 1]
+static EsLists es_layout(void *d_scratch, int64_t n, int64_t U, int zones) {
   uint32_t *w = static_cast<uint32_t *>(d_scratch);
   EsLists L;
-  L.cnt = w; L.cursor = w + U; L.ticket = w + 2 * U; L.cstart = L.ticket + ES_TICKETS; L.istart = L.cstart + (U + 1);   // cnt, cursor, ticket: zeroed together
-  L.cpos = reinterpret_cast<int32_t *>(L.istart + (U + 1));
+  const int64_t K = (int64_t)zones * U;
+  L.zones = zones; L.Z = (int)ceil_div(n, zones); L.K = (int)K;
+  L.cnt = w; L.cursor = w + K; L.ticket = w + 2 * K; L.cstart = L.ticket + ES_ZONES; L.zstart = L.cstart + (K + 1);
+  L.cpos = reinterpret_cast<int32_t *>(L.zstart + (K + 1));
   L.items = reinterpret_cast<int2 *>((reinterpret_cast<uintptr_t>(L.cpos + n) + 15) & ~(uintptr_t)15);
+  L.bsum = reinterpret_cast<uint64_t *>(L.items + (std::min(n, K) + n / ES_COPIES + 2));
+  L.bytes = (size_t)(reinterpret_cast<unsigned char *>(L.bsum + (ceil_div(K, 1024) + 1)) - static_cast<unsigned char *>(d_scratch));
   return L;
 }
-// the copy lists of the row expansion (positions of every unique id's copies, work items), stream-ordered
-int launch_expand_stream_lists(const int32_t *d_uidx, int64_t n, int64_t U, void *d_scratch, hipStream_t stream) {
-  const EsLists L = es_layout(d_scratch, n, U);
-  DA_HIP_TRY(hipMemsetAsync(L.cnt, 0, ((size_t)U * 2 + ES_TICKETS) * 4, stream));
-  const unsigned nb = (unsigned)ceil_div(std::max(n, U), 256);
-  hipLaunchKernelGGL(k_es_count, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, d_uidx, (int)n, L.cnt);
-  hipLaunchKernelGGL(k_es_scan, dim3(1), dim3(1024), 0, stream, L.cnt, (int)U, L.cstart, L.istart);
-  hipLaunchKernelGGL(k_es_fill, dim3(nb), dim3(256), 0, stream, d_uidx, (int)n, (int)U, L.cstart, L.istart, L.cursor, L.cpos, L.items);
+size_t expand_stream_scratch_bytes(int64_t n, int64_t U) {   // (for ES_ZONES zones, whatever the call uses; + the 16-byte alignment of the items)
+  return es_layout(nullptr, n, U, ES_ZONES).bytes + 16;
+}
+// the copy lists of the row expansion (positions of every key's copies, work items) and the zeroed ticket counters, stream-ordered
+static int es_lists(const int32_t *d_uidx, int64_t n, int64_t U, void *d_scratch, int zones, hipStream_t stream) {
+  const EsLists L = es_layout(d_scratch, n, U, zones);
+  const int zero_words = 2 * L.K + ES_ZONES;                            // cnt, cursor, ticket
+  hipLaunchKernelGGL(k_es_zero, dim3((unsigned)ceil_div(zero_words, 256)), dim3(256), 0, stream, L.cnt, zero_words);
+  const unsigned nblk = (unsigned)ceil_div(L.K, 1024);
+  hipLaunchKernelGGL(k_es_count, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, d_uidx, (int)n, (int)U, L.Z, L.cnt);
+  hipLaunchKernelGGL(k_es_scan_sums, dim3(nblk), dim3(1024), 0, stream, L.cnt, L.K, L.bsum);
+  hipLaunchKernelGGL(k_es_scan_offsets, dim3(1), dim3(1024), 0, stream, L.bsum, (int)nblk);
+  hipLaunchKernelGGL(k_es_scan_apply, dim3(nblk), dim3(1024), 0, stream, L.cnt, L.K, L.bsum, L.cstart, L.zstart);
+  hipLaunchKernelGGL(k_es_fill, dim3((unsigned)ceil_div(std::max<int64_t>(n, L.K), 256)), dim3(256), 0, stream, d_uidx, (int)n, (int)U, L.Z, L.K,
+                     L.cstart, L.zstart, L.cursor, L.cpos, L.items);
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
-// the launch both expansions share: table rows [row_begin, row_end) through the row lists L (copies among n_rows output rows), columns through
-// the id map d_colids[n_cols]
-static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_colids, int64_t n_cols, const EsLists &L, int64_t n_rows, int64_t row_begin,
-                     int64_t row_end, int n_hash, double *d_out, int64_t ld, hipStream_t stream, int launch_no, bool pk);
-// k_expand_stream on the table rows [row_begin, row_end) (lists from launch_expand_stream_lists on the same scratch)
+int launch_expand_stream_lists(const int32_t *d_uidx, int64_t n, int64_t U, void *d_scratch, hipStream_t stream) {
+  return es_lists(d_uidx, n, U, d_scratch, es_zones(), stream);
+}
+// tests: the lists of `zones` zones (0: what a call uses) built in d_scratch; offsets_out[6] = byte offsets of cstart, zstart, cpos and items in
+// d_scratch, the bytes needed, the zone height Z; zones_out = the zones used.  d_scratch == NULL: only the sizes.
+extern "C" int da_debug_expand_lists(const int32_t *d_uidx, int64_t n, int64_t U, int zones, void *d_scratch, size_t scratch_bytes, int64_t *offsets_out,
+                                     int *zones_out, void *stream) {
+  if (zones == 0) zones = es_zones();
+  if (n < 1 || n > 0x7fffffffLL || U < 1 || U > 65536 || U > n || (zones != 1 && zones != ES_ZONES) || !offsets_out)
+    return fail(DA_ERR_BAD_ARG, "expand lists: bad arguments");
+  const EsLists L = es_layout(d_scratch, n, U, zones);
+  const unsigned char *b = static_cast<const unsigned char *>(d_scratch);
+  offsets_out[0] = reinterpret_cast<const unsigned char *>(L.cstart) - b; offsets_out[1] = reinterpret_cast<const unsigned char *>(L.zstart) - b;
+  offsets_out[2] = reinterpret_cast<const unsigned char *>(L.cpos) - b; offsets_out[3] = reinterpret_cast<const unsigned char *>(L.items) - b;
+  offsets_out[4] = (int64_t)expand_stream_scratch_bytes(n, U); offsets_out[5] = L.Z;
+  if (zones_out) *zones_out = zones;
+  if (!d_scratch) return DA_OK;
+  if (!d_uidx || scratch_bytes < (size_t)offsets_out[4] || (reinterpret_cast<uintptr_t>(d_scratch) & 15)) return fail(DA_ERR_BAD_ARG, "expand lists: bad scratch");
+  return es_lists(d_uidx, n, U, d_scratch, zones, static_cast<hipStream_t>(stream));
+}
+// the launch both expansions share: the items of the table rows below row_end that no earlier launch of the call has taken, through the row
+// lists L (copies among n_rows output rows), columns through the id map d_colids[n_cols]
+static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_colids, int64_t n_cols, const EsLists &L, int64_t n_rows, int64_t U,
+                     int64_t row_end, int n_hash, double *d_out, int64_t ld, hipStream_t stream, bool pk);
+// k_expand_stream on the table rows below row_end (lists from launch_expand_stream_lists on the same scratch): the launches of a call share the
+// lists' ticket counters, so each takes what the earlier ones left, and the one with row_end = U everything that remains
 int launch_expand_stream_rows(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
-                              void *d_scratch, int64_t row_begin, int64_t row_end, hipStream_t stream, int launch_no, bool pk) {
-  if (!expand_stream_ok(n, U, n_hash, d_out, ld) || (ld_d & (pk ? 127 : 7)) || ld_d > 65536 || (reinterpret_cast<uintptr_t>(d_D) & 15) || launch_no < 0 ||
-      launch_no >= ES_TICKETS || (pk && !expand_stream_packed(n_hash)))
+                              void *d_scratch, int64_t row_end, hipStream_t stream, bool pk) {
+  if (!expand_stream_ok(n, U, n_hash, d_out, ld) || (ld_d & (pk ? 127 : 7)) || ld_d > 65536 || (reinterpret_cast<uintptr_t>(d_D) & 15) ||
+      (pk && !expand_stream_packed(n_hash)))
     return fail(DA_ERR_UNSUPPORTED, "row expansion: shape not covered");
   if (row_end > U) row_end = U;
-  if (row_begin >= row_end) return DA_OK;
-  return es_launch(d_D, ld_d, d_uidx, n, es_layout(d_scratch, n, U), n, row_begin, row_end, n_hash, d_out, ld, stream, launch_no, pk);
+  if (row_end <= 0) return DA_OK;
+  return es_launch(d_D, ld_d, d_uidx, n, es_layout(d_scratch, n, U, es_zones()), n, U, row_end, n_hash, d_out, ld, stream, pk);
 }
-static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, const EsLists &L, int64_t n_rows, int64_t row_begin,
-                     int64_t row_end, int n_hash, double *d_out, int64_t ld, hipStream_t stream, int launch_no, bool pk) {
+static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, const EsLists &L, int64_t n_rows, int64_t U,
+                     int64_t row_end, int n_hash, double *d_out, int64_t ld, hipStream_t stream, bool pk) {
   static std::atomic<int> es_cus;
   static std::atomic<uint64_t> es_attr_done;
   int dev = 0;
@@ -2217,11 +2322,11 @@ static int es_launch(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, i
   // never two of these workgroups on one CU (the pipelined form's consecutive launches would otherwise fill the VGPR file with 8 waves per SIMD
   // and lock the compare kernel out until the older launch has drained): ask for more than half of the CU's 160 KB
   lds = std::max<size_t>(lds, 82 * 1024);
-  // one resident workgroup (16 waves) per CU: every workgroup of the grid must be resident from the start (first items are dealt by block index)
+  // one workgroup (16 waves) per CU, and no more than there can be items
   int64_t grid = (int64_t)es_cus.load();
-  grid = std::min<int64_t>(grid, (row_end - row_begin) + n_rows / ES_COPIES + 1);
+  grid = std::min<int64_t>(grid, std::min<int64_t>(n_rows, L.K) + n_rows / ES_COPIES + 1);
 #define DA_ES(P, Q) hipLaunchKernelGGL((k_expand_stream<P, Q>), dim3((unsigned)grid), dim3(ES_THREADS), lds, stream, d_D, ld_d, d_uidx, L.cstart, L.cpos, L.items, \
-                                       L.istart, (int)row_begin, (int)row_end, (int)n, n_hash, d_out, ld, L.ticket + launch_no)
+                                       L.zstart, (int)U, L.zones, (int)row_end, (int)n, n_hash, d_out, ld, L.ticket, ES_BATCH * ES_ZONES / L.zones)
   const int64_t nq = ceil_div((pk ? pk_row_bytes(ld_d) : 2 * ld_d) >> 4, ES_THREADS);   // 16-byte units of a table row per thread
 #define DA_ES_NQ(F) do { if (nq <= 2) DA_ES(F, 2); else if (nq <= 4) DA_ES(F, 4); else if (nq <= 6) DA_ES(F, 6); else DA_ES(F, 8); } while (0)
   if (pk) DA_ES_NQ(ES_PK);
@@ -2238,7 +2343,7 @@ int launch_expand_stream(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uid
   int rc = launch_expand_stream_lists(d_uidx, n, U, d_scratch, stream);
   if (rc != DA_OK) return rc;
   if (after_lists) DA_HIP_TRY(hipEventRecord(after_lists, stream));
-  return launch_expand_stream_rows(d_D, ld_d, d_uidx, n, U, n_hash, d_out, ld, d_scratch, 0, U, stream, 0, pk);
+  return launch_expand_stream_rows(d_D, ld_d, d_uidx, n, U, n_hash, d_out, ld, d_scratch, U, stream, pk);
 }
 
 // ---- the RECTANGULAR row expansion (two-set calls: da_dev_similarity_mh_cross) ----------------------------------------------------------------
@@ -2258,7 +2363,7 @@ int launch_expand_stream_rect(const uint16_t *d_D, int64_t ld_d, const int32_t *
   int rc = launch_expand_stream_lists(d_uidx_x, m, U_x, d_scratch, stream);   // the copies of every unique row of x: expand_stream_scratch_bytes(m, U_x)
   if (rc != DA_OK) return rc;
   if (after_lists) DA_HIP_TRY(hipEventRecord(after_lists, stream));
-  return es_launch(d_D, ld_d, d_uidx_y, n, es_layout(d_scratch, m, U_x), m, 0, U_x, n_hash, d_out, ld, stream, 0, false);
+  return es_launch(d_D, ld_d, d_uidx_y, n, es_layout(d_scratch, m, U_x, es_zones()), m, U_x, U_x, n_hash, d_out, ld, stream, false);
 }
 
 // filler rows of a signature matrix: rows [m, m_pad) repeat rows 0, 1, ... of the real ones (the two-set operand [x ; pad ; y]: a filler row
