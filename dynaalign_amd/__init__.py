@@ -20,6 +20,8 @@ from .similarity import (  # noqa: F401
     SimilarityStats, compute_similarity_stats, stats_from_histogram, similarityMH_stats, similarityNW_stats, similarityNW_stats_long,
     similarityMH_knn, similarityNW_knn, knn_dense, knn_graph, similarityMH_knn_edges, similarityNW_knn_edges,
     similarityNW_knn_long, similarityNW_knn_edges_long, similarityNW_cross_topk_long,
+    jaccard_dense, jaccard_counts, similarityJaccard, similarityJaccard_cross, similarityJaccard_cross_topk, similarityJaccard_knn,
+    similarityJaccard_knn_edges, similarityJaccard_edges,
 )
 
 __all__ = [
@@ -28,5 +30,7 @@ __all__ = [
     "SimilarityStats", "compute_similarity_stats", "stats_from_histogram", "similarityMH_stats", "similarityNW_stats", "similarityNW_stats_long",
     "similarityMH_knn", "similarityNW_knn", "knn_dense", "knn_graph", "similarityMH_knn_edges", "similarityNW_knn_edges",
     "similarityNW_knn_long", "similarityNW_knn_edges_long", "similarityNW_cross_topk_long",
+    "jaccard_dense", "jaccard_counts", "similarityJaccard", "similarityJaccard_cross", "similarityJaccard_cross_topk", "similarityJaccard_knn",
+    "similarityJaccard_knn_edges", "similarityJaccard_edges",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

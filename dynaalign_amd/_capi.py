@@ -40,6 +40,15 @@ SIGNATURES = {
     "da_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
     "da_similarity_nw_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp]),
     "da_nw_code_ranks": (_i32, [_i32, _vp, _vp]),
+    "da_similarity_jaccard": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "da_similarity_jaccard_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32]),
+    "da_similarity_jaccard_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "da_similarity_jaccard_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "da_similarity_jaccard_edges": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "da_similarity_jaccard_edges_begin": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _vp]),
+    "da_dev_jaccard_sets_ld": (_i64, [_i64, _i32]),
+    "da_dev_jaccard_sets": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "da_dev_jaccard_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_align_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "da_nw_align_workspace_bytes": (_sz, [_i64]),
     "da_dev_nw_align_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1609,6 +1609,39 @@ int da_dev_nw_rect(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, 
                         static_cast<hipStream_t>(stream));
 }
 
+// ---- the exact Jaccard index of k-shingle sets, device layer (jaccard_kernels.hip) -----------------------------------------------------------
+// k in 1 .. 8 and at most 127 shingle positions in a sequence of max_len bytes; `seq` > 0 names the (1-based) sequence that is too long
+static int jaccard_limits(int k, int64_t max_len, int64_t seq) {
+  if (k > 8) return fail(DA_ERR_UNSUPPORTED, "the exact Jaccard index packs a shingle into one 64-bit key: k <= 8 (got %d)", k);
+  if (max_len - k + 1 > 127) {
+    if (seq > 0)
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld has %lld shingle positions: the exact Jaccard index takes at most 127 (length - k + 1 <= 127)",
+                  (long long)seq, (long long)(max_len - k + 1));
+    return fail(DA_ERR_UNSUPPORTED, "max_len - k + 1 = %lld shingle positions: the exact Jaccard index takes at most 127", (long long)(max_len - k + 1));
+  }
+  return DA_OK;
+}
+
+int64_t da_dev_jaccard_sets_ld(int64_t max_len, int k) { return jaccard_sets_ld(max_len, k); }
+
+int da_dev_jaccard_sets(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t max_len, int k, void *d_keys, int64_t ld_keys,
+                        uint8_t *d_counts, void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (!d_residues || !d_offsets || !d_keys || !d_counts) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (max_len < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  int rc;
+  if ((rc = jaccard_limits(k, max_len, 0)) != DA_OK) return rc;
+  return launch_jaccard_sets(d_residues, d_offsets, n, max_len, k, d_keys, ld_keys, d_counts, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_jaccard_rect(const void *d_keys, const uint8_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
+                        int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, void *stream) {
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (k > 8) return jaccard_limits(k, 0, 0);
+  return launch_jaccard_rect(d_keys, d_counts, n, ld_keys, k, row_begin, row_end, col_begin, col_end, kind, d_out, ld, static_cast<hipStream_t>(stream));
+}
+
 int da_dev_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, void *stream) {
   if (!d_mat || ld < n) return fail(DA_ERR_BAD_ARG, "bad matrix / ld");
   return launch_symmetrize(d_mat, n, ld, kind, static_cast<hipStream_t>(stream));
@@ -2693,6 +2726,182 @@ int da_similarity_nw_knn(const uint8_t *residues, const int64_t *offsets, int64_
     for (int64_t i = 0; i < n; ++i) diag_out[i] = table[sk[(size_t)i]];
   }
   return topk_to_host(didx, dkey, n, top, table, idx_out, val_out);
+}
+
+// ---- the exact Jaccard index of k-shingle sets on the host boundary (dynaalign.h) ----------------------------------------------------------------
+// What every host call shares.  check_one / check_two: the documented validation of one set / of x then y, before a device is needed.  build():
+// DA_ERR_NO_DEVICE last, then the sequences -- two sets as ONE operand [x ; y] of m + n sequences, like NwCross -- and their sorted distinct keys
+// (k_jaccard_sets) on the device.  rect(): rows x columns of that operand as uint16 codes (intersection << 8 | union) or doubles.
+struct JaccardSets {
+  int k = 0;
+  int64_t m = 0, n = 0;                                  // one set: m == 0, n sequences; two sets: x has m, y has n
+  int64_t x_total = 0, y_total = 0, max_len = 0, ld_keys = 0;
+  DeviceInput in;
+  DevBuf keys, counts;
+  static int lengths(const int64_t *off, int64_t cnt, int k) {
+    for (int64_t i = 0; i < cnt; ++i) {
+      const int rc = off[i + 1] - off[i] - k + 1 > 127 ? jaccard_limits(k, off[i + 1] - off[i], i + 1) : DA_OK;
+      if (rc != DA_OK) return rc;
+    }
+    return DA_OK;
+  }
+  int check_one(const uint8_t *res, const int64_t *off, int64_t n_, int k_, bool out_ok) {
+    if (n_ <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+    if (k_ <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+    if (!res || !out_ok) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int rc;
+    if ((rc = check_offsets(off, n_, &y_total, &max_len)) != DA_OK) return rc;
+    if ((rc = jaccard_limits(k_, 0, 0)) != DA_OK || (rc = lengths(off, n_, k_)) != DA_OK) return rc;
+    if (n_ > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "exact Jaccard: too many sequences");
+    k = k_; m = 0; n = n_;
+    return DA_OK;
+  }
+  // (k and the empty shapes are the caller's: they differ between the two-set calls)
+  int check_two(const uint8_t *xr, const int64_t *xo, int64_t m_, const uint8_t *yr, const int64_t *yo, int64_t n_, int k_, bool out_ok) {
+    if (!xr || !yr || !out_ok) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int64_t x_max, y_max;
+    int rc;
+    if ((rc = check_offsets(xo, m_, &x_total, &x_max)) != DA_OK || (rc = check_offsets(yo, n_, &y_total, &y_max)) != DA_OK) return rc;
+    if ((rc = jaccard_limits(k_, 0, 0)) != DA_OK || (rc = lengths(xo, m_, k_)) != DA_OK || (rc = lengths(yo, n_, k_)) != DA_OK) return rc;
+    if (m_ + n_ > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "exact Jaccard: too many sequences");
+    max_len = std::max(x_max, y_max);
+    k = k_; m = m_; n = n_;
+    return DA_OK;
+  }
+  int sets() {
+    int rc;
+    ld_keys = jaccard_sets_ld(max_len, k);
+    if ((rc = keys.alloc((size_t)(m + n) * (size_t)ld_keys * (k <= 4 ? 4 : 8))) != DA_OK || (rc = counts.alloc((size_t)(m + n))) != DA_OK) return rc;
+    return launch_jaccard_sets(in.res.as<uint8_t>(), in.off.as<int64_t>(), m + n, max_len, k, keys.p, ld_keys, counts.as<uint8_t>(), nullptr);
+  }
+  int build(const uint8_t *res, const int64_t *off) {
+    int rc;
+    if ((rc = require_device()) != DA_OK || (rc = in.upload(res, off, n, y_total, nullptr, 0)) != DA_OK) return rc;
+    return sets();
+  }
+  int build(const uint8_t *xr, const int64_t *xo, const uint8_t *yr, const int64_t *yo) {
+    int rc;
+    if ((rc = require_device()) != DA_OK) return rc;
+    std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
+    std::vector<int64_t> off((size_t)(m + n) + 1);
+    if (x_total) memcpy(res.data(), xr, (size_t)x_total);
+    if (y_total) memcpy(res.data() + x_total, yr, (size_t)y_total);
+    for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = xo[i];
+    for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + yo[j];
+    if ((rc = in.upload(res.data(), off.data(), m + n, x_total + y_total, nullptr, 0)) != DA_OK) return rc;
+    return sets();
+  }
+  int rect(int64_t r0, int64_t r1, int64_t c0, int64_t c1, int kind, void *d, int64_t ld, hipStream_t stream) const {
+    return launch_jaccard_rect(keys.p, counts.as<uint8_t>(), m + n, ld_keys, k, r0, r1, c0, c1, kind, d, ld, stream);
+  }
+  // the largest shingle count of the call (at least 1: the code of two empty sets is 1 << 8 | 1) and the bins its codes fall into
+  int nbins() const {
+    const int64_t sh = std::max<int64_t>(1, max_len - k + 1);
+    return (int)((sh << 8) | (2 * sh)) + 1;
+  }
+};
+
+// the rank table of the codes (equal values tie whatever their codes) on the device; *bits_out: the bits a rank takes
+static int jaccard_ranks(DevBuf &drank, int *bits_out) {
+  std::vector<uint16_t> ranks(65536);
+  int distinct = 0, rc;
+  if ((rc = da_nw_code_ranks(127, ranks.data(), &distinct)) != DA_OK || (rc = drank.alloc(65536 * sizeof(uint16_t))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(drank.p, ranks.data(), 65536 * sizeof(uint16_t), hipMemcpyHostToDevice));
+  *bits_out = bits_of(distinct - 1);
+  return DA_OK;
+}
+
+int da_similarity_jaccard(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double *out) {
+  JaccardSets js;
+  int rc;
+  if ((rc = js.check_one(residues, offsets, n, k, out != nullptr)) != DA_OK || (rc = js.build(residues, offsets)) != DA_OK) return rc;
+  Trace tr("similarityJaccard host path");
+  const std::vector<double> table = nw_code_values(65536, 0.0);
+  if (rows_per_block(n, sizeof(uint16_t)) >= n)
+    return codes_to_host(n, out, table, tr, [&](void *d) { return js.rect(0, n, 0, n, DA_OUT_COMPACT, d, n, nullptr); });
+  return rows_to_host(n, 0, n, sizeof(uint16_t), out, [&](int64_t b0, int64_t b1, void *d) { return js.rect(b0, b1, 0, n, DA_OUT_COMPACT, d, n, nullptr); },
+                      nullptr, nullptr, table.data());
+}
+
+int da_similarity_jaccard_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                int64_t n, int k, double *out, int column_major) {
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (m <= 0 || n <= 0) return DA_OK;                    // an m x 0 or 0 x n matrix: nothing to write
+  JaccardSets js;
+  int rc;
+  if ((rc = js.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, k, out != nullptr)) != DA_OK ||
+      (rc = js.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+  const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
+  const std::vector<double> table = nw_code_values(65536, 0.0);
+  // J is symmetric: rows of y against columns of x are the transpose, R's column-major NumericMatrix(m, n)
+  return rows_to_host(cols, 0, rows, sizeof(uint16_t), out, [&](int64_t b0, int64_t b1, void *d) {
+    return column_major ? js.rect(m + b0, m + b1, 0, m, DA_OUT_COMPACT, d, cols, nullptr) : js.rect(b0, b1, m, m + n, DA_OUT_COMPACT, d, cols, nullptr);
+  }, nullptr, nullptr, table.data());
+}
+
+int da_similarity_jaccard_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                     int64_t n, int k, int top, int32_t *idx_out, double *val_out) {
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (m <= 0) return DA_OK;                              // no rows: nothing to write
+  if (n <= 0) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = 0)", top);
+  JaccardSets js;
+  int rc, bits = 16;
+  if ((rc = js.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, k, idx_out != nullptr)) != DA_OK || (rc = topk_check(top, n)) != DA_OK ||
+      (rc = js.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+  DevBuf drank, didx, dkey;
+  if ((rc = jaccard_ranks(drank, &bits)) != DA_OK || (rc = didx.alloc((size_t)m * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  rc = topk_blocks(m, n, drank.as<uint16_t>(), bits, top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return js.rect(b0, b1, m, m + n, DA_OUT_COMPACT, d, ld, nullptr); });
+  if (rc != DA_OK) return rc;
+  return topk_to_host(didx, dkey, m, top, nw_code_values(65536, 0.0), idx_out, val_out);
+}
+
+int da_similarity_jaccard_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int top, int32_t *idx_out, double *val_out) {
+  JaccardSets js;
+  int rc, bits = 16;
+  if ((rc = js.check_one(residues, offsets, n, k, idx_out != nullptr)) != DA_OK || (rc = knn_check(top, n)) != DA_OK ||
+      (rc = js.build(residues, offsets)) != DA_OK) return rc;
+  DevBuf drank, didx, dkey;
+  if ((rc = jaccard_ranks(drank, &bits)) != DA_OK || (rc = didx.alloc((size_t)n * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  rc = topk_blocks(n, n, drank.as<uint16_t>(), bits, top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return js.rect(b0, b1, 0, n, DA_OUT_COMPACT, d, ld, nullptr); }, true);
+  if (rc != DA_OK) return rc;
+  return topk_to_host(didx, dkey, n, top, nw_code_values(65536, 0.0), idx_out, val_out);
+}
+
+// the exact index + clusterbreak's threshold step as an edge list: the codes have the NW code's shape, so its histogram / quantile / extraction
+// path applies with the same value table
+static int jaccard_edges_core(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p, bool want_edges, EdgeSet &es,
+                              int64_t *n_edges_out) {
+  JaccardSets js;
+  int rc;
+  if ((rc = js.check_one(residues, offsets, n, k, true)) != DA_OK) return rc;
+  if (n < 2) return fail(DA_ERR_BAD_ARG, "the threshold is a quantile of the strict upper triangle: need >= 2 sequences");
+  if (!(thresh_p >= 0.0 && thresh_p <= 1.0)) return fail(DA_ERR_BAD_ARG, "thresh_p must be in [0, 1]");
+  if ((rc = js.build(residues, offsets)) != DA_OK) return rc;
+  DevBuf cnt, hist;
+  const int nbins = js.nbins();
+  if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK || (rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;   // uint16 codes stay on the device
+  DA_HIP_TRY(hipMemset(hist.p, 0, (size_t)nbins * 8));
+  if ((rc = js.rect(0, n, 0, n, DA_OUT_COMPACT, cnt.p, n, nullptr)) != DA_OK) return rc;
+  if ((rc = launch_upper_histogram(cnt.as<uint16_t>(), n, n, nbins, hist.as<unsigned long long>(), nullptr)) != DA_OK) return rc;
+  return edges_from_counts(cnt.as<uint16_t>(), n, nbins, hist.as<unsigned long long>(), nw_code_values(nbins, 0.0), thresh_p, want_edges, es, n_edges_out);
+}
+
+int da_similarity_jaccard_edges(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p, double *threshold_out,
+                                int64_t *n_edges_out, int64_t capacity, int32_t *ei, int32_t *ej, double *ew) {
+  return edges_run_deliver(threshold_out, n_edges_out, capacity, ei, ej, ew, [&](bool want_edges, EdgeSet &es, int64_t *cnt) {
+    return jaccard_edges_core(residues, offsets, n, k, thresh_p, want_edges, es, cnt);
+  });
+}
+
+int da_similarity_jaccard_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p, da_edges **handle_out,
+                                      double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool want_edges, EdgeSet &es, int64_t *cnt) {
+    return jaccard_edges_core(residues, offsets, n, k, thresh_p, want_edges, es, cnt);
+  });
 }
 
 // ---- the alignment PATH of listed pairs (nw_align_kernels.hip): which residue sits opposite which, and where the gaps are -------------------

@@ -354,6 +354,14 @@ int launch_nw_align_long(const uint8_t *d_x_codes, const int64_t *d_x_off, int64
                          const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pair_base, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
                          uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, int64_t max_len, void *d_work,
                          size_t work_bytes, hipStream_t stream);
+// jaccard_kernels.hip: the exact Jaccard index of k-shingle sets (da_dev_jaccard_sets / da_dev_jaccard_rect).  Keys are uint32 for k <= 4 and uint64
+// for k 5 .. 8; a set is the ascending distinct keys of a sequence, [n][ld_keys] keys + [n] uint8 counts, ld_keys >= jaccard_sets_ld(max_len, k).
+// The rectangle is rows x columns of ONE set operand, DA_OUT_COMPACT (intersection << 8 | union) or DA_OUT_F64.
+int64_t jaccard_sets_ld(int64_t max_len, int k);
+int launch_jaccard_sets(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t max_len, int k, void *d_keys, int64_t ld_keys, uint8_t *d_counts,
+                        hipStream_t stream);
+int launch_jaccard_rect(const void *d_keys, const uint8_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end, int64_t col_begin,
+                        int64_t col_end, int kind, void *d_out, int64_t ld, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

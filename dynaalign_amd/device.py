@@ -219,6 +219,53 @@ def nw_rect(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row
     return out
 
 
+class JaccardSets:
+    """Operand of jaccard_rect: per sequence the ascending distinct keys of its k-shingles -- ``keys`` (n, ld_keys), int32 for k <= 4 and int64
+    for k 5 .. 8, holding the unsigned bit patterns of the k bytes packed big-endian -- and ``counts`` (n,) uint8, how many of a row's keys are
+    its set; the rest of a row is zero and means nothing."""
+
+    def __init__(self, keys, counts, n, k):
+        self.keys, self.counts, self.n, self.k = keys, counts, int(n), int(k)
+
+    @property
+    def ld_keys(self):
+        return self.keys.stride(0)
+
+
+def jaccard_sets_ld(max_len, k):
+    return int(_capi.load().da_dev_jaccard_sets_ld(int(max_len), int(k)))
+
+
+def jaccard_sets(ds, k):
+    """The shingle sets of the sequences in ``ds`` (da_dev_jaccard_sets): k in 1 .. 8, every sequence at most 127 shingle positions."""
+    lib = _capi.load()
+    _require_cuda(ds.residues, "residues")
+    k = int(k)
+    ld = max(jaccard_sets_ld(ds.max_len, k), 4)
+    keys = torch.empty((max(ds.n, 1), ld), dtype=torch.int32 if k <= 4 else torch.int64, device=ds.residues.device)
+    counts = torch.empty(max(ds.n, 1), dtype=torch.uint8, device=ds.residues.device)
+    _call(lib.da_dev_jaccard_sets, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, ds.max_len, k, keys.data_ptr(), ld, counts.data_ptr(),
+          _stream())
+    return JaccardSets(keys, counts, ds.n, k)
+
+
+def jaccard_rect(sets, row_begin=0, row_end=None, col_begin=0, col_end=None, kind=DA_OUT_F64, out=None):
+    """The exact Jaccard index on a rectangle (da_dev_jaccard_rect): rows [row_begin, row_end) x columns [col_begin, col_end) of the sets, as
+    float64 or as uint16 codes ``intersection << 8 | union`` in an int16 tensor.  On the sets of x + y, rows of x against columns of y give the
+    two-set matrix.  ``out`` may be any view with unit column stride (its row stride is the leading dimension)."""
+    lib = _capi.load()
+    _require_cuda(sets.keys, "shingle sets")
+    n = sets.n
+    row_end = n if row_end is None else row_end
+    col_end = n if col_end is None else col_end
+    if out is None:
+        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else torch.int16,
+                          device=sets.keys.device)
+    _call(lib.da_dev_jaccard_rect, sets.keys.data_ptr(), sets.counts.data_ptr(), n, sets.ld_keys, sets.k, int(row_begin), int(row_end),
+          int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
 def nw_align_workspace_bytes(pairs):
     return int(_capi.load().da_nw_align_workspace_bytes(int(pairs)))
 

@@ -20,6 +20,13 @@ and the top-k form of ONE set against itself (per sequence its ``top`` most simi
     similarityNW_knn_long(...), similarityNW_knn_edges_long(...), similarityNW_cross_topk_long(...)    the same for 1 .. 1024 residues
     knn_dense(S, top), knn_graph(idx, val, diag=None, mode="union")   the definitions in numpy
 
+and the EXACT Jaccard index of the k-shingle sets that similarityMH estimates (sequences of at most 127 shingles, k <= 8; no hash functions, no seed)
+
+    similarityJaccard(sequences, k=4)                    similarityJaccard_cross(x, y, k=4)
+    similarityJaccard_cross_topk(x, y, k=4, top=10)      similarityJaccard_knn(sequences, k=4, top=10)
+    similarityJaccard_knn_edges(sequences, k=4, top=10, mode="union")      similarityJaccard_edges(sequences, k=4, thresh_p=0.8)
+    jaccard_dense(sequences, k, y=None), jaccard_counts(sequences, k, y=None)   the definition in Python
+
 and the threshold forms of those (the entries that pass a threshold as a sorted edge list, never the m x n matrix)
 
     similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, threshold=None)
@@ -433,6 +440,121 @@ def similarityNW_knn_edges_long(sequences, matrixName="BLOSUM62", gapOpen=10, ga
     ``clusterbreak(pep, edges_fn=lambda s: similarityNW_knn_edges_long(s, top=10))`` clusters full-length proteins on it."""
     idx, val, diag = _nw_knn("da_similarity_nw_knn_long", sequences, matrixName, gapOpen, gapExt, top)
     return _knn_edges_result(idx, val, diag, mode)
+
+
+def _byte_strings(sequences):
+    if isinstance(sequences, (str, bytes)):
+        sequences = [sequences]
+    return [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in sequences]
+
+
+def jaccard_counts(sequences, k, y=None):
+    """``(intersection, union)``, two int64 matrices: the sizes of S_k(a) & S_k(b) and S_k(a) | S_k(b) for every sequence a of ``sequences``
+    against every b of ``y`` (``y=None``: of ``sequences``), S_k(s) the set of distinct length-k byte substrings of s (empty when
+    len(s) < k).  Plain Python sets, for small inputs: the integers behind jaccard_dense and behind the device's uint16 code
+    ``intersection << 8 | union`` (two empty sets are coded 0x0101)."""
+    k = _as_int(k, "k")
+    if k < 1:
+        raise ValueError("'k' must be a positive integer")
+    xs = [{b[p:p + k] for p in range(len(b) - k + 1)} for b in _byte_strings(sequences)]
+    ys = xs if y is None else [{b[p:p + k] for p in range(len(b) - k + 1)} for b in _byte_strings(y)]
+    inter = np.zeros((len(xs), len(ys)), np.int64)
+    union = np.zeros((len(xs), len(ys)), np.int64)
+    for i, a in enumerate(xs):
+        for j, b in enumerate(ys):
+            c = len(a & b)
+            inter[i, j] = c
+            union[i, j] = len(a) + len(b) - c
+    return inter, union
+
+
+def jaccard_dense(sequences, k, y=None):
+    """The exact Jaccard index of k-shingle sets, the definition in Python: the float64 matrix J[i, j] = intersection / union of
+    jaccard_counts -- one IEEE divide of the two integers -- 1.0 where both sets are empty, 0.0 where exactly one is.  The counterpart of
+    similarityJaccard / similarityJaccard_cross, as knn_dense is of the *_knn calls; no limit on k or the lengths, small inputs only."""
+    inter, union = jaccard_counts(sequences, k, y)
+    out = np.ones(inter.shape, np.float64)
+    np.divide(inter.astype(np.float64), union.astype(np.float64), out=out, where=union > 0)
+    return out
+
+
+def similarityJaccard(sequences, k=4):
+    """The exact Jaccard index of the k-shingle sets of all pairs: what similarityMH estimates with ``n_hash`` hash functions, computed without
+    them -- no seed, no estimator noise, diagonal 1.0 by the definition.  ``== jaccard_dense(sequences, k)`` bit for bit.  k <= 8 and every
+    sequence has at most 127 shingle positions (``len - k + 1 <= 127``); empty sequences and sequences shorter than k are legal (two empty
+    sets give 1.0, one gives 0.0).  Errors "Input sequences vector cannot be empty", "'k' must be a positive integer" as similarityMH."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    out = np.empty((max(n, 1), max(n, 1)), np.float64)
+    _capi.check(lib.da_similarity_jaccard(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), out.ctypes.data))
+    return SimilarityMatrix(out[:n, :n])
+
+
+def similarityJaccard_cross(x, y, k=4):
+    """The exact Jaccard index of every sequence of ``x`` against every sequence of ``y``: the (m, n) matrix, bit for bit the block
+    [0:m, m:m+n] of ``similarityJaccard(x + y, k)``.  An empty ``x`` or ``y`` gives a (0, n) / (m, 0) matrix."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    out = np.empty((max(m, 1), max(n, 1)), np.float64)
+    _capi.check(lib.da_similarity_jaccard_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"),
+                                                out.ctypes.data, 0))
+    return SimilarityMatrix(out[:m, :n])
+
+
+def similarityJaccard_cross_topk(x, y, k=4, top=10):
+    """For every sequence of ``x`` its ``top`` most similar sequences of ``y`` under similarityJaccard_cross, without the (m, n) matrix:
+    ``(idx, val)`` as similarityMH_cross_topk, ``idx == np.argsort(-R, axis=1, kind="stable")[:, :top]``.  Equal values tie whatever their
+    (intersection, union): 2/4 and 3/6 are listed by position.  An empty ``x`` gives (0, top) arrays; ``top`` is clamped to ``len(y)``; an
+    empty ``y`` is an error."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    top = _as_int(top, "top")
+    t = min(top, n) if n > 0 else top
+    idx = np.empty((max(m, 1), max(t, 1)), np.int32)
+    val = np.empty((max(m, 1), max(t, 1)), np.float64)
+    _capi.check(lib.da_similarity_jaccard_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"), t,
+                                                     idx.ctypes.data, val.ctypes.data))
+    return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
+
+
+def similarityJaccard_knn(sequences, k=4, top=10):
+    """For every sequence its ``top`` most similar OTHER sequences under similarityJaccard, without the (n, n) matrix: ``(idx, val) ==
+    knn_dense(similarityJaccard(sequences, k), top)``.  ``top`` is clamped to ``len(sequences) - 1`` and may be at most 1024.  Sequences with
+    equal shingle sets fill each other's lists at 1.0."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    top = _as_int(top, "top")
+    t = min(top, n - 1) if n >= 2 else top
+    idx = np.empty((max(n, 1), max(t, 1)), np.int32)
+    val = np.empty((max(n, 1), max(t, 1)), np.float64)
+    _capi.check(lib.da_similarity_jaccard_knn(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), t, idx.ctypes.data, val.ctypes.data))
+    return idx[:n], val[:n]
+
+
+def similarityJaccard_knn_edges(sequences, k=4, top=10, mode="union"):
+    """The kNN graph of similarityJaccard_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``: knn_graph of the lists with the 1.0
+    diagonal the definition gives.  The ``threshold`` slot holds the smallest off-diagonal weight kept, NaN when none."""
+    idx, val = similarityJaccard_knn(sequences, k, top)
+    return _knn_edges_result(idx, val, 1.0, mode)
+
+
+def similarityJaccard_edges(sequences, k=4, thresh_p=0.8):
+    """similarityJaccard followed by clusterbreak's threshold step (reference R/clusterbreak.R:217-221), fused on the device like
+    similarityMH_edges: ``(threshold, i, j, weight)`` for the entries with i <= j (0-based, sorted, diagonal included) whose value is
+    >= the type-7 ``thresh_p`` quantile of the strict upper triangle and > 0.  A deterministic graph for
+    ``clusterbreak(pep, edges_fn=lambda s: similarityJaccard_edges(s, k=2))``."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    k = _as_int(k, "k")
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_edges_begin(
+        res.ctypes.data, off.ctypes.data, n, k, float(thresh_p), h, thr, cnt))
 
 
 def nw_code_ranks(max_len=127):

@@ -51,6 +51,7 @@ extern "C" {
  * (the two-set threshold entry points -- da_similarity_*_cross_edges_begin, da_dev_similarity_mh_cross_edges, da_dev_rect_histogram,
  *  da_dev_threshold_rows_* -- likewise)
  * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes and their _long forms -- likewise)
+ * (the exact-Jaccard entry points -- da_similarity_jaccard[_cross[_topk] | _knn | _edges[_begin]], da_dev_jaccard_sets[_ld], da_dev_jaccard_rect -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -249,6 +250,55 @@ int da_similarity_mh_knn(const uint8_t *residues, const int64_t *offsets, int64_
                          int32_t *idx_out, double *val_out);
 int da_similarity_nw_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
                          int top, int32_t *idx_out, double *val_out, double *diag_out);
+
+/* ---- the EXACT Jaccard index of k-shingle sets: what similarityMH estimates, without hash functions, seed or estimator noise ----
+ * S_k(s) is the set of distinct length-k byte substrings of s -- byte-wise, any byte value, as the k-mers of da_similarity_mh; empty when
+ * len(s) < k.  J(a, b) = (double)|S_k(a) n S_k(b)| / (double)|S_k(a) u S_k(b)|, one IEEE divide of the two integers; 1.0 when both sets are
+ * empty (what da_similarity_mh gives two strings shorter than k), 0.0 when exactly one is.  Nothing is forced on the diagonal: J(a, a) is 1.0
+ * by the definition.  Empty sequences and sequences shorter than k are legal everywhere; no NaN occurs.
+ * uint16 code (DA_OUT_COMPACT): intersection << 8 | union, 0x0101 for two empty sets -- the shape of the NW code, valued by the same divide
+ * (a code's low byte is never 0).  Wherever an order is needed (top-k, nearest neighbours, the quantile) equal VALUES tie whatever their
+ * codes (2/4 and 3/6): the selection runs on da_nw_code_ranks(127, ...), whose domain holds every (intersection, union) the limits allow.
+ * Limits (DA_ERR_UNSUPPORTED, the text names the limit and, for a sequence, its 1-based index): k <= 8 -- the k bytes pack big-endian into one
+ * key, 32 bits for k <= 4, 64 bits otherwise -- and every sequence has at most 127 shingle positions, len - k + 1 <= 127, so that the union of
+ * a pair fits the code's low byte.
+ * Validation, before any device is needed.  One set: n <= 0 -> DA_ERR_EMPTY_INPUT, k <= 0 -> DA_ERR_BAD_K (the texts of da_similarity_mh), NULL
+ * pointers, the offsets, k > 8, the sequence lengths; then what the call adds -- _knn: n < 2, top < 1 or top > n - 1 -> DA_ERR_BAD_ARG, top > 1024
+ * -> DA_ERR_UNSUPPORTED (the texts of da_similarity_mh_knn); _edges: n < 2, thresh_p outside [0, 1] -> DA_ERR_BAD_ARG (the texts of
+ * da_similarity_nw_edges).  Two sets: k <= 0 -> DA_ERR_BAD_K; m <= 0 or n <= 0 returns DA_OK and writes nothing (_cross_topk: m <= 0 returns DA_OK,
+ * n <= 0 with m > 0 is DA_ERR_BAD_ARG, no top satisfies 1 <= top <= 0); NULL pointers, the offsets of x then y, k > 8, the lengths of x then y;
+ * then top < 1 or top > n -> DA_ERR_BAD_ARG, top > 1024 -> DA_ERR_UNSUPPORTED (the texts of da_similarity_nw_cross_topk).
+ *   da_similarity_jaccard             out: n * n doubles.  The device writes uint16 codes, a quarter of the bytes cross PCIe and the host widens them.
+ *   da_similarity_jaccard_cross       out: m x n, bit for bit the block [0:m, m:m+n] of da_similarity_jaccard on c(x, y); column_major as
+ *                                     da_similarity_mh_cross.  Both sets form ONE set operand [x ; y] on the device.
+ *   da_similarity_jaccard_cross_topk  idx_out [m][top] int32, val_out [m][top] float64 or NULL: numpy's argsort(-R, axis = 1, kind = "stable")[:, :top].
+ *   da_similarity_jaccard_knn         idx_out / val_out [n][top]: the `top` columns j != i of every row, as da_similarity_mh_knn.  Byte-identical
+ *                                     strings (and any two strings with equal shingle sets) fill each other's lists at 1.0.
+ *   da_similarity_jaccard_edges[_begin]  threshold = R's type-7 quantile of the strict upper triangle at thresh_p; the edges i <= j, diagonal
+ *                                     included, with J >= threshold and J > 0, sorted by (i, j); calling conventions of da_similarity_nw_edges[_begin].
+ * Single device, the direct route only; top-k / kNN work in row blocks of DYNAALIGN_BLOCK_BYTES. */
+int da_similarity_jaccard(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double *out);
+int da_similarity_jaccard_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, int k, double *out, int column_major);
+int da_similarity_jaccard_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                     const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, int k, int top, int32_t *idx_out, double *val_out);
+int da_similarity_jaccard_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int top, int32_t *idx_out, double *val_out);
+/* (da_similarity_jaccard_edges[_begin] are declared with the other edge-list calls, after da_edges) */
+/* The device layer.  da_dev_jaccard_sets: per sequence the ascending distinct keys of its shingles (uint32 for k <= 4, uint64 for k 5 .. 8; the k
+ * bytes big-endian) at d_keys[i * ld_keys + 0 .. d_counts[i]) and their number d_counts[i] (uint8); the slots from the count to ld_keys are zeroed
+ * and mean nothing -- FF FF FF FF is a legal shingle, the counts say where a list ends.  ld_keys >= da_dev_jaccard_sets_ld(max_len, k), the call's
+ * largest shingle count rounded up to a multiple of 4 (at least 4, at most 128): a set of 12-mers at k = 2 costs 12 keys a row.  max_len: the longest
+ * sequence (max_len - k + 1 <= 127).  n <= 0 -> DA_ERR_EMPTY_INPUT, k <= 0 -> DA_ERR_BAD_K, NULL pointers -> DA_ERR_BAD_ARG, k > 8 or too long ->
+ * DA_ERR_UNSUPPORTED, ld_keys too small -> DA_ERR_BAD_ARG.
+ * da_dev_jaccard_rect: rows [row_begin, row_end) x columns [col_begin, col_end) of the n sets, element (i, j) = J(set i, set j), as DA_OUT_COMPACT
+ * codes or DA_OUT_F64 doubles at d_out[(i - row_begin) * ld + (j - col_begin)]; any ld >= columns and any naturally aligned d_out (16-byte stores
+ * where the address allows, single elements otherwise); every element written once, nothing else touched; an empty rectangle is DA_OK.  Two sets are
+ * compared through the sets of their concatenation.  Both calls are asynchronous on `stream`. */
+int64_t da_dev_jaccard_sets_ld(int64_t max_len, int k);
+int da_dev_jaccard_sets(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t max_len, int k, void *d_keys, int64_t ld_keys,
+                        uint8_t *d_counts, void *stream);
+int da_dev_jaccard_rect(const void *d_keys, const uint8_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
+                        int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, void *stream);
 
 /* ---- the alignment PATH of listed pairs: how x[i] and y[j] align, not only how similar they are ----
  * Pair p aligns x[pair_x[p]] as sequence1 (length m1) with y[pair_y[p]] as sequence2 (length n2); pair_x == pair_y == NULL means p with p
@@ -664,6 +714,11 @@ int da_similarity_mh_edges_begin(const uint8_t *residues, const int64_t *offsets
 int da_similarity_nw_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n,
                                  const char *matrix_name, int gap_open, int gap_ext, double thresh_p,
                                  da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+/* ... and of the exact Jaccard index (see "the EXACT Jaccard index" above) */
+int da_similarity_jaccard_edges(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p, double *threshold_out,
+                                int64_t *n_edges_out, int64_t capacity, int32_t *ei, int32_t *ej, double *ew);
+int da_similarity_jaccard_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p, da_edges **handle_out,
+                                      double *threshold_out, int64_t *n_edges_out);
 int da_edges_fetch(const da_edges *handle, int64_t capacity, int32_t *ei, int32_t *ej, double *ew);
 void da_edges_free(da_edges *handle);
 /* R's quantile(x, p, type = 7) of the multiset {values[b] repeated hist[b] times},
