@@ -726,7 +726,12 @@ void da_edges_free(da_edges *handle);
 int da_quantile_type7(const uint64_t *hist, const double *values, int nbins, double p, double *q_out);
 /* device pieces: histogram of the strict upper triangle of an n x n uint16 matrix
  * (caller zeroes d_hist[nbins]); append of entries flagged in d_keep[nbins]
- * (caller zeroes *d_count; entries beyond `capacity` are counted, not stored). */
+ * (caller zeroes *d_count; entries beyond `capacity` are counted, not stored).  Both ADD to what they find: a second call
+ * into the same d_hist doubles the counts, a second extraction without zeroing *d_count appends.  Only the strict upper
+ * triangle is read (with include_diagonal != 0 the diagonal too), through any ld >= n and any 2-byte aligned base.  Keys
+ * >= nbins are neither counted nor kept, and the key 65535 is reserved ("not an element"): nbins = 65536 fails with
+ * DA_ERR_UNSUPPORTED ("... value 65535 is reserved") before anything is launched -- d_hist, *d_count and the outputs stay
+ * as they were.  The same holds for the *_rows and shard forms. */
 int da_dev_upper_histogram(const uint16_t *d_compact, int64_t ld, int64_t n, int nbins,
                            uint64_t *d_hist, void *stream);
 int da_dev_extract_edges(const uint16_t *d_compact, int64_t ld, int64_t n, const uint8_t *d_keep,

@@ -171,11 +171,8 @@ def test_rect_odd_rectangles_odd_ld_and_offset_base(da, d4, kind):
                 assert np.array_equal(host.view(np.uint64), want.view(np.uint64)), (r0, r1, c0, c1, ld, offset)
 
 
-@pytest.mark.parametrize("k,length", [(4, 130), (8, 134)], ids=["k4_u32", "k8_u64"])
-def test_rect_127_shingles_beside_empty_sets(da, k, length):
-    """every non-empty sequence has 127 distinct shingles -- the longest list, the largest union (254), the largest LDS tile -- and shares its
-    tiles with empty sets"""
-    from dynaalign_amd import device
+def sequences_of_127_shingles(length):
+    """70 strings of `length` upper-case letters in 3 families with 0-3 substitutions each, and 14 strings without any shingle among them"""
     rng = np.random.RandomState(21)
     par = [bytes(rng.randint(65, 91, length).astype(np.uint8)) for _ in range(3)]
     seqs = []
@@ -186,6 +183,15 @@ def test_rect_127_shingles_beside_empty_sets(da, k, length):
         seqs.append(bytes(b))
         if t % 5 == 0:
             seqs.append(b"" if t % 10 else b"AC")
+    return seqs
+
+
+@pytest.mark.parametrize("k,length", [(4, 130), (8, 134)], ids=["k4_u32", "k8_u64"])
+def test_rect_127_shingles_beside_empty_sets(da, k, length):
+    """every non-empty sequence has 127 distinct shingles -- the longest list, the largest union (254), the largest LDS tile -- and shares its
+    tiles with empty sets"""
+    from dynaalign_amd import device
+    seqs = sequences_of_127_shingles(length)
     d = Data(seqs, k)
     own = np.diag(d.union)
     assert set(own.tolist()) == {0, 127} and d.union.max() == 254 and (d.inter > 100).sum() > d.n
@@ -308,6 +314,70 @@ def test_edges(da, d4, p):
     assert len(ei) > d4.n                                    # more than the diagonal
     if p == 0.8:
         assert thr > 0
+
+
+# ---- the host entry points on 127-shingle sets: codes up to 127 << 8 | 127 = 32 639, so the threshold step's histogram has more bins than its
+# LDS copy holds and the top-k rank table needs 15 bits.  Compared with the set model and numpy alone.
+
+@pytest.fixture(scope="module", params=[(4, 130), (8, 134)], ids=["k4_u32", "k8_u64"])
+def d127(request):
+    k, length = request.param
+    d = Data(sequences_of_127_shingles(length), k)
+    up, codes = d.J[np.triu_indices(d.n, 1)], d.codes[np.triu_indices(d.n, 1)]
+    # an all-zero result, or one whose codes all stay below the 8192 bins of the LDS histogram, cannot pass what follows
+    assert d.n == 84 and codes.max() >= 8192 and (codes >= 8192).mean() > 0.2
+    assert np.quantile(up, 0.8) > 0 and len(np.unique(up)) >= 20
+    return d
+
+
+def quantile_type7_of(x, p):
+    """stats::quantile(x, p, type = 7) in R's arithmetic: qs = x[lo]; (1 - h) qs + h x[hi] when the index lies between two different values"""
+    x = np.sort(np.asarray(x, np.float64))
+    index = 1.0 + (len(x) - 1) * p
+    lo, hi = int(np.floor(index)), int(np.ceil(index))
+    qs, xh = float(x[lo - 1]), float(x[hi - 1])
+    if index > lo and xh != qs:
+        h = index - lo
+        qs = (1.0 - h) * qs + h * xh
+    return qs
+
+
+@pytest.mark.parametrize("p", [0.0, 0.5, 0.8, 1.0])
+def test_edges_of_127_shingle_sets(da, d127, p):
+    thr, ei, ej, w = da.similarityJaccard_edges(d127.seqs, d127.k, p)
+    wthr = quantile_type7_of(d127.J[np.triu_indices(d127.n, 1)], p)
+    assert bits(thr) == bits(wthr), (thr, wthr)
+    wi, wj = np.nonzero(np.triu((d127.J >= wthr) & (d127.J > 0)))              # row-major: sorted by (i, j)
+    order = np.lexsort((ej, ei))
+    assert np.array_equal(ei[order], wi) and np.array_equal(ej[order], wj) and same(w[order], d127.J[wi, wj])
+    assert len(wi) > d127.n and (d127.codes[wi, wj] >= 8192).any()
+    if p == 0.8:
+        assert thr > 0
+    if p == 1.0:
+        assert thr == 1.0 and (wi != wj).any()                                   # the strings without a shingle among themselves
+
+
+def test_knn_of_127_shingle_sets(da, d127):
+    M = d127.J.copy()
+    np.fill_diagonal(M, -np.inf)
+    order = np.argsort(-M, axis=1, kind="stable")
+    for top in (1, 10, d127.n - 1):
+        idx, val = da.similarityJaccard_knn(d127.seqs, d127.k, top)
+        assert idx.dtype == np.int32 and np.array_equal(idx, order[:, :top]), top
+        assert same(val, np.take_along_axis(d127.J, order[:, :top], axis=1)), top
+
+
+def test_cross_topk_of_127_shingle_sets(da, d127):
+    m = 50
+    x, y = d127.seqs[:m], d127.seqs[m:]
+    assert len(y) == 34
+    R = d127.J[:m, m:]
+    assert len(np.unique(R)) >= 10 and (R > 0).mean() > 0.2
+    order = np.argsort(-R, axis=1, kind="stable")
+    for top in (1, 10, 34):
+        idx, val = da.similarityJaccard_cross_topk(x, y, d127.k, top)
+        assert idx.dtype == np.int32 and np.array_equal(idx, order[:, :top]), top
+        assert same(val, np.take_along_axis(R, order[:, :top], axis=1)), top
 
 
 def test_equal_sets_have_equal_minhash_signatures(da, d4):
