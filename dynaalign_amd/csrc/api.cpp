@@ -421,6 +421,7 @@ Config parse_config() {
   c.mh_pipe_wg = (int)std::max<int64_t>(0, std::min<int64_t>(4, env_i64("DYNAALIGN_MH_PIPE_WG", 0)));
   c.mh_pipe_head = (int)std::max<int64_t>(0, env_i64("DYNAALIGN_MH_PIPE_HEAD", 0));
   c.mh_expand_zones = (int)env_i64("DYNAALIGN_MH_EXPAND_ZONES", 0);
+  if (const char *e = getenv("DYNAALIGN_MH_DEDUP_ORDER")) c.mh_dedup_order = !strcmp(e, "first") ? 1 : !strcmp(e, "zoned") ? 2 : 0;
   const int pb = (int)env_i64("DYNAALIGN_PLANE_BITS", 0);
   c.plane_bits = (pb == 32 || pb == 16 || pb == 15 || pb == 14 || pb == 12) ? pb : 0;
   c.k2_no_asm = env_flag("DYNAALIGN_K2_NO_ASM");
@@ -673,7 +674,7 @@ static int count_unique(const uint8_t *d_bytes, const int64_t *d_offsets, int64_
   *U = (int64_t)M + S; return DA_OK;
 }
 enum MhForm { MH_DIRECT = 0, MH_TILES = 1, MH_SPARSE = 2, MH_TILES_PIPE = 3, MH_ROWS = 4, MH_ROWS_PIPE = 5 };   // da_mh_last_route's `taken`
-struct MhRoute { int64_t n = 0, unique = 0, hybrid_pairs = -1; int taken = MH_DIRECT, plane_bits = 0, chunks = 0, expand_launches = 0, hybrid_bits_before = 0; bool packed_table = false; float ms[6] = {0, 0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, column gather, k_expand_rows, diagonal / border tiles
+struct MhRoute { int64_t n = 0, unique = 0, hybrid_pairs = -1; int taken = MH_DIRECT, plane_bits = 0, chunks = 0, expand_launches = 0, hybrid_bits_before = 0, dedup_order = -1; bool packed_table = false; float ms[6] = {0, 0, 0, 0, 0, 0}; };   // plan, K1 + K1b, K2, column gather, k_expand_rows, diagonal / border tiles
 static MhRoute &mh_route() { static thread_local MhRoute r; return r; }
 // the seven events of one call: [0] call, [1] plan done, [2] compare operand done, [3 ..] the form's own
 struct MhEvents {
@@ -693,9 +694,11 @@ struct LaunchUnion {
     if (e > covered_to) { total += e - std::max(b, covered_to); covered_to = e; }
   }
 };
-// The duplicate plan: U unique strings; when collapsed (`take`), ids by first occurrence, the expansion family (`rows`: k_expand_stream, else tiles)
-// and for the tiles ub[b] = unique ids the input rows [0, 1024 b) use (the plan's prefix counts at band boundaries): the tile pipeline's schedule
-struct MhDedup { int64_t U = 0; bool take = false, rows = false; DevBuf work; NwDedupPlan p{}; std::vector<int32_t> ub; };
+// The duplicate plan: U unique strings; when collapsed (`take`), the expansion family (`rows`: k_expand_stream, else tiles) and the ids -- the
+// row forms': zoned (DedupOrder; DYNAALIGN_MH_DEDUP_ORDER=first|zoned), so that every band of table rows the compare finishes unlocks about as
+// many items in each zone of the expansion; the tiles': by first occurrence, with ub[b] = unique ids the input rows [0, 1024 b) use (the plan's
+// prefix counts at band boundaries): the tile pipeline's schedule
+struct MhDedup { int64_t U = 0; bool take = false, rows = false; DedupOrder order = DedupOrder::first; DevBuf work; NwDedupPlan p{}; std::vector<int32_t> ub; };
 // the first half of every MinHash duplicate plan: the plan's workspace and the number of unique strings (synchronises `stream`)
 static int mh_count_unique(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t total, DevBuf *work, NwDedupPlan *p, int64_t *U,
                            hipStream_t stream) {
@@ -721,8 +724,11 @@ static int mh_dedup_plan(const uint8_t *d_res, const int64_t *d_off, int64_t n, 
                         : expand_stream_ok(n, std::min<int64_t>(U, 65536), n_hash, d_out, ld) ? 68 : 60;
   d->take = U > 0 && U * 100 <= n * max_pct && expand_rows_workspace_bytes(n, U, DA_OUT_F64, false, n_hash, 0) != 0;
   if (!d->take) return DA_OK;
-  if ((rc = launch_nw_dedup_build(d_res, d_off, n, U, d->p, stream, true)) != DA_OK) return rc;   // ids by first occurrence
   d->rows = cfg.mh_expand <= MH_EXPAND_ROWSPIPE && expand_stream_ok(n, U, n_hash, d_out, ld);
+  // The row forms take table rows in id order and output rows by zone: the zoned ids put the strings with copies all over the matrix first and
+  // spread every zone's single-copy strings evenly over the remaining table rows.  The matrix does not depend on the numbering.
+  d->order = d->rows && cfg.mh_dedup_order != 1 ? DedupOrder::zoned : DedupOrder::first;
+  if ((rc = launch_nw_dedup_build(d_res, d_off, n, U, d->p, stream, d->order, d->rows ? expand_stream_zones() : 1)) != DA_OK) return rc;
   if (d->rows) return DA_OK;
   const int64_t NB = mh_sym_bands(n);
   std::vector<int32_t> b((size_t)NB);
@@ -1021,6 +1027,7 @@ static int mh_full_symmetric(const uint8_t *d_res, const int64_t *d_off, int64_t
   MhDedup d;
   if ((rc = mh_dedup_plan(d_res, d_off, n, total, n_hash, d_out, ld, &d, stream)) != DA_OK) return rc;
   route.unique = d.U;
+  if (d.take) route.dedup_order = (int)d.order;
   DA_HIP_TRY(hipEventRecord(ev[1], stream));
   // sparse route: only with few duplicates (clustered inputs have large classes: the dense kernels win).  Split: the direct route; the duplicate
   // route's table when it needs more than 12 planes (no banded kernel for those: the split lets the route pipeline at all); with 12 planes the
@@ -1070,6 +1077,44 @@ int da_mh_last_route_split(int64_t *rare_incidences_out, int *plane_bits_without
   const MhRoute &r = mh_route();
   if (rare_incidences_out) *rare_incidences_out = r.hybrid_pairs;
   if (plane_bits_without_out) *plane_bits_without_out = r.hybrid_bits_before;
+  return DA_OK;
+}
+
+// tests: the id order (DedupOrder) of the calling thread's last similarityMH call, -1 when it did not collapse duplicates
+extern "C" int da_debug_mh_last_dedup_order(int *order_out) {
+  if (!order_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *order_out = mh_route().dedup_order;
+  return DA_OK;
+}
+// tests: the duplicate plan's numbering.  Runs the count and the build for `order` (DedupOrder: 0 multi-copy first, 1 first occurrence, 2 zoned)
+// with `zones` zones (0: what a call uses) on n sequences and copies the id of every sequence to d_uidx_out[n]; unique_out = U, multi_out = M, the
+// multi-copy strings.  Synchronises `stream`.
+extern "C" int da_debug_mh_dedup_ids(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t total, int order, int zones, int32_t *d_uidx_out,
+                                     int64_t *unique_out, int64_t *multi_out, void *stream) {
+  if (zones == 0) zones = expand_stream_zones();
+  if (!d_res || !d_off || !d_uidx_out || n < 1 || n > 0x7ffffff0LL || total <= 0 || order < 0 || order > 2 || zones < 1 || zones > ES_ZONES)
+    return fail(DA_ERR_BAD_ARG, "dedup ids: bad arguments");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  DevBuf work;
+  NwDedupPlan p{};
+  int64_t U = 0;
+  int32_t M = 0;
+  int rc;
+  if ((rc = mh_count_unique(d_res, d_off, n, total, &work, &p, &U, st)) != DA_OK) return rc;
+  if ((rc = launch_nw_dedup_build(d_res, d_off, n, U, p, st, static_cast<DedupOrder>(order), zones)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpyAsync(d_uidx_out, p.uidx, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+  DA_HIP_TRY(hipMemcpyAsync(&M, p.pm + n, 4, hipMemcpyDeviceToHost, st));
+  DA_HIP_TRY(hipStreamSynchronize(st));
+  if (unique_out) *unique_out = U;
+  if (multi_out) *multi_out = M;
+  return DA_OK;
+}
+// tests: the zoned order's id function on the host (da_common.hpp zoned_rank).  For zone sizes h[zones] and M multi-copy strings, the ids of
+// all (z, q), q < h[z], zone after zone, into ids_out[sum h]
+extern "C" int da_debug_zoned_ids(const int32_t *h, int zones, int64_t M, int64_t *ids_out) {
+  if (!h || !ids_out || zones < 1 || zones > ES_ZONES || M < 0) return fail(DA_ERR_BAD_ARG, "zoned ids: bad arguments");
+  for (int z = 0; z < zones; ++z)
+    for (int64_t q = 0; q < h[z]; ++q) *ids_out++ = M + zoned_rank(h, zones, z, q);
   return DA_OK;
 }
 
@@ -1182,8 +1227,8 @@ int da_dev_similarity_mh_cross(const uint8_t *d_x_residues, const int64_t *d_x_o
     const double pct = (double)(cfg.mh_dedup_max_pct >= 0 ? cfg.mh_dedup_max_pct : 68);
     take = sx.U > 0 && sy.U > 0 && (double)sx.U * (double)sy.U * 10000.0 <= (double)m * (double)n * pct * pct &&
            expand_stream_rect_ok(m, n, sx.U, sy.U, n_hash, d_out, ld);
-    if (take && ((rc = launch_nw_dedup_build(d_x_residues, d_x_offsets, m, sx.U, sx.p, stream, true)) != DA_OK ||
-                 (rc = launch_nw_dedup_build(d_y_residues, d_y_offsets, n, sy.U, sy.p, stream, true)) != DA_OK)) return rc;
+    if (take && ((rc = launch_nw_dedup_build(d_x_residues, d_x_offsets, m, sx.U, sx.p, stream, DedupOrder::first)) != DA_OK ||
+                 (rc = launch_nw_dedup_build(d_y_residues, d_y_offsets, n, sy.U, sy.p, stream, DedupOrder::first)) != DA_OK)) return rc;
   }
   DA_HIP_TRY(hipEventRecord(ev.e[1], stream));
   MhCrossOperand c;

@@ -27,6 +27,7 @@ struct Config {
   int mh_expand = 0;                                       // 0 default (first form whose shape test passes), 1 rows, 2 rowspipe, 3 pipe, 4 tiles
   int mh_pipe_step = 0, mh_pipe_wg = 0, mh_pipe_head = 0;  // 0: the built-in schedule
   int mh_expand_zones = 0;                                 // row expansion: 1 = one item list and ticket counter, else one per eighth of the output rows
+  int mh_dedup_order = 0;                                  // row forms' unique ids: 0 the built-in choice, 1 first occurrence, 2 zoned (DedupOrder)
   int plane_bits = 0;                                      // lower bound on the code planes: 0 / 12 / 14 / 15 / 16, 32 = raw signature bits
   // compare kernels
   bool k2_no_asm = false, k2_persist = false;
@@ -150,6 +151,20 @@ __host__ __device__ inline int64_t pk_lo_bytes(int64_t U) { return (U + 127) / 1
 __host__ __device__ inline int64_t pk_row_bytes(int64_t lo_bytes) { return lo_bytes + lo_bytes / 8; }
 inline size_t pk_table_bytes(int64_t U) { return (size_t)U * (size_t)pk_row_bytes(pk_lo_bytes(U)); }
 
+// ---- zones of the row expansion (minhash_kernels.hip "ROW expansion") and the duplicate plan's zoned id order --------------------
+// The output rows are cut into `zones` contiguous ranges of zone_rows() rows each (ES_ZONES, one per XCD; 1 = no zoning).  The copy lists
+// (es_layout) and the plan's zoned numbering (k_dd_assign) both take the zone height from here, so they cannot disagree.
+constexpr int ES_ZONES = 8;
+__host__ __device__ inline int64_t zone_rows(int64_t n, int zones) { return (n + zones - 1) / zones; }
+// Zoned order of the single-copy strings: zone z holds h[z] of them, and the q-th one of zone z (in row order) gets the rank of (q, z) among
+// all pairs {(q', z') : q' < h[z']} in lexicographic order -- the singles dealt round-robin over the zones, an exhausted zone skipped.
+// Exact integers: sum over z' of min(q, h[z']) pairs have a smaller q', and one pair per zone z' < z with h[z'] > q shares q.
+__host__ __device__ inline int64_t zoned_rank(const int32_t *h, int zones, int z, int64_t q) {
+  int64_t r = 0;
+  for (int t = 0; t < zones; ++t) r += ((int64_t)h[t] < q ? (int64_t)h[t] : q) + ((t < z && (int64_t)h[t] > q) ? 1 : 0);
+  return r;
+}
+
 // Kernel launchers implemented in the .hip translation units.  All are
 // asynchronous on `stream`; argument checking is done by the C-ABI layer.
 int launch_minhash_signatures(const uint8_t *d_res, const int64_t *d_off, int64_t n,
@@ -244,8 +259,14 @@ struct NwDedupPlan {
 NwDedupPlan nw_dedup_layout(void *work, int64_t n, int64_t total);
 size_t nw_dedup_workspace_bytes(int64_t n, int64_t total);
 int launch_nw_dedup_count(const uint8_t *d_codes, const int64_t *d_off, int64_t n, const NwDedupPlan &p, hipStream_t stream);
+// How the unique strings are numbered (every order is a permutation of [0, U); equal strings share an id):
+//   multi_first  multi-copy strings (ids < M) in order of first occurrence, then the single-copy ones in order of occurrence: NW's plan
+//   first        every string by first occurrence: rows [0, R) of the input only use ids < pm[R] + ps[R] (MinHash's tile forms)
+//   zoned        multi-copy strings as above, then the single-copy ones dealt round-robin over the `zones` row zones of zone_rows(n, zones)
+//                rows (zoned_rank): every band of the table holds about as many singles of each zone (MinHash's row forms)
+enum class DedupOrder { multi_first = 0, first = 1, zoned = 2 };
 int launch_nw_dedup_build(const uint8_t *d_codes, const int64_t *d_off, int64_t n, int64_t U, const NwDedupPlan &p, hipStream_t stream,
-                          bool first_order = false);   // true: unique ids purely by first occurrence (default: multi-copy strings first)
+                          DedupOrder order = DedupOrder::multi_first, int zones = 1);   // zones (1 ... ES_ZONES): the zoned order's
 // minhash_kernels.hip: out[i][j] = value(D[uidx[min(i,j)]][uidx[max(i,j)]]) for the dense symmetric n x n result
 int launch_expand_unique(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int kind, bool is_nw, int n_hash,
                          void *d_out, int64_t ld, hipStream_t stream, int nw_max_len = 0, uint16_t *d_F = nullptr,
@@ -256,6 +277,7 @@ int launch_expand_unique(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uid
 bool expand_stream_ok(int64_t n, int64_t U, int n_hash, const void *d_out, int64_t ld);
 size_t expand_stream_scratch_bytes(int64_t n, int64_t U);
 bool expand_stream_packed(int n_hash);   // the LDS row is packed to 9 bits per count: two K2 rings fit beside it
+int expand_stream_zones();               // the zones of a call's copy lists: ES_ZONES, or 1 (DYNAALIGN_MH_EXPAND_ZONES=1)
 // (pk: d_D is the packed table (pk_*) and ld_d its pk_lo_bytes; needs expand_stream_packed)
 int launch_expand_stream(const uint16_t *d_D, int64_t ld_d, const int32_t *d_uidx, int64_t n, int64_t U, int n_hash, double *d_out, int64_t ld,
                          void *d_scratch, hipStream_t stream, hipEvent_t after_lists = nullptr, bool pk = false);

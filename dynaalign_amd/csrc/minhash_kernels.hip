@@ -1993,7 +1993,7 @@ __global__ __launch_bounds__(256, 4) void k_expand_rows(const uint16_t *__restri
 // the items of table row r begin in it.  One ticket counter per zone serves all launches of a call: a workgroup takes items of the zone of its
 // XCD and, when none is admissible there, of the following zones; a launch on the table rows below row_end may take item k of zone z only
 // while k < zstart[z * U + row_end], which a bounded compare-and-swap enforces (the table rows past row_end may not be written yet).
-constexpr int ES_THREADS = 1024, ES_COPIES = 4, ES_ZONES = 8, ES_BATCH = 16;  // (ES_BATCH: items per ticket at most, with ES_ZONES counters)
+constexpr int ES_THREADS = 1024, ES_COPIES = 4, ES_BATCH = 16;  // (ES_BATCH: items per ticket at most, with ES_ZONES counters; ES_ZONES: da_common.hpp)
 // (the counts, cursors and ticket counters: 2.9 MB at U = 44 931, for which the runtime's fill takes 0.16 ms of the call's serial head)
 __global__ __launch_bounds__(256) void k_es_zero(uint32_t *__restrict__ w, int words) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -2098,6 +2098,9 @@ __global__ __launch_bounds__(256) void k_es_ratio_check(int n_hash, double *__re
 // FMT: ES_U16 (uint16 table, uint16 LDS row), ES_U16_PK (uint16 table, repacked on its way into LDS), ES_PK (the packed table of da_common.hpp,
 // already the LDS image: a plain copy, and 9/16 of the table bytes read)
 enum { ES_U16 = 0, ES_U16_PK = 1, ES_PK = 2 };
+#ifdef ES_STEAL_COUNT   // (experiment build, tools/experiments/build_steal_count.sh: items taken per launch -- indexed by its row_end in bands -- and XCD,
+__device__ unsigned es_steal[64][ES_ZONES][2];   // [0] from the XCD's own zone, [1] from another one; read by da_debug_expand_steals)
+#endif
 template <int FMT, int NQ>                    // NQ: 16-byte units of a table row per thread, rounded up to 2, 4, 6 or 8
 __global__ __launch_bounds__(ES_THREADS, 8)   // <= 64 VGPRs: the 4 waves per SIMD of one workgroup leave 256 VGPRs = two K2 waves
 void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t *__restrict__ uidx,
@@ -2155,6 +2158,9 @@ void k_expand_stream(const uint16_t *__restrict__ D, int64_t ld_d, const int32_t
       while (cur < lim) {
         const uint32_t b = min(min((uint32_t)max_batch, lim - cur), max(1u, (all - cur) / share));   // 1 <= b <= lim - cur
         const uint32_t old = atomicCAS(&ticket[z], cur, cur + b);
+#ifdef ES_STEAL_COUNT
+        if (old == cur) atomicAdd(&es_steal[min(63, (row_end + 1023) >> 10)][home][t ? 1 : 0], b);
+#endif
         if (old == cur) { tz = z; tk = (int)(z0 + cur); te = tk + (int)b; break; }
         cur = old;
       }
@@ -2229,9 +2235,19 @@ extern "C" int da_debug_ratio_check(int n_hash, double *d_out, void *stream) {  
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
+#ifdef ES_STEAL_COUNT
+extern "C" int da_debug_expand_steals(unsigned *out, int reset) {   // out[64][ES_ZONES][2] (host); reset: zero the counters afterwards
+  static const unsigned zero[64 * ES_ZONES * 2] = {};
+  DA_HIP_TRY(hipDeviceSynchronize());
+  if (out) DA_HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(es_steal), sizeof(zero)));
+  if (reset) DA_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(es_steal), zero, sizeof(zero)));
+  return DA_OK;
+}
+#endif
 bool expand_stream_packed(int n_hash) { return n_hash <= 511; }   // counts fit 9 bits: byte + bit plane in LDS
 // the zones of a call: ES_ZONES, or 1 (DYNAALIGN_MH_EXPAND_ZONES=1: one item list and one counter, for A / B timings)
 static int es_zones() { return config().mh_expand_zones == 1 ? 1 : ES_ZONES; }
+int expand_stream_zones() { return es_zones(); }
 struct EsLists { uint32_t *cnt, *cursor, *ticket, *cstart, *zstart; int32_t *cpos; int2 *items; uint64_t *bsum; int zones, Z, K; size_t bytes; };
 // K = zones * U keys: cnt[K] + cursor[K] + ticket[ES_ZONES] (zeroed together), cstart[K + 1], zstart[K + 1], cpos[n], items[min(n, K) + n /
 // ES_COPIES + 2] (a key with c copies has ceil(c / ES_COPIES) items), bsum[ceil(K / 1024) + 1]
@@ -2239,7 +2255,7 @@ static EsLists es_layout(void *d_scratch, int64_t n, int64_t U, int zones) {
   uint32_t *w = static_cast<uint32_t *>(d_scratch);
   EsLists L;
   const int64_t K = (int64_t)zones * U;
-  L.zones = zones; L.Z = (int)ceil_div(n, zones); L.K = (int)K;
+  L.zones = zones; L.Z = (int)zone_rows(n, zones); L.K = (int)K;
   L.cnt = w; L.cursor = w + K; L.ticket = w + 2 * K; L.cstart = L.ticket + ES_ZONES; L.zstart = L.cstart + (K + 1);
   L.cpos = reinterpret_cast<int32_t *>(L.zstart + (K + 1));
   L.items = reinterpret_cast<int2 *>((reinterpret_cast<uintptr_t>(L.cpos + n) + 15) & ~(uintptr_t)15);

@@ -796,16 +796,34 @@ __global__ __launch_bounds__(1024) void k_dd_scan_apply(const int32_t *__restric
     else o64[n] = (int64_t)t;
   }
 }
+// The unique ids (DedupOrder, da_common.hpp).  M = pm[n] multi-copy strings, pm[i] / ps[i] = multi- / single-copy representatives before row i.
+//   multi_first  multi-copy strings pm[i], single-copy ones M + ps[i]
+//   first        pm[i] + ps[i]: one numbering by first occurrence (rows [0, R) of the input only use ids < pm[R] + ps[R])
+//   zoned        multi-copy strings pm[i]; the single-copy string of row i, the q-th single of its zone z = i / Z, M + zoned_rank(h, zones, z, q)
+//                with h[z'] = the singles of zone z' -- a bijection onto [M, U) that deals the zones' singles round-robin
 __global__ __launch_bounds__(256) void k_dd_assign(const int32_t *__restrict__ rep, const int32_t *__restrict__ mult,
                                                    const int32_t *__restrict__ last, const int32_t *__restrict__ pm,
                                                    const int32_t *__restrict__ ps, const int64_t *__restrict__ off, int32_t n,
                                                    int32_t *__restrict__ uid_of, int32_t *__restrict__ ufirst,
-                                                   int32_t *__restrict__ ulast, int32_t *__restrict__ ulen, int first_order) {
+                                                   int32_t *__restrict__ ulast, int32_t *__restrict__ ulen, int order, int zones, int32_t Z) {
+  __shared__ int32_t h[ES_ZONES];
+  if (order == (int)DedupOrder::zoned) {                            // (uniform over the grid)
+    if ((int)threadIdx.x < zones) {
+      const int64_t lo = min((int64_t)n, (int64_t)threadIdx.x * Z), hi = min((int64_t)n, ((int64_t)threadIdx.x + 1) * Z);
+      h[threadIdx.x] = ps[hi] - ps[lo];
+    }
+    __syncthreads();
+  }
   const int32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n || rep[i] != i) return;
   const int32_t M = pm[n];
-  // first_order: one numbering by first occurrence (MinHash's pipelined route: rows [0, R) of the input only use ids < pm[R] + ps[R])
-  const int32_t uid = first_order ? pm[i] + ps[i] : (mult[i] > 1 ? pm[i] : M + ps[i]);
+  int32_t uid;
+  if (order == (int)DedupOrder::first) uid = pm[i] + ps[i];
+  else if (mult[i] > 1) uid = pm[i];
+  else if (order == (int)DedupOrder::zoned) {
+    const int32_t z = i / Z;
+    uid = M + (int32_t)zoned_rank(h, zones, z, (int64_t)(ps[i] - ps[(int64_t)z * Z]));
+  } else uid = M + ps[i];
   uid_of[i] = uid;
   ufirst[uid] = i;
   ulast[uid] = last[i];
@@ -885,10 +903,11 @@ int launch_nw_dedup_count(const uint8_t *d_codes, const int64_t *d_off, int64_t 
 }
 // Stage 2 (stream-ordered, U = M + S known to the host): unique ids, the unique table's codes / offsets, tile-block bounds.
 int launch_nw_dedup_build(const uint8_t *d_codes, const int64_t *d_off, int64_t n, int64_t U, const NwDedupPlan &p, hipStream_t stream,
-                          bool first_order) {
+                          DedupOrder order, int zones) {
+  if (zones < 1 || zones > ES_ZONES) return fail(DA_ERR_BAD_ARG, "dedupe plan: zones must be 1 ... %d (got %d)", ES_ZONES, zones);
   const unsigned nb = (unsigned)ceil_div(n, 256);
   hipLaunchKernelGGL(k_dd_assign, dim3(nb), dim3(256), 0, stream, p.rep, p.mult, p.last, p.pm, p.ps, d_off, (int32_t)n, p.uid_of,
-                     p.ufirst, p.ulast, p.ulen, first_order ? 1 : 0);
+                     p.ufirst, p.ulast, p.ulen, (int)order, zones, (int32_t)zone_rows(n, zones));
   hipLaunchKernelGGL(k_dd_map, dim3(nb), dim3(256), 0, stream, p.rep, p.uid_of, (int32_t)n, p.uidx);
   if (U >= 8192) {
     const int32_t nblk = (int32_t)ceil_div(U, 1024);
