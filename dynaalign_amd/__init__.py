@@ -22,6 +22,8 @@ from .similarity import (  # noqa: F401
     similarityNW_knn_long, similarityNW_knn_edges_long, similarityNW_cross_topk_long,
     jaccard_dense, jaccard_counts, similarityJaccard, similarityJaccard_cross, similarityJaccard_cross_topk, similarityJaccard_knn,
     similarityJaccard_knn_edges, similarityJaccard_edges,
+    similarityJaccard_long, similarityJaccard_cross_long, similarityJaccard_cross_topk_long, similarityJaccard_knn_long,
+    similarityJaccard_knn_edges_long, similarityJaccard_edges_long, similarityJaccard_cross_edges_long, similarityJaccard_stats_long,
 )
 
 __all__ = [
@@ -32,5 +34,7 @@ __all__ = [
     "similarityNW_knn_long", "similarityNW_knn_edges_long", "similarityNW_cross_topk_long",
     "jaccard_dense", "jaccard_counts", "similarityJaccard", "similarityJaccard_cross", "similarityJaccard_cross_topk", "similarityJaccard_knn",
     "similarityJaccard_knn_edges", "similarityJaccard_edges",
+    "similarityJaccard_long", "similarityJaccard_cross_long", "similarityJaccard_cross_topk_long", "similarityJaccard_knn_long",
+    "similarityJaccard_knn_edges_long", "similarityJaccard_edges_long", "similarityJaccard_cross_edges_long", "similarityJaccard_stats_long",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

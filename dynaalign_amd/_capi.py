@@ -49,6 +49,16 @@ SIGNATURES = {
     "da_dev_jaccard_sets_ld": (_i64, [_i64, _i32]),
     "da_dev_jaccard_sets": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
     "da_dev_jaccard_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "da_similarity_jaccard_long": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "da_similarity_jaccard_cross_long": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32]),
+    "da_similarity_jaccard_cross_topk_long": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "da_similarity_jaccard_knn_long": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "da_similarity_jaccard_edges_long_begin": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _vp]),
+    "da_similarity_jaccard_cross_edges_long_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, C.c_double, _i32, _vp, _vp, _vp]),
+    "da_similarity_jaccard_stats_long": (_i32, [_vp, _vp, _i64, _i32, _vp]),
+    "da_jaccard_sets_long_ld": (_i64, [_i64, _i32]),
+    "da_dev_jaccard_sets_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
+    "da_dev_jaccard_rect_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
     "da_nw_align_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "da_nw_align_workspace_bytes": (_sz, [_i64]),
     "da_dev_nw_align_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

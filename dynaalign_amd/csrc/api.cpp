@@ -1655,14 +1655,16 @@ int da_dev_nw_rect(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, 
 }
 
 // ---- the exact Jaccard index of k-shingle sets, device layer (jaccard_kernels.hip) -----------------------------------------------------------
-// k in 1 .. 8 and at most 127 shingle positions in a sequence of max_len bytes; `seq` > 0 names the (1-based) sequence that is too long
-static int jaccard_limits(int k, int64_t max_len, int64_t seq) {
+// k in 1 .. 8 and at most `limit` shingle positions (127, the _long calls 1024) in a sequence of max_len bytes; `seq` > 0 names the (1-based)
+// sequence that is too long
+static int jaccard_limits(int k, int64_t max_len, int64_t seq, int limit = 127) {
   if (k > 8) return fail(DA_ERR_UNSUPPORTED, "the exact Jaccard index packs a shingle into one 64-bit key: k <= 8 (got %d)", k);
-  if (max_len - k + 1 > 127) {
+  if (max_len - k + 1 > limit) {
     if (seq > 0)
-      return fail(DA_ERR_UNSUPPORTED, "sequence %lld has %lld shingle positions: the exact Jaccard index takes at most 127 (length - k + 1 <= 127)",
-                  (long long)seq, (long long)(max_len - k + 1));
-    return fail(DA_ERR_UNSUPPORTED, "max_len - k + 1 = %lld shingle positions: the exact Jaccard index takes at most 127", (long long)(max_len - k + 1));
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld has %lld shingle positions: the exact Jaccard index takes at most %d (length - k + 1 <= %d)",
+                  (long long)seq, (long long)(max_len - k + 1), limit, limit);
+    return fail(DA_ERR_UNSUPPORTED, "max_len - k + 1 = %lld shingle positions: the exact Jaccard index takes at most %d", (long long)(max_len - k + 1),
+                limit);
   }
   return DA_OK;
 }
@@ -1685,6 +1687,28 @@ int da_dev_jaccard_rect(const void *d_keys, const uint8_t *d_counts, int64_t n, 
   if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
   if (k > 8) return jaccard_limits(k, 0, 0);
   return launch_jaccard_rect(d_keys, d_counts, n, ld_keys, k, row_begin, row_end, col_begin, col_end, kind, d_out, ld, static_cast<hipStream_t>(stream));
+}
+
+// ... for sequences of up to 1024 shingle positions (jaccard_long_kernels.hip): the checks of the short pair, in their order
+int64_t da_jaccard_sets_long_ld(int64_t max_len, int k) { return jaccard_sets_long_ld(max_len, k); }
+
+int da_dev_jaccard_sets_long(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t max_len, int k, void *d_keys, int64_t ld_keys,
+                             uint16_t *d_counts, void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (!d_residues || !d_offsets || !d_keys || !d_counts) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (max_len < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  int rc;
+  if ((rc = jaccard_limits(k, max_len, 0, 1024)) != DA_OK) return rc;
+  return launch_jaccard_sets_long(d_residues, d_offsets, n, max_len, k, d_keys, ld_keys, d_counts, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
+                             int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, void *stream) {
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (k > 8) return jaccard_limits(k, 0, 0);
+  return launch_jaccard_rect_long(d_keys, d_counts, n, ld_keys, k, row_begin, row_end, col_begin, col_end, kind, d_out, ld,
+                                  static_cast<hipStream_t>(stream));
 }
 
 int da_dev_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, void *stream) {
@@ -2777,15 +2801,20 @@ int da_similarity_nw_knn(const uint8_t *residues, const int64_t *offsets, int64_
 // What every host call shares.  check_one / check_two: the documented validation of one set / of x then y, before a device is needed.  build():
 // DA_ERR_NO_DEVICE last, then the sequences -- two sets as ONE operand [x ; y] of m + n sequences, like NwCross -- and their sorted distinct keys
 // (k_jaccard_sets) on the device.  rect(): rows x columns of that operand as uint16 codes (intersection << 8 | union) or doubles.
+// JaccardSets(1024) is the operand of the _long calls: the same checks with its limit in the texts, uint16 counts, the long kernels, and
+// rect() as DA_OUT_PACK32 codes (intersection << 16 | union) or doubles.
 struct JaccardSets {
+  const int limit;                                       // shingle positions per sequence: 127, or 1024 (the long kernels)
+  explicit JaccardSets(int limit_ = 127) : limit(limit_) {}
+  bool is_long() const { return limit > 127; }
   int k = 0;
   int64_t m = 0, n = 0;                                  // one set: m == 0, n sequences; two sets: x has m, y has n
   int64_t x_total = 0, y_total = 0, max_len = 0, ld_keys = 0;
   DeviceInput in;
   DevBuf keys, counts;
-  static int lengths(const int64_t *off, int64_t cnt, int k) {
+  int lengths(const int64_t *off, int64_t cnt, int k) const {
     for (int64_t i = 0; i < cnt; ++i) {
-      const int rc = off[i + 1] - off[i] - k + 1 > 127 ? jaccard_limits(k, off[i + 1] - off[i], i + 1) : DA_OK;
+      const int rc = off[i + 1] - off[i] - k + 1 > limit ? jaccard_limits(k, off[i + 1] - off[i], i + 1, limit) : DA_OK;
       if (rc != DA_OK) return rc;
     }
     return DA_OK;
@@ -2816,7 +2845,10 @@ struct JaccardSets {
   int sets() {
     int rc;
     ld_keys = jaccard_sets_ld(max_len, k);
-    if ((rc = keys.alloc((size_t)(m + n) * (size_t)ld_keys * (k <= 4 ? 4 : 8))) != DA_OK || (rc = counts.alloc((size_t)(m + n))) != DA_OK) return rc;
+    if ((rc = keys.alloc((size_t)(m + n) * (size_t)ld_keys * (k <= 4 ? 4 : 8))) != DA_OK ||
+        (rc = counts.alloc((size_t)(m + n) * (is_long() ? sizeof(uint16_t) : 1))) != DA_OK) return rc;
+    if (is_long())
+      return launch_jaccard_sets_long(in.res.as<uint8_t>(), in.off.as<int64_t>(), m + n, max_len, k, keys.p, ld_keys, counts.as<uint16_t>(), nullptr);
     return launch_jaccard_sets(in.res.as<uint8_t>(), in.off.as<int64_t>(), m + n, max_len, k, keys.p, ld_keys, counts.as<uint8_t>(), nullptr);
   }
   int build(const uint8_t *res, const int64_t *off) {
@@ -2837,11 +2869,13 @@ struct JaccardSets {
     return sets();
   }
   int rect(int64_t r0, int64_t r1, int64_t c0, int64_t c1, int kind, void *d, int64_t ld, hipStream_t stream) const {
+    if (is_long()) return launch_jaccard_rect_long(keys.p, counts.as<uint16_t>(), m + n, ld_keys, k, r0, r1, c0, c1, kind, d, ld, stream);
     return launch_jaccard_rect(keys.p, counts.as<uint8_t>(), m + n, ld_keys, k, r0, r1, c0, c1, kind, d, ld, stream);
   }
-  // the largest shingle count of the call (at least 1: the code of two empty sets is 1 << 8 | 1) and the bins its codes fall into
+  // the largest shingle count of the call (at least 1: the code of two empty sets is 1 << 8 | 1) and the bins its uint16 codes fall into
+  int shingles() const { return (int)std::max<int64_t>(1, max_len - k + 1); }
   int nbins() const {
-    const int64_t sh = std::max<int64_t>(1, max_len - k + 1);
+    const int64_t sh = shingles();
     return (int)((sh << 8) | (2 * sh)) + 1;
   }
 };
@@ -3971,17 +4005,14 @@ int da_similarity_nw_stats(const uint8_t *residues, const int64_t *offsets, int6
   return fold.finish(hr, values.data(), n, out);
 }
 
-// The first pass of the long NW edge list (RankBlocks: per block the DP (PACK32), the value ranks in place, the histogram of the strict upper
-// triangle) with the extrema of the block behind it and its records taken to the host: ONE pass of the DP whatever the number of blocks.
-int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
-                                da_similarity_stats *out) {
-  int mid = 0, rc;
-  int64_t total = 0, max_len = 0;
-  if ((rc = nw_stats_validate(residues, offsets, n, matrix_name, out, 1024, &mid, &total, &max_len)) != DA_OK) return rc;
-  NwCodes nw;
-  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
-  hipStream_t stream = nullptr;
-  RankBlocks keys(n, n, true, (int)max_len, nw_square_codes(nw, n, max_len, mid, gap_open, gap_ext, stream), stream);
+}  // extern "C"  (reopened below)
+namespace {
+// The statistics of a square problem on value ranks: the first pass of the long edge lists (RankBlocks: per block the PACK32 codes, the value
+// ranks in place, the histogram of the strict upper triangle) with the extrema of the block behind it and its records taken to the host --
+// ONE pass of the producer whatever the number of blocks.
+int rank_stats(RankBlocks &keys, int64_t n, da_similarity_stats *out) {
+  int rc;
+  const hipStream_t stream = keys.stream;
   const int64_t nbins = keys.bins();
   const std::vector<double> &values = keys.values;
   DevBuf hist, drec;
@@ -4001,6 +4032,128 @@ int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets,
   DA_HIP_TRY(hipMemcpyAsync(h.data(), hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, stream));
   DA_HIP_TRY(hipStreamSynchronize(stream));
   return fold.finish(h, values.data(), n, out);      // ranks ARE the ascending value order
+}
+}  // namespace
+extern "C" {
+
+// the long NW identity's statistics: rank_stats on the symmetric sweep / the row-block DP
+int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open, int gap_ext,
+                                da_similarity_stats *out) {
+  int mid = 0, rc;
+  int64_t total = 0, max_len = 0;
+  if ((rc = nw_stats_validate(residues, offsets, n, matrix_name, out, 1024, &mid, &total, &max_len)) != DA_OK) return rc;
+  NwCodes nw;
+  if ((rc = nw.upload(residues, offsets, n, total)) != DA_OK) return rc;
+  RankBlocks keys(n, n, true, (int)max_len, nw_square_codes(nw, n, max_len, mid, gap_open, gap_ext, nullptr), nullptr);
+  return rank_stats(keys, n, out);
+}
+
+// ---- the exact Jaccard index for sequences of up to 1024 shingle positions (dynaalign.h; jaccard_long_kernels.hip) -------------------------------
+// Each call is its short sibling with JaccardSets(1024).  The dense calls take doubles from the device; wherever an order is needed the
+// PACK32 codes intersection << 16 | union go through the long NW paths' value ranks: with S the call's largest shingle count (at least 1),
+// 1 <= union <= 2 S and intersection <= min(union, S), which is the domain of nw_value_table(S).  A rectangle whose rows and columns are
+// the same range is computed by the symmetric form (launch_jaccard_rect_long sees it), so a square that fits one block costs half.
+int da_similarity_jaccard_long(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double *out) {
+  JaccardSets js(1024);
+  int rc;
+  if ((rc = js.check_one(residues, offsets, n, k, out != nullptr)) != DA_OK || (rc = js.build(residues, offsets)) != DA_OK) return rc;
+  return rows_to_host(n, 0, n, sizeof(double), out, [&](int64_t b0, int64_t b1, void *d) { return js.rect(b0, b1, 0, n, DA_OUT_F64, d, n, nullptr); });
+}
+
+int da_similarity_jaccard_cross_long(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                     const int64_t *y_offsets, int64_t n, int k, double *out, int column_major) {
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (m <= 0 || n <= 0) return DA_OK;                    // an m x 0 or 0 x n matrix: nothing to write
+  JaccardSets js(1024);
+  int rc;
+  if ((rc = js.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, k, out != nullptr)) != DA_OK ||
+      (rc = js.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+  const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
+  // J is symmetric: rows of y against columns of x are the transpose, R's column-major NumericMatrix(m, n)
+  return rows_to_host(cols, 0, rows, sizeof(double), out, [&](int64_t b0, int64_t b1, void *d) {
+    return column_major ? js.rect(m + b0, m + b1, 0, m, DA_OUT_F64, d, cols, nullptr) : js.rect(b0, b1, m, m + n, DA_OUT_F64, d, cols, nullptr);
+  });
+}
+
+int da_similarity_jaccard_cross_topk_long(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                          const int64_t *y_offsets, int64_t n, int k, int top, int32_t *idx_out, double *val_out) {
+  if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+  if (m <= 0) return DA_OK;                              // no rows: nothing to write
+  if (n <= 0) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = 0)", top);
+  JaccardSets js(1024);
+  int rc;
+  if ((rc = js.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, k, idx_out != nullptr)) != DA_OK || (rc = topk_check(top, n)) != DA_OK ||
+      (rc = js.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+  RankBlocks keys(m, n, false, js.shingles(), [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {
+    return js.rect(b0, b1, m, m + n, DA_OUT_PACK32, d, ld, nullptr);
+  }, nullptr);
+  return rank_topk_to_host(keys, m, top, false, idx_out, val_out, nullptr);
+}
+
+int da_similarity_jaccard_knn_long(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int top, int32_t *idx_out, double *val_out) {
+  JaccardSets js(1024);
+  int rc;
+  if ((rc = js.check_one(residues, offsets, n, k, idx_out != nullptr)) != DA_OK || (rc = knn_check(top, n)) != DA_OK ||
+      (rc = js.build(residues, offsets)) != DA_OK) return rc;
+  // not `square`: a block holds all n columns of its rows; the block that is the whole square is computed by the symmetric form
+  RankBlocks keys(n, n, false, js.shingles(), [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {
+    return js.rect(b0, b1, 0, n, DA_OUT_PACK32, d, ld, nullptr);
+  }, nullptr);
+  return rank_topk_to_host(keys, n, top, true, idx_out, val_out, nullptr);
+}
+
+int da_similarity_jaccard_edges_long_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p, da_edges **handle_out,
+                                           double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    JaccardSets js(1024);
+    int rc;
+    if ((rc = js.check_one(residues, offsets, n, k, true)) != DA_OK) return rc;
+    if (n < 2) return fail(DA_ERR_BAD_ARG, "the threshold is a quantile of the strict upper triangle: need >= 2 sequences");
+    if (!(thresh_p >= 0.0 && thresh_p <= 1.0)) return fail(DA_ERR_BAD_ARG, "thresh_p must be in [0, 1]");
+    if ((rc = js.build(residues, offsets)) != DA_OK) return rc;
+    // rows [b0, b1) against columns [c0 = b0, n); the whole square (b0 = 0, b1 = n) is the symmetric form
+    RankKeys keys(n, n, true, js.shingles(), [&](int64_t b0, int64_t b1, int64_t c0, void *d, int64_t ld, bool) {
+      return js.rect(b0, b1, c0, n, DA_OUT_PACK32, d, ld, nullptr);
+    }, nullptr);
+    return edges_to_host(keys, n, thresh_p, true, es, n_edges);
+  });
+}
+
+int da_similarity_jaccard_cross_edges_long_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                                 const int64_t *y_offsets, int64_t n, int k, double thresh, int thresh_is_quantile,
+                                                 da_edges **handle_out, double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    if (k <= 0) return fail(DA_ERR_BAD_K, "%s", da_status_message(DA_ERR_BAD_K));
+    int rc;
+    if (m <= 0 || n <= 0) {                                // an empty rectangle: no edges; it has no quantile
+      if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+      if (thresh_is_quantile) return fail(DA_ERR_BAD_ARG, "quantile of an empty set");
+      es.threshold = thresh;
+      *n_edges = 0;
+      return DA_OK;
+    }
+    JaccardSets js(1024);
+    if ((rc = js.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, k, true)) != DA_OK ||
+        (rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK || (rc = js.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+    RankKeys keys(m, n, false, js.shingles(), [&](int64_t b0, int64_t b1, int64_t, void *d, int64_t ld, bool) {
+      return js.rect(b0, b1, m, m + n, DA_OUT_PACK32, d, ld, nullptr);
+    }, nullptr);
+    return edges_to_host(keys, m, thresh, thresh_is_quantile != 0, es, n_edges);
+  });
+}
+
+// rank_stats on the rectangle kernel.  Empty sets are legal (J = 1.0 for two of them, 0.0 against a non-empty one): no sequence is refused for
+// being empty, unlike in the NW calls.
+int da_similarity_jaccard_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, da_similarity_stats *out) {
+  JaccardSets js(1024);
+  int rc;
+  if ((rc = js.check_one(residues, offsets, n, k, out != nullptr)) != DA_OK) return rc;
+  if (n < 2) return fail(DA_ERR_BAD_ARG, "the statistics are over the strict upper triangle: need >= 2 sequences");
+  if ((rc = js.build(residues, offsets)) != DA_OK) return rc;
+  RankBlocks keys(n, n, true, js.shingles(), [&](int64_t b0, int64_t b1, int64_t c0, void *d, int64_t ld, bool) {
+    return js.rect(b0, b1, c0, n, DA_OUT_PACK32, d, ld, nullptr);
+  }, nullptr);
+  return rank_stats(keys, n, out);
 }
 
 

@@ -384,6 +384,13 @@ int launch_jaccard_sets(const uint8_t *d_res, const int64_t *d_off, int64_t n, i
                         hipStream_t stream);
 int launch_jaccard_rect(const void *d_keys, const uint8_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end, int64_t col_begin,
                         int64_t col_end, int kind, void *d_out, int64_t ld, hipStream_t stream);
+// jaccard_long_kernels.hip: the same for sequences of up to 1024 shingle positions (da_dev_jaccard_sets_long / da_dev_jaccard_rect_long): uint16
+// counts, ld_keys up to 1024, and the rectangle as DA_OUT_PACK32 (intersection << 16 | union) or DA_OUT_F64.
+int64_t jaccard_sets_long_ld(int64_t max_len, int k);
+int launch_jaccard_sets_long(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t max_len, int k, void *d_keys, int64_t ld_keys,
+                             uint16_t *d_counts, hipStream_t stream);
+int launch_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
+                             int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

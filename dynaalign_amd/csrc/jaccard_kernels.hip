@@ -22,6 +22,7 @@
 //   diagonal is stored twice, as it is and transposed, from its codes in LDS (the transposed doubles are the code's own divide, 1 / 1 for 0x0101).
 //   No atomics, no scratch, every element of the rectangle written exactly once, nothing outside it touched.
 #include "da_common.hpp"
+#include "jaccard_common.hpp"
 
 namespace da {
 namespace {
@@ -80,19 +81,6 @@ __global__ __launch_bounds__(JC_THREADS) void k_jaccard_sets(const uint8_t *__re
   }
   for (int q = count + lane; q < ld_keys; q += 64) row[q] = 0;
   if (lane == 0) counts[s] = (uint8_t)count;
-}
-
-// the tile of workgroup b when only the tiles on and above the diagonal of a T x T tile grid are launched, row by row
-__device__ __forceinline__ void jc_upper_tile(unsigned b, int T, int &tr, int &tc) {
-  const double w = 2.0 * T + 1.0;
-  int t = (int)((w - sqrt(w * w - 8.0 * (double)b)) * 0.5);
-  if (t < 0) t = 0;
-  if (t > T - 1) t = T - 1;
-  auto first = [T](int q) { return (long long)q * T - (long long)q * (q - 1) / 2; };   // first workgroup of tile row q
-  while (t > 0 && first(t) > (long long)b) --t;
-  while (t + 1 < T && first(t + 1) <= (long long)b) ++t;
-  tr = t;
-  tc = t + (int)((long long)b - first(t));
 }
 
 template <typename Key, int KIND>

@@ -222,7 +222,8 @@ def nw_rect(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row
 class JaccardSets:
     """Operand of jaccard_rect: per sequence the ascending distinct keys of its k-shingles -- ``keys`` (n, ld_keys), int32 for k <= 4 and int64
     for k 5 .. 8, holding the unsigned bit patterns of the k bytes packed big-endian -- and ``counts`` (n,) uint8, how many of a row's keys are
-    its set; the rest of a row is zero and means nothing."""
+    its set (jaccard_sets_long: uint16 bit patterns in an int16 tensor, the operand of jaccard_rect_long); the rest of a row is zero and means
+    nothing."""
 
     def __init__(self, keys, counts, n, k):
         self.keys, self.counts, self.n, self.k = keys, counts, int(n), int(k)
@@ -262,6 +263,41 @@ def jaccard_rect(sets, row_begin=0, row_end=None, col_begin=0, col_end=None, kin
         out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else torch.int16,
                           device=sets.keys.device)
     _call(lib.da_dev_jaccard_rect, sets.keys.data_ptr(), sets.counts.data_ptr(), n, sets.ld_keys, sets.k, int(row_begin), int(row_end),
+          int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
+def jaccard_sets_long_ld(max_len, k):
+    return int(_capi.load().da_jaccard_sets_long_ld(int(max_len), int(k)))
+
+
+def jaccard_sets_long(ds, k):
+    """The shingle sets of the sequences in ``ds`` for up to 1024 shingle positions a sequence (da_dev_jaccard_sets_long): a JaccardSets whose
+    ``counts`` are uint16 bit patterns in an int16 tensor, the operand of jaccard_rect_long."""
+    lib = _capi.load()
+    _require_cuda(ds.residues, "residues")
+    k = int(k)
+    ld = max(jaccard_sets_long_ld(ds.max_len, k), 4)
+    keys = torch.empty((max(ds.n, 1), ld), dtype=torch.int32 if k <= 4 else torch.int64, device=ds.residues.device)
+    counts = torch.empty(max(ds.n, 1), dtype=torch.int16, device=ds.residues.device)
+    _call(lib.da_dev_jaccard_sets_long, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, ds.max_len, k, keys.data_ptr(), ld,
+          counts.data_ptr(), _stream())
+    return JaccardSets(keys, counts, ds.n, k)
+
+
+def jaccard_rect_long(sets, row_begin=0, row_end=None, col_begin=0, col_end=None, kind=DA_OUT_F64, out=None):
+    """The exact Jaccard index on a rectangle of the sets of jaccard_sets_long (da_dev_jaccard_rect_long): as jaccard_rect, with ``kind``
+    DA_OUT_F64 or DA_OUT_PACK32 -- uint32 codes ``intersection << 16 | union`` (``1 << 16 | 1`` for two empty sets) in an int32 tensor.  A
+    rectangle whose rows and columns are the same range is computed by the symmetric form."""
+    lib = _capi.load()
+    _require_cuda(sets.keys, "shingle sets")
+    n = sets.n
+    row_end = n if row_end is None else row_end
+    col_end = n if col_end is None else col_end
+    if out is None:
+        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else torch.int32,
+                          device=sets.keys.device)
+    _call(lib.da_dev_jaccard_rect_long, sets.keys.data_ptr(), sets.counts.data_ptr(), n, sets.ld_keys, sets.k, int(row_begin), int(row_end),
           int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
     return out
 

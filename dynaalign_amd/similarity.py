@@ -26,6 +26,8 @@ and the EXACT Jaccard index of the k-shingle sets that similarityMH estimates (s
     similarityJaccard_cross_topk(x, y, k=4, top=10)      similarityJaccard_knn(sequences, k=4, top=10)
     similarityJaccard_knn_edges(sequences, k=4, top=10, mode="union")      similarityJaccard_edges(sequences, k=4, thresh_p=0.8)
     jaccard_dense(sequences, k, y=None), jaccard_counts(sequences, k, y=None)   the definition in Python
+    similarityJaccard_long(...), _cross_long, _cross_topk_long, _knn_long, _knn_edges_long, _edges_long, _stats_long: the same for up to 1024
+    shingles, and similarityJaccard_cross_edges_long(x, y, k=4, thresh_p=0.8, threshold=None), the two-set threshold form
 
 and the threshold forms of those (the entries that pass a threshold as a sorted edge list, never the m x n matrix)
 
@@ -483,24 +485,31 @@ def similarityJaccard(sequences, k=4):
     them -- no seed, no estimator noise, diagonal 1.0 by the definition.  ``== jaccard_dense(sequences, k)`` bit for bit.  k <= 8 and every
     sequence has at most 127 shingle positions (``len - k + 1 <= 127``); empty sequences and sequences shorter than k are legal (two empty
     sets give 1.0, one gives 0.0).  Errors "Input sequences vector cannot be empty", "'k' must be a positive integer" as similarityMH."""
+    return _jaccard_square("da_similarity_jaccard", sequences, k)
+
+
+def _jaccard_square(entry, sequences, k):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
     out = np.empty((max(n, 1), max(n, 1)), np.float64)
-    _capi.check(lib.da_similarity_jaccard(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), out.ctypes.data))
+    _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), out.ctypes.data))
     return SimilarityMatrix(out[:n, :n])
 
 
 def similarityJaccard_cross(x, y, k=4):
     """The exact Jaccard index of every sequence of ``x`` against every sequence of ``y``: the (m, n) matrix, bit for bit the block
     [0:m, m:m+n] of ``similarityJaccard(x + y, k)``.  An empty ``x`` or ``y`` gives a (0, n) / (m, 0) matrix."""
+    return _jaccard_cross("da_similarity_jaccard_cross", x, y, k)
+
+
+def _jaccard_cross(entry, x, y, k):
     lib = _capi.load()
     xr, xo = pack_sequences(x)
     yr, yo = pack_sequences(y)
     m, n = len(xo) - 1, len(yo) - 1
     out = np.empty((max(m, 1), max(n, 1)), np.float64)
-    _capi.check(lib.da_similarity_jaccard_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"),
-                                                out.ctypes.data, 0))
+    _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"), out.ctypes.data, 0))
     return SimilarityMatrix(out[:m, :n])
 
 
@@ -509,6 +518,10 @@ def similarityJaccard_cross_topk(x, y, k=4, top=10):
     ``(idx, val)`` as similarityMH_cross_topk, ``idx == np.argsort(-R, axis=1, kind="stable")[:, :top]``.  Equal values tie whatever their
     (intersection, union): 2/4 and 3/6 are listed by position.  An empty ``x`` gives (0, top) arrays; ``top`` is clamped to ``len(y)``; an
     empty ``y`` is an error."""
+    return _jaccard_cross_topk("da_similarity_jaccard_cross_topk", x, y, k, top)
+
+
+def _jaccard_cross_topk(entry, x, y, k, top):
     lib = _capi.load()
     xr, xo = pack_sequences(x)
     yr, yo = pack_sequences(y)
@@ -517,8 +530,8 @@ def similarityJaccard_cross_topk(x, y, k=4, top=10):
     t = min(top, n) if n > 0 else top
     idx = np.empty((max(m, 1), max(t, 1)), np.int32)
     val = np.empty((max(m, 1), max(t, 1)), np.float64)
-    _capi.check(lib.da_similarity_jaccard_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"), t,
-                                                     idx.ctypes.data, val.ctypes.data))
+    _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"), t, idx.ctypes.data,
+                                    val.ctypes.data))
     return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
 
 
@@ -526,6 +539,10 @@ def similarityJaccard_knn(sequences, k=4, top=10):
     """For every sequence its ``top`` most similar OTHER sequences under similarityJaccard, without the (n, n) matrix: ``(idx, val) ==
     knn_dense(similarityJaccard(sequences, k), top)``.  ``top`` is clamped to ``len(sequences) - 1`` and may be at most 1024.  Sequences with
     equal shingle sets fill each other's lists at 1.0."""
+    return _jaccard_knn("da_similarity_jaccard_knn", sequences, k, top)
+
+
+def _jaccard_knn(entry, sequences, k, top):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
@@ -533,7 +550,7 @@ def similarityJaccard_knn(sequences, k=4, top=10):
     t = min(top, n - 1) if n >= 2 else top
     idx = np.empty((max(n, 1), max(t, 1)), np.int32)
     val = np.empty((max(n, 1), max(t, 1)), np.float64)
-    _capi.check(lib.da_similarity_jaccard_knn(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), t, idx.ctypes.data, val.ctypes.data))
+    _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), t, idx.ctypes.data, val.ctypes.data))
     return idx[:n], val[:n]
 
 
@@ -555,6 +572,79 @@ def similarityJaccard_edges(sequences, k=4, thresh_p=0.8):
     k = _as_int(k, "k")
     return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_edges_begin(
         res.ctypes.data, off.ctypes.data, n, k, float(thresh_p), h, thr, cnt))
+
+
+# ---- the exact Jaccard index for sequences of up to 1024 shingle positions: the _long siblings ------------------------------------------------
+
+def similarityJaccard_long(sequences, k=4):
+    """``similarityJaccard`` for sequences of up to 1024 shingle positions, ``len - k + 1 <= 1024`` (da_similarity_jaccard_long): the same
+    arguments, the same result bit for bit -- ``== jaccard_dense(sequences, k)`` -- the same errors with 1024 in place of 127.  What an
+    ``n_hash = 50`` similarityMH estimate of full-length proteins is measured against."""
+    return _jaccard_square("da_similarity_jaccard_long", sequences, k)
+
+
+def similarityJaccard_cross_long(x, y, k=4):
+    """``similarityJaccard_cross`` for sequences of up to 1024 shingle positions (da_similarity_jaccard_cross_long)."""
+    return _jaccard_cross("da_similarity_jaccard_cross_long", x, y, k)
+
+
+def similarityJaccard_cross_topk_long(x, y, k=4, top=10):
+    """``similarityJaccard_cross_topk`` for sequences of up to 1024 shingle positions (da_similarity_jaccard_cross_topk_long): the selection
+    runs on 32-bit value ranks (``nw_value_ranks`` of the call's largest shingle count) of the codes ``intersection << 16 | union``."""
+    return _jaccard_cross_topk("da_similarity_jaccard_cross_topk_long", x, y, k, top)
+
+
+def similarityJaccard_knn_long(sequences, k=4, top=10):
+    """``similarityJaccard_knn`` for sequences of up to 1024 shingle positions (da_similarity_jaccard_knn_long): ``(idx, val) ==
+    knn_dense(similarityJaccard_long(sequences, k), top)`` without the (n, n) matrix."""
+    return _jaccard_knn("da_similarity_jaccard_knn_long", sequences, k, top)
+
+
+def similarityJaccard_knn_edges_long(sequences, k=4, top=10, mode="union"):
+    """``similarityJaccard_knn_edges`` for sequences of up to 1024 shingle positions: knn_graph of similarityJaccard_knn_long's lists with
+    the 1.0 diagonal, as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``."""
+    idx, val = similarityJaccard_knn_long(sequences, k, top)
+    return _knn_edges_result(idx, val, 1.0, mode)
+
+
+def similarityJaccard_edges_long(sequences, k=4, thresh_p=0.8):
+    """``similarityJaccard_edges`` for sequences of up to 1024 shingle positions (da_similarity_jaccard_edges_long_begin): the same
+    arguments, the same result, the same errors.  ``clusterbreak(pep, edges_fn=lambda s: similarityJaccard_edges_long(s, k=4))`` clusters
+    full-length proteins on the exact index."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    k = _as_int(k, "k")
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_edges_long_begin(
+        res.ctypes.data, off.ctypes.data, n, k, float(thresh_p), h, thr, cnt))
+
+
+def similarityJaccard_cross_edges_long(x, y, k=4, thresh_p=0.8, *, threshold=None):
+    """The entries of R = similarityJaccard_cross_long(x, y, k) that pass a threshold, without the (m, n) matrix: ``(threshold, i, j,
+    weight)`` as similarityMH_cross_edges -- every (i, j) with ``R[i, j] >= threshold and R[i, j] > 0``, sorted by (i, j), ``weight`` bit
+    for bit ``R[i, j]``; ``threshold=None`` takes R's type-7 ``thresh_p`` quantile over all m * n entries.  Sequences of up to 1024
+    shingle positions, short ones included (the short family has no such form).  An empty ``x`` or ``y`` gives no edges in the absolute
+    form and is an error in the quantile form."""
+    lib = _capi.load()
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    m, n = len(xo) - 1, len(yo) - 1
+    k = _as_int(k, "k")
+    thresh, is_q = _thresh_args(thresh_p, threshold)
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_cross_edges_long_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, thresh, is_q, h, thr, cnt))
+
+
+def similarityJaccard_stats_long(sequences, k=4):
+    """``compute_similarity_stats(similarityJaccard_long(sequences, k))`` without the matrix on the host (da_similarity_jaccard_stats_long):
+    one pass of the rectangle kernel in row blocks, on 32-bit value ranks.  Empty sequences are legal (two empty sets are 1.0)."""
+    import ctypes
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    s = _capi.DaSimilarityStats()
+    _capi.check(lib.da_similarity_jaccard_stats_long(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), ctypes.addressof(s)))
+    return _stats_result(s)
 
 
 def nw_code_ranks(max_len=127):

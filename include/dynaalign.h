@@ -52,6 +52,8 @@ extern "C" {
  *  da_dev_threshold_rows_* -- likewise)
  * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes and their _long forms -- likewise)
  * (the exact-Jaccard entry points -- da_similarity_jaccard[_cross[_topk] | _knn | _edges[_begin]], da_dev_jaccard_sets[_ld], da_dev_jaccard_rect -- likewise)
+ * (their _long forms -- da_similarity_jaccard[_cross[_topk | _edges] | _knn | _edges | _stats]_long[_begin], da_jaccard_sets_long_ld,
+ *  da_dev_jaccard_sets_long, da_dev_jaccard_rect_long -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -949,6 +951,50 @@ int da_similarity_nw_stats(const uint8_t *residues, const int64_t *offsets, int6
                            da_similarity_stats *out);
 int da_similarity_nw_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, const char *matrix_name, int gap_open,
                                 int gap_ext, da_similarity_stats *out);
+
+/* ---- the exact Jaccard index for sequences of up to 1024 shingle positions (jaccard_long_kernels.hip) ----
+ * Each call is the _long sibling of the da_similarity_jaccard* call of its name: the same arguments, results and errors, with the limit
+ * len - k + 1 <= 1024 (its text is the short call's with 1024 in place of 127) -- the short calls keep their limit of 127.  The code of a
+ * pair is DA_OUT_PACK32, intersection << 16 | union (1 << 16 | 1 for two empty sets); with S the call's largest shingle count (at least
+ * 1) every code lies in the domain of da_nw_value_ranks(S) -- 1 <= union <= 2 S, intersection <= min(union, S) -- and wherever an order is
+ * needed the calls run the long NW paths on those value ranks: histogram, exact type-7 quantile, ordered count / emit, top-k, extrema.
+ *   da_similarity_jaccard_long, _cross_long     doubles from the device, in row blocks of DYNAALIGN_BLOCK_BYTES; a square that fits one
+ *                                               block is computed by the symmetric form (every pair once).
+ *   da_similarity_jaccard_cross_topk_long, _knn_long   as da_similarity_nw_cross_topk_long / _knn_long, in row blocks; the one-set call
+ *                                               computes a block that is the whole square by the symmetric form, else full rows.
+ *   da_similarity_jaccard_edges_long_begin      as da_similarity_jaccard_edges_begin (one pass: da_edges_fetch / da_edges_free).
+ *   da_similarity_jaccard_cross_edges_long_begin  the two-set threshold form, which the short family lacks (it serves short sequences too):
+ *                                               the entries of the m x n matrix with J >= threshold and J > 0, sorted by (i, j); thresh and
+ *                                               thresh_is_quantile as da_similarity_nw_cross_edges_begin.  Validation: k <= 0 -> DA_ERR_BAD_K;
+ *                                               m <= 0 or n <= 0: the threshold check, then DA_ERR_BAD_ARG "quantile of an empty set" in the
+ *                                               quantile form and no edges in the absolute form; NULL pointers, the offsets of x then y, k > 8,
+ *                                               the lengths of x then y; the threshold check; DA_ERR_NO_DEVICE last.
+ *   da_similarity_jaccard_stats_long            compute_similarity_stats of the matrix without the matrix, as da_similarity_nw_stats_long (one
+ *                                               pass of the rectangle kernel whatever the number of blocks).  Validation: the one-set checks,
+ *                                               then n < 2 -> DA_ERR_BAD_ARG.  Empty sets are legal: no sequence is refused for being empty.
+ * Single device, the direct route only.
+ * The device layer.  da_dev_jaccard_sets_long: as da_dev_jaccard_sets with uint16 counts, max_len - k + 1 <= 1024 and ld_keys in
+ * da_jaccard_sets_long_ld(max_len, k) (the largest shingle count rounded up to a multiple of 4, at least 4) .. 1024.  One workgroup per
+ * sequence sorts its keys in LDS.  da_dev_jaccard_rect_long: as da_dev_jaccard_rect with kind DA_OUT_PACK32 (uint32 codes, 16-byte stores
+ * where the address allows) or DA_OUT_F64; a rectangle whose rows and columns are the same range is computed by the symmetric form. */
+int da_similarity_jaccard_long(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double *out);
+int da_similarity_jaccard_cross_long(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                     const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, int k, double *out, int column_major);
+int da_similarity_jaccard_cross_topk_long(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                          const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, int k, int top, int32_t *idx_out,
+                                          double *val_out);
+int da_similarity_jaccard_knn_long(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int top, int32_t *idx_out, double *val_out);
+int da_similarity_jaccard_edges_long_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, double thresh_p,
+                                           da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+int da_similarity_jaccard_cross_edges_long_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                                 const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, int k, double thresh,
+                                                 int thresh_is_quantile, da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+int da_similarity_jaccard_stats_long(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, da_similarity_stats *out);
+int64_t da_jaccard_sets_long_ld(int64_t max_len, int k);
+int da_dev_jaccard_sets_long(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t max_len, int k, void *d_keys,
+                             int64_t ld_keys, uint16_t *d_counts, void *stream);
+int da_dev_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin,
+                             int64_t row_end, int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, void *stream);
 
 /* The device piece.  The block: `rows` rows of ld >= n keys, rows [row_begin, row_begin + rows) x columns [col_begin, col_begin + n) of a
  * square problem (the origin convention of da_dev_rank_histogram).  d_records[r], for the elements of row r whose global column is
