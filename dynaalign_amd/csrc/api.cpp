@@ -3483,6 +3483,184 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
                           }, threshold_out, n_edges_out);
 }
 
+// ---- MinHash LSH banding (lsh_kernels.hip) ---------------------------------------------------------------------------------------------
+}  // extern "C"  (reopened below)
+namespace {
+struct LshRoute { int64_t buckets = 0, incidences = 0, verified = 0, edges = 0; };
+// Declared AFTER the DevBufs of a scope that launches on a caller's stream: whichever way the scope is left -- an early return after a launch
+// included -- the stream is drained before those buffers go back to the cache.
+struct StreamDrain {
+  hipStream_t stream;
+  ~StreamDrain() { (void)hipStreamSynchronize(stream); }
+};
+LshRoute &lsh_route() { static thread_local LshRoute r; return r; }
+
+// bands, rows, threshold and the cap of the LSH calls, in the order include/dynaalign.h gives
+int lsh_arg_check(int n_hash, int bands, int rows, double threshold, int64_t max_candidates) {
+  if (bands < 1) return fail(DA_ERR_BAD_ARG, "bands must be >= 1 (got %d)", bands);
+  if (rows < 1) return fail(DA_ERR_BAD_ARG, "rows must be >= 1 (got %d)", rows);
+  if ((int64_t)bands * rows > n_hash) return fail(DA_ERR_BAD_ARG, "bands * rows = %lld exceeds n_hash = %d", (long long)bands * rows, n_hash);
+  if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(DA_ERR_BAD_ARG, "the threshold must be in [0, 1]");
+  if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
+  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the LSH edge list counts in 16 bits: n_hash <= 65535 (got %d)", n_hash);
+  return DA_OK;
+}
+// the smallest count whose similarity -- the divide of mh_code_values -- reaches the threshold (n_hash + 1: none does)
+uint32_t lsh_c_min(int n_hash, double threshold) {
+  const std::vector<double> values = mh_code_values(n_hash);
+  uint32_t c = 0;
+  while (c <= (uint32_t)n_hash && !(values[c] >= threshold)) ++c;
+  return c;
+}
+// The pipeline on resident signatures.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.
+int lsh_edges_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
+                     void *d_work, size_t work_bytes, DevBuf &key, DevBuf &val, int64_t *edges_out, hipStream_t stream) {
+  if (n > 0x7ffffff0LL || n * (int64_t)bands > LSH_MAX_ELEMENTS)
+    return fail(DA_ERR_UNSUPPORTED, "lsh: n * bands = %lld (sequence, band) elements, at most %lld in one call", (long long)(n * (int64_t)bands),
+                (long long)LSH_MAX_ELEMENTS);
+  int rc;
+  DevBuf cnt, keep, ckept, coff, distinct, temp, key_in, val_in;
+  const StreamDrain drain{stream};
+  const uint64_t *d_keys;
+  const int32_t *d_ids;
+  const int64_t *d_off;
+  uint32_t stats[2] = {0, 0};
+  int64_t inc = 0;
+  if ((rc = lsh_buckets(d_sig, n, ld_sig, bands, rows, d_work, work_bytes, &d_keys, &d_ids, &d_off, stats, &inc, stream)) != DA_OK) return rc;
+  LshRoute &route = lsh_route();
+  route = LshRoute();
+  route.buckets = stats[1];
+  route.incidences = inc;
+  if (inc > max_candidates)
+    return fail(DA_ERR_UNSUPPORTED, "lsh: %lld (pair, band) candidates exceed max_candidates = %lld (largest bucket: %u sequences); use more rows per band",
+                (long long)inc, (long long)max_candidates, stats[0]);
+  const int64_t chunks = ceil_div(inc, 64);
+  if (chunks + 1 > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld candidates are more than one call verifies", (long long)inc);
+  const size_t scan_b = lsh_chunk_scan_bytes(inc);
+  if ((rc = cnt.alloc((size_t)inc * 2)) != DA_OK || (rc = keep.alloc((size_t)inc)) != DA_OK || (rc = ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
+      (rc = coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = distinct.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
+  if ((rc = launch_lsh_verify_enumerated(d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_off, d_ids, d_keys, inc, cnt.as<uint16_t>(),
+                                         keep.as<uint8_t>(), ckept.as<int64_t>(), coff.as<int64_t>(), distinct.as<uint64_t>(), temp.p, scan_b, stream)) != DA_OK)
+    return rc;
+  int64_t kept = 0;
+  uint64_t firsts = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&kept, coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(&firsts, distinct.p, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  const int64_t edges = n + kept;
+  if (edges > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld edges are more than one call sorts", (long long)edges);
+  const size_t sort_b = lsh_edge_sort_bytes(edges);
+  temp.release();
+  if ((rc = key_in.alloc((size_t)edges * 8)) != DA_OK || (rc = val_in.alloc((size_t)edges * 2)) != DA_OK || (rc = key.alloc((size_t)edges * 8)) != DA_OK ||
+      (rc = val.alloc((size_t)edges * 2)) != DA_OK || (rc = temp.alloc(sort_b)) != DA_OK) return rc;
+  if ((rc = launch_lsh_emit_sort(n, n_hash, bands, d_off, d_ids, d_keys, inc, cnt.as<uint16_t>(), keep.as<uint8_t>(), coff.as<int64_t>(), edges,
+                                 key_in.as<uint64_t>(), val_in.as<uint16_t>(), key.as<uint64_t>(), val.as<uint16_t>(), temp.p, sort_b, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  route.verified = (int64_t)firsts;
+  route.edges = edges;
+  *edges_out = edges;
+  return DA_OK;
+}
+int lsh_dev_check(const void *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold) {
+  if (n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (n_hash <= 0) return fail(DA_ERR_BAD_NHASH, "%s", da_status_message(DA_ERR_BAD_NHASH));
+  if (!d_sig) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld_sig < n_hash) return fail(DA_ERR_BAD_ARG, "ld_sig (%lld) < n_hash (%d)", (long long)ld_sig, n_hash);
+  return lsh_arg_check(n_hash, bands, rows, threshold, 0);
+}
+}  // namespace
+extern "C" {
+
+size_t da_dev_lsh_workspace_bytes(int64_t n, int bands) { return lsh_workspace_bytes(n, bands); }
+
+int da_dev_lsh_band_keys(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint64_t *d_keys, int32_t *d_ids,
+                         void *stream) {
+  int rc;
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, 0.0)) != DA_OK) return rc;
+  if (n > 0 && (!d_keys || !d_ids)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_lsh_band_keys(d_sig, n, ld_sig, bands, rows, d_keys, d_ids, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_verify_pairs(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, const int32_t *d_i,
+                            const int32_t *d_j, const int32_t *d_band, int64_t n_triples, uint16_t *d_count, uint8_t *d_keep, void *stream) {
+  int rc;
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, threshold)) != DA_OK) return rc;
+  if (n_triples < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (n_triples > 0 && (!d_i || !d_j || !d_band || !d_count || !d_keep)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_lsh_verify_listed(d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_i, d_j, d_band, n_triples, d_count, d_keep,
+                                  static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
+                     void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_count, int64_t capacity, int64_t *n_edges_out,
+                     void *stream_v) {
+  int rc;
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, threshold)) != DA_OK) return rc;
+  if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
+  if (!n_edges_out || !d_work) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (capacity < 0) return fail(DA_ERR_BAD_ARG, "negative capacity");
+  if (capacity > 0 && (!d_i || !d_j || !d_count)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  DevBuf key, val;
+  const StreamDrain drain{stream};
+  int64_t edges = 0;
+  if ((rc = lsh_edges_device(d_sig, n, ld_sig, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, key, val, &edges, stream)) != DA_OK) return rc;
+  if ((rc = launch_lsh_split(key.as<uint64_t>(), val.as<uint16_t>(), std::min(edges, capacity), d_i, d_j, d_count, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  *n_edges_out = edges;
+  return DA_OK;
+}
+
+int da_similarity_mh_lsh_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                                     int rows, double threshold, int64_t max_candidates, da_edges **handle_out, int64_t *n_edges_out) {
+  int rc = validate_mh(n, k, n_hash);
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !handle_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *handle_out = nullptr;
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, threshold, max_candidates)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf work, key, val;
+  const StreamDrain drain{nullptr};
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash, false)) != DA_OK || (rc = mh.signatures(k, 0, n_hash)) != DA_OK) return rc;
+  const size_t wb = lsh_workspace_bytes(n, bands);
+  if ((rc = work.alloc(wb)) != DA_OK) return rc;
+  int64_t edges = 0;
+  if ((rc = lsh_edges_device(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows, threshold, max_candidates, work.p, wb, key, val, &edges, nullptr)) != DA_OK)
+    return rc;
+  std::unique_ptr<da_edges> h(new da_edges);
+  std::vector<uint64_t> hk((size_t)edges);
+  std::vector<uint16_t> hv((size_t)edges);
+  DA_HIP_TRY(hipMemcpy(hk.data(), key.p, (size_t)edges * 8, hipMemcpyDeviceToHost));
+  DA_HIP_TRY(hipMemcpy(hv.data(), val.p, (size_t)edges * 2, hipMemcpyDeviceToHost));
+  const std::vector<double> values = mh_code_values(n_hash);
+  EdgeSet &es = h->es;
+  es.threshold = threshold;
+  es.i.resize((size_t)edges); es.j.resize((size_t)edges); es.w.resize((size_t)edges);
+  for (size_t e = 0; e < (size_t)edges; ++e) {
+    es.i[e] = (int32_t)(hk[e] >> 32);
+    es.j[e] = (int32_t)(hk[e] & 0xFFFFFFFFull);
+    es.w[e] = values[hv[e]];
+  }
+  h->n_edges = edges;
+  *n_edges_out = edges;
+  *handle_out = h.release();
+  return DA_OK;
+}
+
+int da_mh_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *edges_out) {
+  const LshRoute &r = lsh_route();
+  if (buckets_out) *buckets_out = r.buckets;
+  if (incidences_out) *incidences_out = r.incidences;
+  if (verified_pairs_out) *verified_pairs_out = r.verified;
+  if (edges_out) *edges_out = r.edges;
+  return DA_OK;
+}
+
 
 // ---- NW threshold form for sequences of up to 1024 residues: 32-bit keys (nw_edges_long_kernels.hip) ------------------------------------------
 // The value table of the PACK32 codes (matches << 16 | length) of sequences up to max_len residues: the distinct doubles

@@ -391,6 +391,26 @@ int launch_jaccard_sets_long(const uint8_t *d_res, const int64_t *d_off, int64_t
                              uint16_t *d_counts, hipStream_t stream);
 int launch_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
                              int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, hipStream_t stream);
+// lsh_kernels.hip: MinHash LSH banding (da_dev_lsh_*).  Elements are (sequence, band) pairs, n * bands <= LSH_MAX_ELEMENTS of them; an incidence is
+// a pair of elements of one bucket.  lsh_buckets() does the keys, the sort and the partner counts inside the workspace and reads back
+// {largest bucket, buckets} and the number of incidences; the caller then sizes the per-incidence buffers, verifies, sizes the edge buffers
+// (n + the last entry of the chunk offsets) and emits + sorts.
+constexpr int64_t LSH_MAX_ELEMENTS = 0x7fffff00LL;
+size_t lsh_workspace_bytes(int64_t n, int bands);
+int launch_lsh_band_keys(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, uint64_t *d_keys, int32_t *d_ids, hipStream_t stream);
+int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_work, size_t work_bytes, const uint64_t **d_keys_out,
+                const int32_t **d_ids_out, const int64_t **d_off_out, uint32_t stats_host[2], int64_t *incidences_host, hipStream_t stream);
+int launch_lsh_verify_listed(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int32_t *d_i,
+                             const int32_t *d_j, const int32_t *d_band, int64_t triples, uint16_t *d_count, uint8_t *d_keep, hipStream_t stream);
+size_t lsh_chunk_scan_bytes(int64_t incidences);
+int launch_lsh_verify_enumerated(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int64_t *d_off,
+                                 const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
+                                 int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes, hipStream_t stream);
+size_t lsh_edge_sort_bytes(int64_t edges);
+int launch_lsh_emit_sort(int64_t n, int n_hash, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
+                         const uint16_t *d_count, const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in,
+                         uint64_t *d_key_out, uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
+int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count, int32_t *d_i, int32_t *d_j, uint16_t *d_count, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

@@ -1,0 +1,396 @@
+// lsh_kernels.hip -- MinHash LSH banding: the threshold graph of one set without the n x n compare.  The n_hash columns of a signature are
+// cut into `bands` bands of `rows` columns; two sequences are a CANDIDATE when some band agrees in all its columns, and only candidates are
+// compared.  The result is exact with respect to that definition (lsh_edges_dense in similarity.py): a bucket key is a hash, but a pair
+// becomes an edge only after the band's columns were compared themselves.
+//
+//   1. k_lsh_band_keys: element q = i * bands + t  ->  key = band t in the top 16 bits | 48 bits of a hash of the band's values, id = i;
+//   2. one stable hipcub radix sort of (key, id): a bucket is a run of equal keys, never spans two bands, and holds its ids ascending, so
+//      every enumerated pair already has i < j.  k_lsh_run_heads / an inclusive sum / k_lsh_run_starts / k_lsh_partner_counts give each
+//      element p of a run ending at e its e - 1 - p partners; their exclusive sum numbers the (pair, band) INCIDENCES, and its total is known
+//      -- and checked against the caller's cap -- before any pair is touched;
+//   3. k_lsh_verify, the hot kernel: a wave takes 64 consecutive incidence slots, every lane finds its slot's (i, j, band) (a binary search
+//      of the exclusive sum: balanced whatever the bucket sizes are), then the wave decides the 64 pairs one after the other with
+//      lsh_pair_decide -- both signature rows read coalesced, equal columns counted by ballot / popcount.  A pair survives in the FIRST band
+//      in which it agrees only (exact deduplication without a sort of candidates) and when its count reaches c_min.  Per chunk of 64 slots
+//      the kept count; their scan; k_lsh_emit writes i << 32 | j and the count into final slots -- no output atomic;
+//   4. one radix sort of the 64-bit keys (count as payload) puts the list, diagonal included, in (i, j) order; k_lsh_split unpacks it.
+// The same verify kernel runs on LISTED triples (da_dev_lsh_verify_pairs), so that the per-pair decision can be tested on triples the
+// pipeline never produces (a key collision, a pair of an earlier band).
+#include "da_common.hpp"
+
+#include <algorithm>
+
+#include <hipcub/hipcub.hpp>
+
+namespace da {
+namespace {
+
+constexpr int LSH_THREADS = 256;
+constexpr int LSH_BAND_SHIFT = 48;            // key = band << 48 | hash >> 16
+
+inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+inline unsigned lsh_grid(int64_t items) { return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(items, LSH_THREADS), 1), 256 * 32); }
+
+// the finaliser of splitmix64: every input bit reaches every output bit
+__device__ __forceinline__ uint64_t lsh_mix(uint64_t x) {
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+// Consecutive threads take consecutive bands of one row: a wave reads one stretch of the row and writes one stretch of keys / ids.
+// Only columns < bands * rows are read.
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_band_keys(const uint32_t *__restrict__ sig, int64_t ld_sig, int64_t total, int bands, int rows,
+                                                               unsigned long long *__restrict__ keys, int32_t *__restrict__ ids) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
+    const int64_t i = q / bands;
+    const int t = (int)(q - i * bands);
+    const uint32_t *v = sig + i * ld_sig + (int64_t)t * rows;
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    for (int c = 0; c < rows; ++c) h = lsh_mix(h + v[c]) + 0x9E3779B97F4A7C15ull;
+    keys[q] = ((unsigned long long)t << LSH_BAND_SHIFT) | (h >> (64 - LSH_BAND_SHIFT));
+    ids[q] = (int32_t)i;
+  }
+}
+
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_run_heads(const unsigned long long *__restrict__ keys, int64_t total, uint32_t *__restrict__ head) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride) head[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1u : 0u;
+}
+
+// run_no[p] = the inclusive sum of head[]: the 1-based number of p's run.  start[r] = first element of run r (0-based), start[runs] = total.
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_run_starts(const uint32_t *__restrict__ head, const uint32_t *__restrict__ run_no, int64_t total,
+                                                                uint32_t *__restrict__ start) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += stride) {
+    if (head[p]) start[run_no[p] - 1] = (uint32_t)p;
+    if (p == total - 1) start[run_no[p]] = (uint32_t)total;
+  }
+}
+
+// cnt[p] = e - 1 - p for the run [.., e) of p; cnt[total] = 0 (so that the exclusive sum ends with the total).
+// stats[0] = the largest run (a maximum, taken per wave first), stats[1] = the number of runs.
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_partner_counts(const uint32_t *__restrict__ run_no, const uint32_t *__restrict__ start, int64_t total,
+                                                                    long long *__restrict__ cnt, uint32_t *__restrict__ stats) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  uint32_t longest = 0;
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= total; p += stride) {
+    if (p == total) { cnt[p] = 0; continue; }
+    const uint32_t r = run_no[p], e = start[r];
+    cnt[p] = (long long)e - 1 - p;
+    longest = max(longest, e - start[r - 1]);
+    if (p == total - 1) stats[1] = r;
+  }
+  for (int o = 32; o > 0; o >>= 1) longest = max(longest, (uint32_t)__shfl_down(longest, o));
+  if ((threadIdx.x & 63) == 0 && longest) atomicMax(&stats[0], longest);
+}
+
+// ---- the per-pair decision --------------------------------------------------------------------------------------------------------------
+struct LshVerdict {
+  uint32_t count;   // columns h < n_hash with ri[h] == rj[h]
+  bool first;       // `band` agrees in all its columns and no earlier band does
+};
+// Called by a whole wave with wave-uniform arguments; lane l holds column h0 + l of a chunk of 64.  band_cols = bands * rows: the columns
+// behind belong to no band but count.  A band agrees when the run of equal columns ending at its last column is at least `rows` long; the
+// run is measured inside the chunk from the ballot of mismatches and continued into the chunks before by `tail`, the number of equal
+// columns they end with.  Only the first agreeing band is looked for: the candidate (i, j, band) is that pair's own when it is `band`.
+__device__ __forceinline__ LshVerdict lsh_pair_decide(const uint32_t *__restrict__ ri, const uint32_t *__restrict__ rj, int n_hash, int band_cols, int rows,
+                                                      int band) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long upto = (2ull << lane) - 1;   // my column and those below it in the chunk
+  const int step = 64 % rows;
+  int pos = lane % rows;                                // position of my column in its band
+  int tail = 0, first_end = -1;
+  uint32_t count = 0;
+  for (int h0 = 0; h0 < n_hash; h0 += 64) {
+    const int h = h0 + lane;
+    const bool eq = h < n_hash && ri[h] == rj[h];
+    const unsigned long long equal = __ballot(eq);
+    count += (uint32_t)__popcll(equal);
+    if (first_end < 0 && h0 < band_cols) {
+      const unsigned long long below = ~equal & upto;
+      const int run = below ? lane - 63 + __clzll((long long)below) : lane + 1 + tail;
+      const unsigned long long agree = __ballot(pos == rows - 1 && h < band_cols && run >= rows);
+      if (agree) first_end = h0 + __ffsll((long long)agree) - 1;
+    }
+    tail = ~equal ? __clzll((long long)~equal) : tail + 64;
+    pos += step;
+    if (pos >= rows) pos -= rows;
+  }
+  LshVerdict v;
+  v.count = count;
+  v.first = first_end == band * rows + rows - 1;
+  return v;
+}
+
+// ---- where the triples of the verify kernel come from: lane-level get(slot) ----------------------------------------------------------------
+struct LshListed {
+  const int32_t *__restrict__ i, *__restrict__ j, *__restrict__ band;
+  __device__ __forceinline__ void get(int64_t s, int &pi, int &pj, int &pt) const { pi = i[s]; pj = j[s]; pt = band[s]; }
+};
+// slot s of the exclusive sum off[0 .. total] of the partner counts: the element p with off[p] <= s < off[p + 1] and its partner p + 1 + (s - off[p])
+struct LshEnumerated {
+  const long long *__restrict__ off;
+  const int32_t *__restrict__ ids;
+  const unsigned long long *__restrict__ keys;
+  int64_t total;
+  __device__ __forceinline__ void get(int64_t s, int &pi, int &pj, int &pt) const {
+    int64_t lo = 0, hi = total;                          // the last p with off[p] <= s (s < off[total], so p < total)
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= s) lo = mid; else hi = mid - 1;
+    }
+    pi = ids[lo];
+    pj = ids[lo + 1 + (s - off[lo])];
+    pt = (int)(keys[lo] >> LSH_BAND_SHIFT);
+  }
+};
+
+// out_count[s] = the pair's count, out_keep[s] = 1 when the triple survives.  A triple with an index outside [0, n) or a band outside
+// [0, bands) reads nothing and gets 0 / 0.  chunk_kept[c] (if given) = kept triples of slots [64 c, 64 c + 64); *distinct (if given) += the
+// triples that are their pair's first agreeing band, whatever their count.
+template <typename Src>
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_verify(const uint32_t *__restrict__ sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows,
+                                                            uint32_t c_min, Src src, int64_t slots, uint16_t *__restrict__ out_count,
+                                                            uint8_t *__restrict__ out_keep, long long *__restrict__ chunk_kept,
+                                                            unsigned long long *__restrict__ distinct) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
+  unsigned long long firsts = 0;
+  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
+    const int64_t s = c * 64 + lane;
+    int i = 0, j = 0, t = 0;
+    bool valid = false;
+    if (s < slots) {
+      src.get(s, i, j, t);
+      valid = i >= 0 && i < n && j >= 0 && j < n && t >= 0 && t < bands;
+    }
+    unsigned long long todo = __ballot(valid);
+    uint32_t my_count = 0;
+    bool my_first = false;
+    while (todo) {
+      const int b = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int bi = __shfl(i, b), bj = __shfl(j, b), bt = __shfl(t, b);
+      const LshVerdict v = lsh_pair_decide(sig + (int64_t)bi * ld_sig, sig + (int64_t)bj * ld_sig, n_hash, bands * rows, rows, bt);
+      if (lane == b) { my_count = v.count; my_first = v.first; }
+    }
+    const bool keep = my_first && my_count >= c_min;
+    if (s < slots) { out_count[s] = (uint16_t)my_count; out_keep[s] = keep ? 1 : 0; }
+    const unsigned long long kept = __ballot(keep);
+    if (chunk_kept && lane == 0) chunk_kept[c] = __popcll(kept);
+    firsts += (unsigned long long)__popcll(__ballot(my_first));
+  }
+  if (distinct && lane == 0 && firsts) atomicAdd(distinct, firsts);
+}
+
+// the kept slots of chunk c, in slot order, at edge slots base + chunk_off[c] ...: key = i << 32 | j, value = the count
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_emit(LshEnumerated src, int64_t slots, const uint16_t *__restrict__ count, const uint8_t *__restrict__ keep,
+                                                          const long long *__restrict__ chunk_off, int64_t base, unsigned long long *__restrict__ out_key,
+                                                          uint16_t *__restrict__ out_val) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
+  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
+    const int64_t s = c * 64 + lane;
+    const bool kp = s < slots && keep[s] != 0;
+    const unsigned long long kept = __ballot(kp);
+    if (!kp) continue;
+    int i, j, t;
+    src.get(s, i, j, t);
+    const int64_t slot = base + chunk_off[c] + __popcll(kept & ((1ull << lane) - 1));
+    out_key[slot] = ((unsigned long long)(uint32_t)i << 32) | (uint32_t)j;
+    out_val[slot] = count[s];
+  }
+}
+
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_diagonal(int64_t n, int n_hash, unsigned long long *__restrict__ out_key, uint16_t *__restrict__ out_val) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    out_key[i] = ((unsigned long long)i << 32) | (unsigned long long)i;
+    out_val[i] = (uint16_t)n_hash;
+  }
+}
+
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_split(const unsigned long long *__restrict__ key, const uint16_t *__restrict__ val, int64_t count,
+                                                           int32_t *__restrict__ out_i, int32_t *__restrict__ out_j, uint16_t *__restrict__ out_count) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += stride) {
+    out_i[e] = (int32_t)(key[e] >> 32);
+    out_j[e] = (int32_t)(key[e] & 0xFFFFFFFFull);
+    out_count[e] = val[e];
+  }
+}
+
+int bits_for(int64_t values) {   // bits that hold 0 .. values - 1
+  int b = 1;
+  while (b < 63 && ((int64_t)1 << b) < values) ++b;
+  return b;
+}
+
+size_t sort_u64_i32_bytes(int64_t items) {
+  size_t t = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const int32_t *)nullptr,
+                                           (int32_t *)nullptr, (int)items, 0, 64, nullptr);
+  return t;
+}
+size_t sort_u64_u16_bytes(int64_t items) {
+  size_t t = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint16_t *)nullptr,
+                                           (uint16_t *)nullptr, (int)items, 0, 64, nullptr);
+  return t;
+}
+size_t scan_u32_bytes(int64_t items) {
+  size_t t = 0;
+  (void)hipcub::DeviceScan::InclusiveSum(nullptr, t, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)items, nullptr);
+  return t;
+}
+size_t scan_i64_bytes(int64_t items) {
+  size_t t = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const long long *)nullptr, (long long *)nullptr, (int)items, nullptr);
+  return t;
+}
+
+// the bucket workspace of `total` = n * bands elements, cut into its arrays
+struct BucketLayout {
+  size_t keys_in, keys_out, ids_in, ids_out, start, cnt, off, stats, temp, temp_bytes, bytes;
+  explicit BucketLayout(int64_t total) {
+    const size_t t = (size_t)total;
+    size_t at = 0;
+    auto take = [&](size_t b) { const size_t o = at; at += up256(b); return o; };
+    keys_in = take(t * 8);        // after the sort: head[] and run_no[] (uint32 each)
+    keys_out = take(t * 8);
+    ids_in = take(t * 4);
+    ids_out = take(t * 4);
+    start = take((t + 1) * 4);
+    cnt = take((t + 1) * 8);
+    off = take((t + 1) * 8);
+    stats = take(16);
+    temp_bytes = std::max(std::max(sort_u64_i32_bytes(total), scan_u32_bytes(total)), scan_i64_bytes(total + 1));
+    temp = take(temp_bytes);
+    bytes = at + 256;
+  }
+};
+
+template <typename T> T *at_bytes(void *base, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
+
+}  // namespace
+
+int launch_lsh_band_keys(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, uint64_t *d_keys, int32_t *d_ids, hipStream_t stream) {
+  const int64_t total = n * bands;
+  if (total <= 0) return DA_OK;
+  hipLaunchKernelGGL(k_lsh_band_keys, dim3(lsh_grid(total)), dim3(LSH_THREADS), 0, stream, d_sig, ld_sig, total, bands, rows,
+                     reinterpret_cast<unsigned long long *>(d_keys), d_ids);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+size_t lsh_workspace_bytes(int64_t n, int bands) {
+  if (n <= 0 || bands <= 0 || n * (int64_t)bands > LSH_MAX_ELEMENTS) return 256;
+  return BucketLayout(n * bands).bytes;
+}
+
+// Steps 1 and 2 on the signatures: keys, the sort, the runs, the partner counts and their exclusive sum.  The three device pointers point
+// into the workspace; stats_host = {largest bucket, buckets}, *incidences_host the total; synchronises the stream once (the read-back).
+int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_work, size_t work_bytes, const uint64_t **d_keys_out,
+                const int32_t **d_ids_out, const int64_t **d_off_out, uint32_t stats_host[2], int64_t *incidences_host, hipStream_t stream) {
+  const int64_t total = n * bands;
+  const BucketLayout L(total);
+  if (!d_work || work_bytes < L.bytes) return fail(DA_ERR_BAD_ARG, "lsh: workspace too small (%zu bytes, %zu needed)", work_bytes, L.bytes);
+  // the arrays start on 256 bytes whatever the caller's pointer: the layout's 256 spare bytes are for this
+  d_work = static_cast<char *>(d_work) + ((256 - (reinterpret_cast<uintptr_t>(d_work) & 255)) & 255);
+  unsigned long long *keys_in = at_bytes<unsigned long long>(d_work, L.keys_in), *keys_out = at_bytes<unsigned long long>(d_work, L.keys_out);
+  int32_t *ids_in = at_bytes<int32_t>(d_work, L.ids_in), *ids_out = at_bytes<int32_t>(d_work, L.ids_out);
+  uint32_t *head = at_bytes<uint32_t>(d_work, L.keys_in), *run_no = head + total;
+  uint32_t *start = at_bytes<uint32_t>(d_work, L.start), *stats = at_bytes<uint32_t>(d_work, L.stats);
+  long long *cnt = at_bytes<long long>(d_work, L.cnt), *off = at_bytes<long long>(d_work, L.off);
+  void *temp = at_bytes<char>(d_work, L.temp);
+  int rc;
+  if ((rc = launch_lsh_band_keys(d_sig, n, ld_sig, bands, rows, reinterpret_cast<uint64_t *>(keys_in), ids_in, stream)) != DA_OK) return rc;
+  size_t tb = L.temp_bytes;
+  DA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp, tb, keys_in, keys_out, ids_in, ids_out, (int)total, 0, LSH_BAND_SHIFT + bits_for(bands), stream));
+  const unsigned grid = lsh_grid(total + 1);
+  hipLaunchKernelGGL(k_lsh_run_heads, dim3(grid), dim3(LSH_THREADS), 0, stream, keys_out, total, head);
+  DA_HIP_TRY(hipGetLastError());
+  tb = L.temp_bytes;
+  DA_HIP_TRY(hipcub::DeviceScan::InclusiveSum(temp, tb, head, run_no, (int)total, stream));
+  hipLaunchKernelGGL(k_lsh_run_starts, dim3(grid), dim3(LSH_THREADS), 0, stream, head, run_no, total, start);
+  DA_HIP_TRY(hipGetLastError());
+  DA_HIP_TRY(hipMemsetAsync(stats, 0, 16, stream));
+  hipLaunchKernelGGL(k_lsh_partner_counts, dim3(grid), dim3(LSH_THREADS), 0, stream, run_no, start, total, cnt, stats);
+  DA_HIP_TRY(hipGetLastError());
+  tb = L.temp_bytes;
+  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(temp, tb, cnt, off, (int)(total + 1), stream));
+  long long inc = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&inc, off + total, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(stats_host, stats, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  *incidences_host = (int64_t)inc;
+  *d_keys_out = reinterpret_cast<const uint64_t *>(keys_out);
+  *d_ids_out = ids_out;
+  *d_off_out = reinterpret_cast<const int64_t *>(off);
+  return DA_OK;
+}
+
+int launch_lsh_verify_listed(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int32_t *d_i,
+                             const int32_t *d_j, const int32_t *d_band, int64_t triples, uint16_t *d_count, uint8_t *d_keep, hipStream_t stream) {
+  if (triples <= 0) return DA_OK;
+  hipLaunchKernelGGL(k_lsh_verify<LshListed>, dim3(lsh_grid(ceil_div(triples, 64) * 64)), dim3(LSH_THREADS), 0, stream, d_sig, n, ld_sig, n_hash, bands, rows,
+                     c_min, LshListed{d_i, d_j, d_band}, triples, d_count, d_keep, (long long *)nullptr, (unsigned long long *)nullptr);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+// scratch of the scan over the chunk counts of `incidences` slots
+size_t lsh_chunk_scan_bytes(int64_t incidences) { return up256(scan_i64_bytes(ceil_div(incidences, 64) + 1)) + 256; }
+
+// Step 3 on the enumerated incidences: verdicts into d_count / d_keep (one per incidence), kept counts per chunk of 64 into d_chunk_kept
+// (chunks + 1 entries, the last one 0), their exclusive sum into d_chunk_off; *d_distinct (zeroed here) counts the distinct candidate pairs.
+int launch_lsh_verify_enumerated(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int64_t *d_off,
+                                 const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
+                                 int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  const int64_t chunks = ceil_div(incidences, 64);
+  DA_HIP_TRY(hipMemsetAsync(d_distinct, 0, 8, stream));
+  DA_HIP_TRY(hipMemsetAsync(d_chunk_kept + chunks, 0, 8, stream));
+  if (incidences > 0) {
+    const LshEnumerated src{reinterpret_cast<const long long *>(d_off), d_ids, reinterpret_cast<const unsigned long long *>(d_keys), n * bands};
+    hipLaunchKernelGGL(k_lsh_verify<LshEnumerated>, dim3(lsh_grid(chunks * 64)), dim3(LSH_THREADS), 0, stream, d_sig, n, ld_sig, n_hash, bands, rows, c_min,
+                       src, incidences, d_count, d_keep, reinterpret_cast<long long *>(d_chunk_kept), reinterpret_cast<unsigned long long *>(d_distinct));
+    DA_HIP_TRY(hipGetLastError());
+  }
+  size_t tb = temp_bytes;
+  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_chunk_kept), reinterpret_cast<long long *>(d_chunk_off),
+                                              (int)(chunks + 1), stream));
+  return DA_OK;
+}
+
+size_t lsh_edge_sort_bytes(int64_t edges) { return up256(sort_u64_u16_bytes(edges)) + 256; }
+
+// Step 3's emit and step 4: the n diagonal entries and the kept incidences into d_key_in / d_val_in (edges = n + kept entries), sorted by
+// (i, j) into d_key_out / d_val_out.
+int launch_lsh_emit_sort(int64_t n, int n_hash, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
+                         const uint16_t *d_count, const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in,
+                         uint64_t *d_key_out, uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  unsigned long long *kin = reinterpret_cast<unsigned long long *>(d_key_in), *kout = reinterpret_cast<unsigned long long *>(d_key_out);
+  hipLaunchKernelGGL(k_lsh_diagonal, dim3(lsh_grid(n)), dim3(LSH_THREADS), 0, stream, n, n_hash, kin, d_val_in);
+  DA_HIP_TRY(hipGetLastError());
+  if (incidences > 0 && edges > n) {
+    const LshEnumerated src{reinterpret_cast<const long long *>(d_off), d_ids, reinterpret_cast<const unsigned long long *>(d_keys), n * bands};
+    hipLaunchKernelGGL(k_lsh_emit, dim3(lsh_grid(ceil_div(incidences, 64) * 64)), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep,
+                       reinterpret_cast<const long long *>(d_chunk_off), n, kin, d_val_in);
+    DA_HIP_TRY(hipGetLastError());
+  }
+  size_t tb = temp_bytes;
+  DA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, kin, kout, d_val_in, d_val_out, (int)edges, 0, 32 + bits_for(n), stream));
+  return DA_OK;
+}
+
+int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count, int32_t *d_i, int32_t *d_j, uint16_t *d_count, hipStream_t stream) {
+  if (count <= 0) return DA_OK;
+  hipLaunchKernelGGL(k_lsh_split, dim3(lsh_grid(count)), dim3(LSH_THREADS), 0, stream, reinterpret_cast<const unsigned long long *>(d_key), d_val, count,
+                     d_i, d_j, d_count);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+}  // namespace da

@@ -804,6 +804,79 @@ def similarity_mh_cross_edges(dx, dy, k, n_hash, seeds, thresh_p=None, threshold
     return thr.value, rowptr, j[:stored], w[:stored]
 
 
+def _sig_block(sig, n_hash):
+    _require_cuda(sig, "signatures")
+    if sig.dim() != 2 or sig.element_size() != 4 or sig.stride(1) != 1 or sig.shape[1] < int(n_hash):
+        raise ValueError("signatures must be a 2-d tensor of 32-bit words with unit column stride and at least n_hash columns")
+    return sig.shape[0], sig.stride(0)
+
+
+def lsh_workspace_bytes(n, bands):
+    return int(_capi.load().da_dev_lsh_workspace_bytes(int(n), int(bands)))
+
+
+def lsh_band_keys(sig, n_hash, bands, rows):
+    """The bucket keys of LSH banding (da_dev_lsh_band_keys): ``sig`` (n, >= n_hash) 32-bit -> (keys int64 (n, bands), ids int32 (n, bands)):
+    keys[i, t] = t << 48 | 48 bits of a hash of sig[i, t * rows:(t + 1) * rows], ids[i, t] = i.  Reads columns < bands * rows only."""
+    lib = _capi.load()
+    n, ld = _sig_block(sig, n_hash)
+    keys = torch.empty((n, max(int(bands), 1)), dtype=torch.int64, device=sig.device)
+    ids = torch.empty((n, max(int(bands), 1)), dtype=torch.int32, device=sig.device)
+    _call(lib.da_dev_lsh_band_keys, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), keys.data_ptr(), ids.data_ptr(), _stream())
+    return keys, ids
+
+
+def lsh_verify_pairs(sig, n_hash, bands, rows, threshold, i, j, band):
+    """The per-pair decision of the LSH pipeline on listed triples (da_dev_lsh_verify_pairs) -> (count int16-as-uint16 tensor, keep uint8):
+    count = equal columns of rows i and j; keep = 1 when ``band`` agrees in all its columns, no earlier band does and
+    count / n_hash >= threshold."""
+    lib = _capi.load()
+    n, ld = _sig_block(sig, n_hash)
+    ti, tj, tb = ((a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, np.int32))).to(device=sig.device, dtype=torch.int32).contiguous()
+                  for a in (i, j, band))
+    if not ti.numel() == tj.numel() == tb.numel():
+        raise ValueError("i, j and band must have the same number of entries")
+    m = int(ti.numel())
+    count = torch.zeros(max(m, 1), dtype=torch.int16, device=sig.device)
+    keep = torch.zeros(max(m, 1), dtype=torch.uint8, device=sig.device)
+    _call(lib.da_dev_lsh_verify_pairs, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), ti.data_ptr(), tj.data_ptr(),
+          tb.data_ptr(), m, count.data_ptr(), keep.data_ptr(), _stream())
+    return count[:m], keep[:m]
+
+
+def lsh_edges(sig, n_hash, bands, rows, threshold, max_candidates=1 << 32, capacity=None, work=None):
+    """The LSH threshold graph of resident signatures (da_dev_lsh_edges) -> (i int32, j int32, count int16-as-uint16), sorted by (i, j),
+    diagonal included (count n_hash); weight = count / n_hash.  ``capacity=None``: a first call counts, a second one fills; an int: one
+    call, and at most that many edges are returned (``mh_lsh_last_route()["edges"]`` has the full number).  Synchronises the stream."""
+    lib = _capi.load()
+    n, ld = _sig_block(sig, n_hash)
+    if work is None:
+        work = torch.empty(lsh_workspace_bytes(n, bands), dtype=torch.uint8, device=sig.device)
+    _require_cuda(work, "work")
+    if work.dtype != torch.uint8 or not work.is_contiguous():
+        raise ValueError("work must be a contiguous uint8 tensor of lsh_workspace_bytes(n, bands) bytes")
+    m = ctypes.c_int64(0)
+
+    def run(cap, ti, tj, tc):
+        _call(lib.da_dev_lsh_edges, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), int(max_candidates),
+              work.data_ptr(), work.numel(), ti, tj, tc, cap, ctypes.byref(m), _stream())
+    if capacity is None:
+        run(0, None, None, None)
+        capacity = m.value
+    capacity = int(capacity)
+    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig.device)
+    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig.device)
+    ec = torch.empty(max(capacity, 1), dtype=torch.int16, device=sig.device)
+    run(capacity, ei.data_ptr(), ej.data_ptr(), ec.data_ptr())
+    got = min(m.value, capacity)
+    return ei[:got], ej[:got], ec[:got]
+
+
+def mh_lsh_last_route():
+    from .similarity import mh_lsh_last_route as route
+    return route()
+
+
 def mh_cross_last_route():
     """what this thread's last similarity_mh_cross call did: dict(m, n, unique_x, unique_y, dedup, plane_bits, plan_ms, codes_ms,
     k2_ms, lists_ms, expand_ms)"""

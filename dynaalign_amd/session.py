@@ -13,6 +13,7 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     thr, ptr, j, w = s.cross_edges(new, 0.99, idx=idx)              # == similarityMH_cross_edges(new, sequences[idx], 4, 500, 0.99, seed=12345) as CSR
     i, v = s.knn(10, idx)                                           # == similarityMH_knn(sequences[idx], 4, 500, 10, seed=12345)
     thr, m, ptr, adj, codes, loops, values = s.knn_csr(idx, 10)     # the kNN graph of those lists as CSR (== similarityMH_knn_edges(...))
+    thr, i, j, w = s.lsh_edges(12, 4, 0.5, idx)                     # == similarityMH_lsh_edges(sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) at n_hash = 48
     st = s.stats(idx)                                               # == similarityMH_stats(sequences[idx], 4, 500, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
@@ -263,6 +264,14 @@ class MinHashSession:
             return thr, ei, ej, values[ev]
         order = np.lexsort((ej, ei))
         return thr, ei[order], ej[order], values[ev[order]]
+
+    def lsh_edges(self, bands, rows, threshold, idx=None, max_candidates=1 << 32):
+        """``(threshold, i, j, w)`` == similarityMH_lsh_edges(sequences[idx], k, n_hash, bands, rows, threshold, seed=session.seed), from the
+        resident signatures: bucketing, candidate verification and the (i, j) sort on the device, only the edge list crosses to the host."""
+        sig, m = self._subset(idx)
+        ei, ej, ec = device.lsh_edges(sig[:m], self.n_hash, bands, rows, threshold, max_candidates=max_candidates)
+        c = ec.cpu().numpy().view(np.uint16).astype(np.float64)
+        return float(threshold), ei.cpu().numpy(), ej.cpu().numpy(), c / np.float64(self.n_hash)
 
     def stats(self, idx=None):
         """compute_similarity_stats of the subset's similarity matrix without that matrix on the host (``SimilarityStats``, positions in

@@ -876,6 +876,79 @@ def similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, *, threshold=No
         xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data, thresh, is_q, h, thr, cnt))
 
 
+def similarityMH_lsh_edges(sequences, k=4, n_hash=50, bands=10, rows=5, threshold=0.5, *, seed=None, max_candidates=1 << 32):
+    """The threshold graph of one set from LSH candidates instead of all n (n - 1) / 2 pairs: ``(threshold, i, j, weight)``, 0-based, sorted
+    by (i, j), the contract ``clusterbreak(edges_fn=)`` takes.  The signatures are cut into ``bands`` bands of ``rows`` hash functions
+    (``bands * rows <= n_hash``; the columns behind belong to no band but count); two sequences are compared when some band agrees in all
+    its columns.  The result is exactly ``lsh_edges_dense(minhash_signatures(sequences, k, n_hash, seed=seed), bands, rows, threshold)``:
+    the diagonal at 1.0 and every candidate pair i < j with ``c / n_hash >= threshold`` (c = equal columns, the divide of similarityMH).
+    What is approximate is that definition's relation to ``similarityMH_cross_edges(x, x, threshold=threshold)``: a pair above the
+    threshold that agrees in no whole band is missing (``lsh_collision_probability`` says how likely).  ``max_candidates`` caps the
+    (pair, band) incidences, which are known before any pair is compared: more raises DA_ERR_UNSUPPORTED."""
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    import ctypes
+    handle = ctypes.c_void_p()
+    cnt = np.zeros(1, np.int64)
+    _capi.check(lib.da_similarity_mh_lsh_edges_begin(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, _as_int(bands, "bands"),
+                                                     _as_int(rows, "rows"), float(threshold), int(max_candidates), ctypes.addressof(handle),
+                                                     cnt.ctypes.data))
+    try:
+        m = int(cnt[0])
+        ei, ej, ew = np.empty(max(m, 1), np.int32), np.empty(max(m, 1), np.int32), np.empty(max(m, 1), np.float64)
+        _capi.check(lib.da_edges_fetch(handle, m, ei.ctypes.data, ej.ctypes.data, ew.ctypes.data))
+    finally:
+        lib.da_edges_free(handle)
+    return float(threshold), ei[:m], ej[:m], ew[:m]
+
+
+def mh_lsh_last_route():
+    """What this thread's last LSH call did: buckets, (pair, band) incidences, distinct candidate pairs, edges (diagonal included)."""
+    v = np.zeros(4, np.int64)
+    _capi.check(_capi.load().da_mh_lsh_last_route(*[v[i:].ctypes.data for i in range(4)]))
+    return dict(zip(("buckets", "incidences", "verified_pairs", "edges"), (int(x) for x in v)))
+
+
+def lsh_edges_dense(sig, bands, rows, threshold):
+    """The definition ``similarityMH_lsh_edges`` is exact against, in numpy (host code, the role of ``knn_dense`` / ``jaccard_dense``):
+    ``sig`` is the (n, n_hash) uint32 signature matrix; -> ``(i, j, w)`` sorted by (i, j): (i, i, 1.0) for every i and (i, j, c / n_hash)
+    for i < j that agree in all ``rows`` columns of some band and have ``c / n_hash >= threshold``."""
+    sig = np.ascontiguousarray(sig, np.uint32)
+    n, n_hash = sig.shape
+    bands, rows = int(bands), int(rows)
+    if bands < 1 or rows < 1 or bands * rows > n_hash:
+        raise ValueError("need bands >= 1, rows >= 1 and bands * rows <= n_hash")
+    pairs = [np.stack([np.arange(n, dtype=np.int64)] * 2, 1)]
+    for t in range(bands):
+        band = np.ascontiguousarray(sig[:, t * rows:(t + 1) * rows])
+        _, inv = np.unique(band.view(np.dtype((np.void, 4 * rows))).ravel(), return_inverse=True)
+        inv = inv.ravel()
+        order = np.argsort(inv, kind="stable")
+        ends = np.flatnonzero(np.r_[inv[order][1:] != inv[order][:-1], True]) + 1
+        begin = 0
+        for end in ends:
+            if end - begin > 1:
+                g = order[begin:end]
+                a, b = np.triu_indices(len(g), 1)
+                pairs.append(np.stack([g[a], g[b]], 1))
+            begin = end
+    p = np.unique(np.concatenate(pairs), axis=0)            # sorted by (i, j), each candidate once
+    c = np.empty(len(p), np.int64)
+    for b0 in range(0, len(p), 1 << 16):
+        q = p[b0:b0 + (1 << 16)]
+        c[b0:b0 + len(q)] = (sig[q[:, 0]] == sig[q[:, 1]]).sum(1)
+    w = c.astype(np.float64) / np.float64(n_hash)
+    keep = (p[:, 0] == p[:, 1]) | (w >= float(threshold))
+    return p[keep, 0].astype(np.int32), p[keep, 1].astype(np.int32), w[keep]
+
+
+def lsh_collision_probability(s, bands, rows):
+    """P(two sequences of MinHash similarity ``s`` agree in at least one of ``bands`` bands of ``rows`` hash functions)
+    = 1 - (1 - s^rows)^bands: the S-curve to choose bands and rows by."""
+    s = np.asarray(s, np.float64)
+    p = 1.0 - (1.0 - s ** int(rows)) ** int(bands)
+    return float(p) if p.ndim == 0 else p
+
+
 def similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, *, threshold=None):
     """The entries of R = similarityNW_cross(x, y, ...) (x[i] is sequence1) that pass a threshold: ``(threshold, i, j, weight)`` as
     similarityMH_cross_edges.  Equal similarities pass or fail together whatever their (matches, length): 2/4 and 3/6 are both 0.5.

@@ -54,6 +54,7 @@ extern "C" {
  * (the exact-Jaccard entry points -- da_similarity_jaccard[_cross[_topk] | _knn | _edges[_begin]], da_dev_jaccard_sets[_ld], da_dev_jaccard_rect -- likewise)
  * (their _long forms -- da_similarity_jaccard[_cross[_topk | _edges] | _knn | _edges | _stats]_long[_begin], da_jaccard_sets_long_ld,
  *  da_dev_jaccard_sets_long, da_dev_jaccard_rect_long -- likewise)
+ * (the LSH entry points -- da_similarity_mh_lsh_edges_begin, da_mh_lsh_last_route, da_dev_lsh_[band_keys | verify_pairs | edges | workspace_bytes] -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1044,6 +1045,48 @@ int da_louvain_csr(int64_t n_vertices, const int64_t *ptr, const int32_t *adj, c
 size_t da_dev_edges_to_csr_bytes(int64_t n_edges, int64_t n);
 int da_dev_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_v, int64_t n_edges, int64_t n, void *d_work,
                         size_t work_bytes, int64_t *d_ptr, int32_t *d_adj, uint16_t *d_codes, uint16_t *d_loops, void *stream);
+
+/* ---- MinHash LSH banding: the threshold graph of ONE set from bucketed candidates, not from all n (n - 1) / 2 pairs ---------------------
+ * sig = the n x n_hash signatures of da_minhash_signatures.  bands >= 1, rows >= 1, bands * rows <= n_hash; band t = columns
+ * [t * rows, (t + 1) * rows); columns >= bands * rows belong to no band but count.  cand(i, j): some band agrees in all its columns.
+ * c(i, j) = |{h < n_hash : sig[i][h] == sig[j][h]}|.  The edge set, sorted by (i, j), 0-based:
+ *     (i, i, 1.0) for every i   and   (i, j, c / n_hash) for i < j with cand(i, j) and (double)c / (double)n_hash >= threshold
+ * -- EXACT with respect to this definition (a bucket key is a hash, but a pair is emitted only after the band's columns were compared
+ * themselves); approximate is only the definition's relation to the all-pairs threshold graph: a pair above the threshold that agrees in
+ * no whole band is missing.  P(cand) = 1 - (1 - s^rows)^bands for a pair of similarity s.
+ *
+ * da_similarity_mh_lsh_edges_begin: host boundary, result in a da_edges handle (da_edges_fetch / da_edges_free).  Checks, in this order
+ * and before any device is needed: n <= 0 (DA_ERR_EMPTY_INPUT), k, n_hash, NULL pointers, offsets, then DA_ERR_BAD_ARG for bands < 1,
+ * rows < 1, bands * rows > n_hash, a threshold outside [0, 1] or NaN, max_candidates < 0, then DA_ERR_UNSUPPORTED for n_hash > 65535.
+ * n = 1 is valid (the one diagonal edge).  max_candidates caps the (pair, band) incidences -- pairs of members of one bucket, summed over
+ * the buckets -- which are known before any pair is compared: more gives DA_ERR_UNSUPPORTED, the message naming the count, the cap and the
+ * largest bucket.
+ * da_mh_lsh_last_route: what the calling thread's last LSH call (host or da_dev_lsh_edges) did -- buckets, (pair, band) incidences,
+ * distinct candidate pairs (each verified in its first agreeing band) and edges (diagonal included).  NULL pointers are skipped. */
+int da_similarity_mh_lsh_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds,
+                                     int bands, int rows, double threshold, int64_t max_candidates, da_edges **handle_out,
+                                     int64_t *n_edges_out);
+int da_mh_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *edges_out);
+/* The device pieces, on signatures resident in HBM (row i at d_sig + i * ld_sig; columns >= n_hash are never read, and
+ * da_dev_lsh_band_keys reads columns < bands * rows only).  Asynchronous on `stream` unless stated.
+ * da_dev_lsh_band_keys: element q = i * bands + t  ->  d_keys[q] = t << 48 | 48 bits of a hash of band t's values of row i, d_ids[q] = i.
+ *   Equal band values give equal keys; different values give different keys but for hash collisions.
+ * da_dev_lsh_verify_pairs: the per-pair decision on LISTED triples (i, j, band), which need not be ones the pipeline would produce:
+ *   d_count[p] = c(i, j); d_keep[p] = 1 when `band` agrees in all its columns, no earlier band does, and
+ *   (double)c / (double)n_hash >= threshold -- else 0.  A triple with an index outside [0, n) or a band outside [0, bands) gets 0 / 0.
+ * da_dev_lsh_edges: the whole pipeline.  d_work: da_dev_lsh_workspace_bytes(n, bands) bytes, any alignment (the per-incidence and
+ *   per-edge buffers are sized by the data and allocated inside).  *n_edges_out = the number of edges; the first min(capacity, that)
+ *   of them, in (i, j) order, go to d_i / d_j / d_count (count = c, the diagonal's n_hash), which may be NULL when capacity is 0.
+ *   Synchronises the stream (two totals are read back).  n * bands must stay below 2^31 - 256. */
+size_t da_dev_lsh_workspace_bytes(int64_t n, int bands);
+int da_dev_lsh_band_keys(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint64_t *d_keys,
+                         int32_t *d_ids, void *stream);
+int da_dev_lsh_verify_pairs(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold,
+                            const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t n_triples, uint16_t *d_count,
+                            uint8_t *d_keep, void *stream);
+int da_dev_lsh_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold,
+                     int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_count,
+                     int64_t capacity, int64_t *n_edges_out, void *stream);
 
 /* name -> id for da_dev_nw; -1 + DA_ERR_BAD_MATRIX message when unknown. */
 int da_matrix_id(const char *matrix_name);
