@@ -24,7 +24,7 @@ from .similarity import (  # noqa: F401
     similarityJaccard_knn_edges, similarityJaccard_edges,
     similarityJaccard_long, similarityJaccard_cross_long, similarityJaccard_cross_topk_long, similarityJaccard_knn_long,
     similarityJaccard_knn_edges_long, similarityJaccard_edges_long, similarityJaccard_cross_edges_long, similarityJaccard_stats_long,
-    similarityMH_lsh_edges, lsh_edges_dense, lsh_collision_probability,
+    similarityMH_lsh_edges, lsh_edges_dense, lsh_collision_probability, similarityMH_lsh_knn, similarityMH_lsh_knn_edges, lsh_knn_dense,
 )
 
 __all__ = [
@@ -37,6 +37,6 @@ __all__ = [
     "similarityJaccard_knn_edges", "similarityJaccard_edges",
     "similarityJaccard_long", "similarityJaccard_cross_long", "similarityJaccard_cross_topk_long", "similarityJaccard_knn_long",
     "similarityJaccard_knn_edges_long", "similarityJaccard_edges_long", "similarityJaccard_cross_edges_long", "similarityJaccard_stats_long",
-    "similarityMH_lsh_edges", "lsh_edges_dense", "lsh_collision_probability",
+    "similarityMH_lsh_edges", "lsh_edges_dense", "lsh_collision_probability", "similarityMH_lsh_knn", "similarityMH_lsh_knn_edges", "lsh_knn_dense",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

@@ -183,7 +183,8 @@ class ClusterbreakResult(dict):
 
 
 def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_fn=None, cluster_fn=None,
-                 cluster_wt=True, *, session=None, edges_fn=None, cluster_seed=0, verbose=False, log=None, knn=None, knn_mode="union"):
+                 cluster_wt=True, *, session=None, edges_fn=None, cluster_seed=0, verbose=False, log=None, knn=None, knn_mode="union",
+                 knn_lsh=None):
     """Recursive quantile-threshold + Louvain splitting, reference clusterbreak (R/clusterbreak.R:180-275).
 
     pep        sequences (character vector)
@@ -197,6 +198,10 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
                m * knn edges in place of the quantile's fixed share of m^2 (thresh_p is not used); knn_mode "union" or "mutual".  Without a
                session give the graph as ``edges_fn=lambda s: similarityMH_knn_edges(s, k, n_hash, top, mode)``.  The memberships are not
                those of the quantile threshold: it is another graph.  None (default): the quantile threshold
+    knn_lsh    with a session and knn: a (bands, rows) pair -- a level takes its kNN graph from LSH candidates,
+               session.lsh_knn_csr(bands, rows, idx, min(knn, m - 1), knn_mode), in place of session.knn_csr: only bucket mates are compared,
+               and a neighbour that agrees in no whole band is missing.  Without a session give the graph as
+               ``edges_fn=lambda s: similarityMH_lsh_knn_edges(s, k, n_hash, bands, rows, top, mode)``.  None (default): all pairs
     cluster_seed  call number c of the recursion clusters with seed cluster_seed + c (the reference draws from
                R's global RNG instead)
     """
@@ -217,6 +222,19 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
         knn = int(knn)
         if knn < 1:
             raise ValueError("knn must be at least 1")
+    if knn_lsh is not None:
+        if session is None or knn is None:
+            raise ValueError("knn_lsh needs a session and knn; without them give the graph as "
+                             "edges_fn=lambda s: similarityMH_lsh_knn_edges(s, k, n_hash, bands, rows, top, mode)")
+        try:
+            lsh_bands, lsh_rows = (int(v) for v in knn_lsh)
+        except (TypeError, ValueError):
+            raise ValueError("knn_lsh must be a (bands, rows) pair") from None
+
+    def knn_csr(idx, m):
+        if knn_lsh is not None:
+            return session.lsh_knn_csr(lsh_bands, lsh_rows, idx, min(knn, m - 1), knn_mode)
+        return session.knn_csr(idx, min(knn, m - 1), knn_mode)
     if sim_fn is None and session is None and edges_fn is None:
         from .similarity import similarityMH
         sim_fn = lambda x: similarityMH(x, k=2, n_hash=50)                               # noqa: E731  (:185)
@@ -240,7 +258,7 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
                 thr, ei, ej, ew = edges_fn([pep[t] for t in idx])
                 return float(thr), np.asarray(ei, np.int32), np.asarray(ej, np.int32), np.asarray(ew, np.float64)
             if knn is not None:
-                thr, _, ptr, adj, codes, loops, values = session.knn_csr(idx, min(knn, m - 1), knn_mode)
+                thr, _, ptr, adj, codes, loops, values = knn_csr(idx, m)
                 return (thr,) + _csr_to_edges(ptr, adj, codes, loops, values)
             return session.edges(idx, thresh_p, sort=False)
         return threshold_edges_dense(sim_fn([pep[t] for t in idx]), thresh_p)
@@ -257,7 +275,7 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
         if csr_path and m >= 2:
             # device edge path + built-in Louvain: the graph arrives as canonical CSR sorted on the device (same graph, same result)
             if knn is not None:
-                thr, n_edges, ptr, adj, codes, loops, values = session.knn_csr(idx, min(knn, m - 1), knn_mode)
+                thr, n_edges, ptr, adj, codes, loops, values = knn_csr(idx, m)
             else:
                 thr, n_edges, ptr, adj, codes, loops, values = session.edges_csr(idx, thresh_p)
             t1 = time.perf_counter()

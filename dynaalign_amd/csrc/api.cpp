@@ -3496,13 +3496,16 @@ struct StreamDrain {
 LshRoute &lsh_route() { static thread_local LshRoute r; return r; }
 
 // bands, rows, threshold and the cap of the LSH calls, in the order include/dynaalign.h gives
-int lsh_arg_check(int n_hash, int bands, int rows, double threshold, int64_t max_candidates) {
+// (top: of the nearest-neighbour calls, checked between the cap and the 16-bit limit; nullptr for the edge calls)
+int lsh_arg_check(int n_hash, int bands, int rows, double threshold, int64_t max_candidates, const int *top = nullptr) {
   if (bands < 1) return fail(DA_ERR_BAD_ARG, "bands must be >= 1 (got %d)", bands);
   if (rows < 1) return fail(DA_ERR_BAD_ARG, "rows must be >= 1 (got %d)", rows);
   if ((int64_t)bands * rows > n_hash) return fail(DA_ERR_BAD_ARG, "bands * rows = %lld exceeds n_hash = %d", (long long)bands * rows, n_hash);
   if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(DA_ERR_BAD_ARG, "the threshold must be in [0, 1]");
   if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
-  if (n_hash > 65535) return fail(DA_ERR_UNSUPPORTED, "the LSH edge list counts in 16 bits: n_hash <= 65535 (got %d)", n_hash);
+  if (top && (*top < 1 || *top > DA_TOPK_MAX)) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. %d (got %d)", DA_TOPK_MAX, *top);
+  if (n_hash > 65535)
+    return fail(DA_ERR_UNSUPPORTED, "the LSH %s in 16 bits: n_hash <= 65535 (got %d)", top ? "nearest-neighbour lists count" : "edge list counts", n_hash);
   return DA_OK;
 }
 // the smallest count whose similarity -- the divide of mh_code_values -- reaches the threshold (n_hash + 1: none does)
@@ -3512,61 +3515,101 @@ uint32_t lsh_c_min(int n_hash, double threshold) {
   while (c <= (uint32_t)n_hash && !(values[c] >= threshold)) ++c;
   return c;
 }
-// The pipeline on resident signatures.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.
-int lsh_edges_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
-                     void *d_work, size_t work_bytes, DevBuf &key, DevBuf &val, int64_t *edges_out, hipStream_t stream) {
+// Steps 1 - 3 on resident signatures, what the edge list and the nearest-neighbour lists share: the buckets (the route's counts, the cap),
+// the verdict of every incidence slot (cnt, keep), the kept slots per chunk of 64 and their exclusive sum (coff); `kept` and `firsts` (the
+// distinct candidate pairs) are read back, so the stream is synchronised.  The pointers point into the caller's workspace.
+struct LshVerdicts {
+  DevBuf cnt, keep, ckept, coff, distinct, temp;
+  const uint64_t *d_keys = nullptr;
+  const int32_t *d_ids = nullptr;
+  const int64_t *d_off = nullptr;
+  int64_t inc = 0, kept = 0;
+  uint64_t firsts = 0;
+};
+int lsh_verdicts(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates, void *d_work,
+                 size_t work_bytes, LshVerdicts &v, hipStream_t stream) {
   if (n > 0x7ffffff0LL || n * (int64_t)bands > LSH_MAX_ELEMENTS)
     return fail(DA_ERR_UNSUPPORTED, "lsh: n * bands = %lld (sequence, band) elements, at most %lld in one call", (long long)(n * (int64_t)bands),
                 (long long)LSH_MAX_ELEMENTS);
   int rc;
-  DevBuf cnt, keep, ckept, coff, distinct, temp, key_in, val_in;
-  const StreamDrain drain{stream};
-  const uint64_t *d_keys;
-  const int32_t *d_ids;
-  const int64_t *d_off;
   uint32_t stats[2] = {0, 0};
-  int64_t inc = 0;
-  if ((rc = lsh_buckets(d_sig, n, ld_sig, bands, rows, d_work, work_bytes, &d_keys, &d_ids, &d_off, stats, &inc, stream)) != DA_OK) return rc;
+  if ((rc = lsh_buckets(d_sig, n, ld_sig, bands, rows, d_work, work_bytes, &v.d_keys, &v.d_ids, &v.d_off, stats, &v.inc, stream)) != DA_OK) return rc;
   LshRoute &route = lsh_route();
   route = LshRoute();
   route.buckets = stats[1];
-  route.incidences = inc;
-  if (inc > max_candidates)
+  route.incidences = v.inc;
+  if (v.inc > max_candidates)
     return fail(DA_ERR_UNSUPPORTED, "lsh: %lld (pair, band) candidates exceed max_candidates = %lld (largest bucket: %u sequences); use more rows per band",
-                (long long)inc, (long long)max_candidates, stats[0]);
-  const int64_t chunks = ceil_div(inc, 64);
-  if (chunks + 1 > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld candidates are more than one call verifies", (long long)inc);
-  const size_t scan_b = lsh_chunk_scan_bytes(inc);
-  if ((rc = cnt.alloc((size_t)inc * 2)) != DA_OK || (rc = keep.alloc((size_t)inc)) != DA_OK || (rc = ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
-      (rc = coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = distinct.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_verify_enumerated(d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_off, d_ids, d_keys, inc, cnt.as<uint16_t>(),
-                                         keep.as<uint8_t>(), ckept.as<int64_t>(), coff.as<int64_t>(), distinct.as<uint64_t>(), temp.p, scan_b, stream)) != DA_OK)
+                (long long)v.inc, (long long)max_candidates, stats[0]);
+  const int64_t chunks = ceil_div(v.inc, 64);
+  if (chunks + 1 > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld candidates are more than one call verifies", (long long)v.inc);
+  const size_t scan_b = lsh_chunk_scan_bytes(v.inc);
+  if ((rc = v.cnt.alloc((size_t)v.inc * 2)) != DA_OK || (rc = v.keep.alloc((size_t)v.inc)) != DA_OK || (rc = v.ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
+      (rc = v.coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = v.distinct.alloc(8)) != DA_OK || (rc = v.temp.alloc(scan_b)) != DA_OK) return rc;
+  if ((rc = launch_lsh_verify_enumerated(d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), v.d_off, v.d_ids, v.d_keys, v.inc,
+                                         v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.ckept.as<int64_t>(), v.coff.as<int64_t>(), v.distinct.as<uint64_t>(),
+                                         v.temp.p, scan_b, stream)) != DA_OK)
     return rc;
-  int64_t kept = 0;
-  uint64_t firsts = 0;
-  DA_HIP_TRY(hipMemcpyAsync(&kept, coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipMemcpyAsync(&firsts, distinct.p, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(&v.kept, v.coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(&v.firsts, v.distinct.p, 8, hipMemcpyDeviceToHost, stream));
   DA_HIP_TRY(hipStreamSynchronize(stream));
-  const int64_t edges = n + kept;
+  v.temp.release();
+  return DA_OK;
+}
+// The pipeline on resident signatures.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.
+int lsh_edges_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
+                     void *d_work, size_t work_bytes, DevBuf &key, DevBuf &val, int64_t *edges_out, hipStream_t stream) {
+  int rc;
+  LshVerdicts v;
+  DevBuf temp, key_in, val_in;
+  const StreamDrain drain{stream};
+  if ((rc = lsh_verdicts(d_sig, n, ld_sig, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v, stream)) != DA_OK) return rc;
+  const int64_t edges = n + v.kept;
   if (edges > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld edges are more than one call sorts", (long long)edges);
   const size_t sort_b = lsh_edge_sort_bytes(edges);
-  temp.release();
   if ((rc = key_in.alloc((size_t)edges * 8)) != DA_OK || (rc = val_in.alloc((size_t)edges * 2)) != DA_OK || (rc = key.alloc((size_t)edges * 8)) != DA_OK ||
       (rc = val.alloc((size_t)edges * 2)) != DA_OK || (rc = temp.alloc(sort_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_emit_sort(n, n_hash, bands, d_off, d_ids, d_keys, inc, cnt.as<uint16_t>(), keep.as<uint8_t>(), coff.as<int64_t>(), edges,
+  if ((rc = launch_lsh_emit_sort(n, n_hash, bands, v.d_off, v.d_ids, v.d_keys, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.coff.as<int64_t>(), edges,
                                  key_in.as<uint64_t>(), val_in.as<uint16_t>(), key.as<uint64_t>(), val.as<uint16_t>(), temp.p, sort_b, stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipStreamSynchronize(stream));
-  route.verified = (int64_t)firsts;
+  LshRoute &route = lsh_route();
+  route.verified = (int64_t)v.firsts;
   route.edges = edges;
   *edges_out = edges;
   return DA_OK;
 }
-int lsh_dev_check(const void *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold) {
+int lsh_dev_check(const void *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, const int *top = nullptr) {
   if (n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
   if (n_hash <= 0) return fail(DA_ERR_BAD_NHASH, "%s", da_status_message(DA_ERR_BAD_NHASH));
   if (!d_sig) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
   if (ld_sig < n_hash) return fail(DA_ERR_BAD_ARG, "ld_sig (%lld) < n_hash (%d)", (long long)ld_sig, n_hash);
-  return lsh_arg_check(n_hash, bands, rows, threshold, 0);
+  return lsh_arg_check(n_hash, bands, rows, threshold, 0, top);
+}
+// The nearest-neighbour pipeline on resident signatures: the verdicts, then the directed entries and the selection into d_idx / d_key
+// ((n, top), leading dimension top).  Synchronises the stream (totals are read back).
+int lsh_knn_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int top, int64_t max_candidates,
+                   void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key, hipStream_t stream) {
+  int rc;
+  LshVerdicts v;
+  DevBuf temp, cursor, ptr, col, ecnt, written;
+  const StreamDrain drain{stream};
+  if ((rc = lsh_verdicts(d_sig, n, ld_sig, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v, stream)) != DA_OK) return rc;
+  const int64_t entries = 2 * v.kept;            // both directions of every kept pair
+  const size_t scan_b = lsh_knn_scan_bytes(n);
+  if ((rc = cursor.alloc((size_t)(n + 1) * 8)) != DA_OK || (rc = ptr.alloc((size_t)(n + 1) * 8)) != DA_OK || (rc = col.alloc((size_t)entries * 4)) != DA_OK ||
+      (rc = ecnt.alloc((size_t)entries * 2)) != DA_OK || (rc = written.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
+  if ((rc = launch_lsh_knn_entries(n, bands, v.d_off, v.d_ids, v.d_keys, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), entries, top,
+                                   cursor.as<int64_t>(), ptr.as<int64_t>(), col.as<int32_t>(), ecnt.as<uint16_t>(), written.as<uint64_t>(), temp.p, scan_b,
+                                   stream)) != DA_OK ||
+      (rc = launch_lsh_knn_select(ptr.as<int64_t>(), entries, col.as<int32_t>(), ecnt.as<uint16_t>(), n, top, d_idx, top, d_key, top, stream)) != DA_OK)
+    return rc;
+  uint64_t entries_written = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&entries_written, written.p, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  LshRoute &route = lsh_route();
+  route.verified = (int64_t)v.firsts;
+  route.edges = (int64_t)entries_written;
+  return DA_OK;
 }
 }  // namespace
 extern "C" {
@@ -3650,6 +3693,49 @@ int da_similarity_mh_lsh_edges_begin(const uint8_t *residues, const int64_t *off
   *n_edges_out = edges;
   *handle_out = h.release();
   return DA_OK;
+}
+
+int da_dev_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
+                          int64_t ld_idx, uint16_t *d_key, int64_t ld_key, void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (top < 1 || top > DA_TOPK_MAX) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. %d (got %d)", DA_TOPK_MAX, top);
+  if (nnz < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (ld_idx < top || ld_key < top) return fail(DA_ERR_BAD_ARG, "ld (%lld) < top (%d)", (long long)std::min(ld_idx, ld_key), top);
+  if (!d_ptr || !d_idx || !d_key || (nnz > 0 && (!d_col || !d_count))) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_lsh_knn_select(d_ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key, ld_key, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_knn(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int top, int64_t max_candidates,
+                   void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key, void *stream) {
+  int rc;
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, threshold, &top)) != DA_OK) return rc;
+  if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
+  if (!d_work || !d_idx || !d_key) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return lsh_knn_device(d_sig, n, ld_sig, n_hash, bands, rows, threshold, top, max_candidates, d_work, work_bytes, d_idx, d_key,
+                        static_cast<hipStream_t>(stream));
+}
+
+int da_similarity_mh_lsh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
+                             double threshold, int top, int64_t max_candidates, int32_t *idx_out, double *val_out) {
+  int rc = validate_mh(n, k, n_hash);
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !idx_out || !val_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, threshold, max_candidates, &top)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf work, didx, dkey;
+  const StreamDrain drain{nullptr};
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash, false)) != DA_OK || (rc = mh.signatures(k, 0, n_hash)) != DA_OK) return rc;
+  const size_t wb = lsh_workspace_bytes(n, bands);
+  if ((rc = work.alloc(wb)) != DA_OK || (rc = didx.alloc((size_t)n * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  if ((rc = lsh_knn_device(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows, threshold, top, max_candidates, work.p, wb, didx.as<int32_t>(),
+                           dkey.as<uint16_t>(), nullptr)) != DA_OK) return rc;
+  return topk_to_host(didx, dkey, n, top, mh_code_values(n_hash), idx_out, val_out);
 }
 
 int da_mh_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *edges_out) {

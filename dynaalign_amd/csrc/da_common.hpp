@@ -411,6 +411,16 @@ int launch_lsh_emit_sort(int64_t n, int n_hash, int bands, const int64_t *d_off,
                          const uint16_t *d_count, const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in,
                          uint64_t *d_key_out, uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
 int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count, int32_t *d_i, int32_t *d_j, uint16_t *d_count, hipStream_t stream);
+// ... and the nearest-neighbour lists from the same candidates (da_dev_lsh_knn*): after the verify step, launch_lsh_knn_entries turns the kept
+// slots into ragged rows (both directions of every pair; entries = 2 * kept) and launch_lsh_knn_select takes every row's first `top` entries by
+// (count descending, column ascending) -- rows of up to 64 entries by a wave, longer ones by a workgroup, which sorts up to 2048 entries
+// whole and radix-selects in longer rows.  The selection needs no workspace and does not synchronise.
+size_t lsh_knn_scan_bytes(int64_t n);
+int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
+                           const uint16_t *d_count, const uint8_t *d_keep, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col,
+                           uint16_t *d_cnt, uint64_t *d_written, void *d_temp, size_t temp_bytes, hipStream_t stream);
+int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
+                          int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

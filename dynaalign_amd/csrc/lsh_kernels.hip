@@ -393,4 +393,287 @@ int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count
   return DA_OK;
 }
 
+// ---- nearest-neighbour lists from the candidates (da_dev_lsh_knn, da_dev_lsh_knn_select) --------------------------------------------------
+// After step 3 every kept slot is a distinct pair i < j with its count.  Row i's list is the first `top` of its candidates by (count
+// descending, column ascending), so both directions of a pair are needed:
+//   5. k_lsh_knn_entries<false>: deg[i]++, deg[j]++ over the kept slots; an exclusive sum gives ptr[n + 1];
+//   6. k_lsh_knn_entries<true>: (col = j, count) into row i's segment and (col = i, count) into row j's, through a per-row cursor.  The
+//      slots of a chunk mostly share their i (the partners of one element are consecutive slots), so the i side takes ONE atomic per
+//      distinct i of the chunk and writes its entries side by side; the j side takes one atomic per entry.  The order inside a segment
+//      is whatever the scheduling gives: the selection does not depend on it;
+//   7. the selection, on the 48-bit words (0xFFFF - count) << 32 | col -- ascending word order is count descending, column ascending, and
+//      the words of a row are distinct because its columns are.  Degrees are very skewed, so there are two kernels:
+//        k_lsh_knn_select_short  rows of up to LSH_KNN_WAVE_MAX entries: a wave per row, an entry per lane, a bitonic sort by shuffles;
+//        k_lsh_knn_select_long   the other rows: a workgroup looks at LSH_KNN_TILE rows at a time, lists the long ones in LDS and takes them
+//                                one after the other.  Up to LSH_KNN_LDS_WORDS entries are loaded and sorted whole in LDS.  A longer row
+//                                first finds T, its top-th smallest word, by an MSD radix select over six 8-bit digits (a 256-bin LDS
+//                                histogram per digit, over the entries that match the digits fixed so far), then compacts the words
+//                                <= T -- exactly `top` of them -- through an LDS counter and sorts those.
+//      Neither kernel needs a workspace, so the selection on a caller's ragged rows is asynchronous.
+namespace {
+constexpr int LSH_KNN_WAVE_MAX = 64;
+constexpr int LSH_KNN_LDS_WORDS = 2048;
+constexpr int LSH_KNN_TILE = LSH_THREADS;
+static_assert(DA_TOPK_MAX <= LSH_KNN_LDS_WORDS, "the candidates of the radix path are sorted in the same buffer");
+
+__device__ __forceinline__ unsigned long long lsh_shfl64(unsigned long long v, int src) {
+  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long lsh_shfl_xor64(unsigned long long v, int mask) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long lsh_knn_word(int32_t col, uint16_t count) {
+  return ((unsigned long long)(0xFFFFu - count) << 32) | (uint32_t)col;
+}
+// row r's entries: [b, e), with a pointer that runs backwards or past nnz cut to what lies inside [0, nnz)
+__device__ __forceinline__ void lsh_knn_segment(const long long *__restrict__ ptr, int64_t r, int64_t nnz, int64_t &b, int64_t &e) {
+  b = min(max((int64_t)ptr[r], (int64_t)0), nnz);
+  e = min(max((int64_t)ptr[r + 1], (int64_t)0), nnz);
+  if (e < b) e = b;
+}
+
+// SCATTER = false: at[] are the degrees.  SCATTER = true: at[] are the cursors (they start as the row pointers) and the entries are written.
+template <bool SCATTER>
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(LshEnumerated src, int64_t slots, const uint16_t *__restrict__ count,
+                                                                 const uint8_t *__restrict__ keep, unsigned long long *__restrict__ at,
+                                                                 int32_t *__restrict__ out_col, uint16_t *__restrict__ out_count) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
+  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
+    const int64_t s = c * 64 + lane;
+    const bool kp = s < slots && keep[s] != 0;
+    unsigned long long todo = __ballot(kp);
+    if (!todo) continue;                          // wave-uniform
+    int i = -1, j = -1, t = 0;
+    uint16_t cv = 0;
+    if (kp) {
+      src.get(s, i, j, t);
+      cv = count[s];
+      const unsigned long long pos = atomicAdd(&at[j], 1ull);
+      if (SCATTER) { out_col[pos] = i; out_count[pos] = cv; }
+    }
+    while (todo) {                                // one round per distinct i of the chunk
+      const int leader = __ffsll((long long)todo) - 1;
+      const int li = __shfl(i, leader);
+      const unsigned long long same = __ballot(kp && i == li);
+      unsigned long long base = 0;
+      if (lane == leader) base = atomicAdd(&at[li], (unsigned long long)__popcll(same));
+      if (SCATTER) {
+        base = lsh_shfl64(base, leader);
+        if (kp && i == li) {
+          const unsigned long long pos = base + (unsigned long long)__popcll(same & ((1ull << lane) - 1));
+          out_col[pos] = j;
+          out_count[pos] = cv;
+        }
+      }
+      todo &= ~same;
+    }
+  }
+}
+
+// *out += the list entries the selection writes: the sum of min(degree, top)
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_written(const long long *__restrict__ ptr, int64_t n, int64_t nnz, int top,
+                                                                 unsigned long long *__restrict__ out) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  unsigned long long sum = 0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
+    int64_t b, e;
+    lsh_knn_segment(ptr, r, nnz, b, e);
+    sum += (unsigned long long)min(e - b, (int64_t)top);
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += lsh_shfl_xor64(sum, o);
+  if ((threadIdx.x & 63) == 0 && sum) atomicAdd(out, sum);
+}
+
+// entry t of row r: the word's column and count, or the padding -1 / 0
+__device__ __forceinline__ void lsh_knn_put(unsigned long long word, bool real, int32_t *__restrict__ idx, uint16_t *__restrict__ key) {
+  *idx = real ? (int32_t)(uint32_t)(word & 0xFFFFFFFFull) : -1;
+  *key = real ? (uint16_t)(0xFFFFu - (uint32_t)(word >> 32)) : (uint16_t)0;
+}
+
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_short(const long long *__restrict__ ptr, int64_t nnz, const int32_t *__restrict__ col,
+                                                                      const uint16_t *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
+                                                                      int64_t ld_idx, uint16_t *__restrict__ key, int64_t ld_key) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64);
+  for (int64_t r = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); r < n; r += nwaves) {
+    int64_t b, e;
+    lsh_knn_segment(ptr, r, nnz, b, e);
+    const int deg = (int)min(e - b, (int64_t)(LSH_KNN_WAVE_MAX + 1));
+    if (deg > LSH_KNN_WAVE_MAX) continue;         // wave-uniform: the long kernel's row
+    unsigned long long word = lane < deg ? lsh_knn_word(col[b + lane], count[b + lane]) : ~0ull;
+    for (int k = 2; (k >> 1) < deg; k <<= 1)      // bitonic, ascending; the lanes behind the row hold the largest word
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        const unsigned long long other = lsh_shfl_xor64(word, j);
+        const bool take_min = ((lane & j) == 0) == ((lane & k) == 0);
+        word = take_min ? min(word, other) : max(word, other);
+      }
+    const int real = min(deg, top);
+    for (int t = lane; t < top; t += 64) lsh_knn_put(word, t < real, idx + r * ld_idx + t, key + r * ld_key + t);
+  }
+}
+
+// bitonic sort, ascending, of buf[0 .. p2) (p2 a power of two) by the whole workgroup; ends with a barrier
+__device__ __forceinline__ void lsh_knn_sort_lds(unsigned long long *buf, int p2) {
+  for (int k = 2; k <= p2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int a = threadIdx.x; a < p2; a += LSH_THREADS) {
+        const int o = a ^ j;
+        if (o > a) {
+          const unsigned long long x = buf[a], y = buf[o];
+          if ((x > y) == ((a & k) == 0)) { buf[a] = y; buf[o] = x; }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long long *__restrict__ ptr, int64_t nnz, const int32_t *__restrict__ col,
+                                                                     const uint16_t *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
+                                                                     int64_t ld_idx, uint16_t *__restrict__ key, int64_t ld_key) {
+  __shared__ unsigned long long buf[LSH_KNN_LDS_WORDS];
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned int wtot[LSH_THREADS / 64];
+  __shared__ int long_rows[LSH_KNN_TILE];
+  __shared__ unsigned int ctl[5];                 // long rows of the tile; the digit's bin, the entries below it, those in it; the compaction cursor
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t tiles = (n + LSH_KNN_TILE - 1) / LSH_KNN_TILE;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    if (tid == 0) ctl[0] = 0;
+    __syncthreads();
+    {
+      const int64_t r = tile * LSH_KNN_TILE + tid;
+      if (r < n) {
+        int64_t b, e;
+        lsh_knn_segment(ptr, r, nnz, b, e);
+        if (e - b > LSH_KNN_WAVE_MAX) long_rows[atomicAdd(&ctl[0], 1u)] = tid;
+      }
+    }
+    __syncthreads();
+    const int n_long = (int)ctl[0];
+    for (int q = 0; q < n_long; ++q) {
+      const int64_t r = tile * LSH_KNN_TILE + long_rows[q];
+      int64_t b, e;
+      lsh_knn_segment(ptr, r, nnz, b, e);
+      const int64_t deg = e - b;
+      int have;
+      if (deg <= LSH_KNN_LDS_WORDS) {
+        for (int64_t p = tid; p < deg; p += LSH_THREADS) buf[p] = lsh_knn_word(col[b + p], count[b + p]);
+        have = (int)deg;
+      } else {                                    // top <= DA_TOPK_MAX < deg: the top-th smallest word exists
+        unsigned long long prefix = 0, T = 0;
+        unsigned int need = (unsigned int)top;
+        for (int d = 5; d >= 0; --d) {
+          const int shift = 8 * d;
+          hist[tid] = 0;
+          __syncthreads();
+          for (int64_t p0 = 0; p0 < deg; p0 += LSH_THREADS) {
+            const int64_t p = p0 + tid;
+            unsigned long long w = 0;
+            bool m = false;
+            if (p < deg) {
+              w = lsh_knn_word(col[b + p], count[b + p]);
+              m = d == 5 || (w >> (shift + 8)) == (prefix >> (shift + 8));
+            }
+            const int digit = (int)((w >> shift) & 255);
+            const unsigned long long mm = __ballot(m);
+            if (!mm) continue;                    // wave-uniform
+            const int d0 = __shfl(digit, __ffsll((long long)mm) - 1);
+            if (__ballot(m && digit == d0) == mm) {   // one digit in the whole wave (equal counts, say): one add
+              if (lane == __ffsll((long long)mm) - 1) atomicAdd(&hist[d0], (unsigned int)__popcll(mm));
+            } else if (m) {
+              atomicAdd(&hist[digit], 1u);
+            }
+          }
+          __syncthreads();
+          const unsigned int h = hist[tid];
+          unsigned int incl = h;
+          for (int o = 1; o < 64; o <<= 1) {
+            const unsigned int v = (unsigned int)__shfl_up((int)incl, o);
+            if (lane >= o) incl += v;
+          }
+          if (lane == 63) wtot[wave] = incl;
+          __syncthreads();
+          unsigned int excl = incl - h;
+          for (int w2 = 0; w2 < wave; ++w2) excl += wtot[w2];
+          if (h && excl < need && need <= excl + h) { ctl[1] = (unsigned int)tid; ctl[2] = excl; ctl[3] = h; }   // one bin holds the need-th entry
+          __syncthreads();
+          const unsigned int bin = ctl[1], below = ctl[2], inbin = ctl[3];
+          prefix |= (unsigned long long)bin << shift;
+          T = prefix | ((1ull << shift) - 1);
+          if (below + inbin == need) break;       // everything up to this bin is the selection: the digits behind need no look
+          need -= below;
+        }
+        if (tid == 0) ctl[4] = 0;
+        __syncthreads();
+        for (int64_t p = tid; p < deg; p += LSH_THREADS) {
+          const unsigned long long w = lsh_knn_word(col[b + p], count[b + p]);
+          if (w <= T) {
+            const unsigned int at = atomicAdd(&ctl[4], 1u);
+            if (at < (unsigned int)DA_TOPK_MAX) buf[at] = w;   // exactly `top` words when the columns are distinct, as the contract says
+          }
+        }
+        __syncthreads();
+        have = (int)min(ctl[4], (unsigned int)DA_TOPK_MAX);
+      }
+      int p2 = 2;
+      while (p2 < have) p2 <<= 1;
+      for (int a = have + tid; a < p2; a += LSH_THREADS) buf[a] = ~0ull;
+      __syncthreads();
+      lsh_knn_sort_lds(buf, p2);
+      const int real = min(have, top);
+      for (int t = tid; t < top; t += LSH_THREADS) lsh_knn_put(t < real ? buf[t] : 0ull, t < real, idx + r * ld_idx + t, key + r * ld_key + t);
+      __syncthreads();                            // the buffer and the control words are the next row's
+    }
+  }
+}
+}  // namespace
+
+int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
+                          int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream) {
+  if (n <= 0) return DA_OK;
+  const long long *ptr = reinterpret_cast<const long long *>(d_ptr);
+  hipLaunchKernelGGL(k_lsh_knn_select_short, dim3(lsh_grid(n * 64)), dim3(LSH_THREADS), 0, stream, ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key,
+                     ld_key);
+  DA_HIP_TRY(hipGetLastError());
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, LSH_KNN_TILE), 256 * 8);
+  hipLaunchKernelGGL(k_lsh_knn_select_long, dim3(grid), dim3(LSH_THREADS), 0, stream, ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key, ld_key);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+// scratch of the scan over n + 1 degrees
+size_t lsh_knn_scan_bytes(int64_t n) { return up256(scan_i64_bytes(n + 1)) + 256; }
+
+// Steps 5 and 6 on the verdicts of launch_lsh_verify_enumerated: d_ptr[n + 1] = the row pointers of the directed entries (2 per kept slot),
+// d_col / d_cnt their columns and counts; d_cursor (n + 1 words) is scratch.  *d_written (zeroed here) = the sum of min(degree, top).
+int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
+                           const uint16_t *d_count, const uint8_t *d_keep, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col,
+                           uint16_t *d_cnt, uint64_t *d_written, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  unsigned long long *cursor = reinterpret_cast<unsigned long long *>(d_cursor);
+  const LshEnumerated src{reinterpret_cast<const long long *>(d_off), d_ids, reinterpret_cast<const unsigned long long *>(d_keys), n * bands};
+  const unsigned grid = lsh_grid(ceil_div(incidences, 64) * 64);
+  DA_HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(n + 1) * 8, stream));
+  DA_HIP_TRY(hipMemsetAsync(d_written, 0, 8, stream));
+  if (incidences > 0 && entries > 0) {
+    hipLaunchKernelGGL(k_lsh_knn_entries<false>, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, (int32_t *)nullptr,
+                       (uint16_t *)nullptr);
+    DA_HIP_TRY(hipGetLastError());
+  }
+  size_t tb = temp_bytes;
+  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_cursor), reinterpret_cast<long long *>(d_ptr), (int)(n + 1),
+                                              stream));
+  if (incidences > 0 && entries > 0) {
+    DA_HIP_TRY(hipMemcpyAsync(d_cursor, d_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, stream));
+    hipLaunchKernelGGL(k_lsh_knn_entries<true>, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, d_col, d_cnt);
+    DA_HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_lsh_knn_written, dim3(lsh_grid(n)), dim3(LSH_THREADS), 0, stream, reinterpret_cast<const long long *>(d_ptr), n, entries, top,
+                     reinterpret_cast<unsigned long long *>(d_written));
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
 }  // namespace da

@@ -872,6 +872,60 @@ def lsh_edges(sig, n_hash, bands, rows, threshold, max_candidates=1 << 32, capac
     return ei[:got], ej[:got], ec[:got]
 
 
+# The row classes of the selection (lsh_kernels.hip: LSH_KNN_WAVE_MAX, LSH_KNN_LDS_WORDS): a row of up to LSH_KNN_WAVE_MAX entries is sorted
+# by one wave, one of up to LSH_KNN_LDS_WORDS whole in LDS by a workgroup, a longer one goes through the radix select first.
+LSH_KNN_WAVE_MAX = 64
+LSH_KNN_LDS_WORDS = 2048
+
+
+def lsh_knn_select(ptr, col, count, top, nnz=None, out=None):
+    """The per-row selection of the LSH nearest-neighbour lists on a caller's ragged rows (da_dev_lsh_knn_select): ``ptr`` int64 (n + 1),
+    ``col`` int32 (>= 0, distinct within a row, any order) and ``count`` int16 (uint16 bit pattern) device tensors -> (idx int32 (n, top),
+    key int16 (n, top)): per row the first ``top`` entries by (count descending, column ascending), then -1 / 0.  ``nnz`` (default
+    ``col.numel()``): entries at or behind it are not read, whatever ``ptr`` says.  ``out=(idx, key)``: 2-d tensors with at least ``top``
+    columns and unit column stride to write into (columns >= top stay untouched).  Asynchronous on the current stream."""
+    lib = _capi.load()
+    for t, name in ((ptr, "ptr"), (col, "col"), (count, "count")):
+        _require_cuda(t, name)
+    assert ptr.dtype == torch.int64 and col.dtype == torch.int32 and count.dtype == torch.int16
+    assert ptr.is_contiguous() and col.is_contiguous() and count.is_contiguous() and col.numel() == count.numel()
+    n = int(ptr.numel()) - 1
+    nnz = int(col.numel()) if nnz is None else int(nnz)
+    if not 0 <= nnz <= col.numel():
+        raise ValueError("nnz must be in 0 .. col.numel()")
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    if out is None:
+        idx = torch.empty((max(n, 1), t), dtype=torch.int32, device=ptr.device)
+        key = torch.empty((max(n, 1), t), dtype=torch.int16, device=ptr.device)
+    else:
+        idx, key = out
+        for o, dt in ((idx, torch.int32), (key, torch.int16)):
+            _require_cuda(o, "out")
+            assert o.dim() == 2 and o.dtype == dt and o.shape[0] >= n and o.shape[1] >= t and o.stride(1) == 1
+    _call(lib.da_dev_lsh_knn_select, ptr.data_ptr(), nnz, col.data_ptr(), count.data_ptr(), n, int(top), idx.data_ptr(), idx.stride(0),
+          key.data_ptr(), key.stride(0), _stream())
+    return idx[:n, :t], key[:n, :t]
+
+
+def lsh_knn(sig, n_hash, bands, rows, top, threshold=0.0, max_candidates=1 << 32, work=None):
+    """The LSH nearest-neighbour lists of resident signatures (da_dev_lsh_knn) -> (idx int32 (n, top), key int16 (n, top), the counts as
+    uint16 bit patterns; padding -1 / 0); value = count / n_hash (``widen``).  ``mh_lsh_last_route()["edges"]`` has the number of real
+    entries.  Synchronises the stream."""
+    lib = _capi.load()
+    n, ld = _sig_block(sig, n_hash)
+    if work is None:
+        work = torch.empty(lsh_workspace_bytes(n, bands), dtype=torch.uint8, device=sig.device)
+    _require_cuda(work, "work")
+    if work.dtype != torch.uint8 or not work.is_contiguous():
+        raise ValueError("work must be a contiguous uint8 tensor of lsh_workspace_bytes(n, bands) bytes")
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    idx = torch.empty((max(n, 1), t), dtype=torch.int32, device=sig.device)
+    key = torch.empty((max(n, 1), t), dtype=torch.int16, device=sig.device)
+    _call(lib.da_dev_lsh_knn, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), int(top), int(max_candidates),
+          work.data_ptr(), work.numel(), idx.data_ptr(), key.data_ptr(), _stream())
+    return idx[:n], key[:n]
+
+
 def mh_lsh_last_route():
     from .similarity import mh_lsh_last_route as route
     return route()

@@ -14,6 +14,7 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     i, v = s.knn(10, idx)                                           # == similarityMH_knn(sequences[idx], 4, 500, 10, seed=12345)
     thr, m, ptr, adj, codes, loops, values = s.knn_csr(idx, 10)     # the kNN graph of those lists as CSR (== similarityMH_knn_edges(...))
     thr, i, j, w = s.lsh_edges(12, 4, 0.5, idx)                     # == similarityMH_lsh_edges(sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) at n_hash = 48
+    i, v = s.lsh_knn(12, 4, 10, idx)                                # == similarityMH_lsh_knn(sequences[idx], 4, 48, 12, 4, 10, seed=12345) at n_hash = 48
     st = s.stats(idx)                                               # == similarityMH_stats(sequences[idx], 4, 500, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
@@ -272,6 +273,28 @@ class MinHashSession:
         ei, ej, ec = device.lsh_edges(sig[:m], self.n_hash, bands, rows, threshold, max_candidates=max_candidates)
         c = ec.cpu().numpy().view(np.uint16).astype(np.float64)
         return float(threshold), ei.cpu().numpy(), ej.cpu().numpy(), c / np.float64(self.n_hash)
+
+    def lsh_knn(self, bands, rows, top=10, idx=None, threshold=0.0, max_candidates=1 << 32):
+        """``(idx, val)`` == similarityMH_lsh_knn(sequences[idx], k, n_hash, bands, rows, top, threshold=threshold, seed=session.seed), from the
+        resident signatures: bucketing, candidate verification and the per-row selection on the device; positions are those in idx, the
+        padding is -1 / 0.0.  ``top`` is not clamped to the subset's size."""
+        sig, m = self._subset(idx)
+        i, key = device.lsh_knn(sig[:m], self.n_hash, bands, rows, top, threshold=threshold, max_candidates=max_candidates)
+        val = device.widen(key.contiguous(), False, self.n_hash)         # count / n_hash, the library's divide; the padding's 0 gives 0.0
+        return i.cpu().numpy(), val.cpu().numpy()
+
+    def lsh_knn_csr(self, bands, rows, idx=None, top=10, mode="union"):
+        """The kNN graph of lsh_knn(bands, rows, top, idx) with the 1.0 diagonal as the canonical symmetric CSR knn_csr returns -- lists ->
+        device.knn_edges (which skips the padding) -> device.edges_to_csr, all on the device: (threshold, n_edges, ptr, adj, codes,
+        loop_codes, values).  What ``clusterbreak(session=, knn=, knn_lsh=(bands, rows))`` clusters on."""
+        sig, m = self._subset(idx)
+        i, key = device.lsh_knn(sig[:m], self.n_hash, bands, rows, top)
+        ei, ej, ev, got = device.knn_edges(i, key, mode, is_nw=False, self_code=self.n_hash, loops=True)
+        ptr, adj, codes, loops = device.edges_to_csr(ei, ej, ev, got, m)
+        values = np.arange(self.n_hash + 1, dtype=np.float64) / self.n_hash           # src/minHash.cpp:174
+        codes_h = codes.cpu().numpy().view(np.uint16)
+        thr = float(values[int(codes_h.min())]) if len(codes_h) else float("nan")
+        return thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes_h, loops.cpu().numpy().view(np.uint16), values
 
     def stats(self, idx=None):
         """compute_similarity_stats of the subset's similarity matrix without that matrix on the host (``SimilarityStats``, positions in

@@ -941,6 +941,58 @@ def lsh_edges_dense(sig, bands, rows, threshold):
     return p[keep, 0].astype(np.int32), p[keep, 1].astype(np.int32), w[keep]
 
 
+def similarityMH_lsh_knn(sequences, k=4, n_hash=50, bands=10, rows=5, top=10, *, threshold=0.0, seed=None, max_candidates=1 << 32):
+    """Nearest-neighbour lists from LSH candidates instead of all n (n - 1) pairs: ``(idx, val)``, (n, top) int32 and (n, top) float64.
+    Row i lists the first ``top`` of ``{j != i : i and j agree in all columns of some band, c / n_hash >= threshold}`` by c descending, then
+    j ascending (c = equal columns, the divide of similarityMH); a row with fewer candidates is padded with ``idx = -1, val = 0.0``, and
+    ``val > 0`` marks exactly the real entries.  The result is exactly ``lsh_knn_dense(minhash_signatures(sequences, k, n_hash, seed=seed),
+    bands, rows, top, threshold)``.  What is approximate is that definition's relation to ``similarityMH_knn``: a true neighbour that
+    agrees in no whole band is missing; with ``rows = 1, bands = n_hash`` the lists equal similarityMH_knn's wherever its value is > 0.
+    ``top`` is in 1 .. 1024 and is NOT clamped to n - 1; n = 1 gives one row of padding.  Byte-identical sequences fill each other's lists
+    at 1.0: pass distinct sequences.  ``max_candidates`` as in similarityMH_lsh_edges."""
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    top = _as_int(top, "top")
+    shape = (max(n, 1), min(max(top, 1), 1024))
+    idx = np.empty(shape, np.int32)
+    val = np.empty(shape, np.float64)
+    _capi.check(lib.da_similarity_mh_lsh_knn(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, _as_int(bands, "bands"),
+                                             _as_int(rows, "rows"), float(threshold), top, int(max_candidates), idx.ctypes.data, val.ctypes.data))
+    return idx[:n], val[:n]
+
+
+def similarityMH_lsh_knn_edges(sequences, k=4, n_hash=50, bands=10, rows=5, top=10, mode="union", *, threshold=0.0, seed=None,
+                               max_candidates=1 << 32):
+    """The kNN graph of similarityMH_lsh_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``: knn_graph of the lists (the
+    padding has value 0 and is no edge) with the 1.0 diagonal of similarityMH.  The ``threshold`` slot holds the smallest off-diagonal
+    weight kept, NaN when none."""
+    idx, val = similarityMH_lsh_knn(sequences, k, n_hash, bands, rows, top, threshold=threshold, seed=seed, max_candidates=max_candidates)
+    return _knn_edges_result(idx, val, 1.0, mode)
+
+
+def lsh_knn_dense(sig, bands, rows, top, threshold=0.0):
+    """The definition ``similarityMH_lsh_knn`` is exact against, in numpy (host code, beside ``lsh_edges_dense``): ``sig`` is the
+    (n, n_hash) uint32 signature matrix; -> ``(idx, val)``, (n, top) int32 / float64: row i holds the first ``top`` candidates j != i with
+    ``c / n_hash >= threshold`` by (c descending, j ascending), then ``-1`` / ``0.0``.  1 <= top <= 1024; not clamped to n - 1."""
+    top = _as_int(top, "top")
+    if not 1 <= top <= 1024:
+        raise ValueError("top must be in 1 .. 1024 (got %d)" % top)
+    ei, ej, w = lsh_edges_dense(sig, bands, rows, threshold)
+    n, n_hash = np.asarray(sig).shape
+    off = ei != ej
+    ei, ej, w = ei[off].astype(np.int64), ej[off].astype(np.int64), w[off]
+    r, c, v = np.concatenate([ei, ej]), np.concatenate([ej, ei]), np.concatenate([w, w])
+    order = np.lexsort((c, -v, r))               # row, then value descending (= count descending: one divide), then column ascending
+    r, c, v = r[order], c[order], v[order]
+    start = np.searchsorted(r, np.arange(n))
+    rank = np.arange(len(r)) - start[r]
+    keep = rank < top
+    idx = np.full((n, top), -1, np.int32)
+    val = np.zeros((n, top), np.float64)
+    idx[r[keep], rank[keep]] = c[keep]
+    val[r[keep], rank[keep]] = v[keep]
+    return idx, val
+
+
 def lsh_collision_probability(s, bands, rows):
     """P(two sequences of MinHash similarity ``s`` agree in at least one of ``bands`` bands of ``rows`` hash functions)
     = 1 - (1 - s^rows)^bands: the S-curve to choose bands and rows by."""

@@ -54,7 +54,8 @@ extern "C" {
  * (the exact-Jaccard entry points -- da_similarity_jaccard[_cross[_topk] | _knn | _edges[_begin]], da_dev_jaccard_sets[_ld], da_dev_jaccard_rect -- likewise)
  * (their _long forms -- da_similarity_jaccard[_cross[_topk | _edges] | _knn | _edges | _stats]_long[_begin], da_jaccard_sets_long_ld,
  *  da_dev_jaccard_sets_long, da_dev_jaccard_rect_long -- likewise)
- * (the LSH entry points -- da_similarity_mh_lsh_edges_begin, da_mh_lsh_last_route, da_dev_lsh_[band_keys | verify_pairs | edges | workspace_bytes] -- likewise)
+ * (the LSH entry points -- da_similarity_mh_lsh_edges_begin, da_similarity_mh_lsh_knn, da_mh_lsh_last_route,
+ *  da_dev_lsh_[band_keys | verify_pairs | edges | knn | knn_select | workspace_bytes] -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1087,6 +1088,30 @@ int da_dev_lsh_verify_pairs(const uint32_t *d_sig, int64_t n, int64_t ld_sig, in
 int da_dev_lsh_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold,
                      int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_count,
                      int64_t capacity, int64_t *n_edges_out, void *stream);
+/* Nearest-neighbour lists from the same candidates: row i lists the first `top` (1 .. 1024, NOT clamped to n - 1) members of
+ *     { j != i : cand(i, j) and (double)c / (double)n_hash >= threshold }   by c descending, then j ascending;
+ * a row with fewer candidates is padded with index -1 / value 0.0 (count 0).  A real entry has c >= rows >= 1, so a value > 0 marks
+ * exactly the real entries.  EXACT with respect to this definition; a true nearest neighbour that agrees in no whole band is missing.
+ * n = 1 is valid (one row of padding).
+ *
+ * da_similarity_mh_lsh_knn: host boundary; idx_out int32 (n, top), val_out float64 (n, top) = c / n_hash.  Checks everything
+ *   da_similarity_mh_lsh_edges_begin checks, in its order and with its texts, through max_candidates; then top outside 1 .. 1024
+ *   (DA_ERR_BAD_ARG); then n_hash > 65535 (DA_ERR_UNSUPPORTED).  max_candidates as above.  da_mh_lsh_last_route reports this call too:
+ *   buckets, incidences and verified pairs as above, `edges` = the real list entries written, the sum of min(candidates of row i, top).
+ * da_dev_lsh_knn: the whole pipeline on resident signatures into d_idx int32 (n, top) and d_key uint16 (n, top) (the counts c; padding
+ *   -1 / 0), both with leading dimension top.  d_work: da_dev_lsh_workspace_bytes(n, bands) bytes (the per-incidence and per-entry
+ *   buffers are allocated inside).  Synchronises the stream.  n * bands must stay below 2^31 - 256.
+ * da_dev_lsh_knn_select: the selection alone, on a caller's ragged rows: row r's entries are d_col / d_count [d_ptr[r], d_ptr[r + 1]),
+ *   d_ptr int64 [n + 1], columns >= 0 and distinct within a row, in any order.  d_idx[r * ld_idx + t], d_key[r * ld_key + t] for t < top get
+ *   the row's first `top` entries by (count descending, column ascending), then -1 / 0; columns >= top of the outputs are not touched.
+ *   A row whose pointers run backwards or past nnz is cut to what lies inside [0, nnz): a wrong list, never an access out of bounds.
+ *   Asynchronous on `stream`, no workspace. */
+int da_similarity_mh_lsh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                             int rows, double threshold, int top, int64_t max_candidates, int32_t *idx_out, double *val_out);
+int da_dev_lsh_knn(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int top,
+                   int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key, void *stream);
+int da_dev_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top,
+                          int32_t *d_idx, int64_t ld_idx, uint16_t *d_key, int64_t ld_key, void *stream);
 
 /* name -> id for da_dev_nw; -1 + DA_ERR_BAD_MATRIX message when unknown. */
 int da_matrix_id(const char *matrix_name);
