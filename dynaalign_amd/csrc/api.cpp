@@ -3747,6 +3747,304 @@ int da_mh_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t 
   return DA_OK;
 }
 
+// ---- MinHash LSH banding for two sets: a resident index probed by query batches (lsh_cross_kernels.hip) -------------------------------------
+}  // extern "C"  (reopened below)
+namespace {
+int lsh_elements_check(const char *what, int64_t n, int bands) {
+  if (n > 0x7ffffff0LL || n * (int64_t)bands > LSH_MAX_ELEMENTS)
+    return fail(DA_ERR_UNSUPPORTED, "lsh: %s * bands = %lld (sequence, band) elements, at most %lld in one call", what, (long long)(n * (int64_t)bands),
+                (long long)LSH_MAX_ELEMENTS);
+  return DA_OK;
+}
+// one resident signature matrix of the device calls
+int lsh_sig_check(const void *d_sig, int64_t rows_of, int64_t ld, int n_hash, const char *ld_name) {
+  if (rows_of < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (n_hash <= 0) return fail(DA_ERR_BAD_NHASH, "%s", da_status_message(DA_ERR_BAD_NHASH));
+  if (!d_sig) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (ld < n_hash) return fail(DA_ERR_BAD_ARG, "%s (%lld) < n_hash (%d)", ld_name, (long long)ld, n_hash);
+  return DA_OK;
+}
+int lsh_index_check(const void *d_index, size_t index_bytes, int64_t n, int bands) {
+  int rc;
+  if ((rc = lsh_elements_check("n", n, bands)) != DA_OK) return rc;
+  if (!d_index) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (index_bytes < lsh_index_bytes(n, bands))
+    return fail(DA_ERR_BAD_ARG, "lsh: index too small (%zu bytes, %zu needed)", index_bytes, lsh_index_bytes(n, bands));
+  return DA_OK;
+}
+int lsh_index_mismatch(int64_t n, int bands, int rows) {
+  return fail(DA_ERR_BAD_ARG, "lsh: the index was not built for n = %lld, bands = %d, rows = %d", (long long)n, bands, rows);
+}
+// x, y, the banding and the index of the device calls that run the pipeline
+int lsh_cross_dev_check(const void *d_index, size_t index_bytes, const void *d_sig_x, int64_t m, int64_t ld_x, const void *d_sig_y, int64_t n, int64_t ld_y,
+                        int n_hash, int bands, int rows, double threshold, int64_t max_candidates, const int *top = nullptr) {
+  int rc;
+  if (m <= 0 || n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_sig_check(d_sig_x, m, ld_x, n_hash, "ld_x")) != DA_OK || (rc = lsh_sig_check(d_sig_y, n, ld_y, n_hash, "ld_y")) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, threshold, max_candidates, top)) != DA_OK) return rc;
+  if ((rc = lsh_elements_check("m", m, bands)) != DA_OK) return rc;
+  return lsh_index_check(d_index, index_bytes, n, bands);
+}
+
+// The index of resident signatures into d_index (lsh_index_bytes(n, bands) bytes).  Synchronises: the scratch goes back to the cache.
+int lsh_index_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_index, hipStream_t stream) {
+  int rc;
+  DevBuf scratch;
+  const StreamDrain drain{stream};
+  if ((rc = scratch.alloc(lsh_index_build_scratch_bytes(n, bands))) != DA_OK) return rc;
+  if ((rc = lsh_index_build(d_sig, n, ld_sig, bands, rows, d_index, scratch.p, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  return DA_OK;
+}
+
+// Probe and verify, what the edge list and the lists share: the route's counts, the cap, the verdict of every incidence slot (cnt, keep),
+// the kept slots per chunk of 64 and their exclusive sum (coff); `kept` and `firsts` are read back, so the stream is synchronised.
+struct LshCrossVerdicts {
+  DevBuf cnt, keep, ckept, coff, distinct, temp;
+  LshCrossSlots slots{};
+  int64_t inc = 0, kept = 0;
+  uint64_t firsts = 0;
+};
+int lsh_cross_verdicts(const void *d_index, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash,
+                       int bands, int rows, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, LshCrossVerdicts &v,
+                       hipStream_t stream) {
+  int rc;
+  uint32_t stats[3] = {0, 0, 0};
+  if ((rc = lsh_cross_probe(d_index, n, d_sig_x, m, ld_x, bands, rows, d_work, work_bytes, &v.slots, stats, &v.inc, stream)) != DA_OK) return rc;
+  if (stats[2]) return lsh_index_mismatch(n, bands, rows);
+  LshRoute &route = lsh_route();
+  route = LshRoute();
+  route.buckets = stats[1];
+  route.incidences = v.inc;
+  if (v.inc > max_candidates)
+    return fail(DA_ERR_UNSUPPORTED, "lsh: %lld (pair, band) candidates exceed max_candidates = %lld (largest bucket: %u sequences); use more rows per band",
+                (long long)v.inc, (long long)max_candidates, stats[0]);
+  const int64_t chunks = ceil_div(v.inc, 64);
+  if (chunks + 1 > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld candidates are more than one call verifies", (long long)v.inc);
+  const size_t scan_b = lsh_chunk_scan_bytes(v.inc);
+  if ((rc = v.cnt.alloc((size_t)v.inc * 2)) != DA_OK || (rc = v.keep.alloc((size_t)v.inc)) != DA_OK || (rc = v.ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
+      (rc = v.coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = v.distinct.alloc(8)) != DA_OK || (rc = v.temp.alloc(scan_b)) != DA_OK) return rc;
+  if ((rc = launch_lsh_cross_verify_enumerated(d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, rows, lsh_c_min(n_hash, threshold), v.slots, v.inc,
+                                               v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.ckept.as<int64_t>(), v.coff.as<int64_t>(),
+                                               v.distinct.as<uint64_t>(), v.temp.p, scan_b, stream)) != DA_OK)
+    return rc;
+  DA_HIP_TRY(hipMemcpyAsync(&v.kept, v.coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipMemcpyAsync(&v.firsts, v.distinct.p, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  v.temp.release();
+  return DA_OK;
+}
+// The edge pipeline on resident signatures and a built index.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.
+int lsh_cross_edges_device(const void *d_index, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y,
+                           int n_hash, int bands, int rows, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, DevBuf &key,
+                           DevBuf &val, int64_t *edges_out, hipStream_t stream) {
+  int rc;
+  LshCrossVerdicts v;
+  DevBuf temp, key_in, val_in;
+  const StreamDrain drain{stream};
+  if ((rc = lsh_cross_verdicts(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v,
+                               stream)) != DA_OK) return rc;
+  const int64_t edges = v.kept;
+  if (edges > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld edges are more than one call sorts", (long long)edges);
+  if (edges > 0) {
+    const size_t sort_b = lsh_edge_sort_bytes(edges);
+    if ((rc = key_in.alloc((size_t)edges * 8)) != DA_OK || (rc = val_in.alloc((size_t)edges * 2)) != DA_OK || (rc = key.alloc((size_t)edges * 8)) != DA_OK ||
+        (rc = val.alloc((size_t)edges * 2)) != DA_OK || (rc = temp.alloc(sort_b)) != DA_OK) return rc;
+    if ((rc = launch_lsh_cross_emit_sort(v.slots, m, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.coff.as<int64_t>(), edges, key_in.as<uint64_t>(),
+                                         val_in.as<uint16_t>(), key.as<uint64_t>(), val.as<uint16_t>(), temp.p, sort_b, stream)) != DA_OK) return rc;
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+  }
+  LshRoute &route = lsh_route();
+  route.verified = (int64_t)v.firsts;
+  route.edges = edges;
+  *edges_out = edges;
+  return DA_OK;
+}
+// The list pipeline: the verdicts, then the x rows' entries and the selection into d_idx / d_key ((m, top), leading dimension top).
+int lsh_cross_topk_device(const void *d_index, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y,
+                          int n_hash, int bands, int rows, double threshold, int top, int64_t max_candidates, void *d_work, size_t work_bytes,
+                          int32_t *d_idx, uint16_t *d_key, hipStream_t stream) {
+  int rc;
+  LshCrossVerdicts v;
+  DevBuf temp, cursor, ptr, col, ecnt, written;
+  const StreamDrain drain{stream};
+  if ((rc = lsh_cross_verdicts(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v,
+                               stream)) != DA_OK) return rc;
+  const int64_t entries = v.kept;                // one direction: the x rows
+  const size_t scan_b = lsh_knn_scan_bytes(m);
+  if ((rc = cursor.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = ptr.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = col.alloc((size_t)entries * 4)) != DA_OK ||
+      (rc = ecnt.alloc((size_t)entries * 2)) != DA_OK || (rc = written.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
+  if ((rc = launch_lsh_cross_knn_entries(v.slots, m, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), entries, top, cursor.as<int64_t>(),
+                                         ptr.as<int64_t>(), col.as<int32_t>(), ecnt.as<uint16_t>(), written.as<uint64_t>(), temp.p, scan_b, stream)) != DA_OK ||
+      (rc = launch_lsh_knn_select(ptr.as<int64_t>(), entries, col.as<int32_t>(), ecnt.as<uint16_t>(), m, top, d_idx, top, d_key, top, stream)) != DA_OK)
+    return rc;
+  uint64_t entries_written = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&entries_written, written.p, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  LshRoute &route = lsh_route();
+  route.verified = (int64_t)v.firsts;
+  route.edges = (int64_t)entries_written;
+  return DA_OK;
+}
+// what both two-set LSH host calls check before a device is needed: x empty, y empty, k, n_hash, pointers, the offsets of x, then of y, the banding
+int lsh_cross_host_validate(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+                            int k, int n_hash, const uint32_t *seeds, const void *out1, const void *out2, int bands, int rows, double threshold,
+                            int64_t max_candidates, const int *top, int64_t *x_total, int64_t *y_total) {
+  int rc;
+  if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
+  if (!x_residues || !y_residues || !seeds || !out1 || !out2) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t max_len;
+  if ((rc = check_offsets(x_offsets, m, x_total, &max_len)) != DA_OK || (rc = check_offsets(y_offsets, n, y_total, &max_len)) != DA_OK) return rc;
+  return lsh_arg_check(n_hash, bands, rows, threshold, max_candidates, top);
+}
+// The host calls' device side up to the index: both sets uploaded, their signatures, the index of y and the probe workspace.
+struct LshCrossHost {
+  MhPlanes x, y;
+  DevBuf index, work;
+  size_t wb = 0;
+  int prepare(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, int64_t x_total, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
+              int64_t y_total, int k, int n_hash, const uint32_t *seeds, int bands, int rows) {
+    int rc;
+    if ((rc = lsh_elements_check("m", m, bands)) != DA_OK || (rc = lsh_elements_check("n", n, bands)) != DA_OK) return rc;
+    if ((rc = x.in.upload(x_residues, x_offsets, m, x_total, seeds, n_hash)) != DA_OK || (rc = y.in.upload(y_residues, y_offsets, n, y_total, seeds, n_hash)) != DA_OK)
+      return rc;
+    if ((rc = x.alloc(m, n_hash, false)) != DA_OK || (rc = x.signatures(k, 0, n_hash)) != DA_OK || (rc = y.alloc(n, n_hash, false)) != DA_OK ||
+        (rc = y.signatures(k, 0, n_hash)) != DA_OK) return rc;
+    wb = lsh_cross_workspace_bytes(m, bands);
+    if ((rc = index.alloc(lsh_index_bytes(n, bands))) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+    return lsh_index_device(y.sig.as<uint32_t>(), n, y.lds, bands, rows, index.p, nullptr);
+  }
+};
+}  // namespace
+extern "C" {
+
+size_t da_dev_lsh_index_bytes(int64_t n, int bands) { return lsh_index_bytes(n, bands); }
+size_t da_dev_lsh_cross_workspace_bytes(int64_t m, int bands) { return lsh_cross_workspace_bytes(m, bands); }
+
+int da_dev_lsh_index_build(const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands, int rows, void *d_index, size_t index_bytes,
+                           void *stream) {
+  int rc;
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_sig_check(d_sig_y, n, ld_y, n_hash, "ld_y")) != DA_OK || (rc = lsh_arg_check(n_hash, bands, rows, 0.0, 0)) != DA_OK) return rc;
+  if ((rc = lsh_index_check(d_index, index_bytes, n, bands)) != DA_OK) return rc;
+  return lsh_index_device(d_sig_y, n, ld_y, bands, rows, d_index, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_index_probe(const void *d_index, size_t index_bytes, int64_t n, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, int n_hash, int bands,
+                           int rows, int32_t *d_lo, int32_t *d_len, void *stream_v) {
+  int rc;
+  if (m <= 0 || n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_sig_check(d_sig_x, m, ld_x, n_hash, "ld_x")) != DA_OK || (rc = lsh_arg_check(n_hash, bands, rows, 0.0, 0)) != DA_OK) return rc;
+  if ((rc = lsh_elements_check("m", m, bands)) != DA_OK || (rc = lsh_index_check(d_index, index_bytes, n, bands)) != DA_OK) return rc;
+  if (!d_lo || !d_len) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  DevBuf stats;
+  const StreamDrain drain{stream};
+  if ((rc = stats.alloc(16)) != DA_OK) return rc;
+  int mismatch = 0;
+  if ((rc = lsh_index_probe_listed(d_index, n, d_sig_x, m, ld_x, bands, rows, d_lo, d_len, stats.as<uint32_t>(), &mismatch, stream)) != DA_OK) return rc;
+  return mismatch ? lsh_index_mismatch(n, bands, rows) : DA_OK;
+}
+
+int da_dev_lsh_cross_verify_pairs(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands,
+                                  int rows, double threshold, const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t n_triples,
+                                  uint16_t *d_count, uint8_t *d_keep, void *stream) {
+  int rc;
+  if ((rc = lsh_sig_check(d_sig_x, m, ld_x, n_hash, "ld_x")) != DA_OK || (rc = lsh_sig_check(d_sig_y, n, ld_y, n_hash, "ld_y")) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, threshold, 0)) != DA_OK) return rc;
+  if (n_triples < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (n_triples > 0 && (!d_i || !d_j || !d_band || !d_count || !d_keep)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_lsh_cross_verify_listed(d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_i, d_j, d_band, n_triples,
+                                        d_count, d_keep, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_cross_edges(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n,
+                           int64_t ld_y, int n_hash, int bands, int rows, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes,
+                           int32_t *d_i, int32_t *d_j, uint16_t *d_count, int64_t capacity, int64_t *n_edges_out, void *stream_v) {
+  int rc;
+  if ((rc = lsh_cross_dev_check(d_index, index_bytes, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates)) != DA_OK) return rc;
+  if (!n_edges_out || !d_work) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (capacity < 0) return fail(DA_ERR_BAD_ARG, "negative capacity");
+  if (capacity > 0 && (!d_i || !d_j || !d_count)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  DevBuf key, val;
+  const StreamDrain drain{stream};
+  int64_t edges = 0;
+  if ((rc = lsh_cross_edges_device(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, key, val,
+                                   &edges, stream)) != DA_OK) return rc;
+  if ((rc = launch_lsh_split(key.as<uint64_t>(), val.as<uint16_t>(), std::min(edges, capacity), d_i, d_j, d_count, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  *n_edges_out = edges;
+  return DA_OK;
+}
+
+int da_dev_lsh_cross_topk(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n,
+                          int64_t ld_y, int n_hash, int bands, int rows, double threshold, int top, int64_t max_candidates, void *d_work, size_t work_bytes,
+                          int32_t *d_idx, uint16_t *d_key, void *stream) {
+  int rc;
+  if ((rc = lsh_cross_dev_check(d_index, index_bytes, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, &top)) != DA_OK)
+    return rc;
+  if (!d_work || !d_idx || !d_key) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return lsh_cross_topk_device(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, top, max_candidates, d_work, work_bytes, d_idx,
+                               d_key, static_cast<hipStream_t>(stream));
+}
+
+int da_similarity_mh_lsh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                           const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
+                                           double threshold, int64_t max_candidates, da_edges **handle_out, int64_t *n_edges_out) {
+  int rc;
+  int64_t x_total, y_total;
+  if ((rc = lsh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, handle_out, n_edges_out, bands, rows, threshold,
+                                    max_candidates, nullptr, &x_total, &y_total)) != DA_OK) return rc;
+  *handle_out = nullptr;
+  if ((rc = require_device()) != DA_OK) return rc;
+  LshCrossHost h;
+  DevBuf key, val;
+  const StreamDrain drain{nullptr};
+  if ((rc = h.prepare(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, k, n_hash, seeds, bands, rows)) != DA_OK) return rc;
+  int64_t edges = 0;
+  if ((rc = lsh_cross_edges_device(h.index.p, h.x.sig.as<uint32_t>(), m, h.x.lds, h.y.sig.as<uint32_t>(), n, h.y.lds, n_hash, bands, rows, threshold,
+                                   max_candidates, h.work.p, h.wb, key, val, &edges, nullptr)) != DA_OK) return rc;
+  std::unique_ptr<da_edges> out(new da_edges);
+  std::vector<uint64_t> hk((size_t)edges);
+  std::vector<uint16_t> hv((size_t)edges);
+  if (edges > 0) {
+    DA_HIP_TRY(hipMemcpy(hk.data(), key.p, (size_t)edges * 8, hipMemcpyDeviceToHost));
+    DA_HIP_TRY(hipMemcpy(hv.data(), val.p, (size_t)edges * 2, hipMemcpyDeviceToHost));
+  }
+  const std::vector<double> values = mh_code_values(n_hash);
+  EdgeSet &es = out->es;
+  es.threshold = threshold;
+  es.i.resize((size_t)edges); es.j.resize((size_t)edges); es.w.resize((size_t)edges);
+  for (size_t e = 0; e < (size_t)edges; ++e) {
+    es.i[e] = (int32_t)(hk[e] >> 32);
+    es.j[e] = (int32_t)(hk[e] & 0xFFFFFFFFull);
+    es.w[e] = values[hv[e]];
+  }
+  out->n_edges = edges;
+  *n_edges_out = edges;
+  *handle_out = out.release();
+  return DA_OK;
+}
+
+int da_similarity_mh_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                    int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows, double threshold, int top,
+                                    int64_t max_candidates, int32_t *idx_out, double *val_out) {
+  int rc;
+  int64_t x_total, y_total;
+  if ((rc = lsh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, idx_out, val_out, bands, rows, threshold,
+                                    max_candidates, &top, &x_total, &y_total)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  LshCrossHost h;
+  DevBuf didx, dkey;
+  const StreamDrain drain{nullptr};
+  if ((rc = h.prepare(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, k, n_hash, seeds, bands, rows)) != DA_OK) return rc;
+  if ((rc = didx.alloc((size_t)m * (size_t)top * sizeof(int32_t))) != DA_OK || (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  if ((rc = lsh_cross_topk_device(h.index.p, h.x.sig.as<uint32_t>(), m, h.x.lds, h.y.sig.as<uint32_t>(), n, h.y.lds, n_hash, bands, rows, threshold, top,
+                                  max_candidates, h.work.p, h.wb, didx.as<int32_t>(), dkey.as<uint16_t>(), nullptr)) != DA_OK) return rc;
+  return topk_to_host(didx, dkey, m, top, mh_code_values(n_hash), idx_out, val_out);
+}
+
 
 // ---- NW threshold form for sequences of up to 1024 residues: 32-bit keys (nw_edges_long_kernels.hip) ------------------------------------------
 // The value table of the PACK32 codes (matches << 16 | length) of sequences up to max_len residues: the distinct doubles

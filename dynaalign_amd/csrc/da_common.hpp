@@ -421,6 +421,49 @@ int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int
                            uint16_t *d_cnt, uint64_t *d_written, void *d_temp, size_t temp_bytes, hipStream_t stream);
 int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
                           int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream);
+int launch_lsh_knn_written(const int64_t *d_ptr, int64_t n, int64_t nnz, int top, uint64_t *d_written, hipStream_t stream);
+// lsh_cross_kernels.hip: the two-set form (da_dev_lsh_index_*, da_dev_lsh_cross_*).  The INDEX of a resident set y is its sorted (band key, id)
+// elements with a table of where every band starts (layout: include/dynaalign.h); nothing in it depends on the queries.  A query batch x
+// PROBES it: element q = i * bands + t finds the run of its key, lo[q] / len[q]; the exclusive sum of len numbers the (pair, band)
+// incidences (LshCrossSlots); they are verified against BOTH signature matrices, and the kept ones become a sorted edge list or the ragged
+// rows of the x sequences that launch_lsh_knn_select takes.
+struct LshIndexView {
+  const uint32_t *meta, *band_start;
+  const uint64_t *keys;
+  const int32_t *ids;
+};
+struct LshCrossSlots {
+  const int64_t *off;     // [m * bands + 1]: the exclusive sum of len
+  const uint32_t *lo;     // [m * bands]: where the run of element q starts in ids
+  const int32_t *ids;     // the index's sorted ids
+  int64_t elements;       // m * bands
+  int bands;
+};
+size_t lsh_index_bytes(int64_t n, int bands);
+LshIndexView lsh_index_view(const void *d_index, int64_t n, int bands);
+size_t lsh_index_build_scratch_bytes(int64_t n, int bands);
+int lsh_index_build(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_index, void *d_scratch, hipStream_t stream);
+size_t lsh_cross_workspace_bytes(int64_t m, int bands);
+// probe into caller arrays (d_lo / d_len int32 [m * bands]; d_stats: 16 bytes of scratch); *mismatch_host = 1 when the index was built for
+// another (n, bands, rows).  Synchronises.
+int lsh_index_probe_listed(const void *d_index, int64_t n, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, int bands, int rows, int32_t *d_lo,
+                           int32_t *d_len, uint32_t *d_stats, int *mismatch_host, hipStream_t stream);
+// probe + exclusive sum inside the workspace; reads back stats_host = {largest probed run, runs of the index, mismatch} and the incidences
+int lsh_cross_probe(const void *d_index, int64_t n, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, int bands, int rows, void *d_work, size_t work_bytes,
+                    LshCrossSlots *slots_out, uint32_t stats_host[3], int64_t *incidences_host, hipStream_t stream);
+int launch_lsh_cross_verify_listed(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands,
+                                   int rows, uint32_t c_min, const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t triples,
+                                   uint16_t *d_count, uint8_t *d_keep, hipStream_t stream);
+int launch_lsh_cross_verify_enumerated(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash,
+                                       int rows, uint32_t c_min, const LshCrossSlots &slots, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
+                                       int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes,
+                                       hipStream_t stream);
+int launch_lsh_cross_emit_sort(const LshCrossSlots &slots, int64_t m, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
+                               const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in, uint64_t *d_key_out,
+                               uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
+int launch_lsh_cross_knn_entries(const LshCrossSlots &slots, int64_t m, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep, int64_t entries,
+                                 int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
+                                 size_t temp_bytes, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

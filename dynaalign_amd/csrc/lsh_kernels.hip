@@ -16,27 +16,10 @@
 //   4. one radix sort of the 64-bit keys (count as payload) puts the list, diagonal included, in (i, j) order; k_lsh_split unpacks it.
 // The same verify kernel runs on LISTED triples (da_dev_lsh_verify_pairs), so that the per-pair decision can be tested on triples the
 // pipeline never produces (a key collision, a pair of an earlier band).
-#include "da_common.hpp"
-
-#include <algorithm>
-
-#include <hipcub/hipcub.hpp>
+#include "lsh_common.hpp"
 
 namespace da {
 namespace {
-
-constexpr int LSH_THREADS = 256;
-constexpr int LSH_BAND_SHIFT = 48;            // key = band << 48 | hash >> 16
-
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-inline unsigned lsh_grid(int64_t items) { return (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div(items, LSH_THREADS), 1), 256 * 32); }
-
-// the finaliser of splitmix64: every input bit reaches every output bit
-__device__ __forceinline__ uint64_t lsh_mix(uint64_t x) {
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 // Consecutive threads take consecutive bands of one row: a wave reads one stretch of the row and writes one stretch of keys / ids.
 // Only columns < bands * rows are read.
@@ -46,10 +29,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_band_keys(const uint32_t *_
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
     const int64_t i = q / bands;
     const int t = (int)(q - i * bands);
-    const uint32_t *v = sig + i * ld_sig + (int64_t)t * rows;
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    for (int c = 0; c < rows; ++c) h = lsh_mix(h + v[c]) + 0x9E3779B97F4A7C15ull;
-    keys[q] = ((unsigned long long)t << LSH_BAND_SHIFT) | (h >> (64 - LSH_BAND_SHIFT));
+    keys[q] = lsh_band_key(sig + i * ld_sig + (int64_t)t * rows, rows, t);
     ids[q] = (int32_t)i;
   }
 }
@@ -84,44 +64,6 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_partner_counts(const uint32
   }
   for (int o = 32; o > 0; o >>= 1) longest = max(longest, (uint32_t)__shfl_down(longest, o));
   if ((threadIdx.x & 63) == 0 && longest) atomicMax(&stats[0], longest);
-}
-
-// ---- the per-pair decision --------------------------------------------------------------------------------------------------------------
-struct LshVerdict {
-  uint32_t count;   // columns h < n_hash with ri[h] == rj[h]
-  bool first;       // `band` agrees in all its columns and no earlier band does
-};
-// Called by a whole wave with wave-uniform arguments; lane l holds column h0 + l of a chunk of 64.  band_cols = bands * rows: the columns
-// behind belong to no band but count.  A band agrees when the run of equal columns ending at its last column is at least `rows` long; the
-// run is measured inside the chunk from the ballot of mismatches and continued into the chunks before by `tail`, the number of equal
-// columns they end with.  Only the first agreeing band is looked for: the candidate (i, j, band) is that pair's own when it is `band`.
-__device__ __forceinline__ LshVerdict lsh_pair_decide(const uint32_t *__restrict__ ri, const uint32_t *__restrict__ rj, int n_hash, int band_cols, int rows,
-                                                      int band) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long upto = (2ull << lane) - 1;   // my column and those below it in the chunk
-  const int step = 64 % rows;
-  int pos = lane % rows;                                // position of my column in its band
-  int tail = 0, first_end = -1;
-  uint32_t count = 0;
-  for (int h0 = 0; h0 < n_hash; h0 += 64) {
-    const int h = h0 + lane;
-    const bool eq = h < n_hash && ri[h] == rj[h];
-    const unsigned long long equal = __ballot(eq);
-    count += (uint32_t)__popcll(equal);
-    if (first_end < 0 && h0 < band_cols) {
-      const unsigned long long below = ~equal & upto;
-      const int run = below ? lane - 63 + __clzll((long long)below) : lane + 1 + tail;
-      const unsigned long long agree = __ballot(pos == rows - 1 && h < band_cols && run >= rows);
-      if (agree) first_end = h0 + __ffsll((long long)agree) - 1;
-    }
-    tail = ~equal ? __clzll((long long)~equal) : tail + 64;
-    pos += step;
-    if (pos >= rows) pos -= rows;
-  }
-  LshVerdict v;
-  v.count = count;
-  v.first = first_end == band * rows + rows - 1;
-  return v;
 }
 
 // ---- where the triples of the verify kernel come from: lane-level get(slot) ----------------------------------------------------------------
@@ -222,35 +164,6 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_split(const unsigned long l
   }
 }
 
-int bits_for(int64_t values) {   // bits that hold 0 .. values - 1
-  int b = 1;
-  while (b < 63 && ((int64_t)1 << b) < values) ++b;
-  return b;
-}
-
-size_t sort_u64_i32_bytes(int64_t items) {
-  size_t t = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const int32_t *)nullptr,
-                                           (int32_t *)nullptr, (int)items, 0, 64, nullptr);
-  return t;
-}
-size_t sort_u64_u16_bytes(int64_t items) {
-  size_t t = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, t, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (const uint16_t *)nullptr,
-                                           (uint16_t *)nullptr, (int)items, 0, 64, nullptr);
-  return t;
-}
-size_t scan_u32_bytes(int64_t items) {
-  size_t t = 0;
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, t, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)items, nullptr);
-  return t;
-}
-size_t scan_i64_bytes(int64_t items) {
-  size_t t = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, t, (const long long *)nullptr, (long long *)nullptr, (int)items, nullptr);
-  return t;
-}
-
 // the bucket workspace of `total` = n * bands elements, cut into its arrays
 struct BucketLayout {
   size_t keys_in, keys_out, ids_in, ids_out, start, cnt, off, stats, temp, temp_bytes, bytes;
@@ -271,8 +184,6 @@ struct BucketLayout {
     bytes = at + 256;
   }
 };
-
-template <typename T> T *at_bytes(void *base, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
 
 }  // namespace
 
@@ -416,10 +327,6 @@ constexpr int LSH_KNN_LDS_WORDS = 2048;
 constexpr int LSH_KNN_TILE = LSH_THREADS;
 static_assert(DA_TOPK_MAX <= LSH_KNN_LDS_WORDS, "the candidates of the radix path are sorted in the same buffer");
 
-__device__ __forceinline__ unsigned long long lsh_shfl64(unsigned long long v, int src) {
-  const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src);
-  return ((unsigned long long)hi << 32) | lo;
-}
 __device__ __forceinline__ unsigned long long lsh_shfl_xor64(unsigned long long v, int mask) {
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
   return ((unsigned long long)hi << 32) | lo;
@@ -647,6 +554,14 @@ int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_co
 // scratch of the scan over n + 1 degrees
 size_t lsh_knn_scan_bytes(int64_t n) { return up256(scan_i64_bytes(n + 1)) + 256; }
 
+// *d_written += the sum of min(degree, top) over the n rows of d_ptr
+int launch_lsh_knn_written(const int64_t *d_ptr, int64_t n, int64_t nnz, int top, uint64_t *d_written, hipStream_t stream) {
+  hipLaunchKernelGGL(k_lsh_knn_written, dim3(lsh_grid(n)), dim3(LSH_THREADS), 0, stream, reinterpret_cast<const long long *>(d_ptr), n, nnz, top,
+                     reinterpret_cast<unsigned long long *>(d_written));
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
 // Steps 5 and 6 on the verdicts of launch_lsh_verify_enumerated: d_ptr[n + 1] = the row pointers of the directed entries (2 per kept slot),
 // d_col / d_cnt their columns and counts; d_cursor (n + 1 words) is scratch.  *d_written (zeroed here) = the sum of min(degree, top).
 int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
@@ -670,10 +585,7 @@ int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int
     hipLaunchKernelGGL(k_lsh_knn_entries<true>, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, d_col, d_cnt);
     DA_HIP_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_lsh_knn_written, dim3(lsh_grid(n)), dim3(LSH_THREADS), 0, stream, reinterpret_cast<const long long *>(d_ptr), n, entries, top,
-                     reinterpret_cast<unsigned long long *>(d_written));
-  DA_HIP_TRY(hipGetLastError());
-  return DA_OK;
+  return launch_lsh_knn_written(d_ptr, n, entries, top, d_written, stream);
 }
 
 }  // namespace da

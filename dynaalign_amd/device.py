@@ -926,6 +926,128 @@ def lsh_knn(sig, n_hash, bands, rows, top, threshold=0.0, max_candidates=1 << 32
     return idx[:n], key[:n]
 
 
+def lsh_index_bytes(n, bands):
+    return int(_capi.load().da_dev_lsh_index_bytes(int(n), int(bands)))
+
+
+def lsh_cross_workspace_bytes(m, bands):
+    return int(_capi.load().da_dev_lsh_cross_workspace_bytes(int(m), int(bands)))
+
+
+def _byte_buffer(t, name, what):
+    _require_cuda(t, name)
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous uint8 tensor of %s bytes" % (name, what))
+    return t
+
+
+def lsh_index_build(sig_y, n_hash, bands, rows, out=None):
+    """The LSH bucket index of a resident set (da_dev_lsh_index_build): ``sig_y`` (n, >= n_hash) 32-bit -> a uint8 tensor of
+    lsh_index_bytes(n, bands) bytes holding the sorted band keys, their row ids and the band table (layout: include/dynaalign.h).  It
+    depends on nothing but sig_y, bands and rows, and any number of lsh_cross_edges / lsh_cross_topk / lsh_index_probe calls read it.
+    ``out``: a buffer to build into.  Synchronises the stream."""
+    lib = _capi.load()
+    n, ld = _sig_block(sig_y, n_hash)
+    if out is None:
+        out = torch.empty(lsh_index_bytes(n, bands), dtype=torch.uint8, device=sig_y.device)
+    _byte_buffer(out, "out", "lsh_index_bytes(n, bands)")
+    _call(lib.da_dev_lsh_index_build, sig_y.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), out.data_ptr(), out.numel(), _stream())
+    return out
+
+
+def lsh_index_arrays(index, n, bands):
+    """Views of a built index by the layout of include/dynaalign.h: (meta int32 (8), band_start int32 (bands + 1), keys int64 (n * bands),
+    ids int32 (n * bands)); unsigned values as their signed bit patterns."""
+    up = lambda b: -(-b // 256) * 256
+    total = int(n) * int(bands)
+    at = (-index.data_ptr()) % 256
+    out = []
+    for count, dtype, size in ((8, torch.int32, 4), (int(bands) + 1, torch.int32, 4), (total, torch.int64, 8), (total, torch.int32, 4)):
+        out.append(index[at:at + count * size].view(dtype))
+        at += up(count * size)
+    return tuple(out)
+
+
+def lsh_index_probe(index, n, sig_x, n_hash, bands, rows):
+    """The lookup of a query batch in a built index (da_dev_lsh_index_probe) -> (lo int32 (m, bands), len int32 (m, bands)): the rows of y
+    whose band t equals band t of x[i] are ``ids[lo[i, t]:lo[i, t] + len[i, t]]`` (``lsh_index_arrays``), ascending; len = 0 when there is
+    none.  The index is only read.  Synchronises the stream."""
+    lib = _capi.load()
+    m, ld = _sig_block(sig_x, n_hash)
+    _byte_buffer(index, "index", "lsh_index_bytes(n, bands)")
+    lo = torch.empty((max(m, 1), max(int(bands), 1)), dtype=torch.int32, device=sig_x.device)
+    ln = torch.empty_like(lo)
+    _call(lib.da_dev_lsh_index_probe, index.data_ptr(), index.numel(), int(n), sig_x.data_ptr(), m, ld, int(n_hash), int(bands), int(rows),
+          lo.data_ptr(), ln.data_ptr(), _stream())
+    return lo[:m], ln[:m]
+
+
+def lsh_cross_verify_pairs(sig_x, sig_y, n_hash, bands, rows, threshold, i, j, band):
+    """The per-pair decision of the two-set LSH pipeline on listed triples (da_dev_lsh_cross_verify_pairs), row i of sig_x against row j of
+    sig_y -> (count int16-as-uint16 tensor, keep uint8): keep = 1 when ``band`` agrees in all its columns, no earlier band does and
+    count / n_hash >= threshold."""
+    lib = _capi.load()
+    m, ld_x = _sig_block(sig_x, n_hash)
+    n, ld_y = _sig_block(sig_y, n_hash)
+    ti, tj, tb = ((a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, np.int32))).to(device=sig_x.device, dtype=torch.int32).contiguous()
+                  for a in (i, j, band))
+    if not ti.numel() == tj.numel() == tb.numel():
+        raise ValueError("i, j and band must have the same number of entries")
+    cnt = int(ti.numel())
+    count = torch.zeros(max(cnt, 1), dtype=torch.int16, device=sig_x.device)
+    keep = torch.zeros(max(cnt, 1), dtype=torch.uint8, device=sig_x.device)
+    _call(lib.da_dev_lsh_cross_verify_pairs, sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands), int(rows), float(threshold),
+          ti.data_ptr(), tj.data_ptr(), tb.data_ptr(), cnt, count.data_ptr(), keep.data_ptr(), _stream())
+    return count[:cnt], keep[:cnt]
+
+
+def _lsh_cross_operands(index, sig_x, sig_y, n_hash, bands, work):
+    m, ld_x = _sig_block(sig_x, n_hash)
+    n, ld_y = _sig_block(sig_y, n_hash)
+    _byte_buffer(index, "index", "lsh_index_bytes(n, bands)")
+    if work is None:
+        work = torch.empty(lsh_cross_workspace_bytes(m, bands), dtype=torch.uint8, device=sig_x.device)
+    _byte_buffer(work, "work", "lsh_cross_workspace_bytes(m, bands)")
+    return m, ld_x, n, ld_y, work
+
+
+def lsh_cross_edges(index, sig_x, sig_y, n_hash, bands, rows, threshold, max_candidates=1 << 32, capacity=None, work=None):
+    """The two-set LSH edge list of a query batch against an indexed resident set (da_dev_lsh_cross_edges): ``index`` =
+    lsh_index_build(sig_y, n_hash, bands, rows) -> (i int32, j int32, count int16-as-uint16), sorted by (i, j); weight = count / n_hash.
+    ``capacity=None``: a first call counts, a second one fills; an int: one call, and at most that many edges are returned
+    (``mh_lsh_last_route()["edges"]`` has the full number).  Synchronises the stream."""
+    lib = _capi.load()
+    m, ld_x, n, ld_y, work = _lsh_cross_operands(index, sig_x, sig_y, n_hash, bands, work)
+    got = ctypes.c_int64(0)
+
+    def run(cap, ti, tj, tc):
+        _call(lib.da_dev_lsh_cross_edges, index.data_ptr(), index.numel(), sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands),
+              int(rows), float(threshold), int(max_candidates), work.data_ptr(), work.numel(), ti, tj, tc, cap, ctypes.byref(got), _stream())
+    if capacity is None:
+        run(0, None, None, None)
+        capacity = got.value
+    capacity = int(capacity)
+    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig_x.device)
+    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig_x.device)
+    ec = torch.empty(max(capacity, 1), dtype=torch.int16, device=sig_x.device)
+    run(capacity, ei.data_ptr(), ej.data_ptr(), ec.data_ptr())
+    stored = min(got.value, capacity)
+    return ei[:stored], ej[:stored], ec[:stored]
+
+
+def lsh_cross_topk(index, sig_x, sig_y, n_hash, bands, rows, top, threshold=0.0, max_candidates=1 << 32, work=None):
+    """The two-set LSH nearest-neighbour lists (da_dev_lsh_cross_topk) -> (idx int32 (m, top), key int16 (m, top), the counts as uint16 bit
+    patterns; padding -1 / 0); value = count / n_hash (``widen``).  ``top`` is not clamped to the rows of sig_y.  Synchronises the stream."""
+    lib = _capi.load()
+    m, ld_x, n, ld_y, work = _lsh_cross_operands(index, sig_x, sig_y, n_hash, bands, work)
+    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    idx = torch.empty((max(m, 1), t), dtype=torch.int32, device=sig_x.device)
+    key = torch.empty((max(m, 1), t), dtype=torch.int16, device=sig_x.device)
+    _call(lib.da_dev_lsh_cross_topk, index.data_ptr(), index.numel(), sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands),
+          int(rows), float(threshold), int(top), int(max_candidates), work.data_ptr(), work.numel(), idx.data_ptr(), key.data_ptr(), _stream())
+    return idx[:m], key[:m]
+
+
 def mh_lsh_last_route():
     from .similarity import mh_lsh_last_route as route
     return route()

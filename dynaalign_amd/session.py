@@ -15,6 +15,8 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     thr, m, ptr, adj, codes, loops, values = s.knn_csr(idx, 10)     # the kNN graph of those lists as CSR (== similarityMH_knn_edges(...))
     thr, i, j, w = s.lsh_edges(12, 4, 0.5, idx)                     # == similarityMH_lsh_edges(sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) at n_hash = 48
     i, v = s.lsh_knn(12, 4, 10, idx)                                # == similarityMH_lsh_knn(sequences[idx], 4, 48, 12, 4, 10, seed=12345) at n_hash = 48
+    thr, ptr, j, w = s.lsh_cross_edges(new, 12, 4, 0.5, idx)        # == similarityMH_lsh_cross_edges(new, sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) as CSR
+    i, v = s.lsh_cross_topk(new, 12, 4, 10, idx)                    # == similarityMH_lsh_cross_topk(new, sequences[idx], 4, 48, 12, 4, 10, seed=12345)
     st = s.stats(idx)                                               # == similarityMH_stats(sequences[idx], 4, 500, seed=12345)
 
 The only difference to calling the reference per level is the random stream (the reference draws fresh
@@ -37,6 +39,7 @@ class MinHashSession:
         self.ds = device.DeviceSequences(res, off, device_name)
         # validation (order and messages of the reference) happens in the library call
         self.sig, _ = device.minhash_signatures(self.ds, self.k, self.n_hash, self.seeds, want_planes=False)
+        self._lsh_indexes = {}               # (bands, rows, idx is None) -> (idx, signatures, rows, index): lsh_index
         if reserve and self.n >= 2:
             # the first recursion level needs an n x n uint16 count matrix (20 GB at n = 100k) and a fresh hipMalloc of that size
             # costs 0.3 - 2.3 s depending on the box: take it here once, hand it to the caching allocator, and every level finds it
@@ -295,6 +298,62 @@ class MinHashSession:
         codes_h = codes.cpu().numpy().view(np.uint16)
         thr = float(values[int(codes_h.min())]) if len(codes_h) else float("nan")
         return thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes_h, loops.cpu().numpy().view(np.uint16), values
+
+    def _lsh_index_entry(self, bands, rows, idx):
+        """(signatures of the indexed rows, their number, the index) for lsh_index's key; an idx subset is kept until another one is asked for"""
+        bands, rows = int(bands), int(rows)
+        cache = self._lsh_indexes
+        key = (bands, rows, idx is None)
+        idx_h = None if idx is None else np.ascontiguousarray(idx, np.int64).copy()
+        kept = cache.get(key)
+        if kept is not None and (idx is None or np.array_equal(kept[0], idx_h)):
+            return kept[1:]
+        sig, n = self._subset(idx_h)
+        sig = sig[:n]
+        cache[key] = (idx_h, sig, n, device.lsh_index_build(sig, self.n_hash, bands, rows))
+        return cache[key][1:]
+
+    def lsh_index(self, bands, rows, idx=None):
+        """The LSH bucket index of the resident set (or its subset idx) for lsh_cross_edges / lsh_cross_topk: the device buffer of
+        device.lsh_index_build, built once per (bands, rows, idx is None) and kept -- a second query against the same session neither
+        rebuilds nor re-sorts it.  One subset index is kept per (bands, rows): asking for another idx replaces it."""
+        return self._lsh_index_entry(bands, rows, idx)[2]
+
+    def _query_signatures(self, sequences):
+        res, off = pack_sequences(sequences)
+        m = len(off) - 1
+        if m == 0:
+            _capi.check(_capi.DA_ERR_EMPTY_INPUT)
+        new = device.DeviceSequences(res, off, self.sig.device)
+        sig_new, _ = device.minhash_signatures(new, self.k, self.n_hash, self.seeds, want_planes=False)
+        return sig_new[:m], m
+
+    def lsh_cross_edges(self, sequences, bands, rows, threshold, idx=None, max_candidates=1 << 32):
+        """New sequences against the resident set (or its subset idx) through the kept LSH index, as CSR over the new sequences like
+        cross_edges: (threshold, rowptr, j, w) device tensors -- int64 (m + 1), int32 positions in idx (in the resident set when idx is
+        None), ascending within a row, and the float64 similarities -- of similarityMH_lsh_cross_edges(sequences, resident[idx], k, n_hash,
+        bands, rows, threshold, seed=self.seed).  A call is K1 on the new strings, a probe of the index and the compare of the pairs that
+        share a bucket."""
+        sig_y, n, index = self._lsh_index_entry(bands, rows, idx)
+        sig_x, m = self._query_signatures(sequences)
+        ei, ej, ec = device.lsh_cross_edges(index, sig_x, sig_y, self.n_hash, bands, rows, threshold, max_candidates=max_candidates)
+        rowptr = torch.zeros(m + 1, dtype=torch.int64, device=self.sig.device)
+        if ei.numel():
+            rowptr[1:] = torch.cumsum(torch.bincount(ei.to(torch.int64), minlength=m), 0)
+            w = device.widen(ec.contiguous(), False, self.n_hash)            # count / n_hash, the library's divide
+        else:
+            w = torch.empty(0, dtype=torch.float64, device=self.sig.device)
+        return float(threshold), rowptr, ej, w
+
+    def lsh_cross_topk(self, sequences, bands, rows, top=10, idx=None, threshold=0.0, max_candidates=1 << 32):
+        """``(idx, val)`` == similarityMH_lsh_cross_topk(sequences, resident[idx], k, n_hash, bands, rows, top, threshold=threshold,
+        seed=self.seed) through the kept LSH index: (m, top) int32 positions in idx and the (m, top) float64 values as cross_topk returns
+        them, but a row with fewer candidates is padded with -1 / 0.0 and ``top`` is not clamped to the number of columns."""
+        sig_y, n, index = self._lsh_index_entry(bands, rows, idx)
+        sig_x, m = self._query_signatures(sequences)
+        i, key = device.lsh_cross_topk(index, sig_x, sig_y, self.n_hash, bands, rows, top, threshold=threshold, max_candidates=max_candidates)
+        val = device.widen(key.contiguous(), False, self.n_hash)         # count / n_hash, the library's divide; the padding's 0 gives 0.0
+        return i.cpu().numpy(), val.cpu().numpy()
 
     def stats(self, idx=None):
         """compute_similarity_stats of the subset's similarity matrix without that matrix on the host (``SimilarityStats``, positions in

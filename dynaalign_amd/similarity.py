@@ -993,6 +993,102 @@ def lsh_knn_dense(sig, bands, rows, top, threshold=0.0):
     return idx, val
 
 
+def similarityMH_lsh_cross_edges(x, y, k=4, n_hash=50, bands=10, rows=5, threshold=0.5, *, seed=None, max_candidates=1 << 32):
+    """The threshold form of two sets from LSH candidates instead of all m * n pairs: ``(threshold, i, j, weight)``, 0-based, sorted by
+    (i, j): every pair of an x[i] and a y[j] that agree in all columns of some band and have ``c / n_hash >= threshold`` (c = equal
+    columns, the divide of similarityMH_cross).  No diagonal; every weight is > 0.  The result is exactly
+    ``lsh_cross_edges_dense(minhash_signatures(x, ...), minhash_signatures(y, ...), bands, rows, threshold)``; approximate is only that
+    definition's relation to ``similarityMH_cross_edges(x, y, threshold=threshold)``: a pair that agrees in no whole band is missing
+    (``1 - lsh_collision_probability`` says how likely).  y is bucketed once (an index of its sorted band keys), x looks its keys up;
+    ``MinHashSession.lsh_cross_edges`` keeps that index between calls.  ``max_candidates`` caps the (pair, band) incidences."""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    n = len(yo) - 1
+    bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
+    thr, ei, ej, ew = _edges_one_pass(lambda h, _thr, cnt: lib.da_similarity_mh_lsh_cross_edges_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data, bands, rows, float(threshold),
+        int(max_candidates), h, cnt))
+    return float(threshold), ei, ej, ew
+
+
+def similarityMH_lsh_cross_topk(x, y, k=4, n_hash=50, bands=10, rows=5, top=10, *, threshold=0.0, seed=None, max_candidates=1 << 32):
+    """For every x[i] its ``top`` most similar y[j] among the LSH candidates: ``(idx, val)``, (m, top) int32 and (m, top) float64.  Row i
+    lists the first ``top`` of ``{j : x[i] and y[j] agree in all columns of some band, c / n_hash >= threshold}`` by c descending, then j
+    ascending; a row with fewer candidates is padded with ``idx = -1, val = 0.0`` and ``val > 0`` marks exactly the real entries.  ``top``
+    is in 1 .. 1024 and is NOT clamped to len(y).  Exactly ``lsh_cross_topk_dense`` of the two signature matrices; with ``rows = 1, bands =
+    n_hash`` the lists equal similarityMH_cross_topk's wherever its value is > 0.  ``max_candidates`` as in similarityMH_lsh_cross_edges."""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    n = len(yo) - 1
+    top = _as_int(top, "top")
+    shape = (max(m, 1), min(max(top, 1), 1024))
+    idx = np.empty(shape, np.int32)
+    val = np.empty(shape, np.float64)
+    _capi.check(lib.da_similarity_mh_lsh_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data,
+                                                    _as_int(bands, "bands"), _as_int(rows, "rows"), float(threshold), top, int(max_candidates),
+                                                    idx.ctypes.data, val.ctypes.data))
+    return idx[:m], val[:m]
+
+
+def lsh_cross_edges_dense(sig_x, sig_y, bands, rows, threshold):
+    """The definition ``similarityMH_lsh_cross_edges`` is exact against, in numpy (host code, beside ``lsh_edges_dense``): ``sig_x`` (m,
+    n_hash) and ``sig_y`` (n, n_hash) uint32 -> ``(i, j, w)`` sorted by (i, j): (i, j, c / n_hash) for every row i of sig_x and row j of
+    sig_y that agree in all ``rows`` columns of some band and have ``c / n_hash >= threshold``."""
+    sig_x, sig_y = np.ascontiguousarray(sig_x, np.uint32), np.ascontiguousarray(sig_y, np.uint32)
+    (m, n_hash), (n, nh_y) = sig_x.shape, sig_y.shape
+    bands, rows = int(bands), int(rows)
+    if nh_y != n_hash:
+        raise ValueError("sig_x and sig_y must have the same number of columns")
+    if bands < 1 or rows < 1 or bands * rows > n_hash:
+        raise ValueError("need bands >= 1, rows >= 1 and bands * rows <= n_hash")
+    pairs = [np.empty((0, 2), np.int64)]
+    void = np.dtype((np.void, 4 * rows))
+    for t in range(bands):
+        bx = np.ascontiguousarray(sig_x[:, t * rows:(t + 1) * rows]).view(void).ravel()
+        by = np.ascontiguousarray(sig_y[:, t * rows:(t + 1) * rows]).view(void).ravel()
+        _, inv = np.unique(np.concatenate([bx, by]), return_inverse=True)
+        inv = inv.ravel()
+        ix, iy = inv[:m], inv[m:]
+        order = np.argsort(iy, kind="stable")                  # the rows of y by bucket
+        sorted_y = iy[order]
+        lo, hi = np.searchsorted(sorted_y, ix, "left"), np.searchsorted(sorted_y, ix, "right")
+        ln = hi - lo
+        if ln.sum():
+            i = np.repeat(np.arange(m, dtype=np.int64), ln)
+            within = np.arange(int(ln.sum()), dtype=np.int64) - np.repeat(np.cumsum(ln) - ln, ln)
+            pairs.append(np.stack([i, order[np.repeat(lo, ln) + within].astype(np.int64)], 1))
+    p = np.unique(np.concatenate(pairs), axis=0)               # sorted by (i, j), each candidate once
+    c = np.empty(len(p), np.int64)
+    for b0 in range(0, len(p), 1 << 16):
+        q = p[b0:b0 + (1 << 16)]
+        c[b0:b0 + len(q)] = (sig_x[q[:, 0]] == sig_y[q[:, 1]]).sum(1)
+    w = c.astype(np.float64) / np.float64(n_hash)
+    keep = w >= float(threshold)
+    return p[keep, 0].astype(np.int32), p[keep, 1].astype(np.int32), w[keep]
+
+
+def lsh_cross_topk_dense(sig_x, sig_y, bands, rows, top, threshold=0.0):
+    """The definition ``similarityMH_lsh_cross_topk`` is exact against, in numpy: -> ``(idx, val)``, (m, top) int32 / float64: row i holds the
+    first ``top`` candidates j of ``lsh_cross_edges_dense`` by (c descending, j ascending), then ``-1`` / ``0.0``.  1 <= top <= 1024; not
+    clamped to the rows of sig_y."""
+    top = _as_int(top, "top")
+    if not 1 <= top <= 1024:
+        raise ValueError("top must be in 1 .. 1024 (got %d)" % top)
+    r, c, v = lsh_cross_edges_dense(sig_x, sig_y, bands, rows, threshold)
+    m = np.asarray(sig_x).shape[0]
+    r, c = r.astype(np.int64), c.astype(np.int64)
+    order = np.lexsort((c, -v, r))               # row, then value descending (= count descending: one divide), then column ascending
+    r, c, v = r[order], c[order], v[order]
+    start = np.searchsorted(r, np.arange(m))
+    rank = np.arange(len(r)) - start[r]
+    keep = rank < top
+    idx = np.full((m, top), -1, np.int32)
+    val = np.zeros((m, top), np.float64)
+    idx[r[keep], rank[keep]] = c[keep]
+    val[r[keep], rank[keep]] = v[keep]
+    return idx, val
+
+
 def lsh_collision_probability(s, bands, rows):
     """P(two sequences of MinHash similarity ``s`` agree in at least one of ``bands`` bands of ``rows`` hash functions)
     = 1 - (1 - s^rows)^bands: the S-curve to choose bands and rows by."""

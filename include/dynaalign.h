@@ -56,6 +56,8 @@ extern "C" {
  *  da_dev_jaccard_sets_long, da_dev_jaccard_rect_long -- likewise)
  * (the LSH entry points -- da_similarity_mh_lsh_edges_begin, da_similarity_mh_lsh_knn, da_mh_lsh_last_route,
  *  da_dev_lsh_[band_keys | verify_pairs | edges | knn | knn_select | workspace_bytes] -- likewise)
+ * (the two-set LSH entry points -- da_similarity_mh_lsh_cross_[edges_begin | topk], da_dev_lsh_index_[bytes | build | probe],
+ *  da_dev_lsh_cross_[verify_pairs | workspace_bytes | edges | topk] -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1112,6 +1114,76 @@ int da_dev_lsh_knn(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash,
                    int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key, void *stream);
 int da_dev_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top,
                           int32_t *d_idx, int64_t ld_idx, uint16_t *d_key, int64_t ld_key, void *stream);
+
+/* ---- MinHash LSH banding for TWO sets: a resident set y (n sequences) kept as a bucket INDEX, queried by batches x (m sequences) --------------
+ * sig_x (m x n_hash) and sig_y (n x n_hash) under the same k, n_hash and seeds; bands, rows, the bands and the tail columns as above.
+ * cand(i, j): some band of sig_x[i] equals the same band of sig_y[j] in all its columns; c(i, j) = the equal columns over all n_hash.
+ *   edges:  (i, j, c / n_hash) for 0 <= i < m, 0 <= j < n with cand(i, j) and (double)c / (double)n_hash >= threshold, sorted by (i, j).
+ *           No diagonal (i and j number different sets); every weight is > 0 (c >= rows >= 1).  Exactly the entries (i, j - m) with
+ *           i < m <= j of the one-set edge list of the stacked signatures [sig_x ; sig_y].
+ *   top-k:  row i holds the first `top` (1 .. 1024, NOT clamped to n) of { j : cand(i, j), c / n_hash >= threshold } by c descending, then
+ *           j ascending; the padding is index -1 / value 0.0 (count 0).
+ * EXACT with respect to these definitions; approximate is only their relation to da_similarity_mh_cross_edges_begin (absolute threshold) /
+ * da_similarity_mh_cross_topk: a pair that agrees in no whole band is missing, with probability (1 - s^rows)^bands at similarity s.
+ *
+ * The index of y: its (band key, id) elements -- the keys of da_dev_lsh_band_keys -- in one stable sort, so equal keys keep their ids
+ * ascending.  It lives in ONE caller-owned device buffer of da_dev_lsh_index_bytes(n, bands) bytes, depends on nothing but sig_y, bands and
+ * rows, is only read by the query calls, and serves any number of them.  Layout, from the first 256-byte boundary at or behind d_index
+ * (the size carries 256 spare bytes; a copy of the buffer must keep d_index modulo 256), every array starting on a multiple of 256 bytes
+ * in this order, T = n * bands:
+ *     meta        uint32[8]: 0x4C534831, n, bands, rows, the number of runs (buckets), the longest run, 0, 0
+ *     band_start  uint32[bands + 1]: the elements of band t are [band_start[t], band_start[t + 1]); band_start[bands] = T
+ *     keys        uint64[T], ascending: t << 48 | 48 bits of a hash of band t's values
+ *     ids         int32[T]: the row of y of each element; ascending inside a run of equal keys
+ * A query call given an index whose meta words are not (n, bands, rows) reads nothing else of it and returns DA_ERR_BAD_ARG.
+ * m * bands and n * bands must stay below 2^31 - 256.
+ *
+ * da_dev_lsh_index_bytes / da_dev_lsh_cross_workspace_bytes: sizes; no device needed; > 0 for any arguments.
+ * da_dev_lsh_index_build: sig_y -> d_index.  The sort's scratch is allocated inside; synchronises the stream.
+ * da_dev_lsh_index_probe: the lookup alone: for element q = i * bands + t of x, d_lo[q] = the first element of the index whose key is the
+ *   key of band t of sig_x[i] and d_len[q] = the length of that run -- ids[d_lo[q] .. d_lo[q] + d_len[q]) are the rows of y whose band t
+ *   has that key, ascending; d_len[q] = 0 when there is none (d_lo[q] is then where the key would stand).  int32 [m * bands] each.
+ *   Synchronises the stream (the index check is read back).
+ * da_dev_lsh_cross_verify_pairs: the per-pair decision on LISTED triples (i, j, band), row i of sig_x against row j of sig_y:
+ *   d_count[p] = c(i, j); d_keep[p] = 1 when `band` agrees in all its columns, no earlier band does, and c / n_hash >= threshold -- else 0.
+ *   A triple with i outside [0, m), j outside [0, n) or a band outside [0, bands) gets 0 / 0.  Asynchronous on `stream`.
+ * da_dev_lsh_cross_edges: probe, verify, emit, sort.  d_work: da_dev_lsh_cross_workspace_bytes(m, bands) bytes, any alignment (the
+ *   per-incidence and per-edge buffers are sized by the data and allocated inside).  *n_edges_out = the number of edges; the first
+ *   min(capacity, that) of them, in (i, j) order, go to d_i / d_j / d_count, which may be NULL when capacity is 0.  max_candidates caps the
+ *   (pair, band) incidences -- the sum of the probed run lengths -- known before any pair is compared: more gives DA_ERR_UNSUPPORTED, the
+ *   message naming the count, the cap and the longest probed run.  Synchronises the stream.  ld_x and ld_y are independent.
+ * da_dev_lsh_cross_topk: the same through the verdicts, then the x rows' entries and da_dev_lsh_knn_select's selection into d_idx int32
+ *   (m, top) and d_key uint16 (m, top) (the counts c; padding -1 / 0), both with leading dimension top.  Synchronises the stream.
+ * da_similarity_mh_lsh_cross_edges_begin / da_similarity_mh_lsh_cross_topk: host boundary -- both packed sets, their signatures, the
+ *   index of y and one query, in one call; the result in a da_edges handle / in idx_out int32 (m, top), val_out float64 (m, top).
+ *   Checks, in this order and before any device is needed: m <= 0, n <= 0 (DA_ERR_EMPTY_INPUT), k, n_hash, NULL pointers, the offsets of x,
+ *   the offsets of y; then the checks of the one-set LSH calls in their order and with their texts: bands, rows, bands * rows, the
+ *   threshold, max_candidates, top (the top-k call only), n_hash > 65535.
+ * da_mh_lsh_last_route reports these calls too: buckets = the runs of the index, incidences, distinct verified pairs, and the edges
+ *   or real list entries written. */
+size_t da_dev_lsh_index_bytes(int64_t n, int bands);
+int da_dev_lsh_index_build(const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands, int rows, void *d_index,
+                           size_t index_bytes, void *stream);
+int da_dev_lsh_index_probe(const void *d_index, size_t index_bytes, int64_t n, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, int n_hash,
+                           int bands, int rows, int32_t *d_lo, int32_t *d_len, void *stream);
+int da_dev_lsh_cross_verify_pairs(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y,
+                                  int n_hash, int bands, int rows, double threshold, const int32_t *d_i, const int32_t *d_j,
+                                  const int32_t *d_band, int64_t n_triples, uint16_t *d_count, uint8_t *d_keep, void *stream);
+size_t da_dev_lsh_cross_workspace_bytes(int64_t m, int bands);
+int da_dev_lsh_cross_edges(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x,
+                           const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands, int rows, double threshold,
+                           int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_count,
+                           int64_t capacity, int64_t *n_edges_out, void *stream);
+int da_dev_lsh_cross_topk(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x,
+                          const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands, int rows, double threshold, int top,
+                          int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key, void *stream);
+int da_similarity_mh_lsh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                           const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                                           int rows, double threshold, int64_t max_candidates, da_edges **handle_out,
+                                           int64_t *n_edges_out);
+int da_similarity_mh_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                    const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
+                                    double threshold, int top, int64_t max_candidates, int32_t *idx_out, double *val_out);
 
 /* name -> id for da_dev_nw; -1 + DA_ERR_BAD_MATRIX message when unknown. */
 int da_matrix_id(const char *matrix_name);
