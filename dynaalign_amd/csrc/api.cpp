@@ -1117,6 +1117,29 @@ extern "C" int da_debug_zoned_ids(const int32_t *h, int zones, int64_t M, int64_
     for (int64_t q = 0; q < h[z]; ++q) *ids_out++ = M + zoned_rank(h, zones, z, q);
   return DA_OK;
 }
+// tests: the hash that picks a string's start slot in the duplicate plan's table (da_common.hpp dd_hash), on the host
+extern "C" int da_debug_dd_hash(const uint8_t *bytes, int32_t len, uint32_t *out) {
+  if (!out || len < 0 || (len > 0 && !bytes)) return fail(DA_ERR_BAD_ARG, "dd hash: bad arguments");
+  *out = dd_hash(bytes, 0, len);
+  return DA_OK;
+}
+// tests: the sorted order the ordered DP's prefix sharing uses (launch_nw_sort_unique) on n strings of residue CODES: perm[n] and lcp[n] copied to
+// d_perm_out / d_lcp_out.  Allocates the sort's workspace; synchronises `stream`.
+extern "C" int da_debug_nw_sort_unique(const uint8_t *d_codes, const int64_t *d_off, int64_t n, int32_t *d_perm_out, uint8_t *d_lcp_out, void *stream) {
+  if (!d_codes || !d_off || !d_perm_out || !d_lcp_out || n < 1 || n > 0x7ffffff0LL) return fail(DA_ERR_BAD_ARG, "nw sort: bad arguments");
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  DevBuf work;
+  const size_t sb = nw_sort_unique_workspace_bytes(n);
+  const int32_t *perm = nullptr;
+  const uint8_t *lcp = nullptr;
+  int rc;
+  if ((rc = work.alloc(sb)) != DA_OK) return rc;
+  if ((rc = launch_nw_sort_unique(d_codes, d_off, n, work.p, sb, &perm, &lcp, st)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpyAsync(d_perm_out, perm, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+  DA_HIP_TRY(hipMemcpyAsync(d_lcp_out, lcp, (size_t)n, hipMemcpyDeviceToDevice, st));
+  DA_HIP_TRY(hipStreamSynchronize(st));                     // the workspace goes back to the cache after this
+  return DA_OK;
+}
 
 // tests: whether the calling thread's last similarityMH call kept its count table packed (9 bits per count; the row forms with n_hash <= 511)
 extern "C" int da_debug_mh_last_table_packed(int *packed_out) {

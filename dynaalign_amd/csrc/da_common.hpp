@@ -249,6 +249,14 @@ size_t nw_sort_unique_workspace_bytes(int64_t n);
 int launch_nw_sort_unique(const uint8_t *d_codes, const int64_t *d_off, int64_t n, void *d_work, size_t work_bytes, const int32_t **perm_out,
                           const uint8_t **lcp_out, hipStream_t stream);
 // nw_kernels.hip: collapse byte-identical sequences before the N x N sweep (exact; see the kernels' header comment)
+// The start slot of a string in the plan's open-addressing table is dd_hash & (table_size - 1); host-callable so that the tests' model
+// (tests/unique_plan_model.py, through da_debug_dd_hash) can build probe chains on purpose.
+__host__ __device__ __forceinline__ uint32_t dd_hash(const uint8_t *c, int64_t b, int32_t len) {
+  uint32_t h = 0x9747b28cu ^ (uint32_t)len;
+  for (int32_t q = 0; q < len; ++q) { h ^= c[b + q]; h *= 0x01000193u; h ^= h >> 15; }
+  h ^= h >> 13; h *= 0x5bd1e995u; h ^= h >> 15;
+  return h;
+}
 struct NwDedupPlan {
   uint32_t *table; uint32_t table_size;
   int32_t *rep, *mult, *last, *fm, *fs, *pm, *ps, *uid_of, *uidx, *ufirst, *ulast, *ulen, *minfirst, *maxlast;

@@ -603,12 +603,7 @@ __global__ __launch_bounds__(K4_THREADS) void k_nw_xlong_cols(   // row blocks w
 // the direct kernel runs.
 constexpr uint32_t DD_EMPTY = 0xffffffffu;
 
-__device__ __forceinline__ uint32_t dd_hash(const uint8_t *c, int64_t b, int32_t len) {
-  uint32_t h = 0x9747b28cu ^ (uint32_t)len;
-  for (int32_t q = 0; q < len; ++q) { h ^= c[b + q]; h *= 0x01000193u; h ^= h >> 15; }
-  h ^= h >> 13; h *= 0x5bd1e995u; h ^= h >> 15;
-  return h;
-}
+// (dd_hash, the start slot: da_common.hpp)
 __device__ __forceinline__ bool dd_same(const uint8_t *c, const int64_t *off, int64_t a, int64_t b) {
   const int64_t ba = off[a], bb = off[b];
   const int64_t la = off[a + 1] - ba;

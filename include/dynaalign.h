@@ -588,7 +588,10 @@ int da_dev_shards_to_table(const void *d_gathered, int64_t ld_g, int64_t n, int 
 /* rank `rank` of `world`'s part of the ORDERED unique table of similarityNW, calc(U_p, U_q) with U_p as sequence1
  * (src/pairwiseSeqAlign.cpp:340-346 evaluates calc(seq[i], seq[j]) for i < j and the function is not symmetric): the cyclic 128-row
  * units rank, rank + world, ... stored back to back in d_out (ceil(ceil(unique / 128) / world) * 128 rows of ld >= unique uint16
- * matches<<8|length codes; world = 1: the whole table in natural row order); entries no original pair needs stay unwritten.  The plan
+ * matches<<8|length codes; world = 1: the whole table in natural row order).  Every entry some original pair needs -- p == q, or
+ * d_ufirst[p] < d_ulast[q] -- is written.  What no pair needs is skipped per row and 64-column tile only (row p against the columns of tile t
+ * when d_ufirst[p] >= d_maxlast[t], and never inside a diagonal tile): such an entry either stays unwritten or holds its correct code, so the
+ * caller must not read meaning into an unneeded entry either way.  Rows of the last unit past the table stay unwritten.  The plan
  * must have been built on the ENCODED residues (da_dev_nw_encode).  Sequences of 1..64 residues, penalties >= 0. */
 int da_dev_nw_unique_rows(const da_unique_plan *plan, int64_t max_len, int matrix_id, int gap_open, int gap_ext, int rank, int world,
                           uint16_t *d_out, int64_t ld, void *stream);

@@ -294,3 +294,21 @@ def test_config_reload_hook_is_exported_and_harmless_without_a_gpu():
     finally:
         del os.environ["DYNAALIGN_MH_NO_DEDUP"]
     lib.da_config_reload()
+
+
+def test_debug_entries_of_the_plan_tests_are_exported_and_stay_out_of_the_header(lib):
+    """da_debug_dd_hash and da_debug_nw_sort_unique are declared by the tests that use them (tests/test_unique_plan_cpu.py,
+    tests/test_gpu_unique_plan.py), like the other da_debug_* entries; both refuse bad arguments before they touch a device"""
+    import ctypes
+    from dynaalign_amd import _capi
+    for name in ("da_debug_dd_hash", "da_debug_nw_sort_unique", "da_debug_mh_dedup_ids", "da_debug_zoned_ids"):
+        assert hasattr(lib, name), name
+    declared = _capi.header_symbols()
+    assert "da_debug_dd_hash" not in declared and "da_debug_nw_sort_unique" not in declared
+    fn = lib.da_debug_nw_sort_unique
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    fn.restype = ctypes.c_int
+    assert fn(None, None, 5, None, None, None) == _capi.DA_ERR_BAD_ARG
+    buf = (ctypes.c_int64 * 4)()
+    for n in (0, -1, 2 ** 31):
+        assert fn(ctypes.addressof(buf), ctypes.addressof(buf), n, ctypes.addressof(buf), ctypes.addressof(buf), None) == _capi.DA_ERR_BAD_ARG
