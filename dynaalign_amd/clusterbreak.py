@@ -36,7 +36,8 @@ import numpy as np
 
 from . import _capi
 
-__all__ = ["clusterbreak", "clusterconsensus", "netcluster", "louvain", "threshold_edges_dense", "ClusterbreakResult"]
+__all__ = ["clusterbreak", "clusterconsensus", "netcluster", "louvain", "louvain_sync_dense", "louvain_device", "threshold_edges_dense",
+           "ClusterbreakResult"]
 
 
 def louvain(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_modularity=False):
@@ -60,6 +61,9 @@ def louvain(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_modular
     return (member, float(q[0])) if return_modularity else member
 
 
+_louvain_host = louvain
+
+
 def louvain_csr(n, ptr, adj, codes, loop_codes, values, resolution=1.05, seed=0, weights=True, return_modularity=False):
     """`louvain` on a graph that is already canonical (da_louvain_csr): symmetric CSR, weights as uint16 codes into `values`,
     self-loops per vertex as codes (0xFFFF = none).  What MinHashSession.edges_csr hands over -- sorted on the device, no host-side
@@ -79,6 +83,243 @@ def louvain_csr(n, ptr, adj, codes, loop_codes, values, resolution=1.05, seed=0,
                                    q.ctypes.data if return_modularity else None, lv.ctypes.data))
     member = member[:int(n)]
     return (member, float(q[0])) if return_modularity else member
+
+
+# ---- the synchronous Louvain: its definition (numpy) and the device call that reproduces it bit for bit ------------------------------------
+LV_SCALE_BITS = 30        # every weight becomes the integer rint(w * 2**30); all sums of weights are exact 64-bit integers
+LV_CLASSES = 8            # sub-rounds per iteration
+LV_MAX_ITERATIONS = 64
+LV_MAX_LEVELS = 32
+LV_M2_LIMIT = 1 << 62
+LOUVAIN_DEVICE_MIN_NNZ = 1 << 17   # clusterbreak(louvain="device"): smaller levels stay on the host
+
+
+def _lv_quantise(ew):
+    ew = np.ascontiguousarray(ew, np.float64)
+    if not np.isfinite(ew).all():
+        raise ValueError("edge weights must be finite")
+    if (ew < 0).any():
+        raise ValueError("edge weights must not be negative")
+    return np.rint(ew * float(1 << LV_SCALE_BITS)).astype(np.int64)
+
+
+def _lv_csr(n, ei, ej, wq):
+    """symmetric adjacency without a diagonal (repeated edges summed) + the self-loop weight per vertex"""
+    loop = np.zeros(n, np.int64)
+    d = ei == ej
+    np.add.at(loop, ei[d], wq[d])
+    a = np.concatenate([ei[~d], ej[~d]]).astype(np.int64)
+    b = np.concatenate([ej[~d], ei[~d]]).astype(np.int64)
+    w = np.concatenate([wq[~d], wq[~d]])
+    key = a * n + b
+    o = np.argsort(key, kind="stable")
+    key, w = key[o], w[o]
+    uk, st = np.unique(key, return_index=True)
+    w = np.add.reduceat(w, st) if len(w) else w
+    ptr = np.zeros(n + 1, np.int64)
+    np.add.at(ptr, uk // n + 1, 1)
+    return np.cumsum(ptr), uk % n, w, loop
+
+
+def _lv_modularity(m2, inn, tot, res):
+    """Q = IN / m2 - res * (S / (m2 * m2)): IN and S = sum tot^2 exact integers (S has up to 124 bits), each converted to double once"""
+    s = sum(int(t) * int(t) for t in tot.tolist())
+    return float(inn) / float(m2) - res * (float(s) / (float(m2) * float(m2)))
+
+
+def _lv_pass(ptr, adj, w, loop, res, seed, level):
+    """one level on (ptr, adj, w, loop) -> (comm, moved_any, iterations, Q after the last iteration); m2 > 0"""
+    n = len(ptr) - 1
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+    k = 2 * loop
+    np.add.at(k, rows, w)
+    m2 = int(k.sum())
+    kf, m2f = k.astype(np.float64), float(m2)
+    comm, tot, size = np.arange(n, dtype=np.int64), k.copy(), np.ones(n, np.int64)
+    with np.errstate(over="ignore"):
+        h = ((np.arange(n, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(int(seed) * 40503 + level)) >> np.uint64(7)) & np.uint64(7)
+    h = h.astype(np.int64)
+    loops2 = 2 * int(loop.sum())
+
+    def quality():
+        return _lv_modularity(m2, int(w[comm[rows] == comm[adj]].sum()) + loops2, tot, res)
+    q_prev = q = quality()
+    moved_any, iterations = False, 0
+    for _ in range(LV_MAX_ITERATIONS):
+        iterations += 1
+        moved = 0
+        for g in range(LV_CLASSES):
+            vs = np.nonzero(h == g)[0]
+            if len(vs) == 0:
+                continue
+            sel = h[rows] == g
+            # (vertex, neighbour community, summed weight), the vertex's own community always among them (weight 0 when no neighbour is in it)
+            r = np.concatenate([rows[sel], vs])
+            c = np.concatenate([comm[adj[sel]], comm[vs]])
+            ww = np.concatenate([w[sel], np.zeros(len(vs), np.int64)])
+            key = r * n + c
+            o = np.argsort(key, kind="stable")
+            key, ww = key[o], ww[o]
+            uk, st = np.unique(key, return_index=True)
+            ws = np.add.reduceat(ww, st)
+            rv, cc = uk // n, uk % n
+            own = cc == comm[rv]
+            t = tot[cc] - np.where(own, k[rv], 0)
+            gain = ws.astype(np.float64) - ((res * t.astype(np.float64)) * kf[rv]) / m2f
+            stay = np.empty(n, np.float64)
+            stay[rv[own]] = gain[own]
+            ok = ~own & (gain > stay[rv])
+            ok &= ~((size[comm[rv]] == 1) & (size[cc] == 1) & (cc > comm[rv]))           # two lone vertices must not swap for ever
+            rv, cc, gain = rv[ok], cc[ok], gain[ok]
+            o = np.lexsort((cc, -gain, rv))                                                # largest gain, then the smaller community id
+            rv, cc = rv[o], cc[o]
+            first = np.ones(len(rv), bool)
+            first[1:] = rv[1:] != rv[:-1]
+            mv, mc = rv[first], cc[first]
+            old = comm[mv]
+            np.add.at(tot, old, -k[mv])
+            np.add.at(tot, mc, k[mv])
+            np.add.at(size, old, -1)
+            np.add.at(size, mc, 1)
+            comm[mv] = mc
+            moved += len(mv)
+        q = quality()
+        if moved == 0:
+            break
+        moved_any = True
+        if not q > q_prev:                 # the moves are kept (the host Louvain does the same)
+            break
+        q_prev = q
+    return comm, moved_any, iterations, q
+
+
+def _lv_aggregate(ptr, adj, w, loop, comm):
+    n = len(ptr) - 1
+    u, newc = np.unique(comm, return_inverse=True)
+    nc = len(u)
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+    a, b = newc[rows], newc[adj]
+    nloop = np.zeros(nc, np.int64)
+    np.add.at(nloop, newc, loop)
+    d = a == b
+    inner = np.zeros(nc, np.int64)
+    np.add.at(inner, a[d], w[d])
+    nloop += inner // 2                    # every internal edge was counted from both ends
+    a, b, ww = a[~d], b[~d], w[~d]
+    key = a * nc + b
+    o = np.argsort(key, kind="stable")
+    key, ww = key[o], ww[o]
+    uk, st = np.unique(key, return_index=True)
+    ws = np.add.reduceat(ww, st) if len(ww) else ww
+    nptr = np.zeros(nc + 1, np.int64)
+    np.add.at(nptr, uk // nc + 1, 1)
+    return newc, np.cumsum(nptr), uk % nc, ws, nloop
+
+
+def _lv_first_appearance(member):
+    _, first, inv = np.unique(member, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(1, len(first) + 1)
+    return rank[inv].astype(np.int32)
+
+
+def louvain_sync_dense(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_info=False):
+    """The synchronous Louvain `louvain_device` runs on the GPU, as its definition in numpy (the ``cluster_fn`` calling convention; the
+    device call reproduces membership, modularity, levels and iterations bit for bit).  NOT the host `louvain`: another clustering
+    function with other memberships.
+
+    Weights become integers rint(w * 2**30) and every sum of weights is an exact 64-bit integer.  Symmetric adjacency without a diagonal,
+    self-loops per vertex, k_v = 2 loop_v + sum_u w(v, u), m2 = sum_v k_v.  A level starts from singletons; the vertices fall into 8
+    classes h(v) = ((v * 2654435761 + seed * 40503 + level) >> 7) & 7 (uint64), and an iteration is 8 sub-rounds: the vertices of one
+    class decide from the same snapshot, then all their moves are applied.  With C = comm[v] and g(w, t) = w - ((resolution * t) * k_v) / m2
+    in doubles, v moves to the neighbouring community c != C of largest g(w(v, c), tot[c]) (ties: the smaller c) among those with
+    g > g(w(v, C), tot[C] - k_v), a candidate being barred when size[C] == size[c] == 1 and c > C.  After an iteration
+    Q = IN / m2 - resolution * (S / (m2 * m2)) from the exact internal weight IN and S = sum tot^2; the level stops when nothing moved,
+    when Q did not strictly improve (the moves are kept), or after 64 iterations.  Communities are renumbered by ascending id, the graph is
+    aggregated with integer sums, and levels repeat until one moves nothing, merges nothing, or 32 have run.
+
+    Returns ids from 1 in order of first appearance; with return_info ``(membership, Q, levels, iterations)``: the number of levels run
+    and the iterations of each."""
+    n = int(n)
+    ei = np.ascontiguousarray(ei, np.int64)
+    ej = np.ascontiguousarray(ej, np.int64)
+    ew = np.ascontiguousarray(ew, np.float64) if weights else np.ones(len(ei), np.float64)
+    if not (len(ei) == len(ej) == len(ew)):
+        raise ValueError("edge arrays differ in length")
+    if n < 0:
+        raise ValueError("n must not be negative")
+    if len(ei) and (min(ei.min(), ej.min()) < 0 or max(ei.max(), ej.max()) >= n):
+        raise ValueError("edge endpoint out of range")
+    wq = _lv_quantise(ew)
+    res = float(resolution)
+    ptr, adj, w, loop = _lv_csr(n, ei, ej, wq)
+    if len(adj) * int(wq.max(initial=0)) + 2 * int(loop.sum()) >= LV_M2_LIMIT:
+        raise ValueError("total edge weight too large for exact 64-bit sums")
+    member = np.arange(n, dtype=np.int64)
+    k0 = 2 * loop
+    np.add.at(k0, np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr)), w)
+    q, iterations = 0.0, []
+    if int(k0.sum()) > 0:
+        for level in range(LV_MAX_LEVELS):
+            comm, moved, its, q = _lv_pass(ptr, adj, w, loop, res, seed, level)
+            iterations.append(its)
+            if not moved:
+                break
+            newc, nptr, nadj, nw, nloop = _lv_aggregate(ptr, adj, w, loop, comm)
+            member = newc[member]
+            merged = len(nptr) < len(ptr)
+            ptr, adj, w, loop = nptr, nadj, nw, nloop
+            if not merged:
+                break
+    out = _lv_first_appearance(member)
+    return (out, q, len(iterations), iterations) if return_info else out
+
+
+def canonical_csr(n, ei, ej, ew):
+    """an edge list (i == j = self-loop, either orientation, any order) as the canonical symmetric CSR `louvain_csr` and
+    `device.louvain_csr` take: (ptr, adj, codes, loop_codes, values) with values = unique(ew).  Repeated edges and more than 65 535
+    distinct weights raise ValueError."""
+    n = int(n)
+    ei = np.ascontiguousarray(ei, np.int64)
+    ej = np.ascontiguousarray(ej, np.int64)
+    ew = np.ascontiguousarray(ew, np.float64)
+    if not (len(ei) == len(ej) == len(ew)):
+        raise ValueError("edge arrays differ in length")
+    if len(ei) and (min(ei.min(), ej.min()) < 0 or max(ei.max(), ej.max()) >= n):
+        raise ValueError("edge endpoint out of range")
+    if not np.isfinite(ew).all():
+        raise ValueError("edge weights must be finite")
+    if (ew < 0).any():
+        raise ValueError("edge weights must not be negative")
+    values, code = np.unique(ew, return_inverse=True)
+    if len(values) > 65535:
+        raise ValueError("more than 65535 distinct edge weights")
+    lo, hi = np.minimum(ei, ej), np.maximum(ei, ej)
+    if len(np.unique(lo * max(n, 1) + hi)) != len(lo):
+        raise ValueError("repeated edge")
+    d = lo == hi
+    loops = np.full(n, 0xFFFF, np.uint16)
+    loops[lo[d]] = code[d]
+    a = np.concatenate([lo[~d], hi[~d]])
+    b = np.concatenate([hi[~d], lo[~d]])
+    c = np.concatenate([code[~d], code[~d]])
+    o = np.lexsort((b, a))
+    ptr = np.zeros(n + 1, np.int64)
+    np.add.at(ptr, a + 1, 1)
+    return np.cumsum(ptr), b[o].astype(np.int32), c[o].astype(np.uint16), loops, values
+
+
+def louvain_device(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_modularity=False):
+    """`louvain_sync_dense` on the GPU (da_dev_louvain_csr), in the ``cluster_fn`` calling convention: the canonical CSR is built here in
+    numpy (values = unique(ew)), uploaded, and clustered by `device.louvain_csr`.  Raises ValueError above 65 535 distinct weights, on
+    repeated edges, and -- like `louvain_sync_dense` -- on non-finite or negative weights and endpoints out of range."""
+    import torch
+    from . import device
+    ptr, adj, codes, loops, values = canonical_csr(n, ei, ej, ew)
+    up = lambda a, t: torch.from_numpy(a.view(t) if a.dtype != t else a).cuda()           # noqa: E731
+    member, q, _, _ = device.louvain_csr(up(ptr, np.int64), up(adj, np.int32), up(codes, np.int16), up(loops, np.int16), values,
+                                         resolution=resolution, seed=seed, weights=weights)
+    return (member, q) if return_modularity else member
 
 
 def _quantile_type7_sorted_parts(x, p):
@@ -184,7 +425,7 @@ class ClusterbreakResult(dict):
 
 def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_fn=None, cluster_fn=None,
                  cluster_wt=True, *, session=None, edges_fn=None, cluster_seed=0, verbose=False, log=None, knn=None, knn_mode="union",
-                 knn_lsh=None):
+                 knn_lsh=None, louvain="host", louvain_device_min_nnz=LOUVAIN_DEVICE_MIN_NNZ):
     """Recursive quantile-threshold + Louvain splitting, reference clusterbreak (R/clusterbreak.R:180-275).
 
     pep        sequences (character vector)
@@ -204,6 +445,10 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
                ``edges_fn=lambda s: similarityMH_lsh_knn_edges(s, k, n_hash, bands, rows, top, mode)``.  None (default): all pairs
     cluster_seed  call number c of the recursion clusters with seed cluster_seed + c (the reference draws from
                R's global RNG instead)
+    louvain    "host" (default): the built-in `louvain_csr`.  "device" (needs a session and no cluster_fn): a level whose CSR has at least
+               louvain_device_min_nnz adjacency entries is clustered where it lies, by `device.louvain_csr` -- the synchronous Louvain
+               `louvain_sync_dense` defines, with seed cluster_seed + c -- and the graph is not copied to the host; smaller levels take the
+               host path.  The memberships are not the host Louvain's: it is another clustering function
     """
     if size_max <= size_min:
         raise ValueError("size_max must be greater than size_min")                      # :189-191
@@ -231,16 +476,24 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
         except (TypeError, ValueError):
             raise ValueError("knn_lsh must be a (bands, rows) pair") from None
 
+    import os
+    if louvain not in ("host", "device"):
+        raise ValueError("louvain must be 'host' or 'device'")
+    if louvain == "device" and (session is None or cluster_fn is not None):
+        raise ValueError("louvain='device' clusters the session's resident CSR: it needs a session and no cluster_fn")
+    on_dev = louvain == "device"
+    if on_dev and os.environ.get("DYNAALIGN_CLUSTERBREAK_NO_CSR"):
+        raise ValueError("louvain='device' clusters the CSR path's graph: unset DYNAALIGN_CLUSTERBREAK_NO_CSR")
+
     def knn_csr(idx, m):
         if knn_lsh is not None:
-            return session.lsh_knn_csr(lsh_bands, lsh_rows, idx, min(knn, m - 1), knn_mode)
-        return session.knn_csr(idx, min(knn, m - 1), knn_mode)
+            return (session.lsh_knn_csr_device if on_dev else session.lsh_knn_csr)(lsh_bands, lsh_rows, idx, min(knn, m - 1), knn_mode)
+        return (session.knn_csr_device if on_dev else session.knn_csr)(idx, min(knn, m - 1), knn_mode)
     if sim_fn is None and session is None and edges_fn is None:
         from .similarity import similarityMH
         sim_fn = lambda x: similarityMH(x, k=2, n_hash=50)                               # noqa: E731  (:185)
-    import os
     csr_path = session is not None and cluster_fn is None and not os.environ.get("DYNAALIGN_CLUSTERBREAK_NO_CSR")
-    cluster_fn = cluster_fn or louvain
+    cluster_fn = cluster_fn or _louvain_host           # (`louvain` is this function's mode argument)
     out_seq, out_lab, filtered = [], [], []                                              # state$out.df, state$filter.df
     state = {"itr": 1, "convergence": 1}                                                 # :199-200
     levels = []
@@ -277,9 +530,19 @@ def clusterbreak(pep, thresh_p=0.8, size_max=10, size_min=3, max_itr=10000, sim_
             if knn is not None:
                 thr, n_edges, ptr, adj, codes, loops, values = knn_csr(idx, m)
             else:
-                thr, n_edges, ptr, adj, codes, loops, values = session.edges_csr(idx, thresh_p)
+                thr, n_edges, ptr, adj, codes, loops, values = session.edges_csr(idx, thresh_p, **({"on_device": True} if on_dev else {}))
+            if on_dev:               # the graph kernels are asynchronous: their time belongs to similarity_s, not to cluster_s
+                import torch
+                torch.cuda.synchronize()
             t1 = time.perf_counter()
-            c_index = louvain_csr(m, ptr, adj, codes, loops, values, seed=seed_c, weights=True).astype(np.int64)   # :222 (built-in: see _run_cluster_fn)
+            if on_dev and int(adj.numel()) >= int(louvain_device_min_nnz):
+                from . import device
+                c_index = device.louvain_csr(ptr, adj, codes, loops, values, seed=seed_c, weights=True)[0].astype(np.int64)
+            else:
+                if on_dev:           # a small level: launch-bound on the device, so the host Louvain takes it
+                    ptr, adj = ptr.cpu().numpy(), adj.cpu().numpy()
+                    codes, loops = codes.cpu().numpy().view(np.uint16), loops.cpu().numpy().view(np.uint16)
+                c_index = louvain_csr(m, ptr, adj, codes, loops, values, seed=seed_c, weights=True).astype(np.int64)   # :222 (built-in: see _run_cluster_fn)
             del ptr, adj, codes, loops
         else:
             thr, ei, ej, ew = level_edges(idx)

@@ -1899,6 +1899,28 @@ int da_dev_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *
   return launch_edges_to_csr(d_i, d_j, d_v, n_edges, n, d_work, work_bytes, d_ptr, d_adj, d_codes, d_loops, static_cast<hipStream_t>(stream));
 }
 
+// ---- the synchronous Louvain (clusterbreak.louvain_sync_dense) on the resident CSR: the graph never crosses to the host ------------------
+size_t da_dev_louvain_workspace_bytes(int64_t n, int64_t nnz) { return louvain_device_workspace_bytes(n, nnz); }
+
+int da_dev_louvain_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, const uint16_t *d_codes, const uint16_t *d_loops, const double *values,
+                       int32_t n_values, double resolution, uint32_t seed, void *d_work, size_t work_bytes, int32_t *d_membership,
+                       double *modularity_out, int32_t *levels_out, int32_t *iterations_out, void *stream) {
+  if (n < 0) return fail(DA_ERR_BAD_ARG, "n must not be negative (got %lld)", (long long)n);
+  if (levels_out) *levels_out = 0;
+  if (modularity_out) *modularity_out = 0.0;
+  if (iterations_out) std::fill(iterations_out, iterations_out + 32, 0);
+  if (n == 0) return DA_OK;
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "device Louvain: too many vertices");
+  if (!d_ptr || !d_work || !d_membership) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (n_values < 0 || n_values > 65535 || (n_values > 0 && !values))
+    return fail(DA_ERR_BAD_ARG, "values must hold 0 .. 65535 weights (got %d)", (int)n_values);
+  if (!(resolution >= 0.0) || !std::isfinite(resolution)) return fail(DA_ERR_BAD_ARG, "the resolution must be finite and not negative");
+  if (reinterpret_cast<uintptr_t>(d_work) & 255) return fail(DA_ERR_BAD_ARG, "workspace must be 256-byte aligned");
+  if (work_bytes < louvain_device_workspace_bytes(n, 0)) return fail(DA_ERR_BAD_ARG, "device Louvain: workspace too small");
+  return launch_louvain_device(n, d_ptr, d_adj, d_codes, d_loops, values, n_values, resolution, seed, d_work, work_bytes, d_membership, modularity_out,
+                               levels_out, iterations_out, static_cast<hipStream_t>(stream));
+}
+
 // R's quantile(x, p, type = 7) (stats::quantile.default, the default the reference's
 // R/clusterbreak.R:219 uses) of the multiset {values[b] x hist[b]}, values ascending:
 //   index = 1 + (N-1) p; lo = floor(index); hi = ceiling(index); q = x[lo];

@@ -317,6 +317,11 @@ int launch_gather_columns(const uint16_t *d_D, int64_t ld_d, const int32_t *d_ui
 size_t edges_to_csr_workspace_bytes(int64_t m, int64_t n);
 int launch_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_v, int64_t m, int64_t n, void *d_work, size_t work_bytes,
                         int64_t *d_ptr, int32_t *d_adj, uint16_t *d_codes, uint16_t *d_loops, hipStream_t stream);
+// louvain_kernels.hip: the synchronous Louvain of clusterbreak.louvain_sync_dense on a canonical CSR in device memory (da_dev_louvain_csr)
+size_t louvain_device_workspace_bytes(int64_t n, int64_t nnz);
+int launch_louvain_device(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, const uint16_t *d_codes, const uint16_t *d_loops, const double *values,
+                          int n_values, double resolution, uint32_t seed, void *d_work, size_t work_bytes, int32_t *d_membership, double *modularity_out,
+                          int32_t *levels_out, int32_t *iterations_out, hipStream_t stream);
 // graph_kernels.hip: nearest-neighbour lists (n rows of ld >= top columns and their uint16 keys) -> the (i <= j, code) edge list of their union /
 // mutual kNN graph, the diagonal first in every row's share when `loops` (da_dev_knn_edges); d_i / d_j / d_v hold n * (top + loops) entries
 size_t knn_edges_workspace_bytes(int64_t n, int top);

@@ -495,6 +495,58 @@ def edges_to_csr(ei, ej, ev, n_edges, n):
     return ptr, adj[:nnz], codes[:nnz], loops[:n]
 
 
+# the degree bins of the decide kernels (csrc/louvain_kernels.hip): a wave per row up to LOUVAIN_WAVE_MAX entries, a workgroup and an LDS
+# table up to LOUVAIN_LDS_MAX, a table in the workspace beyond; on a level of at most LOUVAIN_DIRECT_MAX vertices the LDS table is indexed
+# by the community id and takes rows of any length.  A row above LOUVAIN_LDS_MAX tries the LDS table (LOUVAIN_LDS_SLOTS slots) first and takes
+# the workspace table when its neighbouring communities do not fit
+LOUVAIN_WAVE_MAX, LOUVAIN_LDS_MAX, LOUVAIN_DIRECT_MAX, LOUVAIN_LDS_SLOTS = 64, 3072, 4096, 4096
+
+
+def louvain_workspace_bytes(n, nnz):
+    return int(_capi.load().da_dev_louvain_workspace_bytes(int(n), int(nnz)))
+
+
+def louvain_csr(ptr, adj, codes, loops, values, resolution=1.05, seed=0, weights=True, work=None):
+    """The synchronous Louvain (clusterbreak.louvain_sync_dense, reproduced bit for bit) on a canonical symmetric CSR that lies in HBM
+    (da_dev_louvain_csr): the tensors `edges_to_csr` returns -- ptr int64[n + 1], adj int32[nnz], codes int16[nnz] (uint16 bit pattern),
+    loops int16[n] (0xFFFF = no self-loop; None = none) -- and the host array `values` (weight of entry e = values[codes[e]]).
+    weights=False gives every code the weight 1.0.  Returns (membership int32 numpy, ids from 1 in order of first appearance; Q; levels;
+    iterations per level).  The call synchronises the current stream.  A CSR that is not canonical raises DynaAlignError
+    (DA_ERR_BAD_ARG); symmetry is not checked."""
+    lib = _capi.load()
+    _require_cuda(ptr, "ptr")
+    n = int(ptr.numel()) - 1
+    if n < 0:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr must hold n + 1 row pointers")
+    values = np.ascontiguousarray(values, np.float64)
+    if not weights:
+        values = np.ones(len(values), np.float64)
+    if n == 0:
+        return np.zeros(0, np.int32), 0.0, 0, []
+    for t, name in ((adj, "adj"), (codes, "codes")):
+        _require_cuda(t, name)
+    if ptr.dtype != torch.int64 or adj.dtype != torch.int32 or codes.element_size() != 2 or (loops is not None and loops.element_size() != 2):
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr int64, adj int32, codes and loops 16-bit")
+    nnz = int(adj.numel())
+    if int(codes.numel()) != nnz or (loops is not None and int(loops.numel()) < n):
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "adj, codes and loops disagree with ptr in length")
+    if int(ptr[n].item()) != nnz:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr[n] (%d) is not the number of adjacency entries (%d)" % (int(ptr[n].item()), nnz))
+    ptr, adj, codes = ptr.contiguous(), adj.contiguous(), codes.contiguous()
+    loops = None if loops is None else loops.contiguous()
+    nbytes = louvain_workspace_bytes(n, nnz)
+    if work is None:
+        work = torch.empty(nbytes, dtype=torch.uint8, device=ptr.device)
+    member = torch.empty(n, dtype=torch.int32, device=ptr.device)
+    q = ctypes.c_double(0.0)
+    levels = ctypes.c_int32(0)
+    its = (ctypes.c_int32 * 32)()
+    _call(lib.da_dev_louvain_csr, n, ptr.data_ptr(), adj.data_ptr() if nnz else None, codes.data_ptr() if nnz else None,
+          None if loops is None else loops.data_ptr(), values.ctypes.data if len(values) else None, len(values), float(resolution),
+          int(seed) & 0xFFFFFFFF, work.data_ptr(), int(work.numel()), member.data_ptr(), ctypes.byref(q), ctypes.byref(levels), its, _stream())
+    return member.cpu().numpy(), float(q.value), int(levels.value), [int(its[i]) for i in range(int(levels.value))]
+
+
 def similarity_mh(ds, k, n_hash, seeds, out=None):
     """similarityMH (src/minHash.cpp:119-188) on a device-resident set, one C call: K1 + K1b + K2, with byte-identical
     sequences collapsed first when that pays (da_dev_similarity_mh).  Returns the (n, n) float64 tensor."""

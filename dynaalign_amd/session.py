@@ -194,23 +194,42 @@ class MinHashSession:
         val = device.widen(key, False, self.n_hash)                      # count / n_hash, the library's divide
         return i.cpu().numpy(), val.cpu().numpy()
 
+    def _csr_out(self, thr, got, ptr, adj, codes, loops, values, on_device):
+        """the CSR of edges_csr / knn_csr / lsh_knn_csr: host copies, or with on_device the device tensors device.louvain_csr takes"""
+        if on_device:
+            return thr, got, ptr, adj, codes, loops, values
+        return thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes.cpu().numpy().view(np.uint16), loops.cpu().numpy().view(np.uint16), values
+
+    def _min_code_threshold(self, codes, values):
+        """the smallest off-diagonal weight kept (NaN when none), from the device codes"""
+        if codes.numel() == 0:
+            return float("nan")
+        return float(values[int((codes.to(torch.int32) & 0xFFFF).min().item())])
+
     def knn_csr(self, idx=None, top=10, mode="union"):
         """The kNN graph of the subset (knn_graph of knn(top, idx) with the 1.0 diagonal) as the canonical symmetric CSR edges_csr returns --
         lists -> device.knn_edges -> device.edges_to_csr, all on the device: (threshold, n_edges, ptr, adj, codes, loop_codes, values) with
         weight of entry k = values[codes[k]]; n_edges counts i <= j entries, the diagonal included.  The threshold slot holds the smallest
         off-diagonal weight kept, NaN when none."""
+        return self._knn_csr(idx, top, mode, False)
+
+    def knn_csr_device(self, idx=None, top=10, mode="union"):
+        """knn_csr with ptr, adj, codes and loop_codes left as device tensors (what device.louvain_csr takes): nothing but the threshold's
+        code crosses to the host.  (knn_csr keeps its parameter list; edges_csr spells this on_device=True.)"""
+        return self._knn_csr(idx, top, mode, True)
+
+    def _knn_csr(self, idx, top, mode, on_device):
         i, key, m = self._knn_lists(idx, top, 1 << 30)
         ei, ej, ev, got = device.knn_edges(i, key, mode, is_nw=False, self_code=self.n_hash, loops=True)
         ptr, adj, codes, loops = device.edges_to_csr(ei, ej, ev, got, m)
         values = np.arange(self.n_hash + 1, dtype=np.float64) / self.n_hash           # src/minHash.cpp:174
-        codes_h = codes.cpu().numpy().view(np.uint16)
-        thr = float(values[int(codes_h.min())]) if len(codes_h) else float("nan")
-        return thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes_h, loops.cpu().numpy().view(np.uint16), values
+        return self._csr_out(self._min_code_threshold(codes, values), got, ptr, adj, codes, loops, values, on_device)
 
-    def edges_csr(self, idx=None, thresh_p=0.8):
+    def edges_csr(self, idx=None, thresh_p=0.8, on_device=False):
         """The thresholded graph of the subset as the canonical symmetric CSR clusterbreak.louvain_csr takes -- sorted ON THE DEVICE
         (da_dev_edges_to_csr), so neither a host-side sort nor 16 bytes per edge: (threshold, n_edges, ptr, adj, codes, loop_codes,
-        values) with weight of entry k = values[codes[k]]; n_edges counts i <= j entries like `edges`."""
+        values) with weight of entry k = values[codes[k]]; n_edges counts i <= j entries like `edges`.  on_device=True: ptr, adj, codes and
+        loop_codes stay device tensors (what device.louvain_csr takes) and the graph is not copied to the host."""
         import os, sys, time
         trace = os.environ.get("DYNAALIGN_TRACE") is not None
         marks = [("start", time.perf_counter())]
@@ -239,9 +258,8 @@ class MinHashSession:
         mark("extract")
         ptr, adj, codes, loops = device.edges_to_csr(ei, ej, ev, got, m)
         mark("edges -> CSR")
-        out = (thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes.cpu().numpy().view(np.uint16), loops.cpu().numpy().view(np.uint16),
-               values)
-        mark("device -> host")
+        out = self._csr_out(thr, got, ptr, adj, codes, loops, values, on_device)
+        mark("CSR kept on the device" if on_device else "device -> host")
         if trace and m >= 20000:
             print("[dynaalign] edges_csr m=%d: %s" % (m, ", ".join("%s %.1f ms" % (w, (t - marks[i][1]) * 1e3)
                                                                     for i, (w, t) in enumerate(marks[1:]))), file=sys.stderr)
@@ -290,14 +308,19 @@ class MinHashSession:
         """The kNN graph of lsh_knn(bands, rows, top, idx) with the 1.0 diagonal as the canonical symmetric CSR knn_csr returns -- lists ->
         device.knn_edges (which skips the padding) -> device.edges_to_csr, all on the device: (threshold, n_edges, ptr, adj, codes,
         loop_codes, values).  What ``clusterbreak(session=, knn=, knn_lsh=(bands, rows))`` clusters on."""
+        return self._lsh_knn_csr(bands, rows, idx, top, mode, False)
+
+    def lsh_knn_csr_device(self, bands, rows, idx=None, top=10, mode="union"):
+        """lsh_knn_csr with the CSR left in device tensors, as knn_csr_device"""
+        return self._lsh_knn_csr(bands, rows, idx, top, mode, True)
+
+    def _lsh_knn_csr(self, bands, rows, idx, top, mode, on_device):
         sig, m = self._subset(idx)
         i, key = device.lsh_knn(sig[:m], self.n_hash, bands, rows, top)
         ei, ej, ev, got = device.knn_edges(i, key, mode, is_nw=False, self_code=self.n_hash, loops=True)
         ptr, adj, codes, loops = device.edges_to_csr(ei, ej, ev, got, m)
         values = np.arange(self.n_hash + 1, dtype=np.float64) / self.n_hash           # src/minHash.cpp:174
-        codes_h = codes.cpu().numpy().view(np.uint16)
-        thr = float(values[int(codes_h.min())]) if len(codes_h) else float("nan")
-        return thr, got, ptr.cpu().numpy(), adj.cpu().numpy(), codes_h, loops.cpu().numpy().view(np.uint16), values
+        return self._csr_out(self._min_code_threshold(codes, values), got, ptr, adj, codes, loops, values, on_device)
 
     def _lsh_index_entry(self, bands, rows, idx):
         """(signatures of the indexed rows, their number, the index) for lsh_index's key; an idx subset is kept until another one is asked for"""

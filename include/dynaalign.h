@@ -1052,6 +1052,28 @@ size_t da_dev_edges_to_csr_bytes(int64_t n_edges, int64_t n);
 int da_dev_edges_to_csr(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_v, int64_t n_edges, int64_t n, void *d_work,
                         size_t work_bytes, int64_t *d_ptr, int32_t *d_adj, uint16_t *d_codes, uint16_t *d_loops, void *stream);
 
+/* The synchronous Louvain on that CSR where it lies, in device memory: the clustering function clusterbreak.louvain_sync_dense defines in
+ * numpy, reproduced bit for bit (membership, modularity, levels, iterations).  It is NOT da_louvain: another algorithm with other
+ * memberships.  Weights become integers rint(w * 2^30), all sums of weights are exact 64-bit integers; a level is at most 64 iterations of
+ * 8 sub-rounds (vertex classes ((v * 2654435761 + seed * 40503 + level) >> 7) & 7), each sub-round one decide launch per degree bin and one
+ * apply launch; at most 32 levels.  d_ptr / d_adj / d_codes / d_loops: what da_dev_edges_to_csr wrote (d_loops may be NULL: no self-loops);
+ * `values` is HOST memory, n_values <= 65535.  k_lv_validate checks, before anything indexes by a neighbour id or a code, that row pointers
+ * start at 0 and do not decrease, that neighbours are in range, ascending, distinct and not the row itself, and that codes are below
+ * n_values: a violation returns DA_ERR_BAD_ARG and launches nothing further.  Symmetry of the adjacency is NOT checked: an asymmetric
+ * input gives an unspecified clustering (no out-of-range access).  Negative or non-finite values are refused; a graph whose total weight
+ * (d_ptr[n] + 2 n) * max(values) * 2^30 could reach 2^62, or with 2^31 - 256 or more entries, returns DA_ERR_UNSUPPORTED.
+ * d_work: da_dev_louvain_workspace_bytes(n, d_ptr[n]) bytes, 256-byte aligned (about 56 bytes per adjacency entry: the aggregation sorts
+ * one 64-bit key per entry that leaves its community).  d_membership: n ids from 1 in order of first appearance (device memory).
+ * modularity_out, levels_out and iterations_out[32] (host memory) may be NULL.  n < 0, NULL pointers and a workspace too small for n are
+ * refused before the device is touched; n == 0 returns DA_OK.  The call synchronises `stream`.  da_dev_louvain_workspace_bytes (and the
+ * workspace check above) asks hipcub for the scratch sizes of its sort, reduce-by-key and scan: size queries that launch nothing and need
+ * no device, as in the LSH entries.  n and nnz outside what the call accepts (n > 2^31 - 16, nnz >= 2^31 - 256, negative) are clamped to those
+ * limits for the size; the call itself refuses them. */
+size_t da_dev_louvain_workspace_bytes(int64_t n, int64_t nnz);
+int da_dev_louvain_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, const uint16_t *d_codes, const uint16_t *d_loops,
+                       const double *values, int32_t n_values, double resolution, uint32_t seed, void *d_work, size_t work_bytes,
+                       int32_t *d_membership, double *modularity_out, int32_t *levels_out, int32_t *iterations_out /* [32] */, void *stream);
+
 /* ---- MinHash LSH banding: the threshold graph of ONE set from bucketed candidates, not from all n (n - 1) / 2 pairs ---------------------
  * sig = the n x n_hash signatures of da_minhash_signatures.  bands >= 1, rows >= 1, bands * rows <= n_hash; band t = columns
  * [t * rows, (t + 1) * rows); columns >= bands * rows belong to no band but count.  cand(i, j): some band agrees in all its columns.
