@@ -10,7 +10,7 @@ the hot path in the package: without the HIP library and a GPU every compute
 call raises.
 """
 from ._capi import DynaAlignError, load as load_library  # noqa: F401
-from .clusterbreak import clusterbreak, clusterconsensus, louvain, louvain_csr, louvain_device, louvain_sync_dense, netcluster  # noqa: F401
+from .clusterbreak import clusterbreak, clusterconsensus, clusterconsensus_device, louvain, louvain_csr, louvain_device, louvain_sync_dense, netcluster  # noqa: F401
 from .similarity import (  # noqa: F401
     SimilarityMatrix, get_option, hash_family_seeds, mh_counts, minhash_signatures, nw_pairs,
     pack_sequences, quantile_type7, set_option, similarityMH, similarityMH_cross, similarityMH_edges, similarityNW, similarityNW_cross, similarityNW_edges,
@@ -29,7 +29,7 @@ from .similarity import (  # noqa: F401
 )
 
 __all__ = [
-    "clusterbreak", "clusterconsensus", "netcluster", "louvain", "louvain_csr", "louvain_sync_dense", "louvain_device", "nw_align", "nw_align_long", "nw_align_strings", "NWAlignment",
+    "clusterbreak", "clusterconsensus", "clusterconsensus_device", "netcluster", "louvain", "louvain_csr", "louvain_sync_dense", "louvain_device", "nw_align", "nw_align_long", "nw_align_strings", "NWAlignment",
     "similarityMH", "similarityNW", "similarityMH_cross", "similarityNW_cross", "similarityMH_cross_topk", "similarityNW_cross_topk", "similarityMH_cross_edges", "similarityNW_cross_edges", "nw_code_ranks", "similarityMH_edges", "similarityNW_edges", "similarityNW_edges_long", "similarityNW_cross_edges_long", "nw_value_ranks", "quantile_type7", "minhash_signatures", "mh_counts", "nw_pairs", "hash_family_seeds",
     "SimilarityStats", "compute_similarity_stats", "stats_from_histogram", "similarityMH_stats", "similarityNW_stats", "similarityNW_stats_long",
     "similarityMH_knn", "similarityNW_knn", "knn_dense", "knn_graph", "similarityMH_knn_edges", "similarityNW_knn_edges",

@@ -66,6 +66,12 @@ SIGNATURES = {
     "da_nw_align_long_workspace_bytes": (_sz, [_i64, _i64]),
     "da_dev_nw_align_long_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _sz,
                                           _vp]),
+    "da_cluster_consensus": (_i32, [_vp, _vp, _i64, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "da_dev_cluster_consensus_workspace_bytes": (_sz, [_vp, _i64, _i64, _i32]),
+    "da_dev_cluster_consensus": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "da_dev_consensus_center_sums": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "da_dev_consensus_pick": (_i32, [_vp, _vp, _i64, _vp, _vp]),
+    "da_dev_consensus_vote": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
     "da_similarity_mh_opts": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "da_similarity_nw_opts": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _vp]),
     "da_rccl_available": (_i32, []),

@@ -696,3 +696,59 @@ def clusterconsensus(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4, align_f
                 cons.append(win)
         out.append((cid, "".join(cons)))
     return out
+
+
+def clusterconsensus_device(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4, return_centers=False):
+    """``clusterconsensus`` with both of its phases on the device (da_cluster_consensus): the same CENTER-STAR consensus, by definition the
+    result of ``clusterconsensus(df, align_fn=nw_align_long)`` -- the same list of ``(cluster_id, consensus)``, the same strings, the same
+    errors -- and, for sequences of up to 127 residues, of ``clusterconsensus(df)``.  ``df`` as there: rows of ``(sequence, cluster_id)``,
+    an object array, or a ``clusterbreak`` result.
+
+    Nothing is listed or summed on the host: the kernels of consensus_kernels.hip list the ordered in-cluster pairs for the alignment
+    kernels, add every member's ``matches / length`` terms exactly (63-bit fixed point in two 64-bit limbs) and round the sum to a
+    double as ``math.fsum`` does before choosing the center, then tally the centers' alignments column by column and apply the tie rule
+    of ``clusterconsensus``.  Clusters of one are copied through on the host, unvalidated; if every cluster has one member no device
+    is needed.  Members of clusters of two or more have 0 .. 1024 residues.
+
+    ``return_centers=True``: returns ``(consensus_list, centers)``, ``centers[t]`` the index into the rows of the center of the t-th
+    cluster (of its only member for a cluster of one)."""
+    from .similarity import _as_int, pack_sequences
+    rows = df["clustered_seq"] if isinstance(df, dict) else df
+    order, members, where = [], {}, {}
+    for at, row in enumerate(rows):
+        seq, cid = row[0], row[1]
+        seq = seq.decode("latin-1") if isinstance(seq, bytes) else str(seq)
+        if cid not in members:
+            members[cid] = []
+            where[cid] = []
+            order.append(cid)
+        members[cid].append(seq)
+        where[cid].append(at)
+    # every member of a cluster of two or more, pooled; the library numbers these clusters 0, 1, ... in first-appearance order
+    pooled = [cid for cid in order if len(members[cid]) > 1]
+    cons, center = {}, {}
+    if pooled:
+        pool, index, cluster_of = [], [], []
+        for k, cid in enumerate(pooled):
+            pool.extend(members[cid])
+            index.extend(where[cid])
+            cluster_of.extend([k] * len(members[cid]))
+        lib = _capi.load()
+        res, off = pack_sequences(pool)
+        cl = np.asarray(cluster_of, np.int32)
+        ld = max(int(np.diff(off).max()), 1)
+        out = np.zeros((len(pooled), ld), np.uint8)
+        out_len = np.zeros(len(pooled), np.int32)
+        out_center = np.zeros(len(pooled), np.int32)
+        name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+        _capi.check(lib.da_cluster_consensus(res.ctypes.data, off.ctypes.data, len(pool), cl.ctypes.data, len(pooled), name,
+                                             _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), out.ctypes.data, ld, out_len.ctypes.data,
+                                             out_center.ctypes.data))
+        raw = out.tobytes()
+        for k, cid in enumerate(pooled):
+            cons[cid] = raw[k * ld:k * ld + int(out_len[k])].decode("latin-1")
+            center[cid] = index[int(out_center[k])]
+    result = [(cid, cons[cid] if cid in cons else members[cid][0]) for cid in order]
+    if return_centers:
+        return result, [center[cid] if cid in center else where[cid][0] for cid in order]
+    return result

@@ -3257,6 +3257,199 @@ int da_nw_align_long_pairs(const uint8_t *x_residues, const int64_t *x_offsets, 
   return DA_OK;
 }
 
+// ---- the center-star consensus of clusters (consensus_kernels.hip) on top of the two alignment kernels ---------------------------------------
+// the pooled table on the host: cluster_ptr[0] == 0, every cluster has a member, the last entry is the number of sequences
+static int cons_table_check(const int64_t *cluster_ptr, int64_t n, int64_t clusters) {
+  if (!cluster_ptr) return fail(DA_ERR_BAD_ARG, "cluster_ptr is NULL");
+  if (cluster_ptr[0] != 0) return fail(DA_ERR_BAD_ARG, "cluster_ptr[0] must be 0");
+  for (int64_t k = 0; k < clusters; ++k)
+    if (cluster_ptr[k + 1] <= cluster_ptr[k]) return fail(DA_ERR_BAD_ARG, "cluster %lld has no member", (long long)k);
+  if (cluster_ptr[clusters] != n) return fail(DA_ERR_BAD_ARG, "cluster_ptr ends at %lld, not at n = %lld", (long long)cluster_ptr[clusters], (long long)n);
+  return DA_OK;
+}
+
+size_t da_dev_cluster_consensus_workspace_bytes(const int64_t *cluster_ptr, int64_t clusters, int64_t max_len, int minimal) {
+  return cluster_consensus_workspace_bytes(cluster_ptr, clusters, max_len, minimal != 0);
+}
+
+int da_dev_cluster_consensus(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, const int64_t *cluster_ptr, const int64_t *d_cluster_ptr,
+                             int64_t clusters, int64_t max_len, int matrix_id, int gap_open, int gap_ext, uint8_t *d_cons, int64_t ld_cons,
+                             int32_t *d_cons_len, int32_t *d_center, void *d_work, size_t work_bytes, void *stream) {
+  if (n < 0 || clusters < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (clusters == 0) return n == 0 ? DA_OK : fail(DA_ERR_BAD_ARG, "no clusters for %lld sequences", (long long)n);
+  if (!d_codes || !d_offsets || !d_cluster_ptr || !d_cons || !d_cons_len || !d_center || !d_work) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (n > 0x7fffffffLL) return fail(DA_ERR_UNSUPPORTED, "more than 2^31 - 1 pooled sequences");
+  int rc;
+  if ((rc = cons_table_check(cluster_ptr, n, clusters)) != DA_OK) return rc;
+  if (max_len < 0) return fail(DA_ERR_BAD_ARG, "negative max_len");
+  if (max_len > 1024) return fail(DA_ERR_UNSUPPORTED, "the alignment kernel takes sequences up to 1024 residues (max_len = %lld)", (long long)max_len);
+  if (ld_cons < max_len) return fail(DA_ERR_BAD_ARG, "ld_cons = %lld is smaller than the longest member, %lld", (long long)ld_cons, (long long)max_len);
+  if (!matrix_table_host(matrix_id)) return fail(DA_ERR_BAD_ARG, "matrix id %d out of range", matrix_id);
+  if ((rc = require_device()) != DA_OK) return rc;
+  return launch_cluster_consensus(d_codes, d_offsets, n, cluster_ptr, d_cluster_ptr, clusters, max_len, matrix_id, gap_open, gap_ext, d_cons, ld_cons,
+                                  d_cons_len, d_center, d_work, work_bytes, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_consensus_center_sums(const int32_t *d_len, const int32_t *d_matches, int64_t pair_begin, int64_t pairs, const int64_t *cluster_ptr,
+                                 const int64_t *d_cluster_ptr, int64_t clusters, int64_t *d_pair_ptr, uint64_t *d_sums, void *stream) {
+  if (pairs < 0 || pair_begin < 0 || clusters <= 0) return fail(DA_ERR_BAD_ARG, "negative count or no clusters");
+  if (!d_len || !d_matches || !d_cluster_ptr || !d_pair_ptr || !d_sums) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  int rc;
+  if ((rc = cons_table_check(cluster_ptr, cluster_ptr ? cluster_ptr[clusters] : 0, clusters)) != DA_OK) return rc;
+  std::vector<int64_t> pp((size_t)clusters + 1, 0);
+  for (int64_t k = 0; k < clusters; ++k) {
+    const int64_t c = cluster_ptr[k + 1] - cluster_ptr[k];
+    pp[(size_t)k + 1] = pp[(size_t)k] + c * (c - 1);
+  }
+  if (pair_begin + pairs > pp[(size_t)clusters])
+    return fail(DA_ERR_BAD_ARG, "pairs [%lld, %lld) reach past the table's %lld", (long long)pair_begin, (long long)(pair_begin + pairs),
+                (long long)pp[(size_t)clusters]);
+  if ((rc = require_device()) != DA_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = launch_cons_pair_ptr(d_cluster_ptr, clusters, d_pair_ptr, s)) != DA_OK) return rc;
+  return launch_cons_center_sums(d_len, d_matches, pair_begin, pair_begin + pairs, cluster_ptr, pp.data(), d_cluster_ptr, d_pair_ptr, clusters, d_sums, s);
+}
+
+int da_dev_consensus_pick(const uint64_t *d_sums, const int64_t *d_cluster_ptr, int64_t clusters, int32_t *d_center, void *stream) {
+  if (clusters < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (clusters == 0) return DA_OK;
+  if (!d_sums || !d_cluster_ptr || !d_center) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  int rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  return launch_cons_pick(d_sums, d_cluster_ptr, clusters, d_center, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_consensus_vote(const uint8_t *d_codes, const int64_t *d_offsets, const int64_t *d_cluster_ptr, const int32_t *d_center, int64_t cluster_begin,
+                          int64_t cluster_count, const uint8_t *d_ops, int64_t ld_ops, const int32_t *d_len, int64_t row_begin, int64_t rows,
+                          uint32_t *d_carry, uint8_t *d_cons, int64_t ld_cons, int32_t *d_cons_len, int64_t max_len, void *stream) {
+  if (cluster_begin < 0 || cluster_count < 0 || row_begin < 0 || rows < 0 || ld_ops < 0 || ld_cons < 0 || max_len < 0)
+    return fail(DA_ERR_BAD_ARG, "negative count");
+  if (cluster_count == 0) return DA_OK;
+  if (!d_codes || !d_offsets || !d_cluster_ptr || !d_center || !d_carry || !d_cons || !d_cons_len || (rows > 0 && !d_ops))
+    return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (max_len > 1024) return fail(DA_ERR_UNSUPPORTED, "centers have up to 1024 residues (max_len = %lld)", (long long)max_len);
+  if (ld_cons < max_len) return fail(DA_ERR_BAD_ARG, "ld_cons = %lld is smaller than the longest member, %lld", (long long)ld_cons, (long long)max_len);
+  int rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  return launch_cons_vote(d_codes, d_offsets, d_cluster_ptr, d_center, cluster_begin, cluster_count, d_ops, ld_ops, d_len, row_begin, row_begin + rows,
+                          d_carry, d_cons, ld_cons, d_cons_len, max_len, static_cast<hipStream_t>(stream));
+}
+
+int da_cluster_consensus(const uint8_t *residues, const int64_t *offsets, int64_t n, const int32_t *cluster_of, int64_t clusters, const char *matrix_name,
+                         int gap_open, int gap_ext, uint8_t *cons_out, int64_t ld_cons, int32_t *cons_len_out, int32_t *center_out) {
+  const int mid = da_matrix_id(matrix_name);               // before anything else, as in da_nw_align_long_pairs
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  if (n < 0 || clusters < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (n == 0 && clusters == 0) return DA_OK;               // nothing to write
+  if (n > 0x7fffffffLL) return fail(DA_ERR_UNSUPPORTED, "more than 2^31 - 1 sequences");
+  if (!residues || !cluster_of || !cons_out || !cons_len_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t total = 0, longest = 0;
+  int rc;
+  if ((rc = check_offsets(offsets, n, &total, &longest)) != DA_OK) return rc;
+  std::vector<int64_t> size((size_t)clusters, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    if (cluster_of[i] < 0 || cluster_of[i] >= clusters)
+      return fail(DA_ERR_BAD_ARG, "sequence %lld: cluster %d is outside [0, %lld)", (long long)i, (int)cluster_of[i], (long long)clusters);
+    ++size[(size_t)cluster_of[i]];
+  }
+  for (int64_t k = 0; k < clusters; ++k)
+    if (size[(size_t)k] == 0) return fail(DA_ERR_BAD_ARG, "cluster %lld has no member", (long long)k);
+  // the pool: the members of every cluster of two or more, clusters ascending, members in input order -- what both alignment calls index
+  std::vector<int64_t> pool_k, cptr(1, 0), slot((size_t)clusters, -1);
+  for (int64_t k = 0; k < clusters; ++k)
+    if (size[(size_t)k] > 1) { slot[(size_t)k] = (int64_t)pool_k.size(); pool_k.push_back(k); cptr.push_back(cptr.back() + size[(size_t)k]); }
+  const int64_t pk = (int64_t)pool_k.size(), pn = cptr.back();
+  std::vector<int32_t> member((size_t)pn), single((size_t)clusters, -1);
+  {
+    std::vector<int64_t> fill(cptr.begin(), cptr.end() - 1);
+    for (int64_t i = 0; i < n; ++i) {
+      const int64_t s = slot[(size_t)cluster_of[i]];
+      if (s >= 0) member[(size_t)fill[(size_t)s]++] = (int32_t)i; else single[(size_t)cluster_of[i]] = (int32_t)i;
+    }
+  }
+  auto len_of = [&](int64_t g) { return offsets[member[(size_t)g] + 1] - offsets[member[(size_t)g]]; };
+  // the length refusal, worded as the first alignment call words it: pairs in its order, i ascending then j != i ascending.  The first pair of a
+  // cluster with a long member is (0, 1) if member 0 is long, else (0, the first long member).
+  int64_t pair_base = 0, pool_longest = 0;
+  for (int64_t s = 0; s < pk; ++s) {
+    const int64_t b = cptr[(size_t)s], c = cptr[(size_t)s + 1] - b;
+    for (int64_t t = 0; t < c; ++t) {
+      if (len_of(b + t) <= 1024) { pool_longest = std::max(pool_longest, len_of(b + t)); continue; }
+      const int64_t j = t == 0 ? 1 : t;
+      return fail(DA_ERR_UNSUPPORTED, "the alignment kernel takes sequences up to %d residues (pair %lld: %lld and %lld)", 1024,
+                  (long long)(pair_base + j - 1), (long long)len_of(b), (long long)len_of(b + j));
+    }
+    pair_base += c * (c - 1);
+  }
+  if (ld_cons < longest) return fail(DA_ERR_BAD_ARG, "ld_cons = %lld is smaller than the longest member, %lld", (long long)ld_cons, (long long)longest);
+  // the residue error of the first alignment call, from every member's first bad position: member i (not empty) meets, in this order, its own
+  // residue 0, the first bad residue of its first partner, its own first bad residue, then the first bad residue of any other member
+  {
+    const std::vector<int32_t> bad = nw_first_bad(residues, offsets, n);
+    auto bad_of = [&](int64_t g) { return bad[(size_t)member[(size_t)g]]; };
+    auto chr = [&](int64_t g) { return (char)residues[offsets[member[(size_t)g]] + bad_of(g)]; };
+    for (int64_t s = 0; s < pk; ++s) {
+      const int64_t b = cptr[(size_t)s], c = cptr[(size_t)s + 1] - b;
+      int64_t b1 = -1, b2 = -1;                             // the first two members with a bad residue
+      for (int64_t t = 0; t < c && b2 < 0; ++t)
+        if (bad_of(b + t) >= 0) { if (b1 < 0) b1 = t; else b2 = t; }
+      if (b1 < 0) continue;
+      for (int64_t i = 0; i < c; ++i) {
+        if (len_of(b + i) == 0) continue;                   // no row runs
+        if (bad_of(b + i) == 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", chr(b + i));
+        const int64_t j0 = i == 0 ? 1 : 0;
+        if (bad_of(b + j0) >= 0) return fail(DA_ERR_BAD_RESIDUE_SEQ2, "Invalid amino acid in sequence2: %c", chr(b + j0));
+        if (bad_of(b + i) > 0) return fail(DA_ERR_BAD_RESIDUE_SEQ1, "Invalid amino acid in sequence1: %c", chr(b + i));
+        const int64_t other = b1 != i ? b1 : b2;
+        if (other >= 0) return fail(DA_ERR_BAD_RESIDUE_SEQ2, "Invalid amino acid in sequence2: %c", chr(b + other));
+      }
+    }
+  }
+  if (pk > 0 && (rc = require_device()) != DA_OK) return rc;   // nothing is written without one
+  // a cluster of one is its member, copied through
+  for (int64_t k = 0; k < clusters; ++k) {
+    if (single[(size_t)k] < 0) continue;
+    const int64_t i = single[(size_t)k], ln = offsets[i + 1] - offsets[i];
+    memset(cons_out + (size_t)k * (size_t)ld_cons, 0, (size_t)ld_cons);
+    memcpy(cons_out + (size_t)k * (size_t)ld_cons, residues + offsets[i], (size_t)ln);
+    cons_len_out[k] = (int32_t)ln;
+    if (center_out) center_out[k] = (int32_t)i;
+  }
+  if (pk == 0) return DA_OK;                                // no device needed
+  std::vector<int64_t> poff((size_t)pn + 1, 0);
+  for (int64_t g = 0; g < pn; ++g) poff[(size_t)g + 1] = poff[(size_t)g] + len_of(g);
+  std::vector<uint8_t> pres((size_t)std::max<int64_t>(poff[(size_t)pn], 1));
+  for (int64_t g = 0; g < pn; ++g) memcpy(pres.data() + poff[(size_t)g], residues + offsets[member[(size_t)g]], (size_t)len_of(g));
+  NwCodes pool;
+  if ((rc = pool.upload(pres.data(), poff.data(), pn, poff[(size_t)pn])) != DA_OK) return rc;
+  const int64_t ldc = std::max<int64_t>(pool_longest, 1);
+  DevBuf dptr, dcons, dlen, dcen, work;
+  if ((rc = dptr.alloc((size_t)(pk + 1) * sizeof(int64_t))) != DA_OK || (rc = dcons.alloc((size_t)pk * (size_t)ldc)) != DA_OK ||
+      (rc = dlen.alloc((size_t)pk * sizeof(int32_t))) != DA_OK || (rc = dcen.alloc((size_t)pk * sizeof(int32_t))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(dptr.p, cptr.data(), (size_t)(pk + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+  // blocks within DYNAALIGN_BLOCK_BYTES (half of the free memory without it), never less than blocks of 64 pairs take
+  const size_t wbytes = std::max(std::min(cluster_consensus_workspace_bytes(cptr.data(), pk, pool_longest, false), block_budget()),
+                                 cluster_consensus_workspace_bytes(cptr.data(), pk, pool_longest, true));
+  if ((rc = work.alloc(wbytes)) != DA_OK) return rc;
+  if ((rc = launch_cluster_consensus(pool.codes.as<uint8_t>(), pool.in.off.as<int64_t>(), pn, cptr.data(), dptr.as<int64_t>(), pk, pool_longest, mid,
+                                     gap_open, gap_ext, dcons.as<uint8_t>(), ldc, dlen.as<int32_t>(), dcen.as<int32_t>(), work.p, wbytes, nullptr)) != DA_OK)
+    return rc;
+  std::vector<uint8_t> hcons((size_t)pk * (size_t)ldc);
+  std::vector<int32_t> hlen((size_t)pk), hcen((size_t)pk);
+  DA_HIP_TRY(hipMemcpy(hcons.data(), dcons.p, hcons.size(), hipMemcpyDeviceToHost));
+  DA_HIP_TRY(hipMemcpy(hlen.data(), dlen.p, (size_t)pk * sizeof(int32_t), hipMemcpyDeviceToHost));
+  DA_HIP_TRY(hipMemcpy(hcen.data(), dcen.p, (size_t)pk * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if ((rc = sync_or_fail("the consensus kernels failed")) != DA_OK) return rc;
+  for (int64_t s = 0; s < pk; ++s) {
+    const int64_t k = pool_k[(size_t)s];
+    memset(cons_out + (size_t)k * (size_t)ld_cons, 0, (size_t)ld_cons);
+    memcpy(cons_out + (size_t)k * (size_t)ld_cons, hcons.data() + (size_t)s * (size_t)ldc, (size_t)hlen[(size_t)s]);
+    cons_len_out[k] = hlen[(size_t)s];
+    if (center_out) center_out[k] = member[(size_t)hcen[(size_t)s]];
+  }
+  return DA_OK;
+}
+
 
 // ---- two sets, threshold form: the entries of the rectangle that pass a threshold as a sorted edge list (rect_edges_kernels.hip) ---------
 static int rect_block_check(const void *a, const void *b, const void *c, int64_t rows, int64_t n, int64_t ld, int nbins) {

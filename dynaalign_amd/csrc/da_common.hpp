@@ -389,6 +389,26 @@ int launch_nw_align_long(const uint8_t *d_x_codes, const int64_t *d_x_off, int64
                          const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pair_base, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
                          uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, int64_t max_len, void *d_work,
                          size_t work_bytes, hipStream_t stream);
+// consensus_kernels.hip: the center-star consensus of a pooled cluster table (da_dev_cluster_consensus and its pieces).  Pairs are numbered per
+// cluster i ascending then j != i ascending (d_pair_ptr: the running sums of c (c - 1), int64), rows (center, j != center) j ascending.
+// launch_cons_pairs lists entries [p0, p1) of the pairs (d_center == NULL) or of the rows; launch_cons_center_sums ADDS the fixed-point terms of
+// pairs [p0, p1) to the two 64-bit limbs of their members (the host copies of the two tables find the members the block touches);
+// launch_cons_pick rounds the limbs to 53 bits and writes every cluster's center as a pooled index; launch_cons_vote tallies the ops rows
+// [q_lo, q_hi) for clusters [k0, k0 + kcount) and writes the consensus letters of every cluster whose rows end inside the range.
+int launch_cons_pair_ptr(const int64_t *d_cluster_ptr, int64_t clusters, int64_t *d_pair_ptr, hipStream_t stream);
+int launch_cons_pairs(const int64_t *d_cluster_ptr, const int64_t *d_pair_ptr, int64_t clusters, const int32_t *d_center, int64_t p0, int64_t p1,
+                      int32_t *d_pair_x, int32_t *d_pair_y, hipStream_t stream);
+int launch_cons_center_sums(const int32_t *d_len, const int32_t *d_matches, int64_t p0, int64_t p1, const int64_t *cluster_ptr_host,
+                            const int64_t *pair_ptr_host, const int64_t *d_cluster_ptr, const int64_t *d_pair_ptr, int64_t clusters, uint64_t *d_sums,
+                            hipStream_t stream);
+int launch_cons_pick(const uint64_t *d_sums, const int64_t *d_cluster_ptr, int64_t clusters, int32_t *d_center, hipStream_t stream);
+int launch_cons_vote(const uint8_t *d_codes, const int64_t *d_off, const int64_t *d_cluster_ptr, const int32_t *d_center, int64_t k0, int64_t kcount,
+                     const uint8_t *d_ops, int64_t ld_ops, const int32_t *d_len, int64_t q_lo, int64_t q_hi, uint32_t *d_carry, uint8_t *d_cons,
+                     int64_t ld_cons, int32_t *d_cons_len, int64_t max_len, hipStream_t stream);
+size_t cluster_consensus_workspace_bytes(const int64_t *cluster_ptr_host, int64_t clusters, int64_t max_len, bool minimal);
+int launch_cluster_consensus(const uint8_t *d_codes, const int64_t *d_off, int64_t n, const int64_t *cluster_ptr_host, const int64_t *d_cluster_ptr,
+                             int64_t clusters, int64_t max_len, int matrix_id, int gap_open, int gap_ext, uint8_t *d_cons, int64_t ld_cons,
+                             int32_t *d_cons_len, int32_t *d_center, void *d_work, size_t work_bytes, hipStream_t stream);
 // jaccard_kernels.hip: the exact Jaccard index of k-shingle sets (da_dev_jaccard_sets / da_dev_jaccard_rect).  Keys are uint32 for k <= 4 and uint64
 // for k 5 .. 8; a set is the ascending distinct keys of a sequence, [n][ld_keys] keys + [n] uint8 counts, ld_keys >= jaccard_sets_ld(max_len, k).
 // The rectangle is rows x columns of ONE set operand, DA_OUT_COMPACT (intersection << 8 | union) or DA_OUT_F64.

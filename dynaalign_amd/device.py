@@ -398,6 +398,110 @@ def nw_align_long_pairs(dx, dy, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, 
     return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
 
 
+def _cluster_table(cluster_ptr, device):
+    """-> (host int64 array, device int64 tensor) of a pooled cluster table"""
+    if isinstance(cluster_ptr, torch.Tensor):
+        host = np.ascontiguousarray(cluster_ptr.detach().cpu().numpy(), np.int64)
+    else:
+        host = np.ascontiguousarray(cluster_ptr, np.int64)
+    if host.ndim != 1 or len(host) < 1:
+        raise ValueError("cluster_ptr must hold clusters + 1 entries")
+    return host, torch.from_numpy(host.copy()).to(device)
+
+
+def cluster_consensus_workspace_bytes(cluster_ptr, max_len, minimal=False):
+    host = np.ascontiguousarray(cluster_ptr, np.int64)
+    return int(_capi.load().da_dev_cluster_consensus_workspace_bytes(host.ctypes.data, len(host) - 1, int(max_len), int(bool(minimal))))
+
+
+def cluster_consensus(ds, cluster_ptr, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, work=None):
+    """The center-star consensus of pooled clusters on the device (da_dev_cluster_consensus): cluster k is the sequences
+    ds[cluster_ptr[k] : cluster_ptr[k + 1]], at least one each; ds.codes must be filled (nw_encode) and every residue valid.  Returns
+    ``(cons, cons_len, center)``: a (clusters, max(ds.max_len, 1)) uint8 tensor of letters (bytes past a row's length are not written),
+    the int32 lengths and the int32 pooled index of each cluster's center.  Asynchronous; nothing returns to the host between the
+    center choice and the column vote.  work: a uint8 device tensor of at least cluster_consensus_workspace_bytes(cluster_ptr,
+    ds.max_len, minimal=True) bytes (allocated at the size of the largest blocks if None)."""
+    lib = _capi.load()
+    if ds.codes is None:
+        raise ValueError("call nw_encode first")
+    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
+    if mid < 0:
+        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    dev = ds.residues.device
+    host, dptr = _cluster_table(cluster_ptr, dev)
+    clusters = len(host) - 1
+    ld = max(int(ds.max_len), 1)
+    cons = torch.zeros((max(clusters, 1), ld), dtype=torch.uint8, device=dev)
+    cons_len = torch.zeros(max(clusters, 1), dtype=torch.int32, device=dev)
+    center = torch.zeros(max(clusters, 1), dtype=torch.int32, device=dev)
+    if work is None:
+        work = torch.empty(max(cluster_consensus_workspace_bytes(host, ds.max_len), 16), dtype=torch.uint8, device=dev)
+    _call(lib.da_dev_cluster_consensus, ds.codes.data_ptr(), ds.offsets.data_ptr(), ds.n, host.ctypes.data, dptr.data_ptr(), clusters,
+          int(ds.max_len), mid, int(gap_open), int(gap_ext), cons.data_ptr(), ld, cons_len.data_ptr(), center.data_ptr(), work.data_ptr(),
+          work.numel(), _stream())
+    return cons[:clusters], cons_len[:clusters], center[:clusters]
+
+
+def consensus_center_sums(length, matches, cluster_ptr, pair_begin=0, sums=None):
+    """One block of phase 1 (da_dev_consensus_center_sums): length / matches are int32 device tensors with the alignment results of the
+    ordered in-cluster pairs pair_begin, pair_begin + 1, ... (per cluster i ascending, then j != i ascending); every matches / length
+    is added, exactly, to its member's two 64-bit limbs.  sums: the (members, 2) int64 tensor (low, high limb) of an earlier block, or
+    None to start from zero.  Returns sums."""
+    lib = _capi.load()
+    _require_cuda(length, "length")
+    _require_cuda(matches, "matches")
+    if length.dtype != torch.int32 or matches.dtype != torch.int32 or length.numel() != matches.numel():
+        raise ValueError("length and matches must be int32 tensors of the same length")
+    host, dptr = _cluster_table(cluster_ptr, length.device)
+    clusters = len(host) - 1
+    if sums is None:
+        sums = torch.zeros((max(int(host[-1]), 1), 2), dtype=torch.int64, device=length.device)
+    scratch = torch.empty(clusters + 1, dtype=torch.int64, device=length.device)
+    length, matches = length.contiguous(), matches.contiguous()
+    _call(lib.da_dev_consensus_center_sums, length.data_ptr(), matches.data_ptr(), int(pair_begin), length.numel(), host.ctypes.data,
+          dptr.data_ptr(), clusters, scratch.data_ptr(), sums.data_ptr(), _stream())
+    return sums
+
+
+def consensus_pick(sums, cluster_ptr):
+    """The centers (da_dev_consensus_pick): per cluster the pooled index of the member whose sum, rounded to a double as math.fsum
+    rounds, is largest; the lowest index among equals.  Returns an int32 tensor."""
+    lib = _capi.load()
+    _require_cuda(sums, "sums")
+    host, dptr = _cluster_table(cluster_ptr, sums.device)
+    clusters = len(host) - 1
+    center = torch.zeros(max(clusters, 1), dtype=torch.int32, device=sums.device)
+    _call(lib.da_dev_consensus_pick, sums.data_ptr(), dptr.data_ptr(), clusters, center.data_ptr(), _stream())
+    return center[:clusters]
+
+
+def consensus_vote(ds, cluster_ptr, center, ops, length=None):
+    """The column vote (da_dev_consensus_vote) of every cluster on given ops rows: center an int32 device tensor of pooled indices,
+    ops a (rows, ld_ops) uint8 tensor holding, cluster after cluster, the paths of the center as sequence1 with every other member in
+    ascending order ('D' / 'U' / 'L', 0 past a row's end), length their int32 lengths or None.  Returns ``(cons, cons_len)``."""
+    lib = _capi.load()
+    if ds.codes is None:
+        raise ValueError("call nw_encode first")
+    dev = ds.residues.device
+    host, dptr = _cluster_table(cluster_ptr, dev)
+    clusters = len(host) - 1
+    rows = int(host[-1]) - clusters
+    _require_cuda(ops, "ops")
+    if ops.dtype != torch.uint8 or ops.dim() != 2 or ops.shape[0] < rows:
+        raise ValueError("ops must be a (rows, ld_ops) uint8 tensor with a row per member other than the center")
+    ops = ops.contiguous()
+    ld = max(int(ds.max_len), 1)
+    cons = torch.zeros((max(clusters, 1), ld), dtype=torch.uint8, device=dev)
+    cons_len = torch.zeros(max(clusters, 1), dtype=torch.int32, device=dev)
+    carry = torch.empty(25 * ld, dtype=torch.int32, device=dev)
+    center = center.contiguous()
+    length = None if length is None else length.contiguous()
+    _call(lib.da_dev_consensus_vote, ds.codes.data_ptr(), ds.offsets.data_ptr(), dptr.data_ptr(), center.data_ptr(), 0, clusters, ops.data_ptr(),
+          ops.shape[1], None if length is None else length.data_ptr(), 0, rows, carry.data_ptr(), cons.data_ptr(), ld,
+          cons_len.data_ptr(), int(ds.max_len), _stream())
+    return cons[:clusters], cons_len[:clusters]
+
+
 def symmetrize(mat, n, kind=DA_OUT_F64):
     _call(_capi.load().da_dev_symmetrize, mat.data_ptr(), n, mat.stride(0), kind, _stream())
     return mat

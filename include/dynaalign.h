@@ -51,6 +51,8 @@ extern "C" {
  * (the two-set threshold entry points -- da_similarity_*_cross_edges_begin, da_dev_similarity_mh_cross_edges, da_dev_rect_histogram,
  *  da_dev_threshold_rows_* -- likewise)
  * (the alignment-path entry points -- da_nw_align_pairs, da_dev_nw_align_pairs, da_nw_align_workspace_bytes and their _long forms -- likewise)
+ * (the cluster-consensus entry points -- da_cluster_consensus, da_dev_cluster_consensus[_workspace_bytes], da_dev_consensus_[center_sums | pick |
+ *  vote] -- likewise)
  * (the exact-Jaccard entry points -- da_similarity_jaccard[_cross[_topk] | _knn | _edges[_begin]], da_dev_jaccard_sets[_ld], da_dev_jaccard_rect -- likewise)
  * (their _long forms -- da_similarity_jaccard[_cross[_topk | _edges] | _knn | _edges | _stats]_long[_begin], da_jaccard_sets_long_ld,
  *  da_dev_jaccard_sets_long, da_dev_jaccard_rect_long -- likewise)
@@ -378,6 +380,59 @@ int da_dev_nw_align_long_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offs
                                int matrix_id, int gap_open, int gap_ext,
                                uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score,
                                int64_t max_len, void *d_work, size_t work_bytes, void *stream);
+
+/* ---- one consensus sequence per cluster: the center-star consensus on the alignments above (consensus_kernels.hip) ----
+ * For a cluster with members s_0 .. s_{c-1} (input order, duplicates kept): c == 1 gives the member itself, copied through unvalidated; otherwise
+ * the CENTER is the member i with the largest correctly rounded sum over j != i of matches(i, j) / length(i, j) of the alignments of s_i as
+ * sequence1 with s_j (two empty strings count 0.0; ties to the lowest i) -- math.fsum of the doubles, reproduced as an exact 63-bit fixed-point
+ * sum in two 64-bit limbs rounded to 53 bits, ties to even, before comparing.  The center is then aligned as sequence1 with every other member;
+ * column p of the tally holds the center's residue once and, per other member, the residue a D step puts opposite p or '-' for a U step (L steps
+ * are ignored).  The most frequent symbol wins; among tied symbols the center's residue if it is one of them, otherwise the earliest in
+ * "ARNDCQEGHILKMFPSTWYVBZX*-"; columns won by '-' are dropped.
+ *   cluster_of   : [n] int32, the cluster of every sequence, 0 .. clusters - 1
+ *   cons_out     : [clusters][ld_cons] bytes, row k the consensus of cluster k as letters, 0 past its length
+ *   cons_len_out : [clusters] int32         center_out : [clusters] int32 or NULL, the input index of each cluster's center
+ * Validation, before any device is needed, in this order: the matrix name (DA_ERR_BAD_MATRIX); n == clusters == 0 returns DA_OK; negative counts,
+ * NULL pointers, the offsets, a cluster_of outside its range, a cluster without a member -> DA_ERR_BAD_ARG; a member of more than 1024 residues in a
+ * cluster of two or more -> DA_ERR_UNSUPPORTED, in the words of da_nw_align_long_pairs; ld_cons smaller than the longest member -> DA_ERR_BAD_ARG;
+ * then the residue error da_nw_align_long_pairs raises first on all ordered pairs of all clusters of two or more (clusters ascending, i ascending,
+ * j != i ascending, each pair in calc's lazy order as above), derived from every member's first bad position; then DA_ERR_NO_DEVICE (not when every
+ * cluster has one member).  If every member of a cluster of two or more has at most 127 residues the lane-per-pair kernels align, otherwise every
+ * pair takes a wavefront; the result is the same.  Both phases work in blocks within DYNAALIGN_BLOCK_BYTES (half of the free device memory
+ * without it).  Single device. */
+int da_cluster_consensus(const uint8_t *residues, const int64_t *offsets, int64_t n, const int32_t *cluster_of, int64_t clusters,
+                         const char *matrix_name, int gap_open, int gap_ext, uint8_t *cons_out, int64_t ld_cons, int32_t *cons_len_out,
+                         int32_t *center_out);
+/* On device pointers, asynchronous on `stream`, nothing returning to the host between the phases.  The n sequences (codes and offsets as
+ * da_dev_nw_encode leaves them, all residues valid) are POOLED: cluster k is sequences cluster_ptr[k] .. cluster_ptr[k + 1] - 1, at least one each,
+ * cluster_ptr[0] == 0 and cluster_ptr[clusters] == n.  The table is given twice: cluster_ptr on the host, which plans the blocks and is read only
+ * during the call, and d_cluster_ptr, the same int64 values on the device, which the kernels read.  max_len: the longest sequence (<= 1024, else
+ * DA_ERR_UNSUPPORTED; <= 127 selects the lane-per-pair kernels).  d_cons [clusters][ld_cons] (ld_cons >= max_len; bytes past a row's length are
+ * not written), d_cons_len [clusters], d_center [clusters]: the center as a pooled index.  d_work: da_dev_cluster_consensus_workspace_bytes(...,
+ * minimal = 1) bytes at least (blocks of 64 pairs), with minimal = 0 what the largest blocks take (at most 2^20 pairs or rows each); anything in
+ * between means smaller blocks.  Phase 1 cuts its blocks of pairs anywhere; phase 2 takes groups of whole clusters, and a cluster with more rows
+ * than a block holds alone, in member chunks, its tally carried in the workspace. */
+size_t da_dev_cluster_consensus_workspace_bytes(const int64_t *cluster_ptr, int64_t clusters, int64_t max_len, int minimal);
+int da_dev_cluster_consensus(const uint8_t *d_codes, const int64_t *d_offsets, int64_t n, const int64_t *cluster_ptr, const int64_t *d_cluster_ptr,
+                             int64_t clusters, int64_t max_len, int matrix_id, int gap_open, int gap_ext, uint8_t *d_cons, int64_t ld_cons,
+                             int32_t *d_cons_len, int32_t *d_center, void *d_work, size_t work_bytes, void *stream);
+/* The pieces.  PAIRS are numbered per cluster i ascending then j != i ascending, cluster k from the running sum of c (c - 1); ROWS are
+ * (center, j != center), j ascending, cluster k from cluster_ptr[k] - k.
+ * da_dev_consensus_center_sums: d_len / d_matches hold the results of pairs [pair_begin, pair_begin + pairs) (entry 0 is pair_begin); every term
+ * matches / length (0 when length <= 0) is ADDED as 63-bit fixed point to its member's two limbs d_sums[2 g], d_sums[2 g + 1] (low, high; the
+ * caller clears them first).  Consecutive calls may cut the pairs anywhere.  d_pair_ptr: [clusters + 1] int64 of scratch the call fills.
+ * da_dev_consensus_pick: d_center[k] = the pooled index of the member of cluster k whose sum, rounded to 53 bits ties to even, is largest (the
+ * lowest among equals).
+ * da_dev_consensus_vote: for clusters [cluster_begin, cluster_begin + cluster_count), one workgroup each, the ops rows [row_begin, row_begin + rows)
+ * at d_ops (row_begin first; d_len their lengths, or NULL: a row ends at its first 0 byte or at ld_ops).  A cluster whose rows all lie in the range
+ * gets its consensus row and length; one that starts before it takes its tally from d_carry (25 * len(center) uint32), one that goes on past it
+ * leaves it there. */
+int da_dev_consensus_center_sums(const int32_t *d_len, const int32_t *d_matches, int64_t pair_begin, int64_t pairs, const int64_t *cluster_ptr,
+                                 const int64_t *d_cluster_ptr, int64_t clusters, int64_t *d_pair_ptr, uint64_t *d_sums, void *stream);
+int da_dev_consensus_pick(const uint64_t *d_sums, const int64_t *d_cluster_ptr, int64_t clusters, int32_t *d_center, void *stream);
+int da_dev_consensus_vote(const uint8_t *d_codes, const int64_t *d_offsets, const int64_t *d_cluster_ptr, const int32_t *d_center,
+                          int64_t cluster_begin, int64_t cluster_count, const uint8_t *d_ops, int64_t ld_ops, const int32_t *d_len, int64_t row_begin,
+                          int64_t rows, uint32_t *d_carry, uint8_t *d_cons, int64_t ld_cons, int32_t *d_cons_len, int64_t max_len, void *stream);
 
 /* ---- device-pointer entry points (bench / multi-GPU sharding) ------------ */
 
