@@ -3721,7 +3721,7 @@ int da_dev_similarity_mh_cross_edges(const uint8_t *d_x_residues, const int64_t 
                           }, threshold_out, n_edges_out);
 }
 
-// ---- MinHash LSH banding (lsh_kernels.hip) ---------------------------------------------------------------------------------------------
+// ---- MinHash LSH banding: the one-set entries and the pipelines of both forms (lsh_kernels.hip) ----------------------------------------------
 }  // extern "C"  (reopened below)
 namespace {
 struct LshRoute { int64_t buckets = 0, incidences = 0, verified = 0, edges = 0; };
@@ -3753,38 +3753,53 @@ uint32_t lsh_c_min(int n_hash, double threshold) {
   while (c <= (uint32_t)n_hash && !(values[c] >= threshold)) ++c;
   return c;
 }
-// Steps 1 - 3 on resident signatures, what the edge list and the nearest-neighbour lists share: the buckets (the route's counts, the cap),
-// the verdict of every incidence slot (cnt, keep), the kept slots per chunk of 64 and their exclusive sum (coff); `kept` and `firsts` (the
-// distinct candidate pairs) are read back, so the stream is synchronised.  The pointers point into the caller's workspace.
+int lsh_elements_check(const char *what, int64_t n, int bands) {
+  if (n > 0x7ffffff0LL || n * (int64_t)bands > LSH_MAX_ELEMENTS)
+    return fail(DA_ERR_UNSUPPORTED, "lsh: %s * bands = %lld (sequence, band) elements, at most %lld in one call", what, (long long)(n * (int64_t)bands),
+                (long long)LSH_MAX_ELEMENTS);
+  return DA_OK;
+}
+int lsh_index_mismatch(int64_t n, int bands, int rows) {
+  return fail(DA_ERR_BAD_ARG, "lsh: the index was not built for n = %lld, bands = %d, rows = %d", (long long)n, bands, rows);
+}
+// What a pipeline runs on: the m rows of x against the n rows of y through y's built index, or -- d_index NULL -- one set against itself:
+// y is x, and the buckets are made inside the workspace.
+struct LshSets {
+  const void *d_index;
+  const uint32_t *x;
+  int64_t m, ld_x;
+  const uint32_t *y;
+  int64_t n, ld_y;
+  int n_hash, bands, rows;
+};
+LshSets lsh_one_set(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows) {
+  return LshSets{nullptr, d_sig, n, ld_sig, d_sig, n, ld_sig, n_hash, bands, rows};
+}
+// What the edge list and the lists share: a front end's slots (they point into the caller's workspace or the index), the verdict of every
+// incidence slot (cnt, keep), the kept slots per chunk of 64 and their exclusive sum (coff); `kept` and `firsts` (the distinct candidate
+// pairs) are read back, so the stream is synchronised.
 struct LshVerdicts {
   DevBuf cnt, keep, ckept, coff, distinct, temp;
-  const uint64_t *d_keys = nullptr;
-  const int32_t *d_ids = nullptr;
-  const int64_t *d_off = nullptr;
+  LshSlots slots{};
   int64_t inc = 0, kept = 0;
   uint64_t firsts = 0;
 };
-int lsh_verdicts(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates, void *d_work,
-                 size_t work_bytes, LshVerdicts &v, hipStream_t stream) {
-  if (n > 0x7ffffff0LL || n * (int64_t)bands > LSH_MAX_ELEMENTS)
-    return fail(DA_ERR_UNSUPPORTED, "lsh: n * bands = %lld (sequence, band) elements, at most %lld in one call", (long long)(n * (int64_t)bands),
-                (long long)LSH_MAX_ELEMENTS);
+// behind either front end: the route's counts, the cap, the verdicts
+int lsh_verify_slots(const LshSets &s, uint32_t buckets, uint32_t largest, double threshold, int64_t max_candidates, LshVerdicts &v, hipStream_t stream) {
   int rc;
-  uint32_t stats[2] = {0, 0};
-  if ((rc = lsh_buckets(d_sig, n, ld_sig, bands, rows, d_work, work_bytes, &v.d_keys, &v.d_ids, &v.d_off, stats, &v.inc, stream)) != DA_OK) return rc;
   LshRoute &route = lsh_route();
   route = LshRoute();
-  route.buckets = stats[1];
+  route.buckets = buckets;
   route.incidences = v.inc;
   if (v.inc > max_candidates)
     return fail(DA_ERR_UNSUPPORTED, "lsh: %lld (pair, band) candidates exceed max_candidates = %lld (largest bucket: %u sequences); use more rows per band",
-                (long long)v.inc, (long long)max_candidates, stats[0]);
+                (long long)v.inc, (long long)max_candidates, largest);
   const int64_t chunks = ceil_div(v.inc, 64);
   if (chunks + 1 > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld candidates are more than one call verifies", (long long)v.inc);
   const size_t scan_b = lsh_chunk_scan_bytes(v.inc);
   if ((rc = v.cnt.alloc((size_t)v.inc * 2)) != DA_OK || (rc = v.keep.alloc((size_t)v.inc)) != DA_OK || (rc = v.ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
       (rc = v.coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = v.distinct.alloc(8)) != DA_OK || (rc = v.temp.alloc(scan_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_verify_enumerated(d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), v.d_off, v.d_ids, v.d_keys, v.inc,
+  if ((rc = launch_lsh_verify_enumerated(s.x, s.m, s.ld_x, s.y, s.n, s.ld_y, s.n_hash, s.rows, lsh_c_min(s.n_hash, threshold), v.slots, v.inc,
                                          v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.ckept.as<int64_t>(), v.coff.as<int64_t>(), v.distinct.as<uint64_t>(),
                                          v.temp.p, scan_b, stream)) != DA_OK)
     return rc;
@@ -3794,22 +3809,41 @@ int lsh_verdicts(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, i
   v.temp.release();
   return DA_OK;
 }
-// The pipeline on resident signatures.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.
-int lsh_edges_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
-                     void *d_work, size_t work_bytes, DevBuf &key, DevBuf &val, int64_t *edges_out, hipStream_t stream) {
+// the two front ends: the buckets of one set; the probe of y's index, refused when the index was built for something else
+int lsh_verdicts(const LshSets &s, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, LshVerdicts &v, hipStream_t stream) {
+  int rc;
+  uint32_t stats[2] = {0, 0};
+  if ((rc = lsh_elements_check("n", s.n, s.bands)) != DA_OK) return rc;
+  if ((rc = lsh_buckets(s.x, s.n, s.ld_x, s.bands, s.rows, d_work, work_bytes, &v.slots, stats, &v.inc, stream)) != DA_OK) return rc;
+  return lsh_verify_slots(s, stats[1], stats[0], threshold, max_candidates, v, stream);
+}
+int lsh_cross_verdicts(const LshSets &s, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, LshVerdicts &v, hipStream_t stream) {
+  int rc;
+  uint32_t stats[3] = {0, 0, 0};
+  if ((rc = lsh_cross_probe(s.d_index, s.n, s.x, s.m, s.ld_x, s.bands, s.rows, d_work, work_bytes, &v.slots, stats, &v.inc, stream)) != DA_OK) return rc;
+  if (stats[2]) return lsh_index_mismatch(s.n, s.bands, s.rows);
+  return lsh_verify_slots(s, stats[1], stats[0], threshold, max_candidates, v, stream);
+}
+// The edge pipeline on resident signatures.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.  One set always has
+// its n diagonal entries; two sets without a kept pair allocate and launch nothing.
+int lsh_edges_device(const LshSets &s, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, DevBuf &key, DevBuf &val,
+                     int64_t *edges_out, hipStream_t stream) {
   int rc;
   LshVerdicts v;
   DevBuf temp, key_in, val_in;
   const StreamDrain drain{stream};
-  if ((rc = lsh_verdicts(d_sig, n, ld_sig, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v, stream)) != DA_OK) return rc;
-  const int64_t edges = n + v.kept;
+  if ((rc = (s.d_index ? lsh_cross_verdicts : lsh_verdicts)(s, threshold, max_candidates, d_work, work_bytes, v, stream)) != DA_OK) return rc;
+  const int64_t diagonal_n = s.d_index ? 0 : s.n;
+  const int64_t edges = diagonal_n + v.kept;
   if (edges > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld edges are more than one call sorts", (long long)edges);
-  const size_t sort_b = lsh_edge_sort_bytes(edges);
-  if ((rc = key_in.alloc((size_t)edges * 8)) != DA_OK || (rc = val_in.alloc((size_t)edges * 2)) != DA_OK || (rc = key.alloc((size_t)edges * 8)) != DA_OK ||
-      (rc = val.alloc((size_t)edges * 2)) != DA_OK || (rc = temp.alloc(sort_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_emit_sort(n, n_hash, bands, v.d_off, v.d_ids, v.d_keys, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.coff.as<int64_t>(), edges,
-                                 key_in.as<uint64_t>(), val_in.as<uint16_t>(), key.as<uint64_t>(), val.as<uint16_t>(), temp.p, sort_b, stream)) != DA_OK) return rc;
-  DA_HIP_TRY(hipStreamSynchronize(stream));
+  if (edges > 0) {
+    const size_t sort_b = lsh_edge_sort_bytes(edges);
+    if ((rc = key_in.alloc((size_t)edges * 8)) != DA_OK || (rc = val_in.alloc((size_t)edges * 2)) != DA_OK || (rc = key.alloc((size_t)edges * 8)) != DA_OK ||
+        (rc = val.alloc((size_t)edges * 2)) != DA_OK || (rc = temp.alloc(sort_b)) != DA_OK) return rc;
+    if ((rc = launch_lsh_emit_sort(v.slots, s.m, diagonal_n, s.n_hash, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.coff.as<int64_t>(), edges,
+                                   key_in.as<uint64_t>(), val_in.as<uint16_t>(), key.as<uint64_t>(), val.as<uint16_t>(), temp.p, sort_b, stream)) != DA_OK) return rc;
+    DA_HIP_TRY(hipStreamSynchronize(stream));
+  }
   LshRoute &route = lsh_route();
   route.verified = (int64_t)v.firsts;
   route.edges = edges;
@@ -3823,23 +3857,23 @@ int lsh_dev_check(const void *d_sig, int64_t n, int64_t ld_sig, int n_hash, int 
   if (ld_sig < n_hash) return fail(DA_ERR_BAD_ARG, "ld_sig (%lld) < n_hash (%d)", (long long)ld_sig, n_hash);
   return lsh_arg_check(n_hash, bands, rows, threshold, 0, top);
 }
-// The nearest-neighbour pipeline on resident signatures: the verdicts, then the directed entries and the selection into d_idx / d_key
-// ((n, top), leading dimension top).  Synchronises the stream (totals are read back).
-int lsh_knn_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int top, int64_t max_candidates,
-                   void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key, hipStream_t stream) {
+// The list pipeline on resident signatures: the verdicts, then the entries -- both directions of every kept pair of one set, the x rows of
+// two sets -- and the selection into d_idx / d_key ((m, top), leading dimension top).  Synchronises the stream (totals are read back).
+int lsh_lists_device(const LshSets &s, double threshold, int top, int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_idx, uint16_t *d_key,
+                     hipStream_t stream) {
   int rc;
   LshVerdicts v;
   DevBuf temp, cursor, ptr, col, ecnt, written;
   const StreamDrain drain{stream};
-  if ((rc = lsh_verdicts(d_sig, n, ld_sig, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v, stream)) != DA_OK) return rc;
-  const int64_t entries = 2 * v.kept;            // both directions of every kept pair
-  const size_t scan_b = lsh_knn_scan_bytes(n);
-  if ((rc = cursor.alloc((size_t)(n + 1) * 8)) != DA_OK || (rc = ptr.alloc((size_t)(n + 1) * 8)) != DA_OK || (rc = col.alloc((size_t)entries * 4)) != DA_OK ||
+  if ((rc = (s.d_index ? lsh_cross_verdicts : lsh_verdicts)(s, threshold, max_candidates, d_work, work_bytes, v, stream)) != DA_OK) return rc;
+  const bool both = !s.d_index;
+  const int64_t m = s.m, entries = both ? 2 * v.kept : v.kept;
+  const size_t scan_b = lsh_knn_scan_bytes(m);
+  if ((rc = cursor.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = ptr.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = col.alloc((size_t)entries * 4)) != DA_OK ||
       (rc = ecnt.alloc((size_t)entries * 2)) != DA_OK || (rc = written.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_knn_entries(n, bands, v.d_off, v.d_ids, v.d_keys, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), entries, top,
-                                   cursor.as<int64_t>(), ptr.as<int64_t>(), col.as<int32_t>(), ecnt.as<uint16_t>(), written.as<uint64_t>(), temp.p, scan_b,
-                                   stream)) != DA_OK ||
-      (rc = launch_lsh_knn_select(ptr.as<int64_t>(), entries, col.as<int32_t>(), ecnt.as<uint16_t>(), n, top, d_idx, top, d_key, top, stream)) != DA_OK)
+  if ((rc = launch_lsh_knn_entries(v.slots, m, both, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), entries, top, cursor.as<int64_t>(),
+                                   ptr.as<int64_t>(), col.as<int32_t>(), ecnt.as<uint16_t>(), written.as<uint64_t>(), temp.p, scan_b, stream)) != DA_OK ||
+      (rc = launch_lsh_knn_select(ptr.as<int64_t>(), entries, col.as<int32_t>(), ecnt.as<uint16_t>(), m, top, d_idx, top, d_key, top, stream)) != DA_OK)
     return rc;
   uint64_t entries_written = 0;
   DA_HIP_TRY(hipMemcpyAsync(&entries_written, written.p, 8, hipMemcpyDeviceToHost, stream));
@@ -3868,8 +3902,8 @@ int da_dev_lsh_verify_pairs(const uint32_t *d_sig, int64_t n, int64_t ld_sig, in
   if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, threshold)) != DA_OK) return rc;
   if (n_triples < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
   if (n_triples > 0 && (!d_i || !d_j || !d_band || !d_count || !d_keep)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
-  return launch_lsh_verify_listed(d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_i, d_j, d_band, n_triples, d_count, d_keep,
-                                  static_cast<hipStream_t>(stream));
+  return launch_lsh_verify_listed(d_sig, n, ld_sig, d_sig, n, ld_sig, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_i, d_j, d_band, n_triples, d_count,
+                                  d_keep, static_cast<hipStream_t>(stream));
 }
 
 int da_dev_lsh_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
@@ -3886,7 +3920,7 @@ int da_dev_lsh_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_has
   DevBuf key, val;
   const StreamDrain drain{stream};
   int64_t edges = 0;
-  if ((rc = lsh_edges_device(d_sig, n, ld_sig, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, key, val, &edges, stream)) != DA_OK) return rc;
+  if ((rc = lsh_edges_device(lsh_one_set(d_sig, n, ld_sig, n_hash, bands, rows), threshold, max_candidates, d_work, work_bytes, key, val, &edges, stream)) != DA_OK) return rc;
   if ((rc = launch_lsh_split(key.as<uint64_t>(), val.as<uint16_t>(), std::min(edges, capacity), d_i, d_j, d_count, stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipStreamSynchronize(stream));
   *n_edges_out = edges;
@@ -3911,7 +3945,7 @@ int da_similarity_mh_lsh_edges_begin(const uint8_t *residues, const int64_t *off
   const size_t wb = lsh_workspace_bytes(n, bands);
   if ((rc = work.alloc(wb)) != DA_OK) return rc;
   int64_t edges = 0;
-  if ((rc = lsh_edges_device(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows, threshold, max_candidates, work.p, wb, key, val, &edges, nullptr)) != DA_OK)
+  if ((rc = lsh_edges_device(lsh_one_set(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows), threshold, max_candidates, work.p, wb, key, val, &edges, nullptr)) != DA_OK)
     return rc;
   std::unique_ptr<da_edges> h(new da_edges);
   std::vector<uint64_t> hk((size_t)edges);
@@ -3950,8 +3984,8 @@ int da_dev_lsh_knn(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash,
   if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, threshold, &top)) != DA_OK) return rc;
   if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
   if (!d_work || !d_idx || !d_key) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
-  return lsh_knn_device(d_sig, n, ld_sig, n_hash, bands, rows, threshold, top, max_candidates, d_work, work_bytes, d_idx, d_key,
-                        static_cast<hipStream_t>(stream));
+  return lsh_lists_device(lsh_one_set(d_sig, n, ld_sig, n_hash, bands, rows), threshold, top, max_candidates, d_work, work_bytes, d_idx, d_key,
+                          static_cast<hipStream_t>(stream));
 }
 
 int da_similarity_mh_lsh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
@@ -3971,8 +4005,8 @@ int da_similarity_mh_lsh_knn(const uint8_t *residues, const int64_t *offsets, in
   const size_t wb = lsh_workspace_bytes(n, bands);
   if ((rc = work.alloc(wb)) != DA_OK || (rc = didx.alloc((size_t)n * (size_t)top * sizeof(int32_t))) != DA_OK ||
       (rc = dkey.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
-  if ((rc = lsh_knn_device(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows, threshold, top, max_candidates, work.p, wb, didx.as<int32_t>(),
-                           dkey.as<uint16_t>(), nullptr)) != DA_OK) return rc;
+  if ((rc = lsh_lists_device(lsh_one_set(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows), threshold, top, max_candidates, work.p, wb,
+                             didx.as<int32_t>(), dkey.as<uint16_t>(), nullptr)) != DA_OK) return rc;
   return topk_to_host(didx, dkey, n, top, mh_code_values(n_hash), idx_out, val_out);
 }
 
@@ -3985,15 +4019,9 @@ int da_mh_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t 
   return DA_OK;
 }
 
-// ---- MinHash LSH banding for two sets: a resident index probed by query batches (lsh_cross_kernels.hip) -------------------------------------
+// ---- MinHash LSH banding for two sets: a resident index probed by query batches (lsh_cross_kernels.hip; the pipelines are above) -------------
 }  // extern "C"  (reopened below)
 namespace {
-int lsh_elements_check(const char *what, int64_t n, int bands) {
-  if (n > 0x7ffffff0LL || n * (int64_t)bands > LSH_MAX_ELEMENTS)
-    return fail(DA_ERR_UNSUPPORTED, "lsh: %s * bands = %lld (sequence, band) elements, at most %lld in one call", what, (long long)(n * (int64_t)bands),
-                (long long)LSH_MAX_ELEMENTS);
-  return DA_OK;
-}
 // one resident signature matrix of the device calls
 int lsh_sig_check(const void *d_sig, int64_t rows_of, int64_t ld, int n_hash, const char *ld_name) {
   if (rows_of < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
@@ -4009,9 +4037,6 @@ int lsh_index_check(const void *d_index, size_t index_bytes, int64_t n, int band
   if (index_bytes < lsh_index_bytes(n, bands))
     return fail(DA_ERR_BAD_ARG, "lsh: index too small (%zu bytes, %zu needed)", index_bytes, lsh_index_bytes(n, bands));
   return DA_OK;
-}
-int lsh_index_mismatch(int64_t n, int bands, int rows) {
-  return fail(DA_ERR_BAD_ARG, "lsh: the index was not built for n = %lld, bands = %d, rows = %d", (long long)n, bands, rows);
 }
 // x, y, the banding and the index of the device calls that run the pipeline
 int lsh_cross_dev_check(const void *d_index, size_t index_bytes, const void *d_sig_x, int64_t m, int64_t ld_x, const void *d_sig_y, int64_t n, int64_t ld_y,
@@ -4035,95 +4060,6 @@ int lsh_index_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands
   return DA_OK;
 }
 
-// Probe and verify, what the edge list and the lists share: the route's counts, the cap, the verdict of every incidence slot (cnt, keep),
-// the kept slots per chunk of 64 and their exclusive sum (coff); `kept` and `firsts` are read back, so the stream is synchronised.
-struct LshCrossVerdicts {
-  DevBuf cnt, keep, ckept, coff, distinct, temp;
-  LshCrossSlots slots{};
-  int64_t inc = 0, kept = 0;
-  uint64_t firsts = 0;
-};
-int lsh_cross_verdicts(const void *d_index, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash,
-                       int bands, int rows, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, LshCrossVerdicts &v,
-                       hipStream_t stream) {
-  int rc;
-  uint32_t stats[3] = {0, 0, 0};
-  if ((rc = lsh_cross_probe(d_index, n, d_sig_x, m, ld_x, bands, rows, d_work, work_bytes, &v.slots, stats, &v.inc, stream)) != DA_OK) return rc;
-  if (stats[2]) return lsh_index_mismatch(n, bands, rows);
-  LshRoute &route = lsh_route();
-  route = LshRoute();
-  route.buckets = stats[1];
-  route.incidences = v.inc;
-  if (v.inc > max_candidates)
-    return fail(DA_ERR_UNSUPPORTED, "lsh: %lld (pair, band) candidates exceed max_candidates = %lld (largest bucket: %u sequences); use more rows per band",
-                (long long)v.inc, (long long)max_candidates, stats[0]);
-  const int64_t chunks = ceil_div(v.inc, 64);
-  if (chunks + 1 > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld candidates are more than one call verifies", (long long)v.inc);
-  const size_t scan_b = lsh_chunk_scan_bytes(v.inc);
-  if ((rc = v.cnt.alloc((size_t)v.inc * 2)) != DA_OK || (rc = v.keep.alloc((size_t)v.inc)) != DA_OK || (rc = v.ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
-      (rc = v.coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = v.distinct.alloc(8)) != DA_OK || (rc = v.temp.alloc(scan_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_cross_verify_enumerated(d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, rows, lsh_c_min(n_hash, threshold), v.slots, v.inc,
-                                               v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.ckept.as<int64_t>(), v.coff.as<int64_t>(),
-                                               v.distinct.as<uint64_t>(), v.temp.p, scan_b, stream)) != DA_OK)
-    return rc;
-  DA_HIP_TRY(hipMemcpyAsync(&v.kept, v.coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipMemcpyAsync(&v.firsts, v.distinct.p, 8, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipStreamSynchronize(stream));
-  v.temp.release();
-  return DA_OK;
-}
-// The edge pipeline on resident signatures and a built index.  The sorted list (edges entries: i << 32 | j, count) is left in key / val.
-int lsh_cross_edges_device(const void *d_index, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y,
-                           int n_hash, int bands, int rows, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, DevBuf &key,
-                           DevBuf &val, int64_t *edges_out, hipStream_t stream) {
-  int rc;
-  LshCrossVerdicts v;
-  DevBuf temp, key_in, val_in;
-  const StreamDrain drain{stream};
-  if ((rc = lsh_cross_verdicts(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v,
-                               stream)) != DA_OK) return rc;
-  const int64_t edges = v.kept;
-  if (edges > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "lsh: %lld edges are more than one call sorts", (long long)edges);
-  if (edges > 0) {
-    const size_t sort_b = lsh_edge_sort_bytes(edges);
-    if ((rc = key_in.alloc((size_t)edges * 8)) != DA_OK || (rc = val_in.alloc((size_t)edges * 2)) != DA_OK || (rc = key.alloc((size_t)edges * 8)) != DA_OK ||
-        (rc = val.alloc((size_t)edges * 2)) != DA_OK || (rc = temp.alloc(sort_b)) != DA_OK) return rc;
-    if ((rc = launch_lsh_cross_emit_sort(v.slots, m, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), v.coff.as<int64_t>(), edges, key_in.as<uint64_t>(),
-                                         val_in.as<uint16_t>(), key.as<uint64_t>(), val.as<uint16_t>(), temp.p, sort_b, stream)) != DA_OK) return rc;
-    DA_HIP_TRY(hipStreamSynchronize(stream));
-  }
-  LshRoute &route = lsh_route();
-  route.verified = (int64_t)v.firsts;
-  route.edges = edges;
-  *edges_out = edges;
-  return DA_OK;
-}
-// The list pipeline: the verdicts, then the x rows' entries and the selection into d_idx / d_key ((m, top), leading dimension top).
-int lsh_cross_topk_device(const void *d_index, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y,
-                          int n_hash, int bands, int rows, double threshold, int top, int64_t max_candidates, void *d_work, size_t work_bytes,
-                          int32_t *d_idx, uint16_t *d_key, hipStream_t stream) {
-  int rc;
-  LshCrossVerdicts v;
-  DevBuf temp, cursor, ptr, col, ecnt, written;
-  const StreamDrain drain{stream};
-  if ((rc = lsh_cross_verdicts(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, v,
-                               stream)) != DA_OK) return rc;
-  const int64_t entries = v.kept;                // one direction: the x rows
-  const size_t scan_b = lsh_knn_scan_bytes(m);
-  if ((rc = cursor.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = ptr.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = col.alloc((size_t)entries * 4)) != DA_OK ||
-      (rc = ecnt.alloc((size_t)entries * 2)) != DA_OK || (rc = written.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
-  if ((rc = launch_lsh_cross_knn_entries(v.slots, m, v.inc, v.cnt.as<uint16_t>(), v.keep.as<uint8_t>(), entries, top, cursor.as<int64_t>(),
-                                         ptr.as<int64_t>(), col.as<int32_t>(), ecnt.as<uint16_t>(), written.as<uint64_t>(), temp.p, scan_b, stream)) != DA_OK ||
-      (rc = launch_lsh_knn_select(ptr.as<int64_t>(), entries, col.as<int32_t>(), ecnt.as<uint16_t>(), m, top, d_idx, top, d_key, top, stream)) != DA_OK)
-    return rc;
-  uint64_t entries_written = 0;
-  DA_HIP_TRY(hipMemcpyAsync(&entries_written, written.p, 8, hipMemcpyDeviceToHost, stream));
-  DA_HIP_TRY(hipStreamSynchronize(stream));
-  LshRoute &route = lsh_route();
-  route.verified = (int64_t)v.firsts;
-  route.edges = (int64_t)entries_written;
-  return DA_OK;
-}
 // what both two-set LSH host calls check before a device is needed: x empty, y empty, k, n_hash, pointers, the offsets of x, then of y, the banding
 int lsh_cross_host_validate(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
                             int k, int n_hash, const uint32_t *seeds, const void *out1, const void *out2, int bands, int rows, double threshold,
@@ -4151,6 +4087,9 @@ struct LshCrossHost {
     wb = lsh_cross_workspace_bytes(m, bands);
     if ((rc = index.alloc(lsh_index_bytes(n, bands))) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
     return lsh_index_device(y.sig.as<uint32_t>(), n, y.lds, bands, rows, index.p, nullptr);
+  }
+  LshSets sets(int64_t m, int64_t n, int n_hash, int bands, int rows) {
+    return LshSets{index.p, x.sig.as<uint32_t>(), m, x.lds, y.sig.as<uint32_t>(), n, y.lds, n_hash, bands, rows};
   }
 };
 }  // namespace
@@ -4192,8 +4131,8 @@ int da_dev_lsh_cross_verify_pairs(const uint32_t *d_sig_x, int64_t m, int64_t ld
   if ((rc = lsh_arg_check(n_hash, bands, rows, threshold, 0)) != DA_OK) return rc;
   if (n_triples < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
   if (n_triples > 0 && (!d_i || !d_j || !d_band || !d_count || !d_keep)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
-  return launch_lsh_cross_verify_listed(d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_i, d_j, d_band, n_triples,
-                                        d_count, d_keep, static_cast<hipStream_t>(stream));
+  return launch_lsh_verify_listed(d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, lsh_c_min(n_hash, threshold), d_i, d_j, d_band, n_triples, d_count,
+                                  d_keep, static_cast<hipStream_t>(stream));
 }
 
 int da_dev_lsh_cross_edges(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n,
@@ -4208,8 +4147,8 @@ int da_dev_lsh_cross_edges(const void *d_index, size_t index_bytes, const uint32
   DevBuf key, val;
   const StreamDrain drain{stream};
   int64_t edges = 0;
-  if ((rc = lsh_cross_edges_device(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, d_work, work_bytes, key, val,
-                                   &edges, stream)) != DA_OK) return rc;
+  if ((rc = lsh_edges_device(LshSets{d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows}, threshold, max_candidates, d_work, work_bytes, key, val,
+                             &edges, stream)) != DA_OK) return rc;
   if ((rc = launch_lsh_split(key.as<uint64_t>(), val.as<uint16_t>(), std::min(edges, capacity), d_i, d_j, d_count, stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipStreamSynchronize(stream));
   *n_edges_out = edges;
@@ -4223,8 +4162,8 @@ int da_dev_lsh_cross_topk(const void *d_index, size_t index_bytes, const uint32_
   if ((rc = lsh_cross_dev_check(d_index, index_bytes, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, max_candidates, &top)) != DA_OK)
     return rc;
   if (!d_work || !d_idx || !d_key) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
-  return lsh_cross_topk_device(d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, threshold, top, max_candidates, d_work, work_bytes, d_idx,
-                               d_key, static_cast<hipStream_t>(stream));
+  return lsh_lists_device(LshSets{d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows}, threshold, top, max_candidates, d_work, work_bytes, d_idx,
+                          d_key, static_cast<hipStream_t>(stream));
 }
 
 int da_similarity_mh_lsh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
@@ -4241,8 +4180,7 @@ int da_similarity_mh_lsh_cross_edges_begin(const uint8_t *x_residues, const int6
   const StreamDrain drain{nullptr};
   if ((rc = h.prepare(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, k, n_hash, seeds, bands, rows)) != DA_OK) return rc;
   int64_t edges = 0;
-  if ((rc = lsh_cross_edges_device(h.index.p, h.x.sig.as<uint32_t>(), m, h.x.lds, h.y.sig.as<uint32_t>(), n, h.y.lds, n_hash, bands, rows, threshold,
-                                   max_candidates, h.work.p, h.wb, key, val, &edges, nullptr)) != DA_OK) return rc;
+  if ((rc = lsh_edges_device(h.sets(m, n, n_hash, bands, rows), threshold, max_candidates, h.work.p, h.wb, key, val, &edges, nullptr)) != DA_OK) return rc;
   std::unique_ptr<da_edges> out(new da_edges);
   std::vector<uint64_t> hk((size_t)edges);
   std::vector<uint16_t> hv((size_t)edges);
@@ -4278,8 +4216,8 @@ int da_similarity_mh_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_
   const StreamDrain drain{nullptr};
   if ((rc = h.prepare(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, k, n_hash, seeds, bands, rows)) != DA_OK) return rc;
   if ((rc = didx.alloc((size_t)m * (size_t)top * sizeof(int32_t))) != DA_OK || (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
-  if ((rc = lsh_cross_topk_device(h.index.p, h.x.sig.as<uint32_t>(), m, h.x.lds, h.y.sig.as<uint32_t>(), n, h.y.lds, n_hash, bands, rows, threshold, top,
-                                  max_candidates, h.work.p, h.wb, didx.as<int32_t>(), dkey.as<uint16_t>(), nullptr)) != DA_OK) return rc;
+  if ((rc = lsh_lists_device(h.sets(m, n, n_hash, bands, rows), threshold, top, max_candidates, h.work.p, h.wb, didx.as<int32_t>(), dkey.as<uint16_t>(),
+                             nullptr)) != DA_OK) return rc;
   return topk_to_host(didx, dkey, m, top, mh_code_values(n_hash), idx_out, val_out);
 }
 

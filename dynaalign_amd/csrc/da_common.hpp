@@ -424,53 +424,64 @@ int launch_jaccard_sets_long(const uint8_t *d_res, const int64_t *d_off, int64_t
                              uint16_t *d_counts, hipStream_t stream);
 int launch_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
                              int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, hipStream_t stream);
-// lsh_kernels.hip: MinHash LSH banding (da_dev_lsh_*).  Elements are (sequence, band) pairs, n * bands <= LSH_MAX_ELEMENTS of them; an incidence is
-// a pair of elements of one bucket.  lsh_buckets() does the keys, the sort and the partner counts inside the workspace and reads back
-// {largest bucket, buckets} and the number of incidences; the caller then sizes the per-incidence buffers, verifies, sizes the edge buffers
-// (n + the last entry of the chunk offsets) and emits + sorts.
+// MinHash LSH banding (da_dev_lsh_*).  Elements are (sequence, band) pairs, rows * bands <= LSH_MAX_ELEMENTS of them; an INCIDENCE is a pair
+// of sequences that share a bucket in one band.  A front end numbers the incidences as the slots of an exclusive sum, describes them in
+// an LshSlots and reads back their number and its statistics; the caller checks the cap and sizes the per-incidence buffers; the back end
+// (lsh_kernels.hip) verifies the slots -- row i of sig_a against row j of sig_b -- and turns the kept ones into a sorted edge list or into
+// ragged rows for the nearest-neighbour selection.  The two front ends:
+//   one set   lsh_buckets (lsh_kernels.hip): keys, a sort and the partner counts inside the workspace; sig_a = sig_b, every slot has i < j,
+//             and the edge list carries the n diagonal entries;
+//   two sets  lsh_cross_probe (lsh_cross_kernels.hip): the INDEX of a resident set y is its sorted (band key, id) elements with a table of
+//             where every band starts (layout: include/dynaalign.h); nothing in it depends on the queries.  A query batch x PROBES it:
+//             element q = i * bands + t finds the run of its key, lo[q] / len[q], and the exclusive sum of len numbers the incidences.
 constexpr int64_t LSH_MAX_ELEMENTS = 0x7fffff00LL;
+// slot s belongs to the element e with off[e] <= s < off[e + 1]; which (i, j, band) that is depends on the front end:
+//   !probed  e is a position of the sorted elements: i = ids[e], j = ids[e + 1 + s - off[e]], band = keys[e] >> 48
+//   probed   e = i * bands + band, j = ids[lo[e] + s - off[e]]
+struct LshSlots {
+  bool probed;
+  const int64_t *off;     // [elements + 1]: the exclusive sum of the partner counts / the probed lengths
+  const int32_t *ids;     // the sorted ids: of the workspace's sort / of the index
+  const uint64_t *keys;   // !probed: the sorted keys
+  const uint32_t *lo;     // probed: [elements], where the run of element e starts in ids
+  int64_t elements;       // rows * bands
+  int bands;
+};
 size_t lsh_workspace_bytes(int64_t n, int bands);
 int launch_lsh_band_keys(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, uint64_t *d_keys, int32_t *d_ids, hipStream_t stream);
-int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_work, size_t work_bytes, const uint64_t **d_keys_out,
-                const int32_t **d_ids_out, const int64_t **d_off_out, uint32_t stats_host[2], int64_t *incidences_host, hipStream_t stream);
-int launch_lsh_verify_listed(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int32_t *d_i,
-                             const int32_t *d_j, const int32_t *d_band, int64_t triples, uint16_t *d_count, uint8_t *d_keep, hipStream_t stream);
+// keys, sort, partner counts and their exclusive sum inside the workspace; reads back stats_host = {largest bucket, buckets} and the incidences
+int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_work, size_t work_bytes, LshSlots *slots_out,
+                uint32_t stats_host[2], int64_t *incidences_host, hipStream_t stream);
+int launch_lsh_verify_listed(const uint32_t *d_sig_a, int64_t rows_a, int64_t ld_a, const uint32_t *d_sig_b, int64_t rows_b, int64_t ld_b, int n_hash,
+                             int bands, int rows, uint32_t c_min, const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t triples,
+                             uint16_t *d_count, uint8_t *d_keep, hipStream_t stream);
 size_t lsh_chunk_scan_bytes(int64_t incidences);
-int launch_lsh_verify_enumerated(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int64_t *d_off,
-                                 const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
+int launch_lsh_verify_enumerated(const uint32_t *d_sig_a, int64_t rows_a, int64_t ld_a, const uint32_t *d_sig_b, int64_t rows_b, int64_t ld_b, int n_hash,
+                                 int rows, uint32_t c_min, const LshSlots &slots, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
                                  int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes, hipStream_t stream);
 size_t lsh_edge_sort_bytes(int64_t edges);
-int launch_lsh_emit_sort(int64_t n, int n_hash, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
-                         const uint16_t *d_count, const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in,
-                         uint64_t *d_key_out, uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
+// edges = diagonal_n + the last entry of the chunk offsets; diagonal_n = the rows of one set, 0 for two sets
+int launch_lsh_emit_sort(const LshSlots &slots, int64_t rows_a, int64_t diagonal_n, int n_hash, int64_t incidences, const uint16_t *d_count,
+                         const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in, uint64_t *d_key_out,
+                         uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
 int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count, int32_t *d_i, int32_t *d_j, uint16_t *d_count, hipStream_t stream);
-// ... and the nearest-neighbour lists from the same candidates (da_dev_lsh_knn*): after the verify step, launch_lsh_knn_entries turns the kept
-// slots into ragged rows (both directions of every pair; entries = 2 * kept) and launch_lsh_knn_select takes every row's first `top` entries by
-// (count descending, column ascending) -- rows of up to 64 entries by a wave, longer ones by a workgroup, which sorts up to 2048 entries
-// whole and radix-selects in longer rows.  The selection needs no workspace and does not synchronise.
+// ... and the nearest-neighbour lists from the same candidates (da_dev_lsh_knn*, da_dev_lsh_cross_topk): after the verify step,
+// launch_lsh_knn_entries turns the kept slots into ragged rows (both: the two directions of every pair of one set, entries = 2 * kept;
+// otherwise the rows of x, entries = kept) and launch_lsh_knn_select takes every row's first `top` entries by (count descending, column
+// ascending) -- rows of up to 64 entries by a wave, longer ones by a workgroup, which sorts up to 2048 entries whole and radix-selects in
+// longer rows.  The selection needs no workspace and does not synchronise.
 size_t lsh_knn_scan_bytes(int64_t n);
-int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
-                           const uint16_t *d_count, const uint8_t *d_keep, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col,
-                           uint16_t *d_cnt, uint64_t *d_written, void *d_temp, size_t temp_bytes, hipStream_t stream);
+int launch_lsh_knn_entries(const LshSlots &slots, int64_t rows_a, bool both, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
+                           int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
+                           size_t temp_bytes, hipStream_t stream);
 int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
                           int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream);
 int launch_lsh_knn_written(const int64_t *d_ptr, int64_t n, int64_t nnz, int top, uint64_t *d_written, hipStream_t stream);
-// lsh_cross_kernels.hip: the two-set form (da_dev_lsh_index_*, da_dev_lsh_cross_*).  The INDEX of a resident set y is its sorted (band key, id)
-// elements with a table of where every band starts (layout: include/dynaalign.h); nothing in it depends on the queries.  A query batch x
-// PROBES it: element q = i * bands + t finds the run of its key, lo[q] / len[q]; the exclusive sum of len numbers the (pair, band)
-// incidences (LshCrossSlots); they are verified against BOTH signature matrices, and the kept ones become a sorted edge list or the ragged
-// rows of the x sequences that launch_lsh_knn_select takes.
+// lsh_cross_kernels.hip: the index and the probe (da_dev_lsh_index_*, and the front end of da_dev_lsh_cross_*)
 struct LshIndexView {
   const uint32_t *meta, *band_start;
   const uint64_t *keys;
   const int32_t *ids;
-};
-struct LshCrossSlots {
-  const int64_t *off;     // [m * bands + 1]: the exclusive sum of len
-  const uint32_t *lo;     // [m * bands]: where the run of element q starts in ids
-  const int32_t *ids;     // the index's sorted ids
-  int64_t elements;       // m * bands
-  int bands;
 };
 size_t lsh_index_bytes(int64_t n, int bands);
 LshIndexView lsh_index_view(const void *d_index, int64_t n, int bands);
@@ -483,20 +494,7 @@ int lsh_index_probe_listed(const void *d_index, int64_t n, const uint32_t *d_sig
                            int32_t *d_len, uint32_t *d_stats, int *mismatch_host, hipStream_t stream);
 // probe + exclusive sum inside the workspace; reads back stats_host = {largest probed run, runs of the index, mismatch} and the incidences
 int lsh_cross_probe(const void *d_index, int64_t n, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, int bands, int rows, void *d_work, size_t work_bytes,
-                    LshCrossSlots *slots_out, uint32_t stats_host[3], int64_t *incidences_host, hipStream_t stream);
-int launch_lsh_cross_verify_listed(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands,
-                                   int rows, uint32_t c_min, const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t triples,
-                                   uint16_t *d_count, uint8_t *d_keep, hipStream_t stream);
-int launch_lsh_cross_verify_enumerated(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash,
-                                       int rows, uint32_t c_min, const LshCrossSlots &slots, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
-                                       int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes,
-                                       hipStream_t stream);
-int launch_lsh_cross_emit_sort(const LshCrossSlots &slots, int64_t m, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
-                               const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in, uint64_t *d_key_out,
-                               uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
-int launch_lsh_cross_knn_entries(const LshCrossSlots &slots, int64_t m, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep, int64_t entries,
-                                 int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
-                                 size_t temp_bytes, hipStream_t stream);
+                    LshSlots *slots_out, uint32_t stats_host[3], int64_t *incidences_host, hipStream_t stream);
 int launch_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, hipStream_t stream);
 int launch_acc_counts(uint32_t *d_acc, const uint16_t *d_cnt, int64_t count, bool first, hipStream_t stream);
 int launch_counts32_to_f64(const uint32_t *d_acc, double *d_out, int64_t count, int n_hash, hipStream_t stream);

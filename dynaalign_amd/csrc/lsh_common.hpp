@@ -1,5 +1,5 @@
-// lsh_common.hpp -- what the one-set LSH kernels (lsh_kernels.hip) and the two-set ones (lsh_cross_kernels.hip) share: the band key, the
-// per-pair decision, and the host-side sizes of the hipcub calls.  Everything here has internal linkage.
+// lsh_common.hpp -- what the LSH back end and one-set front end (lsh_kernels.hip) and the two-set front end (lsh_cross_kernels.hip) share:
+// the band key, the per-pair decision, and the host-side sizes of the hipcub calls.  Everything here has internal linkage.
 #pragma once
 #include "da_common.hpp"
 

@@ -1,22 +1,17 @@
-// lsh_cross_kernels.hip -- MinHash LSH banding for two sets: a query batch x (m sequences) against a resident set y (n sequences) whose
-// buckets are kept as an INDEX, so that a query costs a lookup and the compare of the pairs that share a bucket, never a sort of y.
-// Bands, rows, cand(i, j), the count c and the first-agreeing-band rule mean what they mean in lsh_kernels.hip; the per-pair decision
-// (lsh_pair_decide) and the band key (lsh_band_key) are the same functions (lsh_common.hpp).
+// lsh_cross_kernels.hip -- the two-set FRONT END of MinHash LSH banding: a query batch x (m sequences) against a resident set y (n
+// sequences) whose buckets are kept as an INDEX, so that a query costs a lookup and the compare of the pairs that share a bucket, never a
+// sort of y.  Bands, rows, cand(i, j), the count c and the first-agreeing-band rule mean what they mean in lsh_kernels.hip, and the band
+// key (lsh_band_key) is the same function (lsh_common.hpp).  This file is the index and the probe; what follows them -- verify, the edge
+// list, the lists -- is the back end in lsh_kernels.hip, which takes the probe's LshSlots.
 //
 //   index  the band keys of sig_y (launch_lsh_band_keys), one stable radix sort of (key, id) -- equal keys keep ids ascending -- and
 //          k_lsh_index_tables: band_start[t] = the first element of band t, the number of runs and the longest one.  Layout: dynaalign.h.
-//   1. k_lsh_probe: element q = i * bands + t of x computes its key and finds the run of that key inside its band's segment of the index
-//      (a lower and an upper bound): lo[q], len[q]; len is 0 when the key is absent.  Consecutive lanes take consecutive bands of ONE row
-//      (the walk of k_lsh_band_keys): the row is read in one stretch and lo / len are written coalesced; the searches of a wave then go
-//      to `bands` different segments.  The exclusive sum of len numbers the (pair, band) incidences; its total is read back and checked
-//      against the caller's cap before any pair is compared.
-//   2. k_lsh_cross_verify: a wave takes 64 incidence slots; a lane finds its slot's q by a binary search of the exclusive sum, i = q /
-//      bands, t = q % bands, j = ids[lo[q] + s - off[q]]; then the wave decides the 64 pairs in turn, row i of sig_x against row j of
-//      sig_y.  Kept: the pair's first agreeing band only, and c >= c_min.  The same kernel runs on listed triples.
-//   3. edges: the kept counts per chunk, their scan, k_lsh_cross_emit (i << 32 | j and the count into final slots, no output atomic), one
-//      radix sort over 32 + bits(m) bits, launch_lsh_split.  There is no diagonal: i and j number different sets.
-//   4. lists: k_lsh_cross_knn_entries counts and then scatters (col = j, count) into row i's segment -- the x rows only, one atomic per
-//      distinct i of a chunk (the slots of one x row are consecutive) -- and launch_lsh_knn_select of lsh_kernels.hip takes each row's top.
+//   probe  k_lsh_probe: element q = i * bands + t of x computes its key and finds the run of that key inside its band's segment of the
+//          index (a lower and an upper bound): lo[q], len[q]; len is 0 when the key is absent.  Consecutive lanes take consecutive bands of
+//          ONE row (the walk of k_lsh_band_keys): the row is read in one stretch and lo / len are written coalesced; the searches of a wave
+//          then go to `bands` different segments.  The exclusive sum of len numbers the (pair, band) incidences: slot s of element q is
+//          (i = q / bands, j = ids[lo[q] + s - off[q]], band = q % bands).  The total is read back and checked against the caller's cap
+//          before any pair is compared.
 #include "lsh_common.hpp"
 
 namespace da {
@@ -112,130 +107,6 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_probe(const uint32_t *__res
   if (!ok && blockIdx.x == 0 && threadIdx.x == 0) stats[1] = 1;
 }
 
-// ---- where the triples of the verify kernel come from: lane-level get(slot) ----------------------------------------------------------------
-struct LshCrossListed {
-  const int32_t *__restrict__ i, *__restrict__ j, *__restrict__ band;
-  __device__ __forceinline__ void get(int64_t s, int &pi, int &pj, int &pt) const { pi = i[s]; pj = j[s]; pt = band[s]; }
-};
-// slot s of the exclusive sum off[0 .. elements] of the probed lengths: the element q with off[q] <= s < off[q + 1] (the LAST q with
-// off[q] <= s: the elements of length 0 behind it share its successor's offset) and member s - off[q] of its run
-struct LshCrossEnumerated {
-  const long long *__restrict__ off;
-  const uint32_t *__restrict__ lo;
-  const int32_t *__restrict__ ids;
-  int64_t elements;
-  int bands;
-  __device__ __forceinline__ void get(int64_t s, int &pi, int &pj, int &pt) const {
-    int64_t a = 0, b = elements;                         // s < off[elements], so the answer is < elements
-    while (a < b) {
-      const int64_t mid = (a + b + 1) >> 1;
-      if (off[mid] <= s) a = mid; else b = mid - 1;
-    }
-    pi = (int)(a / bands);
-    pt = (int)(a - (int64_t)pi * bands);
-    pj = ids[(int64_t)lo[a] + (s - off[a])];
-  }
-};
-LshCrossEnumerated enumerated(const LshCrossSlots &s) {
-  return LshCrossEnumerated{reinterpret_cast<const long long *>(s.off), s.lo, s.ids, s.elements, s.bands};
-}
-
-// out_count[s] = the pair's count, out_keep[s] = 1 when the triple survives.  A triple with i outside [0, m), j outside [0, n) or a band
-// outside [0, bands) reads nothing and gets 0 / 0.  chunk_kept[c] (if given) = kept triples of slots [64 c, 64 c + 64); *distinct (if
-// given) += the triples that are their pair's first agreeing band, whatever their count.
-template <typename Src>
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_cross_verify(const uint32_t *__restrict__ sig_x, int64_t m, int64_t ld_x,
-                                                                  const uint32_t *__restrict__ sig_y, int64_t n, int64_t ld_y, int n_hash, int bands,
-                                                                  int rows, uint32_t c_min, Src src, int64_t slots, uint16_t *__restrict__ out_count,
-                                                                  uint8_t *__restrict__ out_keep, long long *__restrict__ chunk_kept,
-                                                                  unsigned long long *__restrict__ distinct) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
-  unsigned long long firsts = 0;
-  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
-    const int64_t s = c * 64 + lane;
-    int i = 0, j = 0, t = 0;
-    bool valid = false;
-    if (s < slots) {
-      src.get(s, i, j, t);
-      valid = i >= 0 && i < m && j >= 0 && j < n && t >= 0 && t < bands;
-    }
-    unsigned long long todo = __ballot(valid);
-    uint32_t my_count = 0;
-    bool my_first = false;
-    while (todo) {
-      const int b = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int bi = __shfl(i, b), bj = __shfl(j, b), bt = __shfl(t, b);
-      const LshVerdict v = lsh_pair_decide(sig_x + (int64_t)bi * ld_x, sig_y + (int64_t)bj * ld_y, n_hash, bands * rows, rows, bt);
-      if (lane == b) { my_count = v.count; my_first = v.first; }
-    }
-    const bool keep = my_first && my_count >= c_min;
-    if (s < slots) { out_count[s] = (uint16_t)my_count; out_keep[s] = keep ? 1 : 0; }
-    const unsigned long long kept = __ballot(keep);
-    if (chunk_kept && lane == 0) chunk_kept[c] = __popcll(kept);
-    firsts += (unsigned long long)__popcll(__ballot(my_first));
-  }
-  if (distinct && lane == 0 && firsts) atomicAdd(distinct, firsts);
-}
-
-// the kept slots of chunk c, in slot order, at edge slots chunk_off[c] ...: key = i << 32 | j, value = the count
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_cross_emit(LshCrossEnumerated src, int64_t slots, const uint16_t *__restrict__ count,
-                                                                const uint8_t *__restrict__ keep, const long long *__restrict__ chunk_off,
-                                                                unsigned long long *__restrict__ out_key, uint16_t *__restrict__ out_val) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
-  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
-    const int64_t s = c * 64 + lane;
-    const bool kp = s < slots && keep[s] != 0;
-    const unsigned long long kept = __ballot(kp);
-    if (!kp) continue;
-    int i, j, t;
-    src.get(s, i, j, t);
-    const int64_t slot = chunk_off[c] + __popcll(kept & ((1ull << lane) - 1));
-    out_key[slot] = ((unsigned long long)(uint32_t)i << 32) | (uint32_t)j;
-    out_val[slot] = count[s];
-  }
-}
-
-// The x side only.  SCATTER = false: at[] are the degrees.  SCATTER = true: at[] are the cursors (they start as the row pointers) and
-// (col = j, count) is written.  One atomic per distinct i of a chunk: the slots of one x row are consecutive, so a chunk holds few of them.
-template <bool SCATTER>
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_cross_knn_entries(LshCrossEnumerated src, int64_t slots, const uint16_t *__restrict__ count,
-                                                                       const uint8_t *__restrict__ keep, unsigned long long *__restrict__ at,
-                                                                       int32_t *__restrict__ out_col, uint16_t *__restrict__ out_count) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
-  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
-    const int64_t s = c * 64 + lane;
-    const bool kp = s < slots && keep[s] != 0;
-    unsigned long long todo = __ballot(kp);
-    if (!todo) continue;                          // wave-uniform
-    int i = -1, j = -1, t = 0;
-    uint16_t cv = 0;
-    if (kp) {
-      src.get(s, i, j, t);
-      cv = count[s];
-    }
-    while (todo) {                                // one round per distinct i of the chunk
-      const int leader = __ffsll((long long)todo) - 1;
-      const int li = __shfl(i, leader);
-      const unsigned long long same = __ballot(kp && i == li);
-      unsigned long long base = 0;
-      if (lane == leader) base = atomicAdd(&at[li], (unsigned long long)__popcll(same));
-      if (SCATTER) {
-        base = lsh_shfl64(base, leader);
-        if (kp && i == li) {
-          const unsigned long long pos = base + (unsigned long long)__popcll(same & ((1ull << lane) - 1));
-          out_col[pos] = j;
-          out_count[pos] = cv;
-        }
-      }
-      todo &= ~same;
-    }
-  }
-}
-
 // the probe workspace of `elements` = m * bands elements, cut into its arrays
 struct ProbeLayout {
   size_t lo, cnt, off, stats, temp, temp_bytes, bytes;
@@ -324,7 +195,7 @@ int lsh_index_probe_listed(const void *d_index, int64_t n, const uint32_t *d_sig
 }
 
 int lsh_cross_probe(const void *d_index, int64_t n, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, int bands, int rows, void *d_work, size_t work_bytes,
-                    LshCrossSlots *slots_out, uint32_t stats_host[3], int64_t *incidences_host, hipStream_t stream) {
+                    LshSlots *slots_out, uint32_t stats_host[3], int64_t *incidences_host, hipStream_t stream) {
   const int64_t elements = m * bands;
   const ProbeLayout L(elements);
   if (!d_work || work_bytes < L.bytes) return fail(DA_ERR_BAD_ARG, "lsh: workspace too small (%zu bytes, %zu needed)", work_bytes, L.bytes);
@@ -344,82 +215,8 @@ int lsh_cross_probe(const void *d_index, int64_t n, const uint32_t *d_sig_x, int
   DA_HIP_TRY(hipStreamSynchronize(stream));
   stats_host[0] = probed[0]; stats_host[1] = runs; stats_host[2] = probed[1];
   *incidences_host = (int64_t)inc;
-  *slots_out = LshCrossSlots{reinterpret_cast<const int64_t *>(off), lo, ix.ids, elements, bands};
+  *slots_out = LshSlots{true, reinterpret_cast<const int64_t *>(off), ix.ids, nullptr, lo, elements, bands};
   return DA_OK;
-}
-
-int launch_lsh_cross_verify_listed(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands,
-                                   int rows, uint32_t c_min, const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t triples,
-                                   uint16_t *d_count, uint8_t *d_keep, hipStream_t stream) {
-  if (triples <= 0) return DA_OK;
-  hipLaunchKernelGGL(k_lsh_cross_verify<LshCrossListed>, dim3(lsh_grid(ceil_div(triples, 64) * 64)), dim3(LSH_THREADS), 0, stream, d_sig_x, m, ld_x, d_sig_y,
-                     n, ld_y, n_hash, bands, rows, c_min, LshCrossListed{d_i, d_j, d_band}, triples, d_count, d_keep, (long long *)nullptr,
-                     (unsigned long long *)nullptr);
-  DA_HIP_TRY(hipGetLastError());
-  return DA_OK;
-}
-
-// Step 2 on the enumerated incidences: verdicts into d_count / d_keep (one per incidence), kept counts per chunk of 64 into d_chunk_kept
-// (chunks + 1 entries, the last one 0), their exclusive sum into d_chunk_off (d_temp: lsh_chunk_scan_bytes(incidences)); *d_distinct
-// (zeroed here) counts the distinct candidate pairs.
-int launch_lsh_cross_verify_enumerated(const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash,
-                                       int rows, uint32_t c_min, const LshCrossSlots &slots, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
-                                       int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes,
-                                       hipStream_t stream) {
-  const int64_t chunks = ceil_div(incidences, 64);
-  DA_HIP_TRY(hipMemsetAsync(d_distinct, 0, 8, stream));
-  DA_HIP_TRY(hipMemsetAsync(d_chunk_kept + chunks, 0, 8, stream));
-  if (incidences > 0) {
-    hipLaunchKernelGGL(k_lsh_cross_verify<LshCrossEnumerated>, dim3(lsh_grid(chunks * 64)), dim3(LSH_THREADS), 0, stream, d_sig_x, m, ld_x, d_sig_y, n, ld_y,
-                       n_hash, slots.bands, rows, c_min, enumerated(slots), incidences, d_count, d_keep, reinterpret_cast<long long *>(d_chunk_kept),
-                       reinterpret_cast<unsigned long long *>(d_distinct));
-    DA_HIP_TRY(hipGetLastError());
-  }
-  size_t tb = temp_bytes;
-  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_chunk_kept), reinterpret_cast<long long *>(d_chunk_off),
-                                              (int)(chunks + 1), stream));
-  return DA_OK;
-}
-
-// Step 3: the kept incidences into d_key_in / d_val_in (`edges` entries, > 0), sorted by (i, j) into d_key_out / d_val_out
-// (d_temp: lsh_edge_sort_bytes(edges)).
-int launch_lsh_cross_emit_sort(const LshCrossSlots &slots, int64_t m, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
-                               const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in, uint64_t *d_key_out,
-                               uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream) {
-  if (incidences <= 0 || edges <= 0) return DA_OK;
-  unsigned long long *kin = reinterpret_cast<unsigned long long *>(d_key_in), *kout = reinterpret_cast<unsigned long long *>(d_key_out);
-  hipLaunchKernelGGL(k_lsh_cross_emit, dim3(lsh_grid(ceil_div(incidences, 64) * 64)), dim3(LSH_THREADS), 0, stream, enumerated(slots), incidences, d_count,
-                     d_keep, reinterpret_cast<const long long *>(d_chunk_off), kin, d_val_in);
-  DA_HIP_TRY(hipGetLastError());
-  size_t tb = temp_bytes;
-  DA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, kin, kout, d_val_in, d_val_out, (int)edges, 0, 32 + bits_for(m), stream));
-  return DA_OK;
-}
-
-// Step 4 on the verdicts: d_ptr[m + 1] = the row pointers of the x rows' entries (one per kept slot), d_col / d_cnt their columns and
-// counts; d_cursor (m + 1 words) is scratch, d_temp: lsh_knn_scan_bytes(m).  *d_written (zeroed here) = the sum of min(degree, top).
-int launch_lsh_cross_knn_entries(const LshCrossSlots &slots, int64_t m, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep, int64_t entries,
-                                 int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
-                                 size_t temp_bytes, hipStream_t stream) {
-  unsigned long long *cursor = reinterpret_cast<unsigned long long *>(d_cursor);
-  const unsigned grid = lsh_grid(ceil_div(incidences, 64) * 64);
-  DA_HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(m + 1) * 8, stream));
-  DA_HIP_TRY(hipMemsetAsync(d_written, 0, 8, stream));
-  if (incidences > 0 && entries > 0) {
-    hipLaunchKernelGGL(k_lsh_cross_knn_entries<false>, dim3(grid), dim3(LSH_THREADS), 0, stream, enumerated(slots), incidences, d_count, d_keep, cursor,
-                       (int32_t *)nullptr, (uint16_t *)nullptr);
-    DA_HIP_TRY(hipGetLastError());
-  }
-  size_t tb = temp_bytes;
-  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_cursor), reinterpret_cast<long long *>(d_ptr), (int)(m + 1),
-                                              stream));
-  if (incidences > 0 && entries > 0) {
-    DA_HIP_TRY(hipMemcpyAsync(d_cursor, d_ptr, (size_t)(m + 1) * 8, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_lsh_cross_knn_entries<true>, dim3(grid), dim3(LSH_THREADS), 0, stream, enumerated(slots), incidences, d_count, d_keep, cursor, d_col,
-                       d_cnt);
-    DA_HIP_TRY(hipGetLastError());
-  }
-  return launch_lsh_knn_written(d_ptr, m, entries, top, d_written, stream);
 }
 
 }  // namespace da

@@ -1,7 +1,12 @@
-// lsh_kernels.hip -- MinHash LSH banding: the threshold graph of one set without the n x n compare.  The n_hash columns of a signature are
-// cut into `bands` bands of `rows` columns; two sequences are a CANDIDATE when some band agrees in all its columns, and only candidates are
-// compared.  The result is exact with respect to that definition (lsh_edges_dense in similarity.py): a bucket key is a hash, but a pair
-// becomes an edge only after the band's columns were compared themselves.
+// lsh_kernels.hip -- MinHash LSH banding: the threshold graph of one set without the n x n compare, and the BACK END of both LSH forms.
+// The n_hash columns of a signature are cut into `bands` bands of `rows` columns; two sequences are a CANDIDATE when some band agrees in
+// all its columns, and only candidates are compared.  The result is exact with respect to that definition (lsh_edges_dense in
+// similarity.py): a bucket key is a hash, but a pair becomes an edge only after the band's columns were compared themselves.
+//
+// A front end numbers the (pair, band) INCIDENCES as the slots of an exclusive sum and describes them in an LshSlots (da_common.hpp).
+// Steps 1 and 2 below are the one-set front end; the two-set one -- a resident index and its probe -- is lsh_cross_kernels.hip.  Steps 3
+// and 4 and the nearest-neighbour lists further down are the back end: row i of sig_a against row j of sig_b, which the one-set form
+// passes the same matrix for.
 //
 //   1. k_lsh_band_keys: element q = i * bands + t  ->  key = band t in the top 16 bits | 48 bits of a hash of the band's values, id = i;
 //   2. one stable hipcub radix sort of (key, id): a bucket is a run of equal keys, never spans two bands, and holds its ids ascending, so
@@ -9,13 +14,15 @@
 //      element p of a run ending at e its e - 1 - p partners; their exclusive sum numbers the (pair, band) INCIDENCES, and its total is known
 //      -- and checked against the caller's cap -- before any pair is touched;
 //   3. k_lsh_verify, the hot kernel: a wave takes 64 consecutive incidence slots, every lane finds its slot's (i, j, band) (a binary search
-//      of the exclusive sum: balanced whatever the bucket sizes are), then the wave decides the 64 pairs one after the other with
-//      lsh_pair_decide -- both signature rows read coalesced, equal columns counted by ballot / popcount.  A pair survives in the FIRST band
-//      in which it agrees only (exact deduplication without a sort of candidates) and when its count reaches c_min.  Per chunk of 64 slots
-//      the kept count; their scan; k_lsh_emit writes i << 32 | j and the count into final slots -- no output atomic;
-//   4. one radix sort of the 64-bit keys (count as payload) puts the list, diagonal included, in (i, j) order; k_lsh_split unpacks it.
-// The same verify kernel runs on LISTED triples (da_dev_lsh_verify_pairs), so that the per-pair decision can be tested on triples the
-// pipeline never produces (a key collision, a pair of an earlier band).
+//      of the exclusive sum: balanced whatever the bucket sizes are; LshEnumerated for one set, LshProbed for two), then the wave decides
+//      the 64 pairs one after the other with lsh_pair_decide -- both signature rows read coalesced, equal columns counted by ballot /
+//      popcount.  A pair survives in the FIRST band in which it agrees only (exact deduplication without a sort of candidates) and when
+//      its count reaches c_min.  Per chunk of 64 slots the kept count; their scan; k_lsh_emit writes i << 32 | j and the count into final
+//      slots -- no output atomic;
+//   4. one radix sort of the 64-bit keys (count as payload) puts the list in (i, j) order -- behind the n diagonal entries of one set; two
+//      sets have no diagonal, i and j number different sets -- and k_lsh_split unpacks it.
+// The same verify kernel runs on LISTED triples (da_dev_lsh_verify_pairs, da_dev_lsh_cross_verify_pairs), so that the per-pair decision
+// can be tested on triples the pipeline never produces (a key collision, a pair of an earlier band).
 #include "lsh_common.hpp"
 
 namespace da {
@@ -71,7 +78,8 @@ struct LshListed {
   const int32_t *__restrict__ i, *__restrict__ j, *__restrict__ band;
   __device__ __forceinline__ void get(int64_t s, int &pi, int &pj, int &pt) const { pi = i[s]; pj = j[s]; pt = band[s]; }
 };
-// slot s of the exclusive sum off[0 .. total] of the partner counts: the element p with off[p] <= s < off[p + 1] and its partner p + 1 + (s - off[p])
+// one set: slot s of the exclusive sum off[0 .. total] of the partner counts: the element p with off[p] <= s < off[p + 1] and its partner
+// p + 1 + (s - off[p])
 struct LshEnumerated {
   const long long *__restrict__ off;
   const int32_t *__restrict__ ids;
@@ -88,12 +96,38 @@ struct LshEnumerated {
     pt = (int)(keys[lo] >> LSH_BAND_SHIFT);
   }
 };
+// two sets: slot s of the exclusive sum off[0 .. elements] of the probed lengths: the element q with off[q] <= s < off[q + 1] (the LAST q
+// with off[q] <= s: the elements of length 0 behind it share its successor's offset) and member s - off[q] of its run
+struct LshProbed {
+  const long long *__restrict__ off;
+  const uint32_t *__restrict__ lo;
+  const int32_t *__restrict__ ids;
+  int64_t elements;
+  int bands;
+  __device__ __forceinline__ void get(int64_t s, int &pi, int &pj, int &pt) const {
+    int64_t a = 0, b = elements;                         // s < off[elements], so the answer is < elements
+    while (a < b) {
+      const int64_t mid = (a + b + 1) >> 1;
+      if (off[mid] <= s) a = mid; else b = mid - 1;
+    }
+    pi = (int)(a / bands);
+    pt = (int)(a - (int64_t)pi * bands);
+    pj = ids[(int64_t)lo[a] + (s - off[a])];
+  }
+};
+// the one place where a launcher learns which enumeration the slots hold: f(the device-side source)
+template <typename F> void with_source(const LshSlots &s, F f) {
+  const long long *off = reinterpret_cast<const long long *>(s.off);
+  if (s.probed) f(LshProbed{off, s.lo, s.ids, s.elements, s.bands});
+  else f(LshEnumerated{off, s.ids, reinterpret_cast<const unsigned long long *>(s.keys), s.elements});
+}
 
-// out_count[s] = the pair's count, out_keep[s] = 1 when the triple survives.  A triple with an index outside [0, n) or a band outside
-// [0, bands) reads nothing and gets 0 / 0.  chunk_kept[c] (if given) = kept triples of slots [64 c, 64 c + 64); *distinct (if given) += the
-// triples that are their pair's first agreeing band, whatever their count.
+// Row i of sig_a against row j of sig_b.  out_count[s] = the pair's count, out_keep[s] = 1 when the triple survives.  A triple with i
+// outside [0, rows_a), j outside [0, rows_b) or a band outside [0, bands) reads nothing and gets 0 / 0.  chunk_kept[c] (if given) = kept
+// triples of slots [64 c, 64 c + 64); *distinct (if given) += the triples that are their pair's first agreeing band, whatever their count.
 template <typename Src>
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_verify(const uint32_t *__restrict__ sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows,
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_verify(const uint32_t *__restrict__ sig_a, int64_t rows_a, int64_t ld_a,
+                                                            const uint32_t *__restrict__ sig_b, int64_t rows_b, int64_t ld_b, int n_hash, int bands, int rows,
                                                             uint32_t c_min, Src src, int64_t slots, uint16_t *__restrict__ out_count,
                                                             uint8_t *__restrict__ out_keep, long long *__restrict__ chunk_kept,
                                                             unsigned long long *__restrict__ distinct) {
@@ -106,7 +140,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_verify(const uint32_t *__re
     bool valid = false;
     if (s < slots) {
       src.get(s, i, j, t);
-      valid = i >= 0 && i < n && j >= 0 && j < n && t >= 0 && t < bands;
+      valid = i >= 0 && i < rows_a && j >= 0 && j < rows_b && t >= 0 && t < bands;
     }
     unsigned long long todo = __ballot(valid);
     uint32_t my_count = 0;
@@ -115,7 +149,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_verify(const uint32_t *__re
       const int b = __ffsll((long long)todo) - 1;
       todo &= todo - 1;
       const int bi = __shfl(i, b), bj = __shfl(j, b), bt = __shfl(t, b);
-      const LshVerdict v = lsh_pair_decide(sig + (int64_t)bi * ld_sig, sig + (int64_t)bj * ld_sig, n_hash, bands * rows, rows, bt);
+      const LshVerdict v = lsh_pair_decide(sig_a + (int64_t)bi * ld_a, sig_b + (int64_t)bj * ld_b, n_hash, bands * rows, rows, bt);
       if (lane == b) { my_count = v.count; my_first = v.first; }
     }
     const bool keep = my_first && my_count >= c_min;
@@ -128,7 +162,8 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_verify(const uint32_t *__re
 }
 
 // the kept slots of chunk c, in slot order, at edge slots base + chunk_off[c] ...: key = i << 32 | j, value = the count
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_emit(LshEnumerated src, int64_t slots, const uint16_t *__restrict__ count, const uint8_t *__restrict__ keep,
+template <typename Src>
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_emit(Src src, int64_t slots, const uint16_t *__restrict__ count, const uint8_t *__restrict__ keep,
                                                           const long long *__restrict__ chunk_off, int64_t base, unsigned long long *__restrict__ out_key,
                                                           uint16_t *__restrict__ out_val) {
   const int lane = threadIdx.x & 63;
@@ -201,10 +236,10 @@ size_t lsh_workspace_bytes(int64_t n, int bands) {
   return BucketLayout(n * bands).bytes;
 }
 
-// Steps 1 and 2 on the signatures: keys, the sort, the runs, the partner counts and their exclusive sum.  The three device pointers point
-// into the workspace; stats_host = {largest bucket, buckets}, *incidences_host the total; synchronises the stream once (the read-back).
-int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_work, size_t work_bytes, const uint64_t **d_keys_out,
-                const int32_t **d_ids_out, const int64_t **d_off_out, uint32_t stats_host[2], int64_t *incidences_host, hipStream_t stream) {
+// Steps 1 and 2 on the signatures: keys, the sort, the runs, the partner counts and their exclusive sum.  The slots point into the
+// workspace; stats_host = {largest bucket, buckets}, *incidences_host the total; synchronises the stream once (the read-back).
+int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int rows, void *d_work, size_t work_bytes, LshSlots *slots_out,
+                uint32_t stats_host[2], int64_t *incidences_host, hipStream_t stream) {
   const int64_t total = n * bands;
   const BucketLayout L(total);
   if (!d_work || work_bytes < L.bytes) return fail(DA_ERR_BAD_ARG, "lsh: workspace too small (%zu bytes, %zu needed)", work_bytes, L.bytes);
@@ -237,17 +272,17 @@ int lsh_buckets(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands, int
   DA_HIP_TRY(hipMemcpyAsync(stats_host, stats, 8, hipMemcpyDeviceToHost, stream));
   DA_HIP_TRY(hipStreamSynchronize(stream));
   *incidences_host = (int64_t)inc;
-  *d_keys_out = reinterpret_cast<const uint64_t *>(keys_out);
-  *d_ids_out = ids_out;
-  *d_off_out = reinterpret_cast<const int64_t *>(off);
+  *slots_out = LshSlots{false, reinterpret_cast<const int64_t *>(off), ids_out, reinterpret_cast<const uint64_t *>(keys_out), nullptr, total, bands};
   return DA_OK;
 }
 
-int launch_lsh_verify_listed(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int32_t *d_i,
-                             const int32_t *d_j, const int32_t *d_band, int64_t triples, uint16_t *d_count, uint8_t *d_keep, hipStream_t stream) {
+int launch_lsh_verify_listed(const uint32_t *d_sig_a, int64_t rows_a, int64_t ld_a, const uint32_t *d_sig_b, int64_t rows_b, int64_t ld_b, int n_hash,
+                             int bands, int rows, uint32_t c_min, const int32_t *d_i, const int32_t *d_j, const int32_t *d_band, int64_t triples,
+                             uint16_t *d_count, uint8_t *d_keep, hipStream_t stream) {
   if (triples <= 0) return DA_OK;
-  hipLaunchKernelGGL(k_lsh_verify<LshListed>, dim3(lsh_grid(ceil_div(triples, 64) * 64)), dim3(LSH_THREADS), 0, stream, d_sig, n, ld_sig, n_hash, bands, rows,
-                     c_min, LshListed{d_i, d_j, d_band}, triples, d_count, d_keep, (long long *)nullptr, (unsigned long long *)nullptr);
+  hipLaunchKernelGGL(k_lsh_verify<LshListed>, dim3(lsh_grid(ceil_div(triples, 64) * 64)), dim3(LSH_THREADS), 0, stream, d_sig_a, rows_a, ld_a, d_sig_b,
+                     rows_b, ld_b, n_hash, bands, rows, c_min, LshListed{d_i, d_j, d_band}, triples, d_count, d_keep, (long long *)nullptr,
+                     (unsigned long long *)nullptr);
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
@@ -256,17 +291,20 @@ int launch_lsh_verify_listed(const uint32_t *d_sig, int64_t n, int64_t ld_sig, i
 size_t lsh_chunk_scan_bytes(int64_t incidences) { return up256(scan_i64_bytes(ceil_div(incidences, 64) + 1)) + 256; }
 
 // Step 3 on the enumerated incidences: verdicts into d_count / d_keep (one per incidence), kept counts per chunk of 64 into d_chunk_kept
-// (chunks + 1 entries, the last one 0), their exclusive sum into d_chunk_off; *d_distinct (zeroed here) counts the distinct candidate pairs.
-int launch_lsh_verify_enumerated(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, uint32_t c_min, const int64_t *d_off,
-                                 const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
+// (chunks + 1 entries, the last one 0), their exclusive sum into d_chunk_off (d_temp: lsh_chunk_scan_bytes(incidences)); *d_distinct
+// (zeroed here) counts the distinct candidate pairs.
+int launch_lsh_verify_enumerated(const uint32_t *d_sig_a, int64_t rows_a, int64_t ld_a, const uint32_t *d_sig_b, int64_t rows_b, int64_t ld_b, int n_hash,
+                                 int rows, uint32_t c_min, const LshSlots &slots, int64_t incidences, uint16_t *d_count, uint8_t *d_keep,
                                  int64_t *d_chunk_kept, int64_t *d_chunk_off, uint64_t *d_distinct, void *d_temp, size_t temp_bytes, hipStream_t stream) {
   const int64_t chunks = ceil_div(incidences, 64);
   DA_HIP_TRY(hipMemsetAsync(d_distinct, 0, 8, stream));
   DA_HIP_TRY(hipMemsetAsync(d_chunk_kept + chunks, 0, 8, stream));
   if (incidences > 0) {
-    const LshEnumerated src{reinterpret_cast<const long long *>(d_off), d_ids, reinterpret_cast<const unsigned long long *>(d_keys), n * bands};
-    hipLaunchKernelGGL(k_lsh_verify<LshEnumerated>, dim3(lsh_grid(chunks * 64)), dim3(LSH_THREADS), 0, stream, d_sig, n, ld_sig, n_hash, bands, rows, c_min,
-                       src, incidences, d_count, d_keep, reinterpret_cast<long long *>(d_chunk_kept), reinterpret_cast<unsigned long long *>(d_distinct));
+    with_source(slots, [&](auto src) {
+      hipLaunchKernelGGL(k_lsh_verify<decltype(src)>, dim3(lsh_grid(chunks * 64)), dim3(LSH_THREADS), 0, stream, d_sig_a, rows_a, ld_a, d_sig_b, rows_b, ld_b,
+                         n_hash, slots.bands, rows, c_min, src, incidences, d_count, d_keep, reinterpret_cast<long long *>(d_chunk_kept),
+                         reinterpret_cast<unsigned long long *>(d_distinct));
+    });
     DA_HIP_TRY(hipGetLastError());
   }
   size_t tb = temp_bytes;
@@ -277,22 +315,26 @@ int launch_lsh_verify_enumerated(const uint32_t *d_sig, int64_t n, int64_t ld_si
 
 size_t lsh_edge_sort_bytes(int64_t edges) { return up256(sort_u64_u16_bytes(edges)) + 256; }
 
-// Step 3's emit and step 4: the n diagonal entries and the kept incidences into d_key_in / d_val_in (edges = n + kept entries), sorted by
-// (i, j) into d_key_out / d_val_out.
-int launch_lsh_emit_sort(int64_t n, int n_hash, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
-                         const uint16_t *d_count, const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in,
-                         uint64_t *d_key_out, uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+// Step 3's emit and step 4: the diagonal_n diagonal entries (one set: its rows; two sets: 0) and the kept incidences into d_key_in /
+// d_val_in (edges = diagonal_n + kept entries, > 0), sorted by (i, j) into d_key_out / d_val_out (d_temp: lsh_edge_sort_bytes(edges)).
+// rows_a = the range of i.
+int launch_lsh_emit_sort(const LshSlots &slots, int64_t rows_a, int64_t diagonal_n, int n_hash, int64_t incidences, const uint16_t *d_count,
+                         const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in, uint64_t *d_key_out,
+                         uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream) {
   unsigned long long *kin = reinterpret_cast<unsigned long long *>(d_key_in), *kout = reinterpret_cast<unsigned long long *>(d_key_out);
-  hipLaunchKernelGGL(k_lsh_diagonal, dim3(lsh_grid(n)), dim3(LSH_THREADS), 0, stream, n, n_hash, kin, d_val_in);
-  DA_HIP_TRY(hipGetLastError());
-  if (incidences > 0 && edges > n) {
-    const LshEnumerated src{reinterpret_cast<const long long *>(d_off), d_ids, reinterpret_cast<const unsigned long long *>(d_keys), n * bands};
-    hipLaunchKernelGGL(k_lsh_emit, dim3(lsh_grid(ceil_div(incidences, 64) * 64)), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep,
-                       reinterpret_cast<const long long *>(d_chunk_off), n, kin, d_val_in);
+  if (diagonal_n > 0) {
+    hipLaunchKernelGGL(k_lsh_diagonal, dim3(lsh_grid(diagonal_n)), dim3(LSH_THREADS), 0, stream, diagonal_n, n_hash, kin, d_val_in);
+    DA_HIP_TRY(hipGetLastError());
+  }
+  if (incidences > 0 && edges > diagonal_n) {
+    with_source(slots, [&](auto src) {
+      hipLaunchKernelGGL(k_lsh_emit<decltype(src)>, dim3(lsh_grid(ceil_div(incidences, 64) * 64)), dim3(LSH_THREADS), 0, stream, src, incidences, d_count,
+                         d_keep, reinterpret_cast<const long long *>(d_chunk_off), diagonal_n, kin, d_val_in);
+    });
     DA_HIP_TRY(hipGetLastError());
   }
   size_t tb = temp_bytes;
-  DA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, kin, kout, d_val_in, d_val_out, (int)edges, 0, 32 + bits_for(n), stream));
+  DA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, kin, kout, d_val_in, d_val_out, (int)edges, 0, 32 + bits_for(rows_a), stream));
   return DA_OK;
 }
 
@@ -305,13 +347,13 @@ int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count
 }
 
 // ---- nearest-neighbour lists from the candidates (da_dev_lsh_knn, da_dev_lsh_knn_select) --------------------------------------------------
-// After step 3 every kept slot is a distinct pair i < j with its count.  Row i's list is the first `top` of its candidates by (count
-// descending, column ascending), so both directions of a pair are needed:
-//   5. k_lsh_knn_entries<false>: deg[i]++, deg[j]++ over the kept slots; an exclusive sum gives ptr[n + 1];
-//   6. k_lsh_knn_entries<true>: (col = j, count) into row i's segment and (col = i, count) into row j's, through a per-row cursor.  The
-//      slots of a chunk mostly share their i (the partners of one element are consecutive slots), so the i side takes ONE atomic per
-//      distinct i of the chunk and writes its entries side by side; the j side takes one atomic per entry.  The order inside a segment
-//      is whatever the scheduling gives: the selection does not depend on it;
+// After step 3 every kept slot is a distinct pair with its count.  Row i's list is the first `top` of its candidates by (count descending,
+// column ascending).  One set has i < j in every slot, so both directions of a pair are needed (BOTH); two sets list the rows of x only:
+//   5. k_lsh_knn_entries<Src, false, BOTH>: deg[i]++ and, with BOTH, deg[j]++ over the kept slots; an exclusive sum gives ptr[rows + 1];
+//   6. k_lsh_knn_entries<Src, true, BOTH>: (col = j, count) into row i's segment and, with BOTH, (col = i, count) into row j's, through a
+//      per-row cursor.  The slots of a chunk mostly share their i (the partners of one element, the run of one x row, are consecutive
+//      slots), so the i side takes ONE atomic per distinct i of the chunk and writes its entries side by side; the j side takes one atomic
+//      per entry.  The order inside a segment is whatever the scheduling gives: the selection does not depend on it;
 //   7. the selection, on the 48-bit words (0xFFFF - count) << 32 | col -- ascending word order is count descending, column ascending, and
 //      the words of a row are distinct because its columns are.  Degrees are very skewed, so there are two kernels:
 //        k_lsh_knn_select_short  rows of up to LSH_KNN_WAVE_MAX entries: a wave per row, an entry per lane, a bitonic sort by shuffles;
@@ -342,8 +384,9 @@ __device__ __forceinline__ void lsh_knn_segment(const long long *__restrict__ pt
 }
 
 // SCATTER = false: at[] are the degrees.  SCATTER = true: at[] are the cursors (they start as the row pointers) and the entries are written.
-template <bool SCATTER>
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(LshEnumerated src, int64_t slots, const uint16_t *__restrict__ count,
+// BOTH = true (one set): (col = i, count) goes to row j as well; BOTH = false (two sets): the i side only, j numbers the other set.
+template <typename Src, bool SCATTER, bool BOTH>
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(Src src, int64_t slots, const uint16_t *__restrict__ count,
                                                                  const uint8_t *__restrict__ keep, unsigned long long *__restrict__ at,
                                                                  int32_t *__restrict__ out_col, uint16_t *__restrict__ out_count) {
   const int lane = threadIdx.x & 63;
@@ -358,8 +401,10 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(LshEnumerated s
     if (kp) {
       src.get(s, i, j, t);
       cv = count[s];
-      const unsigned long long pos = atomicAdd(&at[j], 1ull);
-      if (SCATTER) { out_col[pos] = i; out_count[pos] = cv; }
+      if (BOTH) {
+        const unsigned long long pos = atomicAdd(&at[j], 1ull);
+        if (SCATTER) { out_col[pos] = i; out_count[pos] = cv; }
+      }
     }
     while (todo) {                                // one round per distinct i of the chunk
       const int leader = __ffsll((long long)todo) - 1;
@@ -562,30 +607,36 @@ int launch_lsh_knn_written(const int64_t *d_ptr, int64_t n, int64_t nnz, int top
   return DA_OK;
 }
 
-// Steps 5 and 6 on the verdicts of launch_lsh_verify_enumerated: d_ptr[n + 1] = the row pointers of the directed entries (2 per kept slot),
-// d_col / d_cnt their columns and counts; d_cursor (n + 1 words) is scratch.  *d_written (zeroed here) = the sum of min(degree, top).
-int launch_lsh_knn_entries(int64_t n, int bands, const int64_t *d_off, const int32_t *d_ids, const uint64_t *d_keys, int64_t incidences,
-                           const uint16_t *d_count, const uint8_t *d_keep, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col,
-                           uint16_t *d_cnt, uint64_t *d_written, void *d_temp, size_t temp_bytes, hipStream_t stream) {
+// Steps 5 and 6 on the verdicts of launch_lsh_verify_enumerated: d_ptr[rows_a + 1] = the row pointers of the entries (both: 2 per kept
+// slot, the rows of one set; otherwise 1, the rows of x), d_col / d_cnt their columns and counts; d_cursor (rows_a + 1 words) is scratch,
+// d_temp: lsh_knn_scan_bytes(rows_a).  *d_written (zeroed here) = the sum of min(degree, top).
+int launch_lsh_knn_entries(const LshSlots &slots, int64_t rows_a, bool both, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
+                           int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
+                           size_t temp_bytes, hipStream_t stream) {
   unsigned long long *cursor = reinterpret_cast<unsigned long long *>(d_cursor);
-  const LshEnumerated src{reinterpret_cast<const long long *>(d_off), d_ids, reinterpret_cast<const unsigned long long *>(d_keys), n * bands};
   const unsigned grid = lsh_grid(ceil_div(incidences, 64) * 64);
-  DA_HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(n + 1) * 8, stream));
+  auto pass = [&](auto scatter) {                 // the count pass and the scatter pass
+    constexpr bool SCATTER = decltype(scatter)::value;
+    with_source(slots, [&](auto src) {
+      const auto kernel = both ? k_lsh_knn_entries<decltype(src), SCATTER, true> : k_lsh_knn_entries<decltype(src), SCATTER, false>;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, d_col, d_cnt);
+    });
+  };
+  DA_HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(rows_a + 1) * 8, stream));
   DA_HIP_TRY(hipMemsetAsync(d_written, 0, 8, stream));
   if (incidences > 0 && entries > 0) {
-    hipLaunchKernelGGL(k_lsh_knn_entries<false>, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, (int32_t *)nullptr,
-                       (uint16_t *)nullptr);
+    pass(std::false_type());
     DA_HIP_TRY(hipGetLastError());
   }
   size_t tb = temp_bytes;
-  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_cursor), reinterpret_cast<long long *>(d_ptr), (int)(n + 1),
-                                              stream));
+  DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_cursor), reinterpret_cast<long long *>(d_ptr),
+                                              (int)(rows_a + 1), stream));
   if (incidences > 0 && entries > 0) {
-    DA_HIP_TRY(hipMemcpyAsync(d_cursor, d_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, stream));
-    hipLaunchKernelGGL(k_lsh_knn_entries<true>, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, d_col, d_cnt);
+    DA_HIP_TRY(hipMemcpyAsync(d_cursor, d_ptr, (size_t)(rows_a + 1) * 8, hipMemcpyDeviceToDevice, stream));
+    pass(std::true_type());
     DA_HIP_TRY(hipGetLastError());
   }
-  return launch_lsh_knn_written(d_ptr, n, entries, top, d_written, stream);
+  return launch_lsh_knn_written(d_ptr, rows_a, entries, top, d_written, stream);
 }
 
 }  // namespace da

@@ -1,4 +1,4 @@
-"""GPU tests of the two-set MinHash LSH form (lsh_cross_kernels.hip): similarityMH_lsh_cross_edges / _topk, the device pieces
+"""GPU tests of the two-set MinHash LSH form (the index and the probe of lsh_cross_kernels.hip, the back end of lsh_kernels.hip): similarityMH_lsh_cross_edges / _topk, the device pieces
 (da_dev_lsh_index_build / _probe, da_dev_lsh_cross_verify_pairs / _edges / _topk) and MinHashSession.lsh_index / lsh_cross_edges /
 lsh_cross_topk.  Every comparison is exact -- indices as integers, weights as uint64 bit patterns -- against test_lsh_cross_cpu.cross_model
 (the i < m <= j block of the one-set model on the stacked signatures) or, where a bucket is too large for a Python model, against the numpy
@@ -215,6 +215,41 @@ def test_tail_columns_count_but_make_no_candidate_and_bands_dedup(da):
     assert list(zip(i.tolist(), j.tolist(), w.tolist())) == [(3, 3, 12 / 48)]
     idx, val = device_cross(sig_x, sig_y, bands, rows, 0.25, top=2)
     assert idx.tolist() == [[-1, -1], [-1, -1], [-1, -1], [3, -1]] and val.tolist() == [[0.0, 0.0]] * 3 + [[12 / 48, 0.0]]
+
+
+def test_one_set_equals_two_sets_on_itself(da):
+    """The back end is one set of kernels with two enumerations of the slots: a set queried against its own index must give the one-set
+    result twice over -- every pair in both directions -- plus the diagonal.  70 copies of row 0 make a bucket of 71 rows in every band:
+    some chunks of 64 slots hold a single i, and one i's slots cross chunk boundaries."""
+    from dynaalign_amd import device, similarity
+    n_hash, bands, rows = 33, 4, 8
+    sig = planted(33, 150, n_hash, bands, rows)
+    sig = np.vstack([sig, np.tile(sig[0], (70, 1))])
+    n = len(sig)
+    assert n == 220
+    t = to_device(sig, n_hash + 5)
+    index = device.lsh_index_build(t, n_hash, bands, rows)
+    rows_of = np.arange(n, dtype=np.int32)
+    for thr in (0.0, 0.5):
+        i1, j1, c1 = (a.cpu().numpy() for a in device.lsh_edges(t, n_hash, bands, rows, thr))
+        one = similarity.mh_lsh_last_route()
+        i2, j2, c2 = (a.cpu().numpy() for a in device.lsh_cross_edges(index, t, t, n_hash, bands, rows, thr))
+        two = similarity.mh_lsh_last_route()
+        assert one["incidences"] >= bands * 71 * 70 // 2 and len(i1) > n
+        off, up, low, diag = i1 != j1, i2 < j2, i2 > j2, i2 == j2
+        assert (i1 <= j1).all() and off.sum() == up.sum() == low.sum() == len(i1) - n
+        assert np.array_equal(i2[up], i1[off]) and np.array_equal(j2[up], j1[off]) and np.array_equal(c2[up], c1[off])
+        order = np.lexsort((i2[low], j2[low]))                 # the lower triangle by (j, i): the upper one
+        assert np.array_equal(j2[low][order], i1[off]) and np.array_equal(i2[low][order], j1[off]) and np.array_equal(c2[low][order], c1[off])
+        assert np.array_equal(i2[diag], rows_of) and (c2[diag].view(np.uint16) == n_hash).all()
+        assert two["incidences"] == 2 * one["incidences"] + n * bands and two["verified_pairs"] == 2 * one["verified_pairs"] + n
+        idx1, key1 = (a.cpu().numpy() for a in device.lsh_knn(t, n_hash, bands, rows, 256, threshold=thr))
+        idx2, key2 = (a.cpu().numpy() for a in device.lsh_cross_topk(index, t, t, n_hash, bands, rows, 257, threshold=thr))
+        assert idx1.shape == key1.shape == (n, 256) and idx2.shape == key2.shape == (n, 257)
+        others = idx2 != rows_of[:, None]                      # every row lists itself exactly once
+        assert (others.sum(1) == 256).all() and (key2[~others].view(np.uint16) == n_hash).all()
+        assert np.array_equal(idx2[others].reshape(n, 256), idx1) and np.array_equal(key2[others].reshape(n, 256), key1)
+        assert (idx1 == -1).any() and (key1[idx1 == -1] == 0).all() and (idx1[:, :70] >= 0)[[0] + list(range(150, n))].all()
 
 
 # ---- the pieces ---------------------------------------------------------------------------------------------------------------------------
