@@ -10,7 +10,10 @@ the hot path in the package: without the HIP library and a GPU every compute
 call raises.
 """
 from ._capi import DynaAlignError, load as load_library  # noqa: F401
-from .clusterbreak import clusterbreak, clusterconsensus, clusterconsensus_device, louvain, louvain_csr, louvain_device, louvain_sync_dense, netcluster  # noqa: F401
+from .clusterbreak import (  # noqa: F401
+    clusterbreak, clusterconsensus, clusterconsensus_device, louvain, louvain_csr, louvain_device, louvain_sync_dense, netcluster,
+    components, components_dense, components_device,
+)
 from .similarity import (  # noqa: F401
     SimilarityMatrix, get_option, hash_family_seeds, mh_counts, minhash_signatures, nw_pairs,
     pack_sequences, quantile_type7, set_option, similarityMH, similarityMH_cross, similarityMH_edges, similarityNW, similarityNW_cross, similarityNW_edges,
@@ -26,6 +29,7 @@ from .similarity import (  # noqa: F401
     similarityJaccard_knn_edges_long, similarityJaccard_edges_long, similarityJaccard_cross_edges_long, similarityJaccard_stats_long,
     similarityMH_lsh_edges, lsh_edges_dense, lsh_collision_probability, similarityMH_lsh_knn, similarityMH_lsh_knn_edges, lsh_knn_dense,
     similarityMH_lsh_cross_edges, similarityMH_lsh_cross_topk, lsh_cross_edges_dense, lsh_cross_topk_dense,
+    similarityMH_lsh_components, lsh_components_dense,
 )
 
 __all__ = [
@@ -40,5 +44,6 @@ __all__ = [
     "similarityJaccard_knn_edges_long", "similarityJaccard_edges_long", "similarityJaccard_cross_edges_long", "similarityJaccard_stats_long",
     "similarityMH_lsh_edges", "lsh_edges_dense", "lsh_collision_probability", "similarityMH_lsh_knn", "similarityMH_lsh_knn_edges", "lsh_knn_dense",
     "similarityMH_lsh_cross_edges", "similarityMH_lsh_cross_topk", "lsh_cross_edges_dense", "lsh_cross_topk_dense",
+    "components", "components_dense", "components_device", "similarityMH_lsh_components", "lsh_components_dense",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

@@ -156,6 +156,12 @@ SIGNATURES = {
     "da_dev_edges_to_csr": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "da_dev_louvain_workspace_bytes": (_sz, [_i64, _i64]),
     "da_dev_louvain_csr": (_i32, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "da_components": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp]),
+    "da_dev_components_workspace_bytes": (_sz, [_i64]),
+    "da_dev_components_edges": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "da_dev_components_csr": (_i32, [_i64, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "da_dev_lsh_components": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "da_similarity_mh_lsh_components": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, _vp, _vp]),
     "da_similarity_mh_lsh_edges_begin": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, _vp, _vp]),
     "da_mh_lsh_last_route": (_i32, [_vp, _vp, _vp, _vp]),
     "da_dev_lsh_workspace_bytes": (_sz, [_i64, _i32]),

@@ -37,7 +37,7 @@ import numpy as np
 from . import _capi
 
 __all__ = ["clusterbreak", "clusterconsensus", "netcluster", "louvain", "louvain_sync_dense", "louvain_device", "threshold_edges_dense",
-           "ClusterbreakResult"]
+           "components", "components_dense", "components_device", "ClusterbreakResult"]
 
 
 def louvain(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_modularity=False):
@@ -320,6 +320,80 @@ def louvain_device(n, ei, ej, ew, resolution=1.05, seed=0, weights=True, return_
     member, q, _, _ = device.louvain_csr(up(ptr, np.int64), up(adj, np.int32), up(codes, np.int16), up(loops, np.int16), values,
                                          resolution=resolution, seed=seed, weights=weights)
     return (member, q) if return_modularity else member
+
+
+# ---- connected components: the definition (numpy), the host call and the device call that reproduce it element for element ------------------
+def _cc_edge_arrays(n, ei, ej):
+    n = int(n)
+    ei = np.ascontiguousarray(ei, np.int64).ravel()
+    ej = np.ascontiguousarray(ej, np.int64).ravel()
+    if len(ei) != len(ej):
+        raise ValueError("edge arrays differ in length")
+    if n < 0:
+        raise ValueError("n must not be negative")
+    if len(ei) and (min(ei.min(), ej.min()) < 0 or max(ei.max(), ej.max()) >= n):
+        raise ValueError("edge endpoint out of range")
+    return n, ei, ej
+
+
+def components_dense(n, ei, ej):
+    """The connected components of the undirected graph on the vertices 0 .. n - 1 with the edges (ei[e], ej[e]), as their definition in
+    numpy: what `components` (host), `components_device` and ``device.components_*`` / ``device.lsh_components`` reproduce element for
+    element.  Edges come in any order and either orientation; repeats and self-loops are harmless; endpoints outside [0, n) raise
+    ValueError; a vertex without an edge is its own component.
+
+    Returns ``(membership int32[n], n_components)``: with min C(v) the smallest vertex of v's component,
+    ``membership[v] = 1 + |{component minima smaller than min C(v)}|`` -- ids from 1 in order of first appearance.  Sizes are
+    ``np.bincount(membership)[1:]``.  n = 0 gives an empty array and 0.
+
+    The minimum is found by propagation: label[v] starts as v and every round takes, over all edges, the smaller label of the two ends and
+    then jumps label[v] <- label[label[v]] until nothing changes."""
+    n, ei, ej = _cc_edge_arrays(n, ei, ej)
+    label = np.arange(n, dtype=np.int64)
+    while True:
+        before = label.copy()
+        low = np.minimum(label[ei], label[ej])
+        np.minimum.at(label, ei, low)
+        np.minimum.at(label, ej, low)
+        while True:
+            jumped = label[label]
+            if np.array_equal(jumped, label):
+                break
+            label = jumped
+        if np.array_equal(before, label):
+            break
+    is_min = label == np.arange(n, dtype=np.int64)             # label[v] = min C(v)
+    rank = np.cumsum(is_min)                                   # 1 + the minima below, at a minimum
+    return rank[label].astype(np.int32), int(is_min.sum())
+
+
+def components(n, ei, ej, ew=None, seed=0, weights=True, return_count=False):
+    """`components_dense` through the library's host union-find (da_components; needs no GPU), in the ``cluster_fn`` calling convention:
+    ``clusterbreak(..., cluster_fn=components)`` is single-linkage splitting under the recursion's tightening quantile.  Weights and seed
+    are ignored.  Returns the membership, with return_count ``(membership, n_components)``.  An endpoint outside [0, n) raises
+    DynaAlignError (DA_ERR_BAD_ARG)."""
+    lib = _capi.load()
+    ei = np.ascontiguousarray(ei, np.int32).ravel()
+    ej = np.ascontiguousarray(ej, np.int32).ravel()
+    if len(ei) != len(ej):
+        raise ValueError("edge arrays differ in length")
+    member = np.zeros(max(int(n), 1), np.int32)
+    count = np.zeros(1, np.int64)
+    _capi.check(lib.da_components(int(n), len(ei), ei.ctypes.data, ej.ctypes.data, member.ctypes.data, count.ctypes.data))
+    member = member[:max(int(n), 0)]
+    return (member, int(count[0])) if return_count else member
+
+
+def components_device(n, ei, ej, ew=None, seed=0, weights=True, return_count=False):
+    """`components_dense` on the GPU (da_dev_components_edges), in the ``cluster_fn`` calling convention: the edge arrays are uploaded as
+    they are -- no canonical form is needed -- and `device.components_edges` labels them.  Weights and seed are ignored.  Like
+    `components_dense`, endpoints out of range raise ValueError (checked here, before the upload)."""
+    import torch
+    from . import device
+    n, ei, ej = _cc_edge_arrays(n, ei, ej)
+    up = lambda a: torch.from_numpy(a.astype(np.int32)).cuda()                              # noqa: E731
+    member, count = device.components_edges(up(ei), up(ej), n)
+    return (member, count) if return_count else member
 
 
 def _quantile_type7_sorted_parts(x, p):

@@ -440,6 +440,7 @@ Config parse_config() {
   c.trace = env_flag("DYNAALIGN_TRACE");
   c.louvain_debug = env_flag("DYNAALIGN_LOUVAIN_DEBUG");
   c.louvain_threads = (int)std::max<int64_t>(0, env_i64("DYNAALIGN_LOUVAIN_THREADS", 0));
+  c.cc_blocks = (int)std::max<int64_t>(0, std::min<int64_t>(1 << 16, env_i64("DYNAALIGN_CC_BLOCKS", 0)));
   return c;
 }
 std::atomic<const Config *> g_config{nullptr};
@@ -1919,6 +1920,47 @@ int da_dev_louvain_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, co
   if (work_bytes < louvain_device_workspace_bytes(n, 0)) return fail(DA_ERR_BAD_ARG, "device Louvain: workspace too small");
   return launch_louvain_device(n, d_ptr, d_adj, d_codes, d_loops, values, n_values, resolution, seed, d_work, work_bytes, d_membership, modularity_out,
                                levels_out, iterations_out, static_cast<hipStream_t>(stream));
+}
+
+// ---- connected components (clusterbreak.components_dense) of a resident edge list or CSR: a lock-free union-find, n labels out -----------
+size_t da_dev_components_workspace_bytes(int64_t n) { return components_workspace_bytes(n); }
+
+}  // extern "C"  (reopened below)
+namespace {
+// what the device component calls share: shapes and pointers, before the device is touched.  DA_OK with *done = true: n == 0, nothing to run.
+int components_dev_check(int64_t n, const void *d_work, size_t work_bytes, const void *d_membership, int64_t *n_components_out, bool *done) {
+  *done = false;
+  if (n < 0) return fail(DA_ERR_BAD_ARG, "n must not be negative (got %lld)", (long long)n);
+  if (!n_components_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *n_components_out = 0;
+  if (n == 0) { *done = true; return DA_OK; }
+  if (n > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "components: too many vertices");
+  if (!d_work || !d_membership) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (work_bytes < components_workspace_bytes(n)) return fail(DA_ERR_BAD_ARG, "components: workspace too small");
+  return DA_OK;
+}
+}  // namespace
+extern "C" {
+
+int da_dev_components_edges(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_code, int min_code, int64_t n_edges, int64_t n, void *d_work,
+                            size_t work_bytes, int32_t *d_membership, int32_t *d_sizes, int64_t *n_components_out, void *stream) {
+  int rc;
+  bool done;
+  if (n_edges < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if ((rc = components_dev_check(n, d_work, work_bytes, d_membership, n_components_out, &done)) != DA_OK || done) return rc;
+  if (n_edges > 0 && (!d_i || !d_j)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_components_edges(d_i, d_j, d_code, min_code, n_edges, n, d_work, work_bytes, d_membership, d_sizes, n_components_out,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int da_dev_components_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, int symmetric, void *d_work, size_t work_bytes, int32_t *d_membership,
+                          int32_t *d_sizes, int64_t *n_components_out, void *stream) {
+  int rc;
+  bool done;
+  if ((rc = components_dev_check(n, d_work, work_bytes, d_membership, n_components_out, &done)) != DA_OK || done) return rc;
+  if (!d_ptr) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_components_csr(n, d_ptr, d_adj, symmetric != 0, d_work, work_bytes, d_membership, d_sizes, n_components_out,
+                               static_cast<hipStream_t>(stream));
 }
 
 // R's quantile(x, p, type = 7) (stats::quantile.default, the default the reference's
@@ -3883,6 +3925,27 @@ int lsh_lists_device(const LshSets &s, double threshold, int top, int64_t max_ca
   route.edges = (int64_t)entries_written;
   return DA_OK;
 }
+// The components pipeline on resident signatures (one set): the verdicts, then the union step over the kept slots and the renumbering.
+// d_work: lsh_workspace_bytes(n, bands) bytes for the buckets, then components_workspace_bytes(n).  Nothing is emitted or sorted.
+int lsh_components_device(const LshSets &s, double threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_membership,
+                          int32_t *d_sizes, int64_t *n_components_out, hipStream_t stream) {
+  int rc;
+  if ((rc = lsh_elements_check("n", s.n, s.bands)) != DA_OK) return rc;
+  const size_t lsh_b = lsh_workspace_bytes(s.n, s.bands), cc_b = components_workspace_bytes(s.n);
+  if (work_bytes < lsh_b + cc_b) return fail(DA_ERR_BAD_ARG, "lsh: workspace too small (%zu bytes, %zu needed)", work_bytes, lsh_b + cc_b);
+  LshVerdicts v;
+  const StreamDrain drain{stream};
+  if ((rc = lsh_verdicts(s, threshold, max_candidates, d_work, lsh_b, v, stream)) != DA_OK) return rc;
+  void *cc_work = static_cast<char *>(d_work) + lsh_b;
+  int32_t *parent = nullptr;
+  if ((rc = launch_cc_init(s.n, cc_work, cc_b, &parent, stream)) != DA_OK ||
+      (rc = launch_lsh_union(v.slots, v.inc, v.keep.as<uint8_t>(), parent, stream)) != DA_OK ||
+      (rc = launch_cc_finish(s.n, cc_work, cc_b, d_membership, d_sizes, n_components_out, stream)) != DA_OK) return rc;
+  LshRoute &route = lsh_route();
+  route.verified = (int64_t)v.firsts;
+  route.edges = s.n + v.kept;                               // what the edge form would have emitted
+  return DA_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -4008,6 +4071,43 @@ int da_similarity_mh_lsh_knn(const uint8_t *residues, const int64_t *offsets, in
   if ((rc = lsh_lists_device(lsh_one_set(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows), threshold, top, max_candidates, work.p, wb,
                              didx.as<int32_t>(), dkey.as<uint16_t>(), nullptr)) != DA_OK) return rc;
   return topk_to_host(didx, dkey, n, top, mh_code_values(n_hash), idx_out, val_out);
+}
+
+int da_dev_lsh_components(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold, int64_t max_candidates,
+                          void *d_work, size_t work_bytes, int32_t *d_membership, int32_t *d_sizes, int64_t *n_components_out, void *stream) {
+  int rc;
+  if (n < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (!n_components_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *n_components_out = 0;
+  if (n == 0) return DA_OK;
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, threshold)) != DA_OK) return rc;
+  if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
+  if (!d_work || !d_membership) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return lsh_components_device(lsh_one_set(d_sig, n, ld_sig, n_hash, bands, rows), threshold, max_candidates, d_work, work_bytes, d_membership,
+                               d_sizes, n_components_out, static_cast<hipStream_t>(stream));
+}
+
+int da_similarity_mh_lsh_components(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                                    int rows, double threshold, int64_t max_candidates, int32_t *membership_out, int64_t *n_components_out) {
+  int rc = validate_mh(n, k, n_hash);
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !membership_out || !n_components_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *n_components_out = 0;
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, threshold, max_candidates)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf work, member;
+  const StreamDrain drain{nullptr};
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash, false)) != DA_OK || (rc = mh.signatures(k, 0, n_hash)) != DA_OK) return rc;
+  const size_t wb = lsh_workspace_bytes(n, bands) + components_workspace_bytes(n);
+  if ((rc = work.alloc(wb)) != DA_OK || (rc = member.alloc((size_t)n * sizeof(int32_t))) != DA_OK) return rc;
+  if ((rc = lsh_components_device(lsh_one_set(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows), threshold, max_candidates, work.p, wb,
+                                  member.as<int32_t>(), nullptr, n_components_out, nullptr)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(membership_out, member.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DA_OK;
 }
 
 int da_mh_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *edges_out) {

@@ -42,6 +42,7 @@ struct Config {
   // diagnostics / host clustering
   bool trace = false, louvain_debug = false;
   int louvain_threads = 0;
+  int cc_blocks = 0;                                       // connected components: cap on the workgroups of a launch (0: 8 per CU)
 };
 const Config &config();
 
@@ -322,6 +323,19 @@ size_t louvain_device_workspace_bytes(int64_t n, int64_t nnz);
 int launch_louvain_device(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, const uint16_t *d_codes, const uint16_t *d_loops, const double *values,
                           int n_values, double resolution, uint32_t seed, void *d_work, size_t work_bytes, int32_t *d_membership, double *modularity_out,
                           int32_t *levels_out, int32_t *iterations_out, hipStream_t stream);
+// components_kernels.hip: connected components (clusterbreak.components_dense) by a lock-free union-find whose roots are the component minima
+// (components_common.hpp), then ids from 1 in order of first appearance (da_dev_components_*).  launch_cc_init / launch_cc_finish frame a
+// union launch of the caller's (launch_lsh_union): parent[v] = v into the workspace; compression, renumbering, optional sizes (n entries)
+// and the number of components.  The finish and the two whole calls synchronise the stream.  1 <= n <= 2^31 - 16.
+size_t components_workspace_bytes(int64_t n);
+int components_max_blocks();   // workgroups of a grid-stride launch of this family
+int launch_cc_init(int64_t n, void *d_work, size_t work_bytes, int32_t **d_parent_out, hipStream_t stream);
+int launch_cc_finish(int64_t n, void *d_work, size_t work_bytes, int32_t *d_membership, int32_t *d_sizes, int64_t *n_components_out,
+                     hipStream_t stream);
+int launch_components_edges(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_code, int min_code, int64_t m, int64_t n, void *d_work,
+                            size_t work_bytes, int32_t *d_membership, int32_t *d_sizes, int64_t *n_components_out, hipStream_t stream);
+int launch_components_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, bool symmetric, void *d_work, size_t work_bytes,
+                          int32_t *d_membership, int32_t *d_sizes, int64_t *n_components_out, hipStream_t stream);
 // graph_kernels.hip: nearest-neighbour lists (n rows of ld >= top columns and their uint16 keys) -> the (i <= j, code) edge list of their union /
 // mutual kNN graph, the diagonal first in every row's share when `loops` (da_dev_knn_edges); d_i / d_j / d_v hold n * (top + loops) entries
 size_t knn_edges_workspace_bytes(int64_t n, int top);
@@ -465,6 +479,8 @@ int launch_lsh_emit_sort(const LshSlots &slots, int64_t rows_a, int64_t diagonal
                          const uint8_t *d_keep, const int64_t *d_chunk_off, int64_t edges, uint64_t *d_key_in, uint16_t *d_val_in, uint64_t *d_key_out,
                          uint16_t *d_val_out, void *d_temp, size_t temp_bytes, hipStream_t stream);
 int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count, int32_t *d_i, int32_t *d_j, uint16_t *d_count, hipStream_t stream);
+// ... and the components of the same graph (da_dev_lsh_components): the union step over the kept slots, into the parent array of launch_cc_init
+int launch_lsh_union(const LshSlots &slots, int64_t incidences, const uint8_t *d_keep, int32_t *d_parent, hipStream_t stream);
 // ... and the nearest-neighbour lists from the same candidates (da_dev_lsh_knn*, da_dev_lsh_cross_topk): after the verify step,
 // launch_lsh_knn_entries turns the kept slots into ragged rows (both: the two directions of every pair of one set, entries = 2 * kept;
 // otherwise the rows of x, entries = kept) and launch_lsh_knn_select takes every row's first `top` entries by (count descending, column

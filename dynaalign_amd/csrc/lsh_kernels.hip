@@ -23,6 +23,7 @@
 //      sets have no diagonal, i and j number different sets -- and k_lsh_split unpacks it.
 // The same verify kernel runs on LISTED triples (da_dev_lsh_verify_pairs, da_dev_lsh_cross_verify_pairs), so that the per-pair decision
 // can be tested on triples the pipeline never produces (a key collision, a pair of an earlier band).
+#include "components_common.hpp"
 #include "lsh_common.hpp"
 
 namespace da {
@@ -181,6 +182,22 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_emit(Src src, int64_t slots
   }
 }
 
+// The components tail (da_dev_lsh_components): the same slot enumeration as k_lsh_emit, but a kept slot is not written anywhere -- its pair
+// goes through the union step of components_common.hpp.  No chunk offsets, no 64-bit keys, no sort.  One set only: i and j number the
+// same vertices.
+template <typename Src>
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_union(Src src, int64_t slots, const uint8_t *__restrict__ keep, int32_t *parent) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
+  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
+    const int64_t s = c * 64 + lane;
+    if (s >= slots || keep[s] == 0) continue;
+    int i, j, t;
+    src.get(s, i, j, t);
+    cc_union(parent, i, j);                       // a kept slot was valid in k_lsh_verify: 0 <= i < j < n
+  }
+}
+
 __global__ __launch_bounds__(LSH_THREADS) void k_lsh_diagonal(int64_t n, int n_hash, unsigned long long *__restrict__ out_key, uint16_t *__restrict__ out_val) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -335,6 +352,19 @@ int launch_lsh_emit_sort(const LshSlots &slots, int64_t rows_a, int64_t diagonal
   }
   size_t tb = temp_bytes;
   DA_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, kin, kout, d_val_in, d_val_out, (int)edges, 0, 32 + bits_for(rows_a), stream));
+  return DA_OK;
+}
+
+// the union step over the kept slots of launch_lsh_verify_enumerated, into the parent array of launch_cc_init (one set: rows_a vertices)
+int launch_lsh_union(const LshSlots &slots, int64_t incidences, const uint8_t *d_keep, int32_t *d_parent, hipStream_t stream) {
+  if (incidences <= 0) return DA_OK;
+  if (slots.probed) return fail(DA_ERR_UNSUPPORTED, "lsh: components of two sets are not defined");
+  const unsigned grid = std::min<unsigned>(lsh_grid(ceil_div(incidences, 64) * 64), (unsigned)components_max_blocks());
+  with_source(slots, [&](auto src) {
+    hipLaunchKernelGGL(k_lsh_union<decltype(src)>, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_keep,
+                       d_parent);
+  });
+  DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
 

@@ -651,6 +651,86 @@ def louvain_csr(ptr, adj, codes, loops, values, resolution=1.05, seed=0, weights
     return member.cpu().numpy(), float(q.value), int(levels.value), [int(its[i]) for i in range(int(levels.value))]
 
 
+def components_workspace_bytes(n):
+    return int(_capi.load().da_dev_components_workspace_bytes(int(n)))
+
+
+def _components_buffers(n, dev, sizes, work, nbytes, what):
+    if work is None:
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _require_cuda(work, "work")
+    if work.dtype != torch.uint8 or not work.is_contiguous() or int(work.numel()) < nbytes:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "work must be a contiguous uint8 tensor of %s bytes" % what)
+    member = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    size_t = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if sizes else None
+    return work, member, size_t
+
+
+def _components_out(n, member, size_t, count):
+    c = int(count.value)
+    member = member[:n].cpu().numpy()
+    return (member, c, size_t[:c].cpu().numpy()) if size_t is not None else (member, c)
+
+
+def components_edges(ei, ej, n, codes=None, min_code=0, sizes=False, work=None):
+    """The connected components (clusterbreak.components_dense, reproduced element for element) of an edge list that lies in HBM
+    (da_dev_components_edges): ``ei`` / ``ej`` int32 device tensors of equal length, any order, either orientation, repeats and self-loops
+    allowed; ``n`` vertices.  ``codes`` (16-bit device tensor, uint16 bit pattern, one per edge): only the edges with code >= ``min_code``
+    count, so one list can be cut at several thresholds.  Returns (membership int32 numpy, ids from 1 in order of first appearance;
+    n_components[; sizes int32 numpy, one per component]).  Synchronises the current stream.  An endpoint outside [0, n) -- of a filtered
+    edge too -- raises DynaAlignError (DA_ERR_BAD_ARG)."""
+    lib = _capi.load()
+    n = int(n)
+    if n < 0:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "n must not be negative")
+    for t, name in ((ei, "ei"), (ej, "ej")) + (((codes, "codes"),) if codes is not None else ()):
+        _require_cuda(t, name)
+    if ei.dtype != torch.int32 or ej.dtype != torch.int32 or (codes is not None and codes.element_size() != 2):
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ei and ej int32, codes 16-bit")
+    m = int(ei.numel())
+    if int(ej.numel()) != m or (codes is not None and int(codes.numel()) != m):
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ei, ej and codes differ in length")
+    if not 0 <= int(min_code) <= 65536:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "min_code must be in 0 .. 65536")
+    if n == 0:
+        return (np.zeros(0, np.int32), 0, np.zeros(0, np.int32)) if sizes else (np.zeros(0, np.int32), 0)
+    ei, ej = ei.contiguous(), ej.contiguous()
+    codes = None if codes is None else codes.contiguous()
+    work, member, size_t = _components_buffers(n, ei.device, sizes, work, components_workspace_bytes(n), "components_workspace_bytes(n)")
+    count = ctypes.c_int64(0)
+    _call(lib.da_dev_components_edges, ei.data_ptr() if m else None, ej.data_ptr() if m else None, None if codes is None or not m else codes.data_ptr(),
+          int(min_code), m, n, work.data_ptr(), int(work.numel()), member.data_ptr(), None if size_t is None else size_t.data_ptr(),
+          ctypes.byref(count), _stream())
+    return _components_out(n, member, size_t, count)
+
+
+def components_csr(ptr, adj, symmetric=True, sizes=False, work=None):
+    """The connected components of a CSR that lies in HBM (da_dev_components_csr): ``ptr`` int64[n + 1] and ``adj`` int32[ptr[n]], exactly
+    what `edges_to_csr` and the kNN graphs of MinHashSession return (codes and loops are not needed).  ``symmetric=True`` says both
+    directions of every edge are present: only the entries with adj > row are united, half the work; pass False for any other CSR.
+    Returns (membership int32 numpy, n_components[, sizes]).  Synchronises the current stream.  Row pointers that do not start at 0,
+    decrease or leave [0, nnz], and a neighbour outside [0, n), raise DynaAlignError (DA_ERR_BAD_ARG)."""
+    lib = _capi.load()
+    _require_cuda(ptr, "ptr")
+    n = int(ptr.numel()) - 1
+    if n < 0:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr must hold n + 1 row pointers")
+    if n == 0:
+        return (np.zeros(0, np.int32), 0, np.zeros(0, np.int32)) if sizes else (np.zeros(0, np.int32), 0)
+    _require_cuda(adj, "adj")
+    if ptr.dtype != torch.int64 or adj.dtype != torch.int32:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr int64, adj int32")
+    nnz = int(adj.numel())
+    if int(ptr[n].item()) != nnz:
+        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr[n] (%d) is not the number of adjacency entries (%d)" % (int(ptr[n].item()), nnz))
+    ptr, adj = ptr.contiguous(), adj.contiguous()
+    work, member, size_t = _components_buffers(n, ptr.device, sizes, work, components_workspace_bytes(n), "components_workspace_bytes(n)")
+    count = ctypes.c_int64(0)
+    _call(lib.da_dev_components_csr, n, ptr.data_ptr(), adj.data_ptr() if nnz else None, 1 if symmetric else 0, work.data_ptr(), int(work.numel()),
+          member.data_ptr(), None if size_t is None else size_t.data_ptr(), ctypes.byref(count), _stream())
+    return _components_out(n, member, size_t, count)
+
+
 def similarity_mh(ds, k, n_hash, seeds, out=None):
     """similarityMH (src/minHash.cpp:119-188) on a device-resident set, one C call: K1 + K1b + K2, with byte-identical
     sequences collapsed first when that pays (da_dev_similarity_mh).  Returns the (n, n) float64 tensor."""
@@ -1026,6 +1106,24 @@ def lsh_edges(sig, n_hash, bands, rows, threshold, max_candidates=1 << 32, capac
     run(capacity, ei.data_ptr(), ej.data_ptr(), ec.data_ptr())
     got = min(m.value, capacity)
     return ei[:got], ej[:got], ec[:got]
+
+
+def lsh_components(sig, n_hash, bands, rows, threshold, max_candidates=1 << 32, sizes=False, work=None):
+    """The connected components of the LSH threshold graph of resident signatures (da_dev_lsh_components): what
+    ``clusterbreak.components_dense`` gives on the edges of `lsh_edges` for the same arguments -- near-duplicate families, single-linkage
+    clusters at the cut -- without emitting, sorting or returning an edge: the kept candidate pairs go straight into the union step.
+    Returns (membership int32 numpy, n_components[, sizes]).  ``work``: `lsh_workspace_bytes` (n, bands) + `components_workspace_bytes` (n)
+    bytes.  ``mh_lsh_last_route()["edges"]`` has the number of edges `lsh_edges` would have returned.  Synchronises the stream."""
+    lib = _capi.load()
+    n, ld = _sig_block(sig, n_hash)
+    if n == 0:
+        return (np.zeros(0, np.int32), 0, np.zeros(0, np.int32)) if sizes else (np.zeros(0, np.int32), 0)
+    nbytes = lsh_workspace_bytes(n, bands) + components_workspace_bytes(n)
+    work, member, size_t = _components_buffers(n, sig.device, sizes, work, nbytes, "lsh_workspace_bytes(n, bands) + components_workspace_bytes(n)")
+    count = ctypes.c_int64(0)
+    _call(lib.da_dev_lsh_components, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), int(max_candidates),
+          work.data_ptr(), int(work.numel()), member.data_ptr(), None if size_t is None else size_t.data_ptr(), ctypes.byref(count), _stream())
+    return _components_out(n, member, size_t, count)
 
 
 # The row classes of the selection (lsh_kernels.hip: LSH_KNN_WAVE_MAX, LSH_KNN_LDS_WORDS): a row of up to LSH_KNN_WAVE_MAX entries is sorted

@@ -13,6 +13,8 @@ full set can stay in HBM and a recursion level only needs K1b (codes of the subs
     thr, ptr, j, w = s.cross_edges(new, 0.99, idx=idx)              # == similarityMH_cross_edges(new, sequences[idx], 4, 500, 0.99, seed=12345) as CSR
     i, v = s.knn(10, idx)                                           # == similarityMH_knn(sequences[idx], 4, 500, 10, seed=12345)
     thr, m, ptr, adj, codes, loops, values = s.knn_csr(idx, 10)     # the kNN graph of those lists as CSR (== similarityMH_knn_edges(...))
+    member, c = s.lsh_components(12, 4, 0.5, idx)                   # == similarityMH_lsh_components(sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) at n_hash = 48
+    member, c = s.components(idx, thresh_p=0.8)                     # == components_dense on s.edges(idx, thresh_p=0.8), the graph kept on the device
     thr, i, j, w = s.lsh_edges(12, 4, 0.5, idx)                     # == similarityMH_lsh_edges(sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) at n_hash = 48
     i, v = s.lsh_knn(12, 4, 10, idx)                                # == similarityMH_lsh_knn(sequences[idx], 4, 48, 12, 4, 10, seed=12345) at n_hash = 48
     thr, ptr, j, w = s.lsh_cross_edges(new, 12, 4, 0.5, idx)        # == similarityMH_lsh_cross_edges(new, sequences[idx], 4, 48, 12, 4, 0.5, seed=12345) as CSR
@@ -294,6 +296,20 @@ class MinHashSession:
         ei, ej, ec = device.lsh_edges(sig[:m], self.n_hash, bands, rows, threshold, max_candidates=max_candidates)
         c = ec.cpu().numpy().view(np.uint16).astype(np.float64)
         return float(threshold), ei.cpu().numpy(), ej.cpu().numpy(), c / np.float64(self.n_hash)
+
+    def lsh_components(self, bands, rows, threshold, idx=None, max_candidates=1 << 32):
+        """``(membership, n_components)`` == similarityMH_lsh_components(sequences[idx], k, n_hash, bands, rows, threshold, seed=session.seed),
+        from the resident signatures: the components of `lsh_edges` for the same arguments, without the edge list -- n labels cross to the
+        host.  Positions are those in idx."""
+        sig, m = self._subset(idx)
+        return device.lsh_components(sig[:m], self.n_hash, bands, rows, threshold, max_candidates=max_candidates)
+
+    def components(self, idx=None, thresh_p=0.8):
+        """``(membership, n_components)``: the connected components of the graph `edges` (idx, thresh_p) returns -- single-linkage groups at
+        the quantile threshold -- by `device.components_csr` on the tensors of ``edges_csr(idx, thresh_p, on_device=True)``: the graph
+        never leaves the device."""
+        _, _, ptr, adj, _, _, _ = self.edges_csr(idx, thresh_p, on_device=True)
+        return device.components_csr(ptr, adj, symmetric=True)
 
     def lsh_knn(self, bands, rows, top=10, idx=None, threshold=0.0, max_candidates=1 << 32):
         """``(idx, val)`` == similarityMH_lsh_knn(sequences[idx], k, n_hash, bands, rows, top, threshold=threshold, seed=session.seed), from the

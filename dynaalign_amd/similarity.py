@@ -941,6 +941,29 @@ def lsh_edges_dense(sig, bands, rows, threshold):
     return p[keep, 0].astype(np.int32), p[keep, 1].astype(np.int32), w[keep]
 
 
+def similarityMH_lsh_components(sequences, k=4, n_hash=50, bands=10, rows=5, threshold=0.5, *, seed=None, max_candidates=1 << 32):
+    """The connected components of the graph `similarityMH_lsh_edges` returns for the same arguments -- everything that is transitively
+    similar at the threshold: duplicate classes at 1.0, near-duplicate families at 0.9 -- as ``(membership int32[n], n_components)``, ids
+    from 1 in order of first appearance.  Exactly ``lsh_components_dense(minhash_signatures(sequences, k, n_hash, seed=seed), bands, rows,
+    threshold)``.  The edges are never emitted, sorted or copied: the kept candidate pairs go into a union-find on the device and n labels
+    come back.  Errors as `similarityMH_lsh_edges`."""
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    member = np.zeros(max(n, 1), np.int32)
+    cnt = np.zeros(1, np.int64)
+    _capi.check(lib.da_similarity_mh_lsh_components(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, _as_int(bands, "bands"),
+                                                    _as_int(rows, "rows"), float(threshold), int(max_candidates), member.ctypes.data,
+                                                    cnt.ctypes.data))
+    return member[:n], int(cnt[0])
+
+
+def lsh_components_dense(sig, bands, rows, threshold):
+    """The definition ``similarityMH_lsh_components`` is exact against, in numpy: `clusterbreak.components_dense` on the edges of
+    `lsh_edges_dense` -> ``(membership int32[n], n_components)``."""
+    from .clusterbreak import components_dense
+    i, j, _ = lsh_edges_dense(sig, bands, rows, threshold)
+    return components_dense(np.asarray(sig).shape[0], i, j)
+
+
 def similarityMH_lsh_knn(sequences, k=4, n_hash=50, bands=10, rows=5, top=10, *, threshold=0.0, seed=None, max_candidates=1 << 32):
     """Nearest-neighbour lists from LSH candidates instead of all n (n - 1) pairs: ``(idx, val)``, (n, top) int32 and (n, top) float64.
     Row i lists the first ``top`` of ``{j != i : i and j agree in all columns of some band, c / n_hash >= threshold}`` by c descending, then

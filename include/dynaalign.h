@@ -60,6 +60,8 @@ extern "C" {
  *  da_dev_lsh_[band_keys | verify_pairs | edges | knn | knn_select | workspace_bytes] -- likewise)
  * (the two-set LSH entry points -- da_similarity_mh_lsh_cross_[edges_begin | topk], da_dev_lsh_index_[bytes | build | probe],
  *  da_dev_lsh_cross_[verify_pairs | workspace_bytes | edges | topk] -- likewise)
+ * (the connected-components entry points -- da_components, da_dev_components_[workspace_bytes | edges | csr], da_dev_lsh_components,
+ *  da_similarity_mh_lsh_components -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1129,6 +1131,46 @@ int da_dev_louvain_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, co
                        const double *values, int32_t n_values, double resolution, uint32_t seed, void *d_work, size_t work_bytes,
                        int32_t *d_membership, double *modularity_out, int32_t *levels_out, int32_t *iterations_out /* [32] */, void *stream);
 
+/* ---- connected components: single-linkage groups of a graph, n labels and no edge list out ----------------------------------------------
+ * The definition every entry below reproduces element for element is clusterbreak.components_dense (numpy): the graph is undirected on
+ * the vertices 0 .. n - 1; edges come in any order and either orientation; repeats and self-loops are harmless; a vertex without an edge
+ * is its own component.  With min C(v) the smallest vertex of v's component, membership[v] = 1 + the number of component minima below
+ * min C(v): ids from 1 in order of first appearance, the convention of every membership here.  The result is a set property of the graph,
+ * so it is deterministic: it depends on neither the order of the edges nor the scheduling of the device.
+ *
+ * da_components: HOST code, a union-find in plain C++; needs no device.  The CPU twin of the device calls and the fallback for small
+ *   graphs.  n < 0, n_edges < 0, n > 2^31 - 16, a NULL n_components_out, a NULL membership_out with n > 0 and NULL edge arrays with
+ *   n_edges > 0 are refused first (DA_ERR_BAD_ARG); n == 0 returns DA_OK with 0 components; an endpoint outside [0, n) returns
+ *   DA_ERR_BAD_ARG naming the edge, before anything is indexed by it. */
+int da_components(int64_t n, int64_t n_edges, const int32_t *ei, const int32_t *ej, int32_t *membership_out, int64_t *n_components_out);
+/* The device calls, on graphs that lie in device memory.  A lock-free union-find in 32-bit words: the larger of two roots is hooked under
+ * the smaller with one compare-and-swap that expects it to be a root still; a failed swap re-finds from the value it read.  At every
+ * instant parent[x] <= x, parent[x] is a vertex of x's component, and a vertex that stopped being a root stays one no more -- so a tree's
+ * root is the minimum of its vertices and the labels do not depend on scheduling.  No lane waits for another; there is no flag, no lock and
+ * no host loop: validate, init, ONE union launch, compress, flag roots, one exclusive sum, label.  find does not shorten paths (DESIGN.md
+ * section 7).  k_cc_validate checks, before anything indexes by an endpoint, that every listed endpoint is in [0, n) -- filtered edges
+ * included -- and, for the CSR, that the row pointers start at 0, do not decrease and end at nnz = d_ptr[n]: a violation returns
+ * DA_ERR_BAD_ARG and launches nothing further.
+ * All three: d_membership int32[n] (device); d_sizes may be NULL, else int32[n] (device): entry c - 1 = the size of component c, the entries
+ * from n_components on 0; *n_components_out is host memory.  n < 0, n_edges < 0, NULL pointers and a workspace that is too small are refused
+ * before the device is touched (DA_ERR_BAD_ARG); n == 0 returns DA_OK with 0 components and reads nothing; n > 2^31 - 16 returns
+ * DA_ERR_UNSUPPORTED.  Edge counts are 64-bit.  The calls synchronise `stream` (one total is read back; the validation reads one word).
+ * da_dev_components_workspace_bytes: the parent array, the root flags, the scan output and the hipcub scratch, about 12 bytes per vertex; any
+ *   alignment.  A size query that launches nothing and needs no device; n outside [0, 2^31 - 16] is clamped for the size.
+ * da_dev_components_edges: an edge list d_i / d_j (int32, n_edges entries).  d_code may be NULL; otherwise only the edges with
+ *   d_code[e] >= min_code count (uint16 codes, e.g. the counts of da_dev_lsh_edges or the codes of da_dev_extract_edges): one list can be
+ *   cut at several thresholds without being recomputed.
+ * da_dev_components_csr: the d_ptr (int64[n + 1]) / d_adj (int32[d_ptr[n]]) that da_dev_edges_to_csr and the kNN graphs produce; codes and
+ *   loops are not needed.  symmetric != 0 says the CSR holds both directions of every edge: only the entries with adj > row are united,
+ *   which halves the work (an asymmetric CSR passed as symmetric loses the edges listed in their lower direction only).  Rows need not
+ *   be sorted; diagonal entries and repeats are harmless.  A wave takes a row of up to 64 entries, the workgroup a longer one. */
+size_t da_dev_components_workspace_bytes(int64_t n);
+int da_dev_components_edges(const int32_t *d_i, const int32_t *d_j, const uint16_t *d_code /* may be NULL */, int min_code, int64_t n_edges,
+                            int64_t n, void *d_work, size_t work_bytes, int32_t *d_membership, int32_t *d_sizes /* may be NULL, n entries */,
+                            int64_t *n_components_out, void *stream);
+int da_dev_components_csr(int64_t n, const int64_t *d_ptr, const int32_t *d_adj, int symmetric, void *d_work, size_t work_bytes,
+                          int32_t *d_membership, int32_t *d_sizes, int64_t *n_components_out, void *stream);
+
 /* ---- MinHash LSH banding: the threshold graph of ONE set from bucketed candidates, not from all n (n - 1) / 2 pairs ---------------------
  * sig = the n x n_hash signatures of da_minhash_signatures.  bands >= 1, rows >= 1, bands * rows <= n_hash; band t = columns
  * [t * rows, (t + 1) * rows); columns >= bands * rows belong to no band but count.  cand(i, j): some band agrees in all its columns.
@@ -1170,6 +1212,22 @@ int da_dev_lsh_verify_pairs(const uint32_t *d_sig, int64_t n, int64_t ld_sig, in
 int da_dev_lsh_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold,
                      int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, uint16_t *d_count,
                      int64_t capacity, int64_t *n_edges_out, void *stream);
+/* The connected components of that edge set -- near-duplicate families, single-linkage clusters at the cut -- without the edge list:
+ * membership as da_components gives it on the edges of da_dev_lsh_edges for the same arguments (the definition above).  One set only.
+ * da_dev_lsh_components: buckets -> the enumerated verify -> the union step on every kept slot (k_lsh_union) -> compress -> renumber.  No
+ *   emit, no 64-bit keys, no edge sort.  d_work: da_dev_lsh_workspace_bytes(n, bands) + da_dev_components_workspace_bytes(n) bytes, any
+ *   alignment.  d_membership int32[n], d_sizes NULL or int32[n] (device), *n_components_out host.  n == 0 returns DA_OK with 0 components;
+ *   otherwise the checks of da_dev_lsh_edges, all before the device is touched.  Synchronises the stream.  da_mh_lsh_last_route reports
+ *   buckets, incidences and verified pairs as for the edge form; `edges` = the kept pairs + n, the number the edge form would have
+ *   emitted, so the two calls can be compared.
+ * da_similarity_mh_lsh_components: host boundary; membership_out int32[n].  Checks everything da_similarity_mh_lsh_edges_begin checks, in
+ *   its order and with its texts, before any device is needed; then n_hash > 65535 (DA_ERR_UNSUPPORTED). */
+int da_dev_lsh_components(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double threshold,
+                          int64_t max_candidates, void *d_work, size_t work_bytes, int32_t *d_membership, int32_t *d_sizes,
+                          int64_t *n_components_out, void *stream);
+int da_similarity_mh_lsh_components(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds,
+                                    int bands, int rows, double threshold, int64_t max_candidates, int32_t *membership_out,
+                                    int64_t *n_components_out);
 /* Nearest-neighbour lists from the same candidates: row i lists the first `top` (1 .. 1024, NOT clamped to n - 1) members of
  *     { j != i : cand(i, j) and (double)c / (double)n_hash >= threshold }   by c descending, then j ascending;
  * a row with fewer candidates is padded with index -1 / value 0.0 (count 0).  A real entry has c >= rows >= 1, so a value > 0 marks
