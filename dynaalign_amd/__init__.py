@@ -30,6 +30,7 @@ from .similarity import (  # noqa: F401
     similarityMH_lsh_edges, lsh_edges_dense, lsh_collision_probability, similarityMH_lsh_knn, similarityMH_lsh_knn_edges, lsh_knn_dense,
     similarityMH_lsh_cross_edges, similarityMH_lsh_cross_topk, lsh_cross_edges_dense, lsh_cross_topk_dense,
     similarityMH_lsh_components, lsh_components_dense,
+    similarityNW_lsh_edges, similarityNW_lsh_cross_edges, nw_lsh_edges_dense, nw_lsh_cross_edges_dense, nw_lsh_last_route,
 )
 
 __all__ = [
@@ -45,5 +46,6 @@ __all__ = [
     "similarityMH_lsh_edges", "lsh_edges_dense", "lsh_collision_probability", "similarityMH_lsh_knn", "similarityMH_lsh_knn_edges", "lsh_knn_dense",
     "similarityMH_lsh_cross_edges", "similarityMH_lsh_cross_topk", "lsh_cross_edges_dense", "lsh_cross_topk_dense",
     "components", "components_dense", "components_device", "similarityMH_lsh_components", "lsh_components_dense",
+    "similarityNW_lsh_edges", "similarityNW_lsh_cross_edges", "nw_lsh_edges_dense", "nw_lsh_cross_edges_dense", "nw_lsh_last_route",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

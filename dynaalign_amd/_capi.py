@@ -181,6 +181,17 @@ SIGNATURES = {
     "da_dev_lsh_cross_topk": (_i32, [_vp, _sz, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
     "da_similarity_mh_lsh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, _vp, _vp]),
     "da_similarity_mh_lsh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i32, _i64, _vp, _vp]),
+    "da_dev_nw_rescore_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "da_dev_nw_rescore_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "da_dev_lsh_nw_edges": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _sz, _vp, _vp,
+                                   _vp, _vp, _i64, _vp, _vp]),
+    "da_dev_lsh_cross_nw_edges": (_i32, [_vp, _sz, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _vp, _vp, _vp, _i32,
+                                         _i32, _i32, C.c_double, _vp, _sz, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "da_similarity_nw_lsh_edges_begin": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, C.c_char_p, _i32, _i32, C.c_double,
+                                                _vp, _vp]),
+    "da_similarity_nw_lsh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, C.c_char_p,
+                                                      _i32, _i32, C.c_double, _vp, _vp]),
+    "da_nw_lsh_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "da_matrix_id": (_i32, [C.c_char_p]),
     "da_shard_rows": (_i64, [_i64, _i32, _i32]),
     "da_shard_ld": (_i64, [_i64, _i32, _i32]),

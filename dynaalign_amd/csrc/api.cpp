@@ -4321,6 +4321,266 @@ int da_similarity_mh_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_
   return topk_to_host(didx, dkey, m, top, mh_code_values(n_hash), idx_out, val_out);
 }
 
+// ---- NW identity on MinHash LSH candidates (nw_lsh_kernels.hip): the LSH back end's sorted candidate list scored by alignment --------------
+}  // extern "C"  (reopened below)
+namespace {
+struct NwLshRoute { int64_t buckets = 0, incidences = 0, verified = 0, aligned = 0, shorts = 0, longs = 0, edges = 0; };
+NwLshRoute &nw_lsh_route() { static thread_local NwLshRoute r; return r; }
+
+// min_matches[length], length 0 .. 2048 (two sequences of 1024 residues and no diagonal step): the smallest matches > 0 whose weight --
+// the divide the host entries use for the weights -- reaches the threshold, length + 1 when none does.  The weight grows with matches.
+constexpr int NWL_TABLE_LEN = 2049;
+std::vector<int32_t> nwl_min_matches(double threshold) {
+  std::vector<int32_t> t((size_t)NWL_TABLE_LEN);
+  for (int len = 0; len < NWL_TABLE_LEN; ++len) {
+    int lo = 1, hi = len + 1;                                // the answer is in [lo, hi]
+    while (lo < hi) {
+      const int mid = lo + (hi - lo) / 2;
+      if ((double)mid / (double)len >= threshold) hi = mid; else lo = mid + 1;
+    }
+    t[(size_t)len] = lo;
+  }
+  return t;
+}
+int nwl_threshold_check(double threshold, double mh_threshold) {
+  if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(DA_ERR_BAD_ARG, "threshold must be in [0, 1]");
+  if (!(mh_threshold >= 0.0 && mh_threshold <= 1.0)) return fail(DA_ERR_BAD_ARG, "mh_threshold must be in [0, 1]");
+  return DA_OK;
+}
+// the encoded sequences the pairs index: i numbers x, j numbers y (one set: the same buffers)
+struct NwlSeqs {
+  const uint8_t *x_codes; const int64_t *x_off; int64_t m;
+  const uint8_t *y_codes; const int64_t *y_off; int64_t n;
+};
+// The pipeline on resident signatures and resident encoded sequences: the candidates of lsh_edges_device at mh_threshold, their
+// (matches, length), the verdicts, and the kept entries -- the first min(capacity, kept) of them -- in d_i / d_j / d_matches / d_length.
+// own: four buffers to allocate for the whole list instead (the host entries).  Synchronises the stream.
+int lsh_nw_edges_device(const LshSets &s, const NwlSeqs &q, double mh_threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int matrix_id,
+                        int gap_open, int gap_ext, double threshold, int32_t *d_i, int32_t *d_j, int32_t *d_matches, int32_t *d_length, int64_t capacity,
+                        int64_t *n_edges_out, hipStream_t stream, DevBuf *own = nullptr) {
+  int rc;
+  DevBuf key, val, ci, cj, mt, ln, keep, ckept, coff, temp, table, work;
+  const StreamDrain drain{stream};
+  NwLshRoute &route = nw_lsh_route();
+  route = NwLshRoute();
+  int64_t cand = 0;
+  if ((rc = lsh_edges_device(s, mh_threshold, max_candidates, d_work, work_bytes, key, val, &cand, stream)) != DA_OK) return rc;
+  const LshRoute &lr = lsh_route();
+  route.buckets = lr.buckets; route.incidences = lr.incidences; route.verified = lr.verified; route.aligned = cand;
+  *n_edges_out = 0;
+  if (cand == 0) return DA_OK;
+  const std::vector<int32_t> min_matches = nwl_min_matches(threshold);
+  const int64_t chunks = ceil_div(cand, 64);
+  const size_t ib = (size_t)cand * sizeof(int32_t), scan_b = nwl_keep_scan_bytes(cand);
+  // the decision words of the short pairs in flight: what the budget (DYNAALIGN_BLOCK_BYTES, or half of the free memory) leaves, one wavefront at least
+  const size_t fixed_b = nw_rescore_fixed_bytes(cand), full_b = nw_rescore_workspace_bytes(cand, false), min_b = nw_rescore_workspace_bytes(cand, true);
+  const size_t wb = std::max(min_b, std::min(full_b, fixed_b + block_budget()));
+  if ((rc = ci.alloc(ib)) != DA_OK || (rc = cj.alloc(ib)) != DA_OK || (rc = mt.alloc(ib)) != DA_OK || (rc = ln.alloc(ib)) != DA_OK ||
+      (rc = keep.alloc((size_t)cand)) != DA_OK || (rc = ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
+      (rc = temp.alloc(scan_b)) != DA_OK || (rc = table.alloc((size_t)NWL_TABLE_LEN * sizeof(int32_t))) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(table.p, min_matches.data(), (size_t)NWL_TABLE_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
+  if ((rc = launch_nwl_split(key.as<uint64_t>(), cand, ci.as<int32_t>(), cj.as<int32_t>(), stream)) != DA_OK) return rc;
+  int64_t counts[3] = {0, 0, 0};
+  if ((rc = launch_nw_rescore(q.x_codes, q.x_off, q.m, q.y_codes, q.y_off, q.n, ci.as<int32_t>(), cj.as<int32_t>(), cand, matrix_id, gap_open, gap_ext,
+                              mt.as<int32_t>(), ln.as<int32_t>(), work.p, wb, counts, stream)) != DA_OK) return rc;
+  route.shorts = counts[0]; route.longs = counts[1];
+  if (counts[2] > 0)
+    return fail(DA_ERR_UNSUPPORTED, "nw lsh: %lld candidate pairs have an empty sequence or one over 1024 residues", (long long)counts[2]);
+  if ((rc = launch_nwl_keep(mt.as<int32_t>(), ln.as<int32_t>(), cand, table.as<int32_t>(), NWL_TABLE_LEN, keep.as<uint8_t>(), ckept.as<int64_t>(),
+                            coff.as<int64_t>(), temp.p, scan_b, stream)) != DA_OK) return rc;
+  int64_t kept = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&kept, coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  if (own) {                                                // a host entry: the whole list, in buffers sized now that its length is known
+    for (int f = 0; f < 4; ++f)
+      if ((rc = own[f].alloc((size_t)std::max<int64_t>(kept, 1) * sizeof(int32_t))) != DA_OK) return rc;
+    d_i = own[0].as<int32_t>(); d_j = own[1].as<int32_t>(); d_matches = own[2].as<int32_t>(); d_length = own[3].as<int32_t>();
+    capacity = kept;
+  }
+  if ((rc = launch_nwl_emit(ci.as<int32_t>(), cj.as<int32_t>(), mt.as<int32_t>(), ln.as<int32_t>(), keep.as<uint8_t>(), coff.as<int64_t>(), cand,
+                            std::min(capacity, kept), d_i, d_j, d_matches, d_length, stream)) != DA_OK) return rc;
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  route.edges = kept;
+  *n_edges_out = kept;
+  return DA_OK;
+}
+// what the device entries check of the sequences, the scoring and the outputs
+int lsh_nw_dev_check(const NwlSeqs &q, int matrix_id, double threshold, const void *d_work, const void *d_i, const void *d_j, const void *d_matches,
+                     const void *d_length, int64_t capacity, const int64_t *n_edges_out) {
+  if (!q.x_codes || !q.x_off || !q.y_codes || !q.y_off) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (!matrix_table_host(matrix_id)) return fail(DA_ERR_BAD_ARG, "matrix id %d out of range", matrix_id);
+  if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(DA_ERR_BAD_ARG, "threshold must be in [0, 1]");
+  if (!n_edges_out || !d_work) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (capacity < 0) return fail(DA_ERR_BAD_ARG, "negative capacity");
+  if (capacity > 0 && (!d_i || !d_j || !d_matches || !d_length)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return DA_OK;
+}
+// the kept list of a host entry: the pipeline with buffers of its own, the lists copied out, the weights divided here
+int lsh_nw_edges_to_host(const LshSets &s, const NwlSeqs &q, double mh_threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int matrix_id,
+                         int gap_open, int gap_ext, double threshold, da_edges **handle_out, int64_t *n_edges_out) {
+  int rc;
+  int64_t edges = 0;
+  DevBuf own[4];
+  if ((rc = lsh_nw_edges_device(s, q, mh_threshold, max_candidates, d_work, work_bytes, matrix_id, gap_open, gap_ext, threshold, nullptr, nullptr, nullptr,
+                                nullptr, 0, &edges, nullptr, own)) != DA_OK) return rc;
+  std::unique_ptr<da_edges> h(new da_edges);
+  EdgeSet &es = h->es;
+  es.threshold = threshold;
+  es.i.resize((size_t)edges); es.j.resize((size_t)edges); es.w.resize((size_t)edges);
+  std::vector<int32_t> hm((size_t)edges), hl((size_t)edges);
+  if (edges > 0) {
+    const size_t ib = (size_t)edges * sizeof(int32_t);
+    DA_HIP_TRY(hipMemcpy(es.i.data(), own[0].p, ib, hipMemcpyDeviceToHost));
+    DA_HIP_TRY(hipMemcpy(es.j.data(), own[1].p, ib, hipMemcpyDeviceToHost));
+    DA_HIP_TRY(hipMemcpy(hm.data(), own[2].p, ib, hipMemcpyDeviceToHost));
+    DA_HIP_TRY(hipMemcpy(hl.data(), own[3].p, ib, hipMemcpyDeviceToHost));
+  }
+  for (size_t e = 0; e < (size_t)edges; ++e) es.w[e] = (double)hm[e] / (double)hl[e];
+  h->n_edges = edges;
+  *n_edges_out = edges;
+  *handle_out = h.release();
+  return DA_OK;
+}
+// the NW checks of the host entries behind the LSH ones: the residues, no empty sequence, the longest sequence
+int nwl_host_lengths(const char *what, const int64_t *off, int64_t count) {
+  for (int64_t i = 0; i < count; ++i)
+    if (off[i + 1] == off[i])
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld%s is empty: its similarities are 0/0 = NaN, which no threshold orders", (long long)(i + 1), what);
+  for (int64_t i = 0; i < count; ++i)
+    if (off[i + 1] - off[i] > 1024)
+      return fail(DA_ERR_UNSUPPORTED, "the alignment kernels take sequences up to 1024 residues (sequence %lld%s: %lld)", (long long)(i + 1), what,
+                  (long long)(off[i + 1] - off[i]));
+  return DA_OK;
+}
+// the residues of an uploaded set encoded for the DP
+int nwl_encode(const DeviceInput &in, int64_t total, DevBuf &codes, DevBuf &bad) {
+  int rc;
+  if ((rc = codes.alloc((size_t)std::max<int64_t>(total, 1))) != DA_OK || (rc = bad.alloc(sizeof(int32_t))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(int32_t), nullptr));
+  return launch_nw_encode(in.res.as<uint8_t>(), total, codes.as<uint8_t>(), bad.as<int32_t>(), nullptr);
+}
+}  // namespace
+extern "C" {
+
+size_t da_dev_nw_rescore_workspace_bytes(int64_t pairs, int64_t max_len, int minimal) {
+  (void)max_len;   // the wavefront kernel stores nothing without ops: only the lane-per-pair kernel's decision words count, whatever the lengths
+  return nw_rescore_workspace_bytes(pairs, minimal != 0);
+}
+
+int da_dev_nw_rescore_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, int64_t m, const uint8_t *d_y_codes, const int64_t *d_y_offsets,
+                            int64_t n, const int32_t *d_i, const int32_t *d_j, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
+                            int32_t *d_matches, int32_t *d_length, void *d_work, size_t work_bytes, void *stream_v) {
+  if (pairs < 0 || m < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (!matrix_table_host(matrix_id)) return fail(DA_ERR_BAD_ARG, "matrix id %d out of range", matrix_id);
+  NwLshRoute &route = nw_lsh_route();
+  route = NwLshRoute();
+  if (pairs == 0) return DA_OK;
+  if (!d_x_codes || !d_x_offsets || !d_y_codes || !d_y_offsets || !d_i || !d_j || !d_matches || !d_length) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  int rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  int64_t counts[3] = {0, 0, 0};
+  if ((rc = launch_nw_rescore(d_x_codes, d_x_offsets, m, d_y_codes, d_y_offsets, n, d_i, d_j, pairs, matrix_id, gap_open, gap_ext, d_matches, d_length,
+                              d_work, work_bytes, counts, stream)) != DA_OK) return rc;
+  route.aligned = pairs; route.shorts = counts[0]; route.longs = counts[1];
+  return DA_OK;
+}
+
+int da_dev_lsh_nw_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double mh_threshold, int64_t max_candidates,
+                        const uint8_t *d_codes, const int64_t *d_offsets, int matrix_id, int gap_open, int gap_ext, double threshold, void *d_work,
+                        size_t work_bytes, int32_t *d_i, int32_t *d_j, int32_t *d_matches, int32_t *d_length, int64_t capacity, int64_t *n_edges_out,
+                        void *stream) {
+  int rc;
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, mh_threshold)) != DA_OK) return rc;
+  if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
+  const NwlSeqs q{d_codes, d_offsets, n, d_codes, d_offsets, n};
+  if ((rc = lsh_nw_dev_check(q, matrix_id, threshold, d_work, d_i, d_j, d_matches, d_length, capacity, n_edges_out)) != DA_OK) return rc;
+  return lsh_nw_edges_device(lsh_one_set(d_sig, n, ld_sig, n_hash, bands, rows), q, mh_threshold, max_candidates, d_work, work_bytes, matrix_id, gap_open,
+                             gap_ext, threshold, d_i, d_j, d_matches, d_length, capacity, n_edges_out, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_cross_nw_edges(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n,
+                              int64_t ld_y, int n_hash, int bands, int rows, double mh_threshold, int64_t max_candidates, const uint8_t *d_x_codes,
+                              const int64_t *d_x_offsets, const uint8_t *d_y_codes, const int64_t *d_y_offsets, int matrix_id, int gap_open, int gap_ext,
+                              double threshold, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, int32_t *d_matches, int32_t *d_length,
+                              int64_t capacity, int64_t *n_edges_out, void *stream) {
+  int rc;
+  if ((rc = lsh_cross_dev_check(d_index, index_bytes, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, mh_threshold, max_candidates)) != DA_OK)
+    return rc;
+  const NwlSeqs q{d_x_codes, d_x_offsets, m, d_y_codes, d_y_offsets, n};
+  if ((rc = lsh_nw_dev_check(q, matrix_id, threshold, d_work, d_i, d_j, d_matches, d_length, capacity, n_edges_out)) != DA_OK) return rc;
+  return lsh_nw_edges_device(LshSets{d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows}, q, mh_threshold, max_candidates, d_work, work_bytes,
+                             matrix_id, gap_open, gap_ext, threshold, d_i, d_j, d_matches, d_length, capacity, n_edges_out, static_cast<hipStream_t>(stream));
+}
+
+int da_similarity_nw_lsh_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                                     int rows, double mh_threshold, int64_t max_candidates, const char *matrix_name, int gap_open, int gap_ext,
+                                     double threshold, da_edges **handle_out, int64_t *n_edges_out) {
+  const int mid = da_matrix_id(matrix_name);               // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  int rc = validate_mh(n, k, n_hash);
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !handle_out || !n_edges_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  *handle_out = nullptr;
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, 0.0, max_candidates)) != DA_OK) return rc;   // the two thresholds come behind the NW checks
+  if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_host_lengths("", offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_threshold_check(threshold, mh_threshold)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf work, codes, bad;
+  const StreamDrain drain{nullptr};
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash, false)) != DA_OK || (rc = mh.signatures(k, 0, n_hash)) != DA_OK) return rc;
+  if ((rc = nwl_encode(mh.in, total, codes, bad)) != DA_OK) return rc;
+  const size_t wb = lsh_workspace_bytes(n, bands);
+  if ((rc = work.alloc(wb)) != DA_OK) return rc;
+  const NwlSeqs q{codes.as<uint8_t>(), mh.in.off.as<int64_t>(), n, codes.as<uint8_t>(), mh.in.off.as<int64_t>(), n};
+  return lsh_nw_edges_to_host(lsh_one_set(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows), q, mh_threshold, max_candidates, work.p, wb, mid, gap_open,
+                              gap_ext, threshold, handle_out, n_edges_out);
+}
+
+int da_similarity_nw_lsh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                           const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
+                                           double mh_threshold, int64_t max_candidates, const char *matrix_name, int gap_open, int gap_ext,
+                                           double threshold, da_edges **handle_out, int64_t *n_edges_out) {
+  const int mid = da_matrix_id(matrix_name);               // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  int rc;
+  int64_t x_total, y_total;
+  if ((rc = lsh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, handle_out, n_edges_out, bands, rows, 0.0,
+                                    max_candidates, nullptr, &x_total, &y_total)) != DA_OK) return rc;
+  *handle_out = nullptr;
+  if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_host_lengths(" of x", x_offsets, m)) != DA_OK || (rc = nwl_host_lengths(" of y", y_offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_threshold_check(threshold, mh_threshold)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  LshCrossHost h;
+  DevBuf x_codes, y_codes, x_bad, y_bad;
+  const StreamDrain drain{nullptr};
+  if ((rc = h.prepare(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, k, n_hash, seeds, bands, rows)) != DA_OK) return rc;
+  if ((rc = nwl_encode(h.x.in, x_total, x_codes, x_bad)) != DA_OK || (rc = nwl_encode(h.y.in, y_total, y_codes, y_bad)) != DA_OK) return rc;
+  const NwlSeqs q{x_codes.as<uint8_t>(), h.x.in.off.as<int64_t>(), m, y_codes.as<uint8_t>(), h.y.in.off.as<int64_t>(), n};
+  return lsh_nw_edges_to_host(h.sets(m, n, n_hash, bands, rows), q, mh_threshold, max_candidates, h.work.p, h.wb, mid, gap_open, gap_ext, threshold,
+                              handle_out, n_edges_out);
+}
+
+int da_nw_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *aligned_pairs_out, int64_t *short_pairs_out,
+                         int64_t *long_pairs_out, int64_t *edges_out) {
+  const NwLshRoute &r = nw_lsh_route();
+  if (buckets_out) *buckets_out = r.buckets;
+  if (incidences_out) *incidences_out = r.incidences;
+  if (verified_pairs_out) *verified_pairs_out = r.verified;
+  if (aligned_pairs_out) *aligned_pairs_out = r.aligned;
+  if (short_pairs_out) *short_pairs_out = r.shorts;
+  if (long_pairs_out) *long_pairs_out = r.longs;
+  if (edges_out) *edges_out = r.edges;
+  return DA_OK;
+}
+
 
 // ---- NW threshold form for sequences of up to 1024 residues: 32-bit keys (nw_edges_long_kernels.hip) ------------------------------------------
 // The value table of the PACK32 codes (matches << 16 | length) of sequences up to max_len residues: the distinct doubles

@@ -403,6 +403,27 @@ int launch_nw_align_long(const uint8_t *d_x_codes, const int64_t *d_x_off, int64
                          const int32_t *d_pair_x, const int32_t *d_pair_y, int64_t pair_base, int64_t pairs, int matrix_id, int gap_open, int gap_ext,
                          uint8_t *d_ops, int64_t ld_ops, int32_t *d_len, int32_t *d_matches, int32_t *d_score, int64_t max_len, void *d_work,
                          size_t work_bytes, hipStream_t stream);
+// nw_lsh_kernels.hip: NW (matches, length) of a resident pair list over two encoded sets, split on the device into the lane-per-pair and the
+// wavefront-per-pair kernels above (da_dev_nw_rescore_pairs); a refused pair -- an index outside its set, a length of 0 or over 1024 --
+// gets -1 / -1.  The workspace is nw_rescore_fixed_bytes(pairs) (lists, classes, scan; 256 spare bytes for any alignment) plus the
+// lane-per-pair kernel's decision words for the short pairs in flight: at least one wavefront of them (minimal), a smaller share means more
+// launches and never another result.  counts_host = {short, long, refused}.  Synchronises the stream once (the class totals are read back);
+// the alignment launches and the scatter behind it are asynchronous.
+size_t nw_rescore_fixed_bytes(int64_t pairs);
+size_t nw_rescore_workspace_bytes(int64_t pairs, bool minimal);
+int launch_nw_rescore(const uint8_t *d_x_codes, const int64_t *d_x_off, int64_t m, const uint8_t *d_y_codes, const int64_t *d_y_off, int64_t n,
+                      const int32_t *d_i, const int32_t *d_j, int64_t pairs, int matrix_id, int gap_open, int gap_ext, int32_t *d_matches,
+                      int32_t *d_length, void *d_work, size_t work_bytes, int64_t counts_host[3], hipStream_t stream);
+// ... and the threshold list of it (da_dev_lsh_nw_edges): the sorted 64-bit keys of the LSH back end unpacked, keep[p] = matches >=
+// min_matches[length] with the kept counts per chunk of 64 and their exclusive sum (chunks + 1 entries each; d_temp: nwl_keep_scan_bytes),
+// and the kept (i, j, matches, length) written in listed order, the first `capacity` of them
+int launch_nwl_split(const uint64_t *d_key, int64_t count, int32_t *d_i, int32_t *d_j, hipStream_t stream);
+size_t nwl_keep_scan_bytes(int64_t pairs);
+int launch_nwl_keep(const int32_t *d_matches, const int32_t *d_length, int64_t pairs, const int32_t *d_min_matches, int table_len, uint8_t *d_keep,
+                    int64_t *d_chunk_kept, int64_t *d_chunk_off, void *d_temp, size_t temp_bytes, hipStream_t stream);
+int launch_nwl_emit(const int32_t *d_i, const int32_t *d_j, const int32_t *d_matches, const int32_t *d_length, const uint8_t *d_keep,
+                    const int64_t *d_chunk_off, int64_t pairs, int64_t capacity, int32_t *d_out_i, int32_t *d_out_j, int32_t *d_out_matches,
+                    int32_t *d_out_length, hipStream_t stream);
 // consensus_kernels.hip: the center-star consensus of a pooled cluster table (da_dev_cluster_consensus and its pieces).  Pairs are numbered per
 // cluster i ascending then j != i ascending (d_pair_ptr: the running sums of c (c - 1), int64), rows (center, j != center) j ascending.
 // launch_cons_pairs lists entries [p0, p1) of the pairs (d_center == NULL) or of the rows; launch_cons_center_sums ADDS the fixed-point terms of

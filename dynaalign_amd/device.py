@@ -1307,6 +1307,98 @@ def mh_lsh_last_route():
     return route()
 
 
+def nw_rescore_workspace_bytes(pairs, max_len=1024, minimal=False):
+    return int(_capi.load().da_dev_nw_rescore_workspace_bytes(int(pairs), int(max_len), 1 if minimal else 0))
+
+
+def _matrix_id(lib, matrix_name):
+    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
+    if mid < 0:
+        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    return mid
+
+
+def nw_rescore_pairs(dx, dy, i, j, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, work=None):
+    """NW ``(matches, length)`` of a resident pair list (da_dev_nw_rescore_pairs): pair p aligns dx[i[p]] as sequence1 with dy[j[p]] as
+    sequence2; dx.codes / dy.codes must be filled (nw_encode; dx may be dy); i / j: int32 device tensors.  Sequences of 1 .. 1024 residues,
+    mixed freely: the split between the lane-per-pair and the wavefront-per-pair kernel happens on the device.  A pair with an index
+    outside its set, an empty sequence or one over 1024 residues gets -1 / -1.  -> (matches int32, length int32); the identity is
+    matches / length.  work: a uint8 device tensor of at least nw_rescore_workspace_bytes(pairs, minimal=True) bytes, any alignment
+    (allocated if None); a smaller one means more launches, never another result.  Synchronises the stream once on the way; the results
+    are ordered on the current stream like any other launch.  ``nw_lsh_last_route()`` has the short and long counts."""
+    lib = _capi.load()
+    if dx.codes is None or dy.codes is None:
+        raise ValueError("call nw_encode on both sets first")
+    mid = _matrix_id(lib, matrix_name)
+    _require_cuda(i, "i")
+    _require_cuda(j, "j")
+    if i.dtype != torch.int32 or j.dtype != torch.int32 or i.numel() != j.numel():
+        raise ValueError("i and j must be int32 tensors of the same length")
+    i, j = i.contiguous(), j.contiguous()
+    pairs = i.numel()
+    dev = dx.residues.device
+    mt = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
+    ln = torch.empty_like(mt)
+    if work is None:
+        work = torch.empty(max(nw_rescore_workspace_bytes(pairs), 16), dtype=torch.uint8, device=dev)
+    _require_cuda(work, "work")
+    if work.dtype != torch.uint8 or work.dim() != 1 or work.stride(0) != 1:
+        raise ValueError("work must be a 1-d uint8 tensor with unit stride")
+    _call(lib.da_dev_nw_rescore_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n, i.data_ptr(),
+          j.data_ptr(), pairs, mid, int(gap_open), int(gap_ext), mt.data_ptr(), ln.data_ptr(), work.data_ptr(), work.numel(), _stream())
+    return mt[:pairs], ln[:pairs]
+
+
+def lsh_nw_edges(sig, ds, n_hash, bands, rows, threshold, mh_threshold=0.0, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, max_candidates=1 << 32,
+                 capacity=None, work=None, index=None, sig_y=None, dy=None):
+    """The NW identity on LSH candidates, resident signatures and resident encoded sequences in, a resident list out (da_dev_lsh_nw_edges):
+    ``sig`` the signatures of ``ds`` (ds.codes filled by nw_encode) -> (i int32, j int32, matches int32, length int32), sorted by (i, j):
+    the candidates of ``lsh_edges(sig, ..., mh_threshold)``, the diagonal included, whose ``matches / length >= threshold`` and > 0.  Two
+    sets (da_dev_lsh_cross_nw_edges): pass ``index = lsh_index_build(sig_y, n_hash, bands, rows)``, ``sig_y`` and ``dy``; ``sig`` / ``ds``
+    are then the queries x, and there is no diagonal.  ``capacity=None``: a first call counts, a second one fills; an int: one call, and at
+    most that many edges are returned (``nw_lsh_last_route()["edges"]`` has the full number).  Synchronises the stream."""
+    lib = _capi.load()
+    cross = index is not None
+    if cross and (sig_y is None or dy is None):
+        raise ValueError("the two-set form needs index, sig_y and dy")
+    if ds.codes is None or (cross and dy.codes is None):
+        raise ValueError("call nw_encode on the sequences first")
+    mid = _matrix_id(lib, matrix_name)
+    dev = sig.device
+    if cross:
+        m, ld_x, n, ld_y, work = _lsh_cross_operands(index, sig, sig_y, n_hash, bands, work)
+    else:
+        n, ld = _sig_block(sig, n_hash)
+        if work is None:
+            work = torch.empty(lsh_workspace_bytes(n, bands), dtype=torch.uint8, device=dev)
+        _byte_buffer(work, "work", "lsh_workspace_bytes(n, bands)")
+    got = ctypes.c_int64(0)
+
+    def run(cap, ti, tj, tm, tl):
+        if cross:
+            _call(lib.da_dev_lsh_cross_nw_edges, index.data_ptr(), index.numel(), sig.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash),
+                  int(bands), int(rows), float(mh_threshold), int(max_candidates), ds.codes.data_ptr(), ds.offsets.data_ptr(), dy.codes.data_ptr(),
+                  dy.offsets.data_ptr(), mid, int(gap_open), int(gap_ext), float(threshold), work.data_ptr(), work.numel(), ti, tj, tm, tl, cap,
+                  ctypes.byref(got), _stream())
+        else:
+            _call(lib.da_dev_lsh_nw_edges, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(mh_threshold), int(max_candidates),
+                  ds.codes.data_ptr(), ds.offsets.data_ptr(), mid, int(gap_open), int(gap_ext), float(threshold), work.data_ptr(), work.numel(),
+                  ti, tj, tm, tl, cap, ctypes.byref(got), _stream())
+    if capacity is None:
+        run(0, None, None, None, None)
+        capacity = got.value
+    capacity = int(capacity)
+    out = [torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+    run(capacity, *[t.data_ptr() for t in out])
+    stored = min(got.value, capacity)
+    return tuple(t[:stored] for t in out)
+
+
+def nw_lsh_last_route():
+    from .similarity import nw_lsh_last_route as route
+    return route()
+
+
 def mh_cross_last_route():
     """what this thread's last similarity_mh_cross call did: dict(m, n, unique_x, unique_y, dedup, plane_bits, plan_ms, codes_ms,
     k2_ms, lists_ms, expand_ms)"""

@@ -1120,6 +1120,75 @@ def lsh_collision_probability(s, bands, rows):
     return float(p) if p.ndim == 0 else p
 
 
+def similarityNW_lsh_edges(sequences, k=4, n_hash=50, bands=10, rows=5, threshold=0.5, *, mh_threshold=0.0, matrixName="BLOSUM62", gapOpen=10,
+                           gapExt=4, seed=None, max_candidates=1 << 32):
+    """The alignment-identity graph of one set at LSH cost: MinHash LSH chooses the pairs, Needleman-Wunsch scores them.
+    ``(threshold, i, j, weight)``, 0-based, sorted by (i, j), the contract ``clusterbreak(edges_fn=)`` takes.  The candidates are the
+    entries of ``similarityMH_lsh_edges(sequences, k, n_hash, bands, rows, mh_threshold, seed=seed)`` -- every (i, i) and every i < j that
+    share a bucket and have ``c / n_hash >= mh_threshold``; each one, the diagonal included, is aligned (sequences[i] as sequence1) and kept
+    when ``w = matches / length`` has ``w >= threshold and w > 0``.  The result is exactly ``nw_lsh_edges_dense`` of the signatures and the
+    reference's pair value, weights bit for bit; approximate is only its relation to the all-pairs graph
+    ``similarityNW_cross_edges_long(x, x, threshold=threshold)``: a pair that shares no bucket is missing.  Sequences of 1 .. 1024 residues,
+    mixed freely; pass distinct strings.  Nothing returns to the host between bucketing and the final list.  Errors: the matrix name, then
+    those of similarityMH_lsh_edges, then invalid residues, an empty sequence, one over 1024 residues, then the two thresholds."""
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
+    bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
+    _thr, ei, ej, ew = _edges_one_pass(lambda h, _t, cnt: lib.da_similarity_nw_lsh_edges_begin(
+        res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, bands, rows, float(mh_threshold), int(max_candidates), name, go, ge,
+        float(threshold), h, cnt))
+    return float(threshold), ei, ej, ew
+
+
+def similarityNW_lsh_cross_edges(x, y, k=4, n_hash=50, bands=10, rows=5, threshold=0.5, *, mh_threshold=0.0, matrixName="BLOSUM62", gapOpen=10,
+                                 gapExt=4, seed=None, max_candidates=1 << 32):
+    """The two-set form of ``similarityNW_lsh_edges``: the candidates of ``similarityMH_lsh_cross_edges(x, y, ..., mh_threshold)``, each
+    aligned with x[i] as sequence1 and y[j] as sequence2, kept when ``w >= threshold and w > 0``.  No diagonal.  Exactly
+    ``nw_lsh_cross_edges_dense`` of the two signature matrices and the reference's pair value."""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    n = len(yo) - 1
+    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
+    bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
+    _thr, ei, ej, ew = _edges_one_pass(lambda h, _t, cnt: lib.da_similarity_nw_lsh_cross_edges_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data, bands, rows, float(mh_threshold),
+        int(max_candidates), name, go, ge, float(threshold), h, cnt))
+    return float(threshold), ei, ej, ew
+
+
+def nw_lsh_last_route():
+    """What this thread's last NW-on-LSH call did: buckets, (pair, band) incidences, distinct verified pairs, aligned pairs (the candidates,
+    diagonal included), how many of them took the lane-per-pair (short) and the wavefront-per-pair (long) kernel, and edges."""
+    v = np.zeros(7, np.int64)
+    _capi.check(_capi.load().da_nw_lsh_last_route(*[v[i:].ctypes.data for i in range(7)]))
+    return dict(zip(("buckets", "incidences", "verified_pairs", "aligned_pairs", "short_pairs", "long_pairs", "edges"), (int(x) for x in v)))
+
+
+def _nw_threshold_keep(ci, cj, nw_value, threshold):
+    w = np.array([nw_value(int(a), int(b)) for a, b in zip(ci, cj)], np.float64).reshape(-1)
+    keep = (w >= float(threshold)) & (w > 0)
+    return ci[keep], cj[keep], w[keep]
+
+
+def nw_lsh_edges_dense(sig, bands, rows, mh_threshold, nw_value, threshold):
+    """The definition ``similarityNW_lsh_edges`` is exact against (host code, beside ``lsh_edges_dense``): the candidates are exactly the
+    pairs ``lsh_edges_dense(sig, bands, rows, mh_threshold)`` returns -- every (i, i), and every i < j that agree in a whole band and have
+    ``c / n_hash >= mh_threshold``; ``nw_value(i, j)`` is the double ``matches / length`` of x[i] as sequence1 against x[j] as sequence2; a
+    candidate is an edge when ``w = nw_value(i, j)`` has ``w >= threshold and w > 0``.  The diagonal is scored like every other pair.
+    -> ``(i, j, w)`` sorted by (i, j)."""
+    ci, cj, _ = lsh_edges_dense(sig, bands, rows, mh_threshold)
+    return _nw_threshold_keep(ci, cj, nw_value, threshold)
+
+
+def nw_lsh_cross_edges_dense(sig_x, sig_y, bands, rows, mh_threshold, nw_value, threshold):
+    """The two-set twin of ``nw_lsh_edges_dense``: the candidates of ``lsh_cross_edges_dense(sig_x, sig_y, bands, rows, mh_threshold)``, no
+    diagonal; ``nw_value(i, j)`` is x[i] as sequence1 against y[j] as sequence2."""
+    ci, cj, _ = lsh_cross_edges_dense(sig_x, sig_y, bands, rows, mh_threshold)
+    return _nw_threshold_keep(ci, cj, nw_value, threshold)
+
+
 def similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, *, threshold=None):
     """The entries of R = similarityNW_cross(x, y, ...) (x[i] is sequence1) that pass a threshold: ``(threshold, i, j, weight)`` as
     similarityMH_cross_edges.  Equal similarities pass or fail together whatever their (matches, length): 2/4 and 3/6 are both 0.5.

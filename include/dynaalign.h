@@ -62,6 +62,8 @@ extern "C" {
  *  da_dev_lsh_cross_[verify_pairs | workspace_bytes | edges | topk] -- likewise)
  * (the connected-components entry points -- da_components, da_dev_components_[workspace_bytes | edges | csr], da_dev_lsh_components,
  *  da_similarity_mh_lsh_components -- likewise)
+ * (the NW-on-LSH-candidates entry points -- da_similarity_nw_lsh_[cross_]edges_begin, da_dev_lsh_[cross_]nw_edges,
+ *  da_dev_nw_rescore_pairs, da_dev_nw_rescore_workspace_bytes, da_nw_lsh_last_route -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1322,6 +1324,73 @@ int da_similarity_mh_lsh_cross_edges_begin(const uint8_t *x_residues, const int6
 int da_similarity_mh_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
                                     const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
                                     double threshold, int top, int64_t max_candidates, int32_t *idx_out, double *val_out);
+
+/* ---- NW identity on MinHash LSH candidates: the LSH filter above, the survivors scored by alignment -------------------------------------
+ * The candidates are the entries of the LSH edge list at mh_threshold -- one set: every (i, i) and every i < j with cand(i, j) and
+ * (double)c / (double)n_hash >= mh_threshold; two sets: every (i, j) with cand(i, j) and that count.  Every candidate, the diagonal
+ * included, is aligned: x[i] as sequence1 against x[j] (two sets: y[j]) as sequence2, w = (double)matches / (double)length of the
+ * reference's traceback (src/pairwiseSeqAlign.cpp:284-311).  The edge set, sorted by (i, j), 0-based:
+ *     (i, j, w) for every candidate with w >= threshold and w > 0        (the rule of da_similarity_nw_cross_edges_begin)
+ * -- EXACT with respect to this definition, weights bit for bit; the diagonal is not assumed to be 1.0 (with gap_open = gap_ext = 0 a
+ * sequence of X against itself has w = 0.0 and no edge).  Approximate is only the definition's relation to the all-pairs NW threshold
+ * graph: a pair that shares no bucket is missing.  Sequences of 1 .. 1024 residues, mixed freely: on the device every pair whose two
+ * sequences have at most 127 residues takes a lane of the lane-per-pair kernel, every other one a wavefront.
+ *
+ * da_dev_nw_rescore_pairs: the reusable piece -- (matches, length) of ANY resident pair list over two encoded sets (da_dev_nw_encode; the
+ *   same buffers twice for one set): pair p is x[d_i[p]] as sequence1 against y[d_j[p]] as sequence2, d_matches[p] / d_length[p] int32.  A
+ *   pair with an index outside its set, a sequence of 0 residues or of more than 1024 gets -1 / -1.  The split by length happens on the
+ *   device (classify, one exclusive sum, a stable partition; the alignment kernels are those of da_dev_nw_align_pairs and
+ *   da_dev_nw_align_long_pairs without ops).  d_work: da_dev_nw_rescore_workspace_bytes(pairs, max_len, minimal) bytes, any alignment;
+ *   minimal != 0 gives the smallest workspace the call takes, 0 the one that keeps up to 2^18 short pairs in flight, anything between
+ *   works: a smaller workspace means more launches, never another result.  max_len is accepted for callers that know it and does not
+ *   change the size today (the wavefront kernel stores nothing without ops).  0 for pairs <= 0; grows with pairs.
+ *   SYNCHRONISES the stream once, between the partition and the alignments (the two class totals and the longest long sequence are
+ *   read back); the alignments and the scatter into d_matches / d_length are asynchronous on `stream`.  pairs <= 2^31 - 16.
+ * da_dev_lsh_nw_edges / da_dev_lsh_cross_nw_edges: the one-call device route on resident signatures and resident encoded sequences
+ *   (d_codes / d_offsets of the set the signatures were made of): da_dev_lsh_edges / da_dev_lsh_cross_edges at mh_threshold, the sorted
+ *   list unpacked, the rescore, the verdicts and the compaction -- nothing returns to the host in between but a few totals.  The verdict
+ *   compares integers: matches >= min_matches[length], a table of 2049 int32 the host builds with the divide it uses for the weights,
+ *   so 2/4 and 3/6 pass or fail together.  d_work / work_bytes: those of da_dev_lsh_edges / da_dev_lsh_cross_edges (the per-candidate
+ *   buffers and the rescore workspace are sized by the data and allocated inside, the latter within DYNAALIGN_BLOCK_BYTES).  Checks:
+ *   those of da_dev_lsh_edges / da_dev_lsh_cross_edges with mh_threshold as the threshold, then NULL sequence pointers, the matrix id,
+ *   threshold outside [0, 1] or NaN, the outputs.  *n_edges_out = the number of edges; the first min(capacity, that) of them go to d_i /
+ *   d_j / d_matches / d_length (int32; weight = (double)matches / (double)length), which may be NULL when capacity is 0.  A candidate
+ *   whose pair the kernels refuse (an empty sequence, one over 1024 residues) makes the call fail with DA_ERR_UNSUPPORTED.
+ *   Synchronises the stream.
+ * da_similarity_nw_lsh_edges_begin / da_similarity_nw_lsh_cross_edges_begin: host boundary; the result in a da_edges handle
+ *   (da_edges_fetch / da_edges_free), weights (double)matches / (double)length divided on the host.  Checks, in this order and before
+ *   any device is needed: the matrix name (DA_ERR_BAD_MATRIX), as every NW entry does; then the checks of
+ *   da_similarity_mh_lsh_edges_begin / da_similarity_mh_lsh_cross_edges_begin in their order and with their texts, the threshold left
+ *   out -- empty input, k, n_hash, NULL pointers, offsets, bands, rows, bands * rows, max_candidates, n_hash > 65535; then the NW
+ *   checks: invalid residues (DA_ERR_BAD_RESIDUE_SEQ1 / _SEQ2, the order of da_similarity_nw / da_similarity_nw_cross), an empty
+ *   sequence (DA_ERR_UNSUPPORTED), a sequence over 1024 residues (DA_ERR_UNSUPPORTED); then threshold, then mh_threshold, outside
+ *   [0, 1] or NaN (DA_ERR_BAD_ARG); DA_ERR_NO_DEVICE last.  max_candidates as for the MinHash calls, with their text.
+ * da_nw_lsh_last_route: what the calling thread's last call of this family did -- buckets, (pair, band) incidences, distinct verified
+ *   pairs, aligned pairs (the candidates, diagonal included), how many of them were short and long, and edges.  After
+ *   da_dev_nw_rescore_pairs only the aligned, short and long counts are set.  NULL pointers are skipped. */
+size_t da_dev_nw_rescore_workspace_bytes(int64_t pairs, int64_t max_len, int minimal);
+int da_dev_nw_rescore_pairs(const uint8_t *d_x_codes, const int64_t *d_x_offsets, int64_t m, const uint8_t *d_y_codes,
+                            const int64_t *d_y_offsets, int64_t n, const int32_t *d_i, const int32_t *d_j, int64_t pairs, int matrix_id,
+                            int gap_open, int gap_ext, int32_t *d_matches, int32_t *d_length, void *d_work, size_t work_bytes, void *stream);
+int da_dev_lsh_nw_edges(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double mh_threshold,
+                        int64_t max_candidates, const uint8_t *d_codes, const int64_t *d_offsets, int matrix_id, int gap_open, int gap_ext,
+                        double threshold, void *d_work, size_t work_bytes, int32_t *d_i, int32_t *d_j, int32_t *d_matches,
+                        int32_t *d_length, int64_t capacity, int64_t *n_edges_out, void *stream);
+int da_dev_lsh_cross_nw_edges(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x,
+                              const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands, int rows, double mh_threshold,
+                              int64_t max_candidates, const uint8_t *d_x_codes, const int64_t *d_x_offsets, const uint8_t *d_y_codes,
+                              const int64_t *d_y_offsets, int matrix_id, int gap_open, int gap_ext, double threshold, void *d_work,
+                              size_t work_bytes, int32_t *d_i, int32_t *d_j, int32_t *d_matches, int32_t *d_length, int64_t capacity,
+                              int64_t *n_edges_out, void *stream);
+int da_similarity_nw_lsh_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds,
+                                     int bands, int rows, double mh_threshold, int64_t max_candidates, const char *matrix_name,
+                                     int gap_open, int gap_ext, double threshold, da_edges **handle_out, int64_t *n_edges_out);
+int da_similarity_nw_lsh_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                           const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                                           int rows, double mh_threshold, int64_t max_candidates, const char *matrix_name, int gap_open,
+                                           int gap_ext, double threshold, da_edges **handle_out, int64_t *n_edges_out);
+int da_nw_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *aligned_pairs_out,
+                         int64_t *short_pairs_out, int64_t *long_pairs_out, int64_t *edges_out);
 
 /* name -> id for da_dev_nw; -1 + DA_ERR_BAD_MATRIX message when unknown. */
 int da_matrix_id(const char *matrix_name);
