@@ -20,190 +20,44 @@ DA_OUT_F64, DA_OUT_COMPACT, DA_OUT_PACK32 = 0, 1, 2
 DA_KNN_UNION, DA_KNN_MUTUAL = 0, 1   # da_dev_knn_edges: which pairs of the nearest-neighbour lists become edges
 DA_TOPK_MAX = 1024   # da_dev_topk_rows: the candidates of a row are sorted in a fixed LDS buffer
 
-_vp, _i64, _i32, _u32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_uint32, C.c_size_t
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "size_t": C.c_size_t, "double": C.c_double}
 
-# name -> (restype, argtypes).  Must list every symbol include/dynaalign.h declares
-# (tests/test_abi.py checks the two against each other).
-SIGNATURES = {
-    "da_last_error": (C.c_char_p, []),
-    "da_status_message": (C.c_char_p, [_i32]),
-    "da_abi_version": (_i32, []),
-    "da_device_count": (_i32, []),
-    "da_release_device_memory": (_sz, []),
-    "da_config_reload": (None, []),
-    "da_debug_comm_cache_state": (C.c_int, [C.c_int, C.c_void_p]),
-    "da_hash_family_seeds": (_i32, [_u32, _i32, _vp]),
-    "da_random_seed": (_u32, []),
-    "da_similarity_mh": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i32]),
-    "da_similarity_nw_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i32]),
-    "da_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
-    "da_similarity_nw_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp]),
-    "da_nw_code_ranks": (_i32, [_i32, _vp, _vp]),
-    "da_similarity_jaccard": (_i32, [_vp, _vp, _i64, _i32, _vp]),
-    "da_similarity_jaccard_cross": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32]),
-    "da_similarity_jaccard_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_similarity_jaccard_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_similarity_jaccard_edges": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "da_similarity_jaccard_edges_begin": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _vp]),
-    "da_dev_jaccard_sets_ld": (_i64, [_i64, _i32]),
-    "da_dev_jaccard_sets": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
-    "da_dev_jaccard_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
-    "da_similarity_jaccard_long": (_i32, [_vp, _vp, _i64, _i32, _vp]),
-    "da_similarity_jaccard_cross_long": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _i32]),
-    "da_similarity_jaccard_cross_topk_long": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_similarity_jaccard_knn_long": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_similarity_jaccard_edges_long_begin": (_i32, [_vp, _vp, _i64, _i32, C.c_double, _vp, _vp, _vp]),
-    "da_similarity_jaccard_cross_edges_long_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, C.c_double, _i32, _vp, _vp, _vp]),
-    "da_similarity_jaccard_stats_long": (_i32, [_vp, _vp, _i64, _i32, _vp]),
-    "da_jaccard_sets_long_ld": (_i64, [_i64, _i32]),
-    "da_dev_jaccard_sets_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
-    "da_dev_jaccard_rect_long": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
-    "da_nw_align_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
-    "da_nw_align_workspace_bytes": (_sz, [_i64]),
-    "da_dev_nw_align_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "da_nw_align_long_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
-    "da_nw_align_long_workspace_bytes": (_sz, [_i64, _i64]),
-    "da_dev_nw_align_long_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _sz,
-                                          _vp]),
-    "da_cluster_consensus": (_i32, [_vp, _vp, _i64, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _i64, _vp, _vp]),
-    "da_dev_cluster_consensus_workspace_bytes": (_sz, [_vp, _i64, _i64, _i32]),
-    "da_dev_cluster_consensus": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
-    "da_dev_consensus_center_sums": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "da_dev_consensus_pick": (_i32, [_vp, _vp, _i64, _vp, _vp]),
-    "da_dev_consensus_vote": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
-    "da_similarity_mh_opts": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
-    "da_similarity_nw_opts": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp, _vp]),
-    "da_rccl_available": (_i32, []),
-    "da_minhash_signatures": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_mh_counts": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i64, _vp]),
-    "da_similarity_nw": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
-    "da_nw_pairs": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _i64, _i64, _vp, _vp, _vp]),
-    "da_sig_ld": (_i64, [_i32]),
-    "da_dev_minhash_signatures": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "da_mh_planes_words": (_i64, [_i64, _i32]),
-    "da_mh_planes_workspace_bytes": (_sz, [_i64, _i32]),
-    "da_dev_mh_planes": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _i64, _vp, _vp]),
-    "da_dev_mh_compare": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_mh_compare_rect": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
-    "da_dev_similarity_mh_cross": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "da_mh_cross_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "da_dev_topk_rows": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "da_dev_topk_rows_self": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "da_similarity_mh_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp]),
-    "da_similarity_nw_knn": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "da_dev_similarity_mh_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
-    "da_dev_knn_edges_bytes": (_sz, [_i64, _i32]),
-    "da_dev_knn_edges": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "da_dev_similarity_mh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp]),
-    "da_similarity_mh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _i32, _vp, _vp, _vp]),
-    "da_similarity_nw_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp]),
-    "da_dev_rect_histogram": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp]),
-    "da_dev_threshold_rows_workspace_bytes": (_sz, [_i64]),
-    "da_dev_threshold_rows_count": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _sz, _vp]),
-    "da_dev_threshold_rows_emit": (_i32, [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
-    "da_dev_similarity_mh_cross_edges": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
-                                                _vp]),
-    "da_similarity_nw_edges_long_begin": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _vp, _vp, _vp]),
-    "da_similarity_nw_cross_edges_long_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp]),
-    "da_nw_value_ranks": (_i32, [_i32, _vp, _vp, _vp]),
-    "da_dev_nw_codes_to_ranks": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
-    "da_dev_rank_histogram": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _i32, _i64, _i64, _vp]),
-    "da_dev_threshold_ranks_count": (_i32, [_vp, _i64, _i64, _i64, _u32, _i64, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
-    "da_dev_threshold_ranks_emit": (_i32, [_vp, _i64, _i64, _i64, _u32, _i64, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
-    "da_stats_from_histogram": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "da_similarity_mh_stats": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
-    "da_similarity_nw_stats": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
-    "da_dev_topk_ranks": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp]),
-    "da_dev_topk_ranks_self": (_i32, [_vp, _i64, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
-    "da_similarity_nw_knn_long": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "da_similarity_nw_cross_topk_long": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, C.c_char_p, _i32, _i32, _i32, _vp, _vp]),
-    "da_similarity_nw_stats_long": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, _vp]),
-    "da_dev_upper_extrema": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
-    "da_dev_upper_extrema32": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "da_dev_nw_rect": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
-    "da_nw_last_route": (_i32, [_vp, _vp, _vp, _vp]),
-    "da_dev_similarity_mh": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "da_mh_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp]),
-    "da_mh_last_route_chunks": (_i32, [_vp, _vp]),
-    "da_mh_last_route_split": (_i32, [_vp, _vp]),
-    "da_dev_unique_plan_bytes": (_sz, [_i64, _i64]),
-    "da_dev_unique_plan": (_i32, [_vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp]),
-    "da_dev_shards_to_table": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_nw_unique_rows": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_expand_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
-    "da_dev_unique_rows_bytes": (_sz, [_i64, _i64]),
-    "da_dev_unique_rows": (_i32, [_vp, _i64, _vp, _vp, _vp]),
-    "da_dev_upper_histogram_rows": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp]),
-    "da_dev_extract_edges_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "da_dev_expand_unique": (_i32, [_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _i64, _vp]),
-    "da_dev_nw_encode": (_i32, [_vp, _i64, _vp, _vp, _vp]),
-    "da_dev_nw": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp]),
-    "da_similarity_mh_edges": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "da_similarity_nw_edges": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "da_similarity_mh_edges_begin": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp]),
-    "da_similarity_nw_edges_begin": (_i32, [_vp, _vp, _i64, C.c_char_p, _i32, _i32, C.c_double, _vp, _vp, _vp]),
-    "da_edges_fetch": (_i32, [_vp, _i64, _vp, _vp, _vp]),
-    "da_edges_free": (None, [_vp]),
-    "da_quantile_type7": (_i32, [_vp, _vp, _i32, C.c_double, _vp]),
-    "da_dev_upper_histogram": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp]),
-    "da_dev_extract_edges": (_i32, [_vp, _i64, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "da_dev_shard_histogram": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
-    "da_dev_shard_extract_edges": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "da_louvain": (_i32, [_i64, _i64, _vp, _vp, _vp, C.c_double, _u32, _vp, _vp, _vp]),
-    "da_louvain_csr": (_i32, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _u32, _vp, _vp, _vp]),
-    "da_dev_edges_to_csr_bytes": (_sz, [_i64, _i64]),
-    "da_dev_edges_to_csr": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "da_dev_louvain_workspace_bytes": (_sz, [_i64, _i64]),
-    "da_dev_louvain_csr": (_i32, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _u32, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "da_components": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp]),
-    "da_dev_components_workspace_bytes": (_sz, [_i64]),
-    "da_dev_components_edges": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "da_dev_components_csr": (_i32, [_i64, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "da_dev_lsh_components": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _sz, _vp, _vp, _vp, _vp]),
-    "da_similarity_mh_lsh_components": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, _vp, _vp]),
-    "da_similarity_mh_lsh_edges_begin": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, _vp, _vp]),
-    "da_mh_lsh_last_route": (_i32, [_vp, _vp, _vp, _vp]),
-    "da_dev_lsh_workspace_bytes": (_sz, [_i64, _i32]),
-    "da_dev_lsh_band_keys": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "da_dev_lsh_verify_pairs": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "da_dev_lsh_edges": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "da_similarity_mh_lsh_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i32, _i64, _vp, _vp]),
-    "da_dev_lsh_knn": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
-    "da_dev_lsh_knn_select": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
-    "da_dev_lsh_index_bytes": (_sz, [_i64, _i32]),
-    "da_dev_lsh_index_build": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "da_dev_lsh_index_probe": (_i32, [_vp, _sz, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "da_dev_lsh_cross_verify_pairs": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    "da_dev_lsh_cross_workspace_bytes": (_sz, [_i64, _i32]),
-    "da_dev_lsh_cross_edges": (_i32, [_vp, _sz, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp,
-                                      _vp]),
-    "da_dev_lsh_cross_topk": (_i32, [_vp, _sz, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i32, _i64, _vp, _sz, _vp, _vp, _vp]),
-    "da_similarity_mh_lsh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, _vp, _vp]),
-    "da_similarity_mh_lsh_cross_topk": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i32, _i64, _vp, _vp]),
-    "da_dev_nw_rescore_workspace_bytes": (_sz, [_i64, _i64, _i32]),
-    "da_dev_nw_rescore_pairs": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "da_dev_lsh_nw_edges": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _sz, _vp, _vp,
-                                   _vp, _vp, _i64, _vp, _vp]),
-    "da_dev_lsh_cross_nw_edges": (_i32, [_vp, _sz, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, C.c_double, _i64, _vp, _vp, _vp, _vp, _i32,
-                                         _i32, _i32, C.c_double, _vp, _sz, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "da_similarity_nw_lsh_edges_begin": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, C.c_char_p, _i32, _i32, C.c_double,
-                                                _vp, _vp]),
-    "da_similarity_nw_lsh_cross_edges_begin": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.c_double, _i64, C.c_char_p,
-                                                      _i32, _i32, C.c_double, _vp, _vp]),
-    "da_nw_lsh_last_route": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "da_matrix_id": (_i32, [C.c_char_p]),
-    "da_shard_rows": (_i64, [_i64, _i32, _i32]),
-    "da_shard_ld": (_i64, [_i64, _i32, _i32]),
-    "da_shard_packed_bytes": (_i64, [_i64, _i32, _i32]),
-    "da_dev_pack_shard": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
-    "da_dev_finalize_shards_packed": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_mh_compare_shard": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_nw_shard": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_finalize_shards": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "da_dev_symmetrize": (_i32, [_vp, _i64, _i64, _i32, _vp]),
-    "da_dev_widen": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp]),
-}
+
+def _ctype(text, name, ret=False):
+    """the ctypes type of one parameter (its name, if any, still attached) or return type as the header spells it"""
+    words = [w for w in text.replace("*", " * ").split() if w not in ("const", "struct", "extern", "DA_API")]
+    if "*" in words:
+        return C.c_char_p if words[:2] == ["char", "*"] and words.count("*") == 1 else C.c_void_p
+    if not ret and len(words) > 1 and re.fullmatch(r"[A-Za-z_]\w*", words[-1]):
+        words = words[:-1]
+    if ret and words == ["void"]:
+        return None
+    if len(words) != 1 or words[0] not in _SCALARS:
+        raise ValueError("%s: no ctypes type for %r in include/dynaalign.h" % (name, " ".join(text.split())))
+    return _SCALARS[words[0]]
+
+
+def header_prototypes(path=HEADER_PATH, text=None):
+    """name -> (restype, argtypes) of every ``ret da_name(args);`` include/dynaalign.h declares (``text``: header text in place of the
+    file).  A pointer is a void *, except char *; the scalars are those of _SCALARS.  Anything else -- another scalar type, a
+    function-pointer or array parameter, a da_ name that is followed by a parenthesis but is no declaration this reader understands --
+    raises with the function's name: there is no default type."""
+    txt = open(path).read() if text is None else text
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*", " ", txt, flags=re.S)
+    txt = re.sub(r"^[ \t]*#.*$", " ", txt, flags=re.M)
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s*]*?)\b(da_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        out[name] = (_ctype(ret, name, ret=True), [_ctype(a, name) for a in args])
+    for m in re.finditer(r"\b(da_[a-z0-9_]+)\s*\(", txt):
+        if m.group(1) not in out:
+            raise ValueError("%s: no declaration this reader understands at %r" % (m.group(1), " ".join(txt[m.start():m.start() + 120].split())))
+    return out
+
+
+# name -> (restype, argtypes) of every function include/dynaalign.h declares, read from the header itself when this module is imported:
+# a new entry point needs its declaration there and nothing here.  load() applies whatever this dict holds when it runs.
+SIGNATURES = header_prototypes()
 
 DA_EXCHANGE = {"rows": 0, "allgather": 1, "peercopy": 2}
 DA_PHASES = ("setup", "compute", "exchange", "finalize", "d2h", "total")

@@ -786,7 +786,7 @@ def clusterconsensus_device(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4, 
 
     ``return_centers=True``: returns ``(consensus_list, centers)``, ``centers[t]`` the index into the rows of the center of the t-th
     cluster (of its only member for a cluster of one)."""
-    from .similarity import _as_int, pack_sequences
+    from .similarity import _as_int, _matrix_name, pack_sequences
     rows = df["clustered_seq"] if isinstance(df, dict) else df
     order, members, where = [], {}, {}
     for at, row in enumerate(rows):
@@ -814,7 +814,7 @@ def clusterconsensus_device(df, *, matrixName="BLOSUM62", gapOpen=10, gapExt=4, 
         out = np.zeros((len(pooled), ld), np.uint8)
         out_len = np.zeros(len(pooled), np.int32)
         out_center = np.zeros(len(pooled), np.int32)
-        name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+        name = _matrix_name(matrixName)
         _capi.check(lib.da_cluster_consensus(res.ctypes.data, off.ctypes.data, len(pool), cl.ctypes.data, len(pooled), name,
                                              _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), out.ctypes.data, ld, out_len.ctypes.data,
                                              out_center.ctypes.data))

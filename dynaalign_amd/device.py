@@ -34,6 +34,65 @@ def _require_cuda(t, name):
         raise _capi.DynaAlignError(_capi.DA_ERR_NO_DEVICE, "%s must live in HBM (dynaalign_amd has no CPU path)" % name)
 
 
+def _seeds_tensor(seeds, device):
+    """the hash seeds as the library takes them, uint32 words in an int32 device tensor: a tensor as it is, anything else through numpy"""
+    if torch.is_tensor(seeds):
+        return seeds
+    return torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(device)
+
+
+def _matrix_id(lib, matrix_name):
+    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
+    if mid < 0:
+        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    return mid
+
+
+_WORK_TEXT = "work must be a contiguous uint8 tensor of %s bytes"
+
+
+def _work(work, nbytes, device, error=None, flat=False, at_least=0):
+    """The workspace of a call: the caller's tensor, or a new one of ``nbytes`` bytes (a number, or a function asked only then) when
+    there is none.  ``error``, the exception to raise, makes it checked: in HBM, uint8, contiguous (``flat``: of one dimension with unit
+    stride, whatever its address or length) and of at least ``at_least`` bytes.  Without it the tensor is taken as it is."""
+    if work is None:
+        work = torch.empty(nbytes() if callable(nbytes) else nbytes, dtype=torch.uint8, device=device)
+    if error is not None:
+        _require_cuda(work, "work")
+        laid_out = (work.dim() == 1 and work.stride(0) == 1) if flat else work.is_contiguous()
+        if work.dtype != torch.uint8 or not laid_out or int(work.numel()) < at_least:
+            raise error
+    return work
+
+
+def _top(top):
+    """the columns of a top-k result: `top`, at least one slot and at most the DA_TOPK_MAX the kernels select"""
+    return max(min(int(top), _capi.DA_TOPK_MAX), 1)
+
+
+def _topk_out(rows, top, key_dtype, device):
+    """(idx int32, key or val of key_dtype), both (max(rows, 1), _top(top)) and unwritten"""
+    shape = (max(rows, 1), _top(top))
+    return torch.empty(shape, dtype=torch.int32, device=device), torch.empty(shape, dtype=key_dtype, device=device)
+
+
+def _edge_slots(capacity, device, dtypes):
+    """one unwritten tensor of max(capacity, 1) slots per dtype: the columns of an edge or entry list"""
+    return tuple(torch.empty(max(capacity, 1), dtype=dt, device=device) for dt in dtypes)
+
+
+def _count_then_fill(run, capacity, device, dtypes):
+    """The capacity protocol of the LSH list calls.  ``run(cap, *pointers)`` makes the library call and returns the full number of
+    entries.  capacity=None: a first call with capacity 0 and NULL columns counts, a second one fills; an int: the one call stores at
+    most that many.  Returns the columns cut to what was stored."""
+    if capacity is None:
+        capacity = run(0, *[None] * len(dtypes))
+    capacity = int(capacity)
+    out = _edge_slots(capacity, device, dtypes)
+    stored = min(run(capacity, *[t.data_ptr() for t in out]), capacity)
+    return tuple(t[:stored] for t in out)
+
+
 class DeviceSequences:
     """Packed sequences resident in HBM: residues uint8[total], offsets int64[n+1]."""
 
@@ -87,8 +146,7 @@ def minhash_signatures(ds, k, n_hash, seeds, out=None, planes=None, want_planes=
     signatures in columns [0, n_hash); `planes` is the Planes operand of mh_compare (None if want_planes is
     False), see mh_planes.  raw_planes=True is min_plane_bits=32."""
     lib = _capi.load()
-    if not torch.is_tensor(seeds):
-        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(ds.residues.device)
+    seeds = _seeds_tensor(seeds, ds.residues.device)
     _require_cuda(ds.residues, "residues")
     ld = sig_ld(n_hash) if n_hash > 0 else 32
     if out is None:
@@ -113,8 +171,7 @@ def mh_planes(sig, n, n_hash, planes=None, work=None, min_plane_bits=0):
         planes = planes.tensor
     if planes is None:
         planes = torch.empty(max(planes_words(n, n_hash), 4), dtype=torch.int32, device=sig.device)
-    if work is None:
-        work = torch.empty(planes_workspace_bytes(n, n_hash), dtype=torch.uint8, device=sig.device)
+    work = _work(work, lambda: planes_workspace_bytes(n, n_hash), sig.device)
     bits = ctypes.c_int(0)
     _call(lib.da_dev_mh_planes, sig.data_ptr(), sig.stride(0), n, int(n_hash), int(min_plane_bits),
                                      work.data_ptr(), work.numel(), planes.data_ptr(), planes.numel(),
@@ -182,9 +239,7 @@ def nw(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row_end=
     lib = _capi.load()
     if ds.codes is None:
         raise ValueError("call nw_encode(ds) first")
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    mid = _matrix_id(lib, matrix_name)
     n = ds.n
     row_end = n if row_end is None else row_end
     if symmetric is None:
@@ -204,9 +259,7 @@ def nw_rect(ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, row_begin=0, row
     lib = _capi.load()
     if ds.codes is None:
         raise ValueError("call nw_encode(ds) first")
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    mid = _matrix_id(lib, matrix_name)
     n = ds.n
     row_end = n if row_end is None else row_end
     col_end = n if col_end is None else col_end
@@ -237,34 +290,39 @@ def jaccard_sets_ld(max_len, k):
     return int(_capi.load().da_dev_jaccard_sets_ld(int(max_len), int(k)))
 
 
-def jaccard_sets(ds, k):
-    """The shingle sets of the sequences in ``ds`` (da_dev_jaccard_sets): k in 1 .. 8, every sequence at most 127 shingle positions."""
-    lib = _capi.load()
+def _jaccard_sets(entry, ld_of, count_dtype, ds, k):
     _require_cuda(ds.residues, "residues")
     k = int(k)
-    ld = max(jaccard_sets_ld(ds.max_len, k), 4)
+    ld = max(ld_of(ds.max_len, k), 4)
     keys = torch.empty((max(ds.n, 1), ld), dtype=torch.int32 if k <= 4 else torch.int64, device=ds.residues.device)
-    counts = torch.empty(max(ds.n, 1), dtype=torch.uint8, device=ds.residues.device)
-    _call(lib.da_dev_jaccard_sets, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, ds.max_len, k, keys.data_ptr(), ld, counts.data_ptr(),
-          _stream())
+    counts = torch.empty(max(ds.n, 1), dtype=count_dtype, device=ds.residues.device)
+    _call(entry, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, ds.max_len, k, keys.data_ptr(), ld, counts.data_ptr(), _stream())
     return JaccardSets(keys, counts, ds.n, k)
+
+
+def _jaccard_rect(entry, code_dtype, sets, row_begin, row_end, col_begin, col_end, kind, out):
+    _require_cuda(sets.keys, "shingle sets")
+    n = sets.n
+    row_end = n if row_end is None else row_end
+    col_end = n if col_end is None else col_end
+    if out is None:
+        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else code_dtype,
+                          device=sets.keys.device)
+    _call(entry, sets.keys.data_ptr(), sets.counts.data_ptr(), n, sets.ld_keys, sets.k, int(row_begin), int(row_end), int(col_begin), int(col_end),
+          kind, out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
+def jaccard_sets(ds, k):
+    """The shingle sets of the sequences in ``ds`` (da_dev_jaccard_sets): k in 1 .. 8, every sequence at most 127 shingle positions."""
+    return _jaccard_sets(_capi.load().da_dev_jaccard_sets, jaccard_sets_ld, torch.uint8, ds, k)
 
 
 def jaccard_rect(sets, row_begin=0, row_end=None, col_begin=0, col_end=None, kind=DA_OUT_F64, out=None):
     """The exact Jaccard index on a rectangle (da_dev_jaccard_rect): rows [row_begin, row_end) x columns [col_begin, col_end) of the sets, as
     float64 or as uint16 codes ``intersection << 8 | union`` in an int16 tensor.  On the sets of x + y, rows of x against columns of y give the
     two-set matrix.  ``out`` may be any view with unit column stride (its row stride is the leading dimension)."""
-    lib = _capi.load()
-    _require_cuda(sets.keys, "shingle sets")
-    n = sets.n
-    row_end = n if row_end is None else row_end
-    col_end = n if col_end is None else col_end
-    if out is None:
-        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else torch.int16,
-                          device=sets.keys.device)
-    _call(lib.da_dev_jaccard_rect, sets.keys.data_ptr(), sets.counts.data_ptr(), n, sets.ld_keys, sets.k, int(row_begin), int(row_end),
-          int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
-    return out
+    return _jaccard_rect(_capi.load().da_dev_jaccard_rect, torch.int16, sets, row_begin, row_end, col_begin, col_end, kind, out)
 
 
 def jaccard_sets_long_ld(max_len, k):
@@ -274,32 +332,14 @@ def jaccard_sets_long_ld(max_len, k):
 def jaccard_sets_long(ds, k):
     """The shingle sets of the sequences in ``ds`` for up to 1024 shingle positions a sequence (da_dev_jaccard_sets_long): a JaccardSets whose
     ``counts`` are uint16 bit patterns in an int16 tensor, the operand of jaccard_rect_long."""
-    lib = _capi.load()
-    _require_cuda(ds.residues, "residues")
-    k = int(k)
-    ld = max(jaccard_sets_long_ld(ds.max_len, k), 4)
-    keys = torch.empty((max(ds.n, 1), ld), dtype=torch.int32 if k <= 4 else torch.int64, device=ds.residues.device)
-    counts = torch.empty(max(ds.n, 1), dtype=torch.int16, device=ds.residues.device)
-    _call(lib.da_dev_jaccard_sets_long, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, ds.max_len, k, keys.data_ptr(), ld,
-          counts.data_ptr(), _stream())
-    return JaccardSets(keys, counts, ds.n, k)
+    return _jaccard_sets(_capi.load().da_dev_jaccard_sets_long, jaccard_sets_long_ld, torch.int16, ds, k)
 
 
 def jaccard_rect_long(sets, row_begin=0, row_end=None, col_begin=0, col_end=None, kind=DA_OUT_F64, out=None):
     """The exact Jaccard index on a rectangle of the sets of jaccard_sets_long (da_dev_jaccard_rect_long): as jaccard_rect, with ``kind``
     DA_OUT_F64 or DA_OUT_PACK32 -- uint32 codes ``intersection << 16 | union`` (``1 << 16 | 1`` for two empty sets) in an int32 tensor.  A
     rectangle whose rows and columns are the same range is computed by the symmetric form."""
-    lib = _capi.load()
-    _require_cuda(sets.keys, "shingle sets")
-    n = sets.n
-    row_end = n if row_end is None else row_end
-    col_end = n if col_end is None else col_end
-    if out is None:
-        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else torch.int32,
-                          device=sets.keys.device)
-    _call(lib.da_dev_jaccard_rect_long, sets.keys.data_ptr(), sets.counts.data_ptr(), n, sets.ld_keys, sets.k, int(row_begin), int(row_end),
-          int(col_begin), int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
-    return out
+    return _jaccard_rect(_capi.load().da_dev_jaccard_rect_long, torch.int32, sets, row_begin, row_end, col_begin, col_end, kind, out)
 
 
 def nw_align_workspace_bytes(pairs):
@@ -314,38 +354,41 @@ def nw_align_pairs(dx, dy, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, pair_
     Nothing is checked against the lists here: a pair the kernel cannot take (an index outside its set, more than 127 residues) gets
     length -1.  work: a uint8 device tensor of at least nw_align_workspace_bytes(64) bytes (allocated if None)."""
     lib = _capi.load()
+    mid, pair_x, pair_y, pairs = _align_operands(lib, dx, dy, matrix_name, pair_x, pair_y)
+    ld_ops, ops_t, ln, mt, sc = _align_out(dx, dy, pairs, ops, ld_ops)
+    work = _work(work, lambda: max(nw_align_workspace_bytes(min(max(pairs, 64), 1 << 19)), 16), dx.residues.device)
+    _call(lib.da_dev_nw_align_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n,
+          None if pair_x is None else pair_x.data_ptr(), None if pair_y is None else pair_y.data_ptr(), pairs, mid, int(gap_open), int(gap_ext),
+          None if ops_t is None else ops_t.data_ptr(), ld_ops, ln.data_ptr(), mt.data_ptr(), sc.data_ptr(), work.data_ptr(),
+          work.numel(), _stream())
+    return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
+
+
+def _align_operands(lib, dx, dy, matrix_name, pair_x, pair_y):
+    """the checks nw_align_pairs and nw_align_long_pairs share, in their order -> (matrix id, pair_x, pair_y, number of pairs)"""
     if dx.codes is None or dy.codes is None:
         raise ValueError("call nw_encode on both sets first")
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    mid = _matrix_id(lib, matrix_name)
     if (pair_x is None) != (pair_y is None):
         raise ValueError("pair_x and pair_y must both be given or both be None")
-    dev = dx.residues.device
     if pair_x is None:
         if dx.n != dy.n:
             raise ValueError("without pair lists, dx and dy must hold the same number of sequences (got %d and %d)" % (dx.n, dy.n))
-        pairs = dx.n
-    else:
-        _require_cuda(pair_x, "pair_x")
-        _require_cuda(pair_y, "pair_y")
-        if pair_x.dtype != torch.int32 or pair_y.dtype != torch.int32 or pair_x.numel() != pair_y.numel():
-            raise ValueError("pair_x and pair_y must be int32 tensors of the same length")
-        pair_x, pair_y = pair_x.contiguous(), pair_y.contiguous()
-        pairs = pair_x.numel()
-    if ld_ops is None:
-        ld_ops = max(dx.max_len + dy.max_len, 1)
-    ops_t = torch.empty((max(pairs, 1), int(ld_ops)), dtype=torch.uint8, device=dev) if ops else None
+        return mid, None, None, dx.n
+    _require_cuda(pair_x, "pair_x")
+    _require_cuda(pair_y, "pair_y")
+    if pair_x.dtype != torch.int32 or pair_y.dtype != torch.int32 or pair_x.numel() != pair_y.numel():
+        raise ValueError("pair_x and pair_y must be int32 tensors of the same length")
+    return mid, pair_x.contiguous(), pair_y.contiguous(), pair_x.numel()
+
+
+def _align_out(dx, dy, pairs, ops, ld_ops):
+    """-> (ld_ops, the ops rows or None, length, matches, score) of an alignment call, unwritten"""
+    dev = dx.residues.device
+    ld_ops = int(max(dx.max_len + dy.max_len, 1) if ld_ops is None else ld_ops)
+    ops_t = torch.empty((max(pairs, 1), ld_ops), dtype=torch.uint8, device=dev) if ops else None
     ln = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
-    mt = torch.empty_like(ln)
-    sc = torch.empty_like(ln)
-    if work is None:
-        work = torch.empty(max(nw_align_workspace_bytes(min(max(pairs, 64), 1 << 19)), 16), dtype=torch.uint8, device=dev)
-    _call(lib.da_dev_nw_align_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n,
-          None if pair_x is None else pair_x.data_ptr(), None if pair_y is None else pair_y.data_ptr(), pairs, mid, int(gap_open), int(gap_ext),
-          None if ops_t is None else ops_t.data_ptr(), int(ld_ops), ln.data_ptr(), mt.data_ptr(), sc.data_ptr(), work.data_ptr(),
-          work.numel(), _stream())
-    return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
+    return ld_ops, ops_t, ln, torch.empty_like(ln), torch.empty_like(ln)
 
 
 def nw_align_long_workspace_bytes(pairs, max_len):
@@ -361,39 +404,14 @@ def nw_align_long_pairs(dx, dy, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, 
     (allocated if None; a smaller one than nw_align_long_workspace_bytes(pairs, max_len) means fewer wavefronts in flight); not needed
     with ops=False."""
     lib = _capi.load()
-    if dx.codes is None or dy.codes is None:
-        raise ValueError("call nw_encode on both sets first")
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
-    if (pair_x is None) != (pair_y is None):
-        raise ValueError("pair_x and pair_y must both be given or both be None")
-    dev = dx.residues.device
-    if pair_x is None:
-        if dx.n != dy.n:
-            raise ValueError("without pair lists, dx and dy must hold the same number of sequences (got %d and %d)" % (dx.n, dy.n))
-        pairs = dx.n
-    else:
-        _require_cuda(pair_x, "pair_x")
-        _require_cuda(pair_y, "pair_y")
-        if pair_x.dtype != torch.int32 or pair_y.dtype != torch.int32 or pair_x.numel() != pair_y.numel():
-            raise ValueError("pair_x and pair_y must be int32 tensors of the same length")
-        pair_x, pair_y = pair_x.contiguous(), pair_y.contiguous()
-        pairs = pair_x.numel()
-    if max_len is None:
-        max_len = max(int(dx.max_len), int(dy.max_len))
-    max_len = int(max_len)
-    if ld_ops is None:
-        ld_ops = max(dx.max_len + dy.max_len, 1)
-    ops_t = torch.empty((max(pairs, 1), int(ld_ops)), dtype=torch.uint8, device=dev) if ops else None
-    ln = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
-    mt = torch.empty_like(ln)
-    sc = torch.empty_like(ln)
-    if work is None and ops:
-        work = torch.empty(max(nw_align_long_workspace_bytes(pairs, max_len), 16), dtype=torch.uint8, device=dev)
+    mid, pair_x, pair_y, pairs = _align_operands(lib, dx, dy, matrix_name, pair_x, pair_y)
+    max_len = max(int(dx.max_len), int(dy.max_len)) if max_len is None else int(max_len)
+    ld_ops, ops_t, ln, mt, sc = _align_out(dx, dy, pairs, ops, ld_ops)
+    if ops:
+        work = _work(work, lambda: max(nw_align_long_workspace_bytes(pairs, max_len), 16), dx.residues.device)
     _call(lib.da_dev_nw_align_long_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n,
           None if pair_x is None else pair_x.data_ptr(), None if pair_y is None else pair_y.data_ptr(), pairs, mid, int(gap_open), int(gap_ext),
-          None if ops_t is None else ops_t.data_ptr(), int(ld_ops), ln.data_ptr(), mt.data_ptr(), sc.data_ptr(), max_len,
+          None if ops_t is None else ops_t.data_ptr(), ld_ops, ln.data_ptr(), mt.data_ptr(), sc.data_ptr(), max_len,
           None if work is None else work.data_ptr(), 0 if work is None else work.numel(), _stream())
     return (None if ops_t is None else ops_t[:pairs]), ln[:pairs], mt[:pairs], sc[:pairs]
 
@@ -424,9 +442,7 @@ def cluster_consensus(ds, cluster_ptr, matrix_name="BLOSUM62", gap_open=10, gap_
     lib = _capi.load()
     if ds.codes is None:
         raise ValueError("call nw_encode first")
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    mid = _matrix_id(lib, matrix_name)
     dev = ds.residues.device
     host, dptr = _cluster_table(cluster_ptr, dev)
     clusters = len(host) - 1
@@ -434,8 +450,7 @@ def cluster_consensus(ds, cluster_ptr, matrix_name="BLOSUM62", gap_open=10, gap_
     cons = torch.zeros((max(clusters, 1), ld), dtype=torch.uint8, device=dev)
     cons_len = torch.zeros(max(clusters, 1), dtype=torch.int32, device=dev)
     center = torch.zeros(max(clusters, 1), dtype=torch.int32, device=dev)
-    if work is None:
-        work = torch.empty(max(cluster_consensus_workspace_bytes(host, ds.max_len), 16), dtype=torch.uint8, device=dev)
+    work = _work(work, lambda: max(cluster_consensus_workspace_bytes(host, ds.max_len), 16), dev)
     _call(lib.da_dev_cluster_consensus, ds.codes.data_ptr(), ds.offsets.data_ptr(), ds.n, host.ctypes.data, dptr.data_ptr(), clusters,
           int(ds.max_len), mid, int(gap_open), int(gap_ext), cons.data_ptr(), ld, cons_len.data_ptr(), center.data_ptr(), work.data_ptr(),
           work.numel(), _stream())
@@ -528,15 +543,17 @@ def upper_histogram(compact, n, nbins):
 def extract_edges(compact, n, keep, capacity, include_diagonal=True):
     """Append (i, j, value) of the upper-triangle entries whose value v has keep[v] != 0.
     Returns (i, j, v, count): int32, int32, int16 tensors of `capacity` slots and the int64 count tensor."""
-    dev = compact.device
+    return _extract_edges(_capi.load().da_dev_extract_edges, compact, (n,), keep, capacity, include_diagonal)
+
+
+def _extract_edges(entry, mat, shape, keep, capacity, include_diagonal):
+    """extract_edges / extract_edges_rows: `shape` is what the entry point takes between the matrix's row stride and the keep table"""
+    dev = mat.device
     keep_t = torch.as_tensor(np.ascontiguousarray(keep, np.uint8)).to(dev)
-    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    ev = torch.empty(max(capacity, 1), dtype=torch.int16, device=dev)
+    ei, ej, ev = _edge_slots(capacity, dev, (torch.int32, torch.int32, torch.int16))
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    _call(_capi.load().da_dev_extract_edges, compact.data_ptr(), compact.stride(0), n, keep_t.data_ptr(),
-                                                  keep_t.numel(), 1 if include_diagonal else 0, ei.data_ptr(),
-                                                  ej.data_ptr(), ev.data_ptr(), int(capacity), cnt.data_ptr(), _stream())
+    _call(entry, mat.data_ptr(), mat.stride(0), *shape, keep_t.data_ptr(), keep_t.numel(), 1 if include_diagonal else 0, ei.data_ptr(),
+          ej.data_ptr(), ev.data_ptr(), int(capacity), cnt.data_ptr(), _stream())
     return ei, ej, ev, cnt
 
 
@@ -569,16 +586,7 @@ def upper_histogram_rows(rows, plan, nbins):
 
 def extract_edges_rows(rows, plan, keep, capacity, include_diagonal=True):
     """extract_edges of the full matrix read through the plan's row map"""
-    dev = rows.device
-    keep_t = torch.as_tensor(np.ascontiguousarray(keep, np.uint8)).to(dev)
-    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    ev = torch.empty(max(capacity, 1), dtype=torch.int16, device=dev)
-    cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    _call(_capi.load().da_dev_extract_edges_rows, rows.data_ptr(), rows.stride(0), plan.c.d_uidx, plan.n, keep_t.data_ptr(),
-                                                       keep_t.numel(), 1 if include_diagonal else 0, ei.data_ptr(), ej.data_ptr(),
-                                                       ev.data_ptr(), int(capacity), cnt.data_ptr(), _stream())
-    return ei, ej, ev, cnt
+    return _extract_edges(_capi.load().da_dev_extract_edges_rows, rows, (plan.c.d_uidx, plan.n), keep, capacity, include_diagonal)
 
 
 def edges_to_csr(ei, ej, ev, n_edges, n):
@@ -638,9 +646,7 @@ def louvain_csr(ptr, adj, codes, loops, values, resolution=1.05, seed=0, weights
         raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "ptr[n] (%d) is not the number of adjacency entries (%d)" % (int(ptr[n].item()), nnz))
     ptr, adj, codes = ptr.contiguous(), adj.contiguous(), codes.contiguous()
     loops = None if loops is None else loops.contiguous()
-    nbytes = louvain_workspace_bytes(n, nnz)
-    if work is None:
-        work = torch.empty(nbytes, dtype=torch.uint8, device=ptr.device)
+    work = _work(work, louvain_workspace_bytes(n, nnz), ptr.device)
     member = torch.empty(n, dtype=torch.int32, device=ptr.device)
     q = ctypes.c_double(0.0)
     levels = ctypes.c_int32(0)
@@ -656,11 +662,7 @@ def components_workspace_bytes(n):
 
 
 def _components_buffers(n, dev, sizes, work, nbytes, what):
-    if work is None:
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _require_cuda(work, "work")
-    if work.dtype != torch.uint8 or not work.is_contiguous() or int(work.numel()) < nbytes:
-        raise _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, "work must be a contiguous uint8 tensor of %s bytes" % what)
+    work = _work(work, nbytes, dev, _capi.DynaAlignError(_capi.DA_ERR_BAD_ARG, _WORK_TEXT % what), at_least=nbytes)
     member = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     size_t = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if sizes else None
     return work, member, size_t
@@ -735,8 +737,7 @@ def similarity_mh(ds, k, n_hash, seeds, out=None):
     """similarityMH (src/minHash.cpp:119-188) on a device-resident set, one C call: K1 + K1b + K2, with byte-identical
     sequences collapsed first when that pays (da_dev_similarity_mh).  Returns the (n, n) float64 tensor."""
     lib = _capi.load()
-    if not torch.is_tensor(seeds):
-        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(ds.residues.device)
+    seeds = _seeds_tensor(seeds, ds.residues.device)
     _require_cuda(ds.residues, "residues")
     n = ds.n
     if out is None:
@@ -751,8 +752,7 @@ def similarity_mh_cross(dx, dy, k, n_hash, seeds, out=None):
     the rectangle compare -- or, when collapsing byte-identical strings per side pays, the table of the unique strings and
     its rectangular row expansion.  Returns the (m, n) float64 tensor."""
     lib = _capi.load()
-    if not torch.is_tensor(seeds):
-        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(dx.residues.device)
+    seeds = _seeds_tensor(seeds, dx.residues.device)
     _require_cuda(dx.residues, "residues of x")
     _require_cuda(dy.residues, "residues of y")
     if out is None:
@@ -761,6 +761,41 @@ def similarity_mh_cross(dx, dy, k, n_hash, seeds, out=None):
                                                dy.offsets.data_ptr(), dy.n, dy.total, int(k), int(n_hash), seeds.data_ptr(),
                                                out.data_ptr(), out.stride(0), _stream())
     return out
+
+
+def _block(keys, dtype, n=None):
+    """(rows, n, ld) of a block of keys: a tensor of `dtype` (or of one of a tuple) of shape (rows, >= n), any row stride and base address,
+    whose first n columns (all of them by default) are the block"""
+    _require_cuda(keys, "keys")
+    assert keys.dim() == 2 and keys.dtype in (dtype if isinstance(dtype, tuple) else (dtype,)) and (keys.shape[1] <= 1 or keys.stride(1) == 1)
+    rows, n = int(keys.shape[0]), int(keys.shape[1] if n is None else n)
+    assert 0 <= n <= keys.shape[1]
+    return rows, n, (int(keys.stride(0)) if rows > 1 else max(n, 1))
+
+
+def _rank_table(rank):
+    """the 65536-entry table of uint16 ranks of topk_rows and upper_extrema"""
+    _require_cuda(rank, "rank table")
+    assert rank.dtype == torch.int16 and rank.numel() == 65536 and rank.is_contiguous()
+    return rank.data_ptr()
+
+
+def _topk(entry, entry_self, keys, block, order, top, self_col0, want_self):
+    """topk_rows / topk_ranks: `block` = (rows, n, ld) of the keys, `order` what the entry points take between ld and top.  A block without
+    rows is not handed to the library (its address is NULL)."""
+    rows = block[0]
+    idx, key = _topk_out(rows, top, keys.dtype, keys.device)
+    out = (idx.data_ptr(), key.data_ptr(), idx.shape[1])
+    if self_col0 is None:
+        if want_self:
+            raise ValueError("want_self needs self_col0")
+        if rows > 0:
+            _call(entry, keys.data_ptr(), *block, *order, int(top), *out, _stream())
+        return idx[:rows], key[:rows]
+    own = torch.zeros(max(rows, 1), dtype=keys.dtype, device=keys.device) if want_self else None
+    if rows > 0:
+        _call(entry_self, keys.data_ptr(), *block, *order, int(top), int(self_col0), *out, None if own is None else own.data_ptr(), _stream())
+    return (idx[:rows], key[:rows], own[:rows]) if want_self else (idx[:rows], key[:rows])
 
 
 def topk_rows(keys, top, rank=None, rank_bits=0, self_col0=None, want_self=False):
@@ -772,26 +807,9 @@ def topk_rows(keys, top, rank=None, rank_bits=0, self_col0=None, want_self=False
     its selection (da_dev_topk_rows_self; 1 <= top <= n - 1); with want_self a third result, int16 (rows,), holds the key found at the
     own column (rows whose own column is outside [0, n) keep 0)."""
     lib = _capi.load()
-    _require_cuda(keys, "keys")
-    assert keys.dim() == 2 and keys.dtype == torch.int16 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
-    rows, n = int(keys.shape[0]), int(keys.shape[1])
-    ld = int(keys.stride(0)) if rows > 1 else max(n, 1)
-    if rank is not None:
-        _require_cuda(rank, "rank table")
-        assert rank.dtype == torch.int16 and rank.numel() == 65536 and rank.is_contiguous()
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
-    idx = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
-    key = torch.empty((max(rows, 1), t), dtype=torch.int16, device=keys.device)
-    if self_col0 is None:
-        if want_self:
-            raise ValueError("want_self needs self_col0")
-        _call(lib.da_dev_topk_rows, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(rank_bits), int(top),
-                                         idx.data_ptr(), key.data_ptr(), t, _stream())
-        return idx[:rows], key[:rows]
-    own = torch.zeros(max(rows, 1), dtype=torch.int16, device=keys.device) if want_self else None
-    _call(lib.da_dev_topk_rows_self, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(rank_bits), int(top),
-                                          int(self_col0), idx.data_ptr(), key.data_ptr(), t, None if own is None else own.data_ptr(), _stream())
-    return (idx[:rows], key[:rows], own[:rows]) if want_self else (idx[:rows], key[:rows])
+    block = _block(keys, torch.int16)
+    order = (None if rank is None else _rank_table(rank), int(rank_bits))
+    return _topk(lib.da_dev_topk_rows, lib.da_dev_topk_rows_self, keys, block, order, top, self_col0, want_self)
 
 
 def topk_ranks(keys, top, nbins, self_col0=None, want_self=False):
@@ -801,22 +819,7 @@ def topk_ranks(keys, top, nbins, self_col0=None, want_self=False):
     digits of the radix select.  self_col0 / want_self as in topk_rows (da_dev_topk_ranks_self; 1 <= top <= n - 1): the third result,
     int32 (rows,), holds the rank found at the own column (rows whose own column is outside [0, n) keep 0)."""
     lib = _capi.load()
-    _require_cuda(keys, "keys")
-    assert keys.dim() == 2 and keys.dtype == torch.int32 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
-    rows, n = int(keys.shape[0]), int(keys.shape[1])
-    ld = int(keys.stride(0)) if rows > 1 else max(n, 1)
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
-    idx = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
-    key = torch.empty((max(rows, 1), t), dtype=torch.int32, device=keys.device)
-    if self_col0 is None:
-        if want_self:
-            raise ValueError("want_self needs self_col0")
-        _call(lib.da_dev_topk_ranks, keys.data_ptr(), rows, n, ld, int(nbins), int(top), idx.data_ptr(), key.data_ptr(), t, _stream())
-        return idx[:rows], key[:rows]
-    own = torch.zeros(max(rows, 1), dtype=torch.int32, device=keys.device) if want_self else None
-    _call(lib.da_dev_topk_ranks_self, keys.data_ptr(), rows, n, ld, int(nbins), int(top), int(self_col0), idx.data_ptr(), key.data_ptr(), t,
-                                           None if own is None else own.data_ptr(), _stream())
-    return (idx[:rows], key[:rows], own[:rows]) if want_self else (idx[:rows], key[:rows])
+    return _topk(lib.da_dev_topk_ranks, lib.da_dev_topk_ranks_self, keys, _block(keys, torch.int32), (int(nbins),), top, self_col0, want_self)
 
 
 def similarity_mh_knn(ds, k, n_hash, seeds, top):
@@ -824,14 +827,11 @@ def similarity_mh_knn(ds, k, n_hash, seeds, top):
     (n, top)).  Row i lists the `top` columns j != i of row i of similarity_mh(ds, ...) by value descending, then column ascending; the
     n x n matrix never exists.  top is NOT clamped here (1 <= top <= n - 1)."""
     lib = _capi.load()
-    if not torch.is_tensor(seeds):
-        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(ds.residues.device)
+    seeds = _seeds_tensor(seeds, ds.residues.device)
     _require_cuda(ds.residues, "residues")
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
-    idx = torch.empty((max(ds.n, 1), t), dtype=torch.int32, device=ds.residues.device)
-    val = torch.empty((max(ds.n, 1), t), dtype=torch.float64, device=ds.residues.device)
+    idx, val = _topk_out(ds.n, top, torch.float64, ds.residues.device)
     _call(lib.da_dev_similarity_mh_knn, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, int(k), int(n_hash), seeds.data_ptr(), int(top),
-                                             idx.data_ptr(), val.data_ptr(), t, _stream())
+                                             idx.data_ptr(), val.data_ptr(), idx.shape[1], _stream())
     return idx[:ds.n], val[:ds.n]
 
 
@@ -854,12 +854,10 @@ def knn_edges(idx, key, mode="union", is_nw=False, self_key=None, self_code=0, l
         _require_cuda(self_key, "self_key")
         self_key = self_key.contiguous()
         assert self_key.dtype == torch.int16 and self_key.numel() == n
-    cap = max(n * (top + (1 if loops else 0)), 1)
+    cap = n * (top + (1 if loops else 0))
     nbytes = int(lib.da_dev_knn_edges_bytes(n, top))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    ei = torch.empty(cap, dtype=torch.int32, device=dev)
-    ej = torch.empty(cap, dtype=torch.int32, device=dev)
-    ev = torch.empty(cap, dtype=torch.int16, device=dev)
+    ei, ej, ev = _edge_slots(cap, dev, (torch.int32, torch.int32, torch.int16))
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     _call(lib.da_dev_knn_edges, idx.data_ptr(), key.data_ptr(), top, n, top, _capi.DA_KNN_MUTUAL if mode == "mutual" else _capi.DA_KNN_UNION,
                                      1 if is_nw else 0, None if self_key is None else self_key.data_ptr(), int(self_code), 1 if loops else 0,
@@ -874,30 +872,19 @@ def similarity_mh_cross_topk(dx, dy, k, n_hash, seeds, top):
     row i of similarity_mh_cross(dx, dy, ...) by value descending, then column ascending; the m x n matrix never exists --
     row blocks of uint16 counts are selected from as they are computed.  top is NOT clamped here (1 <= top <= n)."""
     lib = _capi.load()
-    if not torch.is_tensor(seeds):
-        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(dx.residues.device)
+    seeds = _seeds_tensor(seeds, dx.residues.device)
     _require_cuda(dx.residues, "residues of x")
     _require_cuda(dy.residues, "residues of y")
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
-    idx = torch.empty((max(dx.n, 1), t), dtype=torch.int32, device=dx.residues.device)
-    val = torch.empty((max(dx.n, 1), t), dtype=torch.float64, device=dx.residues.device)
+    idx, val = _topk_out(dx.n, top, torch.float64, dx.residues.device)
     _call(lib.da_dev_similarity_mh_cross_topk, dx.residues.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.residues.data_ptr(),
                                                     dy.offsets.data_ptr(), dy.n, int(k), int(n_hash), seeds.data_ptr(), int(top),
-                                                    idx.data_ptr(), val.data_ptr(), t, _stream())
+                                                    idx.data_ptr(), val.data_ptr(), idx.shape[1], _stream())
     return idx[:dx.n], val[:dx.n]
-
-
-def _key_block(keys):
-    """(rows, n, ld) of a block of uint16 keys held in an int16 tensor of shape (rows, n), any row stride and base address"""
-    _require_cuda(keys, "keys")
-    assert keys.dim() == 2 and keys.dtype == torch.int16 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
-    rows, n = int(keys.shape[0]), int(keys.shape[1])
-    return rows, n, (int(keys.stride(0)) if rows > 1 else max(n, 1))
 
 
 def rect_histogram(keys, nbins):
     """uint64 histogram (int64 tensor of nbins entries) of a whole block of uint16 keys; keys >= nbins are ignored (da_dev_rect_histogram)"""
-    rows, n, ld = _key_block(keys)
+    rows, n, ld = _block(keys, torch.int16)
     hist = torch.zeros(int(nbins), dtype=torch.int64, device=keys.device)
     _call(_capi.load().da_dev_rect_histogram, keys.data_ptr(), rows, n, ld, int(nbins), hist.data_ptr(), _stream())
     return hist
@@ -909,45 +896,40 @@ def threshold_rows(keys, keep, capacity=None):
     (da_dev_threshold_rows_count, then da_dev_threshold_rows_emit).  capacity=None sizes j / key from the count (one 8-byte read-back);
     otherwise they hold `capacity` slots and entries beyond it are counted in rowptr but not stored."""
     lib = _capi.load()
-    rows, n, ld = _key_block(keys)
-    dev = keys.device
+    block = _block(keys, torch.int16)
     keep_t = keep if torch.is_tensor(keep) else torch.as_tensor(np.ascontiguousarray(keep, np.uint8))
-    keep_t = keep_t.to(dev).contiguous()
+    keep_t = keep_t.to(keys.device).contiguous()
     assert keep_t.dtype == torch.uint8
+    return _threshold(lib.da_dev_threshold_rows_count, lib.da_dev_threshold_rows_emit, keys, block, (keep_t.data_ptr(), keep_t.numel()), capacity)
+
+
+def _threshold(entry_count, entry_emit, keys, block, mask, capacity):
+    """threshold_rows / threshold_ranks: the count call, the read-back of rowptr[rows] unless a capacity is given, the emit call.  `block` =
+    (rows, n, ld) of the keys, `mask` what the two entry points take between ld and rowptr: what says which entries are kept."""
+    rows, dev = block[0], keys.device
     rowptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
     if rows > 0:
-        nbytes = int(lib.da_dev_threshold_rows_workspace_bytes(rows))
+        nbytes = int(_capi.load().da_dev_threshold_rows_workspace_bytes(rows))
         work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _call(lib.da_dev_threshold_rows_count, keys.data_ptr(), rows, n, ld, keep_t.data_ptr(), keep_t.numel(), rowptr.data_ptr(),
-                                                    work.data_ptr(), nbytes, _stream())
+        _call(entry_count, keys.data_ptr(), *block, *mask, rowptr.data_ptr(), work.data_ptr(), nbytes, _stream())
     cap = int(rowptr[rows].item()) if capacity is None else int(capacity)
-    j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    key = torch.empty(max(cap, 1), dtype=torch.int16, device=dev)
+    j, key = _edge_slots(cap, dev, (torch.int32, keys.dtype))
     if rows > 0 and cap > 0:
-        _call(lib.da_dev_threshold_rows_emit, keys.data_ptr(), rows, n, ld, keep_t.data_ptr(), keep_t.numel(), rowptr.data_ptr(), j.data_ptr(),
-                                                   key.data_ptr(), cap, _stream())
+        _call(entry_emit, keys.data_ptr(), *block, *mask, rowptr.data_ptr(), j.data_ptr(), key.data_ptr(), cap, _stream())
     return rowptr, j[:cap], key[:cap]
-
-
-def _rank_block(keys):
-    """(rows, n, ld) of a block of uint32 keys held in an int32 tensor of shape (rows, n), any row stride and base address"""
-    _require_cuda(keys, "keys")
-    assert keys.dim() == 2 and keys.dtype == torch.int32 and (keys.shape[1] <= 1 or keys.stride(1) == 1)
-    rows, n = int(keys.shape[0]), int(keys.shape[1])
-    return rows, n, (int(keys.stride(0)) if rows > 1 else max(n, 1))
 
 
 def nw_codes_to_ranks(codes, rank, max_len, out=None):
     """The value ranks of a block of PACK32 codes (matches << 16 | length; an int32 tensor (rows, n)) through ``rank``, the table of
     ``nw_value_ranks(max_len)`` as a flat int32 tensor on the device: a code outside the table's domain gets rank 0
     (da_dev_nw_codes_to_ranks).  ``out=None`` returns a new tensor, ``out=codes`` converts in place."""
-    rows, n, ld = _rank_block(codes)
+    rows, n, ld = _block(codes, torch.int32)
     _require_cuda(rank, "rank table")
     ml = int(max_len)
     assert rank.dtype == torch.int32 and rank.is_contiguous() and rank.numel() == (2 * ml + 1) * (ml + 1)
     if out is None:
         out = torch.empty((rows, n), dtype=torch.int32, device=codes.device)
-    orows, on, old = _rank_block(out)
+    orows, on, old = _block(out, torch.int32)
     assert (orows, on) == (rows, n)
     _call(_capi.load().da_dev_nw_codes_to_ranks, codes.data_ptr(), rows, n, ld, ml, rank.data_ptr(), out.data_ptr(), old, _stream())
     return out
@@ -956,7 +938,7 @@ def nw_codes_to_ranks(codes, rank, max_len, out=None):
 def rank_histogram(keys, nbins, triangle=False, row_begin=0, col_begin=0):
     """uint64 histogram (int64 tensor of nbins entries) of a block of uint32 keys; keys >= nbins are ignored (da_dev_rank_histogram).
     triangle: the block is rows row_begin ... x columns col_begin ... of a square problem and only global column > global row counts."""
-    rows, n, ld = _rank_block(keys)
+    rows, n, ld = _block(keys, torch.int32)
     hist = torch.zeros(int(nbins), dtype=torch.int64, device=keys.device)
     _call(_capi.load().da_dev_rank_histogram, keys.data_ptr(), rows, n, ld, int(nbins), hist.data_ptr(), int(bool(triangle)), int(row_begin),
           int(col_begin), _stream())
@@ -968,20 +950,8 @@ def threshold_ranks(keys, r_min, nbins, triangle=False, row_begin=0, col_begin=0
     pattern)) -- per row the kept columns (local to the block), ascending (da_dev_threshold_ranks_count, then da_dev_threshold_ranks_emit).
     triangle: only global column >= global row, the diagonal included.  capacity as in ``threshold_rows``."""
     lib = _capi.load()
-    rows, n, ld = _rank_block(keys)
-    dev = keys.device
-    rowptr = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
     mask = (int(r_min), int(nbins), int(bool(triangle)), int(row_begin), int(col_begin))
-    if rows > 0:
-        nbytes = int(lib.da_dev_threshold_rows_workspace_bytes(rows))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _call(lib.da_dev_threshold_ranks_count, keys.data_ptr(), rows, n, ld, *mask, rowptr.data_ptr(), work.data_ptr(), nbytes, _stream())
-    cap = int(rowptr[rows].item()) if capacity is None else int(capacity)
-    j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    key = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-    if rows > 0 and cap > 0:
-        _call(lib.da_dev_threshold_ranks_emit, keys.data_ptr(), rows, n, ld, *mask, rowptr.data_ptr(), j.data_ptr(), key.data_ptr(), cap, _stream())
-    return rowptr, j[:cap], key[:cap]
+    return _threshold(lib.da_dev_threshold_ranks_count, lib.da_dev_threshold_ranks_emit, keys, _block(keys, torch.int32), mask, capacity)
 
 
 def upper_extrema(keys, n, rank=None, row_begin=0, col_begin=0):
@@ -992,17 +962,10 @@ def upper_extrema(keys, n, rank=None, row_begin=0, col_begin=0):
     element, the diagonal 0xFFFFFFFF where it lies outside the block).  rank: the 65536-entry int16 table of ``nw_code_ranks`` on the device,
     uint16 keys only -- the comparison is then on rank[key] and the record holds ranks (da_dev_upper_extrema / da_dev_upper_extrema32)."""
     lib = _capi.load()
-    _require_cuda(keys, "keys")
-    assert keys.dim() == 2 and keys.dtype in (torch.int16, torch.int32) and (keys.shape[1] <= 1 or keys.stride(1) == 1)
-    rows, n = int(keys.shape[0]), int(n)
-    assert 0 <= n <= keys.shape[1]
-    ld = int(keys.stride(0)) if rows > 1 else max(n, 1)
+    rows, n, ld = _block(keys, (torch.int16, torch.int32), n)
     rec = torch.empty((max(rows, 1), _capi.ROW_EXTREMA_WORDS), dtype=torch.int32, device=keys.device)
     if keys.dtype == torch.int16:
-        if rank is not None:
-            _require_cuda(rank, "rank table")
-            assert rank.dtype == torch.int16 and rank.numel() == 65536 and rank.is_contiguous()
-        _call(lib.da_dev_upper_extrema, keys.data_ptr(), rows, n, ld, None if rank is None else rank.data_ptr(), int(row_begin), int(col_begin),
+        _call(lib.da_dev_upper_extrema, keys.data_ptr(), rows, n, ld, None if rank is None else _rank_table(rank), int(row_begin), int(col_begin),
               rec.data_ptr(), _stream())
     else:
         assert rank is None, "uint32 keys are value ranks already"
@@ -1017,8 +980,7 @@ def similarity_mh_cross_edges(dx, dy, k, n_hash, seeds, thresh_p=None, threshold
     m * n entries.  With a capacity, j / w hold that many slots and rowptr is complete even when rowptr[m] exceeds it; capacity=None
     starts from a guess and calls again when the result does not fit."""
     lib = _capi.load()
-    if not torch.is_tensor(seeds):
-        seeds = torch.from_numpy(np.ascontiguousarray(seeds, np.uint32).view(np.int32).copy()).to(dx.residues.device)
+    seeds = _seeds_tensor(seeds, dx.residues.device)
     _require_cuda(dx.residues, "residues of x")
     _require_cuda(dy.residues, "residues of y")
     dev = dx.residues.device
@@ -1027,8 +989,7 @@ def similarity_mh_cross_edges(dx, dy, k, n_hash, seeds, thresh_p=None, threshold
     thr, cnt = ctypes.c_double(0.0), ctypes.c_int64(0)
     cap = max(4 * max(dx.n, 0), 1 << 20) if capacity is None else int(capacity)
     while True:
-        j = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        w = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+        j, w = _edge_slots(cap, dev, (torch.int32, torch.float64))
         _call(lib.da_dev_similarity_mh_cross_edges, dx.residues.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.residues.data_ptr(),
                                                          dy.offsets.data_ptr(), dy.n, int(k), int(n_hash), seeds.data_ptr(), thresh, is_q,
                                                          rowptr.data_ptr(), j.data_ptr(), w.data_ptr(), cap, ctypes.addressof(thr),
@@ -1051,6 +1012,20 @@ def lsh_workspace_bytes(n, bands):
     return int(_capi.load().da_dev_lsh_workspace_bytes(int(n), int(bands)))
 
 
+def _lsh_work(work, n, bands, device):
+    return _work(work, lambda: lsh_workspace_bytes(n, bands), device, ValueError(_WORK_TEXT % "lsh_workspace_bytes(n, bands)"))
+
+
+def _listed_triples(i, j, band, device):
+    """-> (i, j, band as int32 device tensors, their number m, the zeroed count int16 and keep uint8 results) of the verify calls"""
+    ti, tj, tb = ((a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, np.int32))).to(device=device, dtype=torch.int32).contiguous()
+                  for a in (i, j, band))
+    if not ti.numel() == tj.numel() == tb.numel():
+        raise ValueError("i, j and band must have the same number of entries")
+    m = int(ti.numel())
+    return ti, tj, tb, m, torch.zeros(max(m, 1), dtype=torch.int16, device=device), torch.zeros(max(m, 1), dtype=torch.uint8, device=device)
+
+
 def lsh_band_keys(sig, n_hash, bands, rows):
     """The bucket keys of LSH banding (da_dev_lsh_band_keys): ``sig`` (n, >= n_hash) 32-bit -> (keys int64 (n, bands), ids int32 (n, bands)):
     keys[i, t] = t << 48 | 48 bits of a hash of sig[i, t * rows:(t + 1) * rows], ids[i, t] = i.  Reads columns < bands * rows only."""
@@ -1068,13 +1043,7 @@ def lsh_verify_pairs(sig, n_hash, bands, rows, threshold, i, j, band):
     count / n_hash >= threshold."""
     lib = _capi.load()
     n, ld = _sig_block(sig, n_hash)
-    ti, tj, tb = ((a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, np.int32))).to(device=sig.device, dtype=torch.int32).contiguous()
-                  for a in (i, j, band))
-    if not ti.numel() == tj.numel() == tb.numel():
-        raise ValueError("i, j and band must have the same number of entries")
-    m = int(ti.numel())
-    count = torch.zeros(max(m, 1), dtype=torch.int16, device=sig.device)
-    keep = torch.zeros(max(m, 1), dtype=torch.uint8, device=sig.device)
+    ti, tj, tb, m, count, keep = _listed_triples(i, j, band, sig.device)
     _call(lib.da_dev_lsh_verify_pairs, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), ti.data_ptr(), tj.data_ptr(),
           tb.data_ptr(), m, count.data_ptr(), keep.data_ptr(), _stream())
     return count[:m], keep[:m]
@@ -1086,26 +1055,14 @@ def lsh_edges(sig, n_hash, bands, rows, threshold, max_candidates=1 << 32, capac
     call, and at most that many edges are returned (``mh_lsh_last_route()["edges"]`` has the full number).  Synchronises the stream."""
     lib = _capi.load()
     n, ld = _sig_block(sig, n_hash)
-    if work is None:
-        work = torch.empty(lsh_workspace_bytes(n, bands), dtype=torch.uint8, device=sig.device)
-    _require_cuda(work, "work")
-    if work.dtype != torch.uint8 or not work.is_contiguous():
-        raise ValueError("work must be a contiguous uint8 tensor of lsh_workspace_bytes(n, bands) bytes")
+    work = _lsh_work(work, n, bands, sig.device)
     m = ctypes.c_int64(0)
 
     def run(cap, ti, tj, tc):
         _call(lib.da_dev_lsh_edges, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), int(max_candidates),
               work.data_ptr(), work.numel(), ti, tj, tc, cap, ctypes.byref(m), _stream())
-    if capacity is None:
-        run(0, None, None, None)
-        capacity = m.value
-    capacity = int(capacity)
-    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig.device)
-    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig.device)
-    ec = torch.empty(max(capacity, 1), dtype=torch.int16, device=sig.device)
-    run(capacity, ei.data_ptr(), ej.data_ptr(), ec.data_ptr())
-    got = min(m.value, capacity)
-    return ei[:got], ej[:got], ec[:got]
+        return m.value
+    return _count_then_fill(run, capacity, sig.device, (torch.int32, torch.int32, torch.int16))
 
 
 def lsh_components(sig, n_hash, bands, rows, threshold, max_candidates=1 << 32, sizes=False, work=None):
@@ -1147,10 +1104,9 @@ def lsh_knn_select(ptr, col, count, top, nnz=None, out=None):
     nnz = int(col.numel()) if nnz is None else int(nnz)
     if not 0 <= nnz <= col.numel():
         raise ValueError("nnz must be in 0 .. col.numel()")
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
+    t = _top(top)
     if out is None:
-        idx = torch.empty((max(n, 1), t), dtype=torch.int32, device=ptr.device)
-        key = torch.empty((max(n, 1), t), dtype=torch.int16, device=ptr.device)
+        idx, key = _topk_out(n, top, torch.int16, ptr.device)
     else:
         idx, key = out
         for o, dt in ((idx, torch.int32), (key, torch.int16)):
@@ -1167,14 +1123,8 @@ def lsh_knn(sig, n_hash, bands, rows, top, threshold=0.0, max_candidates=1 << 32
     entries.  Synchronises the stream."""
     lib = _capi.load()
     n, ld = _sig_block(sig, n_hash)
-    if work is None:
-        work = torch.empty(lsh_workspace_bytes(n, bands), dtype=torch.uint8, device=sig.device)
-    _require_cuda(work, "work")
-    if work.dtype != torch.uint8 or not work.is_contiguous():
-        raise ValueError("work must be a contiguous uint8 tensor of lsh_workspace_bytes(n, bands) bytes")
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
-    idx = torch.empty((max(n, 1), t), dtype=torch.int32, device=sig.device)
-    key = torch.empty((max(n, 1), t), dtype=torch.int16, device=sig.device)
+    work = _lsh_work(work, n, bands, sig.device)
+    idx, key = _topk_out(n, top, torch.int16, sig.device)
     _call(lib.da_dev_lsh_knn, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(threshold), int(top), int(max_candidates),
           work.data_ptr(), work.numel(), idx.data_ptr(), key.data_ptr(), _stream())
     return idx[:n], key[:n]
@@ -1243,13 +1193,7 @@ def lsh_cross_verify_pairs(sig_x, sig_y, n_hash, bands, rows, threshold, i, j, b
     lib = _capi.load()
     m, ld_x = _sig_block(sig_x, n_hash)
     n, ld_y = _sig_block(sig_y, n_hash)
-    ti, tj, tb = ((a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, np.int32))).to(device=sig_x.device, dtype=torch.int32).contiguous()
-                  for a in (i, j, band))
-    if not ti.numel() == tj.numel() == tb.numel():
-        raise ValueError("i, j and band must have the same number of entries")
-    cnt = int(ti.numel())
-    count = torch.zeros(max(cnt, 1), dtype=torch.int16, device=sig_x.device)
-    keep = torch.zeros(max(cnt, 1), dtype=torch.uint8, device=sig_x.device)
+    ti, tj, tb, cnt, count, keep = _listed_triples(i, j, band, sig_x.device)
     _call(lib.da_dev_lsh_cross_verify_pairs, sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands), int(rows), float(threshold),
           ti.data_ptr(), tj.data_ptr(), tb.data_ptr(), cnt, count.data_ptr(), keep.data_ptr(), _stream())
     return count[:cnt], keep[:cnt]
@@ -1259,9 +1203,7 @@ def _lsh_cross_operands(index, sig_x, sig_y, n_hash, bands, work):
     m, ld_x = _sig_block(sig_x, n_hash)
     n, ld_y = _sig_block(sig_y, n_hash)
     _byte_buffer(index, "index", "lsh_index_bytes(n, bands)")
-    if work is None:
-        work = torch.empty(lsh_cross_workspace_bytes(m, bands), dtype=torch.uint8, device=sig_x.device)
-    _byte_buffer(work, "work", "lsh_cross_workspace_bytes(m, bands)")
+    work = _work(work, lambda: lsh_cross_workspace_bytes(m, bands), sig_x.device, ValueError(_WORK_TEXT % "lsh_cross_workspace_bytes(m, bands)"))
     return m, ld_x, n, ld_y, work
 
 
@@ -1277,16 +1219,8 @@ def lsh_cross_edges(index, sig_x, sig_y, n_hash, bands, rows, threshold, max_can
     def run(cap, ti, tj, tc):
         _call(lib.da_dev_lsh_cross_edges, index.data_ptr(), index.numel(), sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands),
               int(rows), float(threshold), int(max_candidates), work.data_ptr(), work.numel(), ti, tj, tc, cap, ctypes.byref(got), _stream())
-    if capacity is None:
-        run(0, None, None, None)
-        capacity = got.value
-    capacity = int(capacity)
-    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig_x.device)
-    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=sig_x.device)
-    ec = torch.empty(max(capacity, 1), dtype=torch.int16, device=sig_x.device)
-    run(capacity, ei.data_ptr(), ej.data_ptr(), ec.data_ptr())
-    stored = min(got.value, capacity)
-    return ei[:stored], ej[:stored], ec[:stored]
+        return got.value
+    return _count_then_fill(run, capacity, sig_x.device, (torch.int32, torch.int32, torch.int16))
 
 
 def lsh_cross_topk(index, sig_x, sig_y, n_hash, bands, rows, top, threshold=0.0, max_candidates=1 << 32, work=None):
@@ -1294,9 +1228,7 @@ def lsh_cross_topk(index, sig_x, sig_y, n_hash, bands, rows, top, threshold=0.0,
     patterns; padding -1 / 0); value = count / n_hash (``widen``).  ``top`` is not clamped to the rows of sig_y.  Synchronises the stream."""
     lib = _capi.load()
     m, ld_x, n, ld_y, work = _lsh_cross_operands(index, sig_x, sig_y, n_hash, bands, work)
-    t = max(min(int(top), _capi.DA_TOPK_MAX), 1)
-    idx = torch.empty((max(m, 1), t), dtype=torch.int32, device=sig_x.device)
-    key = torch.empty((max(m, 1), t), dtype=torch.int16, device=sig_x.device)
+    idx, key = _topk_out(m, top, torch.int16, sig_x.device)
     _call(lib.da_dev_lsh_cross_topk, index.data_ptr(), index.numel(), sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands),
           int(rows), float(threshold), int(top), int(max_candidates), work.data_ptr(), work.numel(), idx.data_ptr(), key.data_ptr(), _stream())
     return idx[:m], key[:m]
@@ -1309,13 +1241,6 @@ def mh_lsh_last_route():
 
 def nw_rescore_workspace_bytes(pairs, max_len=1024, minimal=False):
     return int(_capi.load().da_dev_nw_rescore_workspace_bytes(int(pairs), int(max_len), 1 if minimal else 0))
-
-
-def _matrix_id(lib, matrix_name):
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
-    return mid
 
 
 def nw_rescore_pairs(dx, dy, i, j, matrix_name="BLOSUM62", gap_open=10, gap_ext=4, work=None):
@@ -1339,11 +1264,8 @@ def nw_rescore_pairs(dx, dy, i, j, matrix_name="BLOSUM62", gap_open=10, gap_ext=
     dev = dx.residues.device
     mt = torch.empty(max(pairs, 1), dtype=torch.int32, device=dev)
     ln = torch.empty_like(mt)
-    if work is None:
-        work = torch.empty(max(nw_rescore_workspace_bytes(pairs), 16), dtype=torch.uint8, device=dev)
-    _require_cuda(work, "work")
-    if work.dtype != torch.uint8 or work.dim() != 1 or work.stride(0) != 1:
-        raise ValueError("work must be a 1-d uint8 tensor with unit stride")
+    work = _work(work, lambda: max(nw_rescore_workspace_bytes(pairs), 16), dev, ValueError("work must be a 1-d uint8 tensor with unit stride"),
+                 flat=True)
     _call(lib.da_dev_nw_rescore_pairs, dx.codes.data_ptr(), dx.offsets.data_ptr(), dx.n, dy.codes.data_ptr(), dy.offsets.data_ptr(), dy.n, i.data_ptr(),
           j.data_ptr(), pairs, mid, int(gap_open), int(gap_ext), mt.data_ptr(), ln.data_ptr(), work.data_ptr(), work.numel(), _stream())
     return mt[:pairs], ln[:pairs]
@@ -1369,9 +1291,7 @@ def lsh_nw_edges(sig, ds, n_hash, bands, rows, threshold, mh_threshold=0.0, matr
         m, ld_x, n, ld_y, work = _lsh_cross_operands(index, sig, sig_y, n_hash, bands, work)
     else:
         n, ld = _sig_block(sig, n_hash)
-        if work is None:
-            work = torch.empty(lsh_workspace_bytes(n, bands), dtype=torch.uint8, device=dev)
-        _byte_buffer(work, "work", "lsh_workspace_bytes(n, bands)")
+        work = _lsh_work(work, n, bands, dev)
     got = ctypes.c_int64(0)
 
     def run(cap, ti, tj, tm, tl):
@@ -1384,14 +1304,8 @@ def lsh_nw_edges(sig, ds, n_hash, bands, rows, threshold, mh_threshold=0.0, matr
             _call(lib.da_dev_lsh_nw_edges, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(mh_threshold), int(max_candidates),
                   ds.codes.data_ptr(), ds.offsets.data_ptr(), mid, int(gap_open), int(gap_ext), float(threshold), work.data_ptr(), work.numel(),
                   ti, tj, tm, tl, cap, ctypes.byref(got), _stream())
-    if capacity is None:
-        run(0, None, None, None, None)
-        capacity = got.value
-    capacity = int(capacity)
-    out = [torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) for _ in range(4)]
-    run(capacity, *[t.data_ptr() for t in out])
-    stored = min(got.value, capacity)
-    return tuple(t[:stored] for t in out)
+        return got.value
+    return _count_then_fill(run, capacity, dev, (torch.int32,) * 4)
 
 
 def nw_lsh_last_route():
@@ -1466,9 +1380,7 @@ def shards_to_table(gathered, ld_g, n, world, value_bits, out=None):
 def nw_unique_rows(plan, max_len, matrix_name, gap_open, gap_ext, rank, world, out_rows):
     """rank `rank` of `world`'s cyclic 128-row units of the ordered unique NW table into out_rows (int16 [Q * 128][ld >= unique])"""
     lib = _capi.load()
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    mid = _matrix_id(lib, matrix_name)
     _call(lib.da_dev_nw_unique_rows, plan.ptr(), int(max_len), mid, int(gap_open), int(gap_ext), int(rank), int(world),
                                           out_rows.data_ptr(), out_rows.stride(0), _stream())
 
@@ -1479,8 +1391,7 @@ def expand_workspace_bytes(n, unique, is_nw, n_hash=0, nw_max_len=0):
 
 def expand_unique(table, plan, is_nw, n_hash, nw_max_len, out, table_world=1, work=None):
     """dense float64 n x n from the table of the unique strings (da_dev_expand_unique)"""
-    if work is None:
-        work = torch.empty(expand_workspace_bytes(plan.n, plan.unique, is_nw, n_hash, nw_max_len), dtype=torch.uint8, device=table.device)
+    work = _work(work, lambda: expand_workspace_bytes(plan.n, plan.unique, is_nw, n_hash, nw_max_len), table.device)
     _call(_capi.load().da_dev_expand_unique, table.data_ptr(), table.stride(0), int(table_world), plan.ptr(), 1 if is_nw else 0,
                                                   int(n_hash), int(nw_max_len), work.data_ptr(), work.numel(), out.data_ptr(), out.stride(0),
                                                   _stream())

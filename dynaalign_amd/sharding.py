@@ -205,10 +205,9 @@ def mh_sharded_step_packed(plan, work, planes, n_hash, out, group=None):
 
 def nw_local_block(plan, work, ds, matrix_name="BLOSUM62", gap_open=10, gap_ext=4):
     assert plan.tile == NW_TILE
+    from .device import _matrix_id
     lib = _capi.load()
-    mid = lib.da_matrix_id(matrix_name.encode("latin-1"))
-    if mid < 0:
-        _capi.check(_capi.DA_ERR_BAD_MATRIX)
+    mid = _matrix_id(lib, matrix_name)
     _capi.check(lib.da_dev_nw_shard(ds.codes.data_ptr(), ds.offsets.data_ptr(), plan.n, ds.max_len, mid, int(gap_open),
                                     int(gap_ext), plan.rank, plan.world, work.local.data_ptr(), work.local.stride(0),
                                     _stream()))
@@ -344,11 +343,10 @@ def shard_histogram(plan, local, nbins):
 
 def shard_extract_edges(plan, local, keep, capacity):
     import numpy as np
+    from .device import _edge_slots
     dev = local.device
     keep_t = torch.as_tensor(np.ascontiguousarray(keep, np.uint8)).to(dev)
-    ei = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    ej = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
-    ev = torch.empty(max(capacity, 1), dtype=torch.int16, device=dev)
+    ei, ej, ev = _edge_slots(capacity, dev, (torch.int32, torch.int32, torch.int16))
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
     _capi.check(_capi.load().da_dev_shard_extract_edges(local.data_ptr(), local.stride(0), plan.n, plan.rank, plan.world,
                                                         keep_t.data_ptr(), keep_t.numel(), 1, ei.data_ptr(), ej.data_ptr(),

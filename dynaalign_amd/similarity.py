@@ -57,6 +57,7 @@ extension), ``set_option("seed", s)`` or the environment variable
 ``DYNAALIGN_SEED``; the seed is expanded with the reference's own rule
 (``HashFamily(n_hash, seed)``, src/minHash.cpp:73-81).
 """
+import ctypes
 import os
 
 import numpy as np
@@ -115,6 +116,27 @@ def _as_int(x, name):
         raise TypeError("%s must be an integer" % name)
 
 
+def _matrix_name(matrixName):
+    return matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+
+
+def _pack_two(x, y):
+    """two character vectors -> (x residues, x offsets, m, y residues, y offsets, n)"""
+    xr, xo = pack_sequences(x)
+    yr, yo = pack_sequences(y)
+    return xr, xo, len(xo) - 1, yr, yo, len(yo) - 1
+
+
+def _topk_arrays(rows, top, limit):
+    """-> (top, idx int32, val float64): the host arrays of a top-k call, at least one slot each way, with ``top`` clamped to ``limit``,
+    the number of candidates a row has, when there is one (the C ABI does not clamp)"""
+    top = _as_int(top, "top")
+    if limit >= 1:
+        top = min(top, limit)
+    shape = (max(rows, 1), max(top, 1))
+    return top, np.empty(shape, np.int32), np.empty(shape, np.float64)
+
+
 def hash_family_seeds(seed, n_hash):
     """seeds[h] = h-th raw std::mt19937(seed) output (reference src/minHash.cpp:75-80)."""
     lib = _capi.load()
@@ -143,6 +165,13 @@ def _mh_prelude(sequences, k, n_hash, seed):
     if len(seeds) == 0:
         seeds = np.zeros(1, np.uint32)
     return lib, res, off, n, k, n_hash, seeds
+
+
+def _mh_prelude_two(x, y, k, n_hash, seed):
+    """_mh_prelude on ``x``, then ``y`` packed -> (lib, x residues, x offsets, m, y residues, y offsets, n, k, n_hash, seeds)"""
+    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
+    yr, yo = pack_sequences(y)
+    return lib, xr, xo, m, yr, yo, len(yo) - 1, k, n_hash, seeds
 
 
 def _device_opts(devices, exchange):
@@ -183,7 +212,6 @@ def similarityMH(sequences, k=4, n_hash=50, *, seed=None, devices=None, exchange
         _capi.check(lib.da_similarity_mh(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data,
                                          out.ctypes.data))
     else:
-        import ctypes
         _capi.check(lib.da_similarity_mh_opts(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data,
                                               out.ctypes.data, ctypes.addressof(opts)))
     _record_phases(keep)
@@ -195,9 +223,7 @@ def similarityMH_cross(x, y, k=4, n_hash=50, *, seed=None):
     R[i, j] = #{h : sig_x[i, h] == sig_y[j, h]} / n_hash -- bit for bit the block [0:m, m:m+n] of
     ``similarityMH(x + y, k, n_hash)`` under the same seeds.  No forced diagonal: an element is 1.0 only because the
     signatures agree.  Errors as similarityMH, with "Input sequences vector cannot be empty" for ``x``, then for ``y``."""
-    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
-    yr, yo = pack_sequences(y)
-    n = len(yo) - 1
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
     out = np.empty((max(m, 1), max(n, 1)), np.float64)
     _capi.check(lib.da_similarity_mh_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash,
                                            seeds.ctypes.data, out.ctypes.data, 0))
@@ -211,13 +237,8 @@ def similarityMH_cross_topk(x, y, k=4, n_hash=50, top=10, *, seed=None):
     R = similarityMH_cross(x, y, k, n_hash, seed=seed): value descending, position ascending among equals; columns of
     similarity 0 fill a row with fewer than ``top`` positive ones.  ``top`` is clamped to ``len(y)`` (the C ABI does not clamp) and may be
     at most 1024.  Errors as similarityMH_cross."""
-    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
-    yr, yo = pack_sequences(y)
-    n = len(yo) - 1
-    top = _as_int(top, "top")
-    t = min(top, n) if n > 0 else top
-    idx = np.empty((max(m, 1), max(t, 1)), np.int32)
-    val = np.empty((max(m, 1), max(t, 1)), np.float64)
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
+    t, idx, val = _topk_arrays(m, top, n)
     _capi.check(lib.da_similarity_mh_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash,
                                                 seeds.ctypes.data, t, idx.ctypes.data, val.ctypes.data))
     return idx[:m], val[:m]
@@ -254,13 +275,12 @@ def similarityNW(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, devi
     res, off = pack_sequences(sequences)
     n = len(off) - 1
     out = np.empty((max(n, 1), max(n, 1)), np.float64)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     opts, keep = _device_opts(devices, exchange)
     if opts is None:
         _capi.check(lib.da_similarity_nw(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"),
                                          _as_int(gapExt, "gapExt"), out.ctypes.data))
     else:
-        import ctypes
         _capi.check(lib.da_similarity_nw_opts(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"),
                                               _as_int(gapExt, "gapExt"), out.ctypes.data, ctypes.addressof(opts)))
     _record_phases(keep)
@@ -273,11 +293,9 @@ def similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
     [0:m, m:m+n] of ``similarityNW(x + y, ...)``.  An empty ``x`` or ``y`` gives a (0, n) / (m, 0) matrix; residue errors are
     what the reference's lazy fill would raise first with the pairs visited i over ``x``, then j over ``y``."""
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
     out = np.empty((max(m, 1), max(n, 1)), np.float64)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     _capi.check(lib.da_similarity_nw_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
                                            _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), out.ctypes.data, 0))
     return SimilarityMatrix(out[:m, :n])
@@ -285,14 +303,9 @@ def similarityNW_cross(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4):
 
 def _nw_cross_topk(entry, x, y, matrixName, gapOpen, gapExt, top):
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
-    top = _as_int(top, "top")
-    t = min(top, n) if n > 0 else top
-    idx = np.empty((max(m, 1), max(t, 1)), np.int32)
-    val = np.empty((max(m, 1), max(t, 1)), np.float64)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
+    t, idx, val = _topk_arrays(m, top, n)
+    name = _matrix_name(matrixName)
     _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name,
                                     _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t, idx.ctypes.data, val.ctypes.data))
     return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
@@ -320,10 +333,7 @@ def similarityMH_knn(sequences, k=4, n_hash=50, top=10, *, seed=None):
     row.  ``top`` is clamped to ``len(sequences) - 1`` (the C ABI does not clamp) and may be at most 1024.  Byte-identical sequences fill each
     other's lists at 1.0: pass distinct sequences.  Errors as similarityMH, then "a nearest neighbour needs a second sequence"."""
     lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
-    top = _as_int(top, "top")
-    t = min(top, n - 1) if n >= 2 else top
-    idx = np.empty((max(n, 1), max(t, 1)), np.int32)
-    val = np.empty((max(n, 1), max(t, 1)), np.float64)
+    t, idx, val = _topk_arrays(n, top, n - 1)
     _capi.check(lib.da_similarity_mh_knn(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, t, idx.ctypes.data, val.ctypes.data))
     return idx[:n], val[:n]
 
@@ -332,12 +342,9 @@ def _nw_knn(entry, sequences, matrixName, gapOpen, gapExt, top):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
-    top = _as_int(top, "top")
-    t = min(top, n - 1) if n >= 2 else top
-    idx = np.empty((max(n, 1), max(t, 1)), np.int32)
-    val = np.empty((max(n, 1), max(t, 1)), np.float64)
+    t, idx, val = _topk_arrays(n, top, n - 1)
     diag = np.empty(max(n, 1), np.float64)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), t,
                                     idx.ctypes.data, val.ctypes.data, diag.ctypes.data))
     return idx[:n], val[:n], diag[:n]
@@ -505,9 +512,7 @@ def similarityJaccard_cross(x, y, k=4):
 
 def _jaccard_cross(entry, x, y, k):
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
     out = np.empty((max(m, 1), max(n, 1)), np.float64)
     _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"), out.ctypes.data, 0))
     return SimilarityMatrix(out[:m, :n])
@@ -523,13 +528,8 @@ def similarityJaccard_cross_topk(x, y, k=4, top=10):
 
 def _jaccard_cross_topk(entry, x, y, k, top):
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
-    top = _as_int(top, "top")
-    t = min(top, n) if n > 0 else top
-    idx = np.empty((max(m, 1), max(t, 1)), np.int32)
-    val = np.empty((max(m, 1), max(t, 1)), np.float64)
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
+    t, idx, val = _topk_arrays(m, top, n)
     _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _as_int(k, "k"), t, idx.ctypes.data,
                                     val.ctypes.data))
     return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
@@ -546,10 +546,7 @@ def _jaccard_knn(entry, sequences, k, top):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
-    top = _as_int(top, "top")
-    t = min(top, n - 1) if n >= 2 else top
-    idx = np.empty((max(n, 1), max(t, 1)), np.int32)
-    val = np.empty((max(n, 1), max(t, 1)), np.float64)
+    t, idx, val = _topk_arrays(n, top, n - 1)
     _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), t, idx.ctypes.data, val.ctypes.data))
     return idx[:n], val[:n]
 
@@ -566,12 +563,15 @@ def similarityJaccard_edges(sequences, k=4, thresh_p=0.8):
     similarityMH_edges: ``(threshold, i, j, weight)`` for the entries with i <= j (0-based, sorted, diagonal included) whose value is
     >= the type-7 ``thresh_p`` quantile of the strict upper triangle and > 0.  A deterministic graph for
     ``clusterbreak(pep, edges_fn=lambda s: similarityJaccard_edges(s, k=2))``."""
+    return _jaccard_edges("da_similarity_jaccard_edges_begin", sequences, k, thresh_p)
+
+
+def _jaccard_edges(entry, sequences, k, thresh_p):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
     k = _as_int(k, "k")
-    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_edges_begin(
-        res.ctypes.data, off.ctypes.data, n, k, float(thresh_p), h, thr, cnt))
+    return _edges_one_pass(lambda h, thr, cnt: getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, k, float(thresh_p), h, thr, cnt))
 
 
 # ---- the exact Jaccard index for sequences of up to 1024 shingle positions: the _long siblings ------------------------------------------------
@@ -611,12 +611,7 @@ def similarityJaccard_edges_long(sequences, k=4, thresh_p=0.8):
     """``similarityJaccard_edges`` for sequences of up to 1024 shingle positions (da_similarity_jaccard_edges_long_begin): the same
     arguments, the same result, the same errors.  ``clusterbreak(pep, edges_fn=lambda s: similarityJaccard_edges_long(s, k=4))`` clusters
     full-length proteins on the exact index."""
-    lib = _capi.load()
-    res, off = pack_sequences(sequences)
-    n = len(off) - 1
-    k = _as_int(k, "k")
-    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_edges_long_begin(
-        res.ctypes.data, off.ctypes.data, n, k, float(thresh_p), h, thr, cnt))
+    return _jaccard_edges("da_similarity_jaccard_edges_long_begin", sequences, k, thresh_p)
 
 
 def similarityJaccard_cross_edges_long(x, y, k=4, thresh_p=0.8, *, threshold=None):
@@ -626,9 +621,7 @@ def similarityJaccard_cross_edges_long(x, y, k=4, thresh_p=0.8, *, threshold=Non
     shingle positions, short ones included (the short family has no such form).  An empty ``x`` or ``y`` gives no edges in the absolute
     form and is an error in the quantile form."""
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
     k = _as_int(k, "k")
     thresh, is_q = _thresh_args(thresh_p, threshold)
     return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_jaccard_cross_edges_long_begin(
@@ -638,7 +631,6 @@ def similarityJaccard_cross_edges_long(x, y, k=4, thresh_p=0.8, *, threshold=Non
 def similarityJaccard_stats_long(sequences, k=4):
     """``compute_similarity_stats(similarityJaccard_long(sequences, k))`` without the matrix on the host (da_similarity_jaccard_stats_long):
     one pass of the rectangle kernel in row blocks, on 32-bit value ranks.  Empty sequences are legal (two empty sets are 1.0)."""
-    import ctypes
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
@@ -650,7 +642,6 @@ def similarityJaccard_stats_long(sequences, k=4):
 def nw_code_ranks(max_len=127):
     """(ranks uint16[65536], distinct): the dense value rank of every NW code (matches << 8 | length) sequences up to max_len residues
     can produce -- what similarityNW_cross_topk selects on (da_nw_code_ranks).  Needs no device."""
-    import ctypes
     out = np.zeros(65536, np.uint16)
     d = ctypes.c_int(0)
     _capi.check(_capi.load().da_nw_code_ranks(int(max_len), out.ctypes.data, ctypes.addressof(d)))
@@ -661,7 +652,6 @@ def nw_value_ranks(max_len=1024):
     """(values float64[D], rank uint32[2 * max_len + 1, max_len + 1]): the distinct values ``matches / length`` that sequences of up to max_len
     (1 .. 1024) residues can produce, ascending, and ``rank[length, matches]``, the dense rank of that value -- what the *_edges_long calls
     order and threshold on (da_nw_value_ranks).  Equal doubles share a rank (128/256 and 150/300); rank 0 is the value 0.0.  Needs no device."""
-    import ctypes
     lib = _capi.load()
     ml = int(max_len)
     d = ctypes.c_int64(0)
@@ -683,7 +673,7 @@ def nw_pairs(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, row_begi
     mt = np.zeros((max(r, 1), max(n, 1)), np.int32)
     ln = np.zeros_like(mt)
     sc = np.zeros_like(mt)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     _capi.check(lib.da_nw_pairs(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"),
                                 _as_int(gapExt, "gapExt"), row_begin, row_end, mt.ctypes.data, ln.ctypes.data,
                                 sc.ctypes.data))
@@ -731,9 +721,7 @@ def nw_align_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, *, pairs=No
 def _nw_align_call(entry, ld_cap, x, y, matrixName, gapOpen, gapExt, pairs, ops):
     """nw_align / nw_align_long: marshal, call ``entry``, cut the ops rows into strings.  ld_cap: upper bound of the ops row length."""
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
     if pairs is None:
         if m != n:
             raise ValueError("without pairs, x and y must have the same length (got %d and %d)" % (m, n))
@@ -756,7 +744,7 @@ def _nw_align_call(entry, ld_cap, x, y, matrixName, gapOpen, gapExt, pairs, ops)
     ln = np.zeros(max(count, 1), np.int32)
     mt = np.zeros_like(ln)
     sc = np.zeros_like(ln)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     _capi.check(getattr(lib, entry)(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, _capi.ptr(px), _capi.ptr(py), count,
                                     name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), _capi.ptr(buf), ld, ln.ctypes.data,
                                     mt.ctypes.data, sc.ctypes.data))
@@ -815,7 +803,6 @@ def similarityMH_edges(sequences, k=4, n_hash=50, thresh_p=0.8, *, seed=None):
 
 def _edges_one_pass(begin):
     """*_edges_begin -> da_edges_fetch -> da_edges_free: the pipeline runs once (the size-query form runs it twice)"""
-    import ctypes
     lib = _capi.load()
     handle = ctypes.c_void_p()
     thr = np.zeros(1, np.float64)
@@ -834,26 +821,23 @@ def similarityNW_edges(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, t
     """similarityNW followed by clusterbreak's threshold step (reference R/clusterbreak.R:217-221), fused on
     the device like similarityMH_edges: returns ``(threshold, i, j, weight)`` for the surviving entries with
     i <= j (0-based, sorted).  Sequences up to 127 residues; empty sequences are refused (NaN similarities)."""
+    return _nw_edges("da_similarity_nw_edges_begin", sequences, matrixName, gapOpen, gapExt, thresh_p)
+
+
+def _nw_edges(entry, sequences, matrixName, gapOpen, gapExt, thresh_p):
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
-    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_edges_begin(
-        res.ctypes.data, off.ctypes.data, n, name, go, ge, float(thresh_p), h, thr, cnt))
+    return _edges_one_pass(lambda h, thr, cnt: getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, name, go, ge, float(thresh_p), h, thr, cnt))
 
 
 def similarityNW_edges_long(sequences, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8):
     """``similarityNW_edges`` for sequences of 1 .. 1024 residues (da_similarity_nw_edges_long_begin): the same arguments, the same result,
     the same errors.  The device thresholds 32-bit value ranks (``nw_value_ranks``) of the packed (matches, length) pairs; the dense matrix
     never exists.  ``clusterbreak(pep, edges_fn=lambda s: similarityNW_edges_long(s, thresh_p=0.8), thresh_p=0.8)`` clusters with it."""
-    lib = _capi.load()
-    res, off = pack_sequences(sequences)
-    n = len(off) - 1
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
-    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
-    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_edges_long_begin(
-        res.ctypes.data, off.ctypes.data, n, name, go, ge, float(thresh_p), h, thr, cnt))
+    return _nw_edges("da_similarity_nw_edges_long_begin", sequences, matrixName, gapOpen, gapExt, thresh_p)
 
 
 def _thresh_args(thresh_p, threshold):
@@ -868,9 +852,7 @@ def similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, *, threshold=No
     ``weight`` bit for bit ``R[i, j]``.  ``threshold=None``: the threshold is R's type-7 ``quantile(as.vector(R), thresh_p)`` over all
     m * n entries; a ``threshold`` that is not None is taken as it is (a range query: every y within that similarity of each x) and
     ``thresh_p`` is unused.  Errors as similarityMH_cross, then ``thresh_p`` outside [0, 1] / a NaN threshold."""
-    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
-    yr, yo = pack_sequences(y)
-    n = len(yo) - 1
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
     thresh, is_q = _thresh_args(thresh_p, threshold)
     return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_mh_cross_edges_begin(
         xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data, thresh, is_q, h, thr, cnt))
@@ -886,19 +868,10 @@ def similarityMH_lsh_edges(sequences, k=4, n_hash=50, bands=10, rows=5, threshol
     threshold that agrees in no whole band is missing (``lsh_collision_probability`` says how likely).  ``max_candidates`` caps the
     (pair, band) incidences, which are known before any pair is compared: more raises DA_ERR_UNSUPPORTED."""
     lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
-    import ctypes
-    handle = ctypes.c_void_p()
-    cnt = np.zeros(1, np.int64)
-    _capi.check(lib.da_similarity_mh_lsh_edges_begin(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, _as_int(bands, "bands"),
-                                                     _as_int(rows, "rows"), float(threshold), int(max_candidates), ctypes.addressof(handle),
-                                                     cnt.ctypes.data))
-    try:
-        m = int(cnt[0])
-        ei, ej, ew = np.empty(max(m, 1), np.int32), np.empty(max(m, 1), np.int32), np.empty(max(m, 1), np.float64)
-        _capi.check(lib.da_edges_fetch(handle, m, ei.ctypes.data, ej.ctypes.data, ew.ctypes.data))
-    finally:
-        lib.da_edges_free(handle)
-    return float(threshold), ei[:m], ej[:m], ew[:m]
+    bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
+    _thr, ei, ej, ew = _edges_one_pass(lambda h, _t, cnt: lib.da_similarity_mh_lsh_edges_begin(
+        res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, bands, rows, float(threshold), int(max_candidates), h, cnt))
+    return float(threshold), ei, ej, ew
 
 
 def mh_lsh_last_route():
@@ -1024,9 +997,7 @@ def similarityMH_lsh_cross_edges(x, y, k=4, n_hash=50, bands=10, rows=5, thresho
     definition's relation to ``similarityMH_cross_edges(x, y, threshold=threshold)``: a pair that agrees in no whole band is missing
     (``1 - lsh_collision_probability`` says how likely).  y is bucketed once (an index of its sorted band keys), x looks its keys up;
     ``MinHashSession.lsh_cross_edges`` keeps that index between calls.  ``max_candidates`` caps the (pair, band) incidences."""
-    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
-    yr, yo = pack_sequences(y)
-    n = len(yo) - 1
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
     bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
     thr, ei, ej, ew = _edges_one_pass(lambda h, _thr, cnt: lib.da_similarity_mh_lsh_cross_edges_begin(
         xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data, bands, rows, float(threshold),
@@ -1040,9 +1011,7 @@ def similarityMH_lsh_cross_topk(x, y, k=4, n_hash=50, bands=10, rows=5, top=10, 
     ascending; a row with fewer candidates is padded with ``idx = -1, val = 0.0`` and ``val > 0`` marks exactly the real entries.  ``top``
     is in 1 .. 1024 and is NOT clamped to len(y).  Exactly ``lsh_cross_topk_dense`` of the two signature matrices; with ``rows = 1, bands =
     n_hash`` the lists equal similarityMH_cross_topk's wherever its value is > 0.  ``max_candidates`` as in similarityMH_lsh_cross_edges."""
-    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
-    yr, yo = pack_sequences(y)
-    n = len(yo) - 1
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
     top = _as_int(top, "top")
     shape = (max(m, 1), min(max(top, 1), 1024))
     idx = np.empty(shape, np.int32)
@@ -1132,7 +1101,7 @@ def similarityNW_lsh_edges(sequences, k=4, n_hash=50, bands=10, rows=5, threshol
     mixed freely; pass distinct strings.  Nothing returns to the host between bucketing and the final list.  Errors: the matrix name, then
     those of similarityMH_lsh_edges, then invalid residues, an empty sequence, one over 1024 residues, then the two thresholds."""
     lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
     bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
     _thr, ei, ej, ew = _edges_one_pass(lambda h, _t, cnt: lib.da_similarity_nw_lsh_edges_begin(
@@ -1146,10 +1115,8 @@ def similarityNW_lsh_cross_edges(x, y, k=4, n_hash=50, bands=10, rows=5, thresho
     """The two-set form of ``similarityNW_lsh_edges``: the candidates of ``similarityMH_lsh_cross_edges(x, y, ..., mh_threshold)``, each
     aligned with x[i] as sequence1 and y[j] as sequence2, kept when ``w >= threshold and w > 0``.  No diagonal.  Exactly
     ``nw_lsh_cross_edges_dense`` of the two signature matrices and the reference's pair value."""
-    lib, xr, xo, m, k, n_hash, seeds = _mh_prelude(x, k, n_hash, seed)
-    yr, yo = pack_sequences(y)
-    n = len(yo) - 1
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
+    name = _matrix_name(matrixName)
     go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
     bands, rows = _as_int(bands, "bands"), _as_int(rows, "rows")
     _thr, ei, ej, ew = _edges_one_pass(lambda h, _t, cnt: lib.da_similarity_nw_lsh_cross_edges_begin(
@@ -1194,29 +1161,23 @@ def similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, 
     similarityMH_cross_edges.  Equal similarities pass or fail together whatever their (matches, length): 2/4 and 3/6 are both 0.5.
     Every sequence has 1 .. 127 residues (an empty one is refused: a NaN has no place in a quantile).  An empty ``x`` or ``y`` gives no
     edges in the absolute form and is an error in the quantile form (an empty set has no quantile)."""
+    return _nw_cross_edges("da_similarity_nw_cross_edges_begin", x, y, matrixName, gapOpen, gapExt, thresh_p, threshold)
+
+
+def _nw_cross_edges(entry, x, y, matrixName, gapOpen, gapExt, thresh_p, threshold):
     lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
+    name = _matrix_name(matrixName)
     go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
     thresh, is_q = _thresh_args(thresh_p, threshold)
-    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_cross_edges_begin(
+    return _edges_one_pass(lambda h, thr, cnt: getattr(lib, entry)(
         xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name, go, ge, thresh, is_q, h, thr, cnt))
 
 
 def similarityNW_cross_edges_long(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, *, threshold=None):
     """``similarityNW_cross_edges`` for sequences of 1 .. 1024 residues (da_similarity_nw_cross_edges_long_begin): the same arguments, the
     same result, the same errors."""
-    lib = _capi.load()
-    xr, xo = pack_sequences(x)
-    yr, yo = pack_sequences(y)
-    m, n = len(xo) - 1, len(yo) - 1
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
-    go, ge = _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt")
-    thresh, is_q = _thresh_args(thresh_p, threshold)
-    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_nw_cross_edges_long_begin(
-        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, name, go, ge, thresh, is_q, h, thr, cnt))
+    return _nw_cross_edges("da_similarity_nw_cross_edges_long_begin", x, y, matrixName, gapOpen, gapExt, thresh_p, threshold)
 
 
 # ---- summary statistics (reference R/similarity.R:11-34) --------------------------------------------------------------------------------------
@@ -1333,7 +1294,6 @@ def similarityMH_stats(sequences, k=4, n_hash=50, *, seed=None):
     """``compute_similarity_stats(similarityMH(sequences, k, n_hash, seed=seed))`` without the matrix on the host: the uint16 counts stay on
     the device, a histogram of the strict upper triangle gives mean, median, min and max, and one more pass gives every row's extremes
     with their first columns, from which the positions follow (da_similarity_mh_stats).  Errors as similarityMH_edges."""
-    import ctypes
     lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
     s = _capi.DaSimilarityStats()
     _capi.check(lib.da_similarity_mh_stats(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, ctypes.addressof(s)))
@@ -1341,11 +1301,10 @@ def similarityMH_stats(sequences, k=4, n_hash=50, *, seed=None):
 
 
 def _nw_stats(entry, sequences, matrixName, gapOpen, gapExt):
-    import ctypes
     lib = _capi.load()
     res, off = pack_sequences(sequences)
     n = len(off) - 1
-    name = matrixName.encode("latin-1") if isinstance(matrixName, str) else bytes(matrixName)
+    name = _matrix_name(matrixName)
     s = _capi.DaSimilarityStats()
     _capi.check(getattr(lib, entry)(res.ctypes.data, off.ctypes.data, n, name, _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"),
                                     ctypes.addressof(s)))
