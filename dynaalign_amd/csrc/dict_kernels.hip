@@ -19,6 +19,7 @@
 //                     copy, in the blocked order k_mh_compare stages them in (da_common.hpp)
 //   k_sig_to_planes : raw 32-plane operand from sig (n > DA_DICT_MAX_N, or dictionary overflow)
 #include "da_common.hpp"
+#include "scan.hpp"
 #include <atomic>
 
 namespace da {
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(DK_THREADS) void k_dictionary(const uint32_t *__res
   __shared__ uint32_t wsum[NW];
   __shared__ uint32_t cnt[NW][DK_MAX_PARTS];      // keys of partition p seen by wave w, then its write cursor
   __shared__ uint32_t pbase[DK_MAX_PARTS + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, wave = tid >> 6;
   const uint32_t *col = sigT + (int64_t)blockIdx.x * ldT;
   uint32_t *sz = szT + (int64_t)blockIdx.x * ldT;
   uint32_t *si = siT + (int64_t)blockIdx.x * ldT;
@@ -138,20 +139,8 @@ __global__ __launch_bounds__(DK_THREADS) void k_dictionary(const uint32_t *__res
     // number the repeated keys of this partition: base + exclusive scan over the slots
     uint32_t mine = 0;
     for (int s = tid; s < DK_SLOTS; s += DK_THREADS) mine += vals[s];
-    uint32_t incl = mine;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-    for (int w = 0; w < NW; ++w) {
-      const uint32_t v = wsum[w];
-      if (w < wave) before += v;
-      total += v;
-    }
-    uint32_t next = base + before + incl - mine;
+    uint32_t total;
+    uint32_t next = base + wg_excl_scan<NW>(mine, wsum, &total);
     for (int s = tid; s < DK_SLOTS; s += DK_THREADS) {
       if (keys[s] == EMPTY) continue;
       vals[s] = vals[s] ? (uint16_t)(next++) : (uint16_t)0xFFFFu;
@@ -236,16 +225,7 @@ __global__ __launch_bounds__(1024) void k_hy_split(const uint16_t *__restrict__ 
   for (int c = c_lo; c < c_hi; ++c) { const uint32_t m = hy_hist[c]; f1 += m >= t; f2 += ties && m == t - 1; }
   part[tid] = (f1 << 16) | f2;                       // f1 sums stay <= keep < 2^16, f2 sums <= max_ids <= 2^15
   __syncthreads();
-  if (tid < 64) {                                    // exclusive scan of the 1024 packed partial sums by one wave (16 each)
-    uint32_t v[16], tot = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { v[q] = part[tid * 16 + q]; tot += v[q]; }
-    uint32_t incl = tot;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if (tid >= o) incl += up; }
-    uint32_t run = incl - tot;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { part[tid * 16 + q] = run; run += v[q]; }
-  }
+  wave_scan_1024(part);                              // (the packed sums: no carry between the halves)
   __syncthreads();
   uint32_t p1 = part[tid] >> 16, p2 = part[tid] & 0xffffu;
   unsigned long long e = 0, mx = 0, e_all = 0, mx_all = 0;

@@ -6,10 +6,10 @@
 // the long NW code matches << 16 | length, so the value ranks of da_nw_value_ranks(S), S the call's largest shingle count, order it.
 //
 // k_jaccard_sets_long<Key>: one workgroup of 256 threads per sequence.  The keys of its np <= 1024 positions go to LDS, padded with all-ones
-//   keys to the next power of two P; a workgroup bitonic sort of the P keys; the pad keys are not told apart by their value -- FF FF FF FF
+//   keys to the next power of two P; a workgroup bitonic sort of the P keys (wg_bitonic_sort, scan.hpp); the pad keys are not told apart by their value -- FF FF FF FF
 //   is a legal shingle -- but by their place: whatever ties with them, the first np sorted keys are the sequence's own.  A key of [0, np) is
-//   kept when it differs from its left neighbour, and a workgroup scan of the kept flags (four positions per thread, a wave scan, the four
-//   wave totals) gives its slot: the ascending distinct keys at keys[seq * ld_keys + 0 .. count), the row's tail zeroed, counts[seq].
+//   kept when it differs from its left neighbour, and a workgroup scan of the kept flags (four positions per thread; wg_excl_scan: a wave scan,
+//   the four wave totals) gives its slot: the ascending distinct keys at keys[seq * ld_keys + 0 .. count), the row's tail zeroed, counts[seq].
 // k_jaccard_rect_long<Key, KIND>: rows [row_begin, row_end) x columns [col_begin, col_end) of ONE resident set operand in 64 x 64 tiles, four
 //   waves.  The tile's rows are taken in batches of JL_R = 8: the workgroup stages the batch's lists in LDS ([row][slot], only the count of
 //   every list), then each wave takes every fourth column of the tile, reads that column's list from global memory in coalesced chunks of 64
@@ -25,6 +25,7 @@
 //   No atomics, no scratch, every element of the rectangle written exactly once, nothing outside it touched.
 #include "da_common.hpp"
 #include "jaccard_common.hpp"
+#include "scan.hpp"
 
 namespace da {
 namespace {
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(JL_THREADS) void k_jaccard_sets_long(const uint8_t 
                                                                   Key *__restrict__ keys, int ld_keys, uint16_t *__restrict__ counts) {
   __shared__ Key sk[JL_MAX_SHINGLES];
   __shared__ int swave[JL_WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t s = blockIdx.x;                                          // the grid is n workgroups
   const int64_t b0 = off[s];
   const int64_t len = off[s + 1] - b0;
@@ -60,16 +61,7 @@ __global__ __launch_bounds__(JL_THREADS) void k_jaccard_sets_long(const uint8_t 
     sk[q] = v;
   }
   __syncthreads();
-  for (int k2 = 2; k2 <= P; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (P >> 1); t += JL_THREADS) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const Key a = sk[i], b = sk[l];
-        const bool up = (i & k2) == 0;
-        if ((a > b) == up) { sk[i] = b; sk[l] = a; }
-      }
-      __syncthreads();
-    }
+  wg_bitonic_sort<false, JL_THREADS>(sk, P);
   // positions 4 * tid .. 4 * tid + 3: kept when inside [0, np) and different from the left neighbour
   Key mine[JL_PER];
   bool keep[JL_PER];
@@ -81,21 +73,8 @@ __global__ __launch_bounds__(JL_THREADS) void k_jaccard_sets_long(const uint8_t 
     keep[e] = p < np && (p == 0 || sk[p - 1] != mine[e]);
     cnt += keep[e] ? 1 : 0;
   }
-  int inc = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int v = __shfl_up(inc, d);
-    if (lane >= d) inc += v;
-  }
-  if (lane == 63) swave[wave] = inc;
-  __syncthreads();
-  int slot = inc - cnt, total = 0;
-#pragma unroll
-  for (int w = 0; w < JL_WAVES; ++w) {
-    const int t = swave[w];
-    slot += w < wave ? t : 0;
-    total += t;
-  }
+  int total;
+  int slot = wg_excl_scan<JL_WAVES>(cnt, swave, &total);
   Key *row = keys + s * (int64_t)ld_keys;
 #pragma unroll
   for (int e = 0; e < JL_PER; ++e)

@@ -25,6 +25,7 @@
 // can be tested on triples the pipeline never produces (a key collision, a pair of an earlier band).
 #include "components_common.hpp"
 #include "lsh_common.hpp"
+#include "scan.hpp"
 
 namespace da {
 namespace {
@@ -497,21 +498,6 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_short(const long
   }
 }
 
-// bitonic sort, ascending, of buf[0 .. p2) (p2 a power of two) by the whole workgroup; ends with a barrier
-__device__ __forceinline__ void lsh_knn_sort_lds(unsigned long long *buf, int p2) {
-  for (int k = 2; k <= p2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int a = threadIdx.x; a < p2; a += LSH_THREADS) {
-        const int o = a ^ j;
-        if (o > a) {
-          const unsigned long long x = buf[a], y = buf[o];
-          if ((x > y) == ((a & k) == 0)) { buf[a] = y; buf[o] = x; }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long long *__restrict__ ptr, int64_t nnz, const int32_t *__restrict__ col,
                                                                      const uint16_t *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
                                                                      int64_t ld_idx, uint16_t *__restrict__ key, int64_t ld_key) {
@@ -520,7 +506,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long 
   __shared__ unsigned int wtot[LSH_THREADS / 64];
   __shared__ int long_rows[LSH_KNN_TILE];
   __shared__ unsigned int ctl[5];                 // long rows of the tile; the digit's bin, the entries below it, those in it; the compaction cursor
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int64_t tiles = (n + LSH_KNN_TILE - 1) / LSH_KNN_TILE;
   for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     if (tid == 0) ctl[0] = 0;
@@ -571,15 +557,8 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long 
           }
           __syncthreads();
           const unsigned int h = hist[tid];
-          unsigned int incl = h;
-          for (int o = 1; o < 64; o <<= 1) {
-            const unsigned int v = (unsigned int)__shfl_up((int)incl, o);
-            if (lane >= o) incl += v;
-          }
-          if (lane == 63) wtot[wave] = incl;
-          __syncthreads();
-          unsigned int excl = incl - h;
-          for (int w2 = 0; w2 < wave; ++w2) excl += wtot[w2];
+          unsigned int all;
+          const unsigned int excl = wg_excl_scan<LSH_THREADS / 64>(h, wtot, &all);
           if (h && excl < need && need <= excl + h) { ctl[1] = (unsigned int)tid; ctl[2] = excl; ctl[3] = h; }   // one bin holds the need-th entry
           __syncthreads();
           const unsigned int bin = ctl[1], below = ctl[2], inbin = ctl[3];
@@ -604,7 +583,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long 
       while (p2 < have) p2 <<= 1;
       for (int a = have + tid; a < p2; a += LSH_THREADS) buf[a] = ~0ull;
       __syncthreads();
-      lsh_knn_sort_lds(buf, p2);
+      wg_bitonic_sort<false, LSH_THREADS>(buf, p2);
       const int real = min(have, top);
       for (int t = tid; t < top; t += LSH_THREADS) lsh_knn_put(t < real ? buf[t] : 0ull, t < real, idx + r * ld_idx + t, key + r * ld_key + t);
       __syncthreads();                            // the buffer and the control words are the next row's

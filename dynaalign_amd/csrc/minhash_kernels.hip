@@ -8,6 +8,7 @@
 // Written for CDNA4 only: 64-wide wavefronts, 160 KiB LDS, 8 XCDs.  Integer
 // work; no MFMA (an equality count is not a contraction).
 #include "da_common.hpp"
+#include "scan.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -2004,68 +2005,14 @@ __global__ __launch_bounds__(256) void k_es_count(const int32_t *__restrict__ ui
   if (i < n) atomicAdd(&cnt[(i / Z) * U + uidx[i]], 1u);
 }
 // exclusive scans over the K = zones * U keys of cnt[] (-> cstart: where the positions of a key start) and of ceil(cnt / ES_COPIES) (-> zstart:
-// its work items), both sums in the halves of a 64-bit word, in three steps: block sums, their scan by one workgroup, the scan inside every
-// block; cstart[K] = n, zstart[K] = number of items
-__device__ __forceinline__ uint64_t es_scan_load(const uint32_t *__restrict__ cnt, int K, int i) {
-  const uint32_t c = i < K ? cnt[i] : 0u;
-  return (uint64_t)c | ((uint64_t)((c + ES_COPIES - 1) / ES_COPIES) << 32);
-}
-__global__ __launch_bounds__(1024) void k_es_scan_sums(const uint32_t *__restrict__ cnt, int K, uint64_t *__restrict__ bsum) {
-  __shared__ uint64_t wsum[16];
-  uint64_t x = es_scan_load(cnt, K, blockIdx.x * 1024 + threadIdx.x);
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) { uint64_t t = 0; for (int w = 0; w < 16; ++w) t += wsum[w]; bsum[blockIdx.x] = t; }
-}
-__global__ __launch_bounds__(1024) void k_es_scan_offsets(uint64_t *__restrict__ bsum, int nblocks) {   // in place: exclusive scan; bsum[nblocks] = total
-  __shared__ uint64_t wsum[16];
-  __shared__ uint64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int i = base + tid;
-    const uint64_t v = i < nblocks ? bsum[i] : 0;
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const uint64_t carry = carry_s;
-    if (i < nblocks) bsum[i] = carry + woff + x - v;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) bsum[nblocks] = carry_s;
-}
-__global__ __launch_bounds__(1024) void k_es_scan_apply(const uint32_t *__restrict__ cnt, int K, const uint64_t *__restrict__ bsum,
-                                                        uint32_t *__restrict__ cstart, uint32_t *__restrict__ zstart) {
-  __shared__ uint64_t wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blockIdx.x * 1024 + tid;
-  const uint64_t v = es_scan_load(cnt, K, i);
-  uint64_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint64_t woff = bsum[blockIdx.x];
-  for (int w = 0; w < wave; ++w) woff += wsum[w];
-  const uint64_t e = woff + x - v;
-  if (i < K) { cstart[i] = (uint32_t)e; zstart[i] = (uint32_t)(e >> 32); }
-  if (blockIdx.x == gridDim.x - 1 && tid == 0) { const uint64_t t = bsum[gridDim.x]; cstart[K] = (uint32_t)t; zstart[K] = (uint32_t)(t >> 32); }
-}
+// its work items), both sums in the halves of a 64-bit word, by the three launches of launch_scan (scan.hpp); cstart[K] = n, zstart[K] = number of items
+struct EsCountScan {
+  const uint32_t *cnt;
+  uint32_t *cstart, *zstart;
+  __device__ __forceinline__ uint64_t load(int32_t i) const { const uint32_t c = cnt[i]; return (uint64_t)c | ((uint64_t)((c + ES_COPIES - 1) / ES_COPIES) << 32); }
+  __device__ __forceinline__ void store(int32_t i, uint64_t e) const { cstart[i] = (uint32_t)e; zstart[i] = (uint32_t)(e >> 32); }
+  __device__ __forceinline__ void store_total(int32_t K, uint64_t t) const { store(K, t); }
+};
 // positions of every key's copies (any order inside a key: the copies receive identical values) and the item lists: (id, first copy of the key)
 __global__ __launch_bounds__(256) void k_es_fill(const int32_t *__restrict__ uidx, int n, int U, int Z, int K, const uint32_t *__restrict__ cstart,
                                                  const uint32_t *__restrict__ zstart, uint32_t *__restrict__ cursor, int32_t *__restrict__ cpos,
@@ -2271,11 +2218,8 @@ static int es_lists(const int32_t *d_uidx, int64_t n, int64_t U, void *d_scratch
   const EsLists L = es_layout(d_scratch, n, U, zones);
   const int zero_words = 2 * L.K + ES_ZONES;                            // cnt, cursor, ticket
   hipLaunchKernelGGL(k_es_zero, dim3((unsigned)ceil_div(zero_words, 256)), dim3(256), 0, stream, L.cnt, zero_words);
-  const unsigned nblk = (unsigned)ceil_div(L.K, 1024);
   hipLaunchKernelGGL(k_es_count, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, d_uidx, (int)n, (int)U, L.Z, L.cnt);
-  hipLaunchKernelGGL(k_es_scan_sums, dim3(nblk), dim3(1024), 0, stream, L.cnt, L.K, L.bsum);
-  hipLaunchKernelGGL(k_es_scan_offsets, dim3(1), dim3(1024), 0, stream, L.bsum, (int)nblk);
-  hipLaunchKernelGGL(k_es_scan_apply, dim3(nblk), dim3(1024), 0, stream, L.cnt, L.K, L.bsum, L.cstart, L.zstart);
+  launch_scan(EsCountScan{L.cnt, L.cstart, L.zstart}, L.K, 0, L.bsum, stream);     // (always wide: K = zones x U keys)
   hipLaunchKernelGGL(k_es_fill, dim3((unsigned)ceil_div(std::max<int64_t>(n, L.K), 256)), dim3(256), 0, stream, d_uidx, (int)n, (int)U, L.Z, L.K,
                      L.cstart, L.zstart, L.cursor, L.cpos, L.items);
   DA_HIP_TRY(hipGetLastError());
@@ -2716,16 +2660,7 @@ __global__ __launch_bounds__(1024) void k_sp_classes(const uint16_t *__restrict_
   for (int c = lo; c < hi; ++c) sum += sp_hist[c];
   part[threadIdx.x] = sum;
   __syncthreads();
-  if (threadIdx.x < 64) {                      // exclusive scan of the 1024 partial sums by one wave (16 each)
-    uint32_t v[16], tot = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { v[q] = part[threadIdx.x * 16 + q]; tot += v[q]; }
-    uint32_t incl = tot;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if ((int)threadIdx.x >= o) incl += up; }
-    uint32_t run = incl - tot;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { part[threadIdx.x * 16 + q] = run; run += v[q]; }
-  }
+  wave_scan_1024(part);
   __syncthreads();
   uint32_t run = part[threadIdx.x];
   for (int c = lo; c < hi; ++c) { const uint32_t v = sp_hist[c]; cs[c] = run; sp_hist[c] = run; run += v; }
@@ -2785,7 +2720,7 @@ __global__ __launch_bounds__(1024) void k_sp_scan(uint32_t *__restrict__ cnt, ui
   for (int64_t t = lo; t < hi; ++t) s += cnt[t];
   part[threadIdx.x] = s;
   __syncthreads();
-  if (threadIdx.x == 0) { uint32_t run = 0; for (int k = 0; k < 1024; ++k) { const uint32_t v = part[k]; part[k] = run; run += v; } }
+  wave_scan_1024(part);
   __syncthreads();
   uint32_t run = part[threadIdx.x];
   for (int64_t t = lo; t < hi; ++t) { const uint32_t v = cnt[t]; start[t] = run; cnt[t] = 0; run += v; }
@@ -2808,16 +2743,7 @@ __global__ __launch_bounds__(1024) void k_sp_band(const uint32_t *__restrict__ b
     for (int q = 0; q < 4; ++q) if (v[q] != 0xffffffffu) atomicAdd(&hist[(v[q] & 0x1ffffu) >> 7], 1u);
   }
   __syncthreads();
-  if (threadIdx.x < 64) {                      // exclusive scan of the 1024 counters by one wave (16 each)
-    uint32_t v[16], tot = 0;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { v[q] = hist[threadIdx.x * 16 + q]; tot += v[q]; }
-    uint32_t incl = tot;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if ((int)threadIdx.x >= o) incl += up; }
-    uint32_t run = incl - tot;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) { hist[threadIdx.x * 16 + q] = run; run += v[q]; }
-  }
+  wave_scan_1024(hist);
   __syncthreads();
   const int tj = threadIdx.x;
   if (tj >= ti && tj < T) start[sp_tile_index(ti, tj, T)] = lo + hist[tj];

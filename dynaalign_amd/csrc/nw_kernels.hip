@@ -31,6 +31,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "da_common.hpp"
+#include "scan.hpp"
 
 namespace da {
 namespace {
@@ -654,143 +655,26 @@ __global__ __launch_bounds__(256) void k_dd_flags(const int32_t *__restrict__ re
   fm[i] = (is_rep && mult[i] > 1) ? 1 : 0;
   fs[i] = (is_rep && mult[i] == 1) ? 1 : 0;
 }
-// exclusive prefix sum of n int32 by ONE workgroup (n is ~1e5: not worth more); out[n] = total (int64 output type OUT)
-template <typename OUT>
-__global__ __launch_bounds__(1024) void k_dd_scan(const int32_t *__restrict__ in, OUT *__restrict__ out, int32_t n) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int32_t base = 0; base < n; base += 1024) {
-    const int32_t i = base + tid;
-    const int64_t v = i < n ? in[i] : 0;
-    int64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int64_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int64_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const int64_t carry = carry_s;
-    if (i < n) out[i] = (OUT)(carry + woff + x - v);
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) out[n] = (OUT)carry_s;
-}
-// the two flag arrays of the plan (multi-copy / single-copy representatives) scanned in ONE pass of one workgroup: the counts ride in
-// the two halves of a 64-bit word (n < 2^31), so the cost is that of a single scan (0.14 ms at n = 100k, twice that as two launches)
-__global__ __launch_bounds__(1024) void k_dd_scan_pair(const int32_t *__restrict__ fm, const int32_t *__restrict__ fs, int32_t *__restrict__ pm,
-                                                       int32_t *__restrict__ ps, int32_t n) {
-  __shared__ uint64_t wsum[16];
-  __shared__ uint64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int32_t base = 0; base < n; base += 1024) {
-    const int32_t i = base + tid;
-    const uint64_t v = i < n ? ((uint64_t)(uint32_t)fm[i] | ((uint64_t)(uint32_t)fs[i] << 32)) : 0;
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const uint64_t carry = carry_s;
-    if (i < n) {
-      const uint64_t e = carry + woff + x - v;
-      pm[i] = (int32_t)(uint32_t)e;
-      ps[i] = (int32_t)(uint32_t)(e >> 32);
-    }
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) { pm[n] = (int32_t)(uint32_t)carry_s; ps[n] = (int32_t)(uint32_t)(carry_s >> 32); }
-}
-// The same two scans over many workgroups (n >= 8192): block sums, a scan of the block sums by one workgroup, then every block's own exclusive scan plus
-// its offset -- three short launches (~0.03 ms) instead of one workgroup walking the whole array (0.15 ms at n = 100k: the plan sits in front of everything).
-// MODE 0: (fm, fs) -> (pm, ps) packed in 64 bits;  MODE 1: in (int32) -> out (int64)
-template <int MODE>
-__device__ __forceinline__ uint64_t dd_scan_load(const int32_t *a, const int32_t *b, int32_t i) {
-  if (MODE == 0) return (uint64_t)(uint32_t)a[i] | ((uint64_t)(uint32_t)b[i] << 32);
-  return (uint64_t)(int64_t)a[i];
-}
-template <int MODE>
-__global__ __launch_bounds__(1024) void k_dd_scan_sums(const int32_t *__restrict__ a, const int32_t *__restrict__ b, int32_t n, uint64_t *__restrict__ bsum) {
-  __shared__ uint64_t wsum[16];
-  const int32_t i = blockIdx.x * 1024 + threadIdx.x;
-  uint64_t x = i < n ? dd_scan_load<MODE>(a, b, i) : 0;
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = x;
-  __syncthreads();
-  if (threadIdx.x == 0) { uint64_t t = 0; for (int w = 0; w < 16; ++w) t += wsum[w]; bsum[blockIdx.x] = t; }
-}
-__global__ __launch_bounds__(1024) void k_dd_scan_offsets(uint64_t *__restrict__ bsum, int32_t nblocks) {   // in place: exclusive scan; bsum[nblocks] = total
-  __shared__ uint64_t wsum[16];
-  __shared__ uint64_t carry_s;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid == 0) carry_s = 0;
-  __syncthreads();
-  for (int32_t base = 0; base < nblocks; base += 1024) {
-    const int32_t i = base + tid;
-    const uint64_t v = i < nblocks ? bsum[i] : 0;
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    uint64_t woff = 0;
-    for (int w = 0; w < wave; ++w) woff += wsum[w];
-    const uint64_t carry = carry_s;
-    if (i < nblocks) bsum[i] = carry + woff + x - v;
-    __syncthreads();
-    if (tid == 1023) carry_s = carry + woff + x;
-    __syncthreads();
-  }
-  if (tid == 0) bsum[nblocks] = carry_s;
-}
-template <int MODE>
-__global__ __launch_bounds__(1024) void k_dd_scan_apply(const int32_t *__restrict__ a, const int32_t *__restrict__ b, int32_t n, const uint64_t *__restrict__ bsum,
-                                                        int32_t *__restrict__ o0, int32_t *__restrict__ o1, int64_t *__restrict__ o64) {
-  __shared__ uint64_t wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int32_t i = blockIdx.x * 1024 + tid;
-  const uint64_t v = i < n ? dd_scan_load<MODE>(a, b, i) : 0;
-  uint64_t x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint64_t woff = bsum[blockIdx.x];
-  for (int w = 0; w < wave; ++w) woff += wsum[w];
-  const uint64_t e = woff + x - v;
-  if (i < n) {
-    if (MODE == 0) { o0[i] = (int32_t)(uint32_t)e; o1[i] = (int32_t)(uint32_t)(e >> 32); }
-    else o64[i] = (int64_t)e;
-  }
-  if (blockIdx.x == gridDim.x - 1 && tid == 0) {
-    const uint64_t t = bsum[gridDim.x];
-    if (MODE == 0) { o0[n] = (int32_t)(uint32_t)t; o1[n] = (int32_t)(uint32_t)(t >> 32); }
-    else o64[n] = (int64_t)t;
-  }
-}
+// The plan's two exclusive scans (launch_scan, scan.hpp).  Below DD_SCAN_WIDE elements one workgroup walks the array (0.14 ms at n = 100k); from there
+// on the three short launches (~0.03 ms) run: the plan sits in front of everything.
+// The flag arrays (multi-copy / single-copy representatives) are scanned in ONE pass: the counts ride in the two halves of a 64-bit word
+// (n < 2^31), so the cost is that of a single scan.  pm[n], ps[n] = the totals.
+struct DdFlagsScan {
+  const int32_t *fm, *fs;
+  int32_t *pm, *ps;
+  __device__ __forceinline__ uint64_t load(int32_t i) const { return (uint64_t)(uint32_t)fm[i] | ((uint64_t)(uint32_t)fs[i] << 32); }
+  __device__ __forceinline__ void store(int32_t i, uint64_t e) const { pm[i] = (int32_t)(uint32_t)e; ps[i] = (int32_t)(uint32_t)(e >> 32); }
+  __device__ __forceinline__ void store_total(int32_t n, uint64_t t) const { store(n, t); }
+};
+// the unique strings' lengths -> their offsets (int64), uoff[U] = the total
+struct DdLengthScan {
+  const int32_t *ulen;
+  int64_t *uoff;
+  __device__ __forceinline__ uint64_t load(int32_t i) const { return (uint64_t)(int64_t)ulen[i]; }
+  __device__ __forceinline__ void store(int32_t i, uint64_t e) const { uoff[i] = (int64_t)e; }
+  __device__ __forceinline__ void store_total(int32_t U, uint64_t t) const { store(U, t); }
+};
+constexpr int64_t DD_SCAN_WIDE = 8192;
 // The unique ids (DedupOrder, da_common.hpp).  M = pm[n] multi-copy strings, pm[i] / ps[i] = multi- / single-copy representatives before row i.
 //   multi_first  multi-copy strings pm[i], single-copy ones M + ps[i]
 //   first        pm[i] + ps[i]: one numbering by first occurrence (rows [0, R) of the input only use ids < pm[R] + ps[R])
@@ -884,15 +768,8 @@ int launch_nw_dedup_count(const uint8_t *d_codes, const int64_t *d_off, int64_t 
   hipLaunchKernelGGL(k_dd_insert, dim3(nb), dim3(256), 0, stream, d_codes, d_off, (int32_t)n, p.table, p.table_size - 1);
   hipLaunchKernelGGL(k_dd_lookup, dim3(nb), dim3(256), 0, stream, d_codes, d_off, (int32_t)n, p.table, p.table_size - 1, p.rep, p.mult, p.last);
   hipLaunchKernelGGL(k_dd_flags, dim3(nb), dim3(256), 0, stream, p.rep, p.mult, (int32_t)n, p.fm, p.fs);
-  const bool wide_scan = true;
-  if (n >= 8192 && wide_scan) {     // (the hash table is free again after k_dd_lookup: its words hold the block sums)
-    const int32_t nblk = (int32_t)ceil_div(n, 1024);
-    uint64_t *bsum = reinterpret_cast<uint64_t *>(p.table);
-    hipLaunchKernelGGL(k_dd_scan_sums<0>, dim3((unsigned)nblk), dim3(1024), 0, stream, p.fm, p.fs, (int32_t)n, bsum);
-    hipLaunchKernelGGL(k_dd_scan_offsets, dim3(1), dim3(1024), 0, stream, bsum, nblk);
-    hipLaunchKernelGGL(k_dd_scan_apply<0>, dim3((unsigned)nblk), dim3(1024), 0, stream, p.fm, p.fs, (int32_t)n, bsum, p.pm, p.ps, (int64_t *)nullptr);
-  } else
-    hipLaunchKernelGGL(k_dd_scan_pair, dim3(1), dim3(1024), 0, stream, p.fm, p.fs, p.pm, p.ps, (int32_t)n);
+  // (the hash table is free again after k_dd_lookup: its words hold the block sums)
+  launch_scan(DdFlagsScan{p.fm, p.fs, p.pm, p.ps}, n, DD_SCAN_WIDE, reinterpret_cast<uint64_t *>(p.table), stream);
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }
@@ -904,15 +781,7 @@ int launch_nw_dedup_build(const uint8_t *d_codes, const int64_t *d_off, int64_t 
   hipLaunchKernelGGL(k_dd_assign, dim3(nb), dim3(256), 0, stream, p.rep, p.mult, p.last, p.pm, p.ps, d_off, (int32_t)n, p.uid_of,
                      p.ufirst, p.ulast, p.ulen, (int)order, zones, (int32_t)zone_rows(n, zones));
   hipLaunchKernelGGL(k_dd_map, dim3(nb), dim3(256), 0, stream, p.rep, p.uid_of, (int32_t)n, p.uidx);
-  if (U >= 8192) {
-    const int32_t nblk = (int32_t)ceil_div(U, 1024);
-    uint64_t *bsum = reinterpret_cast<uint64_t *>(p.table);
-    hipLaunchKernelGGL(k_dd_scan_sums<1>, dim3((unsigned)nblk), dim3(1024), 0, stream, p.ulen, (const int32_t *)nullptr, (int32_t)U, bsum);
-    hipLaunchKernelGGL(k_dd_scan_offsets, dim3(1), dim3(1024), 0, stream, bsum, nblk);
-    hipLaunchKernelGGL(k_dd_scan_apply<1>, dim3((unsigned)nblk), dim3(1024), 0, stream, p.ulen, (const int32_t *)nullptr, (int32_t)U, bsum, (int32_t *)nullptr,
-                       (int32_t *)nullptr, p.uoff);
-  } else
-    hipLaunchKernelGGL(k_dd_scan<int64_t>, dim3(1), dim3(1024), 0, stream, p.ulen, p.uoff, (int32_t)U);
+  launch_scan(DdLengthScan{p.ulen, p.uoff}, U, DD_SCAN_WIDE, reinterpret_cast<uint64_t *>(p.table), stream);
   hipLaunchKernelGGL(k_dd_gather, dim3((unsigned)ceil_div(U, 256)), dim3(256), 0, stream, d_codes, d_off, p.ufirst, p.uoff, (int32_t)U, p.ucodes);
   hipLaunchKernelGGL(k_dd_blocks, dim3((unsigned)ceil_div(U, 64)), dim3(64), 0, stream, p.ufirst, p.ulast, (int32_t)U, p.minfirst, p.maxlast);
   DA_HIP_TRY(hipGetLastError());

@@ -6,7 +6,7 @@
 // host) a rectangle has independent rows and nothing to skip, so the list is produced in its final order:
 //   1. k_rect_histogram (quantile form only): the histogram of the whole block, for the host's type-7 quantile;
 //   2. k_threshold_count: per row, the number of kept keys; an exclusive scan of those (hipcub) gives the row pointers;
-//   3. k_threshold_emit: ordered compaction.  The workgroup that owns a row walks it in chunks, scans the per-thread kept counts of a chunk,
+//   3. k_threshold_emit: ordered compaction.  The workgroup that owns a row walks it in chunks, scans the per-thread kept counts of a chunk (wg_excl_scan, scan.hpp),
 //      carries a running base from chunk to chunk, and every thread writes its own contiguous run of slots.  No output atomic, no sort: the
 //      slot of an entry depends on the data alone.
 // Rows of up to 1024 keys take one wave each (k_topk_rows' rule): four times as many rows in flight per CU as with 256 threads.
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(THREADS) void k_threshold_emit(const Key *__restric
   constexpr int WAVES = THREADS / 64;
   constexpr int CHUNK = THREADS * PER;
   __shared__ unsigned int wtot[2][WAVES];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   long long base = rowptr[blockIdx.x];
   if (rowptr[blockIdx.x + 1] == base || base >= capacity) return;   // block-uniform: a row without an edge is not read again
   const Key *row = keys + (int64_t)blockIdx.x * ld;
@@ -167,18 +167,10 @@ __global__ __launch_bounds__(THREADS) void k_threshold_emit(const Key *__restric
     const int nv = KeyRow<Key>::load(row, j0, n, vec, k);
     const uint32_t mask = keep.mask(k, nv, j0, first);
     const uint32_t mine = (uint32_t)__popc(mask);
-    const uint32_t incl = wave_incl_scan(mine);
-    if (lane == 63) wtot[buf][wave] = incl;
-    __syncthreads();                           // the other buffer is written next time: one barrier per chunk
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      const uint32_t t = wtot[buf][w];
-      if (w < wave) before += t;
-      total += t;
-    }
+    uint32_t total;
+    const uint32_t pre = wg_excl_scan<WAVES>(mine, wtot[buf], &total);   // the other buffer is written next time: one barrier per chunk
     if (mine) {
-      long long slot = base + before + incl - mine;
+      long long slot = base + pre;
 #pragma unroll
       for (int e = 0; e < PER; ++e) {
         if (!(mask & (1u << e))) continue;

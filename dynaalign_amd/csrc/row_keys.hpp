@@ -7,18 +7,9 @@
 
 #include <cstdint>
 
-namespace da {
+#include "scan.hpp"
 
-// lanes below `lane` summed: inclusive wave scan by shuffles
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
+namespace da {
 
 // KeyRow<Key>::PER: keys per thread per chunk.  load(row, j0, n, vec, k): k[e] = key of column j0 + e of the row for e < nv (the return
 // value: how many of the columns [j0, j0 + PER) are < n), 0 beyond; vec: the row starts on a 16-byte boundary.

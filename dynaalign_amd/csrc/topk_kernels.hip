@@ -9,8 +9,8 @@
 //   1. radix select on the rank, two 8-bit digits (the top 8 of rank_bits, then the rest): a 256-bin LDS histogram each, read from the top
 //      by one wave -> T, the rank of the top-th element, and `above`, the number of elements above T;
 //   2. ordered compaction: every element above T, and the first top - above elements equal to T in column order -- a workgroup prefix scan
-//      per chunk of the row, so the choice among equals does not depend on scheduling;
-//   3. the <= top candidates, as 64-bit words rank : ~column : key, sorted in LDS (bitonic) and stored.
+//      per chunk of the row (wg_excl_scan, scan.hpp), so the choice among equals does not depend on scheduling;
+//   3. the <= top candidates, as 64-bit words rank : ~column : key, sorted in LDS (wg_bitonic_sort, scan.hpp) and stored.
 // The row is read three times (the second and third time from L2 / MALL); rank 0 -- by far the commonest: unrelated peptides share no
 // k-mer -- is counted in a register, not with 64 lanes on one LDS word (k_upper_histogram does the same).
 //
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
   __shared__ unsigned long long cand[DA_TOPK_MAX];
   __shared__ unsigned int wtot[2][WAVES];
   __shared__ unsigned int sel[4];             // bin, above (high digit), bin, above (low digit)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const uint16_t *row = keys + (int64_t)blockIdx.x * ld;
   const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
   const uint32_t lo_mask = (1u << shift) - 1u;
@@ -124,17 +124,8 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
 #pragma unroll
     for (int e = 0; e < TK_PER; ++e)
       if (e < nv && !(SELF && own - j0 == e)) mine += r[e] > T ? 1u : (r[e] == T ? 0x10000u : 0u);
-    const uint32_t incl = wave_incl_scan(mine);
-    if (lane == 63) wtot[buf][wave] = incl;
-    __syncthreads();                           // the other buffer is written next time: one barrier per chunk
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      const uint32_t t = wtot[buf][w];
-      if (w < wave) before += t;
-      total += t;
-    }
-    uint32_t pre = before + incl - mine;
+    uint32_t total;
+    const uint32_t pre = wg_excl_scan<WAVES>(mine, wtot[buf], &total);   // the other buffer is written next time: one barrier per chunk
     uint32_t gt_at = gt_run + (pre & 0xFFFFu), eq_at = eq_run + (pre >> 16);
     if (mine) {
 #pragma unroll
@@ -160,16 +151,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_rows(const uint16_t *__restric
   __syncthreads();
   for (int s = top + tid; s < P; s += THREADS) cand[s] = 0;     // below every candidate (~column is never 0)
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (P >> 1); t += THREADS) {
-        const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
-        const bool desc = (i & size) == 0;
-        const unsigned long long a = cand[i], b = cand[j];
-        if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
-      }
-      __syncthreads();
-    }
+  wg_bitonic_sort<true, THREADS>(cand, P);
   for (int t = tid; t < top; t += THREADS) {
     const unsigned long long w = cand[t];
     idx[(int64_t)blockIdx.x * ld_idx + t] = (int32_t)(~(uint32_t)(w >> 16));
@@ -192,7 +174,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_ranks(const uint32_t *__restri
   __shared__ unsigned long long cand[DA_TOPK_MAX];
   __shared__ unsigned int wtot[2][WAVES];
   __shared__ unsigned int sel[2];             // bin, above of the digit at hand
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const uint32_t *row = keys + (int64_t)blockIdx.x * ld;
   const bool vec = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
   uint32_t r[PER];
@@ -243,17 +225,8 @@ __global__ __launch_bounds__(THREADS) void k_topk_ranks(const uint32_t *__restri
       r[e] = r[e] < rmax ? r[e] : rmax;
       if (e < nv && !(SELF && own - j0 == e)) mine += r[e] > T ? 1u : (r[e] == T ? 0x10000u : 0u);
     }
-    const uint32_t incl = wave_incl_scan(mine);
-    if (lane == 63) wtot[buf][wave] = incl;
-    __syncthreads();                           // the other buffer is written next time: one barrier per chunk
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      const uint32_t t = wtot[buf][w];
-      if (w < wave) before += t;
-      total += t;
-    }
-    uint32_t pre = before + incl - mine;
+    uint32_t total;
+    const uint32_t pre = wg_excl_scan<WAVES>(mine, wtot[buf], &total);   // the other buffer is written next time: one barrier per chunk
     uint32_t gt_at = gt_run + (pre & 0xFFFFu), eq_at = eq_run + (pre >> 16);
     if (mine) {
 #pragma unroll
@@ -279,16 +252,7 @@ __global__ __launch_bounds__(THREADS) void k_topk_ranks(const uint32_t *__restri
   __syncthreads();
   for (int s = top + tid; s < P; s += THREADS) cand[s] = 0;     // below every candidate (~column is never 0)
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < (P >> 1); t += THREADS) {
-        const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
-        const bool desc = (i & size) == 0;
-        const unsigned long long a = cand[i], b = cand[j];
-        if ((a < b) == desc) { cand[i] = b; cand[j] = a; }
-      }
-      __syncthreads();
-    }
+  wg_bitonic_sort<true, THREADS>(cand, P);
   for (int t = tid; t < top; t += THREADS) {
     const unsigned long long w = cand[t];
     idx[(int64_t)blockIdx.x * ld_idx + t] = (int32_t)(~(uint32_t)w);
