@@ -31,6 +31,7 @@ from .similarity import (  # noqa: F401
     similarityMH_lsh_cross_edges, similarityMH_lsh_cross_topk, lsh_cross_edges_dense, lsh_cross_topk_dense,
     similarityMH_lsh_components, lsh_components_dense,
     similarityNW_lsh_edges, similarityNW_lsh_cross_edges, nw_lsh_edges_dense, nw_lsh_cross_edges_dense, nw_lsh_last_route,
+    similarityNW_lsh_knn, similarityNW_lsh_knn_edges, similarityNW_lsh_cross_topk, nw_lsh_knn_dense, nw_lsh_cross_topk_dense,
 )
 
 __all__ = [
@@ -47,5 +48,6 @@ __all__ = [
     "similarityMH_lsh_cross_edges", "similarityMH_lsh_cross_topk", "lsh_cross_edges_dense", "lsh_cross_topk_dense",
     "components", "components_dense", "components_device", "similarityMH_lsh_components", "lsh_components_dense",
     "similarityNW_lsh_edges", "similarityNW_lsh_cross_edges", "nw_lsh_edges_dense", "nw_lsh_cross_edges_dense", "nw_lsh_last_route",
+    "similarityNW_lsh_knn", "similarityNW_lsh_knn_edges", "similarityNW_lsh_cross_topk", "nw_lsh_knn_dense", "nw_lsh_cross_topk_dense",
     "pack_sequences", "set_option", "get_option", "SimilarityMatrix", "DynaAlignError", "load_library",
 ]

@@ -3777,7 +3777,8 @@ LshRoute &lsh_route() { static thread_local LshRoute r; return r; }
 
 // bands, rows, threshold and the cap of the LSH calls, in the order include/dynaalign.h gives
 // (top: of the nearest-neighbour calls, checked between the cap and the 16-bit limit; nullptr for the edge calls)
-int lsh_arg_check(int n_hash, int bands, int rows, double threshold, int64_t max_candidates, const int *top = nullptr) {
+// (edge_text: the 16-bit limit in the edge calls' words although top is given -- the NW lists, which take the edge calls' checks and texts)
+int lsh_arg_check(int n_hash, int bands, int rows, double threshold, int64_t max_candidates, const int *top = nullptr, bool edge_text = false) {
   if (bands < 1) return fail(DA_ERR_BAD_ARG, "bands must be >= 1 (got %d)", bands);
   if (rows < 1) return fail(DA_ERR_BAD_ARG, "rows must be >= 1 (got %d)", rows);
   if ((int64_t)bands * rows > n_hash) return fail(DA_ERR_BAD_ARG, "bands * rows = %lld exceeds n_hash = %d", (long long)bands * rows, n_hash);
@@ -3785,7 +3786,7 @@ int lsh_arg_check(int n_hash, int bands, int rows, double threshold, int64_t max
   if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
   if (top && (*top < 1 || *top > DA_TOPK_MAX)) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. %d (got %d)", DA_TOPK_MAX, *top);
   if (n_hash > 65535)
-    return fail(DA_ERR_UNSUPPORTED, "the LSH %s in 16 bits: n_hash <= 65535 (got %d)", top ? "nearest-neighbour lists count" : "edge list counts", n_hash);
+    return fail(DA_ERR_UNSUPPORTED, "the LSH %s in 16 bits: n_hash <= 65535 (got %d)", top && !edge_text ? "nearest-neighbour lists count" : "edge list counts", n_hash);
   return DA_OK;
 }
 // the smallest count whose similarity -- the divide of mh_code_values -- reaches the threshold (n_hash + 1: none does)
@@ -4163,13 +4164,13 @@ int lsh_index_device(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int bands
 // what both two-set LSH host calls check before a device is needed: x empty, y empty, k, n_hash, pointers, the offsets of x, then of y, the banding
 int lsh_cross_host_validate(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets, int64_t n,
                             int k, int n_hash, const uint32_t *seeds, const void *out1, const void *out2, int bands, int rows, double threshold,
-                            int64_t max_candidates, const int *top, int64_t *x_total, int64_t *y_total) {
+                            int64_t max_candidates, const int *top, int64_t *x_total, int64_t *y_total, bool edge_text = false) {
   int rc;
   if ((rc = validate_mh(m, k > 0 ? k : 1, n_hash > 0 ? n_hash : 1)) != DA_OK || (rc = validate_mh(n, k, n_hash)) != DA_OK) return rc;   // x empty, y empty, k, n_hash
   if (!x_residues || !y_residues || !seeds || !out1 || !out2) return fail(DA_ERR_BAD_ARG, "NULL pointer");
   int64_t max_len;
   if ((rc = check_offsets(x_offsets, m, x_total, &max_len)) != DA_OK || (rc = check_offsets(y_offsets, n, y_total, &max_len)) != DA_OK) return rc;
-  return lsh_arg_check(n_hash, bands, rows, threshold, max_candidates, top);
+  return lsh_arg_check(n_hash, bands, rows, threshold, max_candidates, top, edge_text);
 }
 // The host calls' device side up to the index: both sets uploaded, their signatures, the index of y and the probe workspace.
 struct LshCrossHost {
@@ -4352,41 +4353,60 @@ struct NwlSeqs {
   const uint8_t *x_codes; const int64_t *x_off; int64_t m;
   const uint8_t *y_codes; const int64_t *y_off; int64_t n;
 };
-// The pipeline on resident signatures and resident encoded sequences: the candidates of lsh_edges_device at mh_threshold, their
-// (matches, length), the verdicts, and the kept entries -- the first min(capacity, kept) of them -- in d_i / d_j / d_matches / d_length.
+// The candidates of lsh_edges_device at mh_threshold and their (matches, length), what the edge list and the lists share: the sorted list
+// unpacked into ci / cj, the rescore into mt / ln (cand entries each).  Sets the route's counts; a refused candidate fails the call.
+struct NwlScored {
+  DevBuf key, val, work, ci, cj, mt, ln;                    // key / val / work: read by launches still in flight when lsh_nw_scored returns
+  int64_t cand = 0;
+};
+int lsh_nw_scored(const LshSets &s, const NwlSeqs &q, double mh_threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int matrix_id,
+                  int gap_open, int gap_ext, NwlScored &sc, hipStream_t stream) {
+  int rc;
+  DevBuf &key = sc.key, &work = sc.work;
+  NwLshRoute &route = nw_lsh_route();
+  route = NwLshRoute();
+  if ((rc = lsh_edges_device(s, mh_threshold, max_candidates, d_work, work_bytes, key, sc.val, &sc.cand, stream)) != DA_OK) return rc;
+  const LshRoute &lr = lsh_route();
+  route.buckets = lr.buckets; route.incidences = lr.incidences; route.verified = lr.verified; route.aligned = sc.cand;
+  const int64_t cand = sc.cand;
+  if (cand == 0) return DA_OK;
+  const size_t ib = (size_t)cand * sizeof(int32_t);
+  // the decision words of the short pairs in flight: what the budget (DYNAALIGN_BLOCK_BYTES, or half of the free memory) leaves, one wavefront at least
+  const size_t fixed_b = nw_rescore_fixed_bytes(cand), full_b = nw_rescore_workspace_bytes(cand, false), min_b = nw_rescore_workspace_bytes(cand, true);
+  const size_t wb = std::max(min_b, std::min(full_b, fixed_b + block_budget()));
+  if ((rc = sc.ci.alloc(ib)) != DA_OK || (rc = sc.cj.alloc(ib)) != DA_OK || (rc = sc.mt.alloc(ib)) != DA_OK || (rc = sc.ln.alloc(ib)) != DA_OK ||
+      (rc = work.alloc(wb)) != DA_OK) return rc;
+  if ((rc = launch_nwl_split(key.as<uint64_t>(), cand, sc.ci.as<int32_t>(), sc.cj.as<int32_t>(), stream)) != DA_OK) return rc;
+  int64_t counts[3] = {0, 0, 0};
+  if ((rc = launch_nw_rescore(q.x_codes, q.x_off, q.m, q.y_codes, q.y_off, q.n, sc.ci.as<int32_t>(), sc.cj.as<int32_t>(), cand, matrix_id, gap_open, gap_ext,
+                              sc.mt.as<int32_t>(), sc.ln.as<int32_t>(), work.p, wb, counts, stream)) != DA_OK) return rc;
+  route.shorts = counts[0]; route.longs = counts[1];
+  if (counts[2] > 0)
+    return fail(DA_ERR_UNSUPPORTED, "nw lsh: %lld candidate pairs have an empty sequence or one over 1024 residues", (long long)counts[2]);
+  return DA_OK;
+}
+// The edge pipeline on resident signatures and resident encoded sequences: the scored candidates, the verdicts, and the kept entries -- the
+// first min(capacity, kept) of them -- in d_i / d_j / d_matches / d_length.
 // own: four buffers to allocate for the whole list instead (the host entries).  Synchronises the stream.
 int lsh_nw_edges_device(const LshSets &s, const NwlSeqs &q, double mh_threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int matrix_id,
                         int gap_open, int gap_ext, double threshold, int32_t *d_i, int32_t *d_j, int32_t *d_matches, int32_t *d_length, int64_t capacity,
                         int64_t *n_edges_out, hipStream_t stream, DevBuf *own = nullptr) {
   int rc;
-  DevBuf key, val, ci, cj, mt, ln, keep, ckept, coff, temp, table, work;
+  NwlScored sc;
+  DevBuf keep, ckept, coff, temp, table;
   const StreamDrain drain{stream};
   NwLshRoute &route = nw_lsh_route();
-  route = NwLshRoute();
-  int64_t cand = 0;
-  if ((rc = lsh_edges_device(s, mh_threshold, max_candidates, d_work, work_bytes, key, val, &cand, stream)) != DA_OK) return rc;
-  const LshRoute &lr = lsh_route();
-  route.buckets = lr.buckets; route.incidences = lr.incidences; route.verified = lr.verified; route.aligned = cand;
   *n_edges_out = 0;
+  if ((rc = lsh_nw_scored(s, q, mh_threshold, max_candidates, d_work, work_bytes, matrix_id, gap_open, gap_ext, sc, stream)) != DA_OK) return rc;
+  const int64_t cand = sc.cand;
   if (cand == 0) return DA_OK;
   const std::vector<int32_t> min_matches = nwl_min_matches(threshold);
   const int64_t chunks = ceil_div(cand, 64);
-  const size_t ib = (size_t)cand * sizeof(int32_t), scan_b = nwl_keep_scan_bytes(cand);
-  // the decision words of the short pairs in flight: what the budget (DYNAALIGN_BLOCK_BYTES, or half of the free memory) leaves, one wavefront at least
-  const size_t fixed_b = nw_rescore_fixed_bytes(cand), full_b = nw_rescore_workspace_bytes(cand, false), min_b = nw_rescore_workspace_bytes(cand, true);
-  const size_t wb = std::max(min_b, std::min(full_b, fixed_b + block_budget()));
-  if ((rc = ci.alloc(ib)) != DA_OK || (rc = cj.alloc(ib)) != DA_OK || (rc = mt.alloc(ib)) != DA_OK || (rc = ln.alloc(ib)) != DA_OK ||
-      (rc = keep.alloc((size_t)cand)) != DA_OK || (rc = ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
-      (rc = temp.alloc(scan_b)) != DA_OK || (rc = table.alloc((size_t)NWL_TABLE_LEN * sizeof(int32_t))) != DA_OK || (rc = work.alloc(wb)) != DA_OK) return rc;
+  const size_t scan_b = nwl_keep_scan_bytes(cand);
+  if ((rc = keep.alloc((size_t)cand)) != DA_OK || (rc = ckept.alloc((size_t)(chunks + 1) * 8)) != DA_OK || (rc = coff.alloc((size_t)(chunks + 1) * 8)) != DA_OK ||
+      (rc = temp.alloc(scan_b)) != DA_OK || (rc = table.alloc((size_t)NWL_TABLE_LEN * sizeof(int32_t))) != DA_OK) return rc;
   DA_HIP_TRY(hipMemcpy(table.p, min_matches.data(), (size_t)NWL_TABLE_LEN * sizeof(int32_t), hipMemcpyHostToDevice));
-  if ((rc = launch_nwl_split(key.as<uint64_t>(), cand, ci.as<int32_t>(), cj.as<int32_t>(), stream)) != DA_OK) return rc;
-  int64_t counts[3] = {0, 0, 0};
-  if ((rc = launch_nw_rescore(q.x_codes, q.x_off, q.m, q.y_codes, q.y_off, q.n, ci.as<int32_t>(), cj.as<int32_t>(), cand, matrix_id, gap_open, gap_ext,
-                              mt.as<int32_t>(), ln.as<int32_t>(), work.p, wb, counts, stream)) != DA_OK) return rc;
-  route.shorts = counts[0]; route.longs = counts[1];
-  if (counts[2] > 0)
-    return fail(DA_ERR_UNSUPPORTED, "nw lsh: %lld candidate pairs have an empty sequence or one over 1024 residues", (long long)counts[2]);
-  if ((rc = launch_nwl_keep(mt.as<int32_t>(), ln.as<int32_t>(), cand, table.as<int32_t>(), NWL_TABLE_LEN, keep.as<uint8_t>(), ckept.as<int64_t>(),
+  if ((rc = launch_nwl_keep(sc.mt.as<int32_t>(), sc.ln.as<int32_t>(), cand, table.as<int32_t>(), NWL_TABLE_LEN, keep.as<uint8_t>(), ckept.as<int64_t>(),
                             coff.as<int64_t>(), temp.p, scan_b, stream)) != DA_OK) return rc;
   int64_t kept = 0;
   DA_HIP_TRY(hipMemcpyAsync(&kept, coff.as<int64_t>() + chunks, 8, hipMemcpyDeviceToHost, stream));
@@ -4397,7 +4417,7 @@ int lsh_nw_edges_device(const LshSets &s, const NwlSeqs &q, double mh_threshold,
     d_i = own[0].as<int32_t>(); d_j = own[1].as<int32_t>(); d_matches = own[2].as<int32_t>(); d_length = own[3].as<int32_t>();
     capacity = kept;
   }
-  if ((rc = launch_nwl_emit(ci.as<int32_t>(), cj.as<int32_t>(), mt.as<int32_t>(), ln.as<int32_t>(), keep.as<uint8_t>(), coff.as<int64_t>(), cand,
+  if ((rc = launch_nwl_emit(sc.ci.as<int32_t>(), sc.cj.as<int32_t>(), sc.mt.as<int32_t>(), sc.ln.as<int32_t>(), keep.as<uint8_t>(), coff.as<int64_t>(), cand,
                             std::min(capacity, kept), d_i, d_j, d_matches, d_length, stream)) != DA_OK) return rc;
   DA_HIP_TRY(hipStreamSynchronize(stream));
   route.edges = kept;
@@ -4915,6 +4935,202 @@ int da_similarity_nw_cross_topk_long(const uint8_t *x_residues, const int64_t *x
     return c.rows(b0, b1, DA_OUT_PACK32, d, ld, nullptr);
   }, nullptr);
   return rank_topk_to_host(keys, m, top, false, idx_out, val_out, nullptr);
+}
+
+// ---- NW-ranked nearest-neighbour lists on MinHash LSH candidates: the scored candidates of lsh_nw_scored, ordered by value rank ----------------
+}  // extern "C"  (reopened below)
+namespace {
+// kept: value >= threshold and value > 0, as in RankKeys::set_threshold
+uint32_t nwl_r_min(const std::vector<double> &values, double threshold) {
+  return (uint32_t)std::max<int64_t>(std::lower_bound(values.begin(), values.end(), threshold) - values.begin(), 1);
+}
+// The list pipeline on resident signatures and resident encoded sequences: the scored candidates, their value ranks and keep bytes (one
+// set: the diagonal into d_diag_key), the ragged rows -- both directions of every kept pair of one set, the x rows of two sets -- and the
+// selection into d_idx / d_key ((m, top), leading dimension top).  Synchronises the stream (totals are read back).
+int lsh_nw_lists_device(const LshSets &s, const NwlSeqs &q, double mh_threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int matrix_id,
+                        int gap_open, int gap_ext, uint32_t r_min, int top, const uint32_t *d_rank, int max_len, int32_t *d_idx, uint32_t *d_key,
+                        uint32_t *d_diag_key, hipStream_t stream) {
+  int rc;
+  NwlScored sc;
+  DevBuf rkey, keep, totals, cursor, ptr, col, val, written, temp;
+  const StreamDrain drain{stream};
+  const bool both = !s.d_index;
+  const int64_t m = s.m;
+  if ((rc = lsh_nw_scored(s, q, mh_threshold, max_candidates, d_work, work_bytes, matrix_id, gap_open, gap_ext, sc, stream)) != DA_OK) return rc;
+  const int64_t cand = sc.cand;
+  if ((rc = rkey.alloc((size_t)cand * sizeof(uint32_t))) != DA_OK || (rc = keep.alloc((size_t)cand)) != DA_OK || (rc = totals.alloc(16)) != DA_OK) return rc;
+  if (both) DA_HIP_TRY(hipMemsetAsync(d_diag_key, 0, (size_t)m * sizeof(uint32_t), stream));
+  if ((rc = launch_nwl_rank_keys(sc.ci.as<int32_t>(), sc.cj.as<int32_t>(), sc.mt.as<int32_t>(), sc.ln.as<int32_t>(), cand, d_rank, max_len, r_min, both, m,
+                                 rkey.as<uint32_t>(), keep.as<uint8_t>(), d_diag_key, totals.as<uint64_t>(), stream)) != DA_OK) return rc;
+  uint64_t tot[2] = {0, 0};
+  DA_HIP_TRY(hipMemcpyAsync(tot, totals.p, 16, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  if (tot[1] > 0)
+    return fail(DA_ERR_UNSUPPORTED, "nw lsh: %llu candidate pairs have no rank: refused by the alignment kernels, or longer than the table's max_len = %d",
+                (unsigned long long)tot[1], max_len);
+  const int64_t entries = (int64_t)(both ? 2 * tot[0] : tot[0]);
+  const size_t scan_b = lsh_knn_scan_bytes(m);
+  if ((rc = cursor.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = ptr.alloc((size_t)(m + 1) * 8)) != DA_OK || (rc = col.alloc((size_t)entries * 4)) != DA_OK ||
+      (rc = val.alloc((size_t)entries * 4)) != DA_OK || (rc = written.alloc(8)) != DA_OK || (rc = temp.alloc(scan_b)) != DA_OK) return rc;
+  if ((rc = launch_nw_knn_entries(sc.ci.as<int32_t>(), sc.cj.as<int32_t>(), cand, rkey.as<uint32_t>(), keep.as<uint8_t>(), m, both, entries, top,
+                                  cursor.as<int64_t>(), ptr.as<int64_t>(), col.as<int32_t>(), val.as<uint32_t>(), written.as<uint64_t>(), temp.p, scan_b,
+                                  stream)) != DA_OK ||
+      (rc = launch_nw_knn_select(ptr.as<int64_t>(), entries, col.as<int32_t>(), val.as<uint32_t>(), m, top, d_idx, top, d_key, top, stream)) != DA_OK)
+    return rc;
+  uint64_t entries_written = 0;
+  DA_HIP_TRY(hipMemcpyAsync(&entries_written, written.p, 8, hipMemcpyDeviceToHost, stream));
+  DA_HIP_TRY(hipStreamSynchronize(stream));
+  nw_lsh_route().edges = (int64_t)entries_written;
+  return DA_OK;
+}
+// what the device list entries check behind the LSH checks
+int lsh_nw_lists_dev_check(const NwlSeqs &q, int matrix_id, double threshold, const uint32_t *d_rank, int max_len, const void *d_work, const void *d_idx,
+                           const void *d_key, const void *d_diag_key, bool one_set) {
+  if (!q.x_codes || !q.x_off || !q.y_codes || !q.y_off) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (!matrix_table_host(matrix_id)) return fail(DA_ERR_BAD_ARG, "matrix id %d out of range", matrix_id);
+  if (!(threshold >= 0.0 && threshold <= 1.0)) return fail(DA_ERR_BAD_ARG, "threshold must be in [0, 1]");
+  if (max_len < 1 || max_len > 1024) return fail(DA_ERR_BAD_ARG, "max_len must be in 1 .. 1024 (got %d)", max_len);
+  if (!d_rank || !d_work || !d_idx || !d_key || (one_set && !d_diag_key)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return DA_OK;
+}
+// a host entry behind its checks: the rank table of the call's longest sequence on the device, the pipeline, idx as it is and
+// val = values[rank] -- the library's divide bit for bit, as in rank_topk_to_host
+int lsh_nw_lists_to_host(const LshSets &s, const NwlSeqs &q, double mh_threshold, int64_t max_candidates, void *d_work, size_t work_bytes, int matrix_id,
+                         int gap_open, int gap_ext, double threshold, int top, int max_len, int32_t *idx_out, double *val_out, double *diag_out) {
+  int rc;
+  const auto table = nw_value_table(max_len);
+  const std::vector<double> &values = table->values;
+  const int64_t m = s.m;
+  const size_t cnt = (size_t)m * (size_t)top;
+  const bool one_set = !s.d_index;
+  DevBuf drank, didx, dkey, ddiag;
+  if ((rc = drank.alloc(table->rank.size() * sizeof(uint32_t))) != DA_OK || (rc = didx.alloc(cnt * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc(cnt * sizeof(uint32_t))) != DA_OK || (rc = ddiag.alloc((size_t)m * sizeof(uint32_t))) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(drank.p, table->rank.data(), table->rank.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if ((rc = lsh_nw_lists_device(s, q, mh_threshold, max_candidates, d_work, work_bytes, matrix_id, gap_open, gap_ext, nwl_r_min(values, threshold), top,
+                                drank.as<uint32_t>(), max_len, didx.as<int32_t>(), dkey.as<uint32_t>(), ddiag.as<uint32_t>(), nullptr)) != DA_OK) return rc;
+  DA_HIP_TRY(hipMemcpy(idx_out, didx.p, cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> rk;
+  if (val_out) {
+    rk.resize(cnt);
+    DA_HIP_TRY(hipMemcpy(rk.data(), dkey.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < cnt; ++e) val_out[e] = values[std::min<size_t>(rk[e], values.size() - 1)];
+  }
+  if (one_set && diag_out) {
+    rk.resize((size_t)m);
+    DA_HIP_TRY(hipMemcpy(rk.data(), ddiag.p, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < m; ++i) diag_out[i] = values[std::min<size_t>(rk[(size_t)i], values.size() - 1)];
+  }
+  return DA_OK;
+}
+}  // namespace
+extern "C" {
+
+int da_dev_nw_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint32_t *d_rank_key, int64_t n, int top, int32_t *d_idx,
+                         int64_t ld_idx, uint32_t *d_key, int64_t ld_key, void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (top < 1 || top > DA_TOPK_MAX) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. %d (got %d)", DA_TOPK_MAX, top);
+  if (nnz < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  if (ld_idx < top || ld_key < top) return fail(DA_ERR_BAD_ARG, "ld (%lld) < top (%d)", (long long)std::min(ld_idx, ld_key), top);
+  if (!d_ptr || !d_idx || !d_key || (nnz > 0 && (!d_col || !d_rank_key))) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_nw_knn_select(d_ptr, nnz, d_col, d_rank_key, n, top, d_idx, ld_idx, d_key, ld_key, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_nw_rank_keys(const int32_t *d_i, const int32_t *d_j, const int32_t *d_matches, const int32_t *d_length, int64_t pairs, const uint32_t *d_rank,
+                        int max_len, uint32_t r_min, int one_set, int64_t n, uint32_t *d_key, uint8_t *d_keep, uint32_t *d_diag_key, uint64_t *d_totals,
+                        void *stream) {
+  if (pairs < 0 || n < 0) return fail(DA_ERR_BAD_ARG, "negative count");
+  if (max_len < 1 || max_len > 1024) return fail(DA_ERR_BAD_ARG, "max_len must be in 1 .. 1024 (got %d)", max_len);
+  if (!d_rank || !d_totals || (one_set && n > 0 && !d_diag_key)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  if (pairs > 0 && (!d_i || !d_j || !d_matches || !d_length || !d_key || !d_keep)) return fail(DA_ERR_BAD_ARG, "NULL device pointer");
+  return launch_nwl_rank_keys(d_i, d_j, d_matches, d_length, pairs, d_rank, max_len, r_min, one_set != 0, n, d_key, d_keep, d_diag_key, d_totals,
+                              static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_nw_knn(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double mh_threshold, int64_t max_candidates,
+                      const uint8_t *d_codes, const int64_t *d_offsets, int matrix_id, int gap_open, int gap_ext, double threshold, int top,
+                      const uint32_t *d_rank, int max_len, void *d_work, size_t work_bytes, int32_t *d_idx, uint32_t *d_key, uint32_t *d_diag_key,
+                      void *stream) {
+  int rc;
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if ((rc = lsh_dev_check(d_sig, n, ld_sig, n_hash, bands, rows, mh_threshold)) != DA_OK) return rc;
+  if (max_candidates < 0) return fail(DA_ERR_BAD_ARG, "max_candidates must be >= 0 (got %lld)", (long long)max_candidates);
+  if (top < 1 || top > DA_TOPK_MAX) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. %d (got %d)", DA_TOPK_MAX, top);
+  const NwlSeqs q{d_codes, d_offsets, n, d_codes, d_offsets, n};
+  if ((rc = lsh_nw_lists_dev_check(q, matrix_id, threshold, d_rank, max_len, d_work, d_idx, d_key, d_diag_key, true)) != DA_OK) return rc;
+  return lsh_nw_lists_device(lsh_one_set(d_sig, n, ld_sig, n_hash, bands, rows), q, mh_threshold, max_candidates, d_work, work_bytes, matrix_id, gap_open,
+                             gap_ext, nwl_r_min(nw_value_table(max_len)->values, threshold), top, d_rank, max_len, d_idx, d_key, d_diag_key,
+                             static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lsh_cross_nw_topk(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x, const uint32_t *d_sig_y, int64_t n,
+                             int64_t ld_y, int n_hash, int bands, int rows, double mh_threshold, int64_t max_candidates, const uint8_t *d_x_codes,
+                             const int64_t *d_x_offsets, const uint8_t *d_y_codes, const int64_t *d_y_offsets, int matrix_id, int gap_open, int gap_ext,
+                             double threshold, int top, const uint32_t *d_rank, int max_len, void *d_work, size_t work_bytes, int32_t *d_idx,
+                             uint32_t *d_key, void *stream) {
+  int rc;
+  if ((rc = lsh_cross_dev_check(d_index, index_bytes, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows, mh_threshold, max_candidates, &top)) != DA_OK)
+    return rc;
+  const NwlSeqs q{d_x_codes, d_x_offsets, m, d_y_codes, d_y_offsets, n};
+  if ((rc = lsh_nw_lists_dev_check(q, matrix_id, threshold, d_rank, max_len, d_work, d_idx, d_key, nullptr, false)) != DA_OK) return rc;
+  return lsh_nw_lists_device(LshSets{d_index, d_sig_x, m, ld_x, d_sig_y, n, ld_y, n_hash, bands, rows}, q, mh_threshold, max_candidates, d_work, work_bytes,
+                             matrix_id, gap_open, gap_ext, nwl_r_min(nw_value_table(max_len)->values, threshold), top, d_rank, max_len, d_idx, d_key, nullptr,
+                             static_cast<hipStream_t>(stream));
+}
+
+int da_similarity_nw_lsh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
+                             double mh_threshold, int64_t max_candidates, const char *matrix_name, int gap_open, int gap_ext, double threshold, int top,
+                             int32_t *idx_out, double *val_out, double *diag_out) {
+  const int mid = da_matrix_id(matrix_name);               // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  int rc = validate_mh(n, k, n_hash);
+  if (rc != DA_OK) return rc;
+  if (!residues || !seeds || !idx_out) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  int64_t total, max_len;
+  if ((rc = check_offsets(offsets, n, &total, &max_len)) != DA_OK) return rc;
+  if ((rc = lsh_arg_check(n_hash, bands, rows, 0.0, max_candidates, &top, true)) != DA_OK) return rc;   // the two thresholds come behind the NW checks
+  if ((rc = nw_validate(residues, offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_host_lengths("", offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_threshold_check(threshold, mh_threshold)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  MhPlanes mh;
+  DevBuf work, codes, bad;
+  const StreamDrain drain{nullptr};
+  if ((rc = mh.in.upload(residues, offsets, n, total, seeds, n_hash)) != DA_OK) return rc;
+  if ((rc = mh.alloc(n, n_hash, false)) != DA_OK || (rc = mh.signatures(k, 0, n_hash)) != DA_OK) return rc;
+  if ((rc = nwl_encode(mh.in, total, codes, bad)) != DA_OK) return rc;
+  const size_t wb = lsh_workspace_bytes(n, bands);
+  if ((rc = work.alloc(wb)) != DA_OK) return rc;
+  const NwlSeqs q{codes.as<uint8_t>(), mh.in.off.as<int64_t>(), n, codes.as<uint8_t>(), mh.in.off.as<int64_t>(), n};
+  return lsh_nw_lists_to_host(lsh_one_set(mh.sig.as<uint32_t>(), n, mh.lds, n_hash, bands, rows), q, mh_threshold, max_candidates, work.p, wb, mid, gap_open,
+                              gap_ext, threshold, top, (int)max_len, idx_out, val_out, diag_out);
+}
+
+int da_similarity_nw_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                    int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows, double mh_threshold,
+                                    int64_t max_candidates, const char *matrix_name, int gap_open, int gap_ext, double threshold, int top,
+                                    int32_t *idx_out, double *val_out) {
+  const int mid = da_matrix_id(matrix_name);               // before anything else, as in similarityNW
+  if (mid < 0) return DA_ERR_BAD_MATRIX;
+  int rc;
+  int64_t x_total, y_total;
+  if ((rc = lsh_cross_host_validate(x_residues, x_offsets, m, y_residues, y_offsets, n, k, n_hash, seeds, idx_out, idx_out, bands, rows, 0.0,
+                                    max_candidates, &top, &x_total, &y_total, true)) != DA_OK) return rc;
+  if ((rc = nw_cross_validate(x_residues, x_offsets, m, y_residues, y_offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_host_lengths(" of x", x_offsets, m)) != DA_OK || (rc = nwl_host_lengths(" of y", y_offsets, n)) != DA_OK) return rc;
+  if ((rc = nwl_threshold_check(threshold, mh_threshold)) != DA_OK) return rc;
+  if ((rc = require_device()) != DA_OK) return rc;
+  int64_t max_len = 1;
+  for (int64_t i = 0; i < m; ++i) max_len = std::max(max_len, x_offsets[i + 1] - x_offsets[i]);
+  for (int64_t j = 0; j < n; ++j) max_len = std::max(max_len, y_offsets[j + 1] - y_offsets[j]);
+  LshCrossHost h;
+  DevBuf x_codes, y_codes, x_bad, y_bad;
+  const StreamDrain drain{nullptr};
+  if ((rc = h.prepare(x_residues, x_offsets, m, x_total, y_residues, y_offsets, n, y_total, k, n_hash, seeds, bands, rows)) != DA_OK) return rc;
+  if ((rc = nwl_encode(h.x.in, x_total, x_codes, x_bad)) != DA_OK || (rc = nwl_encode(h.y.in, y_total, y_codes, y_bad)) != DA_OK) return rc;
+  const NwlSeqs q{x_codes.as<uint8_t>(), h.x.in.off.as<int64_t>(), m, y_codes.as<uint8_t>(), h.y.in.off.as<int64_t>(), n};
+  return lsh_nw_lists_to_host(h.sets(m, n, n_hash, bands, rows), q, mh_threshold, max_candidates, h.work.p, h.wb, mid, gap_open, gap_ext, threshold, top,
+                              (int)max_len, idx_out, val_out, nullptr);
 }
 
 // ---- summary statistics without the matrix on the host (reference R/similarity.R:11-34; dynaalign.h) ---------------------------------------

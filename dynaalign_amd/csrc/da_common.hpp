@@ -424,6 +424,11 @@ int launch_nwl_keep(const int32_t *d_matches, const int32_t *d_length, int64_t p
 int launch_nwl_emit(const int32_t *d_i, const int32_t *d_j, const int32_t *d_matches, const int32_t *d_length, const uint8_t *d_keep,
                     const int64_t *d_chunk_off, int64_t pairs, int64_t capacity, int32_t *d_out_i, int32_t *d_out_j, int32_t *d_out_matches,
                     int32_t *d_out_length, hipStream_t stream);
+// ... and the nearest-neighbour lists of it (da_dev_lsh_nw_knn): the value rank of every pair's (matches, length), the keep byte (rank >=
+// r_min and rank > 0), the diagonal of one set taken aside; d_totals[2] = {kept pairs, pairs without a rank}
+int launch_nwl_rank_keys(const int32_t *d_i, const int32_t *d_j, const int32_t *d_matches, const int32_t *d_length, int64_t pairs, const uint32_t *d_rank,
+                         int max_len, uint32_t r_min, bool one_set, int64_t n_diag, uint32_t *d_key, uint8_t *d_keep, uint32_t *d_diag_key,
+                         uint64_t *d_totals, hipStream_t stream);
 // consensus_kernels.hip: the center-star consensus of a pooled cluster table (da_dev_cluster_consensus and its pieces).  Pairs are numbered per
 // cluster i ascending then j != i ascending (d_pair_ptr: the running sums of c (c - 1), int64), rows (center, j != center) j ascending.
 // launch_cons_pairs lists entries [p0, p1) of the pairs (d_center == NULL) or of the rows; launch_cons_center_sums ADDS the fixed-point terms of
@@ -514,6 +519,13 @@ int launch_lsh_knn_entries(const LshSlots &slots, int64_t rows_a, bool both, int
 int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
                           int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream);
 int launch_lsh_knn_written(const int64_t *d_ptr, int64_t n, int64_t nnz, int top, uint64_t *d_written, hipStream_t stream);
+// the same two steps with a uint32 payload, the NW value ranks (da_dev_lsh_nw_knn, da_dev_nw_knn_select): the entries come from an unpacked
+// candidate list (d_i, d_j, rank key and keep byte per pair), the selection orders (rank descending, column ascending)
+int launch_nw_knn_entries(const int32_t *d_i, const int32_t *d_j, int64_t pairs, const uint32_t *d_rank_key, const uint8_t *d_keep, int64_t rows_a,
+                          bool both, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint32_t *d_val, uint64_t *d_written,
+                          void *d_temp, size_t temp_bytes, hipStream_t stream);
+int launch_nw_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint32_t *d_rank_key, int64_t n, int top, int32_t *d_idx,
+                         int64_t ld_idx, uint32_t *d_key, int64_t ld_key, hipStream_t stream);
 // lsh_cross_kernels.hip: the index and the probe (da_dev_lsh_index_*, and the front end of da_dev_lsh_cross_*)
 struct LshIndexView {
   const uint32_t *meta, *band_start;

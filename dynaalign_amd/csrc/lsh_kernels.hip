@@ -380,17 +380,20 @@ int launch_lsh_split(const uint64_t *d_key, const uint16_t *d_val, int64_t count
 // ---- nearest-neighbour lists from the candidates (da_dev_lsh_knn, da_dev_lsh_knn_select) --------------------------------------------------
 // After step 3 every kept slot is a distinct pair with its count.  Row i's list is the first `top` of its candidates by (count descending,
 // column ascending).  One set has i < j in every slot, so both directions of a pair are needed (BOTH); two sets list the rows of x only:
-//   5. k_lsh_knn_entries<Src, false, BOTH>: deg[i]++ and, with BOTH, deg[j]++ over the kept slots; an exclusive sum gives ptr[rows + 1];
-//   6. k_lsh_knn_entries<Src, true, BOTH>: (col = j, count) into row i's segment and, with BOTH, (col = i, count) into row j's, through a
+//   5. k_lsh_knn_entries<Src, V, false, BOTH> (V: the payload -- the uint16 count here, the uint32 value rank of the NW lists): deg[i]++ and,
+//      with BOTH, deg[j]++ over the kept slots; an exclusive sum gives ptr[rows + 1];
+//   6. k_lsh_knn_entries<Src, V, true, BOTH>: (col = j, count) into row i's segment and, with BOTH, (col = i, count) into row j's, through a
 //      per-row cursor.  The slots of a chunk mostly share their i (the partners of one element, the run of one x row, are consecutive
 //      slots), so the i side takes ONE atomic per distinct i of the chunk and writes its entries side by side; the j side takes one atomic
 //      per entry.  The order inside a segment is whatever the scheduling gives: the selection does not depend on it;
-//   7. the selection, on the 48-bit words (0xFFFF - count) << 32 | col -- ascending word order is count descending, column ascending, and
-//      the words of a row are distinct because its columns are.  Degrees are very skewed, so there are two kernels:
+//   7. the selection, on the words (KEY_MAX - key) << 32 | col -- ascending word order is key descending, column ascending, and the words
+//      of a row are distinct because its columns are.  The key is the uint16 count (a 48-bit word, six radix digits) or, for the NW lists
+//      on the same candidates (da_dev_nw_knn_select, nw_lsh_kernels.hip), a uint32 value rank (the full 64-bit word, eight digits): one
+//      template, KnnKey<K> holds what differs.  Degrees are very skewed, so there are two kernels:
 //        k_lsh_knn_select_short  rows of up to LSH_KNN_WAVE_MAX entries: a wave per row, an entry per lane, a bitonic sort by shuffles;
 //        k_lsh_knn_select_long   the other rows: a workgroup looks at LSH_KNN_TILE rows at a time, lists the long ones in LDS and takes them
 //                                one after the other.  Up to LSH_KNN_LDS_WORDS entries are loaded and sorted whole in LDS.  A longer row
-//                                first finds T, its top-th smallest word, by an MSD radix select over six 8-bit digits (a 256-bin LDS
+//                                first finds T, its top-th smallest word, by an MSD radix select over the word's 8-bit digits (a 256-bin LDS
 //                                histogram per digit, over the entries that match the digits fixed so far), then compacts the words
 //                                <= T -- exactly `top` of them -- through an LDS counter and sorts those.
 //      Neither kernel needs a workspace, so the selection on a caller's ragged rows is asynchronous.
@@ -404,8 +407,12 @@ __device__ __forceinline__ unsigned long long lsh_shfl_xor64(unsigned long long 
   const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
   return ((unsigned long long)hi << 32) | lo;
 }
-__device__ __forceinline__ unsigned long long lsh_knn_word(int32_t col, uint16_t count) {
-  return ((unsigned long long)(0xFFFFu - count) << 32) | (uint32_t)col;
+// what the two key types of the selection differ in: the largest key and the 8-bit digits of the word (KEY_MAX - key) << 32 | column
+template <typename K> struct KnnKey;
+template <> struct KnnKey<uint16_t> { static constexpr unsigned long long MAX = 0xFFFFull; static constexpr int DIGITS = 6; };
+template <> struct KnnKey<uint32_t> { static constexpr unsigned long long MAX = 0xFFFFFFFFull; static constexpr int DIGITS = 8; };
+template <typename K> __device__ __forceinline__ unsigned long long lsh_knn_word(int32_t col, K key) {
+  return ((KnnKey<K>::MAX - (unsigned long long)key) << 32) | (uint32_t)col;
 }
 // row r's entries: [b, e), with a pointer that runs backwards or past nnz cut to what lies inside [0, nnz)
 __device__ __forceinline__ void lsh_knn_segment(const long long *__restrict__ ptr, int64_t r, int64_t nnz, int64_t &b, int64_t &e) {
@@ -416,10 +423,10 @@ __device__ __forceinline__ void lsh_knn_segment(const long long *__restrict__ pt
 
 // SCATTER = false: at[] are the degrees.  SCATTER = true: at[] are the cursors (they start as the row pointers) and the entries are written.
 // BOTH = true (one set): (col = i, count) goes to row j as well; BOTH = false (two sets): the i side only, j numbers the other set.
-template <typename Src, bool SCATTER, bool BOTH>
-__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(Src src, int64_t slots, const uint16_t *__restrict__ count,
+template <typename Src, typename V, bool SCATTER, bool BOTH>
+__global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(Src src, int64_t slots, const V *__restrict__ count,
                                                                  const uint8_t *__restrict__ keep, unsigned long long *__restrict__ at,
-                                                                 int32_t *__restrict__ out_col, uint16_t *__restrict__ out_count) {
+                                                                 int32_t *__restrict__ out_col, V *__restrict__ out_count) {
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (slots + 63) >> 6;
   for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
@@ -428,7 +435,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_entries(Src src, int64_
     unsigned long long todo = __ballot(kp);
     if (!todo) continue;                          // wave-uniform
     int i = -1, j = -1, t = 0;
-    uint16_t cv = 0;
+    V cv = 0;
     if (kp) {
       src.get(s, i, j, t);
       cv = count[s];
@@ -471,14 +478,16 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_written(const long long
 }
 
 // entry t of row r: the word's column and count, or the padding -1 / 0
-__device__ __forceinline__ void lsh_knn_put(unsigned long long word, bool real, int32_t *__restrict__ idx, uint16_t *__restrict__ key) {
+template <typename K>
+__device__ __forceinline__ void lsh_knn_put(unsigned long long word, bool real, int32_t *__restrict__ idx, K *__restrict__ key) {
   *idx = real ? (int32_t)(uint32_t)(word & 0xFFFFFFFFull) : -1;
-  *key = real ? (uint16_t)(0xFFFFu - (uint32_t)(word >> 32)) : (uint16_t)0;
+  *key = real ? (K)(KnnKey<K>::MAX - (word >> 32)) : (K)0;
 }
 
+template <typename K>
 __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_short(const long long *__restrict__ ptr, int64_t nnz, const int32_t *__restrict__ col,
-                                                                      const uint16_t *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
-                                                                      int64_t ld_idx, uint16_t *__restrict__ key, int64_t ld_key) {
+                                                                      const K *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
+                                                                      int64_t ld_idx, K *__restrict__ key, int64_t ld_key) {
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64);
   for (int64_t r = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); r < n; r += nwaves) {
@@ -498,9 +507,11 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_short(const long
   }
 }
 
+template <typename K>
 __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long long *__restrict__ ptr, int64_t nnz, const int32_t *__restrict__ col,
-                                                                     const uint16_t *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
-                                                                     int64_t ld_idx, uint16_t *__restrict__ key, int64_t ld_key) {
+                                                                     const K *__restrict__ count, int64_t n, int top, int32_t *__restrict__ idx,
+                                                                     int64_t ld_idx, K *__restrict__ key, int64_t ld_key) {
+  constexpr int TOP_DIGIT = KnnKey<K>::DIGITS - 1;
   __shared__ unsigned long long buf[LSH_KNN_LDS_WORDS];
   __shared__ unsigned int hist[256];
   __shared__ unsigned int wtot[LSH_THREADS / 64];
@@ -533,7 +544,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long 
       } else {                                    // top <= DA_TOPK_MAX < deg: the top-th smallest word exists
         unsigned long long prefix = 0, T = 0;
         unsigned int need = (unsigned int)top;
-        for (int d = 5; d >= 0; --d) {
+        for (int d = TOP_DIGIT; d >= 0; --d) {
           const int shift = 8 * d;
           hist[tid] = 0;
           __syncthreads();
@@ -543,7 +554,7 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long 
             bool m = false;
             if (p < deg) {
               w = lsh_knn_word(col[b + p], count[b + p]);
-              m = d == 5 || (w >> (shift + 8)) == (prefix >> (shift + 8));
+              m = d == TOP_DIGIT || ((w >> shift) >> 8) == ((prefix >> shift) >> 8);   // two shifts: shift + 8 is 64 at the uint32 key's top digit
             }
             const int digit = (int)((w >> shift) & 255);
             const unsigned long long mm = __ballot(m);
@@ -590,19 +601,29 @@ __global__ __launch_bounds__(LSH_THREADS) void k_lsh_knn_select_long(const long 
     }
   }
 }
+
+template <typename K>
+int knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const K *d_count, int64_t n, int top, int32_t *d_idx, int64_t ld_idx, K *d_key,
+               int64_t ld_key, hipStream_t stream) {
+  if (n <= 0) return DA_OK;
+  const long long *ptr = reinterpret_cast<const long long *>(d_ptr);
+  hipLaunchKernelGGL(k_lsh_knn_select_short<K>, dim3(lsh_grid(n * 64)), dim3(LSH_THREADS), 0, stream, ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key,
+                     ld_key);
+  DA_HIP_TRY(hipGetLastError());
+  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, LSH_KNN_TILE), 256 * 8);
+  hipLaunchKernelGGL(k_lsh_knn_select_long<K>, dim3(grid), dim3(LSH_THREADS), 0, stream, ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key, ld_key);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
 }  // namespace
 
 int launch_lsh_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint16_t *d_count, int64_t n, int top, int32_t *d_idx,
                           int64_t ld_idx, uint16_t *d_key, int64_t ld_key, hipStream_t stream) {
-  if (n <= 0) return DA_OK;
-  const long long *ptr = reinterpret_cast<const long long *>(d_ptr);
-  hipLaunchKernelGGL(k_lsh_knn_select_short, dim3(lsh_grid(n * 64)), dim3(LSH_THREADS), 0, stream, ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key,
-                     ld_key);
-  DA_HIP_TRY(hipGetLastError());
-  const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n, LSH_KNN_TILE), 256 * 8);
-  hipLaunchKernelGGL(k_lsh_knn_select_long, dim3(grid), dim3(LSH_THREADS), 0, stream, ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key, ld_key);
-  DA_HIP_TRY(hipGetLastError());
-  return DA_OK;
+  return knn_select<uint16_t>(d_ptr, nnz, d_col, d_count, n, top, d_idx, ld_idx, d_key, ld_key, stream);
+}
+int launch_nw_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint32_t *d_rank_key, int64_t n, int top, int32_t *d_idx,
+                         int64_t ld_idx, uint32_t *d_key, int64_t ld_key, hipStream_t stream) {
+  return knn_select<uint32_t>(d_ptr, nnz, d_col, d_rank_key, n, top, d_idx, ld_idx, d_key, ld_key, stream);
 }
 
 // scratch of the scan over n + 1 degrees
@@ -619,33 +640,56 @@ int launch_lsh_knn_written(const int64_t *d_ptr, int64_t n, int64_t nnz, int top
 // Steps 5 and 6 on the verdicts of launch_lsh_verify_enumerated: d_ptr[rows_a + 1] = the row pointers of the entries (both: 2 per kept
 // slot, the rows of one set; otherwise 1, the rows of x), d_col / d_cnt their columns and counts; d_cursor (rows_a + 1 words) is scratch,
 // d_temp: lsh_knn_scan_bytes(rows_a).  *d_written (zeroed here) = the sum of min(degree, top).
-int launch_lsh_knn_entries(const LshSlots &slots, int64_t rows_a, bool both, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
-                           int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
-                           size_t temp_bytes, hipStream_t stream) {
-  unsigned long long *cursor = reinterpret_cast<unsigned long long *>(d_cursor);
-  const unsigned grid = lsh_grid(ceil_div(incidences, 64) * 64);
-  auto pass = [&](auto scatter) {                 // the count pass and the scatter pass
-    constexpr bool SCATTER = decltype(scatter)::value;
-    with_source(slots, [&](auto src) {
-      const auto kernel = both ? k_lsh_knn_entries<decltype(src), SCATTER, true> : k_lsh_knn_entries<decltype(src), SCATTER, false>;
-      hipLaunchKernelGGL(kernel, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, d_col, d_cnt);
-    });
-  };
+namespace {
+// the two passes around the scan; pass(tag) launches k_lsh_knn_entries with SCATTER = tag's value on d_cursor
+template <typename Pass>
+int knn_entries(int64_t rows_a, bool any, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, uint64_t *d_written, void *d_temp,
+                size_t temp_bytes, hipStream_t stream, Pass pass) {
   DA_HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)(rows_a + 1) * 8, stream));
   DA_HIP_TRY(hipMemsetAsync(d_written, 0, 8, stream));
-  if (incidences > 0 && entries > 0) {
+  if (any) {
     pass(std::false_type());
     DA_HIP_TRY(hipGetLastError());
   }
   size_t tb = temp_bytes;
   DA_HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_temp, tb, reinterpret_cast<const long long *>(d_cursor), reinterpret_cast<long long *>(d_ptr),
                                               (int)(rows_a + 1), stream));
-  if (incidences > 0 && entries > 0) {
+  if (any) {
     DA_HIP_TRY(hipMemcpyAsync(d_cursor, d_ptr, (size_t)(rows_a + 1) * 8, hipMemcpyDeviceToDevice, stream));
     pass(std::true_type());
     DA_HIP_TRY(hipGetLastError());
   }
   return launch_lsh_knn_written(d_ptr, rows_a, entries, top, d_written, stream);
+}
+}  // namespace
+
+int launch_lsh_knn_entries(const LshSlots &slots, int64_t rows_a, bool both, int64_t incidences, const uint16_t *d_count, const uint8_t *d_keep,
+                           int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint16_t *d_cnt, uint64_t *d_written, void *d_temp,
+                           size_t temp_bytes, hipStream_t stream) {
+  unsigned long long *cursor = reinterpret_cast<unsigned long long *>(d_cursor);
+  const unsigned grid = lsh_grid(ceil_div(incidences, 64) * 64);
+  return knn_entries(rows_a, incidences > 0 && entries > 0, entries, top, d_cursor, d_ptr, d_written, d_temp, temp_bytes, stream, [&](auto scatter) {
+    constexpr bool SCATTER = decltype(scatter)::value;
+    with_source(slots, [&](auto src) {
+      const auto kernel = both ? k_lsh_knn_entries<decltype(src), uint16_t, SCATTER, true> : k_lsh_knn_entries<decltype(src), uint16_t, SCATTER, false>;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(LSH_THREADS), 0, stream, src, incidences, d_count, d_keep, cursor, d_col, d_cnt);
+    });
+  });
+}
+
+// The same on an UNPACKED candidate list with a uint32 payload (the NW lists: d_i / d_j of k_nwl_split, the value ranks and keep bytes of
+// k_nwl_rank_keys): entries = the kept pairs, twice with both.  A kept pair has 0 <= i < rows_a and, with both, 0 <= j < rows_a.
+int launch_nw_knn_entries(const int32_t *d_i, const int32_t *d_j, int64_t pairs, const uint32_t *d_rank_key, const uint8_t *d_keep, int64_t rows_a,
+                          bool both, int64_t entries, int top, int64_t *d_cursor, int64_t *d_ptr, int32_t *d_col, uint32_t *d_val, uint64_t *d_written,
+                          void *d_temp, size_t temp_bytes, hipStream_t stream) {
+  unsigned long long *cursor = reinterpret_cast<unsigned long long *>(d_cursor);
+  const unsigned grid = lsh_grid(ceil_div(pairs, 64) * 64);
+  const LshListed src{d_i, d_j, d_i};             // the band is not read back: any readable array of `pairs` words
+  return knn_entries(rows_a, pairs > 0 && entries > 0, entries, top, d_cursor, d_ptr, d_written, d_temp, temp_bytes, stream, [&](auto scatter) {
+    constexpr bool SCATTER = decltype(scatter)::value;
+    const auto kernel = both ? k_lsh_knn_entries<LshListed, uint32_t, SCATTER, true> : k_lsh_knn_entries<LshListed, uint32_t, SCATTER, false>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(LSH_THREADS), 0, stream, src, pairs, d_rank_key, d_keep, cursor, d_col, d_val);
+  });
 }
 
 }  // namespace da

@@ -16,6 +16,10 @@
 // The threshold step compares integers: the host builds min_matches[length] with the divide it uses for the weights, k_nwl_keep tests
 // matches >= min_matches[length] and counts the kept per chunk, their exclusive sum places them and k_nwl_emit writes (i, j, matches,
 // length) in listed order -- the order of the sorted candidate list, so nothing is sorted again.
+// The nearest-neighbour lists on the same candidates (da_dev_lsh_nw_knn) order VALUES, so they leave the integers another way:
+// k_nwl_rank_keys looks every (matches, length) up in the rank table of da_nw_value_ranks -- 5/10 and 10/20 get one rank -- writes the keep
+// byte (rank >= r_min and rank > 0) and takes the diagonal candidates of one set aside into diag_key.  The ragged rows and the selection
+// are those of the MinHash lists with a uint32 payload (lsh_kernels.hip: launch_nw_knn_entries, launch_nw_knn_select).
 #include "lsh_common.hpp"
 
 namespace da {
@@ -151,6 +155,42 @@ __global__ __launch_bounds__(LSH_THREADS) void k_nwl_emit(const int32_t *__restr
   }
 }
 
+// key[p] = rank[length * (max_len + 1) + matches] under the domain check of k_codes_to_ranks; keep[p] = key >= r_min and key > 0.  one_set:
+// a candidate with i == j is its sequence's diagonal -- its key goes to diag_key[i] (0 <= i < n_diag) and it is not kept.  totals[0] += the
+// kept pairs, totals[1] += the pairs without a rank: a refused pair (-1 / -1) or a code outside the table (they get key 0 and are not kept).
+__global__ __launch_bounds__(LSH_THREADS) void k_nwl_rank_keys(const int32_t *__restrict__ pair_x, const int32_t *__restrict__ pair_y,
+                                                               const int32_t *__restrict__ matches, const int32_t *__restrict__ length, int64_t pairs,
+                                                               const uint32_t *__restrict__ rank, int max_len, uint32_t r_min, bool one_set,
+                                                               int64_t n_diag, uint32_t *__restrict__ key, uint8_t *__restrict__ keep,
+                                                               uint32_t *__restrict__ diag_key, unsigned long long *__restrict__ totals) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = (int64_t)gridDim.x * (LSH_THREADS / 64), chunks = (pairs + 63) >> 6;
+  const int64_t ml = max_len;
+  unsigned long long kept_sum = 0, bad_sum = 0;
+  for (int64_t c = (int64_t)blockIdx.x * (LSH_THREADS / 64) + (threadIdx.x >> 6); c < chunks; c += nwaves) {
+    const int64_t p = c * 64 + lane;
+    bool kp = false, bad = false;
+    if (p < pairs) {
+      const int64_t mt = matches[p], ln = length[p];
+      uint32_t v = 0;
+      if (ln >= 1 && ln <= 2 * ml && mt >= 0 && mt <= ml && mt <= ln) v = rank[ln * (ml + 1) + mt];
+      else bad = true;
+      const int32_t i = pair_x[p];
+      if (one_set && i == pair_y[p]) {
+        if (i >= 0 && i < n_diag) diag_key[i] = v;
+      } else {
+        kp = v >= r_min && v > 0;
+      }
+      key[p] = v;
+      keep[p] = kp ? 1 : 0;
+    }
+    kept_sum += (unsigned long long)__popcll(__ballot(kp));
+    bad_sum += (unsigned long long)__popcll(__ballot(bad));
+  }
+  if (lane == 0 && kept_sum) atomicAdd(&totals[0], kept_sum);
+  if (lane == 0 && bad_sum) atomicAdd(&totals[1], bad_sum);
+}
+
 // the rescore workspace behind its first 256-byte boundary; every array starts on a multiple of 256 bytes
 struct NwlLayout {
   size_t cnt, off, list_x, list_y, origin, list_matches, list_length, cls, longest, scan, scan_bytes, align;
@@ -242,6 +282,18 @@ int launch_nw_rescore(const uint8_t *d_x_codes, const int64_t *d_x_off, int64_t 
 int launch_nwl_split(const uint64_t *d_key, int64_t count, int32_t *d_i, int32_t *d_j, hipStream_t stream) {
   if (count <= 0) return DA_OK;
   hipLaunchKernelGGL(k_nwl_split, dim3(lsh_grid(count)), dim3(LSH_THREADS), 0, stream, reinterpret_cast<const unsigned long long *>(d_key), count, d_i, d_j);
+  DA_HIP_TRY(hipGetLastError());
+  return DA_OK;
+}
+
+// d_totals (two words, zeroed here): the kept pairs and the pairs without a rank; d_diag_key may be NULL when one_set is false
+int launch_nwl_rank_keys(const int32_t *d_i, const int32_t *d_j, const int32_t *d_matches, const int32_t *d_length, int64_t pairs, const uint32_t *d_rank,
+                         int max_len, uint32_t r_min, bool one_set, int64_t n_diag, uint32_t *d_key, uint8_t *d_keep, uint32_t *d_diag_key,
+                         uint64_t *d_totals, hipStream_t stream) {
+  DA_HIP_TRY(hipMemsetAsync(d_totals, 0, 16, stream));
+  if (pairs <= 0) return DA_OK;
+  hipLaunchKernelGGL(k_nwl_rank_keys, dim3(lsh_grid(ceil_div(pairs, 64) * 64)), dim3(LSH_THREADS), 0, stream, d_i, d_j, d_matches, d_length, pairs, d_rank,
+                     max_len, r_min, one_set, n_diag, d_key, d_keep, d_diag_key, reinterpret_cast<unsigned long long *>(d_totals));
   DA_HIP_TRY(hipGetLastError());
   return DA_OK;
 }

@@ -1308,6 +1308,94 @@ def lsh_nw_edges(sig, ds, n_hash, bands, rows, threshold, mh_threshold=0.0, matr
     return _count_then_fill(run, capacity, dev, (torch.int32,) * 4)
 
 
+def nw_knn_select(ptr, col, key, top, nnz=None, out=None):
+    """``lsh_knn_select`` on 32-bit keys (da_dev_nw_knn_select), the selection of the NW-ranked LSH lists: ``key`` int32 (uint32 bit
+    patterns over their whole range: value ranks) -> (idx int32 (n, top), key int32 (n, top)): per row the first ``top`` entries by (key
+    descending as unsigned, column ascending), then -1 / 0.  Everything else as ``lsh_knn_select``."""
+    lib = _capi.load()
+    for t, name in ((ptr, "ptr"), (col, "col"), (key, "key")):
+        _require_cuda(t, name)
+    assert ptr.dtype == torch.int64 and col.dtype == torch.int32 and key.dtype == torch.int32
+    assert ptr.is_contiguous() and col.is_contiguous() and key.is_contiguous() and col.numel() == key.numel()
+    n = int(ptr.numel()) - 1
+    nnz = int(col.numel()) if nnz is None else int(nnz)
+    if not 0 <= nnz <= col.numel():
+        raise ValueError("nnz must be in 0 .. col.numel()")
+    t = _top(top)
+    if out is None:
+        idx, okey = _topk_out(n, top, torch.int32, ptr.device)
+    else:
+        idx, okey = out
+        for o in (idx, okey):
+            _require_cuda(o, "out")
+            assert o.dim() == 2 and o.dtype == torch.int32 and o.shape[0] >= n and o.shape[1] >= t and o.stride(1) == 1
+    _call(lib.da_dev_nw_knn_select, ptr.data_ptr(), nnz, col.data_ptr(), key.data_ptr(), n, int(top), idx.data_ptr(), idx.stride(0),
+          okey.data_ptr(), okey.stride(0), _stream())
+    return idx[:n, :t], okey[:n, :t]
+
+
+def nw_rank_keys(i, j, matches, length, rank, max_len, r_min=1, one_set=True, n=0):
+    """The rank-key step of the NW-ranked LSH lists on a caller's scored pairs (da_dev_nw_rank_keys): int32 device tensors ``i``, ``j``,
+    ``matches``, ``length`` and the device rank table of ``nw_value_ranks(max_len)`` -> (key int32 (uint32 value ranks), keep uint8,
+    diag_key int32 (n), totals int64 (2) = kept pairs, pairs outside the table).  keep = key >= r_min and key > 0; ``one_set``: a pair
+    with i == j is not kept and its key goes to diag_key[i].  Asynchronous on the current stream."""
+    lib = _capi.load()
+    for t, name in ((i, "i"), (j, "j"), (matches, "matches"), (length, "length"), (rank, "rank")):
+        _require_cuda(t, name)
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    pairs = int(i.numel())
+    assert j.numel() == pairs and matches.numel() == pairs and length.numel() == pairs
+    assert rank.numel() >= (2 * int(max_len) + 1) * (int(max_len) + 1)
+    dev = i.device
+    key = torch.zeros(max(pairs, 1), dtype=torch.int32, device=dev)
+    keep = torch.zeros(max(pairs, 1), dtype=torch.uint8, device=dev)
+    diag = torch.zeros(max(int(n), 1), dtype=torch.int32, device=dev)
+    totals = torch.zeros(2, dtype=torch.int64, device=dev)
+    _call(lib.da_dev_nw_rank_keys, i.data_ptr(), j.data_ptr(), matches.data_ptr(), length.data_ptr(), pairs, rank.data_ptr(), int(max_len),
+          int(r_min), 1 if one_set else 0, int(n), key.data_ptr(), keep.data_ptr(), diag.data_ptr(), totals.data_ptr(), _stream())
+    return key[:pairs], keep[:pairs], diag[:int(n)], totals
+
+
+def lsh_nw_knn(sig, ds, n_hash, bands, rows, top, rank, max_len, threshold=0.0, mh_threshold=0.0, matrix_name="BLOSUM62", gap_open=10, gap_ext=4,
+               max_candidates=1 << 32, work=None):
+    """The NW-ranked LSH nearest-neighbour lists, resident signatures and resident encoded sequences in, resident lists out
+    (da_dev_lsh_nw_knn): ``sig`` the signatures of ``ds`` (ds.codes filled by nw_encode), ``rank`` the int32 device copy of the rank table of
+    ``nw_value_ranks(max_len)``, max_len >= the longest sequence -> (idx int32 (n, top), key int32 (n, top), diag_key int32 (n)): value ranks
+    as uint32 bit patterns, padding -1 / 0; value = values[rank].  ``nw_lsh_last_route()["edges"]`` has the number of real entries.
+    Synchronises the stream."""
+    lib = _capi.load()
+    if ds.codes is None:
+        raise ValueError("call nw_encode on the sequences first")
+    mid = _matrix_id(lib, matrix_name)
+    _require_cuda(rank, "rank")
+    n, ld = _sig_block(sig, n_hash)
+    work = _lsh_work(work, n, bands, sig.device)
+    idx, key = _topk_out(n, top, torch.int32, sig.device)
+    diag = torch.empty(max(n, 1), dtype=torch.int32, device=sig.device)
+    _call(lib.da_dev_lsh_nw_knn, sig.data_ptr(), n, ld, int(n_hash), int(bands), int(rows), float(mh_threshold), int(max_candidates),
+          ds.codes.data_ptr(), ds.offsets.data_ptr(), mid, int(gap_open), int(gap_ext), float(threshold), int(top), rank.data_ptr(), int(max_len),
+          work.data_ptr(), work.numel(), idx.data_ptr(), key.data_ptr(), diag.data_ptr(), _stream())
+    return idx[:n], key[:n], diag[:n]
+
+
+def lsh_nw_cross_topk(index, sig_x, dx, sig_y, dy, n_hash, bands, rows, top, rank, max_len, threshold=0.0, mh_threshold=0.0, matrix_name="BLOSUM62",
+                      gap_open=10, gap_ext=4, max_candidates=1 << 32, work=None):
+    """The two-set form of ``lsh_nw_knn`` (da_dev_lsh_cross_nw_topk): ``index = lsh_index_build(sig_y, n_hash, bands, rows)``; the queries
+    ``sig_x`` / ``dx`` against ``sig_y`` / ``dy`` -> (idx int32 (m, top), key int32 (m, top)), x[i] as sequence1.  Synchronises the stream."""
+    lib = _capi.load()
+    if dx.codes is None or dy.codes is None:
+        raise ValueError("call nw_encode on the sequences first")
+    mid = _matrix_id(lib, matrix_name)
+    _require_cuda(rank, "rank")
+    m, ld_x, n, ld_y, work = _lsh_cross_operands(index, sig_x, sig_y, n_hash, bands, work)
+    idx, key = _topk_out(m, top, torch.int32, sig_x.device)
+    _call(lib.da_dev_lsh_cross_nw_topk, index.data_ptr(), index.numel(), sig_x.data_ptr(), m, ld_x, sig_y.data_ptr(), n, ld_y, int(n_hash), int(bands),
+          int(rows), float(mh_threshold), int(max_candidates), dx.codes.data_ptr(), dx.offsets.data_ptr(), dy.codes.data_ptr(), dy.offsets.data_ptr(),
+          mid, int(gap_open), int(gap_ext), float(threshold), int(top), rank.data_ptr(), int(max_len), work.data_ptr(), work.numel(), idx.data_ptr(),
+          key.data_ptr(), _stream())
+    return idx[:m], key[:m]
+
+
 def nw_lsh_last_route():
     from .similarity import nw_lsh_last_route as route
     return route()

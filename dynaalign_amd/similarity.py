@@ -1127,7 +1127,8 @@ def similarityNW_lsh_cross_edges(x, y, k=4, n_hash=50, bands=10, rows=5, thresho
 
 def nw_lsh_last_route():
     """What this thread's last NW-on-LSH call did: buckets, (pair, band) incidences, distinct verified pairs, aligned pairs (the candidates,
-    diagonal included), how many of them took the lane-per-pair (short) and the wavefront-per-pair (long) kernel, and edges."""
+    diagonal included), how many of them took the lane-per-pair (short) and the wavefront-per-pair (long) kernel, and edges -- after a
+    list call (similarityNW_lsh_knn, similarityNW_lsh_cross_topk) the real list entries written."""
     v = np.zeros(7, np.int64)
     _capi.check(_capi.load().da_nw_lsh_last_route(*[v[i:].ctypes.data for i in range(7)]))
     return dict(zip(("buckets", "incidences", "verified_pairs", "aligned_pairs", "short_pairs", "long_pairs", "edges"), (int(x) for x in v)))
@@ -1154,6 +1155,106 @@ def nw_lsh_cross_edges_dense(sig_x, sig_y, bands, rows, mh_threshold, nw_value, 
     diagonal; ``nw_value(i, j)`` is x[i] as sequence1 against y[j] as sequence2."""
     ci, cj, _ = lsh_cross_edges_dense(sig_x, sig_y, bands, rows, mh_threshold)
     return _nw_threshold_keep(ci, cj, nw_value, threshold)
+
+
+def _lsh_topk_arrays(rows_n, top):
+    top = _as_int(top, "top")
+    shape = (max(rows_n, 1), min(max(top, 1), 1024))
+    return top, np.empty(shape, np.int32), np.empty(shape, np.float64)
+
+
+def _nw_lsh_knn(sequences, k, n_hash, bands, rows, top, mh_threshold, threshold, matrixName, gapOpen, gapExt, seed, max_candidates):
+    lib, res, off, n, k, n_hash, seeds = _mh_prelude(sequences, k, n_hash, seed)
+    top, idx, val = _lsh_topk_arrays(n, top)
+    diag = np.empty(max(n, 1), np.float64)
+    _capi.check(lib.da_similarity_nw_lsh_knn(res.ctypes.data, off.ctypes.data, n, k, n_hash, seeds.ctypes.data, _as_int(bands, "bands"),
+                                             _as_int(rows, "rows"), float(mh_threshold), int(max_candidates), _matrix_name(matrixName),
+                                             _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), float(threshold), top, idx.ctypes.data,
+                                             val.ctypes.data, diag.ctypes.data))
+    return idx[:n], val[:n], diag[:n]
+
+
+def similarityNW_lsh_knn(sequences, k=4, n_hash=50, bands=10, rows=5, top=10, *, mh_threshold=0.0, threshold=0.0, matrixName="BLOSUM62",
+                         gapOpen=10, gapExt=4, seed=None, max_candidates=1 << 32):
+    """For every sequence its ``top`` best LSH candidates ranked by alignment identity: ``(idx, val)``, (n, top) int32 and (n, top) float64.
+    The candidates are those of ``similarityNW_lsh_edges`` -- the pairs ``similarityMH_lsh_edges(..., mh_threshold)`` proposes -- each
+    aligned once, the smaller position as sequence1 (the value similarityNW's symmetric matrix holds at both places).  Row r lists the
+    first ``top`` of ``{c : {r, c} a candidate, w >= threshold and w > 0}`` by w descending, then c ascending; a row with fewer is padded
+    with ``idx = -1, val = 0.0``, and ``val > 0`` marks exactly the real entries.  Equal doubles tie whatever their (matches, length).
+    Exactly ``nw_lsh_knn_dense`` of the signatures and the reference's pair value, values bit for bit; approximate is only its relation
+    to ``similarityNW_knn_long``: a neighbour that shares no bucket is missing.  Sequences of 1 .. 1024 residues, mixed freely; ``top`` is
+    in 1 .. 1024 and is NOT clamped to n - 1.  The device orders 32-bit value ranks (``nw_value_ranks``); nothing but the lists returns to
+    the host.  Errors as similarityNW_lsh_edges, ``top`` behind ``max_candidates`` with similarityMH_lsh_knn's text."""
+    idx, val, _ = _nw_lsh_knn(sequences, k, n_hash, bands, rows, top, mh_threshold, threshold, matrixName, gapOpen, gapExt, seed, max_candidates)
+    return idx, val
+
+
+def similarityNW_lsh_knn_edges(sequences, k=4, n_hash=50, bands=10, rows=5, top=10, mode="union", *, mh_threshold=0.0, threshold=0.0,
+                               matrixName="BLOSUM62", gapOpen=10, gapExt=4, seed=None, max_candidates=1 << 32):
+    """The kNN graph of similarityNW_lsh_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``: knn_graph of the lists with the
+    diagonal the DP gives for every sequence against itself (scored, not assumed to be 1.0).  At most ``n * top`` off-diagonal edges.  The
+    ``threshold`` slot holds the smallest off-diagonal weight kept, NaN when none."""
+    idx, val, diag = _nw_lsh_knn(sequences, k, n_hash, bands, rows, top, mh_threshold, threshold, matrixName, gapOpen, gapExt, seed, max_candidates)
+    return _knn_edges_result(idx, val, diag, mode)
+
+
+def similarityNW_lsh_cross_topk(x, y, k=4, n_hash=50, bands=10, rows=5, top=10, *, mh_threshold=0.0, threshold=0.0, matrixName="BLOSUM62",
+                                gapOpen=10, gapExt=4, seed=None, max_candidates=1 << 32):
+    """The two-set form of ``similarityNW_lsh_knn``: for every x[i] the first ``top`` of the candidates y[j] of
+    ``similarityMH_lsh_cross_edges(x, y, ..., mh_threshold)`` by alignment identity (x[i] as sequence1, y[j] as sequence2) descending, then j
+    ascending: ``(idx, val)``, (m, top).  No diagonal; ``top`` is NOT clamped to len(y).  Exactly ``nw_lsh_cross_topk_dense``."""
+    lib, xr, xo, m, yr, yo, n, k, n_hash, seeds = _mh_prelude_two(x, y, k, n_hash, seed)
+    top, idx, val = _lsh_topk_arrays(m, top)
+    _capi.check(lib.da_similarity_nw_lsh_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, k, n_hash, seeds.ctypes.data,
+                                                    _as_int(bands, "bands"), _as_int(rows, "rows"), float(mh_threshold), int(max_candidates),
+                                                    _matrix_name(matrixName), _as_int(gapOpen, "gapOpen"), _as_int(gapExt, "gapExt"), float(threshold),
+                                                    top, idx.ctypes.data, val.ctypes.data))
+    return idx[:m], val[:m]
+
+
+def _ranked_rows(r, c, w, n_rows, top, threshold):
+    """the first ``top`` of every row's (c, w) with w >= threshold and w > 0 by (w descending, c ascending) -> (idx, val), padded -1 / 0.0"""
+    top = _as_int(top, "top")
+    if not 1 <= top <= 1024:
+        raise ValueError("top must be in 1 .. 1024 (got %d)" % top)
+    live = (w >= float(threshold)) & (w > 0)
+    r, c, w = r[live], c[live], w[live]
+    order = np.lexsort((c, -w, r))
+    r, c, w = r[order], c[order], w[order]
+    place = np.arange(len(r)) - np.searchsorted(r, np.arange(n_rows))[r]
+    keep = place < top
+    idx = np.full((n_rows, top), -1, np.int32)
+    val = np.zeros((n_rows, top), np.float64)
+    idx[r[keep], place[keep]] = c[keep]
+    val[r[keep], place[keep]] = w[keep]
+    return idx, val
+
+
+def nw_lsh_knn_dense(sig, bands, rows, top, mh_threshold, nw_value, threshold=0.0):
+    """The definition ``similarityNW_lsh_knn`` is exact against (host code, beside ``nw_lsh_edges_dense``) -> ``(idx, val, diag)``.  The
+    candidates are the off-diagonal pairs i < j of ``lsh_edges_dense(sig, bands, rows, mh_threshold)``; ``w{i, j} = nw_value(i, j)``, the
+    SMALLER position as sequence1 -- the value similarityNW's symmetric matrix holds at (i, j) and (j, i).  Row r lists the first ``top``
+    (1 .. 1024, not clamped to n - 1) of ``{c : {r, c} a candidate, w >= threshold and w > 0}`` by w descending, then c ascending; the
+    padding is -1 / 0.0.  ``diag[r] = nw_value(r, r)``.  Equal doubles tie whatever their (matches, length)."""
+    ci, cj, _ = lsh_edges_dense(sig, bands, rows, mh_threshold)
+    n = np.asarray(sig).shape[0]
+    ci, cj = ci.astype(np.int64), cj.astype(np.int64)
+    w = np.array([nw_value(int(a), int(b)) for a, b in zip(ci, cj)], np.float64).reshape(-1)
+    diag = np.zeros(n, np.float64)
+    on = ci == cj
+    diag[ci[on]] = w[on]
+    ci, cj, w = ci[~on], cj[~on], w[~on]
+    idx, val = _ranked_rows(np.concatenate([ci, cj]), np.concatenate([cj, ci]), np.concatenate([w, w]), n, top, threshold)
+    return idx, val, diag
+
+
+def nw_lsh_cross_topk_dense(sig_x, sig_y, bands, rows, top, mh_threshold, nw_value, threshold=0.0):
+    """The two-set twin of ``nw_lsh_knn_dense`` -> ``(idx, val)``: the candidates of ``lsh_cross_edges_dense(sig_x, sig_y, bands, rows,
+    mh_threshold)``, ``nw_value(i, j)`` with x[i] as sequence1 and y[j] as sequence2; the rows are those of x, no diagonal."""
+    ci, cj, _ = lsh_cross_edges_dense(sig_x, sig_y, bands, rows, mh_threshold)
+    ci, cj = ci.astype(np.int64), cj.astype(np.int64)
+    w = np.array([nw_value(int(a), int(b)) for a, b in zip(ci, cj)], np.float64).reshape(-1)
+    return _ranked_rows(ci, cj, w, np.asarray(sig_x).shape[0], top, threshold)
 
 
 def similarityNW_cross_edges(x, y, matrixName="BLOSUM62", gapOpen=10, gapExt=4, thresh_p=0.8, *, threshold=None):

@@ -64,6 +64,8 @@ extern "C" {
  *  da_similarity_mh_lsh_components -- likewise)
  * (the NW-on-LSH-candidates entry points -- da_similarity_nw_lsh_[cross_]edges_begin, da_dev_lsh_[cross_]nw_edges,
  *  da_dev_nw_rescore_pairs, da_dev_nw_rescore_workspace_bytes, da_nw_lsh_last_route -- likewise)
+ * (the NW-ranked LSH list entry points -- da_similarity_nw_lsh_knn, da_similarity_nw_lsh_cross_topk, da_dev_lsh_nw_knn,
+ *  da_dev_lsh_cross_nw_topk, da_dev_nw_knn_select, da_dev_nw_rank_keys -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1391,6 +1393,63 @@ int da_similarity_nw_lsh_cross_edges_begin(const uint8_t *x_residues, const int6
                                            int gap_ext, double threshold, da_edges **handle_out, int64_t *n_edges_out);
 int da_nw_lsh_last_route(int64_t *buckets_out, int64_t *incidences_out, int64_t *verified_pairs_out, int64_t *aligned_pairs_out,
                          int64_t *short_pairs_out, int64_t *long_pairs_out, int64_t *edges_out);
+
+/* ---- NW-ranked nearest-neighbour lists on the same candidates ---------------------------------------------------------------------------
+ * One set: w{i, j} = the identity of x[min(i, j)] as sequence1 against x[max(i, j)] as sequence2 -- the value da_similarity_nw's symmetric
+ * matrix holds at (i, j) and (j, i).  Row r lists the first `top` (1 .. 1024, NOT clamped to n - 1) members of
+ *     { c != r : {r, c} a candidate at mh_threshold, w >= threshold and w > 0 }     by w descending, then c ascending;
+ * the padding is index -1 / value 0.0, so a value > 0 marks exactly the real entries.  diag[r] = the identity of x[r] against itself,
+ * scored like every other candidate, not assumed to be 1.0.  Two sets: row i of x lists { j : (i, j) a candidate, ... } with x[i] as
+ * sequence1 and y[j] as sequence2; no diagonal.  The order is that of the DOUBLES: 5/10 and 10/20 tie and fall back to the column.  The
+ * device orders 32-bit VALUE RANKS -- the table of da_nw_value_ranks, rank 0 = the value 0.0 -- and divides nothing; EXACT with respect
+ * to this definition, values bit for bit.  Approximate is only the relation to da_similarity_nw_knn_long: a pair that shares no bucket
+ * is missing.  Sequences of 1 .. 1024 residues, mixed freely.
+ *
+ * da_similarity_nw_lsh_knn / da_similarity_nw_lsh_cross_topk: host boundary; idx_out int32 (n, top) / (m, top), val_out float64 of the
+ *   same shape, diag_out float64 [n]; val_out and diag_out may be NULL.  val = values[rank] from the table of da_nw_value_ranks(the
+ *   longest sequence of the call), computed on the host as da_similarity_nw_knn_long does.  Checks, in this order and before any device
+ *   is needed: those of da_similarity_nw_lsh_edges_begin / da_similarity_nw_lsh_cross_edges_begin in their order and with their texts,
+ *   with top outside 1 .. 1024 (DA_ERR_BAD_ARG, the text of da_similarity_mh_lsh_knn) right behind max_candidates; DA_ERR_NO_DEVICE last.
+ * da_dev_lsh_nw_knn / da_dev_lsh_cross_nw_topk: the one-call device routes on resident signatures and resident encoded sequences:
+ *   da_dev_lsh_edges / da_dev_lsh_cross_edges at mh_threshold, the sorted list unpacked, da_dev_nw_rescore_pairs, the rank keys, the
+ *   ragged rows (both directions of every kept pair of one set) and da_dev_nw_knn_select's selection into d_idx int32 and d_key uint32
+ *   (value ranks; padding -1 / 0), both (rows, top) with leading dimension top; the one-set call also writes d_diag_key uint32 [n].
+ *   d_rank: the device copy of the rank table of da_nw_value_ranks(max_len), max_len >= the longest sequence.  The kept ranks are those
+ *   >= r_min, the rank of the smallest table value >= threshold, and > 0.  d_work / work_bytes: those of da_dev_lsh_edges /
+ *   da_dev_lsh_cross_edges.  Nothing returns to the host in between but a few totals.  A candidate the alignment kernels refuse, or
+ *   whose (matches, length) lies outside the table, makes the call fail with DA_ERR_UNSUPPORTED.  Synchronises the stream.
+ * da_dev_nw_rank_keys: the rank-key step alone, on a caller's scored pair list: d_key[p] = d_rank[length * (max_len + 1) + matches]
+ *   (0 when (matches, length) is outside the table: length 1 .. 2 * max_len, matches 0 .. min(length, max_len)), d_keep[p] = 1 when the key
+ *   is >= r_min and > 0.  one_set != 0: a pair with i == j is not kept and its key goes to d_diag_key[i] (0 <= i < n).  d_totals uint64
+ *   [2] (zeroed by the call) = the kept pairs, the pairs outside the table (-1 / -1 of a refused pair among them).  Asynchronous.
+ * da_dev_nw_knn_select: the selection alone, on a caller's ragged rows, with the contract of da_dev_lsh_knn_select word for word and
+ *   uint32 keys over their whole range: row r's entries are d_col / d_rank_key [d_ptr[r], d_ptr[r + 1]), d_ptr int64 [n + 1], columns
+ *   >= 0 and distinct within a row, in any order.  d_idx[r * ld_idx + t], d_key[r * ld_key + t] for t < top get the row's first `top`
+ *   entries by (key descending, column ascending), then -1 / 0; columns >= top of the outputs are not touched.  A row whose pointers
+ *   run backwards or past nnz is cut to what lies inside [0, nnz).  Asynchronous on `stream`, no workspace.
+ * da_nw_lsh_last_route reports these calls too; `edges` = the real list entries written. */
+int da_similarity_nw_lsh_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands,
+                             int rows, double mh_threshold, int64_t max_candidates, const char *matrix_name, int gap_open, int gap_ext,
+                             double threshold, int top, int32_t *idx_out, double *val_out, double *diag_out);
+int da_similarity_nw_lsh_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                    const int64_t *y_offsets, int64_t n, int k, int n_hash, const uint32_t *seeds, int bands, int rows,
+                                    double mh_threshold, int64_t max_candidates, const char *matrix_name, int gap_open, int gap_ext,
+                                    double threshold, int top, int32_t *idx_out, double *val_out);
+int da_dev_lsh_nw_knn(const uint32_t *d_sig, int64_t n, int64_t ld_sig, int n_hash, int bands, int rows, double mh_threshold,
+                      int64_t max_candidates, const uint8_t *d_codes, const int64_t *d_offsets, int matrix_id, int gap_open, int gap_ext,
+                      double threshold, int top, const uint32_t *d_rank, int max_len, void *d_work, size_t work_bytes, int32_t *d_idx,
+                      uint32_t *d_key, uint32_t *d_diag_key, void *stream);
+int da_dev_lsh_cross_nw_topk(const void *d_index, size_t index_bytes, const uint32_t *d_sig_x, int64_t m, int64_t ld_x,
+                             const uint32_t *d_sig_y, int64_t n, int64_t ld_y, int n_hash, int bands, int rows, double mh_threshold,
+                             int64_t max_candidates, const uint8_t *d_x_codes, const int64_t *d_x_offsets, const uint8_t *d_y_codes,
+                             const int64_t *d_y_offsets, int matrix_id, int gap_open, int gap_ext, double threshold, int top,
+                             const uint32_t *d_rank, int max_len, void *d_work, size_t work_bytes, int32_t *d_idx, uint32_t *d_key,
+                             void *stream);
+int da_dev_nw_rank_keys(const int32_t *d_i, const int32_t *d_j, const int32_t *d_matches, const int32_t *d_length, int64_t pairs,
+                        const uint32_t *d_rank, int max_len, uint32_t r_min, int one_set, int64_t n, uint32_t *d_key, uint8_t *d_keep,
+                        uint32_t *d_diag_key, uint64_t *d_totals, void *stream);
+int da_dev_nw_knn_select(const int64_t *d_ptr, int64_t nnz, const int32_t *d_col, const uint32_t *d_rank_key, int64_t n, int top,
+                         int32_t *d_idx, int64_t ld_idx, uint32_t *d_key, int64_t ld_key, void *stream);
 
 /* name -> id for da_dev_nw; -1 + DA_ERR_BAD_MATRIX message when unknown. */
 int da_matrix_id(const char *matrix_name);
