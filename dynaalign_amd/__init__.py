@@ -27,6 +27,8 @@ from .similarity import (  # noqa: F401
     similarityJaccard_knn_edges, similarityJaccard_edges,
     similarityJaccard_long, similarityJaccard_cross_long, similarityJaccard_cross_topk_long, similarityJaccard_knn_long,
     similarityJaccard_knn_edges_long, similarityJaccard_edges_long, similarityJaccard_cross_edges_long, similarityJaccard_stats_long,
+    lev_dense, lev_counts, similarityLev, similarityLev_cross, similarityLev_cross_topk, similarityLev_knn, similarityLev_knn_edges,
+    similarityLev_edges, similarityLev_cross_edges,
     similarityMH_lsh_edges, lsh_edges_dense, lsh_collision_probability, similarityMH_lsh_knn, similarityMH_lsh_knn_edges, lsh_knn_dense,
     similarityMH_lsh_cross_edges, similarityMH_lsh_cross_topk, lsh_cross_edges_dense, lsh_cross_topk_dense,
     similarityMH_lsh_components, lsh_components_dense,
@@ -44,6 +46,8 @@ __all__ = [
     "similarityJaccard_knn_edges", "similarityJaccard_edges",
     "similarityJaccard_long", "similarityJaccard_cross_long", "similarityJaccard_cross_topk_long", "similarityJaccard_knn_long",
     "similarityJaccard_knn_edges_long", "similarityJaccard_edges_long", "similarityJaccard_cross_edges_long", "similarityJaccard_stats_long",
+    "lev_dense", "lev_counts", "similarityLev", "similarityLev_cross", "similarityLev_cross_topk", "similarityLev_knn", "similarityLev_knn_edges",
+    "similarityLev_edges", "similarityLev_cross_edges",
     "similarityMH_lsh_edges", "lsh_edges_dense", "lsh_collision_probability", "similarityMH_lsh_knn", "similarityMH_lsh_knn_edges", "lsh_knn_dense",
     "similarityMH_lsh_cross_edges", "similarityMH_lsh_cross_topk", "lsh_cross_edges_dense", "lsh_cross_topk_dense",
     "components", "components_dense", "components_device", "similarityMH_lsh_components", "lsh_components_dense",

@@ -1735,6 +1735,35 @@ int da_dev_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64
                                   static_cast<hipStream_t>(stream));
 }
 
+// ---- the Levenshtein similarity, device layer (lev_kernels.hip) ------------------------------------------------------------------------------
+// `seq` > 0 names the (1-based) sequence that is too long
+static int lev_limits(int64_t max_len, int64_t seq) {
+  if (max_len > 127) {
+    if (seq > 0)
+      return fail(DA_ERR_UNSUPPORTED, "sequence %lld is %lld bytes long: the Levenshtein similarity takes sequences of at most 127 bytes", (long long)seq,
+                  (long long)max_len);
+    return fail(DA_ERR_UNSUPPORTED, "max_len = %lld: the Levenshtein similarity takes sequences of at most 127 bytes", (long long)max_len);
+  }
+  return DA_OK;
+}
+
+size_t da_dev_lev_masks_bytes(int64_t n, int64_t max_len, int n_classes) { return lev_masks_bytes(n, max_len, n_classes); }
+
+int da_dev_lev_masks(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t max_len, const uint8_t *class_map, int n_classes,
+                     void *d_masks, size_t masks_bytes, void *stream) {
+  if (n <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+  if (!d_residues || !d_offsets || !class_map || !d_masks) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+  if (max_len < 0) return fail(DA_ERR_BAD_ARG, "negative shape");
+  int rc;
+  if ((rc = lev_limits(max_len, 0)) != DA_OK) return rc;
+  return launch_lev_masks(d_residues, d_offsets, n, max_len, class_map, n_classes, d_masks, masks_bytes, static_cast<hipStream_t>(stream));
+}
+
+int da_dev_lev_rect(const void *d_masks, int64_t n, int64_t max_len, int n_classes, int64_t row_begin, int64_t row_end, int64_t col_begin,
+                    int64_t col_end, int kind, void *d_out, int64_t ld, void *stream) {
+  return launch_lev_rect(d_masks, n, max_len, n_classes, row_begin, row_end, col_begin, col_end, kind, d_out, ld, static_cast<hipStream_t>(stream));
+}
+
 int da_dev_symmetrize(void *d_mat, int64_t n, int64_t ld, int kind, void *stream) {
   if (!d_mat || ld < n) return fail(DA_ERR_BAD_ARG, "bad matrix / ld");
   return launch_symmetrize(d_mat, n, ld, kind, static_cast<hipStream_t>(stream));
@@ -5468,6 +5497,204 @@ int da_similarity_jaccard_stats_long(const uint8_t *residues, const int64_t *off
     return js.rect(b0, b1, c0, n, DA_OUT_PACK32, d, ld, nullptr);
   }, nullptr);
   return rank_stats(keys, n, out);
+}
+
+// ---- the Levenshtein similarity on the host boundary (dynaalign.h; lev_kernels.hip) --------------------------------------------------------------
+// The operand of every host call, the sibling of JaccardSets without k.  check_one / check_two: the documented validation of one set / of x
+// then y, before a device is needed.  build(): DA_ERR_NO_DEVICE last, then one pass over the bytes for the class map, the sequences -- two
+// sets as ONE operand [x ; y] of m + n sequences -- and their match masks (k_lev_masks) on the device.  rect(): rows x columns of that operand
+// as uint16 codes ((L - d) << 8 | L) or doubles.  The codes have the NW code's shape with L <= 127: every tail of the short Jaccard calls
+// applies with the same value table and the same rank table.
+struct LevMasks {
+  int64_t m = 0, n = 0;                                  // one set: m == 0, n sequences; two sets: x has m, y has n
+  int64_t x_total = 0, y_total = 0, max_len = 0;
+  int n_classes = 1;
+  uint8_t class_map[256];
+  DeviceInput in;
+  DevBuf masks;
+  static int lengths(const int64_t *off, int64_t cnt) {
+    for (int64_t i = 0; i < cnt; ++i) {
+      const int rc = off[i + 1] - off[i] > 127 ? lev_limits(off[i + 1] - off[i], i + 1) : DA_OK;
+      if (rc != DA_OK) return rc;
+    }
+    return DA_OK;
+  }
+  int check_one(const uint8_t *res, const int64_t *off, int64_t n_, bool out_ok) {
+    if (n_ <= 0) return fail(DA_ERR_EMPTY_INPUT, "%s", da_status_message(DA_ERR_EMPTY_INPUT));
+    if (!res || !out_ok) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int rc;
+    if ((rc = check_offsets(off, n_, &y_total, &max_len)) != DA_OK || (rc = lengths(off, n_)) != DA_OK) return rc;
+    if (n_ > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "Levenshtein: too many sequences");
+    m = 0; n = n_;
+    return DA_OK;
+  }
+  // (the empty shapes are the caller's: they differ between the two-set calls)
+  int check_two(const uint8_t *xr, const int64_t *xo, int64_t m_, const uint8_t *yr, const int64_t *yo, int64_t n_, bool out_ok) {
+    if (!xr || !yr || !out_ok) return fail(DA_ERR_BAD_ARG, "NULL pointer");
+    int64_t x_max, y_max;
+    int rc;
+    if ((rc = check_offsets(xo, m_, &x_total, &x_max)) != DA_OK || (rc = check_offsets(yo, n_, &y_total, &y_max)) != DA_OK) return rc;
+    if ((rc = lengths(xo, m_)) != DA_OK || (rc = lengths(yo, n_)) != DA_OK) return rc;
+    if (m_ + n_ > 0x7ffffff0LL) return fail(DA_ERR_UNSUPPORTED, "Levenshtein: too many sequences");
+    max_len = std::max(x_max, y_max);
+    m = m_; n = n_;
+    return DA_OK;
+  }
+  // the byte values that occur, in ascending order, are the classes 0 .. n_classes - 1 (a call without any byte has the one class 0)
+  void classes(const uint8_t *a, int64_t a_bytes, const uint8_t *b, int64_t b_bytes) {
+    bool seen[256] = {false};
+    for (int64_t p = 0; p < a_bytes; ++p) seen[a[p]] = true;
+    for (int64_t p = 0; p < b_bytes; ++p) seen[b[p]] = true;
+    int c = 0;
+    for (int v = 0; v < 256; ++v) class_map[v] = (uint8_t)(seen[v] ? c++ : 0);
+    n_classes = std::max(c, 1);
+  }
+  int operand() {
+    int rc;
+    const size_t bytes = lev_masks_bytes(m + n, max_len, n_classes);
+    if ((rc = masks.alloc(bytes)) != DA_OK) return rc;
+    return launch_lev_masks(in.res.as<uint8_t>(), in.off.as<int64_t>(), m + n, max_len, class_map, n_classes, masks.p, bytes, nullptr);
+  }
+  int build(const uint8_t *res, const int64_t *off) {
+    int rc;
+    if ((rc = require_device()) != DA_OK) return rc;
+    classes(res, y_total, nullptr, 0);
+    if ((rc = in.upload(res, off, n, y_total, nullptr, 0)) != DA_OK) return rc;
+    return operand();
+  }
+  int build(const uint8_t *xr, const int64_t *xo, const uint8_t *yr, const int64_t *yo) {
+    int rc;
+    if ((rc = require_device()) != DA_OK) return rc;
+    classes(xr, x_total, yr, y_total);
+    std::vector<uint8_t> res((size_t)(x_total + y_total) + 1);
+    std::vector<int64_t> off((size_t)(m + n) + 1);
+    if (x_total) memcpy(res.data(), xr, (size_t)x_total);
+    if (y_total) memcpy(res.data() + x_total, yr, (size_t)y_total);
+    for (int64_t i = 0; i <= m; ++i) off[(size_t)i] = xo[i];
+    for (int64_t j = 1; j <= n; ++j) off[(size_t)(m + j)] = x_total + yo[j];
+    if ((rc = in.upload(res.data(), off.data(), m + n, x_total + y_total, nullptr, 0)) != DA_OK) return rc;
+    return operand();
+  }
+  int rect(int64_t r0, int64_t r1, int64_t c0, int64_t c1, int kind, void *d, int64_t ld, hipStream_t stream) const {
+    return launch_lev_rect(masks.p, m + n, max_len, n_classes, r0, r1, c0, c1, kind, d, ld, stream);
+  }
+  // the bins the call's uint16 codes fall into: L - d <= L <= max_len (at least 1: the code of two empty strings is 1 << 8 | 1)
+  int nbins() const {
+    const int64_t len = std::max<int64_t>(1, max_len);
+    return (int)((len << 8) | len) + 1;
+  }
+};
+
+int da_similarity_lev(const uint8_t *residues, const int64_t *offsets, int64_t n, double *out) {
+  LevMasks lv;
+  int rc;
+  if ((rc = lv.check_one(residues, offsets, n, out != nullptr)) != DA_OK || (rc = lv.build(residues, offsets)) != DA_OK) return rc;
+  Trace tr("similarityLev host path");
+  const std::vector<double> table = nw_code_values(65536, 0.0);
+  if (rows_per_block(n, sizeof(uint16_t)) >= n)
+    return codes_to_host(n, out, table, tr, [&](void *d) { return lv.rect(0, n, 0, n, DA_OUT_COMPACT, d, n, nullptr); });
+  return rows_to_host(n, 0, n, sizeof(uint16_t), out, [&](int64_t b0, int64_t b1, void *d) { return lv.rect(b0, b1, 0, n, DA_OUT_COMPACT, d, n, nullptr); },
+                      nullptr, nullptr, table.data());
+}
+
+int da_similarity_lev_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                            int64_t n, double *out, int column_major) {
+  if (m <= 0 || n <= 0) return DA_OK;                    // an m x 0 or 0 x n matrix: nothing to write
+  LevMasks lv;
+  int rc;
+  if ((rc = lv.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, out != nullptr)) != DA_OK ||
+      (rc = lv.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+  const int64_t rows = column_major ? n : m, cols = column_major ? m : n;
+  const std::vector<double> table = nw_code_values(65536, 0.0);
+  // the distance is symmetric: rows of y against columns of x are the transpose, R's column-major NumericMatrix(m, n)
+  return rows_to_host(cols, 0, rows, sizeof(uint16_t), out, [&](int64_t b0, int64_t b1, void *d) {
+    return column_major ? lv.rect(m + b0, m + b1, 0, m, DA_OUT_COMPACT, d, cols, nullptr) : lv.rect(b0, b1, m, m + n, DA_OUT_COMPACT, d, cols, nullptr);
+  }, nullptr, nullptr, table.data());
+}
+
+int da_similarity_lev_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues, const int64_t *y_offsets,
+                                 int64_t n, int top, int32_t *idx_out, double *val_out) {
+  if (m <= 0) return DA_OK;                              // no rows: nothing to write
+  if (n <= 0) return fail(DA_ERR_BAD_ARG, "top must be in 1 .. n (got top = %d, n = 0)", top);
+  LevMasks lv;
+  int rc, bits = 16;
+  if ((rc = lv.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, idx_out != nullptr)) != DA_OK || (rc = topk_check(top, n)) != DA_OK ||
+      (rc = lv.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+  DevBuf drank, didx, dkey;
+  if ((rc = jaccard_ranks(drank, &bits)) != DA_OK || (rc = didx.alloc((size_t)m * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)m * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  rc = topk_blocks(m, n, drank.as<uint16_t>(), bits, top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return lv.rect(b0, b1, m, m + n, DA_OUT_COMPACT, d, ld, nullptr); });
+  if (rc != DA_OK) return rc;
+  return topk_to_host(didx, dkey, m, top, nw_code_values(65536, 0.0), idx_out, val_out);
+}
+
+int da_similarity_lev_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int top, int32_t *idx_out, double *val_out) {
+  LevMasks lv;
+  int rc, bits = 16;
+  if ((rc = lv.check_one(residues, offsets, n, idx_out != nullptr)) != DA_OK || (rc = knn_check(top, n)) != DA_OK ||
+      (rc = lv.build(residues, offsets)) != DA_OK) return rc;
+  DevBuf drank, didx, dkey;
+  if ((rc = jaccard_ranks(drank, &bits)) != DA_OK || (rc = didx.alloc((size_t)n * (size_t)top * sizeof(int32_t))) != DA_OK ||
+      (rc = dkey.alloc((size_t)n * (size_t)top * sizeof(uint16_t))) != DA_OK) return rc;
+  rc = topk_blocks(n, n, drank.as<uint16_t>(), bits, top, didx.as<int32_t>(), top, dkey.as<uint16_t>(), top, nullptr,
+                   [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return lv.rect(b0, b1, 0, n, DA_OUT_COMPACT, d, ld, nullptr); }, true);
+  if (rc != DA_OK) return rc;
+  return topk_to_host(didx, dkey, n, top, nw_code_values(65536, 0.0), idx_out, val_out);
+}
+
+// the similarity + clusterbreak's threshold step as an edge list: the histogram / quantile / extraction path of the NW codes, as
+// jaccard_edges_core
+static int lev_edges_core(const uint8_t *residues, const int64_t *offsets, int64_t n, double thresh_p, bool want_edges, EdgeSet &es, int64_t *n_edges_out) {
+  LevMasks lv;
+  int rc;
+  if ((rc = lv.check_one(residues, offsets, n, true)) != DA_OK) return rc;
+  if (n < 2) return fail(DA_ERR_BAD_ARG, "the threshold is a quantile of the strict upper triangle: need >= 2 sequences");
+  if (!(thresh_p >= 0.0 && thresh_p <= 1.0)) return fail(DA_ERR_BAD_ARG, "thresh_p must be in [0, 1]");
+  if ((rc = lv.build(residues, offsets)) != DA_OK) return rc;
+  DevBuf cnt, hist;
+  const int nbins = lv.nbins();
+  if ((rc = cnt.alloc((size_t)n * (size_t)n * 2)) != DA_OK || (rc = hist.alloc((size_t)nbins * 8)) != DA_OK) return rc;   // uint16 codes stay on the device
+  DA_HIP_TRY(hipMemset(hist.p, 0, (size_t)nbins * 8));
+  if ((rc = lv.rect(0, n, 0, n, DA_OUT_COMPACT, cnt.p, n, nullptr)) != DA_OK) return rc;
+  if ((rc = launch_upper_histogram(cnt.as<uint16_t>(), n, n, nbins, hist.as<unsigned long long>(), nullptr)) != DA_OK) return rc;
+  return edges_from_counts(cnt.as<uint16_t>(), n, nbins, hist.as<unsigned long long>(), nw_code_values(nbins, 0.0), thresh_p, want_edges, es, n_edges_out);
+}
+
+int da_similarity_lev_edges(const uint8_t *residues, const int64_t *offsets, int64_t n, double thresh_p, double *threshold_out, int64_t *n_edges_out,
+                            int64_t capacity, int32_t *ei, int32_t *ej, double *ew) {
+  return edges_run_deliver(threshold_out, n_edges_out, capacity, ei, ej, ew, [&](bool want_edges, EdgeSet &es, int64_t *cnt) {
+    return lev_edges_core(residues, offsets, n, thresh_p, want_edges, es, cnt);
+  });
+}
+
+int da_similarity_lev_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, double thresh_p, da_edges **handle_out,
+                                  double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool want_edges, EdgeSet &es, int64_t *cnt) {
+    return lev_edges_core(residues, offsets, n, thresh_p, want_edges, es, cnt);
+  });
+}
+
+// the range query: every (i, j) of x against y at or above a threshold, as da_similarity_nw_cross_edges_begin
+int da_similarity_lev_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m, const uint8_t *y_residues,
+                                        const int64_t *y_offsets, int64_t n, double thresh, int thresh_is_quantile, da_edges **handle_out,
+                                        double *threshold_out, int64_t *n_edges_out) {
+  return edges_run_handle(handle_out, threshold_out, n_edges_out, [&](bool, EdgeSet &es, int64_t *n_edges) -> int {
+    int rc;
+    if (m <= 0 || n <= 0) {                                // an empty rectangle: no edges; it has no quantile
+      if ((rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK) return rc;
+      if (thresh_is_quantile) return fail(DA_ERR_BAD_ARG, "quantile of an empty set");
+      es.threshold = thresh;
+      *n_edges = 0;
+      return DA_OK;
+    }
+    LevMasks lv;
+    if ((rc = lv.check_two(x_residues, x_offsets, m, y_residues, y_offsets, n, true)) != DA_OK ||
+        (rc = thresh_arg_check(thresh, thresh_is_quantile)) != DA_OK || (rc = lv.build(x_residues, x_offsets, y_residues, y_offsets)) != DA_OK) return rc;
+    const std::vector<double> values = nw_code_values(lv.nbins(), 0.0);
+    CodeKeys keys(m, n, values, [&](int64_t b0, int64_t b1, void *d, int64_t ld) { return lv.rect(b0, b1, m, m + n, DA_OUT_COMPACT, d, ld, nullptr); }, nullptr);
+    return edges_to_host(keys, m, thresh, thresh_is_quantile != 0, es, n_edges);
+  });
 }
 
 

@@ -464,6 +464,14 @@ int launch_jaccard_sets_long(const uint8_t *d_res, const int64_t *d_off, int64_t
                              uint16_t *d_counts, hipStream_t stream);
 int launch_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin, int64_t row_end,
                              int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, hipStream_t stream);
+// lev_kernels.hip: the Levenshtein similarity in its bit-parallel form (da_dev_lev_masks / da_dev_lev_rect), sequences of at most 127 bytes.
+// class_map (host, 256 entries) maps a byte to its class id below n_classes; the operand is one buffer of lev_masks_bytes(n, max_len, n_classes)
+// bytes holding match masks, texts and lengths.  The rectangle is rows x columns of ONE operand, DA_OUT_COMPACT ((L - d) << 8 | L) or DA_OUT_F64.
+size_t lev_masks_bytes(int64_t n, int64_t max_len, int n_classes);
+int launch_lev_masks(const uint8_t *d_res, const int64_t *d_off, int64_t n, int64_t max_len, const uint8_t *class_map, int n_classes, void *d_masks,
+                     size_t masks_bytes, hipStream_t stream);
+int launch_lev_rect(const void *d_masks, int64_t n, int64_t max_len, int n_classes, int64_t row_begin, int64_t row_end, int64_t col_begin, int64_t col_end,
+                    int kind, void *d_out, int64_t ld, hipStream_t stream);
 // MinHash LSH banding (da_dev_lsh_*).  Elements are (sequence, band) pairs, rows * bands <= LSH_MAX_ELEMENTS of them; an INCIDENCE is a pair
 // of sequences that share a bucket in one band.  A front end numbers the incidences as the slots of an exclusive sum, describes them in
 // an LshSlots and reads back their number and its statistics; the caller checks the cap and sizes the per-incidence buffers; the back end

@@ -342,6 +342,54 @@ def jaccard_rect_long(sets, row_begin=0, row_end=None, col_begin=0, col_end=None
     return _jaccard_rect(_capi.load().da_dev_jaccard_rect_long, torch.int32, sets, row_begin, row_end, col_begin, col_end, kind, out)
 
 
+class LevMasks:
+    """Operand of lev_rect: ``masks``, one uint8 tensor of da_dev_lev_masks_bytes(n, max_len, n_classes) bytes holding per sequence the match
+    masks of its classes, the class ids of its bytes and its length; ``class_map`` (256 uint8 on the host) numbers the bytes that occur as
+    classes 0 .. n_classes - 1."""
+
+    def __init__(self, masks, n, max_len, class_map, n_classes):
+        self.masks, self.n, self.max_len, self.class_map, self.n_classes = masks, int(n), int(max_len), class_map, int(n_classes)
+
+
+def lev_masks_bytes(n, max_len, n_classes):
+    return int(_capi.load().da_dev_lev_masks_bytes(int(n), int(max_len), int(n_classes)))
+
+
+def lev_masks(ds, class_map=None):
+    """The match masks of the sequences in ``ds`` (da_dev_lev_masks): every sequence at most 127 bytes.  ``class_map``: 256 class ids, one per
+    byte value; None numbers the byte values that occur in ``ds`` in ascending order, read from a host copy of the residues."""
+    _require_cuda(ds.residues, "residues")
+    if class_map is None:
+        seen = np.zeros(256, bool)
+        seen[np.unique(ds.residues[:ds.total].cpu().numpy())] = True
+        class_map = np.where(seen, np.cumsum(seen) - 1, 0).astype(np.uint8)
+    class_map = np.ascontiguousarray(class_map, np.uint8)
+    if class_map.shape != (256,):
+        raise ValueError("class_map must hold 256 class ids")
+    n_classes = int(class_map.max()) + 1
+    masks = torch.empty(max(lev_masks_bytes(ds.n, ds.max_len, n_classes), 8), dtype=torch.uint8, device=ds.residues.device)
+    _call(_capi.load().da_dev_lev_masks, ds.residues.data_ptr(), ds.offsets.data_ptr(), ds.n, ds.max_len, class_map.ctypes.data, n_classes,
+          masks.data_ptr(), masks.numel(), _stream())
+    return LevMasks(masks, ds.n, ds.max_len, class_map, n_classes)
+
+
+def lev_rect(masks, row_begin=0, row_end=None, col_begin=0, col_end=None, kind=DA_OUT_F64, out=None):
+    """The Levenshtein similarity on a rectangle (da_dev_lev_rect): rows [row_begin, row_end) x columns [col_begin, col_end) of the operand of
+    lev_masks, as float64 or as uint16 codes ``(L - d) << 8 | L`` in an int16 tensor.  On the masks of x + y, rows of x against columns of y
+    give the two-set matrix; a rectangle whose rows and columns are the same range is computed by the symmetric form.  ``out`` may be any
+    view with unit column stride (its row stride is the leading dimension)."""
+    _require_cuda(masks.masks, "match masks")
+    n = masks.n
+    row_end = n if row_end is None else row_end
+    col_end = n if col_end is None else col_end
+    if out is None:
+        out = torch.empty((max(row_end - row_begin, 1), max(col_end - col_begin, 1)), dtype=torch.float64 if kind == DA_OUT_F64 else torch.int16,
+                          device=masks.masks.device)
+    _call(_capi.load().da_dev_lev_rect, masks.masks.data_ptr(), n, masks.max_len, masks.n_classes, int(row_begin), int(row_end), int(col_begin),
+          int(col_end), kind, out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
 def nw_align_workspace_bytes(pairs):
     return int(_capi.load().da_nw_align_workspace_bytes(int(pairs)))
 

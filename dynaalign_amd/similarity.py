@@ -29,6 +29,14 @@ and the EXACT Jaccard index of the k-shingle sets that similarityMH estimates (s
     similarityJaccard_long(...), _cross_long, _cross_topk_long, _knn_long, _knn_edges_long, _edges_long, _stats_long: the same for up to 1024
     shingles, and similarityJaccard_cross_edges_long(x, y, k=4, thresh_p=0.8, threshold=None), the two-set threshold form
 
+and the Levenshtein similarity (L - d) / L of plain edit distance d, L the longer length (sequences of at most 127 bytes, any byte values)
+
+    similarityLev(sequences)                             similarityLev_cross(x, y)
+    similarityLev_cross_topk(x, y, top=10)               similarityLev_knn(sequences, top=10)
+    similarityLev_knn_edges(sequences, top=10, mode="union")               similarityLev_edges(sequences, thresh_p=0.8)
+    similarityLev_cross_edges(x, y, thresh_p=0.8, threshold=None)          the range query: "everything within t edits"
+    lev_dense(sequences, y=None), lev_counts(sequences, y=None)            the definition in Python
+
 and the threshold forms of those (the entries that pass a threshold as a sorted edge list, never the m x n matrix)
 
     similarityMH_cross_edges(x, y, k=4, n_hash=50, thresh_p=0.8, threshold=None)
@@ -637,6 +645,123 @@ def similarityJaccard_stats_long(sequences, k=4):
     s = _capi.DaSimilarityStats()
     _capi.check(lib.da_similarity_jaccard_stats_long(res.ctypes.data, off.ctypes.data, n, _as_int(k, "k"), ctypes.addressof(s)))
     return _stats_result(s)
+
+
+# ---- the Levenshtein similarity: plain edit distance ------------------------------------------------------------------------------------------
+
+def lev_counts(sequences, y=None):
+    """``(L - d, L)``, two int64 matrices, for every sequence a of ``sequences`` against every b of ``y`` (``y=None``: of ``sequences``):
+    d the Levenshtein distance of the two byte strings -- insert, delete and substitute cost 1 each -- and L the longer of the two lengths.
+    The plain O(len(a) len(b)) dynamic programme, for small inputs: the integers behind lev_dense and behind the device's uint16 code
+    ``(L - d) << 8 | L`` (two empty strings are coded 0x0101)."""
+    xs = _byte_strings(sequences)
+    ys = xs if y is None else _byte_strings(y)
+    num = np.zeros((len(xs), len(ys)), np.int64)
+    den = np.zeros((len(xs), len(ys)), np.int64)
+    for i, a in enumerate(xs):
+        ta = np.frombuffer(a, np.uint8)
+        for j, b in enumerate(ys):
+            prev = np.arange(len(a) + 1, dtype=np.int64)             # d(a[:p], "") = p
+            for q in range(len(b)):
+                # substitute or match, delete from b; then the inserts along the column as a running minimum
+                cur = np.empty_like(prev)
+                cur[0] = q + 1
+                np.minimum(prev[:-1] + (ta != b[q]), prev[1:] + 1, out=cur[1:])
+                cur = np.minimum.accumulate(cur - np.arange(len(cur))) + np.arange(len(cur))
+                prev = cur
+            longer = max(len(a), len(b))
+            num[i, j] = longer - int(prev[-1])
+            den[i, j] = longer
+    return num, den
+
+
+def lev_dense(sequences, y=None):
+    """The Levenshtein similarity, the definition in Python: the float64 matrix ``(L - d) / L`` of lev_counts -- one IEEE divide of the two
+    integers -- 1.0 for two empty strings, 0.0 where exactly one is empty.  The counterpart of similarityLev / similarityLev_cross, as
+    jaccard_dense is of similarityJaccard; no limit on the lengths, small inputs only."""
+    num, den = lev_counts(sequences, y)
+    out = np.ones(num.shape, np.float64)
+    np.divide(num.astype(np.float64), den.astype(np.float64), out=out, where=den > 0)
+    return out
+
+
+def similarityLev(sequences):
+    """The Levenshtein similarity of all pairs: ``(L - d) / L`` with d the unit-cost edit distance of the two byte strings and L the longer
+    length; ``== lev_dense(sequences)`` bit for bit, diagonal 1.0 by the definition, symmetric.  Any byte values (``str`` goes through
+    latin-1), every sequence at most 127 bytes; the empty string is legal (two of them give 1.0, one gives 0.0).  With all strings of
+    length L, the pairs within t edits are those at or above ``(L - t) / L``."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    out = np.empty((max(n, 1), max(n, 1)), np.float64)
+    _capi.check(lib.da_similarity_lev(res.ctypes.data, off.ctypes.data, n, out.ctypes.data))
+    return SimilarityMatrix(out[:n, :n])
+
+
+def similarityLev_cross(x, y):
+    """The Levenshtein similarity of every sequence of ``x`` against every sequence of ``y``: the (m, n) matrix, bit for bit the block
+    [0:m, m:m+n] of ``similarityLev(x + y)``.  An empty ``x`` or ``y`` gives a (0, n) / (m, 0) matrix."""
+    lib = _capi.load()
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
+    out = np.empty((max(m, 1), max(n, 1)), np.float64)
+    _capi.check(lib.da_similarity_lev_cross(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, out.ctypes.data, 0))
+    return SimilarityMatrix(out[:m, :n])
+
+
+def similarityLev_cross_topk(x, y, top=10):
+    """For every sequence of ``x`` its ``top`` most similar sequences of ``y`` under similarityLev_cross, without the (m, n) matrix:
+    ``(idx, val)`` as similarityJaccard_cross_topk, ``idx == np.argsort(-R, axis=1, kind="stable")[:, :top]``.  Equal values tie whatever
+    their (L - d, L): 10/20 and 5/10 are listed by position.  An empty ``x`` gives (0, top) arrays; ``top`` is clamped to ``len(y)``; an
+    empty ``y`` is an error."""
+    lib = _capi.load()
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
+    t, idx, val = _topk_arrays(m, top, n)
+    _capi.check(lib.da_similarity_lev_cross_topk(xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, t, idx.ctypes.data,
+                                                 val.ctypes.data))
+    return idx[:m, :max(t, 0)], val[:m, :max(t, 0)]
+
+
+def similarityLev_knn(sequences, top=10):
+    """For every sequence its ``top`` most similar OTHER sequences under similarityLev, without the (n, n) matrix: ``(idx, val) ==
+    knn_dense(similarityLev(sequences), top)``.  ``top`` is clamped to ``len(sequences) - 1`` and may be at most 1024.  Byte-identical
+    strings fill each other's lists at 1.0."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    t, idx, val = _topk_arrays(n, top, n - 1)
+    _capi.check(lib.da_similarity_lev_knn(res.ctypes.data, off.ctypes.data, n, t, idx.ctypes.data, val.ctypes.data))
+    return idx[:n], val[:n]
+
+
+def similarityLev_knn_edges(sequences, top=10, mode="union"):
+    """The kNN graph of similarityLev_knn as ``(threshold, i, j, w)`` for ``clusterbreak(edges_fn=)``: knn_graph of the lists with the 1.0
+    diagonal the definition gives.  The ``threshold`` slot holds the smallest off-diagonal weight kept, NaN when none."""
+    idx, val = similarityLev_knn(sequences, top)
+    return _knn_edges_result(idx, val, 1.0, mode)
+
+
+def similarityLev_edges(sequences, thresh_p=0.8):
+    """similarityLev followed by clusterbreak's threshold step (reference R/clusterbreak.R:217-221), fused on the device like
+    similarityJaccard_edges: ``(threshold, i, j, weight)`` for the entries with i <= j (0-based, sorted, diagonal included) whose value is
+    >= the type-7 ``thresh_p`` quantile of the strict upper triangle and > 0.  An order-aware graph at bit-vector cost for
+    ``clusterbreak(pep, edges_fn=lambda s: similarityLev_edges(s))``."""
+    lib = _capi.load()
+    res, off = pack_sequences(sequences)
+    n = len(off) - 1
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_lev_edges_begin(res.ctypes.data, off.ctypes.data, n, float(thresh_p), h, thr, cnt))
+
+
+def similarityLev_cross_edges(x, y, thresh_p=0.8, *, threshold=None):
+    """The range query: the entries of R = similarityLev_cross(x, y) that pass a threshold, without the (m, n) matrix: ``(threshold, i, j,
+    weight)`` as similarityNW_cross_edges -- every (i, j) with ``R[i, j] >= threshold and R[i, j] > 0``, sorted by (i, j), ``weight`` bit
+    for bit ``R[i, j]``; ``threshold=None`` takes R's type-7 ``thresh_p`` quantile over all m * n entries.  With all strings of length L,
+    ``threshold=(L - t) / L`` lists every pair within t edits.  An empty ``x`` or ``y`` gives no edges in the absolute form and is an
+    error in the quantile form."""
+    lib = _capi.load()
+    xr, xo, m, yr, yo, n = _pack_two(x, y)
+    thresh, is_q = _thresh_args(thresh_p, threshold)
+    return _edges_one_pass(lambda h, thr, cnt: lib.da_similarity_lev_cross_edges_begin(
+        xr.ctypes.data, xo.ctypes.data, m, yr.ctypes.data, yo.ctypes.data, n, thresh, is_q, h, thr, cnt))
 
 
 def nw_code_ranks(max_len=127):

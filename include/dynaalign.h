@@ -66,6 +66,8 @@ extern "C" {
  *  da_dev_nw_rescore_pairs, da_dev_nw_rescore_workspace_bytes, da_nw_lsh_last_route -- likewise)
  * (the NW-ranked LSH list entry points -- da_similarity_nw_lsh_knn, da_similarity_nw_lsh_cross_topk, da_dev_lsh_nw_knn,
  *  da_dev_lsh_cross_nw_topk, da_dev_nw_knn_select, da_dev_nw_rank_keys -- likewise)
+ * (the Levenshtein entry points -- da_similarity_lev[_cross[_topk | _edges_begin] | _knn | _edges[_begin]], da_dev_lev_masks[_bytes],
+ *  da_dev_lev_rect -- likewise)
  * 2: the folded shard layout changed (da_shard_ld = ceil8(n) + world * 128, back-aligned rows start at column world * 128) and the
  *    duplicate-route / multi-device entry points were added; every round-1 entry point keeps its signature */
 #define DA_ABI_VERSION 2
@@ -1063,6 +1065,65 @@ int da_dev_jaccard_sets_long(const uint8_t *d_residues, const int64_t *d_offsets
                              int64_t ld_keys, uint16_t *d_counts, void *stream);
 int da_dev_jaccard_rect_long(const void *d_keys, const uint16_t *d_counts, int64_t n, int64_t ld_keys, int k, int64_t row_begin,
                              int64_t row_end, int64_t col_begin, int64_t col_end, int kind, void *d_out, int64_t ld, void *stream);
+
+/* ---- the Levenshtein similarity: plain edit distance, on a bit-parallel kernel (lev_kernels.hip) ----
+ * Sequences are byte strings, any byte value, no alphabet check; the empty string is legal.  d(a, b) is the Levenshtein distance -- insert,
+ * delete and substitute cost 1 each -- L = max(len(a), len(b)), and lev(a, b) = (double)(L - d) / (double)L, one IEEE divide of the two
+ * integers; 1.0 for two empty strings, 0.0 when exactly one is empty (d = L).  Nothing is forced on the diagonal: lev(a, a) is 1.0 by the
+ * definition.  The matrix is symmetric; no NaN occurs.  With all strings of length L, "within t edits" is the threshold (L - t) / L.
+ * The distance is computed in its bit-vector form (Myers 1999, Hyyro's global variant): a column of the DP is one uint32 (the call's longest
+ * sequence <= 32 bytes), one uint64 (<= 64) or two uint64 (<= 127), and a pair costs len(b) steps of some seventeen integer operations.
+ * uint16 code (DA_OUT_COMPACT): (L - d) << 8 | L, 0x0101 for two empty strings -- the shape of the NW code, valued by the same divide (a
+ * code's low byte is never 0).  Wherever an order is needed (top-k, nearest neighbours, the quantile) equal VALUES tie whatever their codes
+ * (10/20 and 5/10): the selection runs on da_nw_code_ranks(127, ...), whose domain holds every (L - d, L) the limit allows.
+ * Limit (DA_ERR_UNSUPPORTED, the text names the limit and the sequence's 1-based index): every sequence has at most 127 bytes.
+ * Validation, before any device is needed: that of the da_similarity_jaccard* call of the same form without k.  One set: n <= 0 ->
+ * DA_ERR_EMPTY_INPUT, NULL pointers, the offsets, the sequence lengths; then what the call adds -- _knn: n < 2, top < 1 or top > n - 1 ->
+ * DA_ERR_BAD_ARG, top > 1024 -> DA_ERR_UNSUPPORTED; _edges: n < 2, thresh_p outside [0, 1] -> DA_ERR_BAD_ARG.  Two sets: m <= 0 or n <= 0 returns
+ * DA_OK and writes nothing (_cross_topk: m <= 0 returns DA_OK, n <= 0 with m > 0 is DA_ERR_BAD_ARG; _cross_edges_begin: no edges in the absolute
+ * form, DA_ERR_BAD_ARG "quantile of an empty set" in the quantile form, after the check of thresh); NULL pointers, the offsets of x then y, the
+ * lengths of x then y; then top (the texts of da_similarity_nw_cross_topk) or thresh (those of da_similarity_nw_cross_edges_begin).
+ * DA_ERR_NO_DEVICE comes last.
+ *   da_similarity_lev              out: n * n doubles (the device writes uint16 codes, the host widens them).
+ *   da_similarity_lev_cross        out: m x n, bit for bit the block [0:m, m:m+n] of da_similarity_lev on c(x, y); column_major as
+ *                                  da_similarity_mh_cross.  Both sets form ONE operand [x ; y] on the device.
+ *   da_similarity_lev_cross_topk   idx_out [m][top] int32, val_out [m][top] float64 or NULL: numpy's argsort(-R, axis = 1, kind = "stable")[:, :top].
+ *   da_similarity_lev_knn          idx_out / val_out [n][top]: the `top` columns j != i of every row, as da_similarity_jaccard_knn.
+ *   da_similarity_lev_edges[_begin]  threshold = R's type-7 quantile of the strict upper triangle at thresh_p; the edges i <= j, diagonal
+ *                                  included, with lev >= threshold and lev > 0, sorted by (i, j); conventions of da_similarity_nw_edges[_begin].
+ *   da_similarity_lev_cross_edges_begin  the range query: every (i, j) with R[i, j] >= threshold and R[i, j] > 0, sorted by (i, j); thresh is
+ *                                  an absolute threshold, or with thresh_is_quantile != 0 the level of R's type-7 quantile over all m * n entries;
+ *                                  conventions of da_similarity_nw_cross_edges_begin (da_edges_fetch / da_edges_free).
+ * Single device, the direct route only; top-k / kNN / the range query work in row blocks of DYNAALIGN_BLOCK_BYTES.
+ * The device layer.  The bytes that occur in a call are numbered as classes 0 .. n_classes - 1 (1 <= n_classes <= 256) by class_map, a HOST array of
+ * 256 class ids, each below n_classes; bytes that do not occur may map to any class.  da_dev_lev_masks writes the operand of da_dev_lev_rect into
+ * d_masks (8-byte aligned, masks_bytes >= da_dev_lev_masks_bytes(n, max_len, n_classes); 0 for arguments outside the limits): per sequence and class
+ * the match mask -- bit p of the mask of class c is set iff byte p has class c -- the class ids of its bytes, and its length.  max_len: the longest
+ * sequence (<= 127); it chooses the word shape, so both calls must be given the same n, max_len and n_classes.  n <= 0 -> DA_ERR_EMPTY_INPUT, NULL
+ * pointers -> DA_ERR_BAD_ARG, max_len > 127 -> DA_ERR_UNSUPPORTED, n_classes or a class id out of range, d_masks misaligned or too small -> DA_ERR_BAD_ARG.
+ * da_dev_lev_rect: rows [row_begin, row_end) x columns [col_begin, col_end) of the n sequences, element (i, j) = lev(sequence i, sequence j), as
+ * DA_OUT_COMPACT codes or DA_OUT_F64 doubles at d_out[(i - row_begin) * ld + (j - col_begin)]; any ld >= columns and any naturally aligned d_out
+ * (16-byte stores where the address allows, single elements otherwise); every element written once, nothing else touched; an empty rectangle is
+ * DA_OK.  A rectangle whose rows and columns are the same range is computed by the symmetric form.  Two sets are compared through the operand of
+ * their concatenation.  Both calls are asynchronous on `stream`. */
+int da_similarity_lev(const uint8_t *residues, const int64_t *offsets, int64_t n, double *out);
+int da_similarity_lev_cross(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                            const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, double *out, int column_major);
+int da_similarity_lev_cross_topk(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                 const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, int top, int32_t *idx_out, double *val_out);
+int da_similarity_lev_knn(const uint8_t *residues, const int64_t *offsets, int64_t n, int top, int32_t *idx_out, double *val_out);
+int da_similarity_lev_edges(const uint8_t *residues, const int64_t *offsets, int64_t n, double thresh_p, double *threshold_out,
+                            int64_t *n_edges_out, int64_t capacity, int32_t *ei, int32_t *ej, double *ew);
+int da_similarity_lev_edges_begin(const uint8_t *residues, const int64_t *offsets, int64_t n, double thresh_p, da_edges **handle_out,
+                                  double *threshold_out, int64_t *n_edges_out);
+int da_similarity_lev_cross_edges_begin(const uint8_t *x_residues, const int64_t *x_offsets, int64_t m,
+                                        const uint8_t *y_residues, const int64_t *y_offsets, int64_t n, double thresh, int thresh_is_quantile,
+                                        da_edges **handle_out, double *threshold_out, int64_t *n_edges_out);
+size_t da_dev_lev_masks_bytes(int64_t n, int64_t max_len, int n_classes);
+int da_dev_lev_masks(const uint8_t *d_residues, const int64_t *d_offsets, int64_t n, int64_t max_len, const uint8_t *class_map, int n_classes,
+                     void *d_masks, size_t masks_bytes, void *stream);
+int da_dev_lev_rect(const void *d_masks, int64_t n, int64_t max_len, int n_classes, int64_t row_begin, int64_t row_end, int64_t col_begin,
+                    int64_t col_end, int kind, void *d_out, int64_t ld, void *stream);
 
 /* The device piece.  The block: `rows` rows of ld >= n keys, rows [row_begin, row_begin + rows) x columns [col_begin, col_begin + n) of a
  * square problem (the origin convention of da_dev_rank_histogram).  d_records[r], for the elements of row r whose global column is
